@@ -19,8 +19,8 @@ Before the W warmup steps the same step runs `--preroll` more times untimed (def
 line): from an idle device the clock governor needs 30-50 ms of launches to reach the state it then holds for seconds
 (profiles/r03_clock_ramp.txt), and W + K = 25 launches would otherwise be timed inside that ramp.  The timed region is K steps.
 
-`from_idle` in the line is the same K-step measurement taken FIRST, before any pre-roll (W warmup launches from an idle device,
-then K timed steps): both regimes are in the record.
+Under `--full`, `from_idle` in the line is the same K-step measurement taken FIRST, before any pre-roll (W warmup launches from
+an idle device, then K timed steps): both regimes are in the record.
 
 `python bench.py --gpus N` WITHOUT a torch.distributed launcher (no WORLD_SIZE in the environment), or with
 `--single-process`, drives all N GPUs from ONE process through the library's sharded bank (syldet_create_sharded: a sub-bank and a
@@ -29,11 +29,24 @@ library's own RCCL group) -- the shape of the reference, which is one process th
 (Processor.swift:57-59,128-141) -- and prints the same line with `rccl_ranks` = N and `launcher` = "single-process".
 
 Rank 0 prints one JSON line.  `roofline` is computed from HIP-event timings of the dominant kernel taken inside the timed
-region on the launch stream.  After the timed region the last step's results are spot-checked against the CPU oracle
-(tests/spotcheck.py: head, tail and segment seams of the first, a middle and the last channel) -> `verified`.
-`cpu_baseline` is the oracle's fp32 port of the reference's call sequence in its streaming, frame-at-a-time form, built
--O3 -march=native on this host, single-threaded like the reference (plus an all-core figure beside it), on a bounded sample
-of the same workload (rank 0, N = 1 only).
+region on the launch stream.
+
+A plain run sets up, pre-rolls, warms up, times the K steps and prints the line: nothing else.  `--full` adds, after the
+timed region, everything else the benchmark measures and checks:
+- `from_idle` (the same K steps timed first, before the pre-roll) and `roofline.binding` (the step looped for a second while the
+  package's power and clock are read);
+- the oracle spot-check of the last step's results (tests/spotcheck.py: head, tail and segment seams of the first, a middle and
+  the last channel), then once more on planted syllables -> `verified`, `verify`, `verify_planted`;
+- `host_buffers` and `cpu_baseline`: the oracle's fp32 port of the reference's call sequence in its streaming,
+  frame-at-a-time form, built -O3 -march=native on this host, single-threaded like the reference (plus an all-core figure
+  beside it), on a bounded sample of the same workload (rank 0, N = 1 only; `--no-cpu-baseline` leaves them out);
+- `also`: the other single-GPU BASELINE workloads, clicks over quiet audio, hop 128, the live callback form and configs[3]'s
+  shard shape (N = 1 headline only; `--no-also` leaves them out).
+
+`--dump-outputs DIR` writes, after the timed region, what the last timed step handed its caller (rank 0's outputs and
+detection flags) as DIR/outputs.npy and DIR/flags.npy in float32: every channel when they fit in 64 MB together, else the same
+seeded sample of channels from both (the line's `dump_outputs` names them).  The input audio is seeded: the same arguments give
+the same inputs on every run.
 """
 import argparse
 import glob
@@ -55,6 +68,32 @@ os.environ.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
 
 HBM_PEAK_GBS = 8000.0          # MI355X_MICROARCH.md: HBM3E 8.0 TB/s spec
 MFMA_BF16_PEAK_TFLOPS = 2500.0 # MI355X_MICROARCH.md: dense bf16 matrix peak (no sparsity)
+DUMP_BUDGET_BYTES = 64 * 1000 * 1000 - 4096    # --dump-outputs: every file together, .npy headers included
+DUMP_SEED = 1234
+
+
+def dump_outputs(out_dir, arrays):
+    """`arrays`: name -> tensor whose first axis is the channel (what the timed path handed its caller in its last step).
+    Writes out_dir/<name>.npy in float32; when every channel does not fit in the budget, the same seeded sample of channels
+    (sorted) is taken from every array.  -> the record of what was written."""
+    import numpy as np
+    import torch
+    os.makedirs(out_dir, exist_ok=True)
+    C = next(iter(arrays.values())).shape[0]
+    per_channel = sum(4 * (t.numel() // max(t.shape[0], 1)) for t in arrays.values())
+    keep = min(C, DUMP_BUDGET_BYTES // max(per_channel, 1))
+    idx = None
+    if keep < C:
+        idx = np.sort(np.random.default_rng(DUMP_SEED).choice(C, keep, replace=False))
+    files = {}
+    for name, t in arrays.items():
+        if idx is not None:
+            t = t.index_select(0, torch.from_numpy(idx).to(t.device))
+        a = t.to(torch.float32).cpu().numpy()
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+        files[name] = list(a.shape)
+    return {"dir": out_dir, "files": files, "dtype": "float32",
+            "channels": "all" if idx is None else {"seed": DUMP_SEED, "of": C, "kept": [int(i) for i in idx]}}
 
 
 def cpu_baseline(cfg, samples_host, budget_s=10.0, threads=1):
@@ -564,7 +603,11 @@ def single_process(args, devices=None, emit=True, tag="BASELINE configs[3]"):
             "gathered_bytes_per_rank_per_step": Cmax * ((E + 7) // 8),
             "fixups": {"work_items_last_step_per_shard": [int(f[0]) for f in fix], "overflow": int(max(f[1] for f in fix)),
                        "note": "16-evaluation items the precision guard sent to the exact fp64 recomputation (0 for ordinary audio)"}}
-    if not args.no_verify:
+    if args.dump_outputs:
+        # the last timed step's results of every shard, in channel order (the steps after it, below, plant syllables)
+        line["dump_outputs"] = dump_outputs(args.dump_outputs, {"outputs": torch.cat([o.cpu() for o in outs]),
+                                                                "flags": torch.cat([f.cpu() for f in fls])})
+    if args.full and not args.no_verify:
         # every device holds every channel's flags: all copies equal device 0's, whose own rows equal its local flags; and the
         # last step's outputs of the first and last shard against the oracle -- then once more on planted syllables (an extra,
         # untimed step), so that the flags compared are not all zero
@@ -637,6 +680,11 @@ def main():
     ap.add_argument("--devices", default=None,
                     help="single-process form: the HIP device of every shard, e.g. 0,1,2,3; a device listed several times (0,0,0,0,0,0,0,0) rehearses the "
                          "whole N > 1 branch on one GPU with the copy exchange")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed region, also everything else the benchmark measures and checks: from_idle, binding, the oracle "
+                         "checks, the CPU baseline and host buffers, the `also` records (a plain run times the headline alone)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write the last timed step's outputs and flags as DIR/<name>.npy (float32, at most 64 MB in all)")
     args = ap.parse_args()
     if args.devices is not None:
         devs = [int(v) for v in args.devices.split(",") if v.strip() != ""]
@@ -775,11 +823,12 @@ def main():
     # step (the same count on every rank: the step may hold a collective) brings the device there first; the W warmup steps
     # and the K timed steps follow unchanged.  --preroll 0 times from cold.
     preroll = args.preroll if args.preroll is not None else (150 if args.engine != 3 and args.workload != "config5" else 10)
-    # ... and BEFORE it, the from-idle regime for the record: W warmup launches on the idle device, then K timed steps
-    # (what `--preroll 0` measures), with the same barriers; the pre-rolled measurement below is the headline.
+    # ... and BEFORE it, under --full, the from-idle regime for the record: W warmup launches on the idle device, then K timed
+    # steps (what `--preroll 0` measures), with the same barriers; the pre-rolled measurement below is the headline.
     from_idle = None
-    left[0] = ((args.warmup + args.steps) if preroll > 0 else 0) + preroll + args.warmup + args.steps    # every step() to come
-    if preroll > 0:
+    idle_leg = preroll > 0 and args.full
+    left[0] = ((args.warmup + args.steps) if idle_leg else 0) + preroll + args.warmup + args.steps    # every step() to come
+    if idle_leg:
         for _ in range(args.warmup):
             step()
         torch.cuda.synchronize()
@@ -868,6 +917,9 @@ def main():
             "fixups": {"work_items_last_step": fixups, "overflow": fix_overflow,
                        "note": "16-evaluation items the precision guard sent to the exact fp64 recomputation (0 for ordinary audio)"},
         }
+        if args.dump_outputs:
+            # this rank's results of the last timed step (the --full legs below launch the step again and plant syllables)
+            line["dump_outputs"] = dump_outputs(args.dump_outputs, {"outputs": outputs, "flags": flags})
         if from_idle is not None:
             idle_elapsed, idle_means = from_idle
             idom = max(idle_means, key=idle_means.get)
@@ -899,13 +951,13 @@ def main():
                                 "frac_is": "flops per step / ms_per_step (spectrogram front + GEMM: end to end); frac_kernel_events: / the GEMM kernel's own HIP-event duration",
                                 "traffic": None, "traffic_source": None,
                                 "algorithmic_flops_per_launch": C * E * f_frame, "algorithmic_flops_per_frame": f_frame, "kernel_ms": means}
-        if world == 1:
+        if world == 1 and args.full:
             # what binds the dominant kernel, beside the contract's yardstick (after the timed region: the probe loops the step for a second)
             try:
                 line["roofline"]["binding"] = binding_of(line["roofline"]["kernel"], lambda: det.run(x, outputs, flags))
             except Exception as e:
                 line["roofline"]["binding"] = {"error": "%s: %s" % (type(e).__name__, str(e)[:200])}
-        if not args.no_verify:
+        if args.full and not args.no_verify:
             # the last timed step's results against the oracle's fp64 anchor where a tiling bug would show (tests/spotcheck.py);
             # the bf16 engine at its own, separately stated bar
             import spotcheck
@@ -916,7 +968,7 @@ def main():
             except AssertionError as e:
                 line["verified"] = False
                 line["verify"] = {"error": str(e)[:400]}
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             # the boundary also takes host buffers (syldet_run): H2D + kernel + D2H pipelined along time, bounded sample.
             # Reported beside the headline, never as `value`.
             try:
@@ -932,7 +984,7 @@ def main():
             ncpu = os.cpu_count() or 1
             if ncpu > 1:                                      # also channels spread over all host cores
                 line["cpu_baseline_all_cores"] = cpu_baseline(cfg, host, threads=ncpu)
-        if not args.no_verify and line.get("verified") and g.engine != 3:
+        if args.full and not args.no_verify and line.get("verified") and g.engine != 3:
             # The benchmark's audio never fires the sample network (its flags are all zero): template syllables are written over the
             # checked stretches AFTER the timed region (and after the CPU legs, which read the same tensor), one more (untimed)
             # launch of this rank's kernel alone -- no exchange -- and the same check again: flags that fire, bit for bit
@@ -947,7 +999,7 @@ def main():
             except AssertionError as e:
                 line["verified"] = False
                 line["verify_planted"] = {"error": str(e)[:400]}
-        if world == 1 and not args.no_also and args.workload == "sample" and args.engine == 0 and args.overlap is None \
+        if args.full and world == 1 and not args.no_also and args.workload == "sample" and args.engine == 0 and args.overlap is None \
                 and args.channels is None and args.log2_samples is None and not exchange:
             # the other single-GPU BASELINE workloads and the guard's worst ordinary case, in the same process and on the same
             # box, after the headline's timed region (which they therefore cannot disturb)
@@ -974,7 +1026,7 @@ def main():
             # shape on every GPU; the headline above is configs[1]'s 64 x 2^24, whose launch differs by a few per cent)
             try:
                 a4 = argparse.Namespace(gpus=1, steps=args.steps, warmup=args.warmup, preroll=100, channels=512, log2_samples=21,
-                                        total_channels=None, overlap=None, engine=0, no_verify=args.no_verify)
+                                        total_channels=None, overlap=None, engine=0, no_verify=args.no_verify, full=True, dump_outputs=None)
                 r4 = single_process(a4, devices=[local_rank], emit=False, tag="BASELINE configs[3]'s shard shape on one GPU")
                 line["also"]["config4_shard"] = {k: r4[k] for k in ("value", "unit", "ms_per_step", "steps", "preroll_steps", "config", "roofline", "exchange", "rccl_error",
                                                                    "rccl_ranks", "launcher_threads", "host_enqueue_ms", "verified", "verify_planted") if k in r4}

@@ -215,7 +215,7 @@ def test_bench_multi_gpu_branch_rehearsed_on_one_device():
     """`bench.py --devices 0,0,0,0,0,0,0,0`: the whole single-process N > 1 branch -- eight shards, launcher threads, the exchange
     (by copies: RCCL refuses a device listed twice), per-device timings, gathered flags on every device, the oracle check of the
     first and last shard on the timed step and on planted syllables, JSON emission with `summary` as its last key."""
-    line = _bench(["--devices", "0,0,0,0,0,0,0,0", "--channels", "4", "--log2-samples", "16", "--steps", "4", "--warmup", "1", "--preroll", "3"])
+    line = _bench(["--full", "--devices", "0,0,0,0,0,0,0,0", "--channels", "4", "--log2-samples", "16", "--steps", "4", "--warmup", "1", "--preroll", "3"])
     assert line["shards"] == 8 and line["n_gpus"] == 1 and line["launcher"] == "single-process" and line["launcher_threads"] == 8
     assert line["exchange"] == "peer_copy" and line["rccl_ranks"] == 0 and line["rccl_error"] is None
     assert line["config"]["channels_per_gpu"] == [4] * 8 and line["gathered_flags_shape"][0] == 32
@@ -229,7 +229,7 @@ def test_bench_multi_gpu_branch_rehearsed_on_one_device():
 def test_bench_single_process_falls_back_when_rccl_does_not_come_up():
     """One shard on device 0 is one RCCL rank; with SYLDET_RCCL_FAIL=1 the communicator step fails, and bench.py makes the bank
     again in the same process with the copy exchange and says so in the line."""
-    args = ["--devices", "0", "--channels", "6", "--log2-samples", "16", "--steps", "3", "--warmup", "1", "--preroll", "2"]
+    args = ["--full", "--devices", "0", "--channels", "6", "--log2-samples", "16", "--steps", "3", "--warmup", "1", "--preroll", "2"]
     ok = _bench(args)
     assert ok["exchange"] == "rccl" and ok["rccl_ranks"] == 1 and ok["rccl_error"] is None and ok["verified"] is True
     fb = _bench(args, env={"SYLDET_RCCL_FAIL": "1"})
@@ -243,7 +243,7 @@ def test_bench_process_per_gpu_branch_rehearsed_with_two_ranks_on_one_device():
     device anyway), barriers, max-over-ranks timing, rank 0's line."""
     import sys
     launcher = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1", "--master-port", "29641"]
-    line = _bench(["--gpus", "2", "--channels", "6", "--log2-samples", "16", "--steps", "3", "--warmup", "1", "--preroll", "2"],
+    line = _bench(["--full", "--gpus", "2", "--channels", "6", "--log2-samples", "16", "--steps", "3", "--warmup", "1", "--preroll", "2"],
                   env={"SYLDET_BENCH_NO_RCCL": "1"}, launcher=launcher)
     assert line["n_gpus"] == 2 and line["exchange"] == "gloo_host" and line["rccl_ranks"] == 0 and "SYLDET_BENCH_NO_RCCL" in line["rccl_error"]
     assert line["config"]["total_channels"] == 12 and line["gathered_flags_shape"][0] == 12 and line["verified"] is True
@@ -257,11 +257,37 @@ def test_bench_one_rank_through_the_rccl_group_of_the_process_per_gpu_launcher()
     smaller cousin; the line says which exchange carried the flags."""
     import sys
     launcher = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1", "--master-addr", "127.0.0.1", "--master-port", "29643"]
-    line = _bench(["--gpus", "1", "--force-gather", "--channels", "8", "--log2-samples", "17", "--steps", "3", "--warmup", "1", "--preroll", "2", "--no-cpu-baseline"],
+    line = _bench(["--full", "--gpus", "1", "--force-gather", "--channels", "8", "--log2-samples", "17", "--steps", "3", "--warmup", "1", "--preroll", "2", "--no-cpu-baseline"],
                   launcher=launcher)
     assert line["n_gpus"] == 1 and line["exchange"] == "rccl" and line["rccl_ranks"] == 1 and line["rccl_error"] is None
     assert line["gathered_flags_shape"][0] == 8 and line["verified"] is True and line["verify_planted"]["detections"] > 0
     assert "side stream" in line["config"]["sharding"] and list(line)[-1] == "summary"
+
+
+def test_bench_plain_run_times_the_steps_and_dumps_the_last_ones_results(tmp_path):
+    """A plain `bench.py --gpus 1` run (no --full): the headline's keys, exactly --steps timed steps, none of the --full legs; with
+    --dump-outputs the last timed step's outputs and flags, equal to the same batch run directly on the same seeded audio."""
+    torch = _torch()
+    C, S = 4, 1 << 16
+    line = _bench(["--gpus", "1", "--channels", str(C), "--log2-samples", "16", "--steps", "3", "--warmup", "1", "--preroll", "2",
+                   "--dump-outputs", str(tmp_path)])
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+        assert k in line, k
+    assert line["steps"] == 3 and line["unit"] == "frames/s" and line["higher_is_better"] is True
+    assert line["value"] == pytest.approx(C * line["config"]["frames_per_channel"] / (line["ms_per_step"] * 1e-3), rel=1e-6)
+    for k in ("verified", "verify", "from_idle", "cpu_baseline", "host_buffers", "also"):
+        assert k not in line, k
+    assert "binding" not in line["roofline"] and line["dump_outputs"]["channels"] == "all"
+    out, fl = np.load(str(tmp_path / "outputs.npy")), np.load(str(tmp_path / "flags.npy"))
+    assert out.dtype == np.float32 and fl.dtype == np.float32
+    cfg = nets.from_npz()
+    x = synth.channels_on_device(C, S, torch.device("cuda", 0), fs=cfg.samplingRate)
+    with SyllableDetector(cfg, channels=C, device=0) as det:
+        want_out, want_fl = det.run(x)
+        torch.cuda.synchronize()
+        want_out, want_fl = want_out.cpu().numpy(), want_fl.cpu().numpy()
+    assert out.shape == want_out.shape and fl.shape == want_fl.shape
+    assert np.array_equal(out, want_out) and np.array_equal(fl, want_fl.astype(np.float32))
 
 
 # More than one GPU on the box: the multi-rank RCCL exchange itself (ncclCommInitAll over distinct devices, the grouped
