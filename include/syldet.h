@@ -172,6 +172,28 @@ int  syldet_make_window(int32_t window, int32_t length, float *out);
  * test wants a specific kernel family.                                                  */
 int syldet_create(const syldet_config_t *cfg, int32_t n_channels, int32_t device, int32_t engine,
                   syldet_t **out);
+/* ---- one bank, a network per channel ----
+ * ProcessorBase.init (Processor.swift:50-86) builds one SyllableDetector per channel from that channel's own configuration
+ * (ViewControllerProcessor.loadNetworkForRow, ViewControllerProcessor.swift:222-276, loads one file per row): channel c of
+ * this handle runs network cfgs[channel_net[c]].  All networks must be COMPATIBLE (syldet_config_compatible): they share the
+ * framing and the shape of the chain -- sampling_rate, fourier_length, window_length, window_overlap, time_range, the derived
+ * band (f0, f1) (freq_lo / freq_hi may differ where they give the same bins), scaling, window, spectrum, rule, the number and
+ * kinds of the input and output functions, the number of layers and each layer's inputs, outputs and transfer, n_thresholds.
+ * Weights, biases, the functions' parameters (x_offsets, gains, y) and thresholds may differ -- networks trained with the same
+ * settings for different birds.  Configurations that are not compatible need a handle each.
+ * Statuses: SYLDET_ERR_UNSUPPORTED for incompatible networks (syldet_last_error names the field), SYLDET_ERR_INVALID_ARGUMENT for
+ * a NULL pointer, n_nets < 1 or a channel_net entry outside [0, n_nets); a network no channel uses is allowed.  These checks run
+ * before any device is touched.  Everything is copied at create time.
+ * Engines: AUTO runs the fold kernel (the symmetric-fold fused kernel) when every network's own AUTO handle would, and otherwise
+ * the generic engine exactly as SYLDET_ENGINE_GENERIC has it; FUSED is the fold kernel or SYLDET_ERR_UNSUPPORTED where it does
+ * not take the shape; GENERIC the generic engine; WIDE_BF16 is SYLDET_ERR_UNSUPPORTED.  n_nets == 1 makes a syldet_create handle.
+ * Every other entry point works on the handle unchanged and answers each channel from its own network.                    */
+int syldet_create_multi(const syldet_config_t *const *cfgs, int32_t n_nets, const int32_t *channel_net, int32_t n_channels,
+                        int32_t device, int32_t engine, syldet_t **out);
+/* 1 = a and b may share one handle, 0 = they may not (*field, if field is not NULL, names the first difference: a static
+ * string such as "time_range" or "layers.outputs"), < 0 = status (NULL argument, or a configuration syldet_create refuses) */
+int syldet_config_compatible(const syldet_config_t *a, const syldet_config_t *b, const char **field);
+
 int syldet_destroy(syldet_t *h);
 int syldet_get_geometry(const syldet_t *h, syldet_geometry_t *out);
 int32_t syldet_channels(const syldet_t *h);

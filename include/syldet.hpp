@@ -82,6 +82,16 @@ public:
         check(syldet_create(config.raw(), channels, device, engine, &h_));
         check(syldet_get_geometry(h_, &geometry_));
     }
+    // a network per channel (ProcessorBase.init, Processor.swift:50-86): channel c runs configs[channelNet[c]]; the
+    // configurations must be compatible (syldet_config_compatible)
+    SyllableDetectorBank(const std::vector<const SyllableDetectorConfig *> &configs, const std::vector<int32_t> &channelNet, int device = 0,
+                         int engine = SYLDET_ENGINE_AUTO)
+    {
+        std::vector<const syldet_config_t *> raw;
+        for (const SyllableDetectorConfig *c : configs) raw.push_back(c ? c->raw() : nullptr);
+        check(syldet_create_multi(raw.data(), (int32_t)raw.size(), channelNet.data(), (int32_t)channelNet.size(), device, engine, &h_));
+        check(syldet_get_geometry(h_, &geometry_));
+    }
     ~SyllableDetectorBank() { syldet_destroy(h_); }
     SyllableDetectorBank(const SyllableDetectorBank &) = delete;
     SyllableDetectorBank &operator=(const SyllableDetectorBank &) = delete;

@@ -99,6 +99,8 @@ SIGNATURES = {
     "syldet_frequency_index_range": (C.c_int, [C.c_int32, C.c_double, C.c_double, C.c_double, c_int32_p, c_int32_p]),
     "syldet_make_window": (C.c_int, [C.c_int32, C.c_int32, c_float_p]),
     "syldet_create": (C.c_int, [Config_p, C.c_int32, C.c_int32, C.c_int32, C.POINTER(Handle)]),
+    "syldet_create_multi": (C.c_int, [C.POINTER(Config_p), C.c_int32, c_int32_p, C.c_int32, C.c_int32, C.c_int32, C.POINTER(Handle)]),
+    "syldet_config_compatible": (C.c_int, [Config_p, Config_p, C.POINTER(C.c_char_p)]),
     "syldet_destroy": (C.c_int, [Handle]),
     "syldet_get_geometry": (C.c_int, [Handle, C.POINTER(Geometry)]),
     "syldet_channels": (C.c_int32, [Handle]),

@@ -44,15 +44,33 @@ __device__ __forceinline__ float transfer(int tf, float x)
     }
 }
 
+// Channel c's parameter blob and thresholds: its own network's on a multi-network handle (NetDesc::net_of), else the one.
+__device__ __forceinline__ const float *net_params(const NetDesc &n, int c)
+{
+    return n.net_of ? n.params + (int64_t)__builtin_amdgcn_readfirstlane(n.net_of[c]) * n.params_stride : n.params;
+}
+__device__ __forceinline__ const double *net_thresholds(const NetDesc &n, int c)
+{
+    return n.net_of ? n.thresholds + (int64_t)__builtin_amdgcn_readfirstlane(n.net_of[c]) * n.thr_stride : n.thresholds;
+}
+
+// A map's y: the one network's (in the descriptor), or on a multi-network handle channel c's network's (in its blob P)
+__device__ __forceinline__ DevFn net_fn(const NetDesc &n, const float *P, DevFn fn)
+{
+    if (n.net_of) fn.y = P[fn.yoff];
+    return fn;
+}
+
 // One evaluation by one wave, in the reference's operation order (nothing folded): scaling (SyllableDetector.swift:184-212),
 // the input functions in file order (NeuralNet.swift:300-307), the layers (:310-313, :366-377), the reverse output maps
 // (:316-323), the threshold rule (SyllableDetector.swift:27-31 / TrackDetector.swift:72-77).  `src`: the I = T * F column
 // values of the window, oldest column first (global or LDS); bufA / bufB: this wave's two max_width-float buffers in LDS.
 // Contains workgroup barriers: every wave of the workgroup calls it the same number of times (valid = false: a dry run).
-__device__ __forceinline__ void mlp_eval_wave(const NetDesc &n, const float *src, bool valid, float *bufA, float *bufB, int lane,
+// c: the channel (picks the network of a multi-network handle).
+__device__ __forceinline__ void mlp_eval_wave(const NetDesc &n, int c, const float *src, bool valid, float *bufA, float *bufB, int lane,
                                               float *out, uint8_t *flag)
 {
-    const float *P = n.params;
+    const float *P = net_params(n, c);
     for (int i = lane; i < n.I; i += kWave) {
         float v = valid ? src[i] : 1.0f;
         if (n.scaling == 1) v = logf(v);                    // vvlogf, SyllableDetector.swift:207
@@ -62,7 +80,7 @@ __device__ __forceinline__ void mlp_eval_wave(const NetDesc &n, const float *src
     __syncthreads();
 
     for (int k = 0; k < n.n_in_fns; k++) {
-        const DevFn fn = n.in_fns[k];
+        const DevFn fn = net_fn(n, P, n.in_fns[k]);
         if (fn.kind == 0) {                                  // L2Normalize :47-59
             float s = 0.0f;
             for (int i = lane; i < n.I; i += kWave) s += bufA[i] * bufA[i];
@@ -148,7 +166,7 @@ __device__ __forceinline__ void mlp_eval_wave(const NetDesc &n, const float *src
     for (int o = lane; o < n.n_out; o += kWave) {
         float v = cur[o];
         for (int k = 0; k < n.n_out_fns; k++) {
-            const DevFn fn = n.out_fns[k];
+            const DevFn fn = net_fn(n, P, n.out_fns[k]);
             v = (v - fn.y) / P[fn.gain + o] + P[fn.xoff + o];
         }
         cur[o] = v;
@@ -158,7 +176,8 @@ __device__ __forceinline__ void mlp_eval_wave(const NetDesc &n, const float *src
     if (lane == 0 && valid && flag) {
         uint8_t hit = 0;
         const int lim = n.rule == 0 ? 1 : n.n_out;
-        for (int o = 0; o < lim; o++) hit |= ((double)cur[o] >= n.thresholds[o]) ? 1 : 0;
+        const double *thr = net_thresholds(n, c);
+        for (int o = 0; o < lim; o++) hit |= ((double)cur[o] >= thr[o]) ? 1 : 0;
         *flag = hit;
     }
     __syncthreads();

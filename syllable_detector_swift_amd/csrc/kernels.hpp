@@ -26,6 +26,7 @@ struct DevFn {
     int kind;                 // syldet_fn_kind_t
     int xoff, gain;           // offsets (in floats) into the parameter blob
     float y;
+    int yoff;                 // ... and of y (what a multi-network handle reads: each network has its own y)
 };
 struct DevLayer {
     int in, out, tf;          // tf: syldet_transfer_t
@@ -42,6 +43,10 @@ struct NetDesc {
     int rule;                 // syldet_rule_t
     const float *params;      // parameter blob
     const double *thresholds; // [n_out]
+    // multi-network handles (syldet_create_multi): channel c reads the blob and thresholds of network net_of[c], which sit
+    // params_stride floats / thr_stride doubles apart (compatible networks have the same offsets); null for one network
+    const int *net_of;
+    int params_stride, thr_stride;
 };
 
 // ---- generic engine (any power-of-two N, any processing chain, any layer sizes) ----
@@ -208,6 +213,19 @@ struct FusedDesc {
     int ko;                     // diagnostic build only: knock-out mask (SYLDET_FUSED_KO)
     unsigned long long *stamps; // diagnostic build only: [workgroups][16] phase cycle sums, else null
 };
+// What the fold kernel reads of ONE network, for multi-network handles (syldet_create_multi): everything else of FusedDesc is
+// the shape, which compatible networks share.  A workgroup reads nets[net_of[its channel]] once, before its tiles.
+struct FusedNet {
+    const uint4 *afrag_t, *afrag_w, *afrag_t2, *afrag_w2;   // as in FusedDesc
+    const float *bias0, *rvec, *w1, *b1, *out_params;
+    const double *thresholds;
+    float w_unscale, guard_r, guard_rel_r, guard_range_r, guard_loud;
+    int guard_se_abs_r;
+};
+struct FusedMulti {             // (host side: what launch_fused hands the fold kernel's multi-network form)
+    const FusedNet *nets;       // [networks]
+    const int *net_of;          // [C]
+};
 
 // ---- first layer on the matrix cores for spectrograms already in HBM (kernels_mlpx.hip) --------------------
 // The generic engine's network stage for the detector class the training script writes (l2normalize first, affine
@@ -275,8 +293,9 @@ struct FlagSources {
 hipError_t launch_unpack_flags_from(const FlagSources &from, int64_t rows, int64_t row_len, int64_t shards, int64_t padded,
                                     uint8_t *flags, hipStream_t stream);
 
+// mn: a multi-network handle's tables (only the fold kernel has that form: anything else is hipErrorInvalidValue)
 hipError_t launch_fused(const FusedDesc &d, const float *samples, int64_t stride, int C, int64_t S, int64_t J,
-                        int64_t E, float *outputs, uint8_t *flags, hipStream_t stream);
+                        int64_t E, float *outputs, uint8_t *flags, hipStream_t stream, const FusedMulti *mn = nullptr);
 int fused_choice(const FusedDesc &d, int64_t J);    // 0 the 8-wave kernel, 1 the register-resident-basis kernel, 2 the symmetric-fold kernel
 // the DFT front half alone: samples -> [C][J][F] columns; d: a plan for timeRange 1 with spect_out / spect_power set
 hipError_t launch_fused_spectrogram(const FusedDesc &d, const float *samples, int64_t stride, int C, int64_t J, hipStream_t stream);
@@ -292,7 +311,7 @@ hipError_t launch_fused_r(const FusedDesc &d, const float *samples, int64_t stri
 // the same contract on the symmetric-fold kernel; only called when fused_s_applicable(d)
 bool fused_s_applicable(const FusedDesc &d);
 hipError_t launch_fused_s(const FusedDesc &d, const float *samples, int64_t stride, int C, int64_t S, int64_t J,
-                          int64_t E, float *outputs, uint8_t *flags, hipStream_t stream);
+                          int64_t E, float *outputs, uint8_t *flags, hipStream_t stream, const FusedMulti *mn = nullptr);
 // taps the register-resident first-layer fragments are instantiated for (0: timeRange too long)
 int fused_taps_max(int T);
 

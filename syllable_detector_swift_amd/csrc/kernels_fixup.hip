@@ -101,7 +101,7 @@ fixup_kernel(const FixDesc fd, const NetDesc n, const float *__restrict__ sample
             const int el = r * (kBlock / kWave) + wave;
             const int64_t e = first + el;
             const bool valid = el < item.count && e < E;
-            mlp_eval_wave(n, cols + (valid ? el : 0) * F, valid, bufA, bufB, lane,
+            mlp_eval_wave(n, c, cols + (valid ? el : 0) * F, valid, bufA, bufB, lane,
                           (valid && outputs) ? outputs + ((int64_t)c * E + e) * n.n_out : nullptr,
                           (valid && flags) ? flags + (int64_t)c * E + e : nullptr);
         }

@@ -103,11 +103,16 @@ __device__ __forceinline__ void split2(float a, float b, unsigned &hi, unsigned 
 // holds, so 4 waves a workgroup, one per SIMD, with 512 registers and twice the LDS each.
 // SPECT: the |X| (or |X|^2) columns themselves leave, [C][J][F] fp32 (E counts frames then: the plan's stand-in network has
 // timeRange 1), nothing of the network runs -- the front half of the wide engine and of syldet_spectrogram*.
-template <int K2, bool GEN, int HQ, int NW, int PADP = 0, bool F2 = false, int NT = 1, bool SPECT = false>
+// MN: a multi-network handle (syldet_create_multi).  The workgroup's channel picks its network, nets[net_of[c]], once: a scalar
+// load of a uniform address, so the index and every table pointer derived from it stay in SGPRs (no waterfall loop), and the
+// network's first-layer fragments, biases, output stage, thresholds, weight scale and guard constants come from there instead of
+// from d.  Everything else in d is the shape, shared by compatible networks.  Without MN the two trailing arguments are unused.
+template <int K2, bool GEN, int HQ, int NW, int PADP = 0, bool F2 = false, int NT = 1, bool SPECT = false, bool MN = false>
 __global__ void __launch_bounds__(64 * NW, 1)
 fused_s_kernel(const FusedDesc d, const float *__restrict__ samples, int64_t stride, int64_t s_eff, int64_t E,
-               float *__restrict__ outputs, uint8_t *__restrict__ flags)
+               float *__restrict__ outputs, uint8_t *__restrict__ flags, const FusedNet *__restrict__ nets, const int *__restrict__ net_of)
 {
+    static_assert(!(MN && SPECT), "the spectrogram instantiation runs no network");
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const int tid = threadIdx.x;
     const int lane = tid & 63;
@@ -125,6 +130,8 @@ fused_s_kernel(const FusedDesc d, const float *__restrict__ samples, int64_t str
     const int seg_len = (int)(e_e - e_b);
     const int tiles = (seg_len + (T - 1) + kTile - 1) / kTile;
     const unsigned e_b32 = (unsigned)e_b;
+    const FusedNet *nt = MN ? nets + __builtin_amdgcn_readfirstlane(net_of[c]) : nullptr;
+#define SD_NET(f) (MN ? nt->f : d.f)
 
     // frame of slot n (see the header): slots {0-3, 12-15} take the even frames, {4-11} the odd ones
     const int fr = d.s_perm ? (n < 4 ? 2 * n : (n >= 12 ? 2 * (n - 8) : 2 * (n - 4) + 1)) : n;
@@ -201,7 +208,7 @@ fused_s_kernel(const FusedDesc d, const float *__restrict__ samples, int64_t str
             for (int tau = 0; tau < NT; tau++)
 #pragma unroll
                 for (int p = 0; p < 2; p++)
-                    aft[m][q][tau][p] = as_half8(reinterpret_cast<const uint32x4 *>(F2 ? (HQ == 1 ? d.afrag_t2 : d.afrag_w2) : (HQ == 1 ? d.afrag_t : d.afrag_w))[(((m * HQ + q) * NT + tau) * 2 + p) * 64 + lane]);
+                    aft[m][q][tau][p] = as_half8(reinterpret_cast<const uint32x4 *>(F2 ? (HQ == 1 ? SD_NET(afrag_t2) : SD_NET(afrag_w2)) : (HQ == 1 ? SD_NET(afrag_t) : SD_NET(afrag_w)))[(((m * HQ + q) * NT + tau) * 2 + p) * 64 + lane]);
     float cre[8];                                     // w[0] cos(pi k W / N) 2^13 for this lane's bins 4 g + i, 16 + 4 g + i
 #pragma unroll
     for (int i = 0; i < 8; i++) cre[i] = F2 ? 0.0f : d.slone[lane * 8 + i];
@@ -272,22 +279,22 @@ fused_s_kernel(const FusedDesc d, const float *__restrict__ samples, int64_t str
 #pragma unroll
     for (int m = 0; m < 3; m++) pt_p[m] = 4 * m + g < TP ? prow + 4 * HQ * (4 * m + g) : zquad + 4 * HQ;
 
-    const float c_b1 = GEN ? (g < n_out ? d.b1[g] : 0.0f) : d.b1[0];
+    const float c_b1 = GEN ? (g < n_out ? SD_NET(b1)[g] : 0.0f) : SD_NET(b1)[0];
     float lean_oa = 0.0f, lean_og = 1.0f, lean_ob = 0.0f;
     if (d.n_out_fns == 1) {
         const int o = (GEN && g < n_out) ? g : 0;
-        lean_oa = d.out_params[0]; lean_og = d.out_params[1 + o]; lean_ob = d.out_params[1 + n_out + o];
+        lean_oa = SD_NET(out_params)[0]; lean_og = SD_NET(out_params)[1 + o]; lean_ob = SD_NET(out_params)[1 + n_out + o];
     }
     // this lane group's hidden units: 4 q + g
     float b0g[HQ], w1g[HQ], w1o[4][HQ], rvg[HQ];      // (rvg: (W0 o a) . 1, what the normalisers' offset meets)
 #pragma unroll
     for (int q = 0; q < HQ; q++) {
         const int u = 4 * q + g;
-        rvg[q] = (GEN && u < H) ? d.rvec[u] : 0.0f;
-        b0g[q] = u < H ? d.bias0[u] : 0.0f;
-        w1g[q] = u < H ? d.w1[u] : 0.0f;
+        rvg[q] = (GEN && u < H) ? SD_NET(rvec)[u] : 0.0f;
+        b0g[q] = u < H ? SD_NET(bias0)[u] : 0.0f;
+        w1g[q] = u < H ? SD_NET(w1)[u] : 0.0f;
 #pragma unroll
-        for (int o = 0; o < 4; o++) w1o[o][q] = (GEN && u < H && o < n_out) ? d.w1[o * H + u] : 0.0f;
+        for (int o = 0; o < 4; o++) w1o[o][q] = (GEN && u < H && o < n_out) ? SD_NET(w1)[o * H + u] : 0.0f;
     }
     if (kTbl && n == 0) {
 #pragma unroll
@@ -300,7 +307,7 @@ fused_s_kernel(const FusedDesc d, const float *__restrict__ samples, int64_t str
         }
     }
     const bool multi = GEN && n_out > 1;
-    const double thr_g = d.thresholds[(GEN && g < n_out) ? g : 0];
+    const double thr_g = SD_NET(thresholds)[(GEN && g < n_out) ? g : 0];
     if (kTbl && n == 0) {                              // (the output stage's constants wait in the table too)
         gtab[22] = c_b1; gtab[23] = lean_oa; gtab[24] = lean_og; gtab[25] = lean_ob;
         *reinterpret_cast<double *>(gtab + 26) = thr_g;
@@ -317,7 +324,11 @@ fused_s_kernel(const FusedDesc d, const float *__restrict__ samples, int64_t str
     }
     const float kmag = pow2f(-13 - d.col_shift);
     const bool guard_on = d.fix.counters != nullptr;
-    const float guard_k = norm == 1 ? d.guard_r : (norm == 0 ? d.guard_rel_r : d.guard_range_r);
+    const float guard_k = norm == 1 ? SD_NET(guard_r) : (norm == 0 ? SD_NET(guard_rel_r) : SD_NET(guard_range_r));
+    // (the network's scalars the loop reads, fetched here once; without MN the loop reads d's as before)
+    const float mn_wu = MN ? nt->w_unscale : 0.0f, mn_loud = MN ? nt->guard_loud : 0.0f;
+    const int mn_se_abs = MN ? nt->guard_se_abs_r : 0;
+#undef SD_NET
 
     // ---- prologue: tile 0's samples
     issue_upto(need(0) < allowed(0) ? need(0) : allowed(0));
@@ -822,17 +833,17 @@ fused_s_kernel(const FusedDesc d, const float *__restrict__ samples, int64_t str
         bool hit;
         {
             const int ush = (GEN && scaling != 0) ? 0 : d.col_shift - se_ref;
-            const float alpha0 = d.w_unscale * pow2f(ush < -120 ? -120 : (ush > 120 ? 120 : ush));
-            float alpha = norm == 1 ? d.w_unscale * __builtin_amdgcn_rsqf(ssw) : alpha0, beta = 0.0f;
+            const float alpha0 = (MN ? mn_wu : d.w_unscale) * pow2f(ush < -120 ? -120 : (ush > 120 ? 120 : ush));
+            float alpha = norm == 1 ? (MN ? mn_wu : d.w_unscale) * __builtin_amdgcn_rsqf(ssw) : alpha0, beta = 0.0f;
             if (GEN && norm == 2) {                   // Normalize: 2 (v - mn) / (mx - mn) - 1, all -1 when mx == mn
                 const float range = st1w - ssw;
                 gstat = range;
                 if (range == 0.0f) { alpha = 0.0f; beta = -1.0f; }
-                else { alpha = d.w_unscale * 2.0f / range; beta = (0.0f - ssw - st1w) / range; }
+                else { alpha = (MN ? mn_wu : d.w_unscale) * 2.0f / range; beta = (0.0f - ssw - st1w) / range; }
             } else if (GEN && norm == 3) {            // NormalizeStd: (v - mean) / sigma, population sigma
                 const float sdv = sqrtf(st1w / (float)d.I);
                 gstat = sdv;
-                alpha = d.w_unscale / sdv;
+                alpha = (MN ? mn_wu : d.w_unscale) / sdv;
                 beta = -ssw / sdv;
             }
             float b0_l[HQ], w1_l[HQ], w1o_l[4][HQ], rv_l[HQ];
@@ -920,14 +931,14 @@ fused_s_kernel(const FusedDesc d, const float *__restrict__ samples, int64_t str
                 // no normaliser: loud enough for the floor not to matter?  (the floor in true units against the network's sensitivity)
                 // fww = 4^(se_ref - se_min): se_min = se_ref - log2(fww) / 2
                 const int lg = (int)((__float_as_uint(fww) >> 23) & 0xffu) - 127;
-                if (se_ref - lg / 2 >= d.guard_se_abs_r) bad = false;
+                if (se_ref - lg / 2 >= (MN ? mn_se_abs : d.guard_se_abs_r)) bad = false;
             }
             if (GEN && norm == 0 && scaling == 0 && vld) {
                 // ... and loud enough for the arithmetic's own relative error to matter?  (fused_plan.cpp, guard_loud: the window's
                 // norm in true units through the network's root-sum-square gain)
                 const int ush2 = 2 * (d.col_shift - se_ref);
                 const float u2 = st1w * pow2f(ush2 < -120 ? -120 : (ush2 > 120 ? 120 : ush2));
-                if (u2 * d.guard_loud > 1.0f) bad = true;
+                if (u2 * (MN ? mn_loud : d.guard_loud) > 1.0f) bad = true;
             }
             if (__builtin_amdgcn_ballot_w64(bad) != 0ull) {
                 const int er0 = kTile * t - (T - 1);
@@ -970,11 +981,14 @@ fused_s_kernel(const FusedDesc d, const float *__restrict__ samples, int64_t str
 #undef SD_STAMP
 }
 
-template <int K2, bool GEN, int HQ, int NW, int PADP = 0, bool F2 = false, int NT = 1, bool SPECT = false>
+template <int K2, bool GEN, int HQ, int NW, int PADP = 0, bool F2 = false, int NT = 1, bool SPECT = false, bool MN = false>
 hipError_t launch_one(const FusedDesc &d, const float *samples, int64_t stride, int C, int64_t s_eff, int64_t E,
-                      float *outputs, uint8_t *flags, hipStream_t stream)
+                      float *outputs, uint8_t *flags, hipStream_t stream, const FusedMulti *mn = nullptr)
 {
-    auto kern = fused_s_kernel<K2, GEN, HQ, NW, PADP, F2, NT, SPECT>;
+    // (every network instantiation has its multi-network twin)
+    if constexpr (!SPECT && !MN)
+        if (mn) return launch_one<K2, GEN, HQ, NW, PADP, F2, NT, false, true>(d, samples, stride, C, s_eff, E, outputs, flags, stream, mn);
+    auto kern = fused_s_kernel<K2, GEN, HQ, NW, PADP, F2, NT, SPECT, MN>;
     constexpr int kWaves = NW;
 #ifdef SYLDET_S_ONEWAVE
     const int lds = kWaves == 4 ? 100 * 1024 : d.s_lds_wave * kWaves;       // (one workgroup a CU)
@@ -985,7 +999,9 @@ hipError_t launch_one(const FusedDesc &d, const float *samples, int64_t stride, 
     if (st != hipSuccess) return st;
     const int64_t segs = (E + d.s_seg_evals - 1) / d.s_seg_evals;         // wave segments per channel
     dim3 grid((unsigned)((segs + kWaves - 1) / kWaves), (unsigned)C);
-    hipLaunchKernelGGL(kern, grid, dim3(64 * kWaves), (size_t)lds, stream, d, samples, stride, s_eff, E, outputs, flags);
+    const FusedNet *nets = MN ? mn->nets : nullptr;
+    const int *net_of = MN ? mn->net_of : nullptr;
+    hipLaunchKernelGGL(kern, grid, dim3(64 * kWaves), (size_t)lds, stream, d, samples, stride, s_eff, E, outputs, flags, nets, net_of);
     return hipGetLastError();
 }
 
@@ -1013,7 +1029,7 @@ bool fused_s_applicable(const FusedDesc &d)
 }
 
 hipError_t launch_fused_s(const FusedDesc &d, const float *samples, int64_t stride, int C, int64_t S, int64_t J,
-                          int64_t E, float *outputs, uint8_t *flags, hipStream_t stream)
+                          int64_t E, float *outputs, uint8_t *flags, hipStream_t stream, const FusedMulti *mn)
 {
     (void)S;
     if (E <= 0 || C <= 0) return hipSuccess;
@@ -1023,28 +1039,28 @@ hipError_t launch_fused_s(const FusedDesc &d, const float *samples, int64_t stri
     const bool exact = d.norm == 1 && d.scaling == 0 && d.tf0 == 0 /* TanSig */ && d.tf1 == 2 /* PureLin */ && d.n_out == 1;
 #define SD_S_GO(K2_)                                                                                                  \
     if (d.W == 64 * K2_) {                                                                                            \
-        if (d.H > 12) return launch_one<K2_, true, 4, 4>(d, samples, stride, C, s_eff, E, outputs, flags, stream);    \
-        if (d.H > 8) return launch_one<K2_, true, 3, 4>(d, samples, stride, C, s_eff, E, outputs, flags, stream);     \
-        if (d.H > 4 && d.s_waves == 8) return launch_one<K2_, true, 2, 8>(d, samples, stride, C, s_eff, E, outputs, flags, stream); \
-        if (d.H > 4) return launch_one<K2_, true, 2, 4>(d, samples, stride, C, s_eff, E, outputs, flags, stream);     \
-        if (exact) return launch_one<K2_, false, 1, 8>(d, samples, stride, C, s_eff, E, outputs, flags, stream);      \
-        return launch_one<K2_, true, 1, 8>(d, samples, stride, C, s_eff, E, outputs, flags, stream);                  \
+        if (d.H > 12) return launch_one<K2_, true, 4, 4>(d, samples, stride, C, s_eff, E, outputs, flags, stream, mn);    \
+        if (d.H > 8) return launch_one<K2_, true, 3, 4>(d, samples, stride, C, s_eff, E, outputs, flags, stream, mn);     \
+        if (d.H > 4 && d.s_waves == 8) return launch_one<K2_, true, 2, 8>(d, samples, stride, C, s_eff, E, outputs, flags, stream, mn); \
+        if (d.H > 4) return launch_one<K2_, true, 2, 4>(d, samples, stride, C, s_eff, E, outputs, flags, stream, mn);     \
+        if (exact) return launch_one<K2_, false, 1, 8>(d, samples, stride, C, s_eff, E, outputs, flags, stream, mn);      \
+        return launch_one<K2_, true, 1, 8>(d, samples, stride, C, s_eff, E, outputs, flags, stream, mn);                  \
     }
     // hops that are multiples of 64: the padded ring (256-sample windows, up to 4 hidden units: fused_plan.cpp)
 #define SD_S_PAD(K2_, P_)                                                                                              \
     if (d.W == 64 * K2_ && d.s_padp == P_) {                                                                           \
         if (d.H > 4) return hipErrorInvalidValue;                                                                      \
         if (K2_ == 4 && d.s2_ok && !d.no_fold2) {                                                                      \
-            if (exact) return launch_one<4, false, 1, 8, P_, true>(d, samples, stride, C, s_eff, E, outputs, flags, stream); \
-            return launch_one<4, true, 1, 8, P_, true>(d, samples, stride, C, s_eff, E, outputs, flags, stream);       \
+            if (exact) return launch_one<4, false, 1, 8, P_, true>(d, samples, stride, C, s_eff, E, outputs, flags, stream, mn); \
+            return launch_one<4, true, 1, 8, P_, true>(d, samples, stride, C, s_eff, E, outputs, flags, stream, mn);       \
         }                                                                                                              \
-        if (exact) return launch_one<K2_, false, 1, 8, P_>(d, samples, stride, C, s_eff, E, outputs, flags, stream);   \
-        return launch_one<K2_, true, 1, 8, P_>(d, samples, stride, C, s_eff, E, outputs, flags, stream);               \
+        if (exact) return launch_one<K2_, false, 1, 8, P_>(d, samples, stride, C, s_eff, E, outputs, flags, stream, mn);   \
+        return launch_one<K2_, true, 1, 8, P_>(d, samples, stride, C, s_eff, E, outputs, flags, stream, mn);               \
     }
     // hop 128 under the twice-folded form: whole chunks staggered over the banks (CS8; SYLDET_FUSED_PAD128=1 keeps the padded pieces)
     if (d.s_cs8 && !d.no_cs8 && d.s2_ok && !d.no_fold2 && d.W == 256 && d.H <= 4 && d.s2_nt == 1) {
-        if (exact) return launch_one<4, false, 1, 8, 1, true>(d, samples, stride, C, s_eff, E, outputs, flags, stream);
-        return launch_one<4, true, 1, 8, 1, true>(d, samples, stride, C, s_eff, E, outputs, flags, stream);
+        if (exact) return launch_one<4, false, 1, 8, 1, true>(d, samples, stride, C, s_eff, E, outputs, flags, stream, mn);
+        return launch_one<4, true, 1, 8, 1, true>(d, samples, stride, C, s_eff, E, outputs, flags, stream, mn);
     }
     if (d.s_padp) {
         SD_S_PAD(4, 64) SD_S_PAD(4, 128)
@@ -1054,24 +1070,24 @@ hipError_t launch_fused_s(const FusedDesc &d, const float *samples, int64_t stri
     // W == N == 256, up to four hidden units: the twice-folded instantiation (SYLDET_FUSED_NOFOLD2=1 keeps the once-folded one: A/B runs)
     if (d.s2_ok && d.s2_nt == 2) {                   // bands of 33 .. 64 bins: the twice-folded form with two row tiles per parity, 4 waves
         if (d.no_fold2 || d.s_padp) return hipErrorInvalidValue;
-        if (exact) return launch_one<4, false, 1, 4, 0, true, 2>(d, samples, stride, C, s_eff, E, outputs, flags, stream);
-        return launch_one<4, true, 1, 4, 0, true, 2>(d, samples, stride, C, s_eff, E, outputs, flags, stream);
+        if (exact) return launch_one<4, false, 1, 4, 0, true, 2>(d, samples, stride, C, s_eff, E, outputs, flags, stream, mn);
+        return launch_one<4, true, 1, 4, 0, true, 2>(d, samples, stride, C, s_eff, E, outputs, flags, stream, mn);
     }
     if (d.s2_ok && !d.no_fold2 && d.W == 256) {       // (5 .. 16 hidden units too: the halved basis and the single pass do not depend on the layer's width)
-        if (d.H > 12) return launch_one<4, true, 4, 4, 0, true>(d, samples, stride, C, s_eff, E, outputs, flags, stream);
-        if (d.H > 8) return launch_one<4, true, 3, 4, 0, true>(d, samples, stride, C, s_eff, E, outputs, flags, stream);
+        if (d.H > 12) return launch_one<4, true, 4, 4, 0, true>(d, samples, stride, C, s_eff, E, outputs, flags, stream, mn);
+        if (d.H > 8) return launch_one<4, true, 3, 4, 0, true>(d, samples, stride, C, s_eff, E, outputs, flags, stream, mn);
         // (5 .. 8 hidden units on eight waves stay once-folded: with two accumulator sets AND the kept samples the twice-folded
         // form spills at 256 registers and measures 10 % slower there -- except under hops that are multiples of 64, where
         // reading the ring once (its rows then collide on the banks: there is no padded ring for wider layers) is worth 15 %;
         // MEASUREMENTS.md R4.8)
-        if (d.H > 4 && d.s_waves == 8 && d.hop % 64 == 0) return launch_one<4, true, 2, 8, 0, true>(d, samples, stride, C, s_eff, E, outputs, flags, stream);
-        if (d.H > 4 && d.s_waves == 8) return launch_one<4, true, 2, 8>(d, samples, stride, C, s_eff, E, outputs, flags, stream);
-        if (d.H > 4) return launch_one<4, true, 2, 4, 0, true>(d, samples, stride, C, s_eff, E, outputs, flags, stream);
+        if (d.H > 4 && d.s_waves == 8 && d.hop % 64 == 0) return launch_one<4, true, 2, 8, 0, true>(d, samples, stride, C, s_eff, E, outputs, flags, stream, mn);
+        if (d.H > 4 && d.s_waves == 8) return launch_one<4, true, 2, 8>(d, samples, stride, C, s_eff, E, outputs, flags, stream, mn);
+        if (d.H > 4) return launch_one<4, true, 2, 4, 0, true>(d, samples, stride, C, s_eff, E, outputs, flags, stream, mn);
 #ifdef SYLDET_S_ONEWAVE                // (diagnostic build: ONE wave a SIMD -- how long does a tile take a wave with nobody to share with?)
-        if (exact) return launch_one<4, false, 1, 4, 0, true>(d, samples, stride, C, s_eff, E, outputs, flags, stream);
+        if (exact) return launch_one<4, false, 1, 4, 0, true>(d, samples, stride, C, s_eff, E, outputs, flags, stream, mn);
 #endif
-        if (exact) return launch_one<4, false, 1, 8, 0, true>(d, samples, stride, C, s_eff, E, outputs, flags, stream);
-        return launch_one<4, true, 1, 8, 0, true>(d, samples, stride, C, s_eff, E, outputs, flags, stream);
+        if (exact) return launch_one<4, false, 1, 8, 0, true>(d, samples, stride, C, s_eff, E, outputs, flags, stream, mn);
+        return launch_one<4, true, 1, 8, 0, true>(d, samples, stride, C, s_eff, E, outputs, flags, stream, mn);
     }
     SD_S_GO(4) SD_S_GO(2) SD_S_GO(1) SD_S_GO(3)
 #undef SD_S_GO

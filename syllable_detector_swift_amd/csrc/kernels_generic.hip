@@ -347,7 +347,7 @@ mlp_generic_kernel(NetDesc n, int F, const float *__restrict__ columns, int64_t 
         const bool valid = e < E;
         const float *src = cols + e * F;
 
-        mlp_eval_wave(n, src, valid, bufA, bufB, lane, outputs ? outputs + (((int64_t)c * E) + e) * n.n_out : nullptr,
+        mlp_eval_wave(n, c, src, valid, bufA, bufB, lane, outputs ? outputs + (((int64_t)c * E) + e) * n.n_out : nullptr,
                       flags ? flags + (int64_t)c * E + e : nullptr);
     }
 }
@@ -371,10 +371,11 @@ mlp_small_kernel(NetDesc n, int F, const float *__restrict__ columns, int64_t J,
     const int wave = threadIdx.x / kWave, lane = threadIdx.x & (kWave - 1);
     const int c = blockIdx.y;
     const float *cols = columns + (int64_t)c * J * F;
-    const float *P = n.params;
+    const float *P = net_params(n, c);
     const int I = n.I;
     const DevLayer L0 = n.layers[0];
     const int H = L0.out;
+    const double *thr = net_thresholds(n, c);
 
     extern __shared__ float wlds[];                             // WLDS: [HMAX][KI * 64]
     float w[WLDS ? 1 : HMAX][WLDS ? 1 : KI];                    // else: first-layer rows, this lane's elements
@@ -453,7 +454,7 @@ mlp_small_kernel(NetDesc n, int F, const float *__restrict__ columns, int64_t J,
         if (WLDS) asm volatile("" : "+v"(wl));                  // keeps the LDS reads inside the loop (hoisted, they are 120 registers)
         int slot = 0;
         for (int q = 0; q < n.n_in_fns; q++) {
-            const DevFn fn = n.in_fns[q];
+            const DevFn fn = net_fn(n, P, n.in_fns[q]);
             if (fn.kind == 0) {                                  // L2Normalize :47-59
                 float s = 0.0f;
 #pragma unroll
@@ -550,11 +551,11 @@ mlp_small_kernel(NetDesc n, int F, const float *__restrict__ columns, int64_t J,
             if (o < n_out) {
                 float v = y[o];
                 for (int q = 0; q < n.n_out_fns; q++) {          // reverse maps, NeuralNet.swift:137-142 / :175-180
-                    const DevFn fn = n.out_fns[q];
+                    const DevFn fn = net_fn(n, P, n.out_fns[q]);
                     v = (v - fn.y) / P[fn.gain + o] + P[fn.xoff + o];
                 }
                 if (lane == 0 && outputs) outputs[(((int64_t)c * E) + e) * n_out + o] = v;
-                if (o == 0 || n.rule != 0) hit |= ((double)v >= n.thresholds[o]) ? 1 : 0;
+                if (o == 0 || n.rule != 0) hit |= ((double)v >= thr[o]) ? 1 : 0;
             }
         }
         if (lane == 0 && flags) flags[(int64_t)c * E + e] = hit;
@@ -576,11 +577,11 @@ mlp_chain_kernel(NetDesc n, int F, const float *__restrict__ columns, int64_t J,
     const int wave = threadIdx.x / kWave, lane = threadIdx.x & (kWave - 1);
     const int c = blockIdx.y;
     const float *cols = columns + (int64_t)c * J * F;
-    const float *P = n.params;
+    const float *P = net_params(n, c);
     const int I = n.I;
     const DevLayer L0 = n.layers[0], L1 = n.layers[1];
     const int H = L0.out, n_out = L1.out;
-    const DevFn aff = n.in_fns[L2 ? 1 : 0];
+    const DevFn aff = net_fn(n, P, n.in_fns[L2 ? 1 : 0]);
 
     extern __shared__ float wlds[];                             // WLDS: [HMAX][KI * 64] rows, then offsets and gains [2][KI * 64]
     float *alds = wlds + HMAX * KI * kWave;
@@ -615,8 +616,9 @@ mlp_chain_kernel(NetDesc n, int F, const float *__restrict__ columns, int64_t J,
         og[o] = (n.n_out_fns == 1 && o < n_out) ? P[n.out_fns[0].gain + o] : 1.0f;
         ox[o] = (n.n_out_fns == 1 && o < n_out) ? P[n.out_fns[0].xoff + o] : 0.0f;
     }
-    const float oy = n.n_out_fns == 1 ? n.out_fns[0].y : 0.0f;
-    const double thr0 = n.thresholds[0], thr1 = n_out > 1 ? n.thresholds[1] : 0.0;
+    const float oy = n.n_out_fns == 1 ? net_fn(n, P, n.out_fns[0]).y : 0.0f;
+    const double *thr = net_thresholds(n, c);
+    const double thr0 = thr[0], thr1 = n_out > 1 ? thr[1] : 0.0;
     const int scaling = n.scaling, tf0 = L0.tf, tf1 = L1.tf;
     const bool any_rule = n.rule != 0;
 

@@ -183,6 +183,17 @@ struct syldet {
     DeviceBuffer d_xn;                // [C*E][kWideK] bf16 normalised inputs
     hipStream_t stream = nullptr;     // used by the host-pointer entry points
 
+    // multi-network handles (syldet_create_multi): channel c runs network net_of[c] of n_nets compatible ones.  cfg is network
+    // 0's (the shape every network shares); the per-network tables sit at a fixed stride: the generic engine's parameter blobs
+    // and thresholds (net.params_stride / thr_stride), and the fold kernel's FusedNet tables (d_fnets, fnets).
+    int n_nets = 1;
+    std::vector<int> net_of;          // [C] (empty for one network)
+    std::vector<double> chan_thr0;    // [C] the first threshold of each channel's network (syldet_last_detected)
+    DeviceBuffer d_net_of;            // [C] int
+    DeviceBuffer d_fnets;             // per-network fold-kernel tables, then FusedNet[n_nets]
+    DeviceBuffer d_stage_net;         // [C] int: net_of of the channels one streaming launch carries
+    const FusedNet *fnets = nullptr;  // (in d_fnets) null unless the handle runs the fold kernel's multi-network form
+
     std::vector<std::unique_ptr<ChannelStream>> streams;
     std::mutex pump_mu;               // the staging buffers and the stream below belong to one pump at a time
     PinnedBuffer p_stage_in, p_stage_out;
@@ -224,6 +235,60 @@ struct syldet {
 namespace {
 
 
+// The generic engine's parameter blob of one network (NetDesc's offsets point into it) and the NetDesc that describes it;
+// compatible networks give the same offsets and the same blob length.
+int make_net_blob(const syldet_config_t &c, const syldet_geometry_t &g, NetDesc &n, std::vector<float> &blob)
+{
+    std::memset(&n, 0, sizeof(n));
+    blob.clear();
+    if (c.n_input_fns > kMaxFns || c.n_output_fns > kMaxFns || c.n_layers > kMaxLayers)
+        return fail(SYLDET_ERR_UNSUPPORTED, "more than 8 processing functions or 8 layers");
+    auto push = [&blob](const float *p, size_t cnt) {
+        const int off = (int)blob.size();
+        blob.insert(blob.end(), p, p + cnt);
+        return off;
+    };
+    n.n_in_fns = c.n_input_fns;
+    for (int i = 0; i < c.n_input_fns; i++) {
+        const syldet_fn_t &f = c.input_fns[i];
+        n.in_fns[i].kind = f.kind;
+        n.in_fns[i].y = f.y;
+        n.in_fns[i].yoff = push(&f.y, 1);
+        if (f.count > 0) {
+            n.in_fns[i].xoff = push(f.x_offsets, (size_t)f.count);
+            n.in_fns[i].gain = push(f.gains, (size_t)f.count);
+        }
+    }
+    n.n_layers = c.n_layers;
+    int max_width = g.inputs;
+    for (int l = 0; l < c.n_layers; l++) {
+        const syldet_layer_t &L = c.layers[l];
+        n.layers[l].in = L.inputs;
+        n.layers[l].out = L.outputs;
+        n.layers[l].tf = L.transfer;
+        n.layers[l].w = push(L.weights, (size_t)L.inputs * (size_t)L.outputs);
+        n.layers[l].b = push(L.biases, (size_t)L.outputs);
+        max_width = std::max(max_width, L.outputs);
+    }
+    n.n_out_fns = c.n_output_fns;
+    for (int i = 0; i < c.n_output_fns; i++) {
+        const syldet_fn_t &f = c.output_fns[i];
+        n.out_fns[i].kind = f.kind;
+        n.out_fns[i].y = f.y;
+        n.out_fns[i].yoff = push(&f.y, 1);
+        n.out_fns[i].xoff = push(f.x_offsets, (size_t)f.count);
+        n.out_fns[i].gain = push(f.gains, (size_t)f.count);
+    }
+    n.I = g.inputs;
+    n.n_out = g.outputs;
+    n.max_width = max_width;
+    n.scaling = c.scaling;
+    n.rule = c.rule;
+    if ((size_t)max_width * 2 * 4 * sizeof(float) > 160 * 1024)
+        return fail(SYLDET_ERR_UNSUPPORTED, "layer wider than the generic engine's LDS budget");
+    return SYLDET_OK;
+}
+
 int build_tables(syldet *h)
 {
     const syldet_config_t &c = h->cfg.view;
@@ -261,51 +326,8 @@ int build_tables(syldet *h)
 
     // parameter blob for the unfolded network
     NetDesc &n = h->net;
-    std::memset(&n, 0, sizeof(n));
-    if (c.n_input_fns > kMaxFns || c.n_output_fns > kMaxFns || c.n_layers > kMaxLayers)
-        return fail(SYLDET_ERR_UNSUPPORTED, "more than 8 processing functions or 8 layers");
     std::vector<float> blob;
-    auto push = [&blob](const float *p, size_t cnt) {
-        const int off = (int)blob.size();
-        blob.insert(blob.end(), p, p + cnt);
-        return off;
-    };
-    n.n_in_fns = c.n_input_fns;
-    for (int i = 0; i < c.n_input_fns; i++) {
-        const syldet_fn_t &f = c.input_fns[i];
-        n.in_fns[i].kind = f.kind;
-        n.in_fns[i].y = f.y;
-        if (f.count > 0) {
-            n.in_fns[i].xoff = push(f.x_offsets, (size_t)f.count);
-            n.in_fns[i].gain = push(f.gains, (size_t)f.count);
-        }
-    }
-    n.n_layers = c.n_layers;
-    int max_width = g.inputs;
-    for (int l = 0; l < c.n_layers; l++) {
-        const syldet_layer_t &L = c.layers[l];
-        n.layers[l].in = L.inputs;
-        n.layers[l].out = L.outputs;
-        n.layers[l].tf = L.transfer;
-        n.layers[l].w = push(L.weights, (size_t)L.inputs * (size_t)L.outputs);
-        n.layers[l].b = push(L.biases, (size_t)L.outputs);
-        max_width = std::max(max_width, L.outputs);
-    }
-    n.n_out_fns = c.n_output_fns;
-    for (int i = 0; i < c.n_output_fns; i++) {
-        const syldet_fn_t &f = c.output_fns[i];
-        n.out_fns[i].kind = f.kind;
-        n.out_fns[i].y = f.y;
-        n.out_fns[i].xoff = push(f.x_offsets, (size_t)f.count);
-        n.out_fns[i].gain = push(f.gains, (size_t)f.count);
-    }
-    n.I = g.inputs;
-    n.n_out = g.outputs;
-    n.max_width = max_width;
-    n.scaling = c.scaling;
-    n.rule = c.rule;
-    if ((size_t)max_width * 2 * 4 * sizeof(float) > 160 * 1024)
-        return fail(SYLDET_ERR_UNSUPPORTED, "layer wider than the generic engine's LDS budget");
+    if (int st = make_net_blob(c, g, n, blob)) return st;
     if (int st = h->d_params.reserve(std::max<size_t>(blob.size(), 1) * sizeof(float))) return st;
     if (!blob.empty())
         SYLDET_HIP(hipMemcpy(h->d_params.ptr, blob.data(), blob.size() * sizeof(float), hipMemcpyHostToDevice));
@@ -723,13 +745,21 @@ generic_transform:
     return SYLDET_OK;
 }
 
+// d_net_of: a multi-network handle's network of each of the C rows (null: the handle's own [C] table, rows = channels)
 int run_on_stream(syldet *h, const float *d_samples, int64_t S, int64_t stride, int C, float *d_outputs,
-                  uint8_t *d_flags, hipStream_t stream)
+                  uint8_t *d_flags, hipStream_t stream, const int *d_net_of = nullptr)
 {
     const int64_t J = count_frames(h, S), E = count_evals(h, S);
     if (E <= 0) return SYLDET_OK;
     SYLDET_HIP(hipSetDevice(h->device));
     h->prof_begin();
+    // the network stage's (and the exact recomputation's) view of the rows' networks
+    NetDesc net = h->net;
+    FusedMulti mn{h->fnets, nullptr};
+    if (h->n_nets > 1) {
+        net.net_of = mn.net_of = d_net_of ? d_net_of : (const int *)h->d_net_of.ptr;
+    }
+    const FusedMulti *mnp = h->fnets ? &mn : nullptr;
     // the fused kernel addresses a channel's results with 32-bit byte offsets; longer rows take the generic engine
     bool fused_route = h->engine == SYLDET_ENGINE_FUSED && (uint64_t)E * (uint64_t)h->geom.outputs * 4u < 0xFFFFFFF0ull;
     FusedDesc d{};
@@ -753,6 +783,8 @@ int run_on_stream(syldet *h, const float *d_samples, int64_t S, int64_t stride, 
         const bool runnable = choice != 0 || d.classic_ok;
         const bool in_contract = ((h->cfg.view.scaling == SYLDET_SCALING_LINEAR && normalised_chain(h->cfg.view)) || choice == 2 || h->engine_asked == SYLDET_ENGINE_FUSED);
         if (!runnable || !in_contract) fused_route = false;
+        // (a multi-network handle: only the fold kernel has the form; the diagnostic stamped builds are not for it)
+        if (h->n_nets > 1 && (choice != 2 || h->sw.fused_stamps)) fused_route = false;
     }
     if (fused_route) {
         // diagnostic only: SYLDET_FUSED_STAMPS=1 runs the stamped instantiation and prints where a
@@ -819,9 +851,9 @@ int run_on_stream(syldet *h, const float *d_samples, int64_t S, int64_t stride, 
             // (the launcher picks the register-resident-basis kernel where it is instantiated: named for what runs)
             static const char *const names[3] = {"fused_kernel", "fused_r_kernel", "fused_s_kernel"};
             KernelTimer t(h, stream, names[fused_choice(d, J)]);
-            SYLDET_HIP(launch_fused(d, d_samples, stride, C, S, J, E, d_outputs, d_flags, stream));
+            SYLDET_HIP(launch_fused(d, d_samples, stride, C, S, J, E, d_outputs, d_flags, stream, mnp));
         }
-        return timed_fixup(h, stream, d.fix, [&](const FixList &l) { return launch_fixup(h->fixd, h->net, d_samples, stride, J, E, d_outputs, d_flags, nullptr, l, stream); });
+        return timed_fixup(h, stream, d.fix, [&](const FixList &l) { return launch_fixup(h->fixd, net, d_samples, stride, J, E, d_outputs, d_flags, nullptr, l, stream); });
     }
     // (+ 16 bytes: the matrix-core network stage reads a frame's last bins as a whole quad)
     if (int st = h->d_columns.reserve((size_t)C * (size_t)J * (size_t)h->geom.bins * sizeof(float) + 16)) return st;
@@ -858,7 +890,7 @@ int run_on_stream(syldet *h, const float *d_samples, int64_t S, int64_t stride, 
     }
     {
         KernelTimer t(h, stream, "mlp_generic_kernel");
-        SYLDET_HIP(launch_mlp_generic(h->net, h->geom.bins, (const float *)h->d_columns.ptr, C, J, E, d_outputs,
+        SYLDET_HIP(launch_mlp_generic(net, h->geom.bins, (const float *)h->d_columns.ptr, C, J, E, d_outputs,
                                       d_flags, stream));
     }
     return SYLDET_OK;
@@ -871,6 +903,118 @@ int check_batch_args(const syldet *h, const void *samples, int64_t S, int64_t st
     if (!samples && S > 0) return fail(SYLDET_ERR_INVALID_ARGUMENT, "NULL samples");
     // the stride only matters between rows; a single channel may pass anything
     if (h->channels > 1 && stride < S) return fail(SYLDET_ERR_INVALID_ARGUMENT, "channel_stride must be >= n_samples");
+    return SYLDET_OK;
+}
+
+// Would a handle of this one network, created under AUTO, run its batches on the fold kernel (syldet_create's rule plus the
+// launcher's choice, the SYLDET_* switches included)?  `fused_ok`: the fold kernel takes the shape at all (SYLDET_ENGINE_FUSED).
+bool takes_fold(const syldet_config_t &c, const syldet_geometry_t &g, const syldet::Switches &sw, bool &fused_ok)
+{
+    fused_ok = false;
+    FusedPlan plan;
+    if (!make_fused_plan(c, g, plan) || !fused_s_applicable(plan.desc)) return false;
+    FusedDesc d = plan.desc;
+    d.force_classic = sw.fused_classic ? 1 : 0;
+    d.no_fold = sw.fused_nofold ? 1 : 0;
+    d.no_fold2 = sw.fused_nofold2 ? 1 : 0;
+    d.no_cs8 = sw.fused_pad128 ? 1 : 0;
+    d.ko = sw.fused_ko;
+    d.stamps = nullptr;
+    fused_ok = fused_choice(d, 1) == 2;
+    // AUTO: log / dB columns only behind l2normalize; linear ones on any chain the fold kernel takes
+    return fused_ok && (c.scaling == SYLDET_SCALING_LINEAR || d.norm == 1);
+}
+
+// The fold kernel's per-network tables of a multi-network handle: each network's plan, its weight-dependent arrays in one blob per
+// network at a fixed stride, then the FusedNet table that points into them.
+int upload_fold_nets(syldet *h, const std::vector<std::unique_ptr<OwnedConfig>> &cfgs)
+{
+    const size_t K = cfgs.size();
+    std::vector<FusedPlan> plans(K);
+    for (size_t k = 0; k < K; k++) {
+        if (!make_fused_plan(cfgs[k]->view, h->geom, plans[k]))
+            return fail(SYLDET_ERR_UNSUPPORTED, "fold kernel plan failed for network " + std::to_string(k) + ": " + plans[k].reason);
+        // (the shape is shared: compatible networks give the same layout)
+        const FusedDesc &a = plans[0].desc, &b = plans[k].desc;
+        if (a.s_ok != b.s_ok || a.s2_ok != b.s2_ok || a.s2_nt != b.s2_nt || a.s_padp != b.s_padp || a.s_cs8 != b.s_cs8 ||
+            a.s_waves != b.s_waves || a.s_lds_wave != b.s_lds_wave || a.col_shift != b.col_shift || a.H != b.H || a.norm != b.norm)
+            return fail(SYLDET_ERR_UNSUPPORTED, "network " + std::to_string(k) + " gives the fold kernel another shape");
+    }
+    auto pad = [](size_t b) { return (b + 255) / 256 * 256; };
+    const int n_thr = h->cfg.view.n_thresholds;
+    const FusedPlan &p0 = plans[0];
+    const size_t sz[10] = {p0.afrag_t.size() * 2, p0.afrag_w.size() * 2, p0.afrag_t2.size() * 2, p0.afrag_w2.size() * 2, p0.bias0.size() * 4,
+                           p0.rvec.size() * 4, p0.w1.size() * 4, p0.b1.size() * 4, p0.out_params.size() * 4, (size_t)n_thr * 8};
+    size_t off[10], stride = 0;
+    for (int i = 0; i < 10; i++) {
+        off[i] = stride;
+        stride += pad(std::max<size_t>(sz[i], 16));
+    }
+    std::vector<unsigned char> blob(stride * K + pad(K * sizeof(FusedNet)), 0);
+    for (size_t k = 0; k < K; k++) {
+        const FusedPlan &p = plans[k];
+        const void *src[10] = {p.afrag_t.data(), p.afrag_w.data(), p.afrag_t2.data(), p.afrag_w2.data(), p.bias0.data(),
+                               p.rvec.data(), p.w1.data(), p.b1.data(), p.out_params.data(), cfgs[k]->view.thresholds};
+        const size_t szk[10] = {p.afrag_t.size() * 2, p.afrag_w.size() * 2, p.afrag_t2.size() * 2, p.afrag_w2.size() * 2, p.bias0.size() * 4,
+                                p.rvec.size() * 4, p.w1.size() * 4, p.b1.size() * 4, p.out_params.size() * 4, (size_t)n_thr * 8};
+        for (int i = 0; i < 10; i++) {
+            if (szk[i] != sz[i]) return fail(SYLDET_ERR_UNSUPPORTED, "network " + std::to_string(k) + " gives the fold kernel tables of another size");
+            if (sz[i]) std::memcpy(blob.data() + k * stride + off[i], src[i], sz[i]);
+        }
+    }
+    if (int st = h->d_fnets.reserve(blob.size())) return st;
+    const unsigned char *base = (const unsigned char *)h->d_fnets.ptr;
+    FusedNet *tab = reinterpret_cast<FusedNet *>(blob.data() + stride * K);
+    for (size_t k = 0; k < K; k++) {
+        const unsigned char *nb = base + k * stride;
+        const FusedDesc &d = plans[k].desc;
+        FusedNet &t = tab[k];
+        t.afrag_t = (const uint4 *)(nb + off[0]);
+        t.afrag_w = (const uint4 *)(nb + off[1]);
+        t.afrag_t2 = (const uint4 *)(nb + off[2]);
+        t.afrag_w2 = (const uint4 *)(nb + off[3]);
+        t.bias0 = (const float *)(nb + off[4]);
+        t.rvec = (const float *)(nb + off[5]);
+        t.w1 = (const float *)(nb + off[6]);
+        t.b1 = (const float *)(nb + off[7]);
+        t.out_params = (const float *)(nb + off[8]);
+        t.thresholds = (const double *)(nb + off[9]);
+        t.w_unscale = d.w_unscale;
+        t.guard_r = d.guard_r;
+        t.guard_rel_r = d.guard_rel_r;
+        t.guard_range_r = d.guard_range_r;
+        t.guard_loud = d.guard_loud;
+        t.guard_se_abs_r = d.guard_se_abs_r;
+    }
+    SYLDET_HIP(hipMemcpy(h->d_fnets.ptr, blob.data(), blob.size(), hipMemcpyHostToDevice));
+    h->fnets = (const FusedNet *)(base + stride * K);
+    return SYLDET_OK;
+}
+
+// The generic engine's per-network parameter blobs and thresholds (the network stage and the exact recomputation read them).
+int upload_generic_nets(syldet *h, const std::vector<std::unique_ptr<OwnedConfig>> &cfgs)
+{
+    std::vector<float> all, blob;
+    std::vector<double> thr;
+    size_t stride = 0;
+    for (size_t k = 0; k < cfgs.size(); k++) {
+        NetDesc n;
+        if (int st = make_net_blob(cfgs[k]->view, h->geom, n, blob)) return st;
+        if (k == 0) stride = std::max<size_t>(blob.size(), 1);
+        if (blob.size() > stride) return fail(SYLDET_ERR_UNSUPPORTED, "network " + std::to_string(k) + " has a parameter blob of another size");
+        blob.resize(stride, 0.0f);
+        all.insert(all.end(), blob.begin(), blob.end());
+        thr.insert(thr.end(), cfgs[k]->view.thresholds, cfgs[k]->view.thresholds + cfgs[k]->view.n_thresholds);
+    }
+    if (stride > 0x7fffffff / cfgs.size()) return fail(SYLDET_ERR_UNSUPPORTED, "networks too large for one handle");
+    if (int st = h->d_params.reserve(all.size() * sizeof(float))) return st;
+    if (int st = h->d_thr.reserve(thr.size() * sizeof(double))) return st;
+    SYLDET_HIP(hipMemcpy(h->d_params.ptr, all.data(), all.size() * sizeof(float), hipMemcpyHostToDevice));
+    SYLDET_HIP(hipMemcpy(h->d_thr.ptr, thr.data(), thr.size() * sizeof(double), hipMemcpyHostToDevice));
+    h->net.params = (const float *)h->d_params.ptr;
+    h->net.thresholds = (const double *)h->d_thr.ptr;
+    h->net.params_stride = (int)stride;
+    h->net.thr_stride = h->cfg.view.n_thresholds;
     return SYLDET_OK;
 }
 
@@ -1001,6 +1145,118 @@ int syldet_create(const syldet_config_t *cfg, int32_t n_channels, int32_t device
     return SYLDET_OK;
 }
 
+int syldet_config_compatible(const syldet_config_t *a, const syldet_config_t *b, const char **field)
+{
+    if (field) *field = nullptr;
+    if (!a || !b) return fail(SYLDET_ERR_INVALID_ARGUMENT, "NULL argument");
+    for (const syldet_config_t *x : {a, b})
+        if ((x->n_input_fns > 0 && !x->input_fns) || (x->n_output_fns > 0 && !x->output_fns) || (x->n_layers > 0 && !x->layers))
+            return fail(SYLDET_ERR_INVALID_ARGUMENT, "NULL array in a configuration");
+    syldet_geometry_t ga{}, gb{};
+    if (int st = compute_geometry(*a, &ga)) return st;
+    if (int st = compute_geometry(*b, &gb)) return st;
+    // the first difference in the framing or the shape of the chain: its name (a static string) and, in the last error, where
+    auto differ = [field](const char *name, int index) {
+        if (field) *field = name;
+        set_error(index < 0 ? std::string("configurations differ in ") + name
+                            : std::string("configurations differ in ") + name + " (entry " + std::to_string(index) + ")");
+        return 0;
+    };
+    if (a->sampling_rate != b->sampling_rate) return differ("sampling_rate", -1);
+    if (a->fourier_length != b->fourier_length) return differ("fourier_length", -1);
+    if (a->window_length != b->window_length) return differ("window_length", -1);
+    if (a->window_overlap != b->window_overlap) return differ("window_overlap", -1);
+    if (a->time_range != b->time_range) return differ("time_range", -1);
+    if (ga.f0 != gb.f0 || ga.f1 != gb.f1) return differ("band", -1);          // freq_lo / freq_hi may differ, the bins they give may not
+    if (a->scaling != b->scaling) return differ("scaling", -1);
+    if (a->window != b->window) return differ("window", -1);
+    if (a->spectrum != b->spectrum) return differ("spectrum", -1);
+    if (a->rule != b->rule) return differ("rule", -1);
+    if (a->n_input_fns != b->n_input_fns) return differ("n_input_fns", -1);
+    for (int i = 0; i < a->n_input_fns; i++) {
+        if (a->input_fns[i].kind != b->input_fns[i].kind) return differ("input_fns.kind", i);
+    }
+    if (a->n_output_fns != b->n_output_fns) return differ("n_output_fns", -1);
+    for (int i = 0; i < a->n_output_fns; i++) {
+        if (a->output_fns[i].kind != b->output_fns[i].kind) return differ("output_fns.kind", i);
+    }
+    if (a->n_layers != b->n_layers) return differ("n_layers", -1);
+    for (int l = 0; l < a->n_layers; l++) {
+        if (a->layers[l].inputs != b->layers[l].inputs) return differ("layers.inputs", l);
+        if (a->layers[l].outputs != b->layers[l].outputs) return differ("layers.outputs", l);
+        if (a->layers[l].transfer != b->layers[l].transfer) return differ("layers.transfer", l);
+    }
+    if (a->n_thresholds != b->n_thresholds) return differ("n_thresholds", -1);
+    // (the functions' vector lengths follow from the layers: a valid configuration's maps have inputs / outputs entries)
+    return 1;
+}
+
+int syldet_create_multi(const syldet_config_t *const *cfgs, int32_t n_nets, const int32_t *channel_net, int32_t n_channels,
+                        int32_t device, int32_t engine, syldet_t **out)
+{
+    if (!cfgs || !channel_net || !out) return fail(SYLDET_ERR_INVALID_ARGUMENT, "NULL argument");
+    *out = nullptr;
+    if (n_nets < 1) return fail(SYLDET_ERR_INVALID_ARGUMENT, "n_nets must be >= 1");
+    if (n_channels <= 0 || n_channels > 65535) return fail(SYLDET_ERR_INVALID_ARGUMENT, "n_channels must be in [1, 65535]");
+    if (engine != SYLDET_ENGINE_AUTO && engine != SYLDET_ENGINE_GENERIC && engine != SYLDET_ENGINE_FUSED && engine != SYLDET_ENGINE_WIDE_BF16)
+        return fail(SYLDET_ERR_INVALID_ARGUMENT, "unknown engine");
+    for (int32_t i = 0; i < n_nets; i++)
+        if (!cfgs[i]) return fail(SYLDET_ERR_INVALID_ARGUMENT, "NULL configuration " + std::to_string(i));
+    for (int32_t c = 0; c < n_channels; c++)
+        if (channel_net[c] < 0 || channel_net[c] >= n_nets)
+            return fail(SYLDET_ERR_INVALID_ARGUMENT, "channel_net[" + std::to_string(c) + "] = " + std::to_string(channel_net[c]) + " is outside [0, n_nets)");
+    if (engine == SYLDET_ENGINE_WIDE_BF16) return fail(SYLDET_ERR_UNSUPPORTED, "the wide-network engine has no multi-network form");
+    std::vector<std::unique_ptr<OwnedConfig>> own;
+    syldet::Switches sw;
+    sw.read();
+    bool fold = true, fused_ok = true;
+    try {
+        for (int32_t i = 0; i < n_nets; i++) {
+            own.emplace_back(new OwnedConfig());
+            if (int st = own.back()->assign(*cfgs[i])) return st;
+            syldet_geometry_t g{};
+            if (int st = compute_geometry(own.back()->view, &g)) return st;
+            const char *field = nullptr;
+            const int cmp = syldet_config_compatible(cfgs[0], cfgs[i], &field);
+            if (cmp < 0) return cmp;
+            if (cmp == 0)
+                return fail(SYLDET_ERR_UNSUPPORTED, "network " + std::to_string(i) + " is not compatible with network 0: " + field +
+                                                        " differs (networks that differ there need a handle each)");
+            bool ok = false;
+            if (!takes_fold(own.back()->view, g, sw, ok)) fold = false;
+            if (!ok) fused_ok = false;
+        }
+    } catch (const std::bad_alloc &) {
+        return fail(SYLDET_ERR_OUT_OF_MEMORY, "out of memory");
+    }
+    // one network: exactly a syldet_create handle
+    if (n_nets == 1) return syldet_create(cfgs[0], n_channels, device, engine, out);
+    if (engine == SYLDET_ENGINE_FUSED && !fused_ok)
+        return fail(SYLDET_ERR_UNSUPPORTED, "fused engine on a multi-network handle: only the fold kernel has that form, and it does not take this shape");
+    const bool on_fold = engine == SYLDET_ENGINE_FUSED || (engine == SYLDET_ENGINE_AUTO && fold);
+    // network 0 makes the handle -- the device, the shape's tables, the streams -- on the fold kernel or on the generic engine
+    // exactly as SYLDET_ENGINE_GENERIC has it; the other networks' tables follow
+    syldet_t *raw = nullptr;
+    if (int st = syldet_create(cfgs[0], n_channels, device, on_fold ? engine : SYLDET_ENGINE_GENERIC, &raw)) return st;
+    std::unique_ptr<syldet, int (*)(syldet_t *)> h(raw, syldet_destroy);
+    if (on_fold && h->engine != SYLDET_ENGINE_FUSED) return fail(SYLDET_ERR_UNSUPPORTED, "the fold kernel did not take network 0");
+    try {
+        h->n_nets = n_nets;
+        h->net_of.assign(channel_net, channel_net + n_channels);
+        for (int32_t c = 0; c < n_channels; c++) h->chan_thr0.push_back(own[(size_t)channel_net[c]]->view.thresholds[0]);
+        if (int st = h->d_net_of.reserve((size_t)n_channels * sizeof(int))) return st;
+        SYLDET_HIP(hipMemcpy(h->d_net_of.ptr, h->net_of.data(), (size_t)n_channels * sizeof(int), hipMemcpyHostToDevice));
+        if (int st = upload_generic_nets(h.get(), own)) return st;
+        h->fused.desc.thresholds = h->net.thresholds;            // (network 0's, first in the table that replaced its own)
+        if (on_fold)
+            if (int st = upload_fold_nets(h.get(), own)) return st;
+    } catch (const std::bad_alloc &) {
+        return fail(SYLDET_ERR_OUT_OF_MEMORY, "out of memory");
+    }
+    *out = h.release();
+    return SYLDET_OK;
+}
+
 int syldet_destroy(syldet_t *h)
 {
     if (!h) return SYLDET_OK;
@@ -1012,7 +1268,7 @@ int syldet_destroy(syldet_t *h)
     for (hipEvent_t e : h->events)
         if (e) (void)hipEventDestroy(e);
     if (h->prof_items) (void)hipHostFree(h->prof_items);
-    for (DeviceBuffer *b : {&h->d_window, &h->d_tw, &h->d_sw, &h->d_params, &h->d_thr, &h->d_columns, &h->d_fused, &h->d_mlpx, &h->d_stamps, &h->d_fix, &h->d_ctab, &h->d_planar, &h->d_wide, &h->d_xn, &h->d_dft, &h->d_stage_in,
+    for (DeviceBuffer *b : {&h->d_window, &h->d_tw, &h->d_sw, &h->d_params, &h->d_thr, &h->d_columns, &h->d_fused, &h->d_mlpx, &h->d_stamps, &h->d_fix, &h->d_ctab, &h->d_planar, &h->d_wide, &h->d_xn, &h->d_dft, &h->d_net_of, &h->d_fnets, &h->d_stage_net, &h->d_stage_in,
                             &h->d_stage_out, &h->d_stage_flags, &h->d_stage_idx, &h->d_stage_cnt})
         b->release();
     h->p_stage_in.release();
@@ -1443,7 +1699,16 @@ static int pump_impl(syldet *h, const int32_t *channels, int32_t n, int64_t *que
             cs.copy_out(cs.head.load(std::memory_order_relaxed), in + k * (size_t)S, (size_t)S);
         }
         SYLDET_HIP(hipMemcpyAsync(h->d_stage_in.ptr, in, nc * (size_t)S * sizeof(float), hipMemcpyHostToDevice, h->stream));
-        if (int st = run_on_stream(h, (const float *)h->d_stage_in.ptr, S, S, (int)nc, (float *)h->d_stage_out.ptr, nullptr, h->stream))
+        // (a multi-network handle: the networks of the channels this launch carries, in its row order; the vector outlives the
+        // copy -- the stream is synchronised below)
+        std::vector<int> rows_net;
+        if (h->n_nets > 1) {
+            for (size_t k = 0; k < nc; k++) rows_net.push_back(h->net_of[(size_t)g.second[k]]);
+            if (int st = h->d_stage_net.reserve(nc * sizeof(int))) return st;
+            SYLDET_HIP(hipMemcpyAsync(h->d_stage_net.ptr, rows_net.data(), nc * sizeof(int), hipMemcpyHostToDevice, h->stream));
+        }
+        if (int st = run_on_stream(h, (const float *)h->d_stage_in.ptr, S, S, (int)nc, (float *)h->d_stage_out.ptr, nullptr, h->stream,
+                                   h->n_nets > 1 ? (const int *)h->d_stage_net.ptr : nullptr))
             return st;
         SYLDET_HIP(hipMemcpyAsync(outs, h->d_stage_out.ptr, nc * (size_t)E * (size_t)n_out * sizeof(float), hipMemcpyDeviceToHost,
                                   h->stream));
@@ -1522,7 +1787,8 @@ int syldet_last_detected(const syldet_t *h, int32_t channel)
     if (!h || channel < 0 || channel >= h->channels) return fail(SYLDET_ERR_INVALID_ARGUMENT, "bad argument");
     ChannelStream &cs = *h->streams[(size_t)channel];
     std::lock_guard<std::mutex> lock(cs.mu);
-    return (double)cs.last[0] >= h->cfg.view.thresholds[0] ? 1 : 0;   // SyllableDetector.swift:27-31
+    const double thr = h->chan_thr0.empty() ? h->cfg.view.thresholds[0] : h->chan_thr0[(size_t)channel];   // (the channel's own network)
+    return (double)cs.last[0] >= thr ? 1 : 0;   // SyllableDetector.swift:27-31
 }
 
 int syldet_seen_syllable(syldet_t *h, int32_t channel)

@@ -9,7 +9,7 @@ happens in libsyldet's HIP kernels; torch is used only for device memory and str
 from __future__ import annotations
 
 import ctypes as C
-from typing import List, Optional, Tuple
+from typing import List, Optional, Sequence, Tuple
 
 import numpy as np
 
@@ -35,6 +35,31 @@ class SyllableDetector:
         g = _abi.Geometry()
         check(_abi.lib.syldet_get_geometry(self._h, C.byref(g)))
         self.geometry = g
+
+    @classmethod
+    def multi(cls, configs: Sequence[SyllableDetectorConfig], channelNetworks, device: int = 0,
+              engine: int = _abi.ENGINE_AUTO) -> "SyllableDetector":
+        """One bank, a network per channel (syldet_create_multi; ProcessorBase.init, Processor.swift:50-86): channel c runs
+        configs[channelNetworks[c]].  The configurations must be compatible (configsCompatible); `config` is configs[0] and
+        `configs` the list."""
+        configs = list(configs)
+        nets = np.ascontiguousarray(channelNetworks, dtype=np.int32).reshape(-1)
+        self = cls.__new__(cls)
+        self.config = configs[0] if configs else None
+        self.configs = configs
+        self.channelNetworks = nets.copy()
+        self.channels = int(nets.size)
+        self.device = int(device)
+        self._h = _abi.Handle()
+        abi = [cfg.to_abi() for cfg in configs]
+        ptrs = (_abi.Config_p * max(1, len(abi)))(*[C.pointer(c) for c, _ in abi])
+        check(_abi.lib.syldet_create_multi(ptrs, len(abi), nets.ctypes.data_as(_abi.c_int32_p), self.channels, self.device,
+                                           int(engine), C.byref(self._h)))
+        del abi                       # the library copied every array
+        g = _abi.Geometry()
+        check(_abi.lib.syldet_get_geometry(self._h, C.byref(g)))
+        self.geometry = g
+        return self
 
     @classmethod
     def borrowed(cls, bank, shard: int) -> "SyllableDetector":
@@ -294,3 +319,14 @@ class SyllableDetector:
         check(_abi.lib.syldet_detections(self._h, f.ctypes.data_as(_abi.c_uint8_p), E, float(debounce),
                                          idx.ctypes.data_as(_abi.c_int64_p), cap, cnt.ctypes.data_as(_abi.c_int64_p)))
         return idx, cnt
+
+
+def configsCompatible(a: SyllableDetectorConfig, b: SyllableDetectorConfig) -> Tuple[bool, Optional[str]]:
+    """syldet_config_compatible: may a and b share one SyllableDetector.multi bank?  (True, None), or (False, the first field
+    that differs)."""
+    ca, ka = a.to_abi()
+    cb, kb = b.to_abi()
+    field = C.c_char_p()
+    r = check(_abi.lib.syldet_config_compatible(C.byref(ca), C.byref(cb), C.byref(field)))
+    del ka, kb
+    return (True, None) if r == 1 else (False, field.value.decode() if field.value else None)

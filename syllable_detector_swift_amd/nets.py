@@ -5,7 +5,8 @@
   mapminmax) re-encoded as arrays in tests/golden/sample_net.npz by tests/golden/make_golden.py;
 - `config3`: synthetic N=W=1024, overlap 768 (hop 256), 1160 -> 4 -> 1 (BASELINE config 3);
 - `wide_mlp`: sample front-end with a 290 -> 4096 -> 1 network (BASELINE config 5);
-- `variant`: small edits of a configuration for parity cases.
+- `variant`: small edits of a configuration for parity cases;
+- `perturbed`: the same structure with other weights, map parameters and thresholds (networks for a multi-network bank).
 """
 from __future__ import annotations
 
@@ -106,6 +107,28 @@ def variant(base: SyllableDetectorConfig, **changes) -> SyllableDetectorConfig:
         if not hasattr(cfg, k):
             raise AttributeError(k)
         setattr(cfg, k, v)
+    return cfg
+
+
+def perturbed(base: SyllableDetectorConfig, seed: int, scale: float = 0.1) -> SyllableDetectorConfig:
+    """A network trained with the same settings on another bird, as far as the shape goes: `base` with every layer's weights
+    and biases, every map's offsets, gains and y, and the thresholds moved by seeded noise (compatible with `base`:
+    syldet_config_compatible)."""
+    rng = np.random.default_rng(seed)
+    cfg = copy.deepcopy(base)
+
+    def move(a):
+        a = np.asarray(a, np.float32)
+        return (a * (1.0 + scale * rng.standard_normal(a.shape)) + 0.1 * scale * rng.standard_normal(a.shape)).astype(np.float32)
+    for L in cfg.net.layers:
+        L.weights = move(L.weights)
+        L.biases = move(L.biases)
+    for f in list(cfg.net.inputProcessing) + list(cfg.net.outputProcessing):
+        if f.function in ("mapminmax", "mapstd"):
+            f.xOffsets = move(f.xOffsets)
+            f.gains = move(f.gains)
+            f.y = float(f.y + scale * rng.standard_normal())
+    cfg.thresholds = [float(t + scale * rng.standard_normal()) for t in cfg.thresholds]
     return cfg
 
 
