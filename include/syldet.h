@@ -194,6 +194,36 @@ int syldet_create_multi(const syldet_config_t *const *cfgs, int32_t n_nets, cons
  * string such as "time_range" or "layers.outputs"), < 0 = status (NULL argument, or a configuration syldet_create refuses) */
 int syldet_config_compatible(const syldet_config_t *a, const syldet_config_t *b, const char **field);
 
+/* ---- one bank, networks of different bands and shapes (a mixed bank) ----
+ * The same contract as syldet_create_multi -- channel c runs network cfgs[channel_net[c]] -- for networks that need only share
+ * the EVALUATION CLOCK (syldet_config_same_clock): sampling_rate, window_length, window_overlap, time_range and n_thresholds
+ * (the number of outputs).  Those fix gap, hop, first_index, syldet_count_evals and the [C][E][n_out] output layout, so every
+ * batch, streaming and detection entry point keeps its shapes.  Everything else may differ: fourier_length, the band (and so
+ * the bins and the first layer's inputs), scaling, window, spectrum, rule, the processing functions, the layers and all values
+ * -- ProcessorBase's rows each load their own trained file (Processor.swift:50-86, ViewControllerProcessor.swift:222-276).
+ * The library partitions the networks into CLASSES of compatible ones (syldet_config_compatible); each class runs exactly as a
+ * syldet_create_multi handle of its networks would -- the same engine choice under AUTO / GENERIC / FUSED, the same kernels,
+ * the same arithmetic -- reading the caller's rows where they are and writing each channel's results in place.  A batch call
+ * launches the classes one after another on the caller's stream; a streaming drain makes one H2D copy, the classes' launches,
+ * one D2H copy and one synchronisation per evaluation-count group.  Classes that would want an engine without a multi-network
+ * form (the wide engine, the matrix-core network stages) run on the generic engine, as syldet_create_multi does.
+ * Statuses: SYLDET_ERR_INVALID_ARGUMENT for a NULL pointer, n_nets < 1 or a channel_net entry outside [0, n_nets); a
+ * configuration syldet_create refuses, that status; SYLDET_ERR_UNSUPPORTED for a clock mismatch (syldet_last_error names the
+ * field), for WIDE_BF16, and for FUSED when a class does not take the fold kernel.  All of these before any device is touched.
+ * All networks compatible: exactly a syldet_create_multi handle (n_nets == 1: a syldet_create handle).
+ * syldet_get_geometry: the shared fields as usual; f0, f1, bins, inputs and engine are -1 where the classes differ
+ * (syldet_channel_geometry has each channel's own).  syldet_spectrogram* on a bank of more than one class is
+ * SYLDET_ERR_UNSUPPORTED (the columns are ragged).  Every other entry point works unchanged and answers each channel from its own
+ * network; syldet_fixup_stats sums the classes' recomputations.                                                             */
+int syldet_create_mixed(const syldet_config_t *const *cfgs, int32_t n_nets, const int32_t *channel_net, int32_t n_channels,
+                        int32_t device, int32_t engine, syldet_t **out);
+/* 1 = a and b share the evaluation clock and may share a mixed bank, 0 = they may not (*field names the first difference:
+ * "sampling_rate", "window_length", "window_overlap", "time_range" or "n_thresholds"), < 0 = status, as
+ * syldet_config_compatible */
+int syldet_config_same_clock(const syldet_config_t *a, const syldet_config_t *b, const char **field);
+/* The geometry of channel `channel`'s own network (its class's, on a mixed bank; the handle's, on any other) */
+int syldet_channel_geometry(const syldet_t *h, int32_t channel, syldet_geometry_t *out);
+
 int syldet_destroy(syldet_t *h);
 int syldet_get_geometry(const syldet_t *h, syldet_geometry_t *out);
 int32_t syldet_channels(const syldet_t *h);

@@ -92,6 +92,24 @@ public:
         check(syldet_create_multi(raw.data(), (int32_t)raw.size(), channelNet.data(), (int32_t)channelNet.size(), device, engine, &h_));
         check(syldet_get_geometry(h_, &geometry_));
     }
+    // networks that need only share the evaluation clock (syldet_create_mixed; ProcessorBase's rows each load their own file,
+    // ViewControllerProcessor.swift:222-276): channel c runs configs[channelNet[c]], whatever its band, FFT size, chain or widths
+    struct Mixed {};
+    SyllableDetectorBank(Mixed, const std::vector<const SyllableDetectorConfig *> &configs, const std::vector<int32_t> &channelNet,
+                         int device = 0, int engine = SYLDET_ENGINE_AUTO)
+    {
+        std::vector<const syldet_config_t *> raw;
+        for (const SyllableDetectorConfig *c : configs) raw.push_back(c ? c->raw() : nullptr);
+        check(syldet_create_mixed(raw.data(), (int32_t)raw.size(), channelNet.data(), (int32_t)channelNet.size(), device, engine, &h_));
+        check(syldet_get_geometry(h_, &geometry_));
+    }
+    // channel c's own network's geometry (its class's bins, inputs and engine on a mixed bank)
+    syldet_geometry_t channelGeometry(int32_t channel) const
+    {
+        syldet_geometry_t g;
+        check(syldet_channel_geometry(h_, channel, &g));
+        return g;
+    }
     ~SyllableDetectorBank() { syldet_destroy(h_); }
     SyllableDetectorBank(const SyllableDetectorBank &) = delete;
     SyllableDetectorBank &operator=(const SyllableDetectorBank &) = delete;

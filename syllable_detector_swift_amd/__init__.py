@@ -10,10 +10,11 @@ from .config import (InvalidValue, MismatchedLength, MissingValue, NeuralNet, Ne
                      ProcessingFunction, SyllableDetectorConfig, SyllableDetectorError, UnableToOpenPath,
                      createWindow, frequencyIndexRange)
 from .bank import PinnedArray, ShardedSyllableDetectorBank, shard_table
-from .detector import SyllableDetector, configsCompatible
+from .detector import SyllableDetector, configsCompatible, configsShareClock
 from .resampler import ResamplerLinear, deinterleave
 
 __all__ = ["SyllableDetector", "SyllableDetectorConfig", "NeuralNet", "NeuralNetLayer", "ProcessingFunction",
            "ParseError", "UnableToOpenPath", "MissingValue", "InvalidValue", "MismatchedLength",
            "SyllableDetectorError", "frequencyIndexRange", "createWindow", "ResamplerLinear", "deinterleave",
-           "ShardedSyllableDetectorBank", "PinnedArray", "shard_table", "configsCompatible"]
+           "ShardedSyllableDetectorBank", "PinnedArray", "shard_table", "configsCompatible",
+           "configsShareClock"]

@@ -101,6 +101,9 @@ SIGNATURES = {
     "syldet_create": (C.c_int, [Config_p, C.c_int32, C.c_int32, C.c_int32, C.POINTER(Handle)]),
     "syldet_create_multi": (C.c_int, [C.POINTER(Config_p), C.c_int32, c_int32_p, C.c_int32, C.c_int32, C.c_int32, C.POINTER(Handle)]),
     "syldet_config_compatible": (C.c_int, [Config_p, Config_p, C.POINTER(C.c_char_p)]),
+    "syldet_create_mixed": (C.c_int, [C.POINTER(Config_p), C.c_int32, c_int32_p, C.c_int32, C.c_int32, C.c_int32, C.POINTER(Handle)]),
+    "syldet_config_same_clock": (C.c_int, [Config_p, Config_p, C.POINTER(C.c_char_p)]),
+    "syldet_channel_geometry": (C.c_int, [Handle, C.c_int32, C.POINTER(Geometry)]),
     "syldet_destroy": (C.c_int, [Handle]),
     "syldet_get_geometry": (C.c_int, [Handle, C.POINTER(Geometry)]),
     "syldet_channels": (C.c_int32, [Handle]),

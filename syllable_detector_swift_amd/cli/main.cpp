@@ -34,7 +34,7 @@ void usage(FILE *to)
 {
     std::fprintf(to,
                  "Usage: syllable-detector-cli -n <net> [-a <audio>]... [-d <seconds>] [--device <k>] [--chunk <frames>] [--format <shortest|swift4>] [--probe]\n"
-                 "  -n, --net <net>:\n      Path to trained network file.\n"
+                 "  -n, --net <net>:\n      Path to trained network file.  Given k > 1 times: each file must have exactly k tracks, and track t runs network t (one mixed bank; the networks must share the sampling rate, window length, window overlap, time range and number of outputs).\n"
                  "  -a, --audio <audio>:\n      Path to the audio file to process.\n"
                  "  -d, --debounce <seconds>:\n      Number of seconds to debounce triggers.\n"
                  "      --device <k>:\n      HIP device to run on (default 0).\n"
@@ -87,8 +87,11 @@ struct DevBuf {
 
 struct Event { int64_t buffer; int channel; int64_t sample; int64_t eval; };
 
-int process_file(const std::string &path, const syldet_config_t *cfg, int device, double debounce_s, bool have_debounce, int64_t chunk)
+// cfgs: one network for every track, or (k > 1) network t for track t of a file of exactly k tracks, through one mixed bank
+// (syldet_create_mixed): the networks share the evaluation clock, so the events are found and printed as for one
+int process_file(const std::string &path, const std::vector<syldet_config_t *> &cfgs, int device, double debounce_s, bool have_debounce, int64_t chunk)
 {
+    const syldet_config_t *cfg = cfgs[0];
     wav::Info info;
     std::vector<float> frames;
     std::string err;
@@ -101,8 +104,15 @@ int process_file(const std::string &path, const syldet_config_t *cfg, int device
         std::fprintf(stderr, "No audio tracks found in %s.\n", path.c_str());
         return 1;
     }
+    if (cfgs.size() > 1 && (size_t)C != cfgs.size()) {
+        std::fprintf(stderr, "Unable to process %s: it has %d track(s), but %zu networks were given (one per track).\n", path.c_str(), C, cfgs.size());
+        return 1;
+    }
     syldet_t *h = nullptr;
-    if (int st = syldet_create(cfg, C, device, SYLDET_ENGINE_AUTO, &h)) {
+    std::vector<int32_t> track_net((size_t)C);
+    for (int t = 0; t < C; t++) track_net[(size_t)t] = t;
+    if (int st = cfgs.size() > 1 ? syldet_create_mixed(cfgs.data(), (int32_t)cfgs.size(), track_net.data(), C, device, SYLDET_ENGINE_AUTO, &h)
+                                 : syldet_create(cfg, C, device, SYLDET_ENGINE_AUTO, &h)) {
         std::fprintf(stderr, "Unable to create the detector: %s: %s\n", syldet_strerror(st), syldet_last_error());
         return 2;
     }
@@ -190,7 +200,7 @@ int process_file(const std::string &path, const syldet_config_t *cfg, int device
 
 int main(int argc, char **argv)
 {
-    std::string net;
+    std::vector<std::string> net;
     std::vector<std::string> audio;
     double debounce = 0.0;
     bool have_debounce = false, probe = false;
@@ -206,7 +216,7 @@ int main(int argc, char **argv)
     };
     for (int i = 1; i < argc; i++) {
         const std::string a = argv[i];
-        if (a == "-n" || a == "--net") net = value(i, "--net");
+        if (a == "-n" || a == "--net") net.push_back(value(i, "--net"));
         else if (a == "-a" || a == "--audio") audio.push_back(value(i, "--audio"));
         else if (a == "-d" || a == "--debounce") {
             const char *v = value(i, "--debounce");
@@ -249,19 +259,24 @@ int main(int argc, char **argv)
         usage(stdout);
         return kExUsage;
     }
-    syldet_config_t *cfg = nullptr;
-    if (int st = syldet_config_load_text(net.c_str(), &cfg)) {
-        std::fprintf(stderr, "Unable to load the network configuration: %s: %s\n", syldet_strerror(st), syldet_last_error());
-        return 1;
+    std::vector<syldet_config_t *> cfgs;
+    for (const std::string &n : net) {
+        syldet_config_t *cfg = nullptr;
+        if (int st = syldet_config_load_text(n.c_str(), &cfg)) {
+            std::fprintf(stderr, "Unable to load the network configuration: %s: %s\n", syldet_strerror(st), syldet_last_error());
+            for (syldet_config_t *c : cfgs) syldet_config_free(c);
+            return 1;
+        }
+        cfg->rule = SYLDET_RULE_ANY;                        // any output above its threshold, TrackDetector.swift:72-77
+        cfgs.push_back(cfg);
     }
-    cfg->rule = SYLDET_RULE_ANY;                            // any output above its threshold, TrackDetector.swift:72-77
     int rc = 0;
     for (const std::string &p : audio) {
         if (audio.size() > 1) std::printf("%s\n", p.c_str());   // main.swift:122-124
         std::fflush(stdout);
-        const int r = process_file(p, cfg, device, debounce, have_debounce, chunk);
+        const int r = process_file(p, cfgs, device, debounce, have_debounce, chunk);
         if (r == 2) rc = 2;                                 // device trouble is fatal for the exit code; an unreadable file is skipped
     }
-    syldet_config_free(cfg);
+    for (syldet_config_t *c : cfgs) syldet_config_free(c);
     return rc;
 }

@@ -20,6 +20,9 @@ struct StftDesc {
     const float *window;      // [W]
     const float2 *tw;         // [M/2]  e^{-2 pi i t / M}     (complex FFT stage twiddles)
     const float2 *sw;         // [M]    e^{-2 pi i k / N}     (real-split twiddles)
+    // mixed banks (syldet_create_mixed): channel c of the launch reads samples row row_of[c] of the bank; the columns stay
+    // [C][J][F] in launch order.  Null: row c.
+    const int *row_of;
 };
 
 struct DevFn {
@@ -47,7 +50,16 @@ struct NetDesc {
     // params_stride floats / thr_stride doubles apart (compatible networks have the same offsets); null for one network
     const int *net_of;
     int params_stride, thr_stride;
+    // mixed banks (syldet_create_mixed): channel c of the launch writes outputs and flags row row_of[c] of the bank (and the
+    // exact recomputation reads that samples row); its network stays net_of[c].  Null: row c.
+    const int *row_of;
 };
+
+// The bank row of a launch's channel c (a mixed bank's class launches: row_of, a uniform load), else c itself.
+__device__ __forceinline__ int bank_row(const int *row_of, int c)
+{
+    return row_of ? __builtin_amdgcn_readfirstlane(row_of[c]) : c;
+}
 
 // ---- generic engine (any power-of-two N, any processing chain, any layer sizes) ----
 // columns [C][J][F] <- samples [C][stride]
@@ -225,6 +237,7 @@ struct FusedNet {
 struct FusedMulti {             // (host side: what launch_fused hands the fold kernel's multi-network form)
     const FusedNet *nets;       // [networks]
     const int *net_of;          // [C]
+    const int *row_of;          // [C] the bank row of each launch channel (a mixed bank's class launch), or null: row c
 };
 
 // ---- first layer on the matrix cores for spectrograms already in HBM (kernels_mlpx.hip) --------------------

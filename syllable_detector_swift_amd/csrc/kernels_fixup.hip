@@ -68,7 +68,8 @@ fixup_kernel(const FixDesc fd, const NetDesc n, const float *__restrict__ sample
         int nframes = spect ? item.count : item.count + T - 1;
         if (first + nframes > J) nframes = (int)(J - first);
         if (nframes > kMaxFrames) nframes = kMaxFrames;       // (never: items hold at most kFixMaxCount)
-        const float *row = samples + (int64_t)c * stride + first * fd.hop + fd.gap;
+        const int rc = bank_row(n.row_of, c);           // (the bank row of a mixed bank's class launch; columns stay in launch order)
+        const float *row = samples + (int64_t)rc * stride + first * fd.hop + fd.gap;
         const int span = nframes > 0 ? (nframes - 1) * fd.hop + W : 0;
         __syncthreads();                                      // the previous item's columns and samples are no longer read
         for (int i = tid; i < span; i += kBlock) xs[i] = row[i];
@@ -102,8 +103,8 @@ fixup_kernel(const FixDesc fd, const NetDesc n, const float *__restrict__ sample
             const int64_t e = first + el;
             const bool valid = el < item.count && e < E;
             mlp_eval_wave(n, c, cols + (valid ? el : 0) * F, valid, bufA, bufB, lane,
-                          (valid && outputs) ? outputs + ((int64_t)c * E + e) * n.n_out : nullptr,
-                          (valid && flags) ? flags + (int64_t)c * E + e : nullptr);
+                          (valid && outputs) ? outputs + ((int64_t)rc * E + e) * n.n_out : nullptr,
+                          (valid && flags) ? flags + (int64_t)rc * E + e : nullptr);
         }
     }
     // the last workgroup out resets the list for the next launch (every workgroup has read the count by then) and keeps the

@@ -106,11 +106,15 @@ __device__ __forceinline__ void split2(float a, float b, unsigned &hi, unsigned 
 // MN: a multi-network handle (syldet_create_multi).  The workgroup's channel picks its network, nets[net_of[c]], once: a scalar
 // load of a uniform address, so the index and every table pointer derived from it stay in SGPRs (no waterfall loop), and the
 // network's first-layer fragments, biases, output stage, thresholds, weight scale and guard constants come from there instead of
-// from d.  Everything else in d is the shape, shared by compatible networks.  Without MN the two trailing arguments are unused.
+// from d.  Everything else in d is the shape, shared by compatible networks.  A mixed bank's class launch (syldet_create_mixed)
+// also passes row_of: the workgroup reads its samples from, and writes its outputs and flags to, bank row row_of[c] (one more
+// uniform scalar load); null, row c.  The precision guard's items keep c, the launch's channel.  Without MN the three trailing
+// arguments are unused.
 template <int K2, bool GEN, int HQ, int NW, int PADP = 0, bool F2 = false, int NT = 1, bool SPECT = false, bool MN = false>
 __global__ void __launch_bounds__(64 * NW, 1)
 fused_s_kernel(const FusedDesc d, const float *__restrict__ samples, int64_t stride, int64_t s_eff, int64_t E,
-               float *__restrict__ outputs, uint8_t *__restrict__ flags, const FusedNet *__restrict__ nets, const int *__restrict__ net_of)
+               float *__restrict__ outputs, uint8_t *__restrict__ flags, const FusedNet *__restrict__ nets, const int *__restrict__ net_of,
+               const int *__restrict__ row_of)
 {
     static_assert(!(MN && SPECT), "the spectrogram instantiation runs no network");
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -217,11 +221,12 @@ fused_s_kernel(const FusedDesc d, const float *__restrict__ samples, int64_t str
         for (int i = 0; i < 8; i++) gtab[i] = cre[i];
     }
 
-    const float *row = samples + (int64_t)c * stride;
+    const int rc = MN ? bank_row(row_of, c) : c;     // (the bank row: a mixed bank's class launch reads and writes in place)
+    const float *row = samples + (int64_t)rc * stride;
     const __amdgpu_buffer_rsrc_t in_rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(row), 0, (int)(s_eff * 4), 0x00020000);
     const __amdgpu_buffer_rsrc_t out_rs = __builtin_amdgcn_make_buffer_rsrc(
-        outputs ? outputs + (int64_t)c * E * n_out : nullptr, 0, outputs ? (int)(E * n_out * 4) : 0, 0x00020000);
-    const __amdgpu_buffer_rsrc_t flg_rs = __builtin_amdgcn_make_buffer_rsrc(flags ? flags + (int64_t)c * E : nullptr, 0, flags ? (int)E : 0, 0x00020000);
+        outputs ? outputs + (int64_t)rc * E * n_out : nullptr, 0, outputs ? (int)(E * n_out * 4) : 0, 0x00020000);
+    const __amdgpu_buffer_rsrc_t flg_rs = __builtin_amdgcn_make_buffer_rsrc(flags ? flags + (int64_t)rc * E : nullptr, 0, flags ? (int)E : 0, 0x00020000);
     const __amdgpu_buffer_rsrc_t spc_rs = __builtin_amdgcn_make_buffer_rsrc(
         SPECT ? d.spect_out + (int64_t)c * E * d.F : nullptr, 0, SPECT ? (int)(E * d.F * 4) : 0, 0x00020000);
 
@@ -1001,7 +1006,8 @@ hipError_t launch_one(const FusedDesc &d, const float *samples, int64_t stride, 
     dim3 grid((unsigned)((segs + kWaves - 1) / kWaves), (unsigned)C);
     const FusedNet *nets = MN ? mn->nets : nullptr;
     const int *net_of = MN ? mn->net_of : nullptr;
-    hipLaunchKernelGGL(kern, grid, dim3(64 * kWaves), (size_t)lds, stream, d, samples, stride, s_eff, E, outputs, flags, nets, net_of);
+    const int *row_of = MN ? mn->row_of : nullptr;
+    hipLaunchKernelGGL(kern, grid, dim3(64 * kWaves), (size_t)lds, stream, d, samples, stride, s_eff, E, outputs, flags, nets, net_of, row_of);
     return hipGetLastError();
 }
 

@@ -70,7 +70,7 @@ stft_r8_kernel(StftDesc d, const float *__restrict__ samples, int64_t stride, in
     const int wave = threadIdx.x / kWave, lane = threadIdx.x & (kWave - 1);
     float2 *buf = lds_all + wave * kR8Lds;
     const int c = blockIdx.y;
-    const float *chan = samples + (int64_t)c * stride;
+    const float *chan = samples + (int64_t)bank_row(d.row_of, c) * stride;
     float *cols = columns + (int64_t)c * J * d.F;
     const int hi3 = lane >> 3, lo3 = lane & 7;
     auto w1024 = [&](int idx) {                                   // e^{-2 pi i idx / 1024} from the half table
@@ -206,7 +206,7 @@ stft_generic_kernel(StftDesc d, const float *__restrict__ samples, int64_t strid
     const float2 *twp = tables_in_lds ? lds_tw : d.tw;
     const float2 *swp = tables_in_lds ? lds_sw : d.sw + d.f0;
     const float *winp = tables_in_lds ? lds_win : d.window;
-    const float *chan = samples + (int64_t)c * stride;
+    const float *chan = samples + (int64_t)bank_row(d.row_of, c) * stride;
     float *cols = columns + (int64_t)c * J * d.F;
 
     // a frame whose threads all sit in one wave needs no workgroup barrier: a wave's LDS operations execute in order
@@ -338,6 +338,7 @@ mlp_generic_kernel(NetDesc n, int F, const float *__restrict__ columns, int64_t 
     const int wave = threadIdx.x / kWave;
     const int lane = threadIdx.x & (kWave - 1);
     const int c = blockIdx.y;
+    const int rc = bank_row(n.row_of, c);                       // (outputs and flags: the bank row)
     float *bufA = smem + (size_t)wave * 2 * n.max_width;
     float *bufB = bufA + n.max_width;
     const float *cols = columns + (int64_t)c * J * F;
@@ -347,8 +348,8 @@ mlp_generic_kernel(NetDesc n, int F, const float *__restrict__ columns, int64_t 
         const bool valid = e < E;
         const float *src = cols + e * F;
 
-        mlp_eval_wave(n, c, src, valid, bufA, bufB, lane, outputs ? outputs + (((int64_t)c * E) + e) * n.n_out : nullptr,
-                      flags ? flags + (int64_t)c * E + e : nullptr);
+        mlp_eval_wave(n, c, src, valid, bufA, bufB, lane, outputs ? outputs + (((int64_t)rc * E) + e) * n.n_out : nullptr,
+                      flags ? flags + (int64_t)rc * E + e : nullptr);
     }
 }
 
@@ -370,6 +371,7 @@ mlp_small_kernel(NetDesc n, int F, const float *__restrict__ columns, int64_t J,
 {
     const int wave = threadIdx.x / kWave, lane = threadIdx.x & (kWave - 1);
     const int c = blockIdx.y;
+    const int rc = bank_row(n.row_of, c);                       // (outputs and flags: the bank row)
     const float *cols = columns + (int64_t)c * J * F;
     const float *P = net_params(n, c);
     const int I = n.I;
@@ -554,11 +556,11 @@ mlp_small_kernel(NetDesc n, int F, const float *__restrict__ columns, int64_t J,
                     const DevFn fn = net_fn(n, P, n.out_fns[q]);
                     v = (v - fn.y) / P[fn.gain + o] + P[fn.xoff + o];
                 }
-                if (lane == 0 && outputs) outputs[(((int64_t)c * E) + e) * n_out + o] = v;
+                if (lane == 0 && outputs) outputs[(((int64_t)rc * E) + e) * n_out + o] = v;
                 if (o == 0 || n.rule != 0) hit |= ((double)v >= thr[o]) ? 1 : 0;
             }
         }
-        if (lane == 0 && flags) flags[(int64_t)c * E + e] = hit;
+        if (lane == 0 && flags) flags[(int64_t)rc * E + e] = hit;
     }
 }
 
@@ -576,6 +578,7 @@ mlp_chain_kernel(NetDesc n, int F, const float *__restrict__ columns, int64_t J,
 {
     const int wave = threadIdx.x / kWave, lane = threadIdx.x & (kWave - 1);
     const int c = blockIdx.y;
+    const int rc = bank_row(n.row_of, c);                       // (outputs and flags: the bank row)
     const float *cols = columns + (int64_t)c * J * F;
     const float *P = net_params(n, c);
     const int I = n.I;
@@ -684,11 +687,11 @@ mlp_chain_kernel(NetDesc n, int F, const float *__restrict__ columns, int64_t J,
             if (o < n_out) {                                    // wave-uniform
                 float v = transfer(tf1, y[o] + b1[o]);         // vDSP_mmul, then the bias (NeuralNet.swift:366-377)
                 if (n.n_out_fns == 1) v = (v - oy) / og[o] + ox[o];   // reverse map, NeuralNet.swift:137-142 / :175-180
-                if (lane == 0 && outputs) outputs[(((int64_t)c * E) + e) * n_out + o] = v;
+                if (lane == 0 && outputs) outputs[(((int64_t)rc * E) + e) * n_out + o] = v;
                 if (o == 0 || any_rule) hit |= ((double)v >= (o == 0 ? thr0 : thr1)) ? 1 : 0;
             }
         }
-        if (lane == 0 && flags) flags[(int64_t)c * E + e] = hit;
+        if (lane == 0 && flags) flags[(int64_t)rc * E + e] = hit;
     }
 }
 

@@ -128,7 +128,7 @@ stft_lanes_kernel(StftDesc d, const float *__restrict__ samples, int64_t stride,
     const int b = lane & (P - 1), fw = lane >> L;
     f2 *buf = lds_all + wave * kScratch + fw * 9 * P;
     const int c = blockIdx.y;
-    const float *chan = samples + (int64_t)c * stride + d.gap;
+    const float *chan = samples + (int64_t)bank_row(d.row_of, c) * stride + d.gap;
     float *cols = columns + (int64_t)c * J * d.F;
     const int N = 2 * M;
     auto wN = [&](int idx) {                                    // e^{-2 pi i idx / N} from the half table sw[k], k < M

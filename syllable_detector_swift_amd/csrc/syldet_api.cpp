@@ -194,6 +194,19 @@ struct syldet {
     DeviceBuffer d_stage_net;         // [C] int: net_of of the channels one streaming launch carries
     const FusedNet *fnets = nullptr;  // (in d_fnets) null unless the handle runs the fold kernel's multi-network form
 
+    // mixed banks (syldet_create_mixed): networks that share the evaluation clock and may differ in anything else.  They fall
+    // into classes of compatible networks (syldet_config_compatible); each class is a handle of its own, in `classes`, made as
+    // syldet_create_multi would make one for that class's networks over its channels.  A batch call launches the classes one
+    // after another on the caller's stream, each reading and writing the bank's rows in place through its row table.  This
+    // handle keeps the clock (cfg and geom: the first class's network, the fields that differ between classes set to -1), the
+    // channels' streaming state, the stream and the profile.
+    std::vector<std::unique_ptr<syldet, int (*)(syldet_t *)>> classes;
+    std::vector<int> class_of, local_of;   // [C] a channel's class, and its index among that class's channels
+    // ... and in a class handle: its channels' bank rows, ascending, and the bank it belongs to (what the timers record into)
+    std::vector<int> rows;
+    DeviceBuffer d_row_of;            // [channels] int: rows
+    syldet *root = nullptr;
+
     std::vector<std::unique_ptr<ChannelStream>> streams;
     std::mutex pump_mu;               // the staging buffers and the stream below belong to one pump at a time
     PinnedBuffer p_stage_in, p_stage_out;
@@ -651,7 +664,7 @@ struct KernelTimer {
     syldet *h;
     hipStream_t stream;
     int slot = -1;
-    KernelTimer(syldet *h_, hipStream_t s, const char *name) : h(h_), stream(s)
+    KernelTimer(syldet *h_, hipStream_t s, const char *name) : h(h_->root ? h_->root : h_), stream(s)   // (a class handle: its bank's profile)
     {
         if (!h->profiling || h->prof_calls.empty()) return;
         syldet::ProfCall &pc = h->prof_calls[(size_t)h->prof_cur()];
@@ -678,8 +691,9 @@ struct KernelTimer {
 // spend ten times the fused kernel's time here: MEASUREMENTS R5.7).
 const char kFixupName[] = "fixup_kernel";
 template <class F>
-int timed_fixup(syldet *h, hipStream_t stream, FixList list, F launch)
+int timed_fixup(syldet *hc, hipStream_t stream, FixList list, F launch)
 {
+    syldet *h = hc->root ? hc->root : hc;             // (a class handle: its bank's profile)
     if (h->profiling && !h->prof_calls.empty() && list.counters) {
         if (h->prof_items_n < h->prof_depth) {
             // (the first profiled call since the history's depth grew: once, and nothing may still be writing the old array)
@@ -702,8 +716,9 @@ int timed_fixup(syldet *h, hipStream_t stream, FixList list, F launch)
 
 // samples -> [C][J][F] columns: the fused engine's DFT half where its shape allows (and the handle was not created
 // for the generic engine outright), the generic FFT otherwise
+// row_of: a mixed bank's class launch, channel c reads bank row row_of[c] (the generic FFT kernels only)
 int stft_on_stream(syldet *h, const float *d_samples, int64_t stride, int C, int64_t J, float *d_columns, hipStream_t stream,
-                   bool for_network = true)
+                   bool for_network = true, const int *row_of = nullptr)
 {
     // columns that go through log / dB keep the generic FFT: its error is relative to the frame, the block-floating-point
     // DFT's to the loudest sample of the 128-frame pass, and the logarithm turns relative error of weak bins into absolute
@@ -711,7 +726,7 @@ int stft_on_stream(syldet *h, const float *d_samples, int64_t stride, int C, int
     // ... and columns that meet a network without a normaliser in front keep it too (normalised_chain above); the wide engine
     // is bf16 behind either
     const bool level_input = for_network && !normalised_chain(h->cfg.view) && h->engine != SYLDET_ENGINE_WIDE_BF16 && h->engine_asked == SYLDET_ENGINE_AUTO;
-    if (h->has_dft && !log_input && !level_input && (uint64_t)J * (uint64_t)h->geom.bins * 4u < 0xFFFFFFF0ull) {
+    if (h->has_dft && !log_input && !level_input && !row_of && (uint64_t)J * (uint64_t)h->geom.bins * 4u < 0xFFFFFFF0ull) {
         FusedDesc d = h->dft.desc;
         fused_segmentation(d, J, C);
         d.spect_out = d_columns;
@@ -735,29 +750,43 @@ int stft_on_stream(syldet *h, const float *d_samples, int64_t stride, int C, int
         return timed_fixup(h, stream, d.fix, [&](const FixList &l) { return launch_fixup(h->fixd, h->net, d_samples, stride, J, 0, nullptr, nullptr, d_columns, l, stream); });
     }
 generic_transform:
-    if (!h->sw.no_stft_lanes && stft_lanes_applicable(h->stft, d_samples, stride)) {
+    StftDesc sd = h->stft;
+    sd.row_of = row_of;
+    if (!h->sw.no_stft_lanes && stft_lanes_applicable(sd, d_samples, stride)) {
         KernelTimer t(h, stream, "stft_lanes_kernel");
-        SYLDET_HIP(launch_stft_lanes(h->stft, d_samples, stride, C, J, d_columns, stream));
+        SYLDET_HIP(launch_stft_lanes(sd, d_samples, stride, C, J, d_columns, stream));
         return SYLDET_OK;
     }
     KernelTimer t(h, stream, "stft_generic_kernel");
-    SYLDET_HIP(launch_stft_generic(h->stft, d_samples, stride, C, J, d_columns, stream));
+    SYLDET_HIP(launch_stft_generic(sd, d_samples, stride, C, J, d_columns, stream));
     return SYLDET_OK;
 }
 
-// d_net_of: a multi-network handle's network of each of the C rows (null: the handle's own [C] table, rows = channels)
+// d_net_of: a multi-network handle's network of each of the C rows (null: the handle's own [C] table, rows = channels).
+// d_row_of: a mixed bank's class launch, the bank row of each of the C channels (null: row c).
 int run_on_stream(syldet *h, const float *d_samples, int64_t S, int64_t stride, int C, float *d_outputs,
-                  uint8_t *d_flags, hipStream_t stream, const int *d_net_of = nullptr)
+                  uint8_t *d_flags, hipStream_t stream, const int *d_net_of = nullptr, const int *d_row_of = nullptr)
 {
     const int64_t J = count_frames(h, S), E = count_evals(h, S);
     if (E <= 0) return SYLDET_OK;
     SYLDET_HIP(hipSetDevice(h->device));
-    h->prof_begin();
-    // the network stage's (and the exact recomputation's) view of the rows' networks
+    if (!h->root) h->prof_begin();                   // (a class handle's launches belong to its bank's call)
+    if (!h->classes.empty()) {
+        // a mixed bank over all its channels: each class in turn, in place through its row table
+        if (C != h->channels) return fail(SYLDET_ERR_INVALID_ARGUMENT, "a mixed bank's batch covers all its channels");
+        for (auto &k : h->classes)
+            if (int st = run_on_stream(k.get(), d_samples, S, stride, k->channels, d_outputs, d_flags, stream, nullptr, (const int *)k->d_row_of.ptr))
+                return st;
+        return SYLDET_OK;
+    }
+    // the network stage's (and the exact recomputation's) view of the rows' networks and of the bank's rows
     NetDesc net = h->net;
-    FusedMulti mn{h->fnets, nullptr};
+    net.row_of = d_row_of;
+    FusedMulti mn{h->fnets, nullptr, d_row_of};
     if (h->n_nets > 1) {
         net.net_of = mn.net_of = d_net_of ? d_net_of : (const int *)h->d_net_of.ptr;
+    } else if (h->fnets) {
+        mn.net_of = (const int *)h->d_net_of.ptr;     // (a mixed bank's one-network class on the fold kernel: all zeros)
     }
     const FusedMulti *mnp = h->fnets ? &mn : nullptr;
     // the fused kernel addresses a channel's results with 32-bit byte offsets; longer rows take the generic engine
@@ -784,7 +813,7 @@ int run_on_stream(syldet *h, const float *d_samples, int64_t S, int64_t stride, 
         const bool in_contract = ((h->cfg.view.scaling == SYLDET_SCALING_LINEAR && normalised_chain(h->cfg.view)) || choice == 2 || h->engine_asked == SYLDET_ENGINE_FUSED);
         if (!runnable || !in_contract) fused_route = false;
         // (a multi-network handle: only the fold kernel has the form; the diagnostic stamped builds are not for it)
-        if (h->n_nets > 1 && (choice != 2 || h->sw.fused_stamps)) fused_route = false;
+        if ((h->n_nets > 1 || h->fnets) && (choice != 2 || h->sw.fused_stamps)) fused_route = false;
     }
     if (fused_route) {
         // diagnostic only: SYLDET_FUSED_STAMPS=1 runs the stamped instantiation and prints where a
@@ -882,7 +911,7 @@ int run_on_stream(syldet *h, const float *d_samples, int64_t S, int64_t stride, 
         SYLDET_HIP(launch_fft1k_net(h->stft, h->mlpx.desc, d_samples, stride, C, J, E, d_outputs, d_flags, stream));
         return SYLDET_OK;
     }
-    if (int st = stft_on_stream(h, d_samples, stride, C, J, (float *)h->d_columns.ptr, stream)) return st;
+    if (int st = stft_on_stream(h, d_samples, stride, C, J, (float *)h->d_columns.ptr, stream, true, d_row_of)) return st;
     if (h->mlpx.ok && (uint64_t)E * 4u < 0xFFFFFFF0ull) {
         KernelTimer t(h, stream, "mlp_mfma_kernel");
         SYLDET_HIP(launch_mlpx(h->mlpx.desc, (const float *)h->d_columns.ptr, C, J, E, d_outputs, d_flags, stream));
@@ -1191,8 +1220,12 @@ int syldet_config_compatible(const syldet_config_t *a, const syldet_config_t *b,
     return 1;
 }
 
-int syldet_create_multi(const syldet_config_t *const *cfgs, int32_t n_nets, const int32_t *channel_net, int32_t n_channels,
-                        int32_t device, int32_t engine, syldet_t **out)
+// syldet_create_multi, and (mixed_class) the handle of one class of a mixed bank: the same engine choice and the same kernels,
+// but one network makes no plain handle there -- on the fold kernel it takes the multi-network form (the form with the row
+// table), and elsewhere the generic engine as SYLDET_ENGINE_GENERIC has it (the engines without a multi-network form have no
+// row table either).
+static int create_multi_impl(const syldet_config_t *const *cfgs, int32_t n_nets, const int32_t *channel_net, int32_t n_channels,
+                             int32_t device, int32_t engine, syldet_t **out, bool mixed_class)
 {
     if (!cfgs || !channel_net || !out) return fail(SYLDET_ERR_INVALID_ARGUMENT, "NULL argument");
     *out = nullptr;
@@ -1230,10 +1263,11 @@ int syldet_create_multi(const syldet_config_t *const *cfgs, int32_t n_nets, cons
         return fail(SYLDET_ERR_OUT_OF_MEMORY, "out of memory");
     }
     // one network: exactly a syldet_create handle
-    if (n_nets == 1) return syldet_create(cfgs[0], n_channels, device, engine, out);
+    if (n_nets == 1 && !mixed_class) return syldet_create(cfgs[0], n_channels, device, engine, out);
     if (engine == SYLDET_ENGINE_FUSED && !fused_ok)
         return fail(SYLDET_ERR_UNSUPPORTED, "fused engine on a multi-network handle: only the fold kernel has that form, and it does not take this shape");
     const bool on_fold = engine == SYLDET_ENGINE_FUSED || (engine == SYLDET_ENGINE_AUTO && fold);
+    if (n_nets == 1 && !on_fold) return syldet_create(cfgs[0], n_channels, device, SYLDET_ENGINE_GENERIC, out);
     // network 0 makes the handle -- the device, the shape's tables, the streams -- on the fold kernel or on the generic engine
     // exactly as SYLDET_ENGINE_GENERIC has it; the other networks' tables follow
     syldet_t *raw = nullptr;
@@ -1241,6 +1275,13 @@ int syldet_create_multi(const syldet_config_t *const *cfgs, int32_t n_nets, cons
     std::unique_ptr<syldet, int (*)(syldet_t *)> h(raw, syldet_destroy);
     if (on_fold && h->engine != SYLDET_ENGINE_FUSED) return fail(SYLDET_ERR_UNSUPPORTED, "the fold kernel did not take network 0");
     try {
+        if (n_nets == 1) {                                        // (a mixed bank's one-network class on the fold kernel)
+            if (int st = h->d_net_of.reserve((size_t)n_channels * sizeof(int))) return st;
+            SYLDET_HIP(hipMemset(h->d_net_of.ptr, 0, (size_t)n_channels * sizeof(int)));
+            if (int st = upload_fold_nets(h.get(), own)) return st;
+            *out = h.release();
+            return SYLDET_OK;
+        }
         h->n_nets = n_nets;
         h->net_of.assign(channel_net, channel_net + n_channels);
         for (int32_t c = 0; c < n_channels; c++) h->chan_thr0.push_back(own[(size_t)channel_net[c]]->view.thresholds[0]);
@@ -1254,6 +1295,172 @@ int syldet_create_multi(const syldet_config_t *const *cfgs, int32_t n_nets, cons
         return fail(SYLDET_ERR_OUT_OF_MEMORY, "out of memory");
     }
     *out = h.release();
+    return SYLDET_OK;
+}
+
+int syldet_create_multi(const syldet_config_t *const *cfgs, int32_t n_nets, const int32_t *channel_net, int32_t n_channels,
+                        int32_t device, int32_t engine, syldet_t **out)
+{
+    return create_multi_impl(cfgs, n_nets, channel_net, n_channels, device, engine, out, false);
+}
+
+int syldet_config_same_clock(const syldet_config_t *a, const syldet_config_t *b, const char **field)
+{
+    if (field) *field = nullptr;
+    if (!a || !b) return fail(SYLDET_ERR_INVALID_ARGUMENT, "NULL argument");
+    for (const syldet_config_t *x : {a, b})
+        if ((x->n_input_fns > 0 && !x->input_fns) || (x->n_output_fns > 0 && !x->output_fns) || (x->n_layers > 0 && !x->layers))
+            return fail(SYLDET_ERR_INVALID_ARGUMENT, "NULL array in a configuration");
+    syldet_geometry_t ga{}, gb{};
+    if (int st = compute_geometry(*a, &ga)) return st;
+    if (int st = compute_geometry(*b, &gb)) return st;
+    auto differ = [field](const char *name) {
+        if (field) *field = name;
+        set_error(std::string("configurations differ in ") + name + " (the evaluation clock)");
+        return 0;
+    };
+    // (these fix gap, hop, first_index, the evaluation count and the [C][E][n_out] layout; valid configurations have
+    // n_thresholds == the last layer's outputs)
+    if (a->sampling_rate != b->sampling_rate) return differ("sampling_rate");
+    if (a->window_length != b->window_length) return differ("window_length");
+    if (a->window_overlap != b->window_overlap) return differ("window_overlap");
+    if (a->time_range != b->time_range) return differ("time_range");
+    if (a->n_thresholds != b->n_thresholds || ga.outputs != gb.outputs) return differ("n_thresholds");
+    return 1;
+}
+
+int syldet_create_mixed(const syldet_config_t *const *cfgs, int32_t n_nets, const int32_t *channel_net, int32_t n_channels,
+                        int32_t device, int32_t engine, syldet_t **out)
+{
+    if (!cfgs || !channel_net || !out) return fail(SYLDET_ERR_INVALID_ARGUMENT, "NULL argument");
+    *out = nullptr;
+    if (n_nets < 1) return fail(SYLDET_ERR_INVALID_ARGUMENT, "n_nets must be >= 1");
+    if (n_channels <= 0 || n_channels > 65535) return fail(SYLDET_ERR_INVALID_ARGUMENT, "n_channels must be in [1, 65535]");
+    if (engine != SYLDET_ENGINE_AUTO && engine != SYLDET_ENGINE_GENERIC && engine != SYLDET_ENGINE_FUSED && engine != SYLDET_ENGINE_WIDE_BF16)
+        return fail(SYLDET_ERR_INVALID_ARGUMENT, "unknown engine");
+    for (int32_t i = 0; i < n_nets; i++)
+        if (!cfgs[i]) return fail(SYLDET_ERR_INVALID_ARGUMENT, "NULL configuration " + std::to_string(i));
+    for (int32_t c = 0; c < n_channels; c++)
+        if (channel_net[c] < 0 || channel_net[c] >= n_nets)
+            return fail(SYLDET_ERR_INVALID_ARGUMENT, "channel_net[" + std::to_string(c) + "] = " + std::to_string(channel_net[c]) + " is outside [0, n_nets)");
+    // every network valid on its own (syldet_create's statuses) and on network 0's clock
+    std::vector<int> cls((size_t)n_nets, -1), rep;          // a network's class; each class's first network
+    syldet::Switches sw;
+    sw.read();
+    try {
+        for (int32_t i = 0; i < n_nets; i++) {
+            OwnedConfig own;
+            if (int st = own.assign(*cfgs[i])) return st;
+            syldet_geometry_t g{};
+            if (int st = compute_geometry(own.view, &g)) return st;
+            const char *field = nullptr;
+            const int cmp = syldet_config_same_clock(cfgs[0], cfgs[i], &field);
+            if (cmp < 0) return cmp;
+            if (cmp == 0)
+                return fail(SYLDET_ERR_UNSUPPORTED, "network " + std::to_string(i) + " does not share network 0's evaluation clock: " + field +
+                                                        " differs (networks that differ there need a handle each)");
+            // the classes: syldet_config_compatible is field equality, so comparing with each class's first network partitions
+            for (size_t k = 0; k < rep.size() && cls[(size_t)i] < 0; k++)
+                if (syldet_config_compatible(cfgs[rep[k]], cfgs[i], nullptr) == 1) cls[(size_t)i] = (int)k;
+            if (cls[(size_t)i] < 0) {
+                cls[(size_t)i] = (int)rep.size();
+                rep.push_back(i);
+            }
+        }
+    } catch (const std::bad_alloc &) {
+        return fail(SYLDET_ERR_OUT_OF_MEMORY, "out of memory");
+    }
+    if (engine == SYLDET_ENGINE_WIDE_BF16) return fail(SYLDET_ERR_UNSUPPORTED, "the wide-network engine has no mixed-bank form");
+    // all compatible (one network included): exactly a syldet_create_multi handle
+    if (rep.size() == 1) return syldet_create_multi(cfgs, n_nets, channel_net, n_channels, device, engine, out);
+    // each class that has channels: its networks (in file order), the class-local network of each of its channels, its rows
+    struct Class { std::vector<int32_t> nets, local_net, rows; };
+    std::vector<Class> classes;
+    std::vector<int> slot(rep.size(), -1);                  // class -> index in `classes` (classes without channels are left out)
+    std::vector<int> class_of((size_t)n_channels), local_of((size_t)n_channels);
+    try {
+        for (int32_t c = 0; c < n_channels; c++) {
+            const int k = cls[(size_t)channel_net[c]];
+            if (slot[(size_t)k] < 0) {
+                slot[(size_t)k] = (int)classes.size();
+                classes.emplace_back();
+                for (int32_t i = 0; i < n_nets; i++)
+                    if (cls[(size_t)i] == k) classes.back().nets.push_back(i);
+            }
+            Class &cl = classes[(size_t)slot[(size_t)k]];
+            const int32_t ln = (int32_t)(std::find(cl.nets.begin(), cl.nets.end(), channel_net[c]) - cl.nets.begin());
+            class_of[(size_t)c] = slot[(size_t)k];
+            local_of[(size_t)c] = (int)cl.rows.size();
+            cl.local_net.push_back(ln);
+            cl.rows.push_back(c);
+        }
+        // FUSED: every class on the fold kernel, or nothing (refused before any device is touched)
+        if (engine == SYLDET_ENGINE_FUSED)
+            for (const Class &cl : classes)
+                for (int32_t i : cl.nets) {
+                    OwnedConfig own;
+                    if (int st = own.assign(*cfgs[i])) return st;
+                    syldet_geometry_t g{};
+                    if (int st = compute_geometry(own.view, &g)) return st;
+                    bool ok = false;
+                    (void)takes_fold(own.view, g, sw, ok);
+                    if (!ok)
+                        return fail(SYLDET_ERR_UNSUPPORTED, "fused engine on a mixed bank: network " + std::to_string(i) +
+                                                                "'s class does not take the fold kernel (the only fused kernel with a row table)");
+                }
+    } catch (const std::bad_alloc &) {
+        return fail(SYLDET_ERR_OUT_OF_MEMORY, "out of memory");
+    }
+    // the bank: the clock, the channels' streaming state, the stream (the first class's first network on the generic engine;
+    // its own tables are never launched)
+    syldet_t *raw = nullptr;
+    if (int st = syldet_create(cfgs[classes[0].nets[0]], n_channels, device, SYLDET_ENGINE_GENERIC, &raw)) return st;
+    std::unique_ptr<syldet, int (*)(syldet_t *)> h(raw, syldet_destroy);
+    try {
+        for (const Class &cl : classes) {
+            std::vector<const syldet_config_t *> cc;
+            for (int32_t i : cl.nets) cc.push_back(cfgs[i]);
+            syldet_t *kr = nullptr;
+            if (int st = create_multi_impl(cc.data(), (int32_t)cc.size(), cl.local_net.data(), (int32_t)cl.rows.size(), device, engine, &kr, true))
+                return st;
+            std::unique_ptr<syldet, int (*)(syldet_t *)> k(kr, syldet_destroy);
+            // (the classes launch on the bank's stream: no stream of their own)
+            if (k->stream) {
+                SYLDET_HIP(hipStreamDestroy(k->stream));
+                k->stream = nullptr;
+            }
+            k->root = h.get();
+            k->rows.assign(cl.rows.begin(), cl.rows.end());
+            if (int st = k->d_row_of.reserve(k->rows.size() * sizeof(int))) return st;
+            SYLDET_HIP(hipMemcpy(k->d_row_of.ptr, k->rows.data(), k->rows.size() * sizeof(int), hipMemcpyHostToDevice));
+            h->classes.push_back(std::move(k));
+        }
+        h->class_of = std::move(class_of);
+        h->local_of = std::move(local_of);
+        for (int32_t c = 0; c < n_channels; c++) h->chan_thr0.push_back(cfgs[channel_net[c]]->thresholds[0]);
+    } catch (const std::bad_alloc &) {
+        return fail(SYLDET_ERR_OUT_OF_MEMORY, "out of memory");
+    }
+    // what differs between the classes is -1 in the bank's geometry (syldet_channel_geometry has each channel's own)
+    syldet_geometry_t &g = h->geom;
+    g = h->classes[0]->geom;
+    for (const auto &k : h->classes) {
+        const syldet_geometry_t &o = k->geom;
+        if (o.f0 != g.f0) g.f0 = -1;
+        if (o.f1 != g.f1) g.f1 = -1;
+        if (o.bins != g.bins) g.bins = -1;
+        if (o.inputs != g.inputs) g.inputs = -1;
+        if (o.engine != g.engine) g.engine = -1;
+    }
+    *out = h.release();
+    return SYLDET_OK;
+}
+
+int syldet_channel_geometry(const syldet_t *h, int32_t channel, syldet_geometry_t *out)
+{
+    if (!h || !out) return fail(SYLDET_ERR_INVALID_ARGUMENT, "NULL argument");
+    if (channel < 0 || channel >= h->channels) return fail(SYLDET_ERR_INVALID_ARGUMENT, "channel outside the bank");
+    *out = h->classes.empty() ? h->geom : h->classes[(size_t)h->class_of[(size_t)channel]]->geom;
     return SYLDET_OK;
 }
 
@@ -1362,13 +1569,23 @@ int syldet_last_timings(syldet_t *h, double *milliseconds, const char **names, i
 int syldet_fixup_stats(syldet_t *h, int64_t *items, int32_t *overflow)
 {
     if (!h) return fail(SYLDET_ERR_INVALID_ARGUMENT, "NULL argument");
-    unsigned c[4] = {0, 0, 0, 0};
-    if (h->d_fix.ptr) {
-        SYLDET_HIP(hipSetDevice(h->device));
-        SYLDET_HIP(hipMemcpy(c, h->d_fix.ptr, sizeof(c), hipMemcpyDeviceToHost));
+    int64_t n = 0;
+    int32_t of = 0;
+    // (a mixed bank: its classes' lists, summed)
+    std::vector<syldet *> hs;
+    if (h->classes.empty()) hs.push_back(h);
+    for (auto &k : h->classes) hs.push_back(k.get());
+    for (syldet *x : hs) {
+        unsigned c[4] = {0, 0, 0, 0};
+        if (x->d_fix.ptr) {
+            SYLDET_HIP(hipSetDevice(x->device));
+            SYLDET_HIP(hipMemcpy(c, x->d_fix.ptr, sizeof(c), hipMemcpyDeviceToHost));
+        }
+        n += (int64_t)c[2];
+        of |= (int32_t)c[3];
     }
-    if (items) *items = (int64_t)c[2];
-    if (overflow) *overflow = (int32_t)c[3];
+    if (items) *items = n;
+    if (overflow) *overflow = of;
     return SYLDET_OK;
 }
 
@@ -1401,11 +1618,12 @@ int syldet_spectrogram_device(syldet_t *h, const float *d_samples, int64_t n_sam
                               float *d_columns, void *hip_stream)
 {
     if (int st = check_batch_args(h, d_samples, n_samples, channel_stride)) return st;
+    if (h->classes.size() > 1) return fail(SYLDET_ERR_UNSUPPORTED, "spectrogram of a mixed bank: its classes' columns are ragged");
     if (!d_columns) return fail(SYLDET_ERR_INVALID_ARGUMENT, "NULL argument");
     SYLDET_HIP(hipSetDevice(h->device));
     const int64_t J = count_frames(h, n_samples);
     h->prof_begin();
-    return stft_on_stream(h, d_samples, channel_stride, h->channels, J, d_columns, (hipStream_t)hip_stream, false);
+    return stft_on_stream(h->classes.empty() ? h : h->classes[0].get(), d_samples, channel_stride, h->channels, J, d_columns, (hipStream_t)hip_stream, false);
 }
 
 int syldet_detections_device(syldet_t *h, const uint8_t *d_flags, int64_t n_evals, double debounce_seconds,
@@ -1574,21 +1792,23 @@ int syldet_run_interleaved(syldet_t *h, const float *interleaved, int64_t n_fram
 int syldet_spectrogram(syldet_t *h, const float *samples, int64_t n_samples, int64_t channel_stride, float *columns)
 {
     if (int st = check_batch_args(h, samples, n_samples, channel_stride)) return st;
+    if (h->classes.size() > 1) return fail(SYLDET_ERR_UNSUPPORTED, "spectrogram of a mixed bank: its classes' columns are ragged");
     if (!columns) return fail(SYLDET_ERR_INVALID_ARGUMENT, "NULL argument");
     std::lock_guard<std::mutex> staging(h->pump_mu);   // the staging buffers and h->stream: one user at a time
     SYLDET_HIP(hipSetDevice(h->device));
     const int C = h->channels;
     const int64_t J = count_frames(h, n_samples);
     if (J <= 0) return SYLDET_OK;
+    syldet *sh = h->classes.empty() ? h : h->classes[0].get();    // (the one class of a mixed bank that has one)
     const size_t in_bytes = (size_t)C * (size_t)n_samples * sizeof(float);
-    const size_t col_bytes = (size_t)C * (size_t)J * (size_t)h->geom.bins * sizeof(float);
+    const size_t col_bytes = (size_t)C * (size_t)J * (size_t)sh->geom.bins * sizeof(float);
     if (int st = h->d_stage_in.reserve(in_bytes)) return st;
     if (int st = h->d_columns.reserve(col_bytes)) return st;
     SYLDET_HIP(hipMemcpy2DAsync(h->d_stage_in.ptr, (size_t)n_samples * sizeof(float), samples,
                                 (size_t)channel_stride * sizeof(float), (size_t)n_samples * sizeof(float), (size_t)C,
                                 hipMemcpyHostToDevice, h->stream));
     h->prof_begin();
-    if (int st = stft_on_stream(h, (const float *)h->d_stage_in.ptr, n_samples, C, J, (float *)h->d_columns.ptr, h->stream, false)) return st;
+    if (int st = stft_on_stream(sh, (const float *)h->d_stage_in.ptr, n_samples, C, J, (float *)h->d_columns.ptr, h->stream, false)) return st;
     SYLDET_HIP(hipMemcpyAsync(columns, h->d_columns.ptr, col_bytes, hipMemcpyDeviceToHost, h->stream));
     SYLDET_HIP(hipStreamSynchronize(h->stream));
     return SYLDET_OK;
@@ -1686,30 +1906,57 @@ static int pump_impl(syldet *h, const int32_t *channels, int32_t n, int64_t *que
     }
     if (groups.empty()) return SYLDET_OK;
     SYLDET_HIP(hipSetDevice(h->device));
+    const bool mixed = !h->classes.empty();
     for (auto &g : groups) {
         const int64_t E = g.first, S = frame + (E + h->cfg.view.time_range - 2) * hop;   // samples E evaluations span
         const size_t nc = g.second.size();
-        if (int st = h->p_stage_in.reserve(nc * (size_t)S * sizeof(float))) return st;
+        // a mixed bank: the group's rows ordered by class, so that each class's launch reads and writes a contiguous slice; the
+        // class-local networks of the rows travel behind the samples in the same copy
+        const size_t tab = mixed ? nc * sizeof(int) : 0;
+        if (mixed) std::stable_sort(g.second.begin(), g.second.end(), [h](int32_t a, int32_t b) { return h->class_of[(size_t)a] < h->class_of[(size_t)b]; });
+        if (int st = h->p_stage_in.reserve(nc * (size_t)S * sizeof(float) + tab)) return st;
         if (int st = h->p_stage_out.reserve(nc * (size_t)E * (size_t)n_out * sizeof(float))) return st;
-        if (int st = h->d_stage_in.reserve(nc * (size_t)S * sizeof(float))) return st;
+        if (int st = h->d_stage_in.reserve(nc * (size_t)S * sizeof(float) + tab)) return st;
         if (int st = h->d_stage_out.reserve(nc * (size_t)E * (size_t)n_out * sizeof(float))) return st;
         float *in = (float *)h->p_stage_in.ptr, *outs = (float *)h->p_stage_out.ptr;
         for (size_t k = 0; k < nc; k++) {
             const ChannelStream &cs = *h->streams[(size_t)g.second[k]];
             cs.copy_out(cs.head.load(std::memory_order_relaxed), in + k * (size_t)S, (size_t)S);
         }
-        SYLDET_HIP(hipMemcpyAsync(h->d_stage_in.ptr, in, nc * (size_t)S * sizeof(float), hipMemcpyHostToDevice, h->stream));
-        // (a multi-network handle: the networks of the channels this launch carries, in its row order; the vector outlives the
-        // copy -- the stream is synchronised below)
-        std::vector<int> rows_net;
-        if (h->n_nets > 1) {
-            for (size_t k = 0; k < nc; k++) rows_net.push_back(h->net_of[(size_t)g.second[k]]);
-            if (int st = h->d_stage_net.reserve(nc * sizeof(int))) return st;
-            SYLDET_HIP(hipMemcpyAsync(h->d_stage_net.ptr, rows_net.data(), nc * sizeof(int), hipMemcpyHostToDevice, h->stream));
+        if (mixed) {
+            int *nets = reinterpret_cast<int *>(in + nc * (size_t)S);
+            for (size_t k = 0; k < nc; k++) {
+                const syldet &cl = *h->classes[(size_t)h->class_of[(size_t)g.second[k]]];
+                nets[k] = cl.n_nets > 1 ? cl.net_of[(size_t)h->local_of[(size_t)g.second[k]]] : 0;
+            }
+            SYLDET_HIP(hipMemcpyAsync(h->d_stage_in.ptr, in, nc * (size_t)S * sizeof(float) + tab, hipMemcpyHostToDevice, h->stream));
+            h->prof_begin();                                         // (one call: every class's launches)
+            const int *d_nets = reinterpret_cast<const int *>((const float *)h->d_stage_in.ptr + nc * (size_t)S);
+            for (size_t k0 = 0; k0 < nc;) {
+                const int cls = h->class_of[(size_t)g.second[k0]];
+                size_t k1 = k0;
+                while (k1 < nc && h->class_of[(size_t)g.second[k1]] == cls) k1++;
+                syldet *cl = h->classes[(size_t)cls].get();
+                if (int st = run_on_stream(cl, (const float *)h->d_stage_in.ptr + k0 * (size_t)S, S, S, (int)(k1 - k0),
+                                           (float *)h->d_stage_out.ptr + k0 * (size_t)E * (size_t)n_out, nullptr, h->stream,
+                                           cl->n_nets > 1 ? d_nets + k0 : nullptr))
+                    return st;
+                k0 = k1;
+            }
+        } else {
+            SYLDET_HIP(hipMemcpyAsync(h->d_stage_in.ptr, in, nc * (size_t)S * sizeof(float), hipMemcpyHostToDevice, h->stream));
+            // (a multi-network handle: the networks of the channels this launch carries, in its row order; the vector outlives the
+            // copy -- the stream is synchronised below)
+            std::vector<int> rows_net;
+            if (h->n_nets > 1) {
+                for (size_t k = 0; k < nc; k++) rows_net.push_back(h->net_of[(size_t)g.second[k]]);
+                if (int st = h->d_stage_net.reserve(nc * sizeof(int))) return st;
+                SYLDET_HIP(hipMemcpyAsync(h->d_stage_net.ptr, rows_net.data(), nc * sizeof(int), hipMemcpyHostToDevice, h->stream));
+            }
+            if (int st = run_on_stream(h, (const float *)h->d_stage_in.ptr, S, S, (int)nc, (float *)h->d_stage_out.ptr, nullptr, h->stream,
+                                       h->n_nets > 1 ? (const int *)h->d_stage_net.ptr : nullptr))
+                return st;
         }
-        if (int st = run_on_stream(h, (const float *)h->d_stage_in.ptr, S, S, (int)nc, (float *)h->d_stage_out.ptr, nullptr, h->stream,
-                                   h->n_nets > 1 ? (const int *)h->d_stage_net.ptr : nullptr))
-            return st;
         SYLDET_HIP(hipMemcpyAsync(outs, h->d_stage_out.ptr, nc * (size_t)E * (size_t)n_out * sizeof(float), hipMemcpyDeviceToHost,
                                   h->stream));
         SYLDET_HIP(hipStreamSynchronize(h->stream));

@@ -42,6 +42,19 @@ class SyllableDetector:
         """One bank, a network per channel (syldet_create_multi; ProcessorBase.init, Processor.swift:50-86): channel c runs
         configs[channelNetworks[c]].  The configurations must be compatible (configsCompatible); `config` is configs[0] and
         `configs` the list."""
+        return cls._banked(_abi.lib.syldet_create_multi, configs, channelNetworks, device, engine)
+
+    @classmethod
+    def mixed(cls, configs: Sequence[SyllableDetectorConfig], channelNetworks, device: int = 0,
+              engine: int = _abi.ENGINE_AUTO) -> "SyllableDetector":
+        """One bank of networks that differ in band, FFT size, chain or widths (syldet_create_mixed): channel c runs
+        configs[channelNetworks[c]].  The configurations need only share the evaluation clock (configsShareClock); each class
+        of compatible ones runs as a multi bank of its own would.  `geometry` holds -1 where the classes differ
+        (channelGeometry(c) has each channel's own)."""
+        return cls._banked(_abi.lib.syldet_create_mixed, configs, channelNetworks, device, engine)
+
+    @classmethod
+    def _banked(cls, create, configs, channelNetworks, device, engine) -> "SyllableDetector":
         configs = list(configs)
         nets = np.ascontiguousarray(channelNetworks, dtype=np.int32).reshape(-1)
         self = cls.__new__(cls)
@@ -53,8 +66,7 @@ class SyllableDetector:
         self._h = _abi.Handle()
         abi = [cfg.to_abi() for cfg in configs]
         ptrs = (_abi.Config_p * max(1, len(abi)))(*[C.pointer(c) for c, _ in abi])
-        check(_abi.lib.syldet_create_multi(ptrs, len(abi), nets.ctypes.data_as(_abi.c_int32_p), self.channels, self.device,
-                                           int(engine), C.byref(self._h)))
+        check(create(ptrs, len(abi), nets.ctypes.data_as(_abi.c_int32_p), self.channels, self.device, int(engine), C.byref(self._h)))
         del abi                       # the library copied every array
         g = _abi.Geometry()
         check(_abi.lib.syldet_get_geometry(self._h, C.byref(g)))
@@ -75,6 +87,12 @@ class SyllableDetector:
         check(_abi.lib.syldet_get_geometry(self._h, C.byref(g)))
         self.geometry = g
         return self
+
+    def channelGeometry(self, channel: int):
+        """syldet_channel_geometry: the geometry of channel `channel`'s own network (bins, inputs, engine of its class)."""
+        g = _abi.Geometry()
+        check(_abi.lib.syldet_channel_geometry(self._h, int(channel), C.byref(g)))
+        return g
 
     def close(self):
         if getattr(self, "_h", None):
@@ -231,7 +249,8 @@ class SyllableDetector:
         self._check_samples(samples)
         S = int(samples.shape[1])
         J = self.countFrames(S)
-        cols = torch.empty((self.channels, J, self.geometry.bins), dtype=torch.float32, device=samples.device)
+        # (a mixed bank of several classes has no one bin count, -1: the library refuses the call)
+        cols = torch.empty((self.channels, J, max(self.geometry.bins, 0)), dtype=torch.float32, device=samples.device)
         check(_abi.lib.syldet_spectrogram_device(self._h, samples.data_ptr(), S, int(samples.stride(0)),
                                                  cols.data_ptr(), self._stream_ptr(stream)))
         return cols
@@ -305,7 +324,7 @@ class SyllableDetector:
         a = np.ascontiguousarray(samples, dtype=np.float32).reshape(self.channels, -1)
         S = a.shape[1]
         J = self.countFrames(S)
-        cols = np.zeros((self.channels, J, self.geometry.bins), np.float32)
+        cols = np.zeros((self.channels, J, max(self.geometry.bins, 0)), np.float32)
         check(_abi.lib.syldet_spectrogram(self._h, a.ctypes.data_as(_abi.c_float_p), S, S,
                                           cols.ctypes.data_as(_abi.c_float_p)))
         return cols
@@ -328,5 +347,16 @@ def configsCompatible(a: SyllableDetectorConfig, b: SyllableDetectorConfig) -> T
     cb, kb = b.to_abi()
     field = C.c_char_p()
     r = check(_abi.lib.syldet_config_compatible(C.byref(ca), C.byref(cb), C.byref(field)))
+    del ka, kb
+    return (True, None) if r == 1 else (False, field.value.decode() if field.value else None)
+
+
+def configsShareClock(a: SyllableDetectorConfig, b: SyllableDetectorConfig) -> Tuple[bool, Optional[str]]:
+    """syldet_config_same_clock: may a and b share one SyllableDetector.mixed bank?  (True, None), or (False, the first clock
+    field that differs)."""
+    ca, ka = a.to_abi()
+    cb, kb = b.to_abi()
+    field = C.c_char_p()
+    r = check(_abi.lib.syldet_config_same_clock(C.byref(ca), C.byref(cb), C.byref(field)))
     del ka, kb
     return (True, None) if r == 1 else (False, field.value.decode() if field.value else None)
