@@ -244,6 +244,23 @@ int syldet_run_device(syldet_t *h, const float *d_samples, int64_t n_samples, in
                       float *d_outputs, uint8_t *d_flags, void *hip_stream);
 int syldet_run(syldet_t *h, const float *samples, int64_t n_samples, int64_t channel_stride,
                float *outputs, uint8_t *flags);
+/* 16-bit PCM: samples [C][channel_stride] int16 (strides count elements), sample x meaning x / 32768 = float(x) * 2^-15 --
+ * the value a WAV reader or the reference's AVFoundation reader (32-bit float delivery) gives for it.  Each result is
+ * bit-identical to the fp32 twin's on the same handle fed float(x) * 2^-15 with the same strides: outputs, flags, detections and
+ * syldet_fixup_stats' item counts, on every engine and bank kind; the argument checks and statuses are the fp32 twin's, made
+ * before any device is touched.  Read natively (2 bytes a sample) by the fold kernel's twice-folded form on the plain ring
+ * with up to 4 hidden units -- the reference's 256-point framing wherever the plan keeps the plain sample ring (hop 128's
+ * staggered chunks and the padded ring of other multiples of 64 do not), any chain the fold kernel takes, plain, multi-network
+ * and mixed banks -- where the rows are whole 4-byte words (a 4-byte aligned base, an even stride); the exact recomputation
+ * reads them too.  Every other shape and layout is read once into a packed fp32 copy
+ * (syldet_timings lists "widen_s16_kernel", at most once a call) and runs the fp32 kernels on it.  That copy, C x S x 4 bytes,
+ * is scratch the handle keeps until it is destroyed and the fp32 call does not need: an s16 call may fail with
+ * SYLDET_ERR_OUT_OF_MEMORY where its fp32 twin succeeds.  syldet_run_s16 cuts the recording into the stages syldet_run would
+ * use and copies int16: half the bytes cross the bus.                                                                       */
+int syldet_run_device_s16(syldet_t *h, const int16_t *d_samples, int64_t n_samples, int64_t channel_stride,
+                          float *d_outputs, uint8_t *d_flags, void *hip_stream);
+int syldet_run_s16(syldet_t *h, const int16_t *samples, int64_t n_samples, int64_t channel_stride,
+                   float *outputs, uint8_t *flags);
 
 /* syldet_run cuts a long recording along time into stages of about 256 MiB of input and overlaps the H2D copy of the next
  * stage with the kernel of this one and the D2H copy of the last (device staging: two stages, whatever the length).
@@ -319,6 +336,11 @@ int syldet_append_interleaved(syldet_t *h, const float *data, int64_t n_frames, 
  * source_channel: syldet_channels(h) entries, each in [0, total_channels); a stream channel may feed several bank channels.    */
 int syldet_append_interleaved_channels(syldet_t *h, const float *data, int64_t n_frames, int32_t total_channels,
                                        const int32_t *source_channel);
+/* syldet_append / syldet_append_interleaved for 16-bit PCM: sample x goes into the fp32 ring as x * 2^-15 (exact), with the
+ * same checks and the same ring-full rule (the ring's room is counted in fp32 samples): every later result is the fp32
+ * appends' bit for bit.                                                                                                    */
+int syldet_append_s16(syldet_t *h, int32_t channel, const int16_t *data, int64_t n_samples);
+int syldet_append_interleaved_s16(syldet_t *h, const int16_t *data, int64_t n_frames, int32_t total_channels);
 /* processNewValue() -> Bool, SyllableDetector.swift:153-217: 1 = a new evaluation is in
  * last_outputs, 0 = not enough data yet                                                  */
 int syldet_process_new_value(syldet_t *h, int32_t channel);
@@ -352,6 +374,13 @@ int syldet_run_interleaved_device(syldet_t *h, const float *d_interleaved, int64
                                   float *d_outputs, uint8_t *d_flags, void *hip_stream);
 int syldet_run_interleaved(syldet_t *h, const float *interleaved, int64_t n_frames, int32_t total_channels,
                            float *outputs, uint8_t *flags);
+/* ... on 16-bit PCM frames [n_frames][total_channels] int16 (x meaning float(x) * 2^-15): de-interleaved on the device into
+ * int16 rows (2 bytes a sample), then exactly syldet_run_device_s16; the host form copies int16.  Bit-identical to the fp32
+ * twin fed float(x) * 2^-15, with its checks and statuses, made before any device is touched.                               */
+int syldet_run_interleaved_device_s16(syldet_t *h, const int16_t *d_interleaved, int64_t n_frames, int32_t total_channels,
+                                      float *d_outputs, uint8_t *d_flags, void *hip_stream);
+int syldet_run_interleaved_s16(syldet_t *h, const int16_t *interleaved, int64_t n_frames, int32_t total_channels,
+                               float *outputs, uint8_t *flags);
 
 /* ---- the exchange step of the multi-GPU path (no reference counterpart: the reference runs one process) ----
  * Channels shard across GPUs with no data-path collective; the one exchange is the gather of the detection

@@ -131,6 +131,30 @@ public:
     {
         check(syldet_run_device(h_, d_samples, n, stride, d_outputs, d_flags, hipStream));
     }
+    // 16-bit PCM (sample x = x / 32768): the same calls, bit for bit their results on float(x) * 2^-15, half the bytes in
+    void runPCM16(const int16_t *samples, int64_t n, std::vector<float> &outputs, std::vector<uint8_t> &flags)
+    {
+        const int64_t E = countEvaluations(n);
+        outputs.assign((size_t)channels() * (size_t)E * (size_t)geometry_.outputs, 0.0f);
+        flags.assign((size_t)channels() * (size_t)E, 0);
+        check(syldet_run_s16(h_, samples, n, n, outputs.data(), flags.data()));
+    }
+    void runDevicePCM16(const int16_t *d_samples, int64_t n, int64_t stride, float *d_outputs, uint8_t *d_flags, void *hipStream)
+    {
+        check(syldet_run_device_s16(h_, d_samples, n, stride, d_outputs, d_flags, hipStream));
+    }
+    // interleaved 16-bit PCM frames [frames][channels]
+    void runInterleavedPCM16(const int16_t *frames, int64_t n, std::vector<float> &outputs, std::vector<uint8_t> &flags)
+    {
+        const int64_t E = countEvaluations(n);
+        outputs.assign((size_t)channels() * (size_t)(E > 0 ? E : 0) * (size_t)geometry_.outputs, 0.0f);
+        flags.assign((size_t)channels() * (size_t)(E > 0 ? E : 0), 0);
+        check(syldet_run_interleaved_s16(h_, frames, n, channels(), outputs.data(), flags.data()));
+    }
+    void runInterleavedDevicePCM16(const int16_t *d_frames, int64_t n, float *d_outputs, uint8_t *d_flags, void *hipStream)
+    {
+        check(syldet_run_interleaved_device_s16(h_, d_frames, n, channels(), d_outputs, d_flags, hipStream));
+    }
     // live use: everything every channel has pending in one device round trip (the consumer loop of
     // Processor.swift:128-141 over all detectors); the detectors' processNewValue() then hand the results out
     int64_t processAll()
@@ -140,6 +164,7 @@ public:
         return queued;
     }
     void appendInterleavedData(const float *data, int64_t frames) { check(syldet_append_interleaved(h_, data, frames, channels())); }
+    void appendInterleavedDataPCM16(const int16_t *data, int64_t frames) { check(syldet_append_interleaved_s16(h_, data, frames, channels())); }
     // fromChannel / ofTotalChannels (CircularShortTimeFourierTransform.swift:203-217): the bank on a subset of a wider stream
     void appendInterleavedData(const float *data, int64_t frames, int32_t totalChannels, const int32_t *fromChannels)
     {
@@ -227,6 +252,7 @@ public:
     SyllableDetector(SyllableDetectorBank &bank, int channel) : bank_(bank), channel_(channel) {}
 
     void appendAudioData(const float *data, int64_t withSamples) { check(syldet_append(bank_.raw(), channel_, data, withSamples)); }
+    void appendAudioDataPCM16(const int16_t *data, int64_t withSamples) { check(syldet_append_s16(bank_.raw(), channel_, data, withSamples)); }
     bool processNewValue() { const int r = syldet_process_new_value(bank_.raw(), channel_); check(r); return r == 1; }
     std::vector<float> lastOutputs() const
     {

@@ -46,6 +46,7 @@ c_double_p = C.POINTER(C.c_double)
 c_uint8_p = C.POINTER(C.c_uint8)
 c_int64_p = C.POINTER(C.c_int64)
 c_int32_p = C.POINTER(C.c_int32)
+c_int16_p = C.POINTER(C.c_int16)
 
 
 class Fn(C.Structure):
@@ -111,6 +112,8 @@ SIGNATURES = {
     "syldet_count_evals": (C.c_int64, [Handle, C.c_int64]),
     "syldet_run_device": (C.c_int, [Handle, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
     "syldet_run": (C.c_int, [Handle, c_float_p, C.c_int64, C.c_int64, c_float_p, c_uint8_p]),
+    "syldet_run_device_s16": (C.c_int, [Handle, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "syldet_run_s16": (C.c_int, [Handle, c_int16_p, C.c_int64, C.c_int64, c_float_p, c_uint8_p]),
     "syldet_spectrogram_device": (C.c_int, [Handle, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p]),
     "syldet_spectrogram": (C.c_int, [Handle, c_float_p, C.c_int64, C.c_int64, c_float_p]),
     "syldet_detections_device": (C.c_int, [Handle, C.c_void_p, C.c_int64, C.c_double, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
@@ -124,6 +127,8 @@ SIGNATURES = {
     "syldet_append": (C.c_int, [Handle, C.c_int32, c_float_p, C.c_int64]),
     "syldet_append_interleaved": (C.c_int, [Handle, c_float_p, C.c_int64, C.c_int32]),
     "syldet_append_interleaved_channels": (C.c_int, [Handle, c_float_p, C.c_int64, C.c_int32, C.POINTER(C.c_int32)]),
+    "syldet_append_s16": (C.c_int, [Handle, C.c_int32, c_int16_p, C.c_int64]),
+    "syldet_append_interleaved_s16": (C.c_int, [Handle, c_int16_p, C.c_int64, C.c_int32]),
     "syldet_process_new_value": (C.c_int, [Handle, C.c_int32]),
     "syldet_process_all": (C.c_int, [Handle, c_int64_p]),
     "syldet_pending_evaluations": (C.c_int64, [Handle, C.c_int32]),
@@ -133,6 +138,8 @@ SIGNATURES = {
     "syldet_deinterleave_device": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p]),
     "syldet_run_interleaved_device": (C.c_int, [Handle, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
     "syldet_run_interleaved": (C.c_int, [Handle, c_float_p, C.c_int64, C.c_int32, c_float_p, c_uint8_p]),
+    "syldet_run_interleaved_device_s16": (C.c_int, [Handle, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "syldet_run_interleaved_s16": (C.c_int, [Handle, c_int16_p, C.c_int64, C.c_int32, c_float_p, c_uint8_p]),
     "syldet_pack_flags_device": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p]),
     "syldet_unpack_flags_device": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p]),
     "syldet_resampler_create": (C.c_int, [C.c_double, C.c_double, C.c_int32, C.c_int32, C.POINTER(Handle)]),

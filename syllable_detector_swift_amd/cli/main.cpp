@@ -5,6 +5,8 @@
 // :80,:99), a line with the file name first when more than one file is given (main.swift:122-124).
 // All tracks of a file are one batch on the GPU: decode -> H2D -> de-interleave [-> rate conversion when the
 // file's rate differs from the network's] -> fused STFT + network kernel -> flags/outputs -> host.
+// 16-bit PCM at the network's rate crosses the bus and is de-interleaved as int16 (the library's *_s16 entry points give
+// the fp32 path's bits on x / 32768, which is what the decoder would have produced).
 //
 // Differences a user can see: the reference decodes anything AVFoundation can, this tool reads WAV; the
 // reference has Core Audio deliver the network's rate (SyllableDetector.swift:19-23), this tool converts the decoded
@@ -94,8 +96,13 @@ int process_file(const std::string &path, const std::vector<syldet_config_t *> &
     const syldet_config_t *cfg = cfgs[0];
     wav::Info info;
     std::vector<float> frames;
+    std::vector<int16_t> frames16;
     std::string err;
-    if (!wav::read(path, info, frames, err)) {
+    // 16-bit PCM at the network's rate goes to the device as stored (syldet_run_interleaved_device_s16: the fp32 call's results
+    // on x / 32768, half the bytes); any other file is decoded to fp32 here
+    const bool pcm16 = wav::probe(path, info, err) && info.format == 1 && info.bits == 16 && info.rate == cfgs[0]->sampling_rate;
+    err.clear();
+    if (pcm16 ? !wav::read_s16(path, info, frames16, err) : !wav::read(path, info, frames, err)) {
         std::fprintf(stderr, "Unable to read %s: %s\n", path.c_str(), err.c_str());
         return 1;
     }
@@ -129,8 +136,9 @@ int process_file(const std::string &path, const std::vector<syldet_config_t *> &
         if (hipSetDevice(device) != hipSuccess || hipStreamCreate(&stream) != hipSuccess) { rc = 2; break; }
         const int64_t n = info.frames;
         DevBuf d_inter, d_planar, d_res, d_out, d_flags;
-        if (!d_inter.alloc((size_t)n * C * sizeof(float))) { rc = 2; break; }
-        if (hipMemcpyAsync(d_inter.p, frames.data(), (size_t)n * C * sizeof(float), hipMemcpyHostToDevice, stream) != hipSuccess) { rc = 2; break; }
+        const size_t in_bytes = (size_t)n * C * (pcm16 ? sizeof(int16_t) : sizeof(float));
+        if (!d_inter.alloc(in_bytes)) { rc = 2; break; }
+        if (hipMemcpyAsync(d_inter.p, pcm16 ? (const void *)frames16.data() : (const void *)frames.data(), in_bytes, hipMemcpyHostToDevice, stream) != hipSuccess) { rc = 2; break; }
         int64_t S = n, res_stride = 0;
         int st = 0;
         if (resample) {
@@ -150,7 +158,8 @@ int process_file(const std::string &path, const std::vector<syldet_config_t *> &
         E = syldet_count_evals(h, S);
         if (E <= 0) break;                                  // shorter than one evaluation: no events
         if (!d_out.alloc((size_t)C * E * n_out * sizeof(float)) || !d_flags.alloc((size_t)C * E)) { rc = 2; break; }
-        if (!resample) st = syldet_run_interleaved_device(h, (const float *)d_inter.p, n, C, (float *)d_out.p, (uint8_t *)d_flags.p, stream);
+        if (pcm16) st = syldet_run_interleaved_device_s16(h, (const int16_t *)d_inter.p, n, C, (float *)d_out.p, (uint8_t *)d_flags.p, stream);
+        else if (!resample) st = syldet_run_interleaved_device(h, (const float *)d_inter.p, n, C, (float *)d_out.p, (uint8_t *)d_flags.p, stream);
         else st = syldet_run_device(h, (const float *)d_res.p, S, res_stride, (float *)d_out.p, (uint8_t *)d_flags.p, stream);
         if (st) {
             std::fprintf(stderr, "Unable to process %s: %s: %s\n", path.c_str(), syldet_strerror(st), syldet_last_error());

@@ -2,7 +2,8 @@
 // audioSettings (SyllableDetector.swift:19-23: 32-bit float linear PCM) deliver in the reference, for
 // the container this image can decode without AVFoundation.  PCM 8/16/24/32-bit and IEEE float
 // 32/64-bit, plain or WAVE_FORMAT_EXTENSIBLE, any channel count.  Samples come back frame-major
-// (interleaved) as fp32 in [-1, 1): integer PCM is divided by 2^(bits-1), like Core Audio's converter.
+// (interleaved) as fp32 in [-1, 1): integer PCM is divided by 2^(bits-1), like Core Audio's converter; read_s16 gives 16-bit
+// PCM as stored.
 #pragma once
 
 #include <cstdint>
@@ -110,6 +111,25 @@ inline bool read(const std::string &path, Info &info, std::vector<float> &out, s
     } else {
         for (size_t i = 0; i < n; i++) out[i] = (float)((double)(int32_t)rd32(p + 4 * i) * (1.0 / 2147483648.0));
     }
+    return true;
+}
+
+// Reads every frame of a 16-bit PCM file as interleaved int16, as stored: sample x means x / 32768, the value read() gives
+// for it (the *_s16 entry points of the library take these and move half the bytes of fp32).
+inline bool read_s16(const std::string &path, Info &info, std::vector<int16_t> &out, std::string &err)
+{
+    if (!probe(path, info, err)) return false;
+    if (info.format != 1 || info.bits != 16) { err = "not 16-bit PCM"; return false; }
+    FILE *f = std::fopen(path.c_str(), "rb");
+    if (!f) { err = "cannot open file"; return false; }
+    const size_t n = (size_t)info.frames * (size_t)info.channels;
+    std::vector<unsigned char> raw(n * 2);
+    std::fseek(f, (long)info.data_offset, SEEK_SET);
+    const size_t got = std::fread(raw.data(), 1, raw.size(), f);
+    std::fclose(f);
+    if (got != raw.size()) { err = "truncated sample data"; return false; }
+    out.resize(n);
+    for (size_t i = 0; i < n; i++) out[i] = (int16_t)rd16(raw.data() + 2 * i);
     return true;
 }
 

@@ -292,6 +292,11 @@ hipError_t launch_convert_rate(const float *in, int64_t n_in, int64_t in_stride,
 // frame-major [n_frames][total] -> channel-major rows of channels first .. first+C-1
 hipError_t launch_deinterleave(const float *in, int64_t n_frames, int total, int first, int C, float *out,
                                int64_t out_stride, hipStream_t stream);
+// the same for 16-bit PCM: frame-major int16 [n_frames][total] -> int16 rows of channels 0 .. C-1
+hipError_t launch_deinterleave_s16(const int16_t *in, int64_t n_frames, int total, int C, int16_t *out, int64_t out_stride,
+                                   hipStream_t stream);
+// 16-bit PCM rows [C][in_stride] -> fp32 rows [C][out_stride] of x * 2^-15 (exact); out 16-byte aligned, out_stride % 4 == 0
+hipError_t launch_widen_s16(const int16_t *in, int64_t in_stride, int64_t S, int C, float *out, int64_t out_stride, hipStream_t stream);
 
 // detection flags <-> bits (bit b of byte t of a row = flag 8 t + b), rows padded to whole bytes
 hipError_t launch_pack_flags(const uint8_t *flags, int64_t rows, int64_t row_len, uint8_t *bits, hipStream_t stream);
@@ -307,8 +312,9 @@ hipError_t launch_unpack_flags_from(const FlagSources &from, int64_t rows, int64
                                     uint8_t *flags, hipStream_t stream);
 
 // mn: a multi-network handle's tables (only the fold kernel has that form: anything else is hipErrorInvalidValue)
+// s16: `samples` are int16 rows (16-bit PCM, x * 2^-15), only where fused_s_native_s16(d) and the fold kernel is chosen
 hipError_t launch_fused(const FusedDesc &d, const float *samples, int64_t stride, int C, int64_t S, int64_t J,
-                        int64_t E, float *outputs, uint8_t *flags, hipStream_t stream, const FusedMulti *mn = nullptr);
+                        int64_t E, float *outputs, uint8_t *flags, hipStream_t stream, const FusedMulti *mn = nullptr, bool s16 = false);
 int fused_choice(const FusedDesc &d, int64_t J);    // 0 the 8-wave kernel, 1 the register-resident-basis kernel, 2 the symmetric-fold kernel
 // the DFT front half alone: samples -> [C][J][F] columns; d: a plan for timeRange 1 with spect_out / spect_power set
 hipError_t launch_fused_spectrogram(const FusedDesc &d, const float *samples, int64_t stride, int C, int64_t J, hipStream_t stream);
@@ -324,7 +330,10 @@ hipError_t launch_fused_r(const FusedDesc &d, const float *samples, int64_t stri
 // the same contract on the symmetric-fold kernel; only called when fused_s_applicable(d)
 bool fused_s_applicable(const FusedDesc &d);
 hipError_t launch_fused_s(const FusedDesc &d, const float *samples, int64_t stride, int C, int64_t S, int64_t J,
-                          int64_t E, float *outputs, uint8_t *flags, hipStream_t stream, const FusedMulti *mn = nullptr);
+                          int64_t E, float *outputs, uint8_t *flags, hipStream_t stream, const FusedMulti *mn = nullptr, bool s16 = false);
+// Does the launcher run this plan on a form with a 16-bit PCM twin (the twice-folded form on the plain ring, one quad of units,
+// eight waves)?  The caller also needs rows of whole 4-byte words: int16 rows 4-byte aligned, an even stride, an even gap.
+bool fused_s_native_s16(const FusedDesc &d);
 // taps the register-resident first-layer fragments are instantiated for (0: timeRange too long)
 int fused_taps_max(int T);
 
@@ -334,6 +343,7 @@ struct FixDesc {
     int power_mode;             // spectrogram items: 0 |X| (extractPower), 1 |X|^2 (extractMagnitude)
     const float *window;        // [W] the fp32 window table (WindowType.createWindow)
     const double2 *ctab;        // [N] (cos, sin)(2 pi m / N)
+    int s16;                    // the samples are int16 rows (16-bit PCM: x * 2^-15, exact in fp64 as in fp32)
 };
 constexpr int kFixMaxCount = 16;            // evaluations (or frames) per work item
 // outputs [C][E][n_out], flags [C][E]: the listed evaluations are overwritten; columns [C][J][F]: the listed frames

@@ -1,8 +1,9 @@
 // kernels_aux.hip -- the two data-movement steps either side of the hot path:
 //   resample_linear_kernel   ResamplerLinear.resampleVector, Common/Resampler.swift:36-69
 //   deinterleave_kernel      appendInterleavedData's strided copy, Common/CircularShortTimeFourierTransform.swift:203-217,
-//                            for all channels of a frame-major buffer at once
-// Both are HBM-bound gathers: no matrix work, coalesced on the wide side, one pass over the data.
+//                            for all channels of a frame-major buffer at once (deinterleave_s16_kernel: the same for int16)
+//   widen_s16_kernel         16-bit PCM rows to the fp32 samples x * 2^-15 the batch engines read (the *_s16 entry points)
+// All are HBM-bound gathers: no matrix work, coalesced on the wide side, one pass over the data.
 //
 // gfx950 only.  wave = 64.
 
@@ -69,6 +70,60 @@ deinterleave_kernel(const float *__restrict__ in, int64_t n_frames, int total, i
     __syncthreads();
     for (int ch = 0; ch < nc; ch++)
         if (tid < nf) out[(int64_t)(c0 + ch) * out_stride + f0 + tid] = tile[tid][ch];
+}
+
+// The same tiling for 16-bit PCM: frame-major int16 in, planar int16 rows out (2 bytes a sample both ways).  The tile keeps
+// the samples as ints, so its LDS layout and bank pattern are deinterleave_kernel's.
+__global__ void __launch_bounds__(256)
+deinterleave_s16_kernel(const int16_t *__restrict__ in, int64_t n_frames, int total, int C, int16_t *__restrict__ out,
+                        int64_t out_stride)
+{
+    __shared__ int tile[kTileFrames][kTileCh + 1];
+    const int64_t f0 = (int64_t)blockIdx.x * kTileFrames;
+    const int c0 = blockIdx.y * kTileCh;
+    const int nc = min(kTileCh, C - c0);
+    const int tid = threadIdx.x;
+    const int nf = (int)min((int64_t)kTileFrames, n_frames - f0);
+    for (int e = tid; e < nf * nc; e += 256) {
+        const int fr = e / nc, ch = e - fr * nc;
+        tile[fr][ch] = in[(f0 + fr) * (int64_t)total + c0 + ch];
+    }
+    __syncthreads();
+    for (int ch = 0; ch < nc; ch++)
+        if (tid < nf) out[(int64_t)(c0 + ch) * out_stride + f0 + tid] = (int16_t)tile[tid][ch];
+}
+
+// 16-bit PCM rows [C][in_stride] -> packed fp32 rows [C][out_stride] of x * 2^-15 (exact: |x| <= 2^15 has 16 significant bits),
+// the samples the fp32 entry points would be given.  Eight samples a thread: one 16-byte load where the source row is 16-byte
+// aligned (wave-uniform: one row per blockIdx.y), two 16-byte stores (out_stride is a multiple of 4 and the buffer 16-byte
+// aligned); the tail of a row and rows at other alignments (odd strides, a base pointer between two 16-byte lines) go sample by
+// sample.  HBM-bound: 6 bytes a sample.
+constexpr int kWidenPerThread = 8;
+
+__global__ void __launch_bounds__(256)
+widen_s16_kernel(const int16_t *__restrict__ in, int64_t in_stride, int64_t S, float *__restrict__ out, int64_t out_stride)
+{
+    const int c = blockIdx.y;
+    const int16_t *row = in + (int64_t)c * in_stride;
+    float *dst = out + (int64_t)c * out_stride;
+    const int64_t i0 = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) * kWidenPerThread;
+    if (i0 >= S) return;
+    constexpr float k = 1.0f / 32768.0f;
+    if (i0 + kWidenPerThread <= S && (reinterpret_cast<uintptr_t>(row) & 15) == 0) {
+        const uint4 v = *reinterpret_cast<const uint4 *>(row + i0);
+        const unsigned w[4] = {v.x, v.y, v.z, v.w};
+        float f[8];
+#pragma unroll
+        for (int j = 0; j < 4; j++) {
+            f[2 * j] = (float)(int16_t)(w[j] & 0xffffu) * k;
+            f[2 * j + 1] = (float)(int16_t)(w[j] >> 16) * k;
+        }
+        *reinterpret_cast<float4 *>(dst + i0) = make_float4(f[0], f[1], f[2], f[3]);
+        *reinterpret_cast<float4 *>(dst + i0 + 4) = make_float4(f[4], f[5], f[6], f[7]);
+        return;
+    }
+    const int64_t i1 = min(i0 + (int64_t)kWidenPerThread, S);
+    for (int64_t i = i0; i < i1; i++) dst[i] = (float)row[i] * k;
 }
 
 // Whole-recording rate conversion for offline input: output sample i reads position i * rate_in / rate_out, computed in
@@ -261,6 +316,27 @@ hipError_t launch_deinterleave(const float *in, int64_t n_frames, int total, int
     if (n_frames <= 0 || C <= 0) return hipSuccess;
     dim3 grid((unsigned)((n_frames + kTileFrames - 1) / kTileFrames), (unsigned)((C + kTileCh - 1) / kTileCh));
     hipLaunchKernelGGL(deinterleave_kernel, grid, dim3(256), 0, stream, in, n_frames, total, first, C, out, out_stride);
+    return hipGetLastError();
+}
+
+hipError_t launch_deinterleave_s16(const int16_t *in, int64_t n_frames, int total, int C, int16_t *out, int64_t out_stride,
+                                   hipStream_t stream)
+{
+    if (n_frames <= 0 || C <= 0) return hipSuccess;
+    if (total < C || out_stride < n_frames) return hipErrorInvalidValue;
+    dim3 grid((unsigned)((n_frames + kTileFrames - 1) / kTileFrames), (unsigned)((C + kTileCh - 1) / kTileCh));
+    hipLaunchKernelGGL(deinterleave_s16_kernel, grid, dim3(256), 0, stream, in, n_frames, total, C, out, out_stride);
+    return hipGetLastError();
+}
+
+hipError_t launch_widen_s16(const int16_t *in, int64_t in_stride, int64_t S, int C, float *out, int64_t out_stride, hipStream_t stream)
+{
+    if (S <= 0 || C <= 0) return hipSuccess;
+    if (out_stride < S || out_stride % 4 != 0 || (reinterpret_cast<uintptr_t>(out) & 15) != 0 || (C > 1 && in_stride < S))
+        return hipErrorInvalidValue;
+    const int64_t blocks = (S + 256 * kWidenPerThread - 1) / (256 * kWidenPerThread);
+    if (blocks > 0x7fffffffLL) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(widen_s16_kernel, dim3((unsigned)blocks, (unsigned)C), dim3(256), 0, stream, in, in_stride, S, out, out_stride);
     return hipGetLastError();
 }
 

@@ -69,10 +69,16 @@ fixup_kernel(const FixDesc fd, const NetDesc n, const float *__restrict__ sample
         if (first + nframes > J) nframes = (int)(J - first);
         if (nframes > kMaxFrames) nframes = kMaxFrames;       // (never: items hold at most kFixMaxCount)
         const int rc = bank_row(n.row_of, c);           // (the bank row of a mixed bank's class launch; columns stay in launch order)
-        const float *row = samples + (int64_t)rc * stride + first * fd.hop + fd.gap;
+        const int64_t at = (int64_t)rc * stride + first * fd.hop + fd.gap;
         const int span = nframes > 0 ? (nframes - 1) * fd.hop + W : 0;
         __syncthreads();                                      // the previous item's columns and samples are no longer read
-        for (int i = tid; i < span; i += kBlock) xs[i] = row[i];
+        if (fd.s16) {                                         // (16-bit PCM: the fp32 value x * 2^-15, exactly)
+            const int16_t *row = reinterpret_cast<const int16_t *>(samples) + at;
+            for (int i = tid; i < span; i += kBlock) xs[i] = (float)row[i] * (1.0f / 32768.0f);
+        } else {
+            const float *row = samples + at;
+            for (int i = tid; i < span; i += kBlock) xs[i] = row[i];
+        }
         __syncthreads();
         // |X[k]| for every (frame, bin) of the item: X[k] = sum_n x[n] w[n] e^{-2 pi i k n / N} (:311-333; bin 0 is real, the
         // packed Nyquist term is dropped :323 -- bins stay below N/2), one task per thread at a time, the angle index k n mod N

@@ -801,11 +801,12 @@ int fused_choice(const FusedDesc &d, int64_t J)
 }
 
 hipError_t launch_fused(const FusedDesc &d, const float *samples, int64_t stride, int C, int64_t S, int64_t J,
-                        int64_t E, float *outputs, uint8_t *flags, hipStream_t stream, const FusedMulti *mn)
+                        int64_t E, float *outputs, uint8_t *flags, hipStream_t stream, const FusedMulti *mn, bool s16)
 {
     if (E <= 0 || C <= 0) return hipSuccess;
     const int choice = fused_choice(d, J);
-    if (choice == 2) return launch_fused_s(d, samples, stride, C, S, J, E, outputs, flags, stream, mn);
+    if (choice == 2) return launch_fused_s(d, samples, stride, C, S, J, E, outputs, flags, stream, mn, s16);
+    if (s16) return hipErrorInvalidValue;          // (16-bit PCM: only the fold kernel reads it)
     if (mn) return hipErrorInvalidValue;           // (no multi-network form of the other fused kernels)
     if (choice == 1) return launch_fused_r(d, samples, stride, C, S, J, E, outputs, flags, stream);
     if (!d.classic_ok) return hipErrorInvalidValue;

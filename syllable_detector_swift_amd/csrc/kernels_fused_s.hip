@@ -70,6 +70,17 @@ __device__ __forceinline__ unsigned cvt_pk(float a, float b)
     asm("v_cvt_pk_f16_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
     return r;
 }
+// 16-bit PCM (S16): four samples of the ring as one ds_read_b64, and one as a word, widened to x * 2^-15 -- exactly the fp32
+// value the fp32 form reads for them
+__device__ __forceinline__ floatx4 s16x4(const int16_t *p)
+{
+    const uint2 v = *reinterpret_cast<const uint2 *>(p);
+    constexpr float k = 1.0f / 32768.0f;
+    return floatx4{(float)(int16_t)(v.x & 0xffffu) * k, (float)((int)v.x >> 16) * k, (float)(int16_t)(v.y & 0xffffu) * k,
+                   (float)((int)v.y >> 16) * k};
+}
+__device__ __forceinline__ float s16x1(const int16_t *p) { return (float)p[0] * (1.0f / 32768.0f); }
+
 // two values -> f16 hi pair and f16 lo pair (hi + lo == the value to 2^-22 relative)
 __device__ __forceinline__ void split2(float a, float b, unsigned &hi, unsigned &lo)
 {
@@ -110,13 +121,19 @@ __device__ __forceinline__ void split2(float a, float b, unsigned &hi, unsigned 
 // also passes row_of: the workgroup reads its samples from, and writes its outputs and flags to, bank row row_of[c] (one more
 // uniform scalar load); null, row c.  The precision guard's items keep c, the launch's channel.  Without MN the three trailing
 // arguments are unused.
-template <int K2, bool GEN, int HQ, int NW, int PADP = 0, bool F2 = false, int NT = 1, bool SPECT = false, bool MN = false>
+// S16: the samples are 16-bit PCM (`samples` points at int16 rows; sample x means x * 2^-15: syldet_run_device_s16).  The DMA
+// moves raw int16 into the same ring bytes -- a chunk of 1024 bytes is 512 samples, so a tile needs half the DMA instructions --
+// and the lanes widen after the LDS read: a ds_read_b64 where the fp32 form reads a ds_read_b128 quad, a word where it reads a
+// word.  From there every instruction is the fp32 form's, so the bits are.  Instantiated for the twice-folded form on the plain
+// ring with one quad of units on eight waves (the reference's framing at ordinary hops), GEN and MN either way.
+template <int K2, bool GEN, int HQ, int NW, int PADP = 0, bool F2 = false, int NT = 1, bool SPECT = false, bool MN = false, bool S16 = false>
 __global__ void __launch_bounds__(64 * NW, 1)
 fused_s_kernel(const FusedDesc d, const float *__restrict__ samples, int64_t stride, int64_t s_eff, int64_t E,
                float *__restrict__ outputs, uint8_t *__restrict__ flags, const FusedNet *__restrict__ nets, const int *__restrict__ net_of,
                const int *__restrict__ row_of)
 {
     static_assert(!(MN && SPECT), "the spectrogram instantiation runs no network");
+    static_assert(!S16 || (K2 == 4 && F2 && PADP == 0 && NT == 1 && HQ == 1 && NW == 8 && !SPECT), "16-bit PCM: the twice-folded form on the plain ring");
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const int tid = threadIdx.x;
     const int lane = tid & 63;
@@ -142,13 +159,14 @@ fused_s_kernel(const FusedDesc d, const float *__restrict__ samples, int64_t str
 
     // ---- wave-private LDS: sample ring (RC chunks of 256 floats + one mirror chunk), tap products, a zero quad
     unsigned char *wbase = smem + (size_t)wave * d.s_lds_wave;
-    const int RC = PADP == 1 ? d.s_cs8_rc : d.s_ring_chunks, R = RC * 256;
+    const int RC = PADP == 1 ? d.s_cs8_rc : d.s_ring_chunks, R = RC * (S16 ? 512 : 256);     // (R: samples the ring holds)
     constexpr bool CS8 = PADP == 1;                   // whole chunks staggered over the banks (hop 128: see the header)
     static_assert(!CS8 || (F2 && HQ == 1 && NT == 1), "staggered chunks: the twice-folded form at hop 128");
     constexpr int kSub = PADP > 1 ? 256 / PADP : 1;   // padded pieces of a chunk of 256 floats
     constexpr int kChunkB = CS8 ? 1280 : 1024 + (PADP > 1 ? 16 * kSub : 0);
     auto sk = [](int i) { return PADP > 1 ? 4 * (i / (PADP > 1 ? PADP : 1)) : 0; };   // padding (floats) in front of position i of a frame / of the ring
     float *ring = reinterpret_cast<float *>(wbase);
+    const int16_t *ring16 = reinterpret_cast<const int16_t *>(wbase);   // (S16)
     const int PS = d.s_pstride, TP = d.s_tp;          // floats per frame row: 4 TP tap products, sum of squares, floor weight, padding
     float *rows = reinterpret_cast<float *>(wbase + (size_t)(RC + (CS8 ? 0 : 1)) * kChunkB);    // [T - 1 + 16][PS]
     float *zquad = rows + (T - 1 + kTile) * PS;       // 8 HQ floats: HQ zero quads (what taps past timeRange read), HQ quads for stores that have no place
@@ -222,18 +240,20 @@ fused_s_kernel(const FusedDesc d, const float *__restrict__ samples, int64_t str
     }
 
     const int rc = MN ? bank_row(row_of, c) : c;     // (the bank row: a mixed bank's class launch reads and writes in place)
-    const float *row = samples + (int64_t)rc * stride;
-    const __amdgpu_buffer_rsrc_t in_rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(row), 0, (int)(s_eff * 4), 0x00020000);
+    const float *row = S16 ? reinterpret_cast<const float *>(reinterpret_cast<const int16_t *>(samples) + (int64_t)rc * stride)
+                           : samples + (int64_t)rc * stride;
+    const __amdgpu_buffer_rsrc_t in_rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(row), 0, (int)(s_eff * (S16 ? 2 : 4)), 0x00020000);
     const __amdgpu_buffer_rsrc_t out_rs = __builtin_amdgcn_make_buffer_rsrc(
         outputs ? outputs + (int64_t)rc * E * n_out : nullptr, 0, outputs ? (int)(E * n_out * 4) : 0, 0x00020000);
     const __amdgpu_buffer_rsrc_t flg_rs = __builtin_amdgcn_make_buffer_rsrc(flags ? flags + (int64_t)rc * E : nullptr, 0, flags ? (int)E : 0, 0x00020000);
     const __amdgpu_buffer_rsrc_t spc_rs = __builtin_amdgcn_make_buffer_rsrc(
         SPECT ? d.spect_out + (int64_t)c * E * d.F : nullptr, 0, SPECT ? (int)(E * d.F * 4) : 0, 0x00020000);
 
-    // ---- the sample stream: chunk q holds samples [256 q, 256 q + 256) behind the segment's first one, in ring slot q mod RC;
+    // ---- the sample stream: chunk q holds samples [256 q, 256 q + 256) behind the segment's first one, in ring slot q mod RC
+    // (S16: [512 q, 512 q + 512) -- the same 1024 bytes);
     // slot 0's chunks are written a second time behind the ring (the mirror), so that a frame's reads never wrap.
     // A chunk may be issued once the chunk it replaces is dead: while tile t is read, chunks up to RC - 1 + floor(16 hop t / 256).
-    const unsigned org = (unsigned)((e_b * hop + d.gap) * 4);            // byte offset of the segment's first sample in its row (row < 4 GB: launcher)
+    const unsigned org = (unsigned)((e_b * hop + d.gap) * (S16 ? 2 : 4));            // byte offset of the segment's first sample in its row (row < 4 GB: launcher)
     int cn = 0, slot = 0;                                                // next chunk, its ring slot
     auto issue_upto = [&](int last) {
         while (cn <= last) {
@@ -258,8 +278,9 @@ fused_s_kernel(const FusedDesc d, const float *__restrict__ samples, int64_t str
         }
     };
     const int span = (kTile - 1) * hop + W;                              // samples under one tile
-    auto need = [&](int t) { return (kTile * hop * t + span - 1) >> 8; };
-    auto allowed = [&](int t) { return RC - 1 + ((kTile * hop * t) >> 8); };
+    constexpr int kChunkLog = S16 ? 9 : 8;                               // samples a chunk: 2^kChunkLog
+    auto need = [&](int t) { return (kTile * hop * t + span - 1) >> kChunkLog; };
+    auto allowed = [&](int t) { return RC - 1 + ((kTile * hop * t) >> kChunkLog); };
 
     // ---- per-lane LDS places.  fo: this lane's frame inside the ring (floats), advanced by 16 hop a tile.
     unsigned fo = (unsigned)(hop * fr);                                  // < R (launcher: 16 hop <= R)
@@ -395,6 +416,20 @@ fused_s_kernel(const FusedDesc d, const float *__restrict__ samples, int64_t str
                     P4w[ks] = b3[8];                      // (g == 0, ks == 0: position 256, the next frame's -- read, never used)
                     continue;
                 }
+                if (S16) {                    // (every quad starts on a multiple of 4 samples: 8-byte aligned)
+                    const int16_t *a = ring16 + fo + 32 * ks + 8 * g, *b = ring16 + fo + 120 - 32 * ks - 8 * g;
+                    P1[ks][0] = s16x4(a);
+                    P1[ks][1] = s16x4(a + 4);
+                    P3[ks][0] = s16x4(a + 128);
+                    P3[ks][1] = s16x4(a + 132);
+                    P2[ks][0] = s16x4(b);
+                    P2[ks][1] = s16x4(b + 4);
+                    P2w[ks] = s16x1(b + 8);
+                    P4[ks][0] = s16x4(b + 128);
+                    P4[ks][1] = s16x4(b + 132);
+                    P4w[ks] = s16x1(b + 136);
+                    continue;
+                }
                 const float *a = fp + 32 * ks + 8 * g, *b = fp + 120 - 32 * ks - 8 * g;
                 P1[ks][0] = *reinterpret_cast<const floatx4 *>(a);
                 P1[ks][1] = *reinterpret_cast<const floatx4 *>(a + 4);
@@ -407,8 +442,8 @@ fused_s_kernel(const FusedDesc d, const float *__restrict__ samples, int64_t str
                 P4[ks][1] = *reinterpret_cast<const floatx4 *>(b + 132 + sk(192));
                 P4w[ks] = b[136 + sk(192)];             // (g == 0, ks == 0: x[256], the next frame's -- read, never used)
             }
-            x64 = CS8 ? f1[64] : fp[64 + sk(64)];
-            x192 = CS8 ? f2[64] : fp[192 + sk(192)];
+            x64 = S16 ? s16x1(ring16 + fo + 64) : (CS8 ? f1[64] : fp[64 + sk(64)]);
+            x192 = S16 ? s16x1(ring16 + fo + 192) : (CS8 ? f2[64] : fp[192 + sk(192)]);
             // the raw samples of this tile are dead as soon as they are in registers: all of the next tile's chunks, a whole tile
             // of arithmetic ahead of their use
             SD_STAMP(st_lg, asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"));
@@ -476,7 +511,7 @@ fused_s_kernel(const FusedDesc d, const float *__restrict__ samples, int64_t str
         if (!F2 && t + 1 < tiles) issue_upto(need(t + 1) < allowed(t) ? need(t + 1) : allowed(t));
 
         // ---- the folded DFT: per k-step this lane folds, scales and splits 8 positions of its frame, then 12 MFMAs
-        const float xl = fp[0] * sx;                  // the frame's first sample (no partner)
+        const float xl = S16 ? 0.0f : fp[0] * sx;     // the frame's first sample (no partner; the twice-folded form has none)
         floatx4 acc[4 * NT];                          // re 0-15, re 16-31, im 0-15, im 16-31 (twice folded: re even, re odd, im even, im odd of row tile tau at 4 tau + ..)
 #pragma unroll
         for (int i = 0; i < 4 * NT; i++) acc[i] = floatx4{0.f, 0.f, 0.f, 0.f};
@@ -986,14 +1021,14 @@ fused_s_kernel(const FusedDesc d, const float *__restrict__ samples, int64_t str
 #undef SD_STAMP
 }
 
-template <int K2, bool GEN, int HQ, int NW, int PADP = 0, bool F2 = false, int NT = 1, bool SPECT = false, bool MN = false>
+template <int K2, bool GEN, int HQ, int NW, int PADP = 0, bool F2 = false, int NT = 1, bool SPECT = false, bool MN = false, bool S16 = false>
 hipError_t launch_one(const FusedDesc &d, const float *samples, int64_t stride, int C, int64_t s_eff, int64_t E,
                       float *outputs, uint8_t *flags, hipStream_t stream, const FusedMulti *mn = nullptr)
 {
     // (every network instantiation has its multi-network twin)
     if constexpr (!SPECT && !MN)
-        if (mn) return launch_one<K2, GEN, HQ, NW, PADP, F2, NT, false, true>(d, samples, stride, C, s_eff, E, outputs, flags, stream, mn);
-    auto kern = fused_s_kernel<K2, GEN, HQ, NW, PADP, F2, NT, SPECT, MN>;
+        if (mn) return launch_one<K2, GEN, HQ, NW, PADP, F2, NT, false, true, S16>(d, samples, stride, C, s_eff, E, outputs, flags, stream, mn);
+    auto kern = fused_s_kernel<K2, GEN, HQ, NW, PADP, F2, NT, SPECT, MN, S16>;
     constexpr int kWaves = NW;
 #ifdef SYLDET_S_ONEWAVE
     const int lds = kWaves == 4 ? 100 * 1024 : d.s_lds_wave * kWaves;       // (one workgroup a CU)
@@ -1035,7 +1070,7 @@ bool fused_s_applicable(const FusedDesc &d)
 }
 
 hipError_t launch_fused_s(const FusedDesc &d, const float *samples, int64_t stride, int C, int64_t S, int64_t J,
-                          int64_t E, float *outputs, uint8_t *flags, hipStream_t stream, const FusedMulti *mn)
+                          int64_t E, float *outputs, uint8_t *flags, hipStream_t stream, const FusedMulti *mn, bool s16)
 {
     (void)S;
     if (E <= 0 || C <= 0) return hipSuccess;
@@ -1043,6 +1078,13 @@ hipError_t launch_fused_s(const FusedDesc &d, const float *samples, int64_t stri
     const int64_t s_eff = (J - 1) * (int64_t)d.hop + d.gap + d.W;
     if (s_eff * 4 >= 0x7fffffffll) return hipErrorInvalidValue;           // (the launcher's caller keeps such rows on the other kernels)
     const bool exact = d.norm == 1 && d.scaling == 0 && d.tf0 == 0 /* TanSig */ && d.tf1 == 2 /* PureLin */ && d.n_out == 1;
+    if (s16) {
+        // 16-bit PCM: the forms below that have an S16 twin (fused_s_native_s16 says which); the rows must be of whole words
+        if (!fused_s_native_s16(d) || (reinterpret_cast<uintptr_t>(samples) & 3) != 0 || (stride & 1) != 0 || (d.gap & 1) != 0)
+            return hipErrorInvalidValue;
+        if (exact) return launch_one<4, false, 1, 8, 0, true, 1, false, false, true>(d, samples, stride, C, s_eff, E, outputs, flags, stream, mn);
+        return launch_one<4, true, 1, 8, 0, true, 1, false, false, true>(d, samples, stride, C, s_eff, E, outputs, flags, stream, mn);
+    }
 #define SD_S_GO(K2_)                                                                                                  \
     if (d.W == 64 * K2_) {                                                                                            \
         if (d.H > 12) return launch_one<K2_, true, 4, 4>(d, samples, stride, C, s_eff, E, outputs, flags, stream, mn);    \
@@ -1098,6 +1140,18 @@ hipError_t launch_fused_s(const FusedDesc &d, const float *samples, int64_t stri
     SD_S_GO(4) SD_S_GO(2) SD_S_GO(1) SD_S_GO(3)
 #undef SD_S_GO
     return hipErrorInvalidValue;
+}
+
+bool fused_s_native_s16(const FusedDesc &d)
+{
+    // exactly where launch_fused_s picks launch_one<4, *, 1, 8, 0, true> below: not the padded ring, not CS8, not two row tiles
+    if (!fused_s_applicable(d) || d.s_padp || d.W != 256 || d.H > 4 || !d.s2_ok || d.no_fold2 || d.s2_nt == 2) return false;
+    if (d.s_cs8 && !d.no_cs8 && d.s2_nt == 1) return false;
+#ifdef SYLDET_S_ONEWAVE
+    return false;
+#else
+    return true;
+#endif
 }
 
 // The DFT front half alone on the twice-folded form: |X| or |X|^2 columns [C][J][F] (d.spect_out), for 256-point frames under a

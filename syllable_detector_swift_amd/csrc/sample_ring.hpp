@@ -66,6 +66,14 @@ struct ChannelStream {
         for (int64_t i = 0; i < n; i++) r[(size_t)((t + (uint64_t)i) & mask)] = data[i * step];
         tail.store(t + (uint64_t)n, std::memory_order_release);
     }
+    // ... 16-bit PCM: sample x goes in as x * 2^-15 (exact), the value the fp32 appends would be given
+    void write(const int16_t *data, int64_t n, int64_t step)
+    {
+        const uint64_t t = tail.load(std::memory_order_relaxed);
+        float *r = ring.data();
+        for (int64_t i = 0; i < n; i++) r[(size_t)((t + (uint64_t)i) & mask)] = (float)data[i * step] * (1.0f / 32768.0f);
+        tail.store(t + (uint64_t)n, std::memory_order_release);
+    }
 
     // Consumer side: n samples from absolute position `from` (n > 0 only after an append: the ring exists).
     void copy_out(uint64_t from, float *dst, size_t n) const

@@ -163,7 +163,8 @@ struct syldet {
     bool has_fix = false;
     DeviceBuffer d_fused;             // one blob: dfrag | wfrag | koff | bias0 | rvec | w1 | b1 | out_params
     DeviceBuffer d_stage_in, d_stage_out, d_stage_flags, d_stage_idx, d_stage_cnt;
-    DeviceBuffer d_planar;            // channel-major copy of interleaved input (syldet_run_interleaved*)
+    DeviceBuffer d_planar;            // channel-major copy of interleaved input (syldet_run_interleaved*: fp32 or int16)
+    DeviceBuffer d_widen;             // 16-bit PCM batches: the packed fp32 copy x * 2^-15 the engines read (widen_s16_kernel)
 
     // the fused engine's DFT front half as the STFT of the other engines (W <= 256, F <= 32, hop % 4 == 0)
     FusedPlan dft;
@@ -762,36 +763,21 @@ generic_transform:
     return SYLDET_OK;
 }
 
-// d_net_of: a multi-network handle's network of each of the C rows (null: the handle's own [C] table, rows = channels).
-// d_row_of: a mixed bank's class launch, the bank row of each of the C channels (null: row c).
-int run_on_stream(syldet *h, const float *d_samples, int64_t S, int64_t stride, int C, float *d_outputs,
-                  uint8_t *d_flags, hipStream_t stream, const int *d_net_of = nullptr, const int *d_row_of = nullptr)
+// A batch's device samples as the caller passed them: fp32, or 16-bit PCM whose sample x means x * 2^-15 (the *_s16 entry
+// points).  One route decision serves both (run_on_stream).
+struct Samples {
+    const void *p = nullptr;
+    bool s16 = false;
+    Samples(const float *f) : p(f) {}
+    Samples(const void *q, bool pcm16) : p(q), s16(pcm16) {}
+};
+
+// The fused route's decision for a batch of E evaluations (J frames) on C rows: whether it takes a fused kernel, and the
+// plan `d` it runs.  One decision for both sample types (run_on_stream, takes_native_s16).
+bool fused_route_for(const syldet *h, int64_t J, int64_t E, int C, FusedDesc &d)
 {
-    const int64_t J = count_frames(h, S), E = count_evals(h, S);
-    if (E <= 0) return SYLDET_OK;
-    SYLDET_HIP(hipSetDevice(h->device));
-    if (!h->root) h->prof_begin();                   // (a class handle's launches belong to its bank's call)
-    if (!h->classes.empty()) {
-        // a mixed bank over all its channels: each class in turn, in place through its row table
-        if (C != h->channels) return fail(SYLDET_ERR_INVALID_ARGUMENT, "a mixed bank's batch covers all its channels");
-        for (auto &k : h->classes)
-            if (int st = run_on_stream(k.get(), d_samples, S, stride, k->channels, d_outputs, d_flags, stream, nullptr, (const int *)k->d_row_of.ptr))
-                return st;
-        return SYLDET_OK;
-    }
-    // the network stage's (and the exact recomputation's) view of the rows' networks and of the bank's rows
-    NetDesc net = h->net;
-    net.row_of = d_row_of;
-    FusedMulti mn{h->fnets, nullptr, d_row_of};
-    if (h->n_nets > 1) {
-        net.net_of = mn.net_of = d_net_of ? d_net_of : (const int *)h->d_net_of.ptr;
-    } else if (h->fnets) {
-        mn.net_of = (const int *)h->d_net_of.ptr;     // (a mixed bank's one-network class on the fold kernel: all zeros)
-    }
-    const FusedMulti *mnp = h->fnets ? &mn : nullptr;
     // the fused kernel addresses a channel's results with 32-bit byte offsets; longer rows take the generic engine
     bool fused_route = h->engine == SYLDET_ENGINE_FUSED && (uint64_t)E * (uint64_t)h->geom.outputs * 4u < 0xFFFFFFF0ull;
-    FusedDesc d{};
     if (fused_route) {
         d = h->fused.desc;
         fused_segmentation(d, E, C);
@@ -815,6 +801,83 @@ int run_on_stream(syldet *h, const float *d_samples, int64_t S, int64_t stride, 
         // (a multi-network handle: only the fold kernel has the form; the diagnostic stamped builds are not for it)
         if ((h->n_nets > 1 || h->fnets) && (choice != 2 || h->sw.fused_stamps)) fused_route = false;
     }
+    return fused_route;
+}
+
+// Does this 16-bit PCM batch run on a kernel that reads int16 natively?  The fused route's own decision, the launcher's choice of
+// the fold kernel's form (fused_s_native_s16), and rows of whole 4-byte words (the DMA's): a 4-byte aligned base, an even stride
+// and gap.  Anything else is widened first (widen_s16).
+bool takes_native_s16(const syldet *h, Samples x, int64_t S, int64_t stride, int C)
+{
+    const int64_t J = count_frames(h, S), E = count_evals(h, S);
+    FusedDesc d{};
+    if (E <= 0 || !fused_route_for(h, J, E, C, d)) return false;
+    return fused_choice(d, J) == 2 && !h->sw.fused_stamps && fused_s_native_s16(d) && (reinterpret_cast<uintptr_t>(x.p) & 3) == 0 &&
+           (stride & 1) == 0 && (d.gap & 1) == 0;
+}
+
+// 16-bit PCM rows for kernels that read fp32: one packed copy x * 2^-15 in the bank's scratch (d_widen; rows of whole 16-byte
+// quads).  The conversion is exact and no engine's arithmetic depends on a row's alignment or stride (only its load widths do),
+// so the batch gives the bits of the fp32 call on the same samples.  x and stride become the copy's.
+int widen_s16(syldet *h, Samples &x, int64_t S, int64_t &stride, int C, hipStream_t stream)
+{
+    syldet *owner = h->root ? h->root : h;
+    const int64_t ws = (S + 3) & ~(int64_t)3;
+    if (int st = owner->d_widen.reserve((size_t)C * (size_t)ws * sizeof(float))) return st;
+    {
+        KernelTimer t(h, stream, "widen_s16_kernel");
+        SYLDET_HIP(launch_widen_s16((const int16_t *)x.p, stride, S, C, (float *)owner->d_widen.ptr, ws, stream));
+    }
+    x = Samples((const float *)owner->d_widen.ptr);
+    stride = ws;
+    return SYLDET_OK;
+}
+
+// d_net_of: a multi-network handle's network of each of the C rows (null: the handle's own [C] table, rows = channels).
+// d_row_of: a mixed bank's class launch, the bank row of each of the C channels (null: row c).
+int run_on_stream(syldet *h, Samples x, int64_t S, int64_t stride, int C, float *d_outputs,
+                  uint8_t *d_flags, hipStream_t stream, const int *d_net_of = nullptr, const int *d_row_of = nullptr)
+{
+    const int64_t J = count_frames(h, S), E = count_evals(h, S);
+    if (E <= 0) return SYLDET_OK;
+    SYLDET_HIP(hipSetDevice(h->device));
+    if (!h->root) h->prof_begin();                   // (a class handle's launches belong to its bank's call)
+    if (!h->classes.empty()) {
+        // a mixed bank over all its channels: each class in turn, in place through its row table.  16-bit PCM: a class on the
+        // fold kernel's s16 form reads the int16 rows in place; the others share one widened copy, made at most once a call.
+        if (C != h->channels) return fail(SYLDET_ERR_INVALID_ARGUMENT, "a mixed bank's batch covers all its channels");
+        Samples wide = x;
+        int64_t wstride = stride;
+        for (auto &k : h->classes) {
+            Samples xk = x;
+            int64_t sk = stride;
+            if (x.s16 && !takes_native_s16(k.get(), x, S, stride, k->channels)) {
+                if (wide.s16)
+                    if (int st = widen_s16(h, wide, S, wstride, C, stream)) return st;
+                xk = wide;
+                sk = wstride;
+            }
+            if (int st = run_on_stream(k.get(), xk, S, sk, k->channels, d_outputs, d_flags, stream, nullptr, (const int *)k->d_row_of.ptr))
+                return st;
+        }
+        return SYLDET_OK;
+    }
+    // 16-bit PCM: natively on the fold kernel's s16 form where this batch takes it, else through one widened copy
+    if (x.s16 && !takes_native_s16(h, x, S, stride, C))
+        if (int st = widen_s16(h, x, S, stride, C, stream)) return st;
+    const float *d_samples = (const float *)x.p;      // (x.s16 from here on: int16 rows, read by the fold kernel's s16 form alone)
+    // the network stage's (and the exact recomputation's) view of the rows' networks and of the bank's rows
+    NetDesc net = h->net;
+    net.row_of = d_row_of;
+    FusedMulti mn{h->fnets, nullptr, d_row_of};
+    if (h->n_nets > 1) {
+        net.net_of = mn.net_of = d_net_of ? d_net_of : (const int *)h->d_net_of.ptr;
+    } else if (h->fnets) {
+        mn.net_of = (const int *)h->d_net_of.ptr;     // (a mixed bank's one-network class on the fold kernel: all zeros)
+    }
+    const FusedMulti *mnp = h->fnets ? &mn : nullptr;
+    FusedDesc d{};
+    bool fused_route = fused_route_for(h, J, E, C, d);
     if (fused_route) {
         // diagnostic only: SYLDET_FUSED_STAMPS=1 runs the stamped instantiation and prints where a
         // workgroup pass spends its cycles (never set in tests or the benchmark)
@@ -880,9 +943,11 @@ int run_on_stream(syldet *h, const float *d_samples, int64_t S, int64_t stride, 
             // (the launcher picks the register-resident-basis kernel where it is instantiated: named for what runs)
             static const char *const names[3] = {"fused_kernel", "fused_r_kernel", "fused_s_kernel"};
             KernelTimer t(h, stream, names[fused_choice(d, J)]);
-            SYLDET_HIP(launch_fused(d, d_samples, stride, C, S, J, E, d_outputs, d_flags, stream, mnp));
+            SYLDET_HIP(launch_fused(d, d_samples, stride, C, S, J, E, d_outputs, d_flags, stream, mnp, x.s16));
         }
-        return timed_fixup(h, stream, d.fix, [&](const FixList &l) { return launch_fixup(h->fixd, net, d_samples, stride, J, E, d_outputs, d_flags, nullptr, l, stream); });
+        FixDesc fd = h->fixd;
+        fd.s16 = x.s16 ? 1 : 0;                      // (the exact recomputation reads the same rows)
+        return timed_fixup(h, stream, d.fix, [&](const FixList &l) { return launch_fixup(fd, net, d_samples, stride, J, E, d_outputs, d_flags, nullptr, l, stream); });
     }
     // (+ 16 bytes: the matrix-core network stage reads a frame's last bins as a whole quad)
     if (int st = h->d_columns.reserve((size_t)C * (size_t)J * (size_t)h->geom.bins * sizeof(float) + 16)) return st;
@@ -1475,7 +1540,7 @@ int syldet_destroy(syldet_t *h)
     for (hipEvent_t e : h->events)
         if (e) (void)hipEventDestroy(e);
     if (h->prof_items) (void)hipHostFree(h->prof_items);
-    for (DeviceBuffer *b : {&h->d_window, &h->d_tw, &h->d_sw, &h->d_params, &h->d_thr, &h->d_columns, &h->d_fused, &h->d_mlpx, &h->d_stamps, &h->d_fix, &h->d_ctab, &h->d_planar, &h->d_wide, &h->d_xn, &h->d_dft, &h->d_net_of, &h->d_fnets, &h->d_stage_net, &h->d_stage_in,
+    for (DeviceBuffer *b : {&h->d_window, &h->d_tw, &h->d_sw, &h->d_params, &h->d_thr, &h->d_columns, &h->d_fused, &h->d_mlpx, &h->d_stamps, &h->d_fix, &h->d_ctab, &h->d_planar, &h->d_widen, &h->d_wide, &h->d_xn, &h->d_dft, &h->d_net_of, &h->d_fnets, &h->d_stage_net, &h->d_stage_in,
                             &h->d_stage_out, &h->d_stage_flags, &h->d_stage_idx, &h->d_stage_cnt})
         b->release();
     h->p_stage_in.release();
@@ -1614,6 +1679,13 @@ int syldet_run_device(syldet_t *h, const float *d_samples, int64_t n_samples, in
     return run_on_stream(h, d_samples, n_samples, channel_stride, h->channels, d_outputs, d_flags, (hipStream_t)hip_stream);
 }
 
+int syldet_run_device_s16(syldet_t *h, const int16_t *d_samples, int64_t n_samples, int64_t channel_stride, float *d_outputs,
+                          uint8_t *d_flags, void *hip_stream)
+{
+    if (int st = check_batch_args(h, d_samples, n_samples, channel_stride)) return st;
+    return run_on_stream(h, Samples(d_samples, true), n_samples, channel_stride, h->channels, d_outputs, d_flags, (hipStream_t)hip_stream);
+}
+
 int syldet_spectrogram_device(syldet_t *h, const float *d_samples, int64_t n_samples, int64_t channel_stride,
                               float *d_columns, void *hip_stream)
 {
@@ -1665,9 +1737,12 @@ static int pipe_bring_up(syldet *h)
 // truly asynchronous; for ordinary memory the runtime pins the pages of each copy on the fly and the copy call returns when
 // its bytes have moved -- the kernel of the stage before runs meanwhile all the same (measured: within a few per cent of
 // the PCIe rate either way, and a staging copy through a pinned buffer of our own was half as fast).
-int syldet_run(syldet_t *h, const float *samples, int64_t n_samples, int64_t channel_stride, float *outputs, uint8_t *flags)
+// 16-bit PCM (syldet_run_s16) takes the same stages -- n_c from the fp32 byte count, so that the pass-scaled kernels see the
+// tiling of syldet_run and give its bits -- with int16 staging: the copies in move half the bytes.
+static int run_host(syldet *h, Samples x, int64_t n_samples, int64_t channel_stride, float *outputs, uint8_t *flags)
 {
-    if (int st = check_batch_args(h, samples, n_samples, channel_stride)) return st;
+    const size_t es = x.s16 ? sizeof(int16_t) : sizeof(float);    // bytes a sample in the caller's rows and the device stages
+    const char *samples = (const char *)x.p;
     std::lock_guard<std::mutex> staging(h->pump_mu);   // the staging buffers and h->stream: one user at a time
     SYLDET_HIP(hipSetDevice(h->device));
     const int C = h->channels, n_out = h->geom.outputs, T = h->cfg.view.time_range;
@@ -1684,7 +1759,7 @@ int syldet_run(syldet_t *h, const float *samples, int64_t n_samples, int64_t cha
     n_c = (E + n_stages - 1) / n_stages;
     const int64_t S_max = (n_c + T - 2) * hop + frame;
     for (int b = 0; b < (n_stages > 1 ? 2 : 1); b++) {
-        if (int st = p.d_in[b].reserve((size_t)C * (size_t)S_max * 4)) return st;
+        if (int st = p.d_in[b].reserve((size_t)C * (size_t)S_max * es)) return st;
         if (int st = p.d_out[b].reserve((size_t)C * (size_t)n_c * (size_t)n_out * 4)) return st;
         if (int st = p.d_fl[b].reserve((size_t)C * (size_t)n_c)) return st;
     }
@@ -1703,12 +1778,12 @@ int syldet_run(syldet_t *h, const float *samples, int64_t n_samples, int64_t cha
         const int b = (int)(k & 1);
         const int64_t e0 = k * n_c, n = std::min(n_c, E - e0), s0 = e0 * hop, Sc = (n + T - 2) * hop + frame;
         if (k >= 2) SYLDET_HIP(hipStreamWaitEvent(p.s_in, p.ev_k[b], 0));      // the kernel of stage k - 2 has read this device buffer
-        SYLDET_HIP(hipMemcpy2DAsync(p.d_in[b].ptr, (size_t)Sc * 4, samples + s0, (size_t)channel_stride * 4, (size_t)Sc * 4, (size_t)C,
-                                    hipMemcpyHostToDevice, p.s_in));
+        SYLDET_HIP(hipMemcpy2DAsync(p.d_in[b].ptr, (size_t)Sc * es, samples + (size_t)s0 * es, (size_t)channel_stride * es, (size_t)Sc * es,
+                                    (size_t)C, hipMemcpyHostToDevice, p.s_in));
         SYLDET_HIP(hipEventRecord(p.ev_h2d[b], p.s_in));
         SYLDET_HIP(hipStreamWaitEvent(h->stream, p.ev_h2d[b], 0));
         if (k >= 2) SYLDET_HIP(hipStreamWaitEvent(h->stream, p.ev_d2h[b], 0)); // stage k - 2's results have left the device buffers
-        if (int st = run_on_stream(h, (const float *)p.d_in[b].ptr, Sc, Sc, C, (float *)p.d_out[b].ptr, (uint8_t *)p.d_fl[b].ptr, h->stream)) return st;
+        if (int st = run_on_stream(h, Samples(p.d_in[b].ptr, x.s16), Sc, Sc, C, (float *)p.d_out[b].ptr, (uint8_t *)p.d_fl[b].ptr, h->stream)) return st;
         SYLDET_HIP(hipEventRecord(p.ev_k[b], h->stream));
         SYLDET_HIP(hipStreamWaitEvent(p.s_out, p.ev_k[b], 0));
         if (outputs)
@@ -1720,6 +1795,18 @@ int syldet_run(syldet_t *h, const float *samples, int64_t n_samples, int64_t cha
     }
     SYLDET_HIP(hipStreamSynchronize(p.s_out));
     return SYLDET_OK;
+}
+
+int syldet_run(syldet_t *h, const float *samples, int64_t n_samples, int64_t channel_stride, float *outputs, uint8_t *flags)
+{
+    if (int st = check_batch_args(h, samples, n_samples, channel_stride)) return st;
+    return run_host(h, samples, n_samples, channel_stride, outputs, flags);
+}
+
+int syldet_run_s16(syldet_t *h, const int16_t *samples, int64_t n_samples, int64_t channel_stride, float *outputs, uint8_t *flags)
+{
+    if (int st = check_batch_args(h, samples, n_samples, channel_stride)) return st;
+    return run_host(h, Samples(samples, true), n_samples, channel_stride, outputs, flags);
 }
 
 // Host memory for audio and results that the device reads and writes in place (page-locked): what the reference's ring
@@ -1746,47 +1833,79 @@ int syldet_host_free(void *p)
 
 // ---- interleaved (frame-major) audio: de-interleave on the device, then the batch path ----
 
+static int interleaved_args(const syldet *h, int64_t n_frames, int32_t total_channels)
+{
+    if (!h) return fail(SYLDET_ERR_INVALID_ARGUMENT, "NULL handle");
+    if (total_channels != h->channels) return fail(SYLDET_ERR_INVALID_ARGUMENT, "total_channels must equal the bank's channel count");
+    if (n_frames < 0) return fail(SYLDET_ERR_INVALID_ARGUMENT, "n_frames must be >= 0");
+    return SYLDET_OK;
+}
+
+// fp32 or (s16) int16 frames: the planar copy keeps the caller's sample width, then the batch path on it
+static int run_interleaved_device(syldet *h, Samples x, int64_t n_frames, float *d_outputs, uint8_t *d_flags, hipStream_t stream)
+{
+    if (count_evals(h, n_frames) <= 0) return SYLDET_OK;
+    if (!x.p) return fail(SYLDET_ERR_INVALID_ARGUMENT, "NULL buffer");
+    SYLDET_HIP(hipSetDevice(h->device));
+    const int C = h->channels;
+    if (int st = h->d_planar.reserve((size_t)C * (size_t)n_frames * (x.s16 ? sizeof(int16_t) : sizeof(float)))) return st;
+    if (x.s16)
+        SYLDET_HIP(launch_deinterleave_s16((const int16_t *)x.p, n_frames, C, C, (int16_t *)h->d_planar.ptr, n_frames, stream));
+    else
+        SYLDET_HIP(launch_deinterleave((const float *)x.p, n_frames, C, 0, C, (float *)h->d_planar.ptr, n_frames, stream));
+    return run_on_stream(h, Samples(h->d_planar.ptr, x.s16), n_frames, n_frames, C, d_outputs, d_flags, stream);
+}
+
 int syldet_run_interleaved_device(syldet_t *h, const float *d_interleaved, int64_t n_frames, int32_t total_channels,
                                   float *d_outputs, uint8_t *d_flags, void *hip_stream)
 {
-    if (!h) return fail(SYLDET_ERR_INVALID_ARGUMENT, "NULL handle");
-    if (total_channels != h->channels) return fail(SYLDET_ERR_INVALID_ARGUMENT, "total_channels must equal the bank's channel count");
-    if (n_frames < 0) return fail(SYLDET_ERR_INVALID_ARGUMENT, "n_frames must be >= 0");
-    if (count_evals(h, n_frames) <= 0) return SYLDET_OK;
-    if (!d_interleaved) return fail(SYLDET_ERR_INVALID_ARGUMENT, "NULL buffer");
-    SYLDET_HIP(hipSetDevice(h->device));
-    const int C = h->channels;
-    if (int st = h->d_planar.reserve((size_t)C * (size_t)n_frames * sizeof(float))) return st;
-    SYLDET_HIP(launch_deinterleave(d_interleaved, n_frames, C, 0, C, (float *)h->d_planar.ptr, n_frames, (hipStream_t)hip_stream));
-    return run_on_stream(h, (const float *)h->d_planar.ptr, n_frames, n_frames, C, d_outputs, d_flags, (hipStream_t)hip_stream);
+    if (int st = interleaved_args(h, n_frames, total_channels)) return st;
+    return run_interleaved_device(h, d_interleaved, n_frames, d_outputs, d_flags, (hipStream_t)hip_stream);
 }
 
-int syldet_run_interleaved(syldet_t *h, const float *interleaved, int64_t n_frames, int32_t total_channels, float *outputs,
-                           uint8_t *flags)
+int syldet_run_interleaved_device_s16(syldet_t *h, const int16_t *d_interleaved, int64_t n_frames, int32_t total_channels,
+                                      float *d_outputs, uint8_t *d_flags, void *hip_stream)
 {
-    if (!h) return fail(SYLDET_ERR_INVALID_ARGUMENT, "NULL handle");
-    if (total_channels != h->channels) return fail(SYLDET_ERR_INVALID_ARGUMENT, "total_channels must equal the bank's channel count");
-    if (n_frames < 0) return fail(SYLDET_ERR_INVALID_ARGUMENT, "n_frames must be >= 0");
+    if (int st = interleaved_args(h, n_frames, total_channels)) return st;
+    return run_interleaved_device(h, Samples(d_interleaved, true), n_frames, d_outputs, d_flags, (hipStream_t)hip_stream);
+}
+
+static int run_interleaved_host(syldet *h, Samples x, int64_t n_frames, float *outputs, uint8_t *flags)
+{
     const int C = h->channels;
     const int64_t E = count_evals(h, n_frames);
     if (E <= 0) return SYLDET_OK;
-    if (!interleaved) return fail(SYLDET_ERR_INVALID_ARGUMENT, "NULL buffer");
+    if (!x.p) return fail(SYLDET_ERR_INVALID_ARGUMENT, "NULL buffer");
     std::lock_guard<std::mutex> staging(h->pump_mu);   // the staging buffers and h->stream: one user at a time
     SYLDET_HIP(hipSetDevice(h->device));
-    const size_t in_bytes = (size_t)C * (size_t)n_frames * sizeof(float);
+    const size_t in_bytes = (size_t)C * (size_t)n_frames * (x.s16 ? sizeof(int16_t) : sizeof(float));
     const size_t out_bytes = (size_t)C * (size_t)E * (size_t)h->geom.outputs * sizeof(float);
     const size_t fl_bytes = (size_t)C * (size_t)E;
     if (int st = h->d_stage_in.reserve(in_bytes)) return st;
     if (int st = h->d_stage_out.reserve(out_bytes)) return st;
     if (int st = h->d_stage_flags.reserve(fl_bytes)) return st;
-    SYLDET_HIP(hipMemcpyAsync(h->d_stage_in.ptr, interleaved, in_bytes, hipMemcpyHostToDevice, h->stream));
-    if (int st = syldet_run_interleaved_device(h, (const float *)h->d_stage_in.ptr, n_frames, total_channels,
-                                               (float *)h->d_stage_out.ptr, (uint8_t *)h->d_stage_flags.ptr, h->stream))
+    SYLDET_HIP(hipMemcpyAsync(h->d_stage_in.ptr, x.p, in_bytes, hipMemcpyHostToDevice, h->stream));
+    if (int st = run_interleaved_device(h, Samples(h->d_stage_in.ptr, x.s16), n_frames, (float *)h->d_stage_out.ptr,
+                                        (uint8_t *)h->d_stage_flags.ptr, h->stream))
         return st;
     if (outputs) SYLDET_HIP(hipMemcpyAsync(outputs, h->d_stage_out.ptr, out_bytes, hipMemcpyDeviceToHost, h->stream));
     if (flags) SYLDET_HIP(hipMemcpyAsync(flags, h->d_stage_flags.ptr, fl_bytes, hipMemcpyDeviceToHost, h->stream));
     SYLDET_HIP(hipStreamSynchronize(h->stream));
     return SYLDET_OK;
+}
+
+int syldet_run_interleaved(syldet_t *h, const float *interleaved, int64_t n_frames, int32_t total_channels, float *outputs,
+                           uint8_t *flags)
+{
+    if (int st = interleaved_args(h, n_frames, total_channels)) return st;
+    return run_interleaved_host(h, interleaved, n_frames, outputs, flags);
+}
+
+int syldet_run_interleaved_s16(syldet_t *h, const int16_t *interleaved, int64_t n_frames, int32_t total_channels, float *outputs,
+                               uint8_t *flags)
+{
+    if (int st = interleaved_args(h, n_frames, total_channels)) return st;
+    return run_interleaved_host(h, Samples(interleaved, true), n_frames, outputs, flags);
 }
 
 int syldet_spectrogram(syldet_t *h, const float *samples, int64_t n_samples, int64_t channel_stride, float *columns)
@@ -1847,7 +1966,10 @@ int syldet_detections(syldet_t *h, const uint8_t *flags, int64_t n_evals, double
 // the consumer asks for a value and none is queued, every evaluation those samples allow
 // is computed in one device pass and queued.  Results are the batch engine's.
 
-int syldet_append(syldet_t *h, int32_t channel, const float *data, int64_t n_samples)
+// (T: float, or int16_t converted on the way into the fp32 ring: x * 2^-15, exact; the ring's room is counted as for fp32)
+extern "C++" {
+template <class T>
+static int append_impl(syldet *h, int32_t channel, const T *data, int64_t n_samples)
 {
     if (!h || channel < 0 || channel >= h->channels || n_samples < 0 || (n_samples > 0 && !data))
         return fail(SYLDET_ERR_INVALID_ARGUMENT, "bad argument");
@@ -1858,7 +1980,8 @@ int syldet_append(syldet_t *h, int32_t channel, const float *data, int64_t n_sam
     return SYLDET_OK;
 }
 
-int syldet_append_interleaved(syldet_t *h, const float *data, int64_t n_frames, int32_t total_channels)
+template <class T>
+static int append_interleaved_impl(syldet *h, const T *data, int64_t n_frames, int32_t total_channels)
 {
     if (!h || n_frames < 0 || (n_frames > 0 && !data) || total_channels != h->channels)
         return fail(SYLDET_ERR_INVALID_ARGUMENT, "bad argument");
@@ -1870,6 +1993,27 @@ int syldet_append_interleaved(syldet_t *h, const float *data, int64_t n_frames, 
         if (!h->streams[(size_t)c]->ensure_ring()) return fail(SYLDET_ERR_OUT_OF_MEMORY, "out of memory");
     for (int c = 0; c < h->channels; c++) h->streams[(size_t)c]->write(data + c, n_frames, total_channels);
     return SYLDET_OK;
+}
+}  // extern "C++"
+
+int syldet_append(syldet_t *h, int32_t channel, const float *data, int64_t n_samples)
+{
+    return append_impl(h, channel, data, n_samples);
+}
+
+int syldet_append_s16(syldet_t *h, int32_t channel, const int16_t *data, int64_t n_samples)
+{
+    return append_impl(h, channel, data, n_samples);
+}
+
+int syldet_append_interleaved(syldet_t *h, const float *data, int64_t n_frames, int32_t total_channels)
+{
+    return append_interleaved_impl(h, data, n_frames, total_channels);
+}
+
+int syldet_append_interleaved_s16(syldet_t *h, const int16_t *data, int64_t n_frames, int32_t total_channels)
+{
+    return append_interleaved_impl(h, data, n_frames, total_channels);
 }
 
 int syldet_append_interleaved_channels(syldet_t *h, const float *data, int64_t n_frames, int32_t total_channels, const int32_t *source_channel)

@@ -138,6 +138,17 @@ class SyllableDetector:
         check(_abi.lib.syldet_append_interleaved_channels(self._h, a.ctypes.data_as(_abi.c_float_p), a.shape[0], a.shape[1],
                                                           src.ctypes.data_as(_abi.C.POINTER(_abi.C.c_int32))))
 
+    def appendAudioDataPCM16(self, data, channel: int = 0) -> None:
+        """appendAudioData for 16-bit PCM (syldet_append_s16): an int16 array whose sample x means x / 32768, converted exactly on
+        the way into the channel's fp32 ring."""
+        a = np.ascontiguousarray(_pcm16(data))
+        check(_abi.lib.syldet_append_s16(self._h, channel, a.ctypes.data_as(_abi.c_int16_p), a.size))
+
+    def appendInterleavedDataPCM16(self, data) -> None:
+        """appendInterleavedData for 16-bit PCM (syldet_append_interleaved_s16): int16 `data` [frames, channels]."""
+        a = np.ascontiguousarray(_pcm16(data)).reshape(-1, self.channels)
+        check(_abi.lib.syldet_append_interleaved_s16(self._h, a.ctypes.data_as(_abi.c_int16_p), a.shape[0], self.channels))
+
     def processNewValue(self, channel: int = 0) -> bool:
         return check(_abi.lib.syldet_process_new_value(self._h, channel)) == 1
 
@@ -215,6 +226,46 @@ class SyllableDetector:
                                          outputs.data_ptr(), flags.data_ptr(), self._stream_ptr(stream)))
         return outputs, flags
 
+    def runPCM16(self, samples, outputs=None, flags=None, stream=None):
+        """16-bit PCM samples [C, S] (an int16 CUDA tensor, x meaning x / 32768) -> (outputs, flags) like run(), bit for bit what
+        run() gives for samples.float() * 2**-15 (syldet_run_device_s16)."""
+        torch = _torch()
+        if not (samples.is_cuda and samples.dtype == torch.int16 and samples.dim() == 2):
+            raise ValueError("samples must be a 2-D int16 CUDA tensor [channels, n_samples]")
+        if samples.shape[0] != self.channels or samples.stride(1) != 1:
+            raise ValueError("samples must have one contiguous row per channel")
+        if samples.device.index != self.device:
+            raise ValueError("samples live on a different device than the detector")
+        S = int(samples.shape[1])
+        E = self.countEvaluations(S)
+        self._check_results(outputs, flags, E, samples.device)
+        if outputs is None:
+            outputs = torch.empty((self.channels, E, self.geometry.outputs), dtype=torch.float32, device=samples.device)
+        if flags is None:
+            flags = torch.empty((self.channels, E), dtype=torch.uint8, device=samples.device)
+        check(_abi.lib.syldet_run_device_s16(self._h, samples.data_ptr(), S, int(samples.stride(0)),
+                                             outputs.data_ptr(), flags.data_ptr(), self._stream_ptr(stream)))
+        return outputs, flags
+
+    def runInterleavedPCM16(self, frames, outputs=None, flags=None, stream=None):
+        """16-bit PCM frames [n, C] (an int16 CUDA tensor) -> (outputs, flags) like runInterleaved() on frames.float() * 2**-15
+        (syldet_run_interleaved_device_s16)."""
+        torch = _torch()
+        if not (frames.is_cuda and frames.dtype == torch.int16 and frames.dim() == 2 and frames.is_contiguous()):
+            raise ValueError("frames must be a contiguous 2-D int16 CUDA tensor [n_frames, channels]")
+        if frames.shape[1] != self.channels or frames.device.index != self.device:
+            raise ValueError("frames must have one column per channel and live on the detector's device")
+        n = int(frames.shape[0])
+        E = max(self.countEvaluations(n), 0)
+        self._check_results(outputs, flags, E, frames.device)
+        if outputs is None:
+            outputs = torch.empty((self.channels, E, self.geometry.outputs), dtype=torch.float32, device=frames.device)
+        if flags is None:
+            flags = torch.empty((self.channels, E), dtype=torch.uint8, device=frames.device)
+        check(_abi.lib.syldet_run_interleaved_device_s16(self._h, frames.data_ptr(), n, self.channels, outputs.data_ptr(),
+                                                         flags.data_ptr(), self._stream_ptr(stream)))
+        return outputs, flags
+
     def runInterleaved(self, frames, outputs=None, flags=None, stream=None):
         """frames [n, C] (frame-major, as a decoder delivers audio) -> (outputs, flags) like run()."""
         torch = _torch()
@@ -241,6 +292,17 @@ class SyllableDetector:
         fl = np.zeros((self.channels, E), np.uint8)
         check(_abi.lib.syldet_run_interleaved(self._h, a.ctypes.data_as(_abi.c_float_p), n, self.channels,
                                               out.ctypes.data_as(_abi.c_float_p), fl.ctypes.data_as(_abi.c_uint8_p)))
+        return out, fl
+
+    def runInterleavedPCM16Host(self, frames: np.ndarray) -> Tuple[np.ndarray, np.ndarray]:
+        """runInterleavedHost for 16-bit PCM: int16 frames [n, C] (syldet_run_interleaved_s16; half the bytes cross the bus)."""
+        a = np.ascontiguousarray(_pcm16(frames)).reshape(-1, self.channels)
+        n = a.shape[0]
+        E = max(self.countEvaluations(n), 0)
+        out = np.zeros((self.channels, E, self.geometry.outputs), np.float32)
+        fl = np.zeros((self.channels, E), np.uint8)
+        check(_abi.lib.syldet_run_interleaved_s16(self._h, a.ctypes.data_as(_abi.c_int16_p), n, self.channels,
+                                                  out.ctypes.data_as(_abi.c_float_p), fl.ctypes.data_as(_abi.c_uint8_p)))
         return out, fl
 
     def spectrogram(self, samples, stream=None):
@@ -306,8 +368,18 @@ class SyllableDetector:
     # ---- batch, host arrays -------------------------------------------------------
     def runHost(self, samples: np.ndarray, outputs: Optional[np.ndarray] = None, flags: Optional[np.ndarray] = None) -> Tuple[np.ndarray, np.ndarray]:
         """syldet_run: the batch call on host arrays, pipelined along time inside the library.  `outputs` / `flags`: arrays to
-        write into (e.g. bank.PinnedArray views, which the DMA engines write in place)."""
+        write into (e.g. bank.PinnedArray views, which the DMA engines write in place).  Any array is cast to float32 as it is:
+        an np.int16 recording becomes integer-valued samples, not x / 32768 -- 16-bit PCM goes to runPCM16Host."""
         a = np.ascontiguousarray(samples, dtype=np.float32).reshape(self.channels, -1)
+        return self._run_host(_abi.lib.syldet_run, a, _abi.c_float_p, outputs, flags)
+
+    def runPCM16Host(self, samples: np.ndarray, outputs: Optional[np.ndarray] = None, flags: Optional[np.ndarray] = None) -> Tuple[np.ndarray, np.ndarray]:
+        """syldet_run_s16: runHost for 16-bit PCM, an int16 array [C, S] whose sample x means x / 32768 -- runHost's bits for
+        samples * 2**-15, with half the bytes crossing the bus (a bank.PinnedArray of int16 is copied in place)."""
+        a = np.ascontiguousarray(_pcm16(samples)).reshape(self.channels, -1)
+        return self._run_host(_abi.lib.syldet_run_s16, a, _abi.c_int16_p, outputs, flags)
+
+    def _run_host(self, fn, a, ptr_type, outputs, flags):
         S = a.shape[1]
         E = max(self.countEvaluations(S), 0)
         out = outputs if outputs is not None else np.zeros((self.channels, E, self.geometry.outputs), np.float32)
@@ -316,8 +388,7 @@ class SyllableDetector:
             raise ValueError("outputs must be a C-contiguous float32 array [channels, E, outputs]")
         if fl.shape != (self.channels, E) or fl.dtype != np.uint8 or not fl.flags.c_contiguous:
             raise ValueError("flags must be a C-contiguous uint8 array [channels, E]")
-        check(_abi.lib.syldet_run(self._h, a.ctypes.data_as(_abi.c_float_p), S, S,
-                                  out.ctypes.data_as(_abi.c_float_p), fl.ctypes.data_as(_abi.c_uint8_p)))
+        check(fn(self._h, a.ctypes.data_as(ptr_type), S, S, out.ctypes.data_as(_abi.c_float_p), fl.ctypes.data_as(_abi.c_uint8_p)))
         return out, fl
 
     def spectrogramHost(self, samples: np.ndarray) -> np.ndarray:
@@ -338,6 +409,14 @@ class SyllableDetector:
         check(_abi.lib.syldet_detections(self._h, f.ctypes.data_as(_abi.c_uint8_p), E, float(debounce),
                                          idx.ctypes.data_as(_abi.c_int64_p), cap, cnt.ctypes.data_as(_abi.c_int64_p)))
         return idx, cnt
+
+
+def _pcm16(data) -> np.ndarray:
+    """16-bit PCM as given: an int16 array (never a cast -- a float recording is not PCM)."""
+    a = np.asarray(data)
+    if a.dtype != np.int16:
+        raise ValueError("16-bit PCM must be an int16 array (got %s)" % a.dtype)
+    return a
 
 
 def configsCompatible(a: SyllableDetectorConfig, b: SyllableDetectorConfig) -> Tuple[bool, Optional[str]]:
