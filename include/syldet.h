@@ -287,6 +287,41 @@ int syldet_detections_device(syldet_t *h, const uint8_t *d_flags, int64_t n_eval
 int syldet_detections(syldet_t *h, const uint8_t *flags, int64_t n_evals, double debounce_seconds,
                       int64_t *indices, int64_t capacity, int64_t *counts);
 
+/* ---- the Simulator's output track (SyllableDetector/ViewControllerSimulator.swift:251-344) ----
+ * simulateNetwork writes a second audio file of the recording's length and rate whose samples are output 0 as a fraction of
+ * its threshold, held from one evaluation to the next (:322-343).  With D = first_index (the Simulator's nextCount, :251-254,
+ * TrackDetector.swift:39-42's number) and hop = windowLength - windowOverlap (the hold, :331):
+ *   v[e]     = clamp01(out[e][output] / Float(thresholds[output]))     fp32 division (:322); clamp01 is two comparisons
+ *                                                                      (:323-328): v > 1 -> 1, v < 0 -> 0, else unchanged --
+ *                                                                      NaN stays NaN, x / 0 is 1 or 0 by its sign
+ *   trace[s] = 0 for s < D;  v[(s - D) / hop] for D <= s < D + n_evals hop;  0 beyond
+ * d_outputs [C][n_evals][outputs] as syldet_run_device wrote them; d_trace [C][trace_stride], the first n_samples of each row
+ * are written and nothing else.  n_evals and n_samples are independent (with n_evals = syldet_count_evals(n_samples) the
+ * last hold reaches n_samples or beyond: no sample lies behind it).  `output` picks the output (0: the Simulator's).  On
+ * syldet_create_multi / syldet_create_mixed banks channel c divides by its own network's threshold.  The fp32 form is the
+ * reference's, bit for bit.  The 16-bit form is THIS LIBRARY'S convention (the reference hands its floats to AVFoundation's
+ * 16-bit file writer, :206-218, whose rounding is not specified):
+ *   q = (int16) rint(v * 32767), ties to even, computed in fp32 without contraction, NaN -> 0
+ * so 0 <-> 0 and the threshold and everything above it <-> 32767.  One kernel launch a call (syldet_timings lists it as
+ * "trace_kernel", the frame-major form of two or more channels as "trace_interleaved_s16_kernel"); the [C] table of
+ * Float(thresholds[output]) is made on the first call for that output (a blocking copy) and kept by the handle.
+ * Statuses, before any device is touched: SYLDET_ERR_INVALID_ARGUMENT for a NULL handle or pointer, n_evals < 0, n_samples < 0,
+ * trace_stride < n_samples, output outside [0, outputs).  n_samples == 0 writes nothing; n_evals == 0 writes rows of zeros.
+ * The device forms follow the handle's rule of one stream at a time.                                                        */
+int syldet_trace_device(syldet_t *h, const float *d_outputs, int64_t n_evals, int32_t output,
+                        float *d_trace, int64_t n_samples, int64_t trace_stride, void *hip_stream);
+int syldet_trace_device_s16(syldet_t *h, const float *d_outputs, int64_t n_evals, int32_t output,
+                            int16_t *d_trace, int64_t n_samples, int64_t trace_stride, void *hip_stream);
+/* d_frames [n_samples][C] int16: what a 16-bit WAV of C tracks stores (simulateNetwork writes 16-bit linear PCM, :187-218;
+ * here every track at once); equal to syldet_trace_device_s16's rows, transposed (one channel: the planar kernel)         */
+int syldet_trace_interleaved_device_s16(syldet_t *h, const float *d_outputs, int64_t n_evals, int32_t output,
+                                        int16_t *d_frames, int64_t n_samples, void *hip_stream);
+/* host pointers, blocking (as syldet_detections is to syldet_detections_device) */
+int syldet_trace(syldet_t *h, const float *outputs, int64_t n_evals, int32_t output,
+                 float *trace, int64_t n_samples, int64_t trace_stride);
+int syldet_trace_s16(syldet_t *h, const float *outputs, int64_t n_evals, int32_t output,
+                     int16_t *trace, int64_t n_samples, int64_t trace_stride);
+
 /* ---- measurement (replaces the reference's Time stopwatch, SyllableDetector/Time.swift:36-100,
  * which wraps processNewValue in ViewControllerSimulator.swift:309-319) ----
  * With profiling enabled every kernel of a batch call is bracketed by HIP events on the stream it

@@ -178,6 +178,28 @@ public:
         return std::vector<int64_t>(idx.begin() + (size_t)channel * (size_t)nEvals,
                                     idx.begin() + (size_t)channel * (size_t)nEvals + (size_t)counts[(size_t)channel]);
     }
+    // The Simulator's output track (ViewControllerSimulator.swift:251-344): output `output` of every channel as a fraction of
+    // its threshold, held from one evaluation to the next, one value per sample: trace [channels][n] from outputs
+    // [channels][nEvals][outputs] (host buffers, blocking)
+    std::vector<float> trace(const float *outputs, int64_t nEvals, int64_t n, int32_t output = 0)
+    {
+        std::vector<float> t((size_t)channels() * (size_t)n);
+        check(syldet_trace(h_, outputs, nEvals, output, t.data(), n, n));
+        return t;
+    }
+    // device buffers, asynchronous on `hipStream`: fp32 rows, 16-bit rows (rint(v * 32767)), 16-bit frames [n][channels]
+    void traceDevice(const float *d_outputs, int64_t nEvals, int32_t output, float *d_trace, int64_t n, int64_t stride, void *hipStream)
+    {
+        check(syldet_trace_device(h_, d_outputs, nEvals, output, d_trace, n, stride, hipStream));
+    }
+    void traceDevicePCM16(const float *d_outputs, int64_t nEvals, int32_t output, int16_t *d_trace, int64_t n, int64_t stride, void *hipStream)
+    {
+        check(syldet_trace_device_s16(h_, d_outputs, nEvals, output, d_trace, n, stride, hipStream));
+    }
+    void traceInterleavedDevicePCM16(const float *d_outputs, int64_t nEvals, int32_t output, int16_t *d_frames, int64_t n, void *hipStream)
+    {
+        check(syldet_trace_interleaved_device_s16(h_, d_outputs, nEvals, output, d_frames, n, hipStream));
+    }
     syldet_t *raw() { return h_; }
 
 private:

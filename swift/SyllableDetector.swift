@@ -43,6 +43,18 @@ final class SyllableDetectorBank {
         syldet_process_all(handle, &queued)
         return Int(queued)
     }
+
+    /// simulateNetwork (ViewControllerSimulator.swift:251-344) for every channel: the outputs, the flags and the 16-bit output
+    /// track [channels][n] (output 0 over its threshold, held between evaluations) of a whole recording.
+    func simulate(samples: UnsafePointer<Float>, samplesPerChannel n: Int) -> (trace: [Int16], outputs: [Float], flags: [UInt8]) {
+        let c = Int(syldet_channels(handle)), e = max(0, Int(syldet_count_evals(handle, Int64(n))))
+        var outputs = [Float](repeating: 0, count: max(1, c * e * Int(geometry.outputs)))
+        var flags = [UInt8](repeating: 0, count: max(1, c * e)), trace = [Int16](repeating: 0, count: max(1, c * n))
+        var st = syldet_run(handle, samples, Int64(n), Int64(n), &outputs, &flags)
+        if st == 0 { st = syldet_trace_s16(handle, outputs, Int64(e), 0, &trace, Int64(n), Int64(n)) }
+        if st != 0 { fatalError(String(cString: syldet_strerror(st)) + ": " + String(cString: syldet_last_error())) }
+        return (trace, outputs, flags)
+    }
 }
 
 /// One bank over several MI355X of this host, one process: the reference is one process that owns every channel

@@ -118,6 +118,11 @@ SIGNATURES = {
     "syldet_spectrogram": (C.c_int, [Handle, c_float_p, C.c_int64, C.c_int64, c_float_p]),
     "syldet_detections_device": (C.c_int, [Handle, C.c_void_p, C.c_int64, C.c_double, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
     "syldet_detections": (C.c_int, [Handle, c_uint8_p, C.c_int64, C.c_double, c_int64_p, C.c_int64, c_int64_p]),
+    "syldet_trace_device": (C.c_int, [Handle, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p]),
+    "syldet_trace_device_s16": (C.c_int, [Handle, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p]),
+    "syldet_trace_interleaved_device_s16": (C.c_int, [Handle, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p]),
+    "syldet_trace": (C.c_int, [Handle, c_float_p, C.c_int64, C.c_int32, c_float_p, C.c_int64, C.c_int64]),
+    "syldet_trace_s16": (C.c_int, [Handle, c_float_p, C.c_int64, C.c_int32, c_int16_p, C.c_int64, C.c_int64]),
     "syldet_profile": (C.c_int, [Handle, C.c_int]),
     "syldet_last_timings": (C.c_int, [Handle, c_double_p, C.POINTER(C.c_char_p), C.c_int32, c_int32_p]),
     "syldet_profile_history": (C.c_int, [Handle, C.c_int32]),

@@ -7,6 +7,8 @@
 // file's rate differs from the network's] -> fused STFT + network kernel -> flags/outputs -> host.
 // 16-bit PCM at the network's rate crosses the bus and is de-interleaved as int16 (the library's *_s16 entry points give
 // the fp32 path's bits on x / 32768, which is what the decoder would have produced).
+// --simulate <out.wav> also writes what the reference's Simulator writes (ViewControllerSimulator.swift:251-344): the chosen output
+// over its threshold, held between evaluations, as a 16-bit WAV of every track (syldet_trace_interleaved_device_s16).
 //
 // Differences a user can see: the reference decodes anything AVFoundation can, this tool reads WAV; the
 // reference has Core Audio deliver the network's rate (SyllableDetector.swift:19-23), this tool converts the decoded
@@ -35,13 +37,15 @@ constexpr int kExUsage = 64;   // EX_USAGE, main.swift:40
 void usage(FILE *to)
 {
     std::fprintf(to,
-                 "Usage: syllable-detector-cli -n <net> [-a <audio>]... [-d <seconds>] [--device <k>] [--chunk <frames>] [--format <shortest|swift4>] [--probe]\n"
+                 "Usage: syllable-detector-cli -n <net> [-a <audio>]... [-d <seconds>] [--device <k>] [--chunk <frames>] [--format <shortest|swift4>] [--simulate <out.wav>] [--simulate-output <k>] [--probe]\n"
                  "  -n, --net <net>:\n      Path to trained network file.  Given k > 1 times: each file must have exactly k tracks, and track t runs network t (one mixed bank; the networks must share the sampling rate, window length, window overlap, time range and number of outputs).\n"
                  "  -a, --audio <audio>:\n      Path to the audio file to process.\n"
                  "  -d, --debounce <seconds>:\n      Number of seconds to debounce triggers.\n"
                  "      --device <k>:\n      HIP device to run on (default 0).\n"
                  "      --chunk <frames>:\n      Frames per decode buffer when interleaving events of several channels (default 8192; 0: channel by channel).\n"
                  "      --format <shortest|swift4>:\n      How numbers are printed: the shortest digits that round-trip (Swift 4.2 and later; default) or 15 / 6 significant digits (Swift 4.0, the toolchain the project declares: the example line below).\n"
+                 "      --simulate <out.wav>:\n      Also write the Simulator's output track of every track of the (one) audio file as a 16-bit WAV at the network's sampling rate: the chosen output as a fraction of its threshold (0 = 0, threshold and above = 32767), held from one evaluation to the next.\n"
+                 "      --simulate-output <k>:\n      The network output --simulate follows (default 0).\n"
                  "      --probe:\n      Only print what the audio files contain; does not touch the GPU.\n"
                  "The command line will write a comma-separated list of detection events (when the network has at least one output above threshold) to standard out. For example, it might output:\n"
                  "\n\t0,1593298,36.1292063492063,0.918557\n\n"
@@ -91,7 +95,11 @@ struct Event { int64_t buffer; int channel; int64_t sample; int64_t eval; };
 
 // cfgs: one network for every track, or (k > 1) network t for track t of a file of exactly k tracks, through one mixed bank
 // (syldet_create_mixed): the networks share the evaluation clock, so the events are found and printed as for one
-int process_file(const std::string &path, const std::vector<syldet_config_t *> &cfgs, int device, double debounce_s, bool have_debounce, int64_t chunk)
+// simulate: a path for the Simulator's output track (ViewControllerSimulator.swift:251-344) of every track, made on the device from
+// the outputs the run left there (syldet_trace_interleaved_device_s16) and written as a 16-bit WAV of as many frames as the detector
+// was fed, at the network's rate; empty: none
+int process_file(const std::string &path, const std::vector<syldet_config_t *> &cfgs, int device, double debounce_s, bool have_debounce, int64_t chunk,
+                 const std::string &simulate = std::string(), int simulate_output = 0)
 {
     const syldet_config_t *cfg = cfgs[0];
     wav::Info info;
@@ -131,7 +139,8 @@ int process_file(const std::string &path, const std::vector<syldet_config_t *> &
     hipStream_t stream = nullptr;
     std::vector<float> out;
     std::vector<uint8_t> flags;
-    int64_t E = 0;
+    std::vector<int16_t> track;
+    int64_t E = 0, fed = 0;
     do {
         if (hipSetDevice(device) != hipSuccess || hipStreamCreate(&stream) != hipSuccess) { rc = 2; break; }
         const int64_t n = info.frames;
@@ -156,6 +165,12 @@ int process_file(const std::string &path, const std::vector<syldet_config_t *> &
             }
         }
         E = syldet_count_evals(h, S);
+        fed = S;
+        DevBuf d_track;
+        if (E <= 0 && !simulate.empty()) {                   // shorter than one evaluation: a track of zeros
+            track.assign((size_t)S * C, 0);
+            break;
+        }
         if (E <= 0) break;                                  // shorter than one evaluation: no events
         if (!d_out.alloc((size_t)C * E * n_out * sizeof(float)) || !d_flags.alloc((size_t)C * E)) { rc = 2; break; }
         if (pcm16) st = syldet_run_interleaved_device_s16(h, (const int16_t *)d_inter.p, n, C, (float *)d_out.p, (uint8_t *)d_flags.p, stream);
@@ -166,6 +181,17 @@ int process_file(const std::string &path, const std::vector<syldet_config_t *> &
             rc = 2;
             break;
         }
+        if (!simulate.empty()) {
+            track.resize((size_t)S * C);
+            if (!d_track.alloc(track.size() * sizeof(int16_t))) { rc = 2; break; }
+            st = syldet_trace_interleaved_device_s16(h, (const float *)d_out.p, E, simulate_output, (int16_t *)d_track.p, S, stream);
+            if (st) {
+                std::fprintf(stderr, "Unable to simulate %s: %s: %s\n", path.c_str(), syldet_strerror(st), syldet_last_error());
+                rc = 2;
+                break;
+            }
+            if (hipMemcpyAsync(track.data(), d_track.p, track.size() * sizeof(int16_t), hipMemcpyDeviceToHost, stream) != hipSuccess) { rc = 2; break; }
+        }
         out.resize((size_t)C * E * n_out);
         flags.resize((size_t)C * E);
         if (hipMemcpyAsync(out.data(), d_out.p, out.size() * sizeof(float), hipMemcpyDeviceToHost, stream) != hipSuccess ||
@@ -175,7 +201,16 @@ int process_file(const std::string &path, const std::vector<syldet_config_t *> &
     if (rc == 2 && hipPeekAtLastError() != hipSuccess) std::fprintf(stderr, "Unable to process %s: %s\n", path.c_str(), hipGetErrorString(hipGetLastError()));
     if (stream) (void)hipStreamDestroy(stream);
     syldet_destroy(h);
-    if (rc || E <= 0) return rc;
+    // the track is written behind the detection lines, which a failing write must not cost: 3 = the lines are out, the track is not
+    auto write_track = [&]() -> int {
+        if (simulate.empty()) return 0;
+        std::string werr;
+        if (wav::write_s16(simulate, cfg->sampling_rate, C, fed, track.data(), werr)) return 0;
+        std::fprintf(stderr, "Unable to write %s: %s\n", simulate.c_str(), werr.c_str());
+        return 3;
+    };
+    if (rc) return rc;
+    if (E <= 0) return write_track();
 
     // events: sample number of evaluation e = first_index + e*hop (TrackDetector.swift:39-43,67-68); debounce :80,:99
     const int64_t debounce_frames = have_debounce ? (int64_t)(debounce_s * cfg->sampling_rate) : 0;   // Int(newValue * samplingRate), :24
@@ -202,7 +237,8 @@ int process_file(const std::string &path, const std::vector<syldet_config_t *> &
         for (int o = 0; o < n_out; o++) line += "," + number(out[((size_t)ev.channel * E + ev.eval) * n_out + o]);
         std::puts(line.c_str());
     }
-    return 0;
+    std::fflush(stdout);
+    return write_track();
 }
 
 }  // namespace
@@ -211,6 +247,9 @@ int main(int argc, char **argv)
 {
     std::vector<std::string> net;
     std::vector<std::string> audio;
+    std::string simulate;
+    bool have_simulate = false, have_simulate_output = false;
+    int simulate_output = 0;
     double debounce = 0.0;
     bool have_debounce = false, probe = false;
     int device = 0;
@@ -235,6 +274,21 @@ int main(int argc, char **argv)
         } else if (a == "--device") device = std::atoi(value(i, "--device"));
         else if (a == "--chunk") chunk = std::atoll(value(i, "--chunk"));
         else if (a == "--probe") probe = true;
+        else if (a == "--simulate") {
+            simulate = value(i, "--simulate");
+            have_simulate = true;
+        } else if (a == "--simulate-output") {
+            const char *v = value(i, "--simulate-output");
+            char *end = nullptr;
+            const long k = std::strtol(v, &end, 10);
+            if (end == v || *end != 0 || k < 0 || k > 0x7fffffffL) {
+                std::fprintf(stderr, "--simulate-output takes an output number (0, 1, ...).\n");
+                usage(stdout);
+                return kExUsage;
+            }
+            simulate_output = (int)k;
+            have_simulate_output = true;
+        }
         else if (a == "--format") {
             const std::string f = value(i, "--format");
             if (f != "shortest" && f != "swift4") { usage(stdout); return kExUsage; }
@@ -268,6 +322,16 @@ int main(int argc, char **argv)
         usage(stdout);
         return kExUsage;
     }
+    if (have_simulate && (audio.size() != 1 || simulate.empty())) {   // the Simulator takes one recording (simulateNetwork(_:withAudio:writeTo:), ViewControllerSimulator.swift:135)
+        std::fprintf(stderr, "--simulate writes the track of exactly one audio file (-a).\n");
+        usage(stdout);
+        return kExUsage;
+    }
+    if (have_simulate_output && !have_simulate) {
+        std::fprintf(stderr, "--simulate-output needs --simulate <out.wav>.\n");
+        usage(stdout);
+        return kExUsage;
+    }
     std::vector<syldet_config_t *> cfgs;
     for (const std::string &n : net) {
         syldet_config_t *cfg = nullptr;
@@ -279,12 +343,21 @@ int main(int argc, char **argv)
         cfg->rule = SYLDET_RULE_ANY;                        // any output above its threshold, TrackDetector.swift:72-77
         cfgs.push_back(cfg);
     }
+    if (have_simulate)                                      // (before the GPU is opened)
+        for (syldet_config_t *c : cfgs)
+            if (simulate_output >= c->n_thresholds) {
+                std::fprintf(stderr, "--simulate-output %d: the network has %d output(s).\n", simulate_output, c->n_thresholds);
+                for (syldet_config_t *k : cfgs) syldet_config_free(k);
+                usage(stdout);
+                return kExUsage;
+            }
     int rc = 0;
     for (const std::string &p : audio) {
         if (audio.size() > 1) std::printf("%s\n", p.c_str());   // main.swift:122-124
         std::fflush(stdout);
-        const int r = process_file(p, cfgs, device, debounce, have_debounce, chunk);
+        const int r = process_file(p, cfgs, device, debounce, have_debounce, chunk, simulate, simulate_output);
         if (r == 2) rc = 2;                                 // device trouble is fatal for the exit code; an unreadable file is skipped
+        else if (r == 3 && rc == 0) rc = 1;                 // ... and so is a track that could not be written
     }
     for (syldet_config_t *c : cfgs) syldet_config_free(c);
     return rc;

@@ -3,9 +3,11 @@
 // the container this image can decode without AVFoundation.  PCM 8/16/24/32-bit and IEEE float
 // 32/64-bit, plain or WAVE_FORMAT_EXTENSIBLE, any channel count.  Samples come back frame-major
 // (interleaved) as fp32 in [-1, 1): integer PCM is divided by 2^(bits-1), like Core Audio's converter; read_s16 gives 16-bit
-// PCM as stored.
+// PCM as stored.  write_s16 writes what the Simulator's file writer does for the tool's --simulate (ViewControllerSimulator.swift:187-218:
+// 16-bit linear PCM at the network's rate).
 #pragma once
 
+#include <algorithm>
 #include <cstdint>
 #include <cstdio>
 #include <cstring>
@@ -131,6 +133,38 @@ inline bool read_s16(const std::string &path, Info &info, std::vector<int16_t> &
     out.resize(n);
     for (size_t i = 0; i < n; i++) out[i] = (int16_t)rd16(raw.data() + 2 * i);
     return true;
+}
+
+// Writes `frames` frames of `channels` interleaved 16-bit samples as a canonical WAV: the 44-byte header (RIFF, a 16-byte PCM fmt
+// chunk, data), little endian.  Refuses what a RIFF size field cannot hold (the file would pass 4 GiB).
+inline bool write_s16(const std::string &path, double rate, int channels, int64_t frames, const int16_t *data, std::string &err)
+{
+    if (channels <= 0 || channels > 32767 || frames < 0 || rate < 1.0 || rate > 4294967295.0) { err = "bad arguments"; return false; }
+    const uint64_t bytes = (uint64_t)frames * (uint64_t)channels * 2u;
+    if (bytes + 36u > 0xFFFFFFFFull) { err = "too long for a WAV file (4 GiB)"; return false; }
+    if (frames > 0 && !data) { err = "bad arguments"; return false; }
+    unsigned char h[44];
+    auto wr32 = [](unsigned char *p, uint32_t v) { p[0] = (unsigned char)v; p[1] = (unsigned char)(v >> 8); p[2] = (unsigned char)(v >> 16); p[3] = (unsigned char)(v >> 24); };
+    auto wr16 = [](unsigned char *p, uint32_t v) { p[0] = (unsigned char)v; p[1] = (unsigned char)(v >> 8); };
+    const uint32_t r = (uint32_t)(rate + 0.5), align = (uint32_t)channels * 2u;
+    std::memcpy(h, "RIFF", 4); wr32(h + 4, (uint32_t)(bytes + 36u)); std::memcpy(h + 8, "WAVEfmt ", 8); wr32(h + 16, 16u);
+    wr16(h + 20, 1u); wr16(h + 22, (uint32_t)channels); wr32(h + 24, r); wr32(h + 28, (uint32_t)std::min<uint64_t>((uint64_t)r * align, 0xFFFFFFFFull));
+    wr16(h + 32, align); wr16(h + 34, 16u); std::memcpy(h + 36, "data", 4); wr32(h + 40, (uint32_t)bytes);
+    FILE *f = std::fopen(path.c_str(), "wb");
+    if (!f) { err = "cannot create file"; return false; }
+    bool ok = std::fwrite(h, 1, 44, f) == 44;
+    // (little endian on the wire whatever the host: a chunk of samples at a time)
+    std::vector<unsigned char> buf;
+    const size_t n = (size_t)frames * (size_t)channels, step = 1u << 16;
+    for (size_t i = 0; ok && i < n; i += step) {
+        const size_t m = n - i < step ? n - i : step;
+        buf.resize(2 * m);
+        for (size_t k = 0; k < m; k++) { const uint16_t v = (uint16_t)data[i + k]; buf[2 * k] = (unsigned char)v; buf[2 * k + 1] = (unsigned char)(v >> 8); }
+        ok = std::fwrite(buf.data(), 1, buf.size(), f) == buf.size();
+    }
+    if (std::fclose(f) != 0) ok = false;
+    if (!ok) err = "write failed";
+    return ok;
 }
 
 }  // namespace wav

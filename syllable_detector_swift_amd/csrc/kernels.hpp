@@ -298,6 +298,18 @@ hipError_t launch_deinterleave_s16(const int16_t *in, int64_t n_frames, int tota
 // 16-bit PCM rows [C][in_stride] -> fp32 rows [C][out_stride] of x * 2^-15 (exact); out 16-byte aligned, out_stride % 4 == 0
 hipError_t launch_widen_s16(const int16_t *in, int64_t in_stride, int64_t S, int C, float *out, int64_t out_stride, hipStream_t stream);
 
+// ---- the Simulator's output track (kernels_trace.hip; ViewControllerSimulator.swift:251-344) ----
+// outputs [C][n_evals][n_out], thr [C] = Float(thresholds[k]) of each channel's network -> trace [C][stride] (the first n_samples of
+// each row): 0 in front of first_index, clamp01(out[e][k] / thr[c]) over the hop samples of evaluation e, 0 behind the last one.
+// fp32: the reference's values; int16: rint(v * 32767), NaN -> 0.
+hipError_t launch_trace(const float *outputs, int64_t n_evals, int n_out, int k, const float *thr, int C, float *trace,
+                        int64_t n_samples, int64_t stride, int64_t first_index, int64_t hop, hipStream_t stream);
+hipError_t launch_trace_s16(const float *outputs, int64_t n_evals, int n_out, int k, const float *thr, int C, int16_t *trace,
+                            int64_t n_samples, int64_t stride, int64_t first_index, int64_t hop, hipStream_t stream);
+// the int16 form frame-major, frames [n_frames][C] (one channel: the planar kernel)
+hipError_t launch_trace_interleaved_s16(const float *outputs, int64_t n_evals, int n_out, int k, const float *thr, int C,
+                                        int16_t *frames, int64_t n_frames, int64_t first_index, int64_t hop, hipStream_t stream);
+
 // detection flags <-> bits (bit b of byte t of a row = flag 8 t + b), rows padded to whole bytes
 hipError_t launch_pack_flags(const uint8_t *flags, int64_t rows, int64_t row_len, uint8_t *bits, hipStream_t stream);
 hipError_t launch_unpack_flags(const uint8_t *bits, int64_t rows, int64_t row_len, uint8_t *flags, hipStream_t stream);

@@ -191,6 +191,10 @@ struct syldet {
     std::vector<int> net_of;          // [C] (empty for one network)
     std::vector<double> chan_thr0;    // [C] the first threshold of each channel's network (syldet_last_detected)
     DeviceBuffer d_net_of;            // [C] int
+    // the Simulator's trace (syldet_trace*): channel c divides by Float(thresholds[k]) of its own network
+    std::vector<double> chan_thr;     // [C][outputs] every threshold of each channel's network (multi-network and mixed banks; empty: cfg's for all)
+    std::vector<DeviceBuffer> d_trace_thr;   // [outputs] the [C] fp32 table of output k, made on the first trace of that output
+    DeviceBuffer d_trace;             // the host forms' trace rows on the device
     DeviceBuffer d_fnets;             // per-network fold-kernel tables, then FusedNet[n_nets]
     DeviceBuffer d_stage_net;         // [C] int: net_of of the channels one streaming launch carries
     const FusedNet *fnets = nullptr;  // (in d_fnets) null unless the handle runs the fold kernel's multi-network form
@@ -1349,7 +1353,11 @@ static int create_multi_impl(const syldet_config_t *const *cfgs, int32_t n_nets,
         }
         h->n_nets = n_nets;
         h->net_of.assign(channel_net, channel_net + n_channels);
-        for (int32_t c = 0; c < n_channels; c++) h->chan_thr0.push_back(own[(size_t)channel_net[c]]->view.thresholds[0]);
+        for (int32_t c = 0; c < n_channels; c++) {
+            const syldet_config_t &v = own[(size_t)channel_net[c]]->view;
+            h->chan_thr0.push_back(v.thresholds[0]);
+            h->chan_thr.insert(h->chan_thr.end(), v.thresholds, v.thresholds + v.n_thresholds);
+        }
         if (int st = h->d_net_of.reserve((size_t)n_channels * sizeof(int))) return st;
         SYLDET_HIP(hipMemcpy(h->d_net_of.ptr, h->net_of.data(), (size_t)n_channels * sizeof(int), hipMemcpyHostToDevice));
         if (int st = upload_generic_nets(h.get(), own)) return st;
@@ -1502,7 +1510,11 @@ int syldet_create_mixed(const syldet_config_t *const *cfgs, int32_t n_nets, cons
         }
         h->class_of = std::move(class_of);
         h->local_of = std::move(local_of);
-        for (int32_t c = 0; c < n_channels; c++) h->chan_thr0.push_back(cfgs[channel_net[c]]->thresholds[0]);
+        for (int32_t c = 0; c < n_channels; c++) {
+            const syldet_config_t *v = cfgs[channel_net[c]];
+            h->chan_thr0.push_back(v->thresholds[0]);
+            h->chan_thr.insert(h->chan_thr.end(), v->thresholds, v->thresholds + v->n_thresholds);
+        }
     } catch (const std::bad_alloc &) {
         return fail(SYLDET_ERR_OUT_OF_MEMORY, "out of memory");
     }
@@ -1543,6 +1555,8 @@ int syldet_destroy(syldet_t *h)
     for (DeviceBuffer *b : {&h->d_window, &h->d_tw, &h->d_sw, &h->d_params, &h->d_thr, &h->d_columns, &h->d_fused, &h->d_mlpx, &h->d_stamps, &h->d_fix, &h->d_ctab, &h->d_planar, &h->d_widen, &h->d_wide, &h->d_xn, &h->d_dft, &h->d_net_of, &h->d_fnets, &h->d_stage_net, &h->d_stage_in,
                             &h->d_stage_out, &h->d_stage_flags, &h->d_stage_idx, &h->d_stage_cnt})
         b->release();
+    h->d_trace.release();
+    for (DeviceBuffer &b : h->d_trace_thr) b.release();
     h->p_stage_in.release();
     h->p_stage_out.release();
     for (int b = 0; b < 2; b++) {
@@ -1957,6 +1971,125 @@ int syldet_detections(syldet_t *h, const uint8_t *flags, int64_t n_evals, double
     SYLDET_HIP(hipMemcpyAsync(counts, h->d_stage_cnt.ptr, (size_t)C * sizeof(int64_t), hipMemcpyDeviceToHost, h->stream));
     SYLDET_HIP(hipStreamSynchronize(h->stream));
     return SYLDET_OK;
+}
+
+// ---- the Simulator's output track (ViewControllerSimulator.swift:251-344; kernels_trace.hip) ----
+
+static int trace_args(const syldet *h, const void *outputs, int64_t n_evals, int32_t output, const void *trace, int64_t n_samples,
+                      int64_t trace_stride)
+{
+    if (!h || !outputs || !trace) return fail(SYLDET_ERR_INVALID_ARGUMENT, "NULL argument");
+    if (n_evals < 0 || n_samples < 0) return fail(SYLDET_ERR_INVALID_ARGUMENT, "negative size");
+    if (trace_stride < n_samples) return fail(SYLDET_ERR_INVALID_ARGUMENT, "trace_stride < n_samples");
+    if (output < 0 || output >= h->geom.outputs) return fail(SYLDET_ERR_INVALID_ARGUMENT, "output outside [0, outputs)");
+    return SYLDET_OK;
+}
+
+// Float(thresholds[k]) of every channel's own network on the device: made on the first trace of output k, kept by the handle
+static int trace_thresholds(syldet *h, int k, const float **out)
+{
+    try {
+        if (h->d_trace_thr.empty()) h->d_trace_thr.resize((size_t)h->geom.outputs);
+        DeviceBuffer &b = h->d_trace_thr[(size_t)k];
+        if (!b.ptr) {
+            const int C = h->channels, n_out = h->geom.outputs;
+            std::vector<float> t((size_t)C);
+            for (int c = 0; c < C; c++)
+                t[(size_t)c] = (float)(h->chan_thr.empty() ? h->cfg.view.thresholds[k] : h->chan_thr[(size_t)c * (size_t)n_out + (size_t)k]);
+            if (int st = b.reserve((size_t)C * sizeof(float))) return st;
+            if (hipError_t e = hipMemcpy(b.ptr, t.data(), (size_t)C * sizeof(float), hipMemcpyHostToDevice)) {
+                b.release();
+                return fail(SYLDET_ERR_DEVICE, std::string("hipMemcpy: ") + hipGetErrorString(e));
+            }
+        }
+        *out = (const float *)b.ptr;
+    } catch (const std::bad_alloc &) {
+        return fail(SYLDET_ERR_OUT_OF_MEMORY, "out of memory");
+    }
+    return SYLDET_OK;
+}
+
+// T: float or int16_t rows [C][stride]; frames: int16 [n_samples][C] instead
+extern "C++" {
+template <class T>
+static int trace_on_stream(syldet *h, const float *d_outputs, int64_t n_evals, int32_t k, T *d_trace, int64_t n_samples, int64_t stride,
+                           bool frames, hipStream_t stream)
+{
+    if (n_samples == 0) return SYLDET_OK;
+    SYLDET_HIP(hipSetDevice(h->device));
+    const float *thr = nullptr;
+    if (int st = trace_thresholds(h, k, &thr)) return st;
+    const int C = h->channels, n_out = h->geom.outputs;
+    const int64_t D = h->geom.first_index, hop = h->geom.hop;
+    h->prof_begin();
+    if constexpr (sizeof(T) == 2) {
+        if (frames) {
+            KernelTimer t(h, stream, C == 1 ? "trace_kernel" : "trace_interleaved_s16_kernel");   // (one channel: launch_trace_interleaved_s16 runs the planar kernel)
+            SYLDET_HIP(launch_trace_interleaved_s16(d_outputs, n_evals, n_out, k, thr, C, d_trace, n_samples, D, hop, stream));
+            return SYLDET_OK;
+        }
+        KernelTimer t(h, stream, "trace_kernel");
+        SYLDET_HIP(launch_trace_s16(d_outputs, n_evals, n_out, k, thr, C, d_trace, n_samples, stride, D, hop, stream));
+    } else {
+        KernelTimer t(h, stream, "trace_kernel");
+        SYLDET_HIP(launch_trace(d_outputs, n_evals, n_out, k, thr, C, d_trace, n_samples, stride, D, hop, stream));
+    }
+    return SYLDET_OK;
+}
+}
+
+int syldet_trace_device(syldet_t *h, const float *d_outputs, int64_t n_evals, int32_t output, float *d_trace, int64_t n_samples,
+                        int64_t trace_stride, void *hip_stream)
+{
+    if (int st = trace_args(h, d_outputs, n_evals, output, d_trace, n_samples, trace_stride)) return st;
+    return trace_on_stream(h, d_outputs, n_evals, output, d_trace, n_samples, trace_stride, false, (hipStream_t)hip_stream);
+}
+
+int syldet_trace_device_s16(syldet_t *h, const float *d_outputs, int64_t n_evals, int32_t output, int16_t *d_trace, int64_t n_samples,
+                            int64_t trace_stride, void *hip_stream)
+{
+    if (int st = trace_args(h, d_outputs, n_evals, output, d_trace, n_samples, trace_stride)) return st;
+    return trace_on_stream(h, d_outputs, n_evals, output, d_trace, n_samples, trace_stride, false, (hipStream_t)hip_stream);
+}
+
+int syldet_trace_interleaved_device_s16(syldet_t *h, const float *d_outputs, int64_t n_evals, int32_t output, int16_t *d_frames,
+                                        int64_t n_samples, void *hip_stream)
+{
+    if (int st = trace_args(h, d_outputs, n_evals, output, d_frames, n_samples, n_samples)) return st;
+    return trace_on_stream(h, d_outputs, n_evals, output, d_frames, n_samples, n_samples, true, (hipStream_t)hip_stream);
+}
+
+extern "C++" {
+template <class T>
+static int trace_host(syldet *h, const float *outputs, int64_t n_evals, int32_t output, T *trace, int64_t n_samples, int64_t trace_stride)
+{
+    if (int st = trace_args(h, outputs, n_evals, output, trace, n_samples, trace_stride)) return st;
+    if (n_samples == 0) return SYLDET_OK;
+    std::lock_guard<std::mutex> staging(h->pump_mu);   // the staging buffers and h->stream: one user at a time
+    SYLDET_HIP(hipSetDevice(h->device));
+    const int C = h->channels;
+    const size_t out_bytes = (size_t)C * (size_t)n_evals * (size_t)h->geom.outputs * sizeof(float);
+    const int64_t ws = (n_samples + 7) & ~(int64_t)7;  // rows of whole 16-byte groups
+    if (int st = h->d_stage_out.reserve(std::max<size_t>(out_bytes, 4))) return st;
+    if (int st = h->d_trace.reserve((size_t)C * (size_t)ws * sizeof(T))) return st;
+    if (out_bytes) SYLDET_HIP(hipMemcpyAsync(h->d_stage_out.ptr, outputs, out_bytes, hipMemcpyHostToDevice, h->stream));
+    if (int st = trace_on_stream(h, (const float *)h->d_stage_out.ptr, n_evals, output, (T *)h->d_trace.ptr, n_samples, ws, false, h->stream)) return st;
+    SYLDET_HIP(hipMemcpy2DAsync(trace, (size_t)trace_stride * sizeof(T), h->d_trace.ptr, (size_t)ws * sizeof(T), (size_t)n_samples * sizeof(T),
+                                (size_t)C, hipMemcpyDeviceToHost, h->stream));
+    SYLDET_HIP(hipStreamSynchronize(h->stream));
+    return SYLDET_OK;
+}
+}
+
+int syldet_trace(syldet_t *h, const float *outputs, int64_t n_evals, int32_t output, float *trace, int64_t n_samples, int64_t trace_stride)
+{
+    return trace_host(h, outputs, n_evals, output, trace, n_samples, trace_stride);
+}
+
+int syldet_trace_s16(syldet_t *h, const float *outputs, int64_t n_evals, int32_t output, int16_t *trace, int64_t n_samples,
+                     int64_t trace_stride)
+{
+    return trace_host(h, outputs, n_evals, output, trace, n_samples, trace_stride);
 }
 
 // ---- streaming front-end -------------------------------------------------------------

@@ -331,6 +331,86 @@ class SyllableDetector:
                                                 cnt.data_ptr(), self._stream_ptr(stream)))
         return idx, cnt
 
+    # ---- the Simulator's output track ---------------------------------------------------
+    @staticmethod
+    def _trace_dtype(dtype, interleaved):
+        dt = np.dtype(dtype)
+        if dt not in (np.dtype(np.float32), np.dtype(np.int16)):
+            raise ValueError("dtype must be np.float32 or np.int16 (got %s)" % dt)
+        if interleaved and dt != np.dtype(np.int16):
+            raise ValueError("interleaved=True needs dtype=np.int16 (frames as a 16-bit WAV stores them)")
+        return dt
+
+    def trace(self, outputs, n_samples: int, output: int = 0, dtype=np.float32, interleaved: bool = False, out=None, stream=None):
+        """The Simulator's output track (ViewControllerSimulator.swift:251-344; syldet_trace_device*): outputs [C, n_evals, n_out]
+        (a float32 CUDA tensor, as run() returns it) -> trace [C, n_samples], output `output` as a fraction of its channel's
+        threshold, clamped to [0, 1] and held from one evaluation to the next; 0 before the first evaluation's sample number and
+        behind the last hold.  dtype np.float32: the reference's values; np.int16: rint(v * 32767), NaN -> 0.  interleaved=True
+        (int16 only): frames [n_samples, C], what a 16-bit WAV of C tracks stores.  `out`: a tensor to write into (rows may be
+        wider than n_samples: only the first n_samples of each are written).  Asynchronous on `stream`."""
+        torch = _torch()
+        dt = self._trace_dtype(dtype, interleaved)
+        tdt = torch.float32 if dt == np.dtype(np.float32) else torch.int16
+        n = int(n_samples)
+        if n < 0:
+            raise ValueError("n_samples must not be negative")
+        if not (outputs.is_cuda and outputs.dtype == torch.float32 and outputs.dim() == 3 and outputs.is_contiguous()
+                and outputs.shape[0] == self.channels and outputs.shape[2] == self.geometry.outputs
+                and outputs.device.index == self.device):
+            raise ValueError("outputs must be a contiguous float32 CUDA tensor [channels, n_evals, outputs] on the detector's device")
+        E = int(outputs.shape[1])
+        if out is None:
+            out = torch.empty((n, self.channels) if interleaved else (self.channels, n), dtype=tdt, device=outputs.device)
+        elif interleaved:
+            if not (out.is_cuda and out.dtype == tdt and tuple(out.shape) == (n, self.channels) and out.is_contiguous()
+                    and out.device == outputs.device):
+                raise ValueError("out must be a contiguous int16 CUDA tensor [n_samples, channels] on the outputs' device")
+        else:
+            if not (out.is_cuda and out.dtype == tdt and out.dim() == 2 and out.shape[0] == self.channels and out.shape[1] >= n
+                    and (out.shape[1] == 0 or out.stride(1) == 1) and (self.channels == 1 or out.stride(0) >= n)
+                    and out.device == outputs.device):
+                raise ValueError("out must be a CUDA tensor [channels, >= n_samples] of the trace's dtype with contiguous rows")
+        if n == 0:
+            return out
+        # (an empty tensor has no address: a bank too short for one evaluation still gets its rows of zeros)
+        src = outputs if E > 0 else torch.zeros(1, dtype=torch.float32, device=outputs.device)
+        if interleaved:
+            check(_abi.lib.syldet_trace_interleaved_device_s16(self._h, src.data_ptr(), E, int(output), out.data_ptr(), n,
+                                                               self._stream_ptr(stream)))
+        else:
+            fn = _abi.lib.syldet_trace_device if dt == np.dtype(np.float32) else _abi.lib.syldet_trace_device_s16
+            stride = int(out.stride(0)) if self.channels > 1 else max(int(out.shape[1]), n)
+            check(fn(self._h, src.data_ptr(), E, int(output), out.data_ptr(), n, stride, self._stream_ptr(stream)))
+        return out
+
+    def traceHost(self, outputs: np.ndarray, n_samples: int, output: int = 0, dtype=np.float32) -> np.ndarray:
+        """trace() on host arrays, blocking (syldet_trace / syldet_trace_s16): outputs [C, n_evals, n_out] -> [C, n_samples]."""
+        dt = self._trace_dtype(dtype, False)
+        n = int(n_samples)
+        if n < 0:
+            raise ValueError("n_samples must not be negative")
+        a = np.ascontiguousarray(outputs, dtype=np.float32)
+        if a.ndim != 3 or a.shape[0] != self.channels or a.shape[2] != self.geometry.outputs:
+            raise ValueError("outputs must be [channels, n_evals, outputs]")
+        E = a.shape[1]
+        src = a if E > 0 else np.zeros(1, np.float32)
+        tr = np.zeros((self.channels, n), dt)
+        if n == 0:
+            return tr
+        if dt == np.dtype(np.float32):
+            check(_abi.lib.syldet_trace(self._h, src.ctypes.data_as(_abi.c_float_p), E, int(output), tr.ctypes.data_as(_abi.c_float_p), n, n))
+        else:
+            check(_abi.lib.syldet_trace_s16(self._h, src.ctypes.data_as(_abi.c_float_p), E, int(output), tr.ctypes.data_as(_abi.c_int16_p), n, n))
+        return tr
+
+    def simulate(self, samples, output: int = 0, dtype=np.int16, stream=None):
+        """The Simulator in one call (simulateNetwork, ViewControllerSimulator.swift:251-344): run() followed by trace() on device
+        tensors; samples [C, S] float32 -> (trace [C, S], outputs [C, E, n_out], flags [C, E])."""
+        self._trace_dtype(dtype, False)
+        outputs, flags = self.run(samples, stream=stream)
+        tr = self.trace(outputs, int(samples.shape[1]), output=output, dtype=dtype, stream=stream)
+        return tr, outputs, flags
+
     # ---- measurement ------------------------------------------------------------------
     def profile(self, enable: bool = True, history: int = 1) -> None:
         """Bracket every kernel of a batch call with HIP events; `history`: how many calls' events to keep (a timing loop
