@@ -118,6 +118,7 @@ def _load(path: str):
     L.orc_net_apply.argtypes = [cp, _f32p, C.c_int, _f64p]
     L.orc_run.argtypes = [cp, _f32p, C.c_int64, C.c_int, C.c_int, _f32p, _u8p, _f64p]
     L.orc_run.restype = C.c_int64
+    L.orc_detect.argtypes = [cp, _f32p, C.c_int, C.c_int]
     L.orc_detections.argtypes = [cp, _u8p, C.c_int64, C.c_double, _i64p, C.c_int64]
     L.orc_detections.restype = C.c_int64
     L.orc_stream_create.argtypes = [cp, C.c_int]
@@ -201,6 +202,17 @@ def from_config(cfg) -> Dict:
                         "biases": np.asarray(L.biases, np.float32), "transferFunction": L.transferFunction}
                        for L in cfg.net.layers],
             "outputs": [fn(f) for f in cfg.net.outputProcessing]}
+
+
+def detect(outputs, thresholds, rule: int = RULE_FIRST) -> int:
+    """The oracle's detection rule alone (orc_detect) on one evaluation's float outputs against double thresholds."""
+    out = np.ascontiguousarray(outputs, np.float32).reshape(-1)
+    thr = np.ascontiguousarray(thresholds, np.float64).reshape(-1)
+    assert out.size == thr.size and out.size >= 1
+    c = _Config()
+    c.n_thresholds = thr.size
+    c.thresholds = thr.ctypes.data_as(_f64p)
+    return int(lib().orc_detect(C.byref(c), out.ctypes.data_as(_f32p), out.size, int(rule)))
 
 
 class Oracle:

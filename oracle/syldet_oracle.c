@@ -484,6 +484,12 @@ static uint8_t detect(const orc_config_t *c, const float *out, int n_out, int ru
     return 0;
 }
 
+/* the rule alone on given outputs (reads c->thresholds only): tests pin it at the threshold's edge */
+int orc_detect(const orc_config_t *c, const float *outputs, int n_out, int rule)
+{
+    return detect(c, outputs, n_out, rule);
+}
+
 /* processNewValue over a whole channel, Common/SyllableDetector.swift:153-217        */
 int64_t orc_run(const orc_config_t *c, const float *samples, int64_t S, int precision, int rule,
                 float *outputs, uint8_t *flags, double *outputs64)

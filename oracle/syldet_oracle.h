@@ -101,6 +101,10 @@ int orc_net_apply(const orc_config_t *c, const float *in, int precision, double 
 int64_t orc_run(const orc_config_t *c, const float *samples, int64_t S, int precision,
                 int rule, float *outputs, uint8_t *flags, double *outputs64);
 
+/* The detection rule alone: Double(outputs[i]) >= thresholds[i] for output 0 (ORC_RULE_FIRST) or any output
+ * (ORC_RULE_ANY); reads c->thresholds only.                                          */
+int orc_detect(const orc_config_t *c, const float *outputs, int n_out, int rule);
+
 /* Detection sample indices + debounce, TrackDetector.swift:39-43,65-100.           */
 int64_t orc_detections(const orc_config_t *c, const uint8_t *flags, int64_t E,
                        double debounce_seconds, int64_t *idx, int64_t cap);

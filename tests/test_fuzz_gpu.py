@@ -159,6 +159,7 @@ def test_random_configuration(oracle_lib, seed):
                 util.assert_outputs_close(out[c][ok], w64[ok], tol)
                 util.assert_flags_exact(fl[c][ok], w64[ok], cfg.thresholds, cfg.rule, tol)
             assert not fl[c][~ok].any()
+            util.assert_flags_follow_outputs(fl[c], out[c], cfg.thresholds, cfg.rule)     # (the decision itself: no guard band)
 
 
 def test_most_draws_of_the_detectors_mode_run_on_the_fused_engine():
@@ -296,6 +297,7 @@ def test_random_example_class_detector_on_the_register_resident_kernel(oracle_li
             util.assert_outputs_close(out[c][ok], w64[ok], tol)
             util.assert_flags_exact(fl[c][ok], w64[ok], cfg.thresholds, cfg.rule, tol)
         assert not fl[c][~ok].any()
+        util.assert_flags_follow_outputs(fl[c], out[c], cfg.thresholds, cfg.rule)     # (the decision itself: no guard band)
 
 
 @pytest.mark.parametrize("seed", range(int(os.environ.get("SYLDET_FUZZ_DRAWS_BLOCKS", "16"))))
@@ -423,3 +425,4 @@ def test_random_wide_band_detector(oracle_lib, seed):
             util.assert_outputs_close(out[c][ok], w64[ok], tol)
             util.assert_flags_exact(fl[c][ok], w64[ok], cfg.thresholds, cfg.rule, tol)
         assert not fl[c][~ok].any()
+        util.assert_flags_follow_outputs(fl[c], out[c], cfg.thresholds, cfg.rule)     # (the decision itself: no guard band)

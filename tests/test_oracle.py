@@ -261,3 +261,73 @@ def test_the_evidence_rule_itself():
     assert util.widened_evaluations(np.array([9e-6, 1e-6]), own[:2], util.TOL, tol[:2], None) is None
     ok = util.widened_evaluations(np.array([2e-5]), np.array([5.1e-6]), util.TOL, np.array([1e-4]), None)
     assert ok["unexplained"] == 0
+
+
+def _decision_table():
+    """(outputs f32 [n_out], thresholds f64 [n_out], rule, hit) at the edge of the rule `Double(output) >= threshold`
+    (SyllableDetector.swift:27-31; any output against its own threshold: TrackDetector.swift:72-77)."""
+    f32, f64 = np.float32, np.float64
+    up = lambda v: np.nextafter(f64(v), np.inf)          # (between two floats: any rounding of it to float changes the answer)
+    down = lambda v: np.nextafter(f64(v), -np.inf)
+    rows = []
+    for v in (f32(0.3372), f32(-0.81250006), f32(1e-30), f32(-3.5e6)):
+        rows += [([v], [f64(v)], 0, 1), ([v], [up(v)], 0, 0), ([v], [down(v)], 0, 1)]
+        assert f64(f32(up(v))) != up(v) and f64(f32(down(v))) != down(v)
+    rows += [([f32(0.0)], [-0.0], 0, 1), ([f32(-0.0)], [0.0], 0, 1)]
+    rows += [([f32(np.nan)], [0.0], 0, 0), ([f32(np.nan)], [-np.inf], 0, 0), ([f32(np.nan), f32(np.nan)], [-np.inf, -1e30], 1, 0)]
+    for v in (f32(0.0), f32(-3e38), f32(3e38), f32(np.inf), f32(-np.inf)):
+        rows += [([v], [-np.inf], 0, 1), ([v], [np.nan], 0, 0)]
+        rows += [([v], [np.inf], 0, 1 if v == np.inf else 0)]      # (inf >= inf: what Double >= Double gives)
+    # rule 0 ignores outputs 1 and above; rule 1 uses each output's own threshold
+    a, b, c = f32(0.25), f32(-0.5), f32(0.75)
+    rows += [([a, b, c], [up(a), f64(b), f64(c)], 0, 0), ([a, b, c], [up(a), f64(b), f64(c)], 1, 1),
+             ([a, b, c], [f64(a), 1e30, 1e30], 0, 1), ([a, b, c], [f64(a), 1e30, 1e30], 1, 1),
+             ([a, b, c], [up(a), up(b), up(c)], 1, 0), ([a, b, c], [up(a), up(b), f64(c)], 1, 1),
+             ([a, b, c], [up(a), f64(b), up(c)], 1, 1), ([a, b, c], [up(a), f64(b), up(c)], 0, 0),
+             # another output's threshold would hit (b >= its own, not c's; c >= b's, not its own)
+             ([a, b, c], [1e30, up(b), up(c)], 1, 0), ([a, b, c], [1e30, f64(c), up(c)], 1, 0),
+             ([f32(np.nan), b, c], [-np.inf, f64(b), 1e30], 0, 0), ([f32(np.nan), b, c], [-np.inf, f64(b), 1e30], 1, 1)]
+    return rows
+
+
+def test_detection_rule_at_the_threshold_edge(oracle_lib):
+    """The anchor of every flag: orc_detect on hand-made values, and tests/util.flags_from_outputs shown to be the same
+    function on the same table."""
+    rows = _decision_table()
+    assert len(rows) > 40
+    for out, thr, rule, hit in rows:
+        out, thr = np.asarray(out, np.float32), np.asarray(thr, np.float64)
+        assert po.detect(out, thr, rule) == hit, (out, [float(t).hex() for t in thr], rule)
+        assert util.flags_from_outputs(out[None, :], thr, rule).tolist() == [hit], (out, [float(t).hex() for t in thr], rule)
+    # the batched forms: [E, n_out] against [n_out], and [C, E, n_out] against a network's thresholds per channel
+    three = [r for r in rows if len(r[0]) == 3]
+    for rule in (0, 1):
+        sel = [r for r in three if r[2] == rule]
+        out = np.asarray([r[0] for r in sel], np.float32)
+        thr = np.asarray([r[1] for r in sel], np.float64)
+        got = util.flags_from_outputs(out[:, None, :], thr, rule)              # every row a channel with thresholds of its own
+        assert got.shape == (len(sel), 1) and got.dtype == np.uint8 and got[:, 0].tolist() == [r[3] for r in sel]
+        util.assert_flags_follow_outputs(got, out[:, None, :], thr, rule)
+        wrong = got.copy()
+        wrong[0, 0] ^= 1
+        with pytest.raises(AssertionError, match="do not follow"):
+            util.assert_flags_follow_outputs(wrong, out[:, None, :], thr, rule)
+        with pytest.raises(AssertionError, match="0 / 1"):
+            util.assert_flags_follow_outputs(got * np.uint8(255), out[:, None, :], np.full_like(thr, -np.inf), rule)
+
+
+def test_oracle_flags_follow_its_own_outputs(sample):
+    """orc_run's flags are orc_detect of its own float outputs (both precisions), with the threshold on a produced value."""
+    cfg, _ = sample
+    x = synth.syllable_channel(30000, util.template(), seed=3)
+    out = util.oracle_for(cfg).run(x, po.F32)[0]
+    v = np.sort(out[:, 0])[int(0.8 * len(out))]
+    for thr in (np.float64(v), np.nextafter(np.float64(v), np.inf)):
+        o = util.oracle_for(nets.variant(cfg, thresholds=[float(thr)]))
+        for prec in (po.F32, po.F64):
+            got, fl, _ = o.run(x, prec)
+            util.assert_flags_follow_outputs(fl, got, [thr], 0)
+            assert 0 < fl.sum() < fl.size
+        got, fl, _ = o.run(x, po.F32)
+        at = got[:, 0] == v
+        assert at.any() and (fl[at] == (1 if thr == np.float64(v) else 0)).all()

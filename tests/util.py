@@ -110,6 +110,42 @@ def assert_flags_exact(got_flags, want_out64, thresholds, rule, tol=TOL):
     return safe
 
 
+def flags_from_outputs(out, thresholds, rule) -> np.ndarray:
+    """The reference's decision (SyllableDetector.swift:27-31 / TrackDetector.swift:72-77) applied to float outputs
+    [..., E, n_out]: Double(output) >= Double threshold, output 0 under rule 0, any output under rule 1; a NaN output never
+    hits.  `thresholds`: [n_out], or [C, n_out] (a network per channel: out is [C, E, n_out]).  -> uint8 [..., E].  Exact: the
+    flag is a pure function of the float an engine produced and the double threshold."""
+    out = np.asarray(out)
+    assert out.dtype == np.float32, out.dtype
+    thr = np.asarray(thresholds, np.float64)
+    assert thr.shape[-1] == out.shape[-1], (thr.shape, out.shape)
+    if thr.ndim == 2:
+        assert out.ndim == 3 and thr.shape[0] == out.shape[0], (thr.shape, out.shape)
+        thr = thr[:, None, :]
+    with np.errstate(invalid="ignore"):
+        hit = out.astype(np.float64) >= thr
+    return (hit[..., 0] if int(rule) == 0 else hit.any(axis=-1)).astype(np.uint8)
+
+
+def assert_flags_follow_outputs(fl, out, thresholds, rule):
+    """Every flag byte is 0 or 1 and equals flags_from_outputs() of the engine's OWN outputs, at every evaluation."""
+    fl = np.asarray(fl)
+    out = np.asarray(out)
+    want = flags_from_outputs(out, thresholds, rule)
+    assert fl.dtype == np.uint8 and fl.shape == want.shape, (fl.dtype, fl.shape, want.shape)
+    assert (fl <= 1).all(), "flag bytes other than 0 / 1: %s" % np.unique(fl[fl > 1])[:8]
+    bad = np.argwhere(fl != want)
+    if bad.size:
+        thr = np.asarray(thresholds, np.float64)
+        lines = []
+        for idx in bad[:6]:
+            idx = tuple(int(i) for i in idx)
+            t = thr[idx[0]] if thr.ndim == 2 else thr
+            lines.append("%s: flag %d, want %d, output bits %s, thresholds %s"
+                         % (idx, fl[idx], want[idx], ["0x%08x" % b for b in out[idx].view(np.uint32)], [float(v).hex() for v in t]))
+        raise AssertionError("%d flags do not follow their own outputs (rule %d):\n  %s" % (len(bad), int(rule), "\n  ".join(lines)))
+
+
 def band_condition(o: "po.Oracle", cfg, x: np.ndarray, cols64: np.ndarray = None) -> np.ndarray:
     """Per evaluation: (norm of the window's whole one-sided spectra) / (norm of its in-band columns).  Any fp32 transform
     leaves an error of about 2^-24 of a frame's whole energy in every bin, so a band that holds 1/kappa of the norm is known
@@ -240,6 +276,9 @@ def check_with_evidence(o: "po.Oracle", cfg, x: np.ndarray, out, fl, w64=None, w
         w64 = o.run(x, po.F64, cfg.rule)[2]
     if w32 is None:
         w32 = o.run(x, po.F32, cfg.rule)[0]
+    if fl is not None:
+        # the decision itself, no guard band: the flag is the reference's comparison on the engine's own float
+        assert_flags_follow_outputs(np.asarray(fl).reshape(-1), np.asarray(out, np.float32).reshape(w64.shape), cfg.thresholds, cfg.rule)
     out = np.asarray(out, np.float64).reshape(w64.shape)
     ok = np.isfinite(w64).all(axis=1)
     assert (np.isfinite(out).all(axis=1) == ok).all(), "NaN/inf evaluations must coincide"
