@@ -322,6 +322,63 @@ int syldet_trace(syldet_t *h, const float *outputs, int64_t n_evals, int32_t out
 int syldet_trace_s16(syldet_t *h, const float *outputs, int64_t n_evals, int32_t output,
                      int16_t *trace, int64_t n_samples, int64_t trace_stride);
 
+/* ---- the level meters of a row (SyllableDetector/Processor.swift:111-113, :138, :158-184; SummaryStat.swift) ----
+ * ProcessorBase keeps two StatMax statistics per row, read and reset by a 0.1 s timer (ViewControllerProcessor.swift:57,
+ * :184-189, :278-284): the input meter takes Double(sum of squares) / Double(length) of every callback buffer (its reading is the
+ * square root of the greatest: an RMS), the output meter Double(lastOutputs[0]) of every evaluation.
+ * StatMax takes its first value as it is and a later one only if it is greater: a reading is NaN if its first value is NaN, and
+ * otherwise the greatest (the first of equal ones) of its values that are not NaN.
+ * The sum of squares is THIS LIBRARY'S convention (vDSP_svesq's order is not specified), sum_squares_tree(x, n): every square
+ * x[i] * x[i] rounded to fp32 on its own, the squares added as a balanced binary tree in index order over next_pow2(n) slots,
+ * the slots past n holding +0, every addition rounded to fp32, no multiply-add contraction.  (Padding to a longer power of two
+ * gives the same bits.)  syldet_sum_squares is that function on the host.
+ * The batch form of the timer, for buffer_length L (a power of two, 8 <= L <= 4096; the reference's default is 32,
+ * AudioInterface.swift:342, :474) and buffers_per_reading P >= 1: buffer b is samples [b L, min((b + 1) L, S)) -- B = ceil(S / L),
+ * the last one may be short and divides by its own length --, reading m is buffers [m P, (m + 1) P), M = ceil(B / P) =
+ * syldet_levels_count.
+ *   d_mean_square [C][M] fp64   the StatMax of the buffers' mean squares (the RMS is its sqrt; the host forms below return that)
+ *   d_levels      [C][M] fp32   the StatMax of out[e][output] over the evaluations the reading's buffers make available:
+ *                               [min(ce(min(m P L, S)), n_evals), min(ce(min((m + 1) P L, S)), n_evals)), ce = syldet_count_evals
+ *                               (syldet_levels_eval_range); 0 for a reading without one (the table's `?? 0.0`)
+ * int16 samples mean float(x) * 2^-15 and give the fp32 form's bits.  syldet_timings lists "levels_in_kernel", "levels_fold_kernel"
+ * (where a reading crosses workgroups) and "levels_out_kernel"; the interleaved forms de-interleave into the handle's planar
+ * scratch first (total_channels == syldet_channels(h), as syldet_run_interleaved*).
+ * Statuses, before any device is touched: SYLDET_ERR_INVALID_ARGUMENT for a NULL handle or pointer, negative counts, a stride
+ * below n_samples, output outside [0, outputs), an L that is not a power of two in [8, 4096], P < 1.  n_samples == 0 writes
+ * nothing.  The device forms follow the handle's rule of one stream at a time.  Plain, multi-network and mixed banks alike.  */
+int64_t syldet_levels_count(int64_t n_samples, int32_t buffer_length, int64_t buffers_per_reading);   /* M; -1 for bad arguments */
+float   syldet_sum_squares(const float *x, int64_t n);
+/* the evaluations [*first, *first + *count) of reading `reading` (in [0, M)) for n_evals evaluations of n_samples samples */
+int syldet_levels_eval_range(const syldet_t *h, int64_t n_samples, int64_t n_evals, int32_t buffer_length,
+                             int64_t buffers_per_reading, int64_t reading, int64_t *first, int64_t *count);
+int syldet_levels_device(syldet_t *h, const float *d_samples, int64_t n_samples, int64_t channel_stride,
+                         int32_t buffer_length, int64_t buffers_per_reading, double *d_mean_square, void *hip_stream);
+int syldet_levels_device_s16(syldet_t *h, const int16_t *d_samples, int64_t n_samples, int64_t channel_stride,
+                             int32_t buffer_length, int64_t buffers_per_reading, double *d_mean_square, void *hip_stream);
+int syldet_levels_interleaved_device(syldet_t *h, const float *d_interleaved, int64_t n_frames, int32_t total_channels,
+                                     int32_t buffer_length, int64_t buffers_per_reading, double *d_mean_square, void *hip_stream);
+int syldet_levels_interleaved_device_s16(syldet_t *h, const int16_t *d_interleaved, int64_t n_frames, int32_t total_channels,
+                                         int32_t buffer_length, int64_t buffers_per_reading, double *d_mean_square, void *hip_stream);
+int syldet_output_levels_device(syldet_t *h, const float *d_outputs, int64_t n_evals, int32_t output, int64_t n_samples,
+                                int32_t buffer_length, int64_t buffers_per_reading, float *d_levels, void *hip_stream);
+/* host pointers, blocking (as syldet_trace is to syldet_trace_device); rms [C][M]: the square roots (std::sqrt on the host) */
+int syldet_levels(syldet_t *h, const float *samples, int64_t n_samples, int64_t channel_stride,
+                  int32_t buffer_length, int64_t buffers_per_reading, double *rms);
+int syldet_levels_s16(syldet_t *h, const int16_t *samples, int64_t n_samples, int64_t channel_stride,
+                      int32_t buffer_length, int64_t buffers_per_reading, double *rms);
+int syldet_output_levels(syldet_t *h, const float *outputs, int64_t n_evals, int32_t output, int64_t n_samples,
+                         int32_t buffer_length, int64_t buffers_per_reading, float *levels);
+/* Streaming: getInputForChannel / getOutputForChannel (Processor.swift:158-184).  Off until syldet_meters_enable(h, 1) (a handle
+ * that never enables them does what it always did; enabling or disabling clears both statistics).  When on, every syldet_append*
+ * call that succeeds with n > 0 is one buffer per channel (sum_squares_tree over the call's samples -- for the s16 appends over
+ * the converted values -- divided by the call's length), and every evaluation syldet_process_new_value / syldet_seen_syllable
+ * makes lastOutputs writes output 0.  The getters read and reset (*has_value = 0 and *rms / *level = 0 where nothing was
+ * written: the reference's nil); they may be called from any thread beside the producer and the consumer (a small lock per
+ * channel: no value is lost between a write and a read-and-reset).                                                        */
+int syldet_meters_enable(syldet_t *h, int enable);
+int syldet_input_level(syldet_t *h, int32_t channel, double *rms, int32_t *has_value);
+int syldet_output_level(syldet_t *h, int32_t channel, double *level, int32_t *has_value);
+
 /* ---- measurement (replaces the reference's Time stopwatch, SyllableDetector/Time.swift:36-100,
  * which wraps processNewValue in ViewControllerSimulator.swift:309-319) ----
  * With profiling enabled every kernel of a batch call is bracketed by HIP events on the stream it

@@ -14,7 +14,9 @@
 // is the batched form the MI355X engine is built around.
 #pragma once
 
+#include <algorithm>
 #include <cstdint>
+#include <optional>
 #include <stdexcept>
 #include <string>
 #include <utility>
@@ -199,6 +201,75 @@ public:
     void traceInterleavedDevicePCM16(const float *d_outputs, int64_t nEvals, int32_t output, int16_t *d_frames, int64_t n, void *hipStream)
     {
         check(syldet_trace_interleaved_device_s16(h_, d_outputs, nEvals, output, d_frames, n, hipStream));
+    }
+    // The level meters of the rows (Processor.swift:111-113, :138, :158-184).  Whole recordings, host buffers, blocking: the RMS
+    // readings [channels][M] of samples [channels][n] (M = levelsCount: one reading per buffersPerReading buffers of bufferLength
+    // samples), and the output readings [channels][M] of outputs [channels][nEvals][outputs]
+    static int64_t levelsCount(int64_t n, int32_t bufferLength, int64_t buffersPerReading)
+    {
+        return syldet_levels_count(n, bufferLength, buffersPerReading);
+    }
+    std::vector<double> levels(const float *samples, int64_t n, int32_t bufferLength, int64_t buffersPerReading)
+    {
+        std::vector<double> rms((size_t)channels() * (size_t)std::max<int64_t>(0, levelsCount(n, bufferLength, buffersPerReading)));
+        check(syldet_levels(h_, samples, n, n, bufferLength, buffersPerReading, rms.data()));
+        return rms;
+    }
+    std::vector<double> levelsPCM16(const int16_t *samples, int64_t n, int32_t bufferLength, int64_t buffersPerReading)
+    {
+        std::vector<double> rms((size_t)channels() * (size_t)std::max<int64_t>(0, levelsCount(n, bufferLength, buffersPerReading)));
+        check(syldet_levels_s16(h_, samples, n, n, bufferLength, buffersPerReading, rms.data()));
+        return rms;
+    }
+    std::vector<float> outputLevels(const float *outputs, int64_t nEvals, int64_t n, int32_t bufferLength, int64_t buffersPerReading,
+                                    int32_t output = 0)
+    {
+        std::vector<float> lv((size_t)channels() * (size_t)std::max<int64_t>(0, levelsCount(n, bufferLength, buffersPerReading)));
+        check(syldet_output_levels(h_, outputs, nEvals, output, n, bufferLength, buffersPerReading, lv.data()));
+        return lv;
+    }
+    // device buffers, asynchronous on `hipStream`: the fp64 MEAN SQUARES [channels][M] (the RMS is their sqrt), fp32 output readings
+    void levelsDevice(const float *d_samples, int64_t n, int64_t stride, int32_t bufferLength, int64_t buffersPerReading,
+                      double *d_meanSquare, void *hipStream)
+    {
+        check(syldet_levels_device(h_, d_samples, n, stride, bufferLength, buffersPerReading, d_meanSquare, hipStream));
+    }
+    void levelsDevicePCM16(const int16_t *d_samples, int64_t n, int64_t stride, int32_t bufferLength, int64_t buffersPerReading,
+                           double *d_meanSquare, void *hipStream)
+    {
+        check(syldet_levels_device_s16(h_, d_samples, n, stride, bufferLength, buffersPerReading, d_meanSquare, hipStream));
+    }
+    void levelsInterleavedDevice(const float *d_frames, int64_t n, int32_t bufferLength, int64_t buffersPerReading, double *d_meanSquare,
+                                 void *hipStream)
+    {
+        check(syldet_levels_interleaved_device(h_, d_frames, n, channels(), bufferLength, buffersPerReading, d_meanSquare, hipStream));
+    }
+    void levelsInterleavedDevicePCM16(const int16_t *d_frames, int64_t n, int32_t bufferLength, int64_t buffersPerReading,
+                                      double *d_meanSquare, void *hipStream)
+    {
+        check(syldet_levels_interleaved_device_s16(h_, d_frames, n, channels(), bufferLength, buffersPerReading, d_meanSquare, hipStream));
+    }
+    void outputLevelsDevice(const float *d_outputs, int64_t nEvals, int32_t output, int64_t n, int32_t bufferLength,
+                            int64_t buffersPerReading, float *d_levels, void *hipStream)
+    {
+        check(syldet_output_levels_device(h_, d_outputs, nEvals, output, n, bufferLength, buffersPerReading, d_levels, hipStream));
+    }
+    // live use: getInputForChannel / getOutputForChannel (Processor.swift:158-184), read and reset, nullopt for no value; off
+    // until enableMeters()
+    void enableMeters(bool enable = true) { check(syldet_meters_enable(h_, enable ? 1 : 0)); }
+    std::optional<double> getInputForChannel(int32_t channel)
+    {
+        double v = 0.0;
+        int32_t has = 0;
+        check(syldet_input_level(h_, channel, &v, &has));
+        return has ? std::optional<double>(v) : std::nullopt;
+    }
+    std::optional<double> getOutputForChannel(int32_t channel)
+    {
+        double v = 0.0;
+        int32_t has = 0;
+        check(syldet_output_level(h_, channel, &v, &has));
+        return has ? std::optional<double>(v) : std::nullopt;
     }
     syldet_t *raw() { return h_; }
 

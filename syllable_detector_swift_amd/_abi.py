@@ -123,6 +123,20 @@ SIGNATURES = {
     "syldet_trace_interleaved_device_s16": (C.c_int, [Handle, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p]),
     "syldet_trace": (C.c_int, [Handle, c_float_p, C.c_int64, C.c_int32, c_float_p, C.c_int64, C.c_int64]),
     "syldet_trace_s16": (C.c_int, [Handle, c_float_p, C.c_int64, C.c_int32, c_int16_p, C.c_int64, C.c_int64]),
+    "syldet_levels_count": (C.c_int64, [C.c_int64, C.c_int32, C.c_int64]),
+    "syldet_sum_squares": (C.c_float, [c_float_p, C.c_int64]),
+    "syldet_levels_eval_range": (C.c_int, [Handle, C.c_int64, C.c_int64, C.c_int32, C.c_int64, C.c_int64, c_int64_p, c_int64_p]),
+    "syldet_levels_device": (C.c_int, [Handle, C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_int64, C.c_void_p, C.c_void_p]),
+    "syldet_levels_device_s16": (C.c_int, [Handle, C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_int64, C.c_void_p, C.c_void_p]),
+    "syldet_levels_interleaved_device": (C.c_int, [Handle, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_int64, C.c_void_p, C.c_void_p]),
+    "syldet_levels_interleaved_device_s16": (C.c_int, [Handle, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_int64, C.c_void_p, C.c_void_p]),
+    "syldet_output_levels_device": (C.c_int, [Handle, C.c_void_p, C.c_int64, C.c_int32, C.c_int64, C.c_int32, C.c_int64, C.c_void_p, C.c_void_p]),
+    "syldet_levels": (C.c_int, [Handle, c_float_p, C.c_int64, C.c_int64, C.c_int32, C.c_int64, c_double_p]),
+    "syldet_levels_s16": (C.c_int, [Handle, c_int16_p, C.c_int64, C.c_int64, C.c_int32, C.c_int64, c_double_p]),
+    "syldet_output_levels": (C.c_int, [Handle, c_float_p, C.c_int64, C.c_int32, C.c_int64, C.c_int32, C.c_int64, c_float_p]),
+    "syldet_meters_enable": (C.c_int, [Handle, C.c_int]),
+    "syldet_input_level": (C.c_int, [Handle, C.c_int32, c_double_p, c_int32_p]),
+    "syldet_output_level": (C.c_int, [Handle, C.c_int32, c_double_p, c_int32_p]),
     "syldet_profile": (C.c_int, [Handle, C.c_int]),
     "syldet_last_timings": (C.c_int, [Handle, c_double_p, C.POINTER(C.c_char_p), C.c_int32, c_int32_p]),
     "syldet_profile_history": (C.c_int, [Handle, C.c_int32]),

@@ -20,6 +20,7 @@
 
 #include <algorithm>
 #include <charconv>
+#include <cmath>
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
@@ -37,7 +38,7 @@ constexpr int kExUsage = 64;   // EX_USAGE, main.swift:40
 void usage(FILE *to)
 {
     std::fprintf(to,
-                 "Usage: syllable-detector-cli -n <net> [-a <audio>]... [-d <seconds>] [--device <k>] [--chunk <frames>] [--format <shortest|swift4>] [--simulate <out.wav>] [--simulate-output <k>] [--probe]\n"
+                 "Usage: syllable-detector-cli -n <net> [-a <audio>]... [-d <seconds>] [--device <k>] [--chunk <frames>] [--format <shortest|swift4>] [--simulate <out.wav>] [--simulate-output <k>] [--levels <out.tsv>] [--levels-buffer <L>] [--levels-period <seconds>] [--probe]\n"
                  "  -n, --net <net>:\n      Path to trained network file.  Given k > 1 times: each file must have exactly k tracks, and track t runs network t (one mixed bank; the networks must share the sampling rate, window length, window overlap, time range and number of outputs).\n"
                  "  -a, --audio <audio>:\n      Path to the audio file to process.\n"
                  "  -d, --debounce <seconds>:\n      Number of seconds to debounce triggers.\n"
@@ -46,6 +47,9 @@ void usage(FILE *to)
                  "      --format <shortest|swift4>:\n      How numbers are printed: the shortest digits that round-trip (Swift 4.2 and later; default) or 15 / 6 significant digits (Swift 4.0, the toolchain the project declares: the example line below).\n"
                  "      --simulate <out.wav>:\n      Also write the Simulator's output track of every track of the (one) audio file as a 16-bit WAV at the network's sampling rate: the chosen output as a fraction of its threshold (0 = 0, threshold and above = 32767), held from one evaluation to the next.\n"
                  "      --simulate-output <k>:\n      The network output --simulate follows (default 0).\n"
+                 "      --levels <out.tsv>:\n      Also write the level meters of every track of the (one) audio file, one line per reading and track, tab separated: the track, the time of the reading's end in seconds, the input RMS (the loudest buffer of the reading), the output level (the greatest first output evaluated in the reading; empty for a reading without an evaluation).\n"
+                 "      --levels-buffer <L>:\n      Samples per buffer of the input meter: a power of two from 8 to 4096 (default 32).\n"
+                 "      --levels-period <seconds>:\n      Time between two readings (default 0.1); a reading is a whole number of buffers, at least one.\n"
                  "      --probe:\n      Only print what the audio files contain; does not touch the GPU.\n"
                  "The command line will write a comma-separated list of detection events (when the network has at least one output above threshold) to standard out. For example, it might output:\n"
                  "\n\t0,1593298,36.1292063492063,0.918557\n\n"
@@ -93,13 +97,21 @@ struct DevBuf {
 
 struct Event { int64_t buffer; int channel; int64_t sample; int64_t eval; };
 
+// --levels: the two meters of every row (Processor.swift:111-113, :138, :158-184) over the recording, as the 0.1 s timer of
+// ViewControllerProcessor.swift:57 would have read them
+struct LevelsOpt {
+    std::string path;                                      // empty: none
+    int buffer = 32;                                       // AudioInterface.swift:342, :474
+    double period = 0.1;
+};
+
 // cfgs: one network for every track, or (k > 1) network t for track t of a file of exactly k tracks, through one mixed bank
 // (syldet_create_mixed): the networks share the evaluation clock, so the events are found and printed as for one
 // simulate: a path for the Simulator's output track (ViewControllerSimulator.swift:251-344) of every track, made on the device from
 // the outputs the run left there (syldet_trace_interleaved_device_s16) and written as a 16-bit WAV of as many frames as the detector
 // was fed, at the network's rate; empty: none
 int process_file(const std::string &path, const std::vector<syldet_config_t *> &cfgs, int device, double debounce_s, bool have_debounce, int64_t chunk,
-                 const std::string &simulate = std::string(), int simulate_output = 0)
+                 const std::string &simulate = std::string(), int simulate_output = 0, const LevelsOpt &levels = LevelsOpt())
 {
     const syldet_config_t *cfg = cfgs[0];
     wav::Info info;
@@ -140,6 +152,10 @@ int process_file(const std::string &path, const std::vector<syldet_config_t *> &
     std::vector<float> out;
     std::vector<uint8_t> flags;
     std::vector<int16_t> track;
+    std::vector<double> lv_in;                              // [C][M] mean squares
+    std::vector<float> lv_out;                              // [C][M]
+    std::vector<uint8_t> lv_empty;                          // [M] the reading holds no evaluation
+    int64_t lv_P = 1, lv_M = 0;
     int64_t E = 0, fed = 0;
     do {
         if (hipSetDevice(device) != hipSuccess || hipStreamCreate(&stream) != hipSuccess) { rc = 2; break; }
@@ -166,12 +182,37 @@ int process_file(const std::string &path, const std::vector<syldet_config_t *> &
         }
         E = syldet_count_evals(h, S);
         fed = S;
-        DevBuf d_track;
-        if (E <= 0 && !simulate.empty()) {                   // shorter than one evaluation: a track of zeros
-            track.assign((size_t)S * C, 0);
+        DevBuf d_track, d_lv_in, d_lv_out;
+        if (E <= 0 && !simulate.empty()) track.assign((size_t)S * C, 0);   // shorter than one evaluation: a track of zeros
+        // the meters: the input readings of the samples the detector is fed (queued here, behind the copy; a recording shorter
+        // than one evaluation has them too), the output readings behind the run
+        auto meters = [&](bool outputs_too) -> bool {
+            if (levels.path.empty() || S <= 0) return true;
+            const double per = levels.period * cfg->sampling_rate / (double)levels.buffer;
+            lv_P = per >= 1.0 ? (per < 9e18 ? (int64_t)per : INT64_MAX) : 1;
+            lv_M = syldet_levels_count(S, levels.buffer, lv_P);
+            const size_t cells = (size_t)C * (size_t)lv_M;
+            if (!outputs_too) {
+                lv_in.resize(cells);
+                if (!d_lv_in.alloc(cells * sizeof(double))) return false;
+                if (pcm16) st = syldet_levels_interleaved_device_s16(h, (const int16_t *)d_inter.p, n, C, levels.buffer, lv_P, (double *)d_lv_in.p, stream);
+                else if (!resample) st = syldet_levels_interleaved_device(h, (const float *)d_inter.p, n, C, levels.buffer, lv_P, (double *)d_lv_in.p, stream);
+                else st = syldet_levels_device(h, (const float *)d_res.p, S, res_stride, levels.buffer, lv_P, (double *)d_lv_in.p, stream);
+                if (!st && hipMemcpyAsync(lv_in.data(), d_lv_in.p, cells * sizeof(double), hipMemcpyDeviceToHost, stream) != hipSuccess) return false;
+            } else {
+                lv_out.resize(cells);
+                if (!d_lv_out.alloc(cells * sizeof(float))) return false;
+                st = syldet_output_levels_device(h, (const float *)d_out.p, E, 0, S, levels.buffer, lv_P, (float *)d_lv_out.p, stream);
+                if (!st && hipMemcpyAsync(lv_out.data(), d_lv_out.p, cells * sizeof(float), hipMemcpyDeviceToHost, stream) != hipSuccess) return false;
+            }
+            if (st) std::fprintf(stderr, "Unable to meter %s: %s: %s\n", path.c_str(), syldet_strerror(st), syldet_last_error());
+            return st == 0;
+        };
+        if (!meters(false)) { rc = 2; break; }
+        if (E <= 0) {                                       // shorter than one evaluation: no events
+            if (!levels.path.empty() && hipStreamSynchronize(stream) != hipSuccess) rc = 2;
             break;
         }
-        if (E <= 0) break;                                  // shorter than one evaluation: no events
         if (!d_out.alloc((size_t)C * E * n_out * sizeof(float)) || !d_flags.alloc((size_t)C * E)) { rc = 2; break; }
         if (pcm16) st = syldet_run_interleaved_device_s16(h, (const int16_t *)d_inter.p, n, C, (float *)d_out.p, (uint8_t *)d_flags.p, stream);
         else if (!resample) st = syldet_run_interleaved_device(h, (const float *)d_inter.p, n, C, (float *)d_out.p, (uint8_t *)d_flags.p, stream);
@@ -192,6 +233,7 @@ int process_file(const std::string &path, const std::vector<syldet_config_t *> &
             }
             if (hipMemcpyAsync(track.data(), d_track.p, track.size() * sizeof(int16_t), hipMemcpyDeviceToHost, stream) != hipSuccess) { rc = 2; break; }
         }
+        if (!meters(true)) { rc = 2; break; }
         out.resize((size_t)C * E * n_out);
         flags.resize((size_t)C * E);
         if (hipMemcpyAsync(out.data(), d_out.p, out.size() * sizeof(float), hipMemcpyDeviceToHost, stream) != hipSuccess ||
@@ -200,6 +242,13 @@ int process_file(const std::string &path, const std::vector<syldet_config_t *> &
     } while (false);
     if (rc == 2 && hipPeekAtLastError() != hipSuccess) std::fprintf(stderr, "Unable to process %s: %s\n", path.c_str(), hipGetErrorString(hipGetLastError()));
     if (stream) (void)hipStreamDestroy(stream);
+    if (!rc && !levels.path.empty()) {
+        lv_empty.assign((size_t)lv_M, 1);
+        for (int64_t m = 0; m < lv_M; m++) {
+            int64_t first = 0, count = 0;
+            if (syldet_levels_eval_range(h, fed, E > 0 ? E : 0, levels.buffer, lv_P, m, &first, &count) == SYLDET_OK) lv_empty[(size_t)m] = count == 0;
+        }
+    }
     syldet_destroy(h);
     // the track is written behind the detection lines, which a failing write must not cost: 3 = the lines are out, the track is not
     auto write_track = [&]() -> int {
@@ -209,8 +258,30 @@ int process_file(const std::string &path, const std::vector<syldet_config_t *> &
         std::fprintf(stderr, "Unable to write %s: %s\n", simulate.c_str(), werr.c_str());
         return 3;
     };
+    // ... and so are the meters' readings: track, time of the reading's end, input RMS, output level (empty: no evaluation)
+    auto write_levels = [&]() -> int {
+        if (levels.path.empty()) return 0;
+        FILE *f = std::fopen(levels.path.c_str(), "w");
+        bool ok = f != nullptr;
+        const int64_t PL = std::min(lv_P, (fed + levels.buffer - 1) / levels.buffer) * levels.buffer;
+        for (int64_t m = 0; ok && m < lv_M; m++)
+            for (int c = 0; ok && c < C; c++) {
+                const size_t at = (size_t)c * (size_t)lv_M + (size_t)m;
+                const std::string line = std::to_string(c) + "\t" + number((double)std::min((m + 1) * PL, fed) / cfg->sampling_rate) + "\t" +
+                                         number(std::sqrt(lv_in[at])) + "\t" + (lv_empty[(size_t)m] ? std::string() : number(lv_out[at])) + "\n";
+                ok = std::fputs(line.c_str(), f) >= 0;
+            }
+        if (f && std::fclose(f) != 0) ok = false;
+        if (ok) return 0;
+        std::fprintf(stderr, "Unable to write %s.\n", levels.path.c_str());
+        return 3;
+    };
+    auto write_files = [&]() -> int {
+        const int a = write_track(), b = write_levels();
+        return a ? a : b;
+    };
     if (rc) return rc;
-    if (E <= 0) return write_track();
+    if (E <= 0) return write_files();
 
     // events: sample number of evaluation e = first_index + e*hop (TrackDetector.swift:39-43,67-68); debounce :80,:99
     const int64_t debounce_frames = have_debounce ? (int64_t)(debounce_s * cfg->sampling_rate) : 0;   // Int(newValue * samplingRate), :24
@@ -238,7 +309,7 @@ int process_file(const std::string &path, const std::vector<syldet_config_t *> &
         std::puts(line.c_str());
     }
     std::fflush(stdout);
-    return write_track();
+    return write_files();
 }
 
 }  // namespace
@@ -252,6 +323,8 @@ int main(int argc, char **argv)
     int simulate_output = 0;
     double debounce = 0.0;
     bool have_debounce = false, probe = false;
+    LevelsOpt levels;
+    bool have_levels = false, have_levels_option = false;
     int device = 0;
     int64_t chunk = 8192;
     auto value = [&](int &i, const char *name) -> const char * {
@@ -288,6 +361,31 @@ int main(int argc, char **argv)
             }
             simulate_output = (int)k;
             have_simulate_output = true;
+        }
+        else if (a == "--levels") {
+            levels.path = value(i, "--levels");
+            have_levels = true;
+        } else if (a == "--levels-buffer") {
+            const char *v = value(i, "--levels-buffer");
+            char *end = nullptr;
+            const long k = std::strtol(v, &end, 10);
+            if (end == v || *end != 0 || k < 8 || k > 4096 || (k & (k - 1)) != 0) {
+                std::fprintf(stderr, "--levels-buffer takes a power of two from 8 to 4096.\n");
+                usage(stdout);
+                return kExUsage;
+            }
+            levels.buffer = (int)k;
+            have_levels_option = true;
+        } else if (a == "--levels-period") {
+            const char *v = value(i, "--levels-period");
+            char *end = nullptr;
+            levels.period = std::strtod(v, &end);
+            if (end == v || *end != 0 || !(levels.period > 0.0) || levels.period > 1e15) {
+                std::fprintf(stderr, "--levels-period takes a positive number of seconds.\n");
+                usage(stdout);
+                return kExUsage;
+            }
+            have_levels_option = true;
         }
         else if (a == "--format") {
             const std::string f = value(i, "--format");
@@ -332,6 +430,16 @@ int main(int argc, char **argv)
         usage(stdout);
         return kExUsage;
     }
+    if (have_levels && (audio.size() != 1 || levels.path.empty())) {   // one table, one recording
+        std::fprintf(stderr, "--levels writes the readings of exactly one audio file (-a).\n");
+        usage(stdout);
+        return kExUsage;
+    }
+    if (have_levels_option && !have_levels) {
+        std::fprintf(stderr, "--levels-buffer and --levels-period need --levels <out.tsv>.\n");
+        usage(stdout);
+        return kExUsage;
+    }
     std::vector<syldet_config_t *> cfgs;
     for (const std::string &n : net) {
         syldet_config_t *cfg = nullptr;
@@ -355,7 +463,7 @@ int main(int argc, char **argv)
     for (const std::string &p : audio) {
         if (audio.size() > 1) std::printf("%s\n", p.c_str());   // main.swift:122-124
         std::fflush(stdout);
-        const int r = process_file(p, cfgs, device, debounce, have_debounce, chunk, simulate, simulate_output);
+        const int r = process_file(p, cfgs, device, debounce, have_debounce, chunk, simulate, simulate_output, levels);
         if (r == 2) rc = 2;                                 // device trouble is fatal for the exit code; an unreadable file is skipped
         else if (r == 3 && rc == 0) rc = 1;                 // ... and so is a track that could not be written
     }

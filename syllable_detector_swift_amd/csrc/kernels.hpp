@@ -310,6 +310,25 @@ hipError_t launch_trace_s16(const float *outputs, int64_t n_evals, int n_out, in
 hipError_t launch_trace_interleaved_s16(const float *outputs, int64_t n_evals, int n_out, int k, const float *thr, int C,
                                         int16_t *frames, int64_t n_frames, int64_t first_index, int64_t hop, hipStream_t stream);
 
+// ---- the level meters (kernels_levels.hip; Processor.swift:111-113, :138, :158-184) ----
+// what a workgroup of levels_in_kernel leaves of a reading that reaches into a neighbour: the greatest mean square of its buffers
+// that is not NaN (-1: none), and the reading's first value where the workgroup holds its first buffer
+struct LevelsPartial {
+    double best, first;
+};
+// scratch launch_levels_in needs for rows of n_samples (two partials a workgroup)
+size_t levels_scratch_bytes(int64_t n_samples, int C, int L, bool s16);
+// samples [C][stride] fp32 or (s16) int16 -> mean_square [C][M] fp64, M = ceil(ceil(n_samples / L) / P): the StatMax over the P
+// buffers of a reading of Double(sum_squares_tree(buffer)) / Double(length).  *needs_fold: readings cross workgroups, and
+// launch_levels_fold (levels_fold_kernel) has to follow on the same stream with the same arguments.
+hipError_t launch_levels_in(const void *samples, bool s16, int C, int64_t n_samples, int64_t stride, int L, int64_t P, double *mean_square,
+                            void *scratch, hipStream_t stream, bool *needs_fold);
+hipError_t launch_levels_fold(const void *scratch, bool s16, int C, int64_t n_samples, int L, int64_t P, double *mean_square, hipStream_t stream);
+// outputs [C][n_evals][n_out] -> levels [C][M] fp32: the StatMax of output k over the evaluations of each reading (need = gap +
+// window, T = timeRange: syldet_count_evals' rule), 0 for a reading without one
+hipError_t launch_levels_out(const float *outputs, int64_t n_evals, int n_out, int k, int C, int64_t n_samples, int L, int64_t P,
+                             int64_t need, int64_t hop, int T, float *levels, hipStream_t stream);
+
 // detection flags <-> bits (bit b of byte t of a row = flag 8 t + b), rows padded to whole bytes
 hipError_t launch_pack_flags(const uint8_t *flags, int64_t rows, int64_t row_len, uint8_t *bits, hipStream_t stream);
 hipError_t launch_unpack_flags(const uint8_t *bits, int64_t rows, int64_t row_len, uint8_t *flags, hipStream_t stream);

@@ -36,4 +36,10 @@ int compute_geometry(const syldet_config_t &cfg, syldet_geometry_t *out);
 
 void make_window(int window, int length, float *out);
 
+// The library's sum of squares (syldet_levels.cpp, include/syldet.h): n samples `step` elements apart; int16 x is float(x) * 2^-15.
+float sum_squares_tree(const float *x, int64_t n, int64_t step);
+float sum_squares_tree(const int16_t *x, int64_t n, int64_t step);
+// is L a buffer length the level meters take (a power of two in [8, 4096])?
+inline bool levels_buffer_ok(int64_t L) { return L >= 8 && L <= 4096 && (L & (L - 1)) == 0; }
+
 }  // namespace sd

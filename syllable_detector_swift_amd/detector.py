@@ -411,6 +411,159 @@ class SyllableDetector:
         tr = self.trace(outputs, int(samples.shape[1]), output=output, dtype=dtype, stream=stream)
         return tr, outputs, flags
 
+    # ---- the level meters (Processor.swift:111-113, :138, :158-184) ---------------------------
+    def defaultBuffersPerReading(self, bufferLength: int = 32) -> int:
+        """Buffers between two firings of the reference's 0.1 s timer (ViewControllerProcessor.swift:57):
+        max(1, floor(0.1 * samplingRate / bufferLength))."""
+        return max(1, int(0.1 * float(self.config.samplingRate) / int(bufferLength)))
+
+    def _levels_geometry(self, n_samples, bufferLength, buffersPerReading):
+        L = int(bufferLength)
+        P = self.defaultBuffersPerReading(L) if buffersPerReading is None else int(buffersPerReading)
+        M = int(_abi.lib.syldet_levels_count(int(n_samples), L, P))
+        if M < 0:
+            raise ValueError("bufferLength must be a power of two in [8, 4096] and buffersPerReading >= 1")
+        return L, P, M
+
+    def levelsCount(self, n_samples: int, bufferLength: int = 32, buffersPerReading: Optional[int] = None) -> int:
+        """syldet_levels_count: readings of n_samples samples."""
+        return self._levels_geometry(n_samples, bufferLength, buffersPerReading)[2]
+
+    def levelsEvalRange(self, n_samples: int, n_evals: int, reading: int, bufferLength: int = 32,
+                        buffersPerReading: Optional[int] = None) -> Tuple[int, int]:
+        """syldet_levels_eval_range: (first, count) of the evaluations of reading `reading` (count 0: an empty reading)."""
+        L, P, _ = self._levels_geometry(n_samples, bufferLength, buffersPerReading)
+        first, count = C.c_int64(), C.c_int64()
+        check(_abi.lib.syldet_levels_eval_range(self._h, int(n_samples), int(n_evals), L, P, int(reading), C.byref(first), C.byref(count)))
+        return int(first.value), int(count.value)
+
+    def _levels_device(self, fn, tensor, n, stride_or_channels, bufferLength, buffersPerReading, stream):
+        torch = _torch()
+        L, P, M = self._levels_geometry(n, bufferLength, buffersPerReading)
+        ms = torch.empty((self.channels, M), dtype=torch.float64, device=tensor.device)
+        if n > 0:
+            check(fn(self._h, tensor.data_ptr(), n, stride_or_channels, L, P, ms.data_ptr(), self._stream_ptr(stream)))
+        return ms
+
+    def levels(self, samples, bufferLength: int = 32, buffersPerReading: Optional[int] = None, stream=None):
+        """The input meter of every channel over a recording (syldet_levels_device): samples [C, S] float32 -> the fp64 MEAN SQUARES
+        [C, M] of the readings (the RMS is their sqrt), one reading per buffersPerReading buffers of bufferLength samples: the
+        greatest mean square of its buffers, NaN if its first buffer's is.  buffersPerReading None: the 0.1 s timer
+        (defaultBuffersPerReading).  Asynchronous on `stream`."""
+        self._check_samples(samples)
+        S = int(samples.shape[1])
+        return self._levels_device(_abi.lib.syldet_levels_device, samples, S, max(int(samples.stride(0)), S), bufferLength,
+                                   buffersPerReading, stream)
+
+    def levelsPCM16(self, samples, bufferLength: int = 32, buffersPerReading: Optional[int] = None, stream=None):
+        """levels() for 16-bit PCM [C, S] (an int16 CUDA tensor, x meaning x / 32768; syldet_levels_device_s16): levels()'s bits
+        for samples.float() * 2**-15."""
+        torch = _torch()
+        if not (samples.is_cuda and samples.dtype == torch.int16 and samples.dim() == 2 and samples.shape[0] == self.channels
+                and samples.stride(1) == 1 and samples.device.index == self.device):
+            raise ValueError("samples must be a 2-D int16 CUDA tensor [channels, n_samples] with contiguous rows on the detector's device")
+        S = int(samples.shape[1])
+        return self._levels_device(_abi.lib.syldet_levels_device_s16, samples, S, max(int(samples.stride(0)), S), bufferLength,
+                                   buffersPerReading, stream)
+
+    def levelsInterleaved(self, frames, bufferLength: int = 32, buffersPerReading: Optional[int] = None, stream=None):
+        """levels() on frames [n, C] float32 (syldet_levels_interleaved_device)."""
+        torch = _torch()
+        if not (frames.is_cuda and frames.dtype == torch.float32 and frames.dim() == 2 and frames.is_contiguous()
+                and frames.shape[1] == self.channels and frames.device.index == self.device):
+            raise ValueError("frames must be a contiguous 2-D float32 CUDA tensor [n_frames, channels] on the detector's device")
+        return self._levels_device(_abi.lib.syldet_levels_interleaved_device, frames, int(frames.shape[0]), self.channels, bufferLength,
+                                   buffersPerReading, stream)
+
+    def levelsInterleavedPCM16(self, frames, bufferLength: int = 32, buffersPerReading: Optional[int] = None, stream=None):
+        """levels() on 16-bit PCM frames [n, C] int16 (syldet_levels_interleaved_device_s16)."""
+        torch = _torch()
+        if not (frames.is_cuda and frames.dtype == torch.int16 and frames.dim() == 2 and frames.is_contiguous()
+                and frames.shape[1] == self.channels and frames.device.index == self.device):
+            raise ValueError("frames must be a contiguous 2-D int16 CUDA tensor [n_frames, channels] on the detector's device")
+        return self._levels_device(_abi.lib.syldet_levels_interleaved_device_s16, frames, int(frames.shape[0]), self.channels,
+                                   bufferLength, buffersPerReading, stream)
+
+    def _levels_host(self, fn, a, ptr_type, bufferLength, buffersPerReading):
+        S = a.shape[1]
+        L, P, M = self._levels_geometry(S, bufferLength, buffersPerReading)
+        rms = np.zeros((self.channels, M), np.float64)
+        if S > 0:
+            check(fn(self._h, a.ctypes.data_as(ptr_type), S, S, L, P, rms.ctypes.data_as(_abi.c_double_p)))
+        return rms
+
+    def levelsHost(self, samples: np.ndarray, bufferLength: int = 32, buffersPerReading: Optional[int] = None) -> np.ndarray:
+        """syldet_levels: host samples [C, S] -> the RMS readings [C, M] (getInputForChannel's values), blocking."""
+        a = np.ascontiguousarray(samples, dtype=np.float32)
+        a = a.reshape(self.channels, a.size // self.channels)
+        return self._levels_host(_abi.lib.syldet_levels, a, _abi.c_float_p, bufferLength, buffersPerReading)
+
+    def levelsPCM16Host(self, samples: np.ndarray, bufferLength: int = 32, buffersPerReading: Optional[int] = None) -> np.ndarray:
+        """syldet_levels_s16: levelsHost for an int16 array [C, S] (x meaning x / 32768)."""
+        a = np.ascontiguousarray(_pcm16(samples))
+        a = a.reshape(self.channels, a.size // self.channels)
+        return self._levels_host(_abi.lib.syldet_levels_s16, a, _abi.c_int16_p, bufferLength, buffersPerReading)
+
+    def outputLevels(self, outputs, n_samples: int, output: int = 0, bufferLength: int = 32, buffersPerReading: Optional[int] = None,
+                     stream=None):
+        """The output meter (syldet_output_levels_device): outputs [C, n_evals, n_out] (as run() returns them, for a recording of
+        n_samples samples) -> float32 [C, M], the greatest value of output `output` among the evaluations each reading's buffers
+        make available (NaN if the first of them is); 0 for a reading without an evaluation (levelsEvalRange tells which)."""
+        torch = _torch()
+        if not (outputs.is_cuda and outputs.dtype == torch.float32 and outputs.dim() == 3 and outputs.is_contiguous()
+                and outputs.shape[0] == self.channels and outputs.shape[2] == self.geometry.outputs
+                and outputs.device.index == self.device):
+            raise ValueError("outputs must be a contiguous float32 CUDA tensor [channels, n_evals, outputs] on the detector's device")
+        n, E = int(n_samples), int(outputs.shape[1])
+        L, P, M = self._levels_geometry(n, bufferLength, buffersPerReading)
+        lv = torch.empty((self.channels, M), dtype=torch.float32, device=outputs.device)
+        if n > 0:
+            # (an empty tensor has no address)
+            src = outputs if E > 0 else torch.zeros(1, dtype=torch.float32, device=outputs.device)
+            check(_abi.lib.syldet_output_levels_device(self._h, src.data_ptr(), E, int(output), n, L, P, lv.data_ptr(),
+                                                       self._stream_ptr(stream)))
+        return lv
+
+    def outputLevelsHost(self, outputs: np.ndarray, n_samples: int, output: int = 0, bufferLength: int = 32,
+                         buffersPerReading: Optional[int] = None) -> np.ndarray:
+        """outputLevels() on host arrays, blocking (syldet_output_levels)."""
+        a = np.ascontiguousarray(outputs, dtype=np.float32)
+        if a.ndim != 3 or a.shape[0] != self.channels or a.shape[2] != self.geometry.outputs:
+            raise ValueError("outputs must be [channels, n_evals, outputs]")
+        n, E = int(n_samples), a.shape[1]
+        L, P, M = self._levels_geometry(n, bufferLength, buffersPerReading)
+        lv = np.zeros((self.channels, M), np.float32)
+        if n > 0:
+            src = a if E > 0 else np.zeros(1, np.float32)
+            check(_abi.lib.syldet_output_levels(self._h, src.ctypes.data_as(_abi.c_float_p), E, int(output), n, L, P,
+                                                lv.ctypes.data_as(_abi.c_float_p)))
+        return lv
+
+    def monitor(self, samples, bufferLength: int = 32, buffersPerReading: Optional[int] = None, stream=None):
+        """run() and both meters on device tensors: samples [C, S] float32 -> (outputs, flags, mean squares [C, M] float64, output
+        levels [C, M] float32) -- what a ProcessorBase row shows beside its detections."""
+        outputs, flags = self.run(samples, stream=stream)
+        ms = self.levels(samples, bufferLength, buffersPerReading, stream=stream)
+        lv = self.outputLevels(outputs, int(samples.shape[1]), 0, bufferLength, buffersPerReading, stream=stream)
+        return outputs, flags, ms, lv
+
+    def enableMeters(self, enable: bool = True) -> None:
+        """syldet_meters_enable: the streaming meters (off by default); enabling or disabling clears them."""
+        check(_abi.lib.syldet_meters_enable(self._h, 1 if enable else 0))
+
+    def inputLevel(self, channel: int = 0) -> Optional[float]:
+        """getInputForChannel (Processor.swift:158-172): the RMS of the loudest buffer appended since the last call, read and
+        reset; None if nothing was appended (or the meters are off)."""
+        v, has = C.c_double(), C.c_int32()
+        check(_abi.lib.syldet_input_level(self._h, int(channel), C.byref(v), C.byref(has)))
+        return float(v.value) if has.value else None
+
+    def outputLevel(self, channel: int = 0) -> Optional[float]:
+        """getOutputForChannel (Processor.swift:174-184): the greatest output 0 evaluated since the last call, read and reset."""
+        v, has = C.c_double(), C.c_int32()
+        check(_abi.lib.syldet_output_level(self._h, int(channel), C.byref(v), C.byref(has)))
+        return float(v.value) if has.value else None
+
     # ---- measurement ------------------------------------------------------------------
     def profile(self, enable: bool = True, history: int = 1) -> None:
         """Bracket every kernel of a batch call with HIP events; `history`: how many calls' events to keep (a timing loop
