@@ -105,6 +105,7 @@ struct WideDesc {
 // columns [C][J][F] -> xn [C*E][kWideK] bf16 (scaling + input functions applied)
 int wide_front_stage_floats(int F, int I);
 bool wide_front_fits(int F, int I);        // WideDesc::front needs the columns under 512 evaluations in LDS
+bool wide_front_fits_half(int F, int I);   // ... and the two-workgroup forms (WideDesc::m32 among them) those under 256 in half a CU's
 bool wide_prep_is_chain(const NetDesc &n);   // which of the two preparation kernels launch_wide_prep picks (for timing labels)
 hipError_t launch_wide_prep(const NetDesc &n, int F, const float *columns, int C, int64_t J, int64_t E, void *xn, hipStream_t stream);
 // xn [NE][kWideK] -> outputs [NE][n_out], flags [NE]

@@ -18,6 +18,8 @@
 //
 // Precision is bf16's (8-bit significands on inputs and weights): this engine is opt-in
 // (SYLDET_ENGINE_WIDE_BF16), never chosen by AUTO, and its parity bar is stated separately (1e-2).
+// What the GEMM itself owes is held apart from what bf16 costs: 1e-5 against a bf16-exact model of this file's arithmetic
+// (tests/wide_ref.py lists where it rounds; tests/test_wide_model_gpu.py, profiles/wide_model_parity.json).
 //
 // gfx950 only.  wave = 64.
 
@@ -945,6 +947,7 @@ wide_gemm32s_kernel(WideDesc d, const float *__restrict__ columns, int64_t J, in
 int wide_front_stage_floats(int F, int I, int tile) { return (tile - 1) * F + I + 32 + tile + I / (F > 0 ? F : 1); }   // (+ slack, + the columns' sums of squares)
 int wide_front_stage_floats(int F, int I) { return wide_front_stage_floats(F, I, kWideTile); }
 bool wide_front_fits(int F, int I) { return (size_t)wide_front_stage_floats(F, I) * 4 + 2 * kChunkU4Pad * 16 <= 150 * 1024; }
+bool wide_front_fits_half(int F, int I) { return (size_t)wide_front_stage_floats(F, I, 256) * 4 + 2 * kChunkU4Pad * 16 <= 78 * 1024; }
 
 bool wide_prep_is_chain(const NetDesc &n)
 {

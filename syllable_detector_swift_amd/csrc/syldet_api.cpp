@@ -432,7 +432,9 @@ int upload_wide(syldet *h, std::string &why)
     // w1' = w1 / 2, b1' = b1 + sum w1 / 2.
     // SYLDET_WIDE_M32: the chunks in the 32x32x16 order for wide_gemm32s_kernel (one output, the front end, 256 evaluations' columns
     // and two chunk buffers in half a CU's LDS: launch_wide_gemm checks the same)
-    const bool m32 = shape16 && front && n_out == 1 && h->sw.wide_m32 && !h->sw.wide_tanh_poly;
+    // (a band too wide for that keeps the 16x16x32 kernel under the switch, as a network of several outputs does: the launch
+    // would refuse it)
+    const bool m32 = shape16 && front && n_out == 1 && h->sw.wide_m32 && !h->sw.wide_tanh_poly && wide_front_fits_half(h->geom.bins, I);
     const bool pack16 = shape16 && !m32;
     const bool poly = sig && shape16 && front && n_out == 1 && h->sw.wide_tanh_poly;   // (the forms that have an instantiation: kernels_wide.hip)
     const double sc = !sig ? 1.0 : poly ? (L0.transfer == SYLDET_TF_TANSIG ? 1.0 : 0.5)
