@@ -411,6 +411,26 @@ int syldet_fixup_stats(syldet_t *h, int64_t *items, int32_t *overflow);
  * (consecutive segments of a channel are computed by different workgroups; 0: the engine in use has no such seams).
  * Results do not depend on it; verification uses it to aim spot checks at the seams.  No reference counterpart.          */
 int64_t syldet_segment_evals(const syldet_t *h, int64_t n_samples);
+/* Which instantiation of the fused kernels ran: *kernel = 0 the 8-wave kernel, 1 the register-resident-basis kernel, 2 the
+ * symmetric-fold kernel; params = that instantiation's template arguments in declaration order (booleans as 0 / 1, defaulted
+ * ones included, zeros behind the last) -- of the calling thread's most recent batch or spectrogram call through this handle.
+ * SYLDET_ERR_UNSUPPORTED if that call ran no fused kernel (or the thread made none through this handle);
+ * SYLDET_ERR_INVALID_ARGUMENT for a NULL pointer.  Verification names the compiled form a case reached with it; results do not
+ * depend on it.  No reference counterpart (diagnostic).                                                                   */
+int syldet_last_fused_form(const syldet_t *h, int32_t *kernel, int32_t params[10]);
+/* The same answer from the host alone, without a device: the instantiation a handle of these configurations would run for a
+ * batch of n_samples per channel over n_channels channels.  n_nets == 1 and channel_net NULL: the handle syldet_create makes
+ * of cfgs[0]; otherwise syldet_create_multi's.  s16 != 0: the batch is 16-bit PCM in rows of whole words (syldet_run_device_s16
+ * on an aligned base with an even stride).  spectrogram != 0: syldet_spectrogram_device's transform instead of the batch call.
+ * The plan is built as the create call builds it, under the same SYLDET_FUSED_* switches, and handed to the very launchers the
+ * batch call uses, which record the form and return before they touch the device.  SYLDET_ERR_UNSUPPORTED (syldet_last_error
+ * says why) for what is not on the fused engine: what AUTO keeps elsewhere, batches without an evaluation; the create calls'
+ * statuses for what they refuse.  No reference counterpart (diagnostic).                                                */
+int syldet_fused_form_of_config(const syldet_config_t *const *cfgs, int32_t n_nets, const int32_t *channel_net, int32_t n_channels,
+                                int64_t n_samples, int32_t s16, int32_t spectrogram, int32_t engine, int32_t *kernel, int32_t params[10]);
+/* 1 while the calling thread is inside syldet_fused_form_of_config's dry run of the launchers, 0 at any other time -- a failed
+ * plan included (verification: a launch after it must reach the device).                                                    */
+int32_t syldet_fused_dry_run_active(void);
 
 /* ---- streaming: the reference's per-detector API, one call per channel ----
  * Each channel owns a single-producer / single-consumer sample ring like the reference's

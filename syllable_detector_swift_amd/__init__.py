@@ -10,11 +10,11 @@ from .config import (InvalidValue, MismatchedLength, MissingValue, NeuralNet, Ne
                      ProcessingFunction, SyllableDetectorConfig, SyllableDetectorError, UnableToOpenPath,
                      createWindow, frequencyIndexRange)
 from .bank import PinnedArray, ShardedSyllableDetectorBank, shard_table
-from .detector import SyllableDetector, configsCompatible, configsShareClock
+from .detector import SyllableDetector, configsCompatible, configsShareClock, fusedFormOfConfig
 from .resampler import ResamplerLinear, deinterleave
 
 __all__ = ["SyllableDetector", "SyllableDetectorConfig", "NeuralNet", "NeuralNetLayer", "ProcessingFunction",
            "ParseError", "UnableToOpenPath", "MissingValue", "InvalidValue", "MismatchedLength",
            "SyllableDetectorError", "frequencyIndexRange", "createWindow", "ResamplerLinear", "deinterleave",
            "ShardedSyllableDetectorBank", "PinnedArray", "shard_table", "configsCompatible",
-           "configsShareClock"]
+           "configsShareClock", "fusedFormOfConfig"]

@@ -143,6 +143,10 @@ SIGNATURES = {
     "syldet_timings": (C.c_int, [Handle, C.c_int32, c_double_p, C.POINTER(C.c_char_p), C.c_int32, c_int32_p]),
     "syldet_fixup_stats": (C.c_int, [Handle, c_int64_p, c_int32_p]),
     "syldet_segment_evals": (C.c_int64, [Handle, C.c_int64]),
+    "syldet_last_fused_form": (C.c_int, [Handle, c_int32_p, c_int32_p]),
+    "syldet_fused_form_of_config": (C.c_int, [C.POINTER(Config_p), C.c_int32, c_int32_p, C.c_int32, C.c_int64, C.c_int32, C.c_int32, C.c_int32,
+                                              c_int32_p, c_int32_p]),
+    "syldet_fused_dry_run_active": (C.c_int32, []),
     "syldet_append": (C.c_int, [Handle, C.c_int32, c_float_p, C.c_int64]),
     "syldet_append_interleaved": (C.c_int, [Handle, c_float_p, C.c_int64, C.c_int32]),
     "syldet_append_interleaved_channels": (C.c_int, [Handle, c_float_p, C.c_int64, C.c_int32, C.POINTER(C.c_int32)]),

@@ -821,4 +821,10 @@ void fused_segmentation(FusedDesc &d, int64_t E, int C)
     }
 }
 
+FusedSeam &fused_seam()
+{
+    static thread_local FusedSeam seam{{-1, {0, 0, 0, 0, 0, 0, 0, 0, 0, 0}}, false};
+    return seam;
+}
+
 }  // namespace sd

@@ -343,6 +343,27 @@ struct FlagSources {
 hipError_t launch_unpack_flags_from(const FlagSources &from, int64_t rows, int64_t row_len, int64_t shards, int64_t padded,
                                     uint8_t *flags, hipStream_t stream);
 
+// ---- which instantiation ran (the tests' seam: syldet_last_fused_form, syldet_fused_form_of_config) ----
+// Every launch_one of the three fused kernel files leaves its template arguments here before its first HIP call: kernel as in
+// fused_choice (0 the 8-wave kernel, 1 the register-resident-basis kernel, 2 the symmetric-fold kernel), p the arguments in
+// declaration order, defaulted ones included (booleans as 0 / 1), zero behind the last.  Under `dry` it then returns hipSuccess
+// without touching the device: the launchers themselves say which form a plan takes, nothing restates their routing.
+struct FusedForm {
+    int kernel;
+    int p[10];
+};
+struct FusedSeam {
+    FusedForm last;
+    bool dry;
+};
+FusedSeam &fused_seam();        // the calling thread's (fused_plan.cpp)
+inline bool fused_note_form(int kernel, int p0, int p1, int p2, int p3, int p4, int p5, int p6 = 0, int p7 = 0, int p8 = 0, int p9 = 0)
+{
+    FusedSeam &s = fused_seam();
+    s.last = FusedForm{kernel, {p0, p1, p2, p3, p4, p5, p6, p7, p8, p9}};
+    return s.dry;
+}
+
 // mn: a multi-network handle's tables (only the fold kernel has that form: anything else is hipErrorInvalidValue)
 // s16: `samples` are int16 rows (16-bit PCM, x * 2^-15), only where fused_s_native_s16(d) and the fold kernel is chosen
 hipError_t launch_fused(const FusedDesc &d, const float *samples, int64_t stride, int C, int64_t S, int64_t J,

@@ -770,6 +770,7 @@ template <int KS, int TMAX, int NL, bool EXACT, bool SKEW, bool LEAN = false, bo
 hipError_t launch_one(const FusedDesc &d, const float *samples, int64_t stride, int C, int64_t s_eff, int64_t E,
                       float *outputs, uint8_t *flags, hipStream_t stream)
 {
+    if (fused_note_form(0, KS, TMAX, NL, EXACT, SKEW, LEAN, STAMP, KNOCK, SPECT)) return hipSuccess;
     auto kern = fused_kernel<KS, TMAX, NL, EXACT, SKEW, LEAN, STAMP, KNOCK, SPECT>;
     hipError_t st = hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, d.lds_total);
     if (st != hipSuccess) return st;

@@ -682,6 +682,7 @@ template <int KS, int TMAX, int NL, int SKEW, bool STAMP = false, bool GEN = fal
 hipError_t launch_one(const FusedDesc &d, const float *samples, int64_t stride, int C, int64_t s_eff, int64_t E,
                       float *outputs, uint8_t *flags, hipStream_t stream)
 {
+    if (fused_note_form(1, KS, TMAX, NL, SKEW, STAMP, GEN)) return hipSuccess;
     auto kern = fused_r_kernel<KS, TMAX, NL, SKEW, STAMP, GEN>;
     hipError_t st = hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, d.r_lds_total);
     if (st != hipSuccess) return st;

@@ -1028,6 +1028,7 @@ hipError_t launch_one(const FusedDesc &d, const float *samples, int64_t stride, 
     // (every network instantiation has its multi-network twin)
     if constexpr (!SPECT && !MN)
         if (mn) return launch_one<K2, GEN, HQ, NW, PADP, F2, NT, false, true, S16>(d, samples, stride, C, s_eff, E, outputs, flags, stream, mn);
+    if (fused_note_form(2, K2, GEN, HQ, NW, PADP, F2, NT, SPECT, MN, S16)) return hipSuccess;
     auto kern = fused_s_kernel<K2, GEN, HQ, NW, PADP, F2, NT, SPECT, MN, S16>;
     constexpr int kWaves = NW;
 #ifdef SYLDET_S_ONEWAVE

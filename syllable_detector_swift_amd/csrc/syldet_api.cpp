@@ -633,7 +633,8 @@ int upload_bdft(syldet *h)
 
 // A plan for the DFT front half alone: the real STFT geometry with a one-frame, one-unit stand-in network (the
 // spectrogram instantiation never touches the network tables).
-int build_dft_plan(syldet *h)
+// (the host half: the plan itself, and whether a fused kernel has a spectrogram instantiation for it)
+bool plan_dft(syldet *h)
 {
     const syldet_config_t &c = h->cfg.view;
     syldet_config_t sc = c;
@@ -649,12 +650,17 @@ int build_dft_plan(syldet *h)
     sc.n_layers = 2; sc.layers = layers; sc.n_thresholds = 1; sc.thresholds = &thr;
     syldet_geometry_t sg = h->geom;
     sg.inputs = F; sg.outputs = 1;
-    if (!make_fused_plan(sc, sg, h->dft)) return SYLDET_OK;          // not applicable: the generic FFT stays
+    if (!make_fused_plan(sc, sg, h->dft)) return false;              // not applicable: the generic FFT stays
     // (two spectrogram instantiations: the fold kernel's twice-folded form for 256-point frames under a 256-sample window,
     // the 8-wave kernel's for its shapes)
-    if (!h->dft.desc.classic_ok && !fused_s_spectrogram_applicable(h->dft.desc)) return SYLDET_OK;
+    return h->dft.desc.classic_ok || fused_s_spectrogram_applicable(h->dft.desc);
+}
+
+int build_dft_plan(syldet *h)
+{
+    if (!plan_dft(h)) return SYLDET_OK;
     if (int st = upload_plan(h, h->dft, h->d_dft)) return st;
-    h->dft.desc.spect_power = c.spectrum == SYLDET_SPECTRUM_MAGNITUDE ? 1 : 0;
+    h->dft.desc.spect_power = h->cfg.view.spectrum == SYLDET_SPECTRUM_MAGNITUDE ? 1 : 0;
     h->has_dft = true;
     return SYLDET_OK;
 }
@@ -682,6 +688,26 @@ int64_t count_evals(const syldet *h, int64_t S)
     const int64_t J = count_frames(h, S);
     const int T = h->cfg.view.time_range;
     return J >= T ? J - T + 1 : 0;                                           // SyllableDetector.swift:164-178
+}
+
+// The calling thread's most recent batch call: the handle it went through and, if a fused kernel ran, the instantiation its
+// launcher recorded (kernels.hpp, FusedForm) -- syldet_last_fused_form.  A class handle's launch counts for its bank.
+struct LastCall {
+    const syldet *h = nullptr;
+    bool fused = false;
+    FusedForm form{};
+};
+thread_local LastCall t_last_call;
+void note_call_begin(const syldet *h)
+{
+    t_last_call.h = h->root ? h->root : h;
+    t_last_call.fused = false;
+}
+void note_fused_launch(const syldet *h)
+{
+    t_last_call.h = h->root ? h->root : h;
+    t_last_call.fused = true;
+    t_last_call.form = fused_seam().last;
 }
 
 // Brackets one kernel launch with events on its own stream when profiling is on.
@@ -742,8 +768,9 @@ int timed_fixup(syldet *hc, hipStream_t stream, FixList list, F launch)
 // samples -> [C][J][F] columns: the fused engine's DFT half where its shape allows (and the handle was not created
 // for the generic engine outright), the generic FFT otherwise
 // row_of: a mixed bank's class launch, channel c reads bank row row_of[c] (the generic FFT kernels only)
-int stft_on_stream(syldet *h, const float *d_samples, int64_t stride, int C, int64_t J, float *d_columns, hipStream_t stream,
-                   bool for_network = true, const int *row_of = nullptr)
+// The transform's decision for J frames of C rows: whether a fused kernel's spectrogram instantiation takes them, the plan `d` it
+// runs, and whether that is the fold kernel's (`fold`) or the 8-wave kernel's.  (stft_on_stream, syldet_fused_form_of_config)
+bool dft_route_for(const syldet *h, int64_t J, int C, bool for_network, const int *row_of, float *d_columns, FusedDesc &d, bool &fold)
 {
     // columns that go through log / dB keep the generic FFT: its error is relative to the frame, the block-floating-point
     // DFT's to the loudest sample of the 128-frame pass, and the logarithm turns relative error of weak bins into absolute
@@ -751,18 +778,25 @@ int stft_on_stream(syldet *h, const float *d_samples, int64_t stride, int C, int
     // ... and columns that meet a network without a normaliser in front keep it too (normalised_chain above); the wide engine
     // is bf16 behind either
     const bool level_input = for_network && !normalised_chain(h->cfg.view) && h->engine != SYLDET_ENGINE_WIDE_BF16 && h->engine_asked == SYLDET_ENGINE_AUTO;
-    if (h->has_dft && !log_input && !level_input && !row_of && (uint64_t)J * (uint64_t)h->geom.bins * 4u < 0xFFFFFFF0ull) {
-        FusedDesc d = h->dft.desc;
-        fused_segmentation(d, J, C);
-        d.spect_out = d_columns;
-        d.stamps = nullptr;
-        d.ko = 0;
-        d.no_fold2 = h->sw.fused_nofold2 ? 1 : 0;
-        d.no_cs8 = h->sw.fused_pad128 ? 1 : 0;
-        // the fold kernel's spectrogram instantiation where the plan allows it (rows under 2 GiB: its 32-bit byte offsets)
-        const bool fold = !h->sw.fused_nofold && fused_s_spectrogram_applicable(d) &&
-                          ((J - 1) * (int64_t)d.hop + d.gap + d.W) * 4 < 0x7fffffffll;
-        if (!fold && !d.classic_ok) goto generic_transform;
+    if (!(h->has_dft && !log_input && !level_input && !row_of && (uint64_t)J * (uint64_t)h->geom.bins * 4u < 0xFFFFFFF0ull)) return false;
+    d = h->dft.desc;
+    fused_segmentation(d, J, C);
+    d.spect_out = d_columns;
+    d.stamps = nullptr;
+    d.ko = 0;
+    d.no_fold2 = h->sw.fused_nofold2 ? 1 : 0;
+    d.no_cs8 = h->sw.fused_pad128 ? 1 : 0;
+    // the fold kernel's spectrogram instantiation where the plan allows it (rows under 2 GiB: its 32-bit byte offsets)
+    fold = !h->sw.fused_nofold && fused_s_spectrogram_applicable(d) && ((J - 1) * (int64_t)d.hop + d.gap + d.W) * 4 < 0x7fffffffll;
+    return fold || d.classic_ok;
+}
+
+int stft_on_stream(syldet *h, const float *d_samples, int64_t stride, int C, int64_t J, float *d_columns, hipStream_t stream,
+                   bool for_network = true, const int *row_of = nullptr)
+{
+    FusedDesc d{};
+    bool fold = false;
+    if (dft_route_for(h, J, C, for_network, row_of, d_columns, d, fold)) {
         // the precision guard's work list, and behind the kernel the exact recomputation of the frames it reports
         if (int st = prepare_fix(h, C, J, (J + d.seg_evals - 1) / d.seg_evals + (d.s_seg_evals > 0 ? (J + d.s_seg_evals - 1) / d.s_seg_evals : 0), stream, d.fix)) return st;
         if (fold) {
@@ -772,9 +806,9 @@ int stft_on_stream(syldet *h, const float *d_samples, int64_t stride, int C, int
             KernelTimer t(h, stream, "fused_kernel (spectrogram)");
             SYLDET_HIP(launch_fused_spectrogram(d, d_samples, stride, C, J, stream));
         }
+        note_fused_launch(h);
         return timed_fixup(h, stream, d.fix, [&](const FixList &l) { return launch_fixup(h->fixd, h->net, d_samples, stride, J, 0, nullptr, nullptr, d_columns, l, stream); });
     }
-generic_transform:
     StftDesc sd = h->stft;
     sd.row_of = row_of;
     if (!h->sw.no_stft_lanes && stft_lanes_applicable(sd, d_samples, stride)) {
@@ -866,6 +900,7 @@ int run_on_stream(syldet *h, Samples x, int64_t S, int64_t stride, int C, float 
     if (E <= 0) return SYLDET_OK;
     SYLDET_HIP(hipSetDevice(h->device));
     if (!h->root) h->prof_begin();                   // (a class handle's launches belong to its bank's call)
+    if (!h->root) note_call_begin(h);
     if (!h->classes.empty()) {
         // a mixed bank over all its channels: each class in turn, in place through its row table.  16-bit PCM: a class on the
         // fold kernel's s16 form reads the int16 rows in place; the others share one widened copy, made at most once a call.
@@ -968,6 +1003,7 @@ int run_on_stream(syldet *h, Samples x, int64_t S, int64_t stride, int C, float 
             static const char *const names[3] = {"fused_kernel", "fused_r_kernel", "fused_s_kernel"};
             KernelTimer t(h, stream, names[fused_choice(d, J)]);
             SYLDET_HIP(launch_fused(d, d_samples, stride, C, S, J, E, d_outputs, d_flags, stream, mnp, x.s16));
+            note_fused_launch(h);
         }
         FixDesc fd = h->fixd;
         fd.s16 = x.s16 ? 1 : 0;                      // (the exact recomputation reads the same rows)
@@ -1136,37 +1172,39 @@ int upload_generic_nets(syldet *h, const std::vector<std::unique_ptr<OwnedConfig
     return SYLDET_OK;
 }
 
-}  // namespace
-
-extern "C" {
-
-int syldet_create(const syldet_config_t *cfg, int32_t n_channels, int32_t device, int32_t engine, syldet_t **out)
+// A multi-network handle's networks: owned copies, every one compatible with network 0, and whether all of them would run on
+// the fold kernel under AUTO (`fold`) / take it at all (`fused_ok`) -- host work only.
+int survey_nets(const syldet_config_t *const *cfgs, int32_t n_nets, std::vector<std::unique_ptr<OwnedConfig>> &own, bool &fold, bool &fused_ok)
 {
-    if (!cfg || !out) return fail(SYLDET_ERR_INVALID_ARGUMENT, "NULL argument");
-    *out = nullptr;
-    if (n_channels <= 0 || n_channels > 65535)
-        return fail(SYLDET_ERR_INVALID_ARGUMENT, "n_channels must be in [1, 65535]");
-    if (engine != SYLDET_ENGINE_AUTO && engine != SYLDET_ENGINE_GENERIC && engine != SYLDET_ENGINE_FUSED && engine != SYLDET_ENGINE_WIDE_BF16)
-        return fail(SYLDET_ERR_INVALID_ARGUMENT, "unknown engine");
-    std::unique_ptr<syldet> h(new (std::nothrow) syldet());
-    if (!h) return fail(SYLDET_ERR_OUT_OF_MEMORY, "out of memory");
-    if (int st = h->cfg.assign(*cfg)) return st;
-    if (int st = compute_geometry(h->cfg.view, &h->geom)) return st;
-    h->sw.read();
-    if (h->sw.host_chunk > 0) h->host_chunk_bytes = (size_t)h->sw.host_chunk;
+    syldet::Switches sw;
+    sw.read();
+    fold = fused_ok = true;
+    try {
+        for (int32_t i = 0; i < n_nets; i++) {
+            own.emplace_back(new OwnedConfig());
+            if (int st = own.back()->assign(*cfgs[i])) return st;
+            syldet_geometry_t g{};
+            if (int st = compute_geometry(own.back()->view, &g)) return st;
+            const char *field = nullptr;
+            const int cmp = syldet_config_compatible(cfgs[0], cfgs[i], &field);
+            if (cmp < 0) return cmp;
+            if (cmp == 0)
+                return fail(SYLDET_ERR_UNSUPPORTED, "network " + std::to_string(i) + " is not compatible with network 0: " + field +
+                                                        " differs (networks that differ there need a handle each)");
+            bool ok = false;
+            if (!takes_fold(own.back()->view, g, sw, ok)) fold = false;
+            if (!ok) fused_ok = false;
+        }
+    } catch (const std::bad_alloc &) {
+        return fail(SYLDET_ERR_OUT_OF_MEMORY, "out of memory");
+    }
+    return SYLDET_OK;
+}
 
-    int n_dev = 0;
-    hipError_t e = hipGetDeviceCount(&n_dev);
-    if (e != hipSuccess || n_dev <= 0)
-        return fail(SYLDET_ERR_NO_DEVICE, std::string("no HIP device: ") + (e != hipSuccess ? hipGetErrorString(e) : "count is 0"));
-    if (device < 0 || device >= n_dev) return fail(SYLDET_ERR_NO_DEVICE, "device index out of range");
-    hipDeviceProp_t prop;
-    if (hipGetDeviceProperties(&prop, device) != hipSuccess) return fail(SYLDET_ERR_NO_DEVICE, "hipGetDeviceProperties failed");
-    if (std::strncmp(prop.gcnArchName, "gfx950", 6) != 0)
-        return fail(SYLDET_ERR_NO_DEVICE, std::string("libsyldet is built for gfx950 only, found ") + prop.gcnArchName);
-    SYLDET_HIP(hipSetDevice(device));
-    h->device = device;
-    h->channels = n_channels;
+// syldet_create's choice between the fused and the generic engine for a handle whose configuration, geometry and switches are in
+// place (host work only: the fused plan is made here, uploaded later).
+int choose_engine(syldet *h, int engine)
+{
     h->engine_asked = engine;
     h->engine = SYLDET_ENGINE_GENERIC;
     if (engine != SYLDET_ENGINE_GENERIC && engine != SYLDET_ENGINE_WIDE_BF16) {
@@ -1199,6 +1237,41 @@ int syldet_create(const syldet_config_t *cfg, int32_t n_channels, int32_t device
             return fail(SYLDET_ERR_UNSUPPORTED, "fused engine not available for this configuration: " + h->fused.reason);
         }
     }
+    return SYLDET_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int syldet_create(const syldet_config_t *cfg, int32_t n_channels, int32_t device, int32_t engine, syldet_t **out)
+{
+    if (!cfg || !out) return fail(SYLDET_ERR_INVALID_ARGUMENT, "NULL argument");
+    *out = nullptr;
+    if (n_channels <= 0 || n_channels > 65535)
+        return fail(SYLDET_ERR_INVALID_ARGUMENT, "n_channels must be in [1, 65535]");
+    if (engine != SYLDET_ENGINE_AUTO && engine != SYLDET_ENGINE_GENERIC && engine != SYLDET_ENGINE_FUSED && engine != SYLDET_ENGINE_WIDE_BF16)
+        return fail(SYLDET_ERR_INVALID_ARGUMENT, "unknown engine");
+    std::unique_ptr<syldet> h(new (std::nothrow) syldet());
+    if (!h) return fail(SYLDET_ERR_OUT_OF_MEMORY, "out of memory");
+    if (int st = h->cfg.assign(*cfg)) return st;
+    if (int st = compute_geometry(h->cfg.view, &h->geom)) return st;
+    h->sw.read();
+    if (h->sw.host_chunk > 0) h->host_chunk_bytes = (size_t)h->sw.host_chunk;
+
+    int n_dev = 0;
+    hipError_t e = hipGetDeviceCount(&n_dev);
+    if (e != hipSuccess || n_dev <= 0)
+        return fail(SYLDET_ERR_NO_DEVICE, std::string("no HIP device: ") + (e != hipSuccess ? hipGetErrorString(e) : "count is 0"));
+    if (device < 0 || device >= n_dev) return fail(SYLDET_ERR_NO_DEVICE, "device index out of range");
+    hipDeviceProp_t prop;
+    if (hipGetDeviceProperties(&prop, device) != hipSuccess) return fail(SYLDET_ERR_NO_DEVICE, "hipGetDeviceProperties failed");
+    if (std::strncmp(prop.gcnArchName, "gfx950", 6) != 0)
+        return fail(SYLDET_ERR_NO_DEVICE, std::string("libsyldet is built for gfx950 only, found ") + prop.gcnArchName);
+    SYLDET_HIP(hipSetDevice(device));
+    h->device = device;
+    h->channels = n_channels;
+    if (int st = choose_engine(h.get(), engine)) return st;
     h->geom.engine = h->engine;
     SYLDET_HIP(hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking));
     if (int st = build_tables(h.get())) {
@@ -1329,28 +1402,8 @@ static int create_multi_impl(const syldet_config_t *const *cfgs, int32_t n_nets,
             return fail(SYLDET_ERR_INVALID_ARGUMENT, "channel_net[" + std::to_string(c) + "] = " + std::to_string(channel_net[c]) + " is outside [0, n_nets)");
     if (engine == SYLDET_ENGINE_WIDE_BF16) return fail(SYLDET_ERR_UNSUPPORTED, "the wide-network engine has no multi-network form");
     std::vector<std::unique_ptr<OwnedConfig>> own;
-    syldet::Switches sw;
-    sw.read();
     bool fold = true, fused_ok = true;
-    try {
-        for (int32_t i = 0; i < n_nets; i++) {
-            own.emplace_back(new OwnedConfig());
-            if (int st = own.back()->assign(*cfgs[i])) return st;
-            syldet_geometry_t g{};
-            if (int st = compute_geometry(own.back()->view, &g)) return st;
-            const char *field = nullptr;
-            const int cmp = syldet_config_compatible(cfgs[0], cfgs[i], &field);
-            if (cmp < 0) return cmp;
-            if (cmp == 0)
-                return fail(SYLDET_ERR_UNSUPPORTED, "network " + std::to_string(i) + " is not compatible with network 0: " + field +
-                                                        " differs (networks that differ there need a handle each)");
-            bool ok = false;
-            if (!takes_fold(own.back()->view, g, sw, ok)) fold = false;
-            if (!ok) fused_ok = false;
-        }
-    } catch (const std::bad_alloc &) {
-        return fail(SYLDET_ERR_OUT_OF_MEMORY, "out of memory");
-    }
+    if (int st = survey_nets(cfgs, n_nets, own, fold, fused_ok)) return st;
     // one network: exactly a syldet_create handle
     if (n_nets == 1 && !mixed_class) return syldet_create(cfgs[0], n_channels, device, engine, out);
     if (engine == SYLDET_ENGINE_FUSED && !fused_ok)
@@ -1564,6 +1617,7 @@ int syldet_channel_geometry(const syldet_t *h, int32_t channel, syldet_geometry_
 int syldet_destroy(syldet_t *h)
 {
     if (!h) return SYLDET_OK;
+    if (t_last_call.h == h) t_last_call = LastCall();     // (the next handle may get this address)
     (void)hipSetDevice(h->device);
     if (h->stream) {
         (void)hipStreamSynchronize(h->stream);
@@ -1705,6 +1759,98 @@ int64_t syldet_segment_evals(const syldet_t *h, int64_t n_samples)
     return choice == 2 ? d.s_seg_evals : (choice == 1 ? d.r_seg_evals : d.seg_evals);
 }
 
+int syldet_last_fused_form(const syldet_t *h, int32_t *kernel, int32_t params[10])
+{
+    if (!h || !kernel || !params) return fail(SYLDET_ERR_INVALID_ARGUMENT, "NULL argument");
+    if (t_last_call.h != h || !t_last_call.fused) return fail(SYLDET_ERR_UNSUPPORTED, "this thread's last call through the handle ran no fused kernel");
+    *kernel = t_last_call.form.kernel;
+    for (int i = 0; i < 10; i++) params[i] = t_last_call.form.p[i];
+    return SYLDET_OK;
+}
+
+int32_t syldet_fused_dry_run_active(void) { return fused_seam().dry ? 1 : 0; }
+
+int syldet_fused_form_of_config(const syldet_config_t *const *cfgs, int32_t n_nets, const int32_t *channel_net, int32_t n_channels,
+                                int64_t n_samples, int32_t s16, int32_t spectrogram, int32_t engine, int32_t *kernel, int32_t params[10])
+{
+    if (!cfgs || !kernel || !params) return fail(SYLDET_ERR_INVALID_ARGUMENT, "NULL argument");
+    if (n_nets < 1 || (n_nets > 1 && !channel_net)) return fail(SYLDET_ERR_INVALID_ARGUMENT, "n_nets must be >= 1, with a channel_net for more than one");
+    if (n_channels <= 0 || n_channels > 65535) return fail(SYLDET_ERR_INVALID_ARGUMENT, "n_channels must be in [1, 65535]");
+    if (n_samples < 0) return fail(SYLDET_ERR_INVALID_ARGUMENT, "n_samples must be >= 0");
+    if (engine != SYLDET_ENGINE_AUTO && engine != SYLDET_ENGINE_GENERIC && engine != SYLDET_ENGINE_FUSED && engine != SYLDET_ENGINE_WIDE_BF16)
+        return fail(SYLDET_ERR_INVALID_ARGUMENT, "unknown engine");
+    for (int32_t i = 0; i < n_nets; i++)
+        if (!cfgs[i]) return fail(SYLDET_ERR_INVALID_ARGUMENT, "NULL configuration " + std::to_string(i));
+    const bool multi = channel_net != nullptr && n_nets > 1;
+    for (int32_t c = 0; multi && c < n_channels; c++)
+        if (channel_net[c] < 0 || channel_net[c] >= n_nets) return fail(SYLDET_ERR_INVALID_ARGUMENT, "channel_net entry outside [0, n_nets)");
+    // the launchers run dry from here to the end of the call, whichever way it ends
+    struct Dry {
+        Dry() { fused_seam().dry = true; fused_seam().last.kernel = -1; }
+        ~Dry() { fused_seam().dry = false; }
+    } dry;
+    // a handle as the create calls make it, as far as the host goes: configuration, geometry, switches, engine, plans
+    int asked = engine;
+    bool on_fold = false;
+    if (multi) {
+        if (engine == SYLDET_ENGINE_WIDE_BF16) return fail(SYLDET_ERR_UNSUPPORTED, "the wide-network engine has no multi-network form");
+        std::vector<std::unique_ptr<OwnedConfig>> own;
+        bool fold = true, fused_ok = true;
+        if (int st = survey_nets(cfgs, n_nets, own, fold, fused_ok)) return st;
+        if (engine == SYLDET_ENGINE_FUSED && !fused_ok)
+            return fail(SYLDET_ERR_UNSUPPORTED, "fused engine on a multi-network handle: only the fold kernel has that form, and it does not take this shape");
+        on_fold = engine == SYLDET_ENGINE_FUSED || (engine == SYLDET_ENGINE_AUTO && fold);
+        if (!on_fold) asked = SYLDET_ENGINE_GENERIC;
+    }
+    std::unique_ptr<syldet> h(new (std::nothrow) syldet());
+    if (!h) return fail(SYLDET_ERR_OUT_OF_MEMORY, "out of memory");
+    if (int st = h->cfg.assign(*cfgs[0])) return st;
+    if (int st = compute_geometry(h->cfg.view, &h->geom)) return st;
+    h->sw.read();
+    h->channels = n_channels;
+    if (int st = choose_engine(h.get(), asked)) return st;
+    static const FusedNet no_tables{};                     // (never read: a multi-network handle's tables are on the device)
+    if (multi) {
+        h->n_nets = n_nets;
+        if (on_fold) {
+            if (h->engine != SYLDET_ENGINE_FUSED) return fail(SYLDET_ERR_UNSUPPORTED, "the fold kernel did not take network 0");
+            h->fnets = &no_tables;
+        }
+    }
+    const int C = n_channels;
+    const int64_t S = n_samples, J = count_frames(h.get(), S), E = count_evals(h.get(), S);
+    FusedDesc d{};
+    hipError_t e = hipSuccess;
+    if (spectrogram) {
+        if (multi) return fail(SYLDET_ERR_UNSUPPORTED, "the transform's form is asked of one configuration");
+        if (J <= 0) return fail(SYLDET_ERR_UNSUPPORTED, "not on the fused engine: no frame in n_samples");
+        if (asked != SYLDET_ENGINE_GENERIC && plan_dft(h.get())) {
+            h->dft.desc.spect_power = h->cfg.view.spectrum == SYLDET_SPECTRUM_MAGNITUDE ? 1 : 0;
+            h->has_dft = true;
+        }
+        bool fold = false;
+        static float no_columns;                           // (never written: the launcher wants a destination)
+        if (!dft_route_for(h.get(), J, C, false, nullptr, &no_columns, d, fold))
+            return fail(SYLDET_ERR_UNSUPPORTED, "not on the fused engine: the transform keeps the generic FFT");
+        e = fold ? launch_fused_s_spectrogram(d, nullptr, S, C, J, nullptr) : launch_fused_spectrogram(d, nullptr, S, C, J, nullptr);
+    } else {
+        if (E <= 0) return fail(SYLDET_ERR_UNSUPPORTED, "not on the fused engine: no evaluation in n_samples");
+        if (h->sw.fused_stamps) return fail(SYLDET_ERR_UNSUPPORTED, "SYLDET_FUSED_STAMPS: the diagnostic instantiations are not reported");
+        if (!fused_route_for(h.get(), J, E, C, d))
+            return fail(SYLDET_ERR_UNSUPPORTED, "not on the fused engine" + (h->fused.reason.empty() ? std::string() : ": " + h->fused.reason));
+        // (16-bit PCM: natively where this batch takes the fold kernel's s16 form, else widened to fp32 first, as run_on_stream does)
+        const bool native = s16 != 0 && takes_native_s16(h.get(), Samples(nullptr, true), S, (S + 1) & ~(int64_t)1, C);
+        FusedMulti mn{h->fnets, nullptr, nullptr};
+        e = launch_fused(d, nullptr, (S + 1) & ~(int64_t)1, C, S, J, E, nullptr, nullptr, nullptr, h->fnets ? &mn : nullptr, native);
+    }
+    if (e != hipSuccess) return fail(SYLDET_ERR_UNSUPPORTED, "not on the fused engine: no instantiation takes the plan");
+    const FusedForm &f = fused_seam().last;
+    if (f.kernel < 0) return fail(SYLDET_ERR_UNSUPPORTED, "not on the fused engine: the launcher ran nothing");
+    *kernel = f.kernel;
+    for (int i = 0; i < 10; i++) params[i] = f.p[i];
+    return SYLDET_OK;
+}
+
 int64_t syldet_count_frames(const syldet_t *h, int64_t n_samples) { return h ? count_frames(h, n_samples) : -1; }
 int64_t syldet_count_evals(const syldet_t *h, int64_t n_samples) { return h ? count_evals(h, n_samples) : -1; }
 
@@ -1731,6 +1877,7 @@ int syldet_spectrogram_device(syldet_t *h, const float *d_samples, int64_t n_sam
     SYLDET_HIP(hipSetDevice(h->device));
     const int64_t J = count_frames(h, n_samples);
     h->prof_begin();
+    note_call_begin(h);
     return stft_on_stream(h->classes.empty() ? h : h->classes[0].get(), d_samples, channel_stride, h->channels, J, d_columns, (hipStream_t)hip_stream, false);
 }
 

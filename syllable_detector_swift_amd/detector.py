@@ -598,6 +598,14 @@ class SyllableDetector:
         """Evaluations per workgroup segment of the fused kernels for a batch of this length (0: no seams)."""
         return int(_abi.lib.syldet_segment_evals(self._h, int(n_samples)))
 
+    def lastFusedForm(self):
+        """syldet_last_fused_form: (kernel, template arguments) of the fused kernel instantiation this thread's last batch or
+        spectrogram call through the detector ran -- kernel 0 the 8-wave kernel, 1 the register-resident-basis kernel, 2 the
+        symmetric-fold kernel; raises SyllableDetectorError (unsupported) if that call ran no fused kernel."""
+        kernel, params = C.c_int32(), (C.c_int32 * 10)()
+        check(_abi.lib.syldet_last_fused_form(self._h, C.byref(kernel), params))
+        return int(kernel.value), tuple(int(v) for v in params)
+
     # ---- batch, host arrays -------------------------------------------------------
     def runHost(self, samples: np.ndarray, outputs: Optional[np.ndarray] = None, flags: Optional[np.ndarray] = None) -> Tuple[np.ndarray, np.ndarray]:
         """syldet_run: the batch call on host arrays, pipelined along time inside the library.  `outputs` / `flags`: arrays to
@@ -672,3 +680,19 @@ def configsShareClock(a: SyllableDetectorConfig, b: SyllableDetectorConfig) -> T
     r = check(_abi.lib.syldet_config_same_clock(C.byref(ca), C.byref(cb), C.byref(field)))
     del ka, kb
     return (True, None) if r == 1 else (False, field.value.decode() if field.value else None)
+
+
+def fusedFormOfConfig(configs, channels: int, n_samples: int, channelNetworks=None, s16: bool = False, spectrogram: bool = False,
+                      engine: int = _abi.ENGINE_AUTO):
+    """syldet_fused_form_of_config: (kernel, template arguments) of the fused kernel instantiation a detector of `configs` (one
+    configuration, or a list with channelNetworks: SyllableDetector.multi's) would run for a batch of n_samples per channel --
+    from the host alone, no device needed; raises SyllableDetectorError (unsupported) for what is not on the fused engine."""
+    configs = [configs] if isinstance(configs, SyllableDetectorConfig) else list(configs)
+    abi = [cfg.to_abi() for cfg in configs]
+    ptrs = (_abi.Config_p * max(1, len(abi)))(*[C.pointer(c) for c, _ in abi])
+    nets = None if channelNetworks is None else np.ascontiguousarray(channelNetworks, dtype=np.int32).reshape(-1)
+    kernel, params = C.c_int32(), (C.c_int32 * 10)()
+    check(_abi.lib.syldet_fused_form_of_config(ptrs, len(abi), None if nets is None else nets.ctypes.data_as(_abi.c_int32_p), int(channels),
+                                               int(n_samples), 1 if s16 else 0, 1 if spectrogram else 0, int(engine), C.byref(kernel), params))
+    del abi
+    return int(kernel.value), tuple(int(v) for v in params)
