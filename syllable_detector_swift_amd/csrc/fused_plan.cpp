@@ -18,6 +18,7 @@
 #include <cstring>
 
 #include "fused_plan.hpp"
+#include "hopk_schedule.hpp"
 
 namespace sd {
 
@@ -266,6 +267,12 @@ bool make_fused_plan(const syldet_config_t &c, const syldet_geometry_t &g, Fused
                     d.s_cs8_rc = rc8;
                 }
             }
+            // hop 132 on the plain ring, one quad of units on eight waves: the ring whose schedule the kernel holds at compile time
+            // (HOP; hopk_schedule.hpp) -- eleven slots close the slot pattern with the period of four tiles.  They take no more
+            // of the wave's share than the RC slots above (the rows of tap products move up behind them).
+            d.s_hopk_rc = 0;
+            if (hop == hopk::kHop && W == hopk::kWindow && HQ == 1 && d.s_padp == 0 && s_waves == kFusedSBlock / 64 && RC >= hopk::kRing && fits(hopk::kRing))
+                d.s_hopk_rc = hopk::kRing;
             const int K2 = W / 64, c0 = W / 2;
             // A operands, lane l: row l & 15 of its tile, k = 8 (l >> 4) + j -> folded position m = 32 ks + k.
             // s rows (real part): w[c0 + m] cos(2 pi k m / N), half of it at m = 0 (s[0] = 2 x[c0]);

@@ -40,6 +40,7 @@
 // gfx950 only.  wave = 64.
 
 #include "fused_common.hpp"
+#include "hopk_schedule.hpp"
 
 namespace sd {
 
@@ -88,6 +89,19 @@ __device__ __forceinline__ void split2(float a, float b, unsigned &hi, unsigned 
     lo = cvt_pk(rem_lo(a, hi), rem_hi(b, hi));
 }
 
+// (HOP) chunks QF .. QL of the ring's period, as straight-line code: chunk q goes to its slot, slot 0's chunks to the mirror as
+// well -- every LDS destination and every byte offset from `pv` (the period's first chunk, this lane's quad) is a constant
+template <int QF, int QL>
+__device__ __forceinline__ void hopk_issue(__amdgpu_buffer_rsrc_t in_rs, unsigned char *wbase, unsigned pv)
+{
+#pragma unroll
+    for (int q = QF; q <= QL; q++) {
+        const unsigned voff = pv + (unsigned)q * 1024u;
+        __builtin_amdgcn_raw_ptr_buffer_load_lds(in_rs, (lds_void *)(wbase + hopk::slot_of(q) * 1024), 16, voff, 0, 0, 2 /* nt */);
+        if (hopk::mirrored(q)) __builtin_amdgcn_raw_ptr_buffer_load_lds(in_rs, (lds_void *)(wbase + hopk::kRing * 1024), 16, voff, 0, 0, 2);
+    }
+}
+
 // K2: k-steps of 32 folded positions (W = 64 K2).  GEN: the network class as run-time facts (any transfer functions, with or
 // without l2normalize, up to four outputs, log / dB columns); without it the reference's example class (l2normalize, TanSig, one
 // linear output).  HQ: quads of hidden units (H <= 4 HQ).  One quad: 8 waves a workgroup, two per SIMD, 256 registers each.
@@ -126,7 +140,26 @@ __device__ __forceinline__ void split2(float a, float b, unsigned &hi, unsigned 
 // and the lanes widen after the LDS read: a ds_read_b64 where the fp32 form reads a ds_read_b128 quad, a word where it reads a
 // word.  From there every instruction is the fp32 form's, so the bits are.  Instantiated for the twice-folded form on the plain
 // ring with one quad of units on eight waves (the reference's framing at ordinary hops), GEN and MN either way.
-template <int K2, bool GEN, int HQ, int NW, int PADP = 0, bool F2 = false, int NT = 1, bool SPECT = false, bool MN = false, bool S16 = false>
+// HOP: 0, or the hop as a compile-time constant: 132, the windowOverlap the reference's sample.txt ships, for the twice-folded
+// form on the plain fp32 ring with one quad of units on eight waves (GEN and MN either way; the launcher picks it inside
+// launch_one -- the form syldet_last_fused_form reports is the run-time one's).  A tile moves on by 16 x 132 = 2112 samples = 8.25
+// chunks, so four tiles are exactly 33 chunks, and on a ring of ELEVEN slots (33 = 3 x 11; fused_plan.cpp, s_hopk_rc) the whole
+// schedule repeats every four tiles (hopk_schedule.hpp holds the table; tests/cpp/hopk_schedule_test.cpp walks it on the host):
+//     phase | the tile reads chunks | and issues, once its reads have returned | into slots      | mirror copy of
+//       0   |    0 ..  8           |    9 .. 16                               | 9 10 0 1 .. 5   | 11
+//       1   |    8 .. 16           |   17 .. 25                               | 6 .. 10 0 .. 3  | 22
+//       2   |   16 .. 25           |   26 .. 33                               | 4 .. 10 0       | 33
+//       3   |   24 .. 33           |   34 .. 41 (1 .. 8 of the next period)   | 1 .. 8          | --
+// The loop keeps the tile's phase and one byte offset per lane that moves on once a period; a phase's chunks are straight-line
+// LDS-DMA instructions with constant LDS destinations and constant byte offsets (hopk_issue): no chunk counter, no slot wrap,
+// no `need` / `allowed` arithmetic, no inner loop.  The loop body itself stays ONE copy with a four-way branch on the phase around
+// the DMA block -- unrolled four times (a generic lambda a phase) the run-time instantiations no longer compiled to the parent's
+// instructions, and the code would be four times the size for the half dozen scalar instructions the branch costs.  The carried
+// rows' writes and the row's statistics are stored without lane-masked branches (clamped lanes rewrite quad 0 with its own
+// value; all four lane groups hold the same statistics to the bit).  The arithmetic is the run-time form's, instruction for
+// instruction on the same values: outputs and flags are bit-identical (tests/test_hopk_gpu.py).  SYLDET_FUSED_HOPK=0 keeps
+// the run-time hop.
+template <int K2, bool GEN, int HQ, int NW, int PADP = 0, bool F2 = false, int NT = 1, bool SPECT = false, bool MN = false, bool S16 = false, int HOP = 0>
 __global__ void __launch_bounds__(64 * NW, 1)
 fused_s_kernel(const FusedDesc d, const float *__restrict__ samples, int64_t stride, int64_t s_eff, int64_t E,
                float *__restrict__ outputs, uint8_t *__restrict__ flags, const FusedNet *__restrict__ nets, const int *__restrict__ net_of,
@@ -134,6 +167,8 @@ fused_s_kernel(const FusedDesc d, const float *__restrict__ samples, int64_t str
 {
     static_assert(!(MN && SPECT), "the spectrogram instantiation runs no network");
     static_assert(!S16 || (K2 == 4 && F2 && PADP == 0 && NT == 1 && HQ == 1 && NW == 8 && !SPECT), "16-bit PCM: the twice-folded form on the plain ring");
+    static_assert(HOP == 0 || (HOP == hopk::kHop && K2 == 4 && F2 && PADP == 0 && NT == 1 && HQ == 1 && NW == 8 && !SPECT && !S16 && kFusedSTileFrames == hopk::kTileFrames),
+                  "a compile-time hop: 132, the twice-folded form on the plain fp32 ring, one quad of units on eight waves");
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const int tid = threadIdx.x;
     const int lane = tid & 63;
@@ -141,7 +176,7 @@ fused_s_kernel(const FusedDesc d, const float *__restrict__ samples, int64_t str
     const int n = lane & 15, g = lane >> 4;
     constexpr int kWaves = NW;
     const int c = blockIdx.y;
-    const int T = d.T, H = d.H, hop = d.hop;
+    const int T = d.T, H = d.H, hop = HOP ? HOP : d.hop;
     constexpr int W = 64 * K2;
     const int n_out = GEN ? d.n_out : 1;
     // this wave's segment of the channel
@@ -159,7 +194,7 @@ fused_s_kernel(const FusedDesc d, const float *__restrict__ samples, int64_t str
 
     // ---- wave-private LDS: sample ring (RC chunks of 256 floats + one mirror chunk), tap products, a zero quad
     unsigned char *wbase = smem + (size_t)wave * d.s_lds_wave;
-    const int RC = PADP == 1 ? d.s_cs8_rc : d.s_ring_chunks, R = RC * (S16 ? 512 : 256);     // (R: samples the ring holds)
+    const int RC = HOP ? hopk::kRing : (PADP == 1 ? d.s_cs8_rc : d.s_ring_chunks), R = RC * (S16 ? 512 : 256);     // (R: samples the ring holds)
     constexpr bool CS8 = PADP == 1;                   // whole chunks staggered over the banks (hop 128: see the header)
     static_assert(!CS8 || (F2 && HQ == 1 && NT == 1), "staggered chunks: the twice-folded form at hop 128");
     constexpr int kSub = PADP > 1 ? 256 / PADP : 1;   // padded pieces of a chunk of 256 floats
@@ -277,6 +312,12 @@ fused_s_kernel(const FusedDesc d, const float *__restrict__ samples, int64_t str
             slot = slot + 1 == RC ? 0 : slot + 1;
         }
     };
+    // HOP: the same stream as straight-line code (hopk_issue above, hopk_schedule.hpp).  pv: this lane's byte offset of the
+    // PERIOD's first chunk, moved on by 33 chunks once a period; ph: the tile's phase in the period of four tiles -- all the
+    // loop keeps of the schedule: no chunk counter, no slot, no `need` / `allowed`.
+    unsigned pv = 0;
+    int ph = 0;
+    if constexpr (HOP != 0) pv = org + (unsigned)lane * 16u;
     const int span = (kTile - 1) * hop + W;                              // samples under one tile
     constexpr int kChunkLog = S16 ? 9 : 8;                               // samples a chunk: 2^kChunkLog
     auto need = [&](int t) { return (kTile * hop * t + span - 1) >> kChunkLog; };
@@ -357,7 +398,8 @@ fused_s_kernel(const FusedDesc d, const float *__restrict__ samples, int64_t str
 #undef SD_NET
 
     // ---- prologue: tile 0's samples
-    issue_upto(need(0) < allowed(0) ? need(0) : allowed(0));
+    if constexpr (HOP != 0) hopk_issue<0, hopk::last_chunk(0)>(in_rs, wbase, pv);
+    else issue_upto(need(0) < allowed(0) ? need(0) : allowed(0));
     int se_ref = 0;                                   // products are stored relative to the segment's first frame that has a level
 
 #ifdef SYLDET_S_STAMPS                // (diagnostic build: shader clocks a wave spends waiting for its samples' DMA / for the LDS, and in all)
@@ -447,7 +489,19 @@ fused_s_kernel(const FusedDesc d, const float *__restrict__ samples, int64_t str
             // the raw samples of this tile are dead as soon as they are in registers: all of the next tile's chunks, a whole tile
             // of arithmetic ahead of their use
             SD_STAMP(st_lg, asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"));
-            if (t + 1 < tiles) issue_upto(need(t + 1));
+            if constexpr (HOP != 0) {
+                // what the next tile reads beyond this one: one straight-line case a phase
+                static_assert(hopk::kPeriod == 4, "one case a phase");
+                if (t + 1 < tiles) {
+                    if (ph == 0) hopk_issue<hopk::issue_first(0), hopk::issue_last(0)>(in_rs, wbase, pv);
+                    else if (ph == 1) hopk_issue<hopk::issue_first(1), hopk::issue_last(1)>(in_rs, wbase, pv);
+                    else if (ph == 2) hopk_issue<hopk::issue_first(2), hopk::issue_last(2)>(in_rs, wbase, pv);
+                    else {
+                        hopk_issue<hopk::issue_first(3), hopk::issue_last(3)>(in_rs, wbase, pv);
+                        pv += (unsigned)(hopk::kPeriodChunks * 1024);
+                    }
+                }
+            } else if (t + 1 < tiles) issue_upto(need(t + 1));
         }
         // ---- the frame's own scale from its loudest sample (this lane looks at a quarter of the frame)
         float amax;
@@ -784,7 +838,10 @@ fused_s_kernel(const FusedDesc d, const float *__restrict__ samples, int64_t str
             }
             if (GEN && norm == 0) st1 = st0;           // no normaliser: the frame's sum of squares once more, for the window's level (the loudness guard)
             const float fw = far ? INFINITY : ((fst == 1 || (GEN && scaling != 0)) ? 0.0f : pow2f(2 * dsc));
-            if (g == 0) *reinterpret_cast<floatx4 *>(prow + 4 * HQ * TP) = floatx4{st0, fw, st1, 0.0f};
+            // (HOP: no lane-masked branch -- the four lane groups of a frame hold the same statistics to the bit, every one of them
+            // all-reduced by swaps that add or compare in the same operand order in both halves: all four write them)
+            if constexpr (HOP != 0) *reinterpret_cast<floatx4 *>(prow + 4 * HQ * TP) = floatx4{st0, fw, st1, 0.0f};
+            else if (g == 0) *reinterpret_cast<floatx4 *>(prow + 4 * HQ * TP) = floatx4{st0, fw, st1, 0.0f};
         }
 
         // ---- the tile's 16 evaluations: evaluation n ends on frame n of the tile; its taps are rows n .. n + T - 1.  Lane
@@ -993,7 +1050,12 @@ fused_s_kernel(const FusedDesc d, const float *__restrict__ samples, int64_t str
         // ---- the carried rows' writes (their reads went out with the evaluation's)
         {
             floatx4 *dst = reinterpret_cast<floatx4 *>(rows);
-            if (HQ == 1) {
+            if constexpr (HOP != 0) {
+                // (the clamped lanes hold quad 0 of the source -- what lane 0 writes to quad 0: the same value to the same place)
+                dst[lane < nq ? lane : 0] = cy0;
+                dst[lane + 64 < nq ? lane + 64 : 0] = cy1;
+                if (nq > 128) dst[lane + 128 < nq ? lane + 128 : 0] = cy2;
+            } else if (HQ == 1) {
                 if (lane < nq) dst[lane] = cy0;
                 if (lane + 64 < nq) dst[lane + 64] = cy1;
                 if (nq > 128 && lane + 128 < nq) dst[lane + 128] = cy2;
@@ -1004,6 +1066,7 @@ fused_s_kernel(const FusedDesc d, const float *__restrict__ samples, int64_t str
         }
         fo += (unsigned)(kTile * hop);
         fo = fo >= (unsigned)R ? fo - (unsigned)R : fo;
+        if constexpr (HOP != 0) ph = (ph + 1) & (hopk::kPeriod - 1);
         if (CS8) {                                    // eight chunks a tile: the slots move on, the pads (q & 7) stay
             sb1 += 8u * kChunkB; sb1 = sb1 >= (unsigned)(RC * kChunkB) ? sb1 - (unsigned)(RC * kChunkB) : sb1;
             sb2 += 8u * kChunkB; sb2 = sb2 >= (unsigned)(RC * kChunkB) ? sb2 - (unsigned)(RC * kChunkB) : sb2;
@@ -1030,6 +1093,16 @@ hipError_t launch_one(const FusedDesc &d, const float *samples, int64_t stride, 
         if (mn) return launch_one<K2, GEN, HQ, NW, PADP, F2, NT, false, true, S16>(d, samples, stride, C, s_eff, E, outputs, flags, stream, mn);
     if (fused_note_form(2, K2, GEN, HQ, NW, PADP, F2, NT, SPECT, MN, S16)) return hipSuccess;
     auto kern = fused_s_kernel<K2, GEN, HQ, NW, PADP, F2, NT, SPECT, MN, S16>;
+    // hop 132 on the plain fp32 ring of the twice-folded form, one quad of units on eight waves: the instantiation whose ring
+    // schedule is fixed at compile time (HOP; hopk_schedule.hpp) -- the same form to syldet_last_fused_form, the same bits.
+    // SYLDET_FUSED_HOPK=0 keeps the run-time hop (A/B runs, and the test that holds the two against each other).
+    if constexpr (K2 == 4 && HQ == 1 && NW == 8 && PADP == 0 && F2 && NT == 1 && !SPECT && !S16) {
+        if (d.hop == hopk::kHop && d.s_hopk_rc != 0) {
+            if (d.s_hopk_rc != hopk::kRing || (d.s_hopk_rc + 1) * 1024 + ((d.T - 1 + kTile) * d.s_pstride + 8 * HQ + 128) * 4 > d.s_lds_wave)
+                return hipErrorInvalidValue;                             // (the plan's ring is not the compiled one)
+            kern = fused_s_kernel<K2, GEN, HQ, NW, PADP, F2, NT, SPECT, MN, S16, hopk::kHop>;
+        }
+    }
     constexpr int kWaves = NW;
 #ifdef SYLDET_S_ONEWAVE
     const int lds = kWaves == 4 ? 100 * 1024 : d.s_lds_wave * kWaves;       // (one workgroup a CU)

@@ -117,6 +117,7 @@ struct syldet {
         bool fused_nofold = false;    // SYLDET_FUSED_NOFOLD: not the symmetric-fold kernel (the register-resident-basis / 8-wave kernels)
         bool fused_pad128 = false;    // SYLDET_FUSED_PAD128: hop 128 on the fold kernel's padded pieces, not the staggered chunks (round 6)
         bool fused_nofold2 = false;   // SYLDET_FUSED_NOFOLD2: the fold kernel's once-folded form where the twice-folded one takes the shape
+        bool fused_nohopk = false;    // SYLDET_FUSED_HOPK=0: the fold kernel's run-time hop where the compile-time schedule (hop 132) takes the shape
         bool fused_stamps = false;    // SYLDET_FUSED_STAMPS: the stamped diagnostic instantiation
         int fused_ko = 0;             // SYLDET_FUSED_KO=<mask>: knock-out instantiation
         long long host_chunk = 0;     // SYLDET_HOST_CHUNK_BYTES=<n>: bytes of input per stage of the host-pointer pipeline (tests force seams with it)
@@ -139,6 +140,7 @@ struct syldet {
             no_mlpx = std::getenv("SYLDET_NO_MLPX") != nullptr;
             fused_nofold = std::getenv("SYLDET_FUSED_NOFOLD") != nullptr;
             fused_nofold2 = std::getenv("SYLDET_FUSED_NOFOLD2") != nullptr;
+            fused_nohopk = std::getenv("SYLDET_FUSED_HOPK") != nullptr && std::atoi(std::getenv("SYLDET_FUSED_HOPK")) == 0;
             fused_pad128 = std::getenv("SYLDET_FUSED_PAD128") != nullptr;
             fused_stamps = std::getenv("SYLDET_FUSED_STAMPS") != nullptr;
             fused_ko = std::getenv("SYLDET_FUSED_KO") ? std::atoi(std::getenv("SYLDET_FUSED_KO")) : 0;
@@ -785,6 +787,7 @@ bool dft_route_for(const syldet *h, int64_t J, int C, bool for_network, const in
     d.stamps = nullptr;
     d.ko = 0;
     d.no_fold2 = h->sw.fused_nofold2 ? 1 : 0;
+    if (h->sw.fused_nohopk) d.s_hopk_rc = 0;
     d.no_cs8 = h->sw.fused_pad128 ? 1 : 0;
     // the fold kernel's spectrogram instantiation where the plan allows it (rows under 2 GiB: its 32-bit byte offsets)
     fold = !h->sw.fused_nofold && fused_s_spectrogram_applicable(d) && ((J - 1) * (int64_t)d.hop + d.gap + d.W) * 4 < 0x7fffffffll;
@@ -846,6 +849,7 @@ bool fused_route_for(const syldet *h, int64_t J, int64_t E, int C, FusedDesc &d)
         d.force_classic = h->sw.fused_classic ? 1 : 0;
         d.no_fold = h->sw.fused_nofold ? 1 : 0;
         d.no_fold2 = h->sw.fused_nofold2 ? 1 : 0;
+        if (h->sw.fused_nohopk) d.s_hopk_rc = 0;
         d.no_cs8 = h->sw.fused_pad128 ? 1 : 0;
         // Which fused kernel THIS batch gets is known only now (the fold kernel addresses a row with 32-bit byte offsets; a
         // diagnostic switch may rule it out).  The batch takes the fused route only if that kernel can run it (plans whose hop
@@ -1071,6 +1075,7 @@ bool takes_fold(const syldet_config_t &c, const syldet_geometry_t &g, const syld
     d.force_classic = sw.fused_classic ? 1 : 0;
     d.no_fold = sw.fused_nofold ? 1 : 0;
     d.no_fold2 = sw.fused_nofold2 ? 1 : 0;
+    if (sw.fused_nohopk) d.s_hopk_rc = 0;
     d.no_cs8 = sw.fused_pad128 ? 1 : 0;
     d.ko = sw.fused_ko;
     d.stamps = nullptr;
