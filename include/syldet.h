@@ -379,6 +379,79 @@ int syldet_meters_enable(syldet_t *h, int enable);
 int syldet_input_level(syldet_t *h, int32_t channel, double *rms, int32_t *has_value);
 int syldet_output_level(syldet_t *h, int32_t channel, double *level, int32_t *has_value);
 
+/* ---- the TTL trigger track: detections as the pulses the rig emits ----
+ * The reference's product is a TTL pulse on an audio output, recorded beside the microphone:
+ *   Processor.swift:128-148          a callback buffer is `seen` if any evaluation it made available has lastDetected
+ *   ProcessorAudio :217-221          prepareOutputFor then calls createHighOutput(channel, forDuration: 0.001)
+ *   AudioInterface.swift:442-445     outputHighFor[channel] = Int(duration * rate) -- set, not added to (:444)
+ *   AudioInterface.swift:13-40       renderOutput writes 1.0 for that many samples from the next render buffer on
+ *   ProcessorArduino :266-291        the same monostable counted in callbacks: high until 20 callbacks without a syllable
+ * With D = first_index, hop, callback buffers of L = buffer_length samples (a power of two, 8 <= L <= 4096; the reference's 32),
+ * pulse width N = width_samples >= 1 and output latency Lat = latency_samples >= 0 (the reference's README: "up to 5 ms"; 0 is the
+ * model's default):
+ *   b(e)     = (D + e hop - 1) / L     the buffer whose callback makes evaluation e available (integer division); the same
+ *                                      statement as syldet_levels_eval_range(..., buffers_per_reading = 1, ...)
+ *   seen(b)  = some e < n_evals with b(e) = b has flags[c][e] != 0
+ *   t_b      = (b + 1) L + Lat         a seen buffer arms the output as its callback returns: the next render buffer's first sample
+ *   track[c][s] = 1 iff some seen buffer b has t_b <= s < t_b + N      (0 <= s < n_samples; else 0)
+ * A later arm inside a pulse extends it to its own t_b + N (:444 sets), which is the union above.
+ * An onset is a seen buffer b with no seen buffer in [b - N / L, b) (integer division; pulses that abut are one pulse); its
+ * sample is t_b; onsets at t_b >= n_samples are not reported.  The onsets are the rising edges of the track.
+ * The Arduino form is N = 20 L.  syldet_trigger_width(seconds, rate) is Int(seconds * rate) (:444); -1 for a result below 1 or
+ * not finite.
+ * d_flags [C][n_evals] as syldet_run_device* wrote them: the reference's lastDetected is output 0 against its threshold
+ * (SyllableDetector.swift:27-31), which is SYLDET_RULE_FIRST; flags of another rule give that rule's pulses.  D and hop come from
+ * the handle as in syldet_trace*; plain, multi-network and mixed banks alike.
+ *   d_track  [C][track_stride], the first n_samples of each row: fp32 1.0f / 0.0f (the reference's floats), int16 32767 / 0 (the
+ *            trace's convention)
+ *   d_frames [n_samples][C] int16 (syldet_trigger_interleaved_device_s16), or [n_samples][2 C] (syldet_trigger_mux_device_s16):
+ *            frame f = (audio[0][f], ttl[0][f], audio[1][f], ttl[1][f], ...), the audio copied bit for bit from the planar int16
+ *            rows syldet_run_device_s16 takes -- the stereo file a DAQ would have recorded, for every channel at once
+ *   d_indices [C][capacity] int64, d_counts [C] int64: the onsets' samples in order, and how many there are (the convention of
+ *            syldet_detections_device: the first min(count, capacity) are written)
+ * Every call scans the flags into a table last_seen[c][b] (the greatest seen buffer <= b, or -1; B' = ceil((n_samples + L - 1) / L)
+ * entries a channel, scratch the handle keeps and grows) and then expands or compacts from it: syldet_timings lists
+ * "trigger_scan_kernel" and one of "trigger_kernel", "trigger_interleaved_s16_kernel", "trigger_onsets_kernel".
+ * Statuses, before any device is touched: SYLDET_ERR_INVALID_ARGUMENT for a NULL handle or pointer, negative counts, a stride
+ * below n_samples, an L that is not a power of two in [8, 4096], N < 1 or N > 2^24, Lat < 0 or Lat > 2^24.  n_samples == 0
+ * writes no sample (the onsets' counts are 0); n_evals == 0 writes zeros.  The device forms follow the handle's rule of one
+ * stream at a time.                                                                                                          */
+int64_t syldet_trigger_width(double seconds, double rate);
+int syldet_trigger_device(syldet_t *h, const uint8_t *d_flags, int64_t n_evals, int32_t buffer_length, int64_t width_samples,
+                          int64_t latency_samples, float *d_track, int64_t n_samples, int64_t track_stride, void *hip_stream);
+int syldet_trigger_device_s16(syldet_t *h, const uint8_t *d_flags, int64_t n_evals, int32_t buffer_length, int64_t width_samples,
+                              int64_t latency_samples, int16_t *d_track, int64_t n_samples, int64_t track_stride, void *hip_stream);
+int syldet_trigger_interleaved_device_s16(syldet_t *h, const uint8_t *d_flags, int64_t n_evals, int32_t buffer_length,
+                                          int64_t width_samples, int64_t latency_samples, int16_t *d_frames, int64_t n_samples,
+                                          void *hip_stream);
+int syldet_trigger_mux_device_s16(syldet_t *h, const uint8_t *d_flags, int64_t n_evals, int32_t buffer_length, int64_t width_samples,
+                                  int64_t latency_samples, const int16_t *d_samples, int64_t channel_stride, int16_t *d_frames,
+                                  int64_t n_samples, void *hip_stream);
+int syldet_trigger_onsets_device(syldet_t *h, const uint8_t *d_flags, int64_t n_evals, int32_t buffer_length, int64_t width_samples,
+                                 int64_t latency_samples, int64_t n_samples, int64_t *d_indices, int64_t capacity, int64_t *d_counts,
+                                 void *hip_stream);
+/* the track and its onsets from ONE scan of the flags (what a rehearsal of a recording wants: syldet_timings lists
+ * "trigger_scan_kernel", "trigger_kernel", "trigger_onsets_kernel"); the results are those of the two calls above                  */
+int syldet_trigger_rehearse_device(syldet_t *h, const uint8_t *d_flags, int64_t n_evals, int32_t buffer_length, int64_t width_samples,
+                                   int64_t latency_samples, float *d_track, int64_t n_samples, int64_t track_stride,
+                                   int64_t *d_indices, int64_t capacity, int64_t *d_counts, void *hip_stream);
+int syldet_trigger_rehearse_device_s16(syldet_t *h, const uint8_t *d_flags, int64_t n_evals, int32_t buffer_length, int64_t width_samples,
+                                       int64_t latency_samples, int16_t *d_track, int64_t n_samples, int64_t track_stride,
+                                       int64_t *d_indices, int64_t capacity, int64_t *d_counts, void *hip_stream);
+/* host pointers, blocking (as syldet_trace is to syldet_trace_device) */
+int syldet_trigger(syldet_t *h, const uint8_t *flags, int64_t n_evals, int32_t buffer_length, int64_t width_samples,
+                   int64_t latency_samples, float *track, int64_t n_samples, int64_t track_stride);
+int syldet_trigger_s16(syldet_t *h, const uint8_t *flags, int64_t n_evals, int32_t buffer_length, int64_t width_samples,
+                       int64_t latency_samples, int16_t *track, int64_t n_samples, int64_t track_stride);
+int syldet_trigger_onsets(syldet_t *h, const uint8_t *flags, int64_t n_evals, int32_t buffer_length, int64_t width_samples,
+                          int64_t latency_samples, int64_t n_samples, int64_t *indices, int64_t capacity, int64_t *counts);
+/* Streaming, host only: the two reference functions.  syldet_trigger_arm is createHighOutput (the channel's counter = width_samples,
+ * >= 0); syldet_trigger_render is renderOutput for one channel: out[i] = i < high ? 1 : 0 for n_frames frames, and the counter
+ * goes down by min(high, n_frames).  The counter is an atomic: an audio-output thread may render beside the consumer that arms
+ * (an arm that lands inside a render is kept whole).  A handle that never arms renders zeros and does what it always did.    */
+int syldet_trigger_arm(syldet_t *h, int32_t channel, int64_t width_samples);
+int syldet_trigger_render(syldet_t *h, int32_t channel, float *out, int32_t n_frames);
+
 /* ---- measurement (replaces the reference's Time stopwatch, SyllableDetector/Time.swift:36-100,
  * which wraps processNewValue in ViewControllerSimulator.swift:309-319) ----
  * With profiling enabled every kernel of a batch call is bracketed by HIP events on the stream it
@@ -480,6 +553,10 @@ int syldet_seen_syllable(syldet_t *h, int32_t channel);
 int syldet_deinterleave_device(const float *d_interleaved, int64_t n_frames, int32_t total_channels,
                                int32_t first_channel, int32_t n_channels, float *d_out, int64_t out_stride,
                                void *hip_stream);
+/* the same for 16-bit PCM frames: channels 0 .. n_channels - 1 of total_channels -> int16 rows [n_channels][out_stride] (the
+ * rows syldet_run_device_s16 and syldet_trigger_mux_device_s16 take)                                                        */
+int syldet_deinterleave_device_s16(const int16_t *d_interleaved, int64_t n_frames, int32_t total_channels, int32_t n_channels,
+                                   int16_t *d_out, int64_t out_stride, void *hip_stream);
 /* The batch call on interleaved audio (total_channels == syldet_channels(h)): de-interleave
  * on the device, then exactly syldet_run_device / syldet_run.                             */
 int syldet_run_interleaved_device(syldet_t *h, const float *d_interleaved, int64_t n_frames, int32_t total_channels,

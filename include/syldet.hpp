@@ -202,6 +202,74 @@ public:
     {
         check(syldet_trace_interleaved_device_s16(h_, d_outputs, nEvals, output, d_frames, n, hipStream));
     }
+    // The TTL trigger track (Processor.swift:128-148, AudioInterface.swift:13-40, :442-445): the pulses the rig would have emitted for
+    // flags [channels][nEvals] -- high for `width` samples from the render buffer behind every callback buffer of bufferLength
+    // samples that made a flagged evaluation available, `latency` samples later.  track [channels][n] (host buffers, blocking)
+    static int64_t triggerWidth(double seconds, double rate) { return syldet_trigger_width(seconds, rate); }
+    std::vector<float> triggerTrack(const uint8_t *flags, int64_t nEvals, int64_t n, int64_t width, int32_t bufferLength = 32, int64_t latency = 0)
+    {
+        std::vector<float> t((size_t)channels() * (size_t)n);
+        check(syldet_trigger(h_, flags, nEvals, bufferLength, width, latency, t.data(), n, n));
+        return t;
+    }
+    std::vector<int16_t> triggerTrackPCM16(const uint8_t *flags, int64_t nEvals, int64_t n, int64_t width, int32_t bufferLength = 32,
+                                           int64_t latency = 0)
+    {
+        std::vector<int16_t> t((size_t)channels() * (size_t)n);
+        check(syldet_trigger_s16(h_, flags, nEvals, bufferLength, width, latency, t.data(), n, n));
+        return t;
+    }
+    // the rising edges of one channel's track, as sample numbers
+    std::vector<int64_t> triggerOnsets(const uint8_t *flags, int64_t nEvals, int64_t n, int64_t width, int32_t channel, int32_t bufferLength = 32,
+                                       int64_t latency = 0)
+    {
+        const int64_t cap = std::min<int64_t>(nEvals, n / bufferLength + 1);
+        std::vector<int64_t> idx((size_t)channels() * (size_t)std::max<int64_t>(cap, 1)), counts((size_t)channels());
+        check(syldet_trigger_onsets(h_, flags, nEvals, bufferLength, width, latency, n, idx.data(), cap, counts.data()));
+        return std::vector<int64_t>(idx.begin() + (size_t)channel * (size_t)cap,
+                                    idx.begin() + (size_t)channel * (size_t)cap + (size_t)std::min(counts[(size_t)channel], cap));
+    }
+    // device buffers, asynchronous on `hipStream`: fp32 rows, 16-bit rows (32767 / 0), 16-bit frames [n][channels], 16-bit frames
+    // [n][2 channels] with the recording's int16 rows beside the triggers, and the onsets
+    void triggerDevice(const uint8_t *d_flags, int64_t nEvals, int32_t bufferLength, int64_t width, int64_t latency, float *d_track, int64_t n,
+                       int64_t stride, void *hipStream)
+    {
+        check(syldet_trigger_device(h_, d_flags, nEvals, bufferLength, width, latency, d_track, n, stride, hipStream));
+    }
+    void triggerDevicePCM16(const uint8_t *d_flags, int64_t nEvals, int32_t bufferLength, int64_t width, int64_t latency, int16_t *d_track,
+                            int64_t n, int64_t stride, void *hipStream)
+    {
+        check(syldet_trigger_device_s16(h_, d_flags, nEvals, bufferLength, width, latency, d_track, n, stride, hipStream));
+    }
+    void triggerInterleavedDevicePCM16(const uint8_t *d_flags, int64_t nEvals, int32_t bufferLength, int64_t width, int64_t latency,
+                                       int16_t *d_frames, int64_t n, void *hipStream)
+    {
+        check(syldet_trigger_interleaved_device_s16(h_, d_flags, nEvals, bufferLength, width, latency, d_frames, n, hipStream));
+    }
+    void triggerMuxDevicePCM16(const uint8_t *d_flags, int64_t nEvals, int32_t bufferLength, int64_t width, int64_t latency,
+                               const int16_t *d_samples, int64_t channelStride, int16_t *d_frames, int64_t n, void *hipStream)
+    {
+        check(syldet_trigger_mux_device_s16(h_, d_flags, nEvals, bufferLength, width, latency, d_samples, channelStride, d_frames, n, hipStream));
+    }
+    void triggerOnsetsDevice(const uint8_t *d_flags, int64_t nEvals, int32_t bufferLength, int64_t width, int64_t latency, int64_t n,
+                             int64_t *d_indices, int64_t capacity, int64_t *d_counts, void *hipStream)
+    {
+        check(syldet_trigger_onsets_device(h_, d_flags, nEvals, bufferLength, width, latency, n, d_indices, capacity, d_counts, hipStream));
+    }
+    // the planar track and the onsets from one scan of the flags
+    void triggerRehearseDevice(const uint8_t *d_flags, int64_t nEvals, int32_t bufferLength, int64_t width, int64_t latency, float *d_track,
+                               int64_t n, int64_t stride, int64_t *d_indices, int64_t capacity, int64_t *d_counts, void *hipStream)
+    {
+        check(syldet_trigger_rehearse_device(h_, d_flags, nEvals, bufferLength, width, latency, d_track, n, stride, d_indices, capacity, d_counts, hipStream));
+    }
+    void triggerRehearseDevicePCM16(const uint8_t *d_flags, int64_t nEvals, int32_t bufferLength, int64_t width, int64_t latency, int16_t *d_track,
+                                    int64_t n, int64_t stride, int64_t *d_indices, int64_t capacity, int64_t *d_counts, void *hipStream)
+    {
+        check(syldet_trigger_rehearse_device_s16(h_, d_flags, nEvals, bufferLength, width, latency, d_track, n, stride, d_indices, capacity, d_counts, hipStream));
+    }
+    // streaming: createHighOutput and renderOutput (AudioInterface.swift:442-445, :13-40) of one channel
+    void armTrigger(int32_t channel, int64_t width) { check(syldet_trigger_arm(h_, channel, width)); }
+    void renderTrigger(int32_t channel, float *out, int32_t nFrames) { check(syldet_trigger_render(h_, channel, out, nFrames)); }
     // The level meters of the rows (Processor.swift:111-113, :138, :158-184).  Whole recordings, host buffers, blocking: the RMS
     // readings [channels][M] of samples [channels][n] (M = levelsCount: one reading per buffersPerReading buffers of bufferLength
     // samples), and the output readings [channels][M] of outputs [channels][nEvals][outputs]

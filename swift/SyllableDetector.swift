@@ -55,6 +55,70 @@ final class SyllableDetectorBank {
         if st != 0 { fatalError(String(cString: syldet_strerror(st)) + ": " + String(cString: syldet_last_error())) }
         return (trace, outputs, flags)
     }
+
+    /// The rig's TTL output for a whole recording (Processor.swift:128-148, AudioInterface.swift:13-40, :442-445): the outputs, the
+    /// flags, the 16-bit trigger track [channels][n] (32767 for `width` samples behind every callback buffer that saw a syllable) and
+    /// every channel's rising edges.
+    func rehearse(samples: UnsafePointer<Float>, samplesPerChannel n: Int, width: Int, bufferLength: Int32 = 32, latency: Int = 0)
+        -> (track: [Int16], onsets: [[Int64]], outputs: [Float], flags: [UInt8]) {
+        let c = Int(syldet_channels(handle)), e = max(0, Int(syldet_count_evals(handle, Int64(n))))
+        var outputs = [Float](repeating: 0, count: max(1, c * e * Int(geometry.outputs)))
+        var flags = [UInt8](repeating: 0, count: max(1, c * e)), track = [Int16](repeating: 0, count: max(1, c * n))
+        let cap = max(1, min(e, n / Int(bufferLength) + 1))
+        var idx = [Int64](repeating: 0, count: c * cap), counts = [Int64](repeating: 0, count: c)
+        var st = syldet_run(handle, samples, Int64(n), Int64(n), &outputs, &flags)
+        if st == 0 { st = syldet_trigger_s16(handle, flags, Int64(e), bufferLength, Int64(width), Int64(latency), &track, Int64(n), Int64(n)) }
+        if st == 0 { st = syldet_trigger_onsets(handle, flags, Int64(e), bufferLength, Int64(width), Int64(latency), Int64(n), &idx, Int64(cap), &counts) }
+        if st != 0 { fatalError(String(cString: syldet_strerror(st)) + ": " + String(cString: syldet_last_error())) }
+        return (track, (0..<c).map { ch in Array(idx[(ch * cap)..<(ch * cap + min(cap, Int(counts[ch])))]) }, outputs, flags)
+    }
+
+    private func checkTrigger(_ st: Int32) {
+        if st != 0 { fatalError(String(cString: syldet_strerror(st)) + ": " + String(cString: syldet_last_error())) }
+    }
+
+    /// Int(seconds * rate), createHighOutput's width (AudioInterface.swift:444); -1 below one sample
+    static func triggerWidth(seconds: Double, rate: Double) -> Int { return Int(syldet_trigger_width(seconds, rate)) }
+
+    /// The trigger track [channels][n] of flags [channels][nEvals] (host buffers, blocking): 1.0 / 0.0, or 32767 / 0
+    func triggerTrack(flags: UnsafePointer<UInt8>, evaluations e: Int, samplesPerChannel n: Int, width: Int, bufferLength: Int32 = 32, latency: Int = 0) -> [Float] {
+        var t = [Float](repeating: 0, count: max(1, Int(syldet_channels(handle)) * n))
+        checkTrigger(syldet_trigger(handle, flags, Int64(e), bufferLength, Int64(width), Int64(latency), &t, Int64(n), Int64(n)))
+        return t
+    }
+    func triggerTrackPCM16(flags: UnsafePointer<UInt8>, evaluations e: Int, samplesPerChannel n: Int, width: Int, bufferLength: Int32 = 32, latency: Int = 0) -> [Int16] {
+        var t = [Int16](repeating: 0, count: max(1, Int(syldet_channels(handle)) * n))
+        checkTrigger(syldet_trigger_s16(handle, flags, Int64(e), bufferLength, Int64(width), Int64(latency), &t, Int64(n), Int64(n)))
+        return t
+    }
+    /// the rising edges of one channel's track, as sample numbers
+    func triggerOnsets(flags: UnsafePointer<UInt8>, evaluations e: Int, samplesPerChannel n: Int, width: Int, channel: Int, bufferLength: Int32 = 32, latency: Int = 0) -> [Int64] {
+        let c = Int(syldet_channels(handle)), cap = max(1, min(e, n / Int(bufferLength) + 1))
+        var idx = [Int64](repeating: 0, count: c * cap), counts = [Int64](repeating: 0, count: c)
+        checkTrigger(syldet_trigger_onsets(handle, flags, Int64(e), bufferLength, Int64(width), Int64(latency), Int64(n), &idx, Int64(cap), &counts))
+        return Array(idx[(channel * cap)..<(channel * cap + min(cap, Int(counts[channel])))])
+    }
+    /// device buffers, asynchronous on `hipStream`: fp32 rows, 16-bit rows, 16-bit frames [n][channels], 16-bit frames [n][2 channels]
+    /// with the recording's int16 rows beside the triggers, and the onsets
+    func triggerDevice(flags: UnsafePointer<UInt8>, evaluations e: Int64, bufferLength: Int32, width: Int64, latency: Int64, track: UnsafeMutablePointer<Float>, samplesPerChannel n: Int64, stride: Int64, hipStream: UnsafeMutableRawPointer?) {
+        checkTrigger(syldet_trigger_device(handle, flags, e, bufferLength, width, latency, track, n, stride, hipStream))
+    }
+    func triggerDevicePCM16(flags: UnsafePointer<UInt8>, evaluations e: Int64, bufferLength: Int32, width: Int64, latency: Int64, track: UnsafeMutablePointer<Int16>, samplesPerChannel n: Int64, stride: Int64, hipStream: UnsafeMutableRawPointer?) {
+        checkTrigger(syldet_trigger_device_s16(handle, flags, e, bufferLength, width, latency, track, n, stride, hipStream))
+    }
+    func triggerInterleavedDevicePCM16(flags: UnsafePointer<UInt8>, evaluations e: Int64, bufferLength: Int32, width: Int64, latency: Int64, frames: UnsafeMutablePointer<Int16>, samplesPerChannel n: Int64, hipStream: UnsafeMutableRawPointer?) {
+        checkTrigger(syldet_trigger_interleaved_device_s16(handle, flags, e, bufferLength, width, latency, frames, n, hipStream))
+    }
+    func triggerMuxDevicePCM16(flags: UnsafePointer<UInt8>, evaluations e: Int64, bufferLength: Int32, width: Int64, latency: Int64, samples: UnsafePointer<Int16>, channelStride: Int64, frames: UnsafeMutablePointer<Int16>, samplesPerChannel n: Int64, hipStream: UnsafeMutableRawPointer?) {
+        checkTrigger(syldet_trigger_mux_device_s16(handle, flags, e, bufferLength, width, latency, samples, channelStride, frames, n, hipStream))
+    }
+    func triggerOnsetsDevice(flags: UnsafePointer<UInt8>, evaluations e: Int64, bufferLength: Int32, width: Int64, latency: Int64, samplesPerChannel n: Int64, indices: UnsafeMutablePointer<Int64>?, capacity: Int64, counts: UnsafeMutablePointer<Int64>, hipStream: UnsafeMutableRawPointer?) {
+        checkTrigger(syldet_trigger_onsets_device(handle, flags, e, bufferLength, width, latency, n, indices, capacity, counts, hipStream))
+    }
+
+    /// createHighOutput (AudioInterface.swift:442-445) and renderOutput (:13-40) of one channel
+    func armTrigger(channel: Int32, width: Int) { checkTrigger(syldet_trigger_arm(handle, channel, Int64(width))) }
+    func renderTrigger(channel: Int32, into out: UnsafeMutablePointer<Float>, frames: Int32) { checkTrigger(syldet_trigger_render(handle, channel, out, frames)) }
 }
 
 /// One bank over several MI355X of this host, one process: the reference is one process that owns every channel

@@ -123,6 +123,19 @@ SIGNATURES = {
     "syldet_trace_interleaved_device_s16": (C.c_int, [Handle, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p]),
     "syldet_trace": (C.c_int, [Handle, c_float_p, C.c_int64, C.c_int32, c_float_p, C.c_int64, C.c_int64]),
     "syldet_trace_s16": (C.c_int, [Handle, c_float_p, C.c_int64, C.c_int32, c_int16_p, C.c_int64, C.c_int64]),
+    "syldet_trigger_width": (C.c_int64, [C.c_double, C.c_double]),
+    "syldet_trigger_device": (C.c_int, [Handle, C.c_void_p, C.c_int64, C.c_int32, C.c_int64, C.c_int64, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p]),
+    "syldet_trigger_device_s16": (C.c_int, [Handle, C.c_void_p, C.c_int64, C.c_int32, C.c_int64, C.c_int64, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p]),
+    "syldet_trigger_interleaved_device_s16": (C.c_int, [Handle, C.c_void_p, C.c_int64, C.c_int32, C.c_int64, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p]),
+    "syldet_trigger_mux_device_s16": (C.c_int, [Handle, C.c_void_p, C.c_int64, C.c_int32, C.c_int64, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p]),
+    "syldet_trigger_onsets_device": (C.c_int, [Handle, C.c_void_p, C.c_int64, C.c_int32, C.c_int64, C.c_int64, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
+    "syldet_trigger_rehearse_device": (C.c_int, [Handle, C.c_void_p, C.c_int64, C.c_int32, C.c_int64, C.c_int64, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
+    "syldet_trigger_rehearse_device_s16": (C.c_int, [Handle, C.c_void_p, C.c_int64, C.c_int32, C.c_int64, C.c_int64, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
+    "syldet_trigger": (C.c_int, [Handle, c_uint8_p, C.c_int64, C.c_int32, C.c_int64, C.c_int64, c_float_p, C.c_int64, C.c_int64]),
+    "syldet_trigger_s16": (C.c_int, [Handle, c_uint8_p, C.c_int64, C.c_int32, C.c_int64, C.c_int64, c_int16_p, C.c_int64, C.c_int64]),
+    "syldet_trigger_onsets": (C.c_int, [Handle, c_uint8_p, C.c_int64, C.c_int32, C.c_int64, C.c_int64, C.c_int64, c_int64_p, C.c_int64, c_int64_p]),
+    "syldet_trigger_arm": (C.c_int, [Handle, C.c_int32, C.c_int64]),
+    "syldet_trigger_render": (C.c_int, [Handle, C.c_int32, c_float_p, C.c_int32]),
     "syldet_levels_count": (C.c_int64, [C.c_int64, C.c_int32, C.c_int64]),
     "syldet_sum_squares": (C.c_float, [c_float_p, C.c_int64]),
     "syldet_levels_eval_range": (C.c_int, [Handle, C.c_int64, C.c_int64, C.c_int32, C.c_int64, C.c_int64, c_int64_p, c_int64_p]),
@@ -158,6 +171,7 @@ SIGNATURES = {
     "syldet_last_outputs": (C.c_int, [Handle, C.c_int32, c_float_p]),
     "syldet_last_detected": (C.c_int, [Handle, C.c_int32]),
     "syldet_seen_syllable": (C.c_int, [Handle, C.c_int32]),
+    "syldet_deinterleave_device_s16": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p]),
     "syldet_deinterleave_device": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p]),
     "syldet_run_interleaved_device": (C.c_int, [Handle, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
     "syldet_run_interleaved": (C.c_int, [Handle, c_float_p, C.c_int64, C.c_int32, c_float_p, c_uint8_p]),

@@ -38,7 +38,7 @@ constexpr int kExUsage = 64;   // EX_USAGE, main.swift:40
 void usage(FILE *to)
 {
     std::fprintf(to,
-                 "Usage: syllable-detector-cli -n <net> [-a <audio>]... [-d <seconds>] [--device <k>] [--chunk <frames>] [--format <shortest|swift4>] [--simulate <out.wav>] [--simulate-output <k>] [--levels <out.tsv>] [--levels-buffer <L>] [--levels-period <seconds>] [--probe]\n"
+                 "Usage: syllable-detector-cli -n <net> [-a <audio>]... [-d <seconds>] [--device <k>] [--chunk <frames>] [--format <shortest|swift4>] [--simulate <out.wav>] [--simulate-output <k>] [--levels <out.tsv>] [--levels-buffer <L>] [--levels-period <seconds>] [--ttl <out.wav>] [--ttl-mux] [--ttl-width <seconds>] [--ttl-steps <n>] [--ttl-buffer <L>] [--ttl-latency <seconds>] [--ttl-onsets <out.tsv>] [--probe]\n"
                  "  -n, --net <net>:\n      Path to trained network file.  Given k > 1 times: each file must have exactly k tracks, and track t runs network t (one mixed bank; the networks must share the sampling rate, window length, window overlap, time range and number of outputs).\n"
                  "  -a, --audio <audio>:\n      Path to the audio file to process.\n"
                  "  -d, --debounce <seconds>:\n      Number of seconds to debounce triggers.\n"
@@ -50,6 +50,13 @@ void usage(FILE *to)
                  "      --levels <out.tsv>:\n      Also write the level meters of every track of the (one) audio file, one line per reading and track, tab separated: the track, the time of the reading's end in seconds, the input RMS (the loudest buffer of the reading), the output level (the greatest first output evaluated in the reading; empty for a reading without an evaluation).\n"
                  "      --levels-buffer <L>:\n      Samples per buffer of the input meter: a power of two from 8 to 4096 (default 32).\n"
                  "      --levels-period <seconds>:\n      Time between two readings (default 0.1); a reading is a whole number of buffers, at least one.\n"
+                 "      --ttl <out.wav>:\n      Also write the TTL trigger track of every track of the (one) audio file as a 16-bit WAV at the network's sampling rate: 32767 for the pulse's width from the output buffer behind every input buffer in which a detection became available, 0 elsewhere.\n"
+                 "      --ttl-mux:\n      Write --ttl's file with twice the tracks, every audio track followed by its trigger track (16-bit PCM input at the network's rate only).\n"
+                 "      --ttl-width <seconds>:\n      Width of a pulse (default 0.001).\n"
+                 "      --ttl-steps <n>:\n      Width of a pulse as n buffers (the Arduino output holds for 20), instead of --ttl-width.\n"
+                 "      --ttl-buffer <L>:\n      Samples per input and output buffer: a power of two from 8 to 4096 (default 32).\n"
+                 "      --ttl-latency <seconds>:\n      Delay of the output behind the input (default 0).\n"
+                 "      --ttl-onsets <out.tsv>:\n      Also write the rising edges of the trigger tracks, one line each, tab separated: the track, the sample, the time in seconds.\n"
                  "      --probe:\n      Only print what the audio files contain; does not touch the GPU.\n"
                  "The command line will write a comma-separated list of detection events (when the network has at least one output above threshold) to standard out. For example, it might output:\n"
                  "\n\t0,1593298,36.1292063492063,0.918557\n\n"
@@ -105,13 +112,26 @@ struct LevelsOpt {
     double period = 0.1;
 };
 
+// --ttl / --ttl-onsets: the pulses the rig would have emitted (Processor.swift:128-148, AudioInterface.swift:13-40, :442-445)
+struct TtlOpt {
+    std::string path, onsets;                              // empty: none
+    bool mux = false;
+    double width = 0.001, latency = 0.0;                   // ProcessorAudio :217-221
+    long steps = 0;                                        // > 0: the width as buffers (ProcessorArduino :266-291 holds for 20)
+    int buffer = 32;
+    bool any() const { return !path.empty() || !onsets.empty(); }
+    int64_t width_samples(double rate) const { return steps > 0 ? (int64_t)steps * buffer : syldet_trigger_width(width, rate); }
+    int64_t latency_samples(double rate) const { const double x = latency * rate; return x < 9e18 ? (int64_t)x : INT64_MAX; }
+};
+
 // cfgs: one network for every track, or (k > 1) network t for track t of a file of exactly k tracks, through one mixed bank
 // (syldet_create_mixed): the networks share the evaluation clock, so the events are found and printed as for one
 // simulate: a path for the Simulator's output track (ViewControllerSimulator.swift:251-344) of every track, made on the device from
 // the outputs the run left there (syldet_trace_interleaved_device_s16) and written as a 16-bit WAV of as many frames as the detector
 // was fed, at the network's rate; empty: none
 int process_file(const std::string &path, const std::vector<syldet_config_t *> &cfgs, int device, double debounce_s, bool have_debounce, int64_t chunk,
-                 const std::string &simulate = std::string(), int simulate_output = 0, const LevelsOpt &levels = LevelsOpt())
+                 const std::string &simulate = std::string(), int simulate_output = 0, const LevelsOpt &levels = LevelsOpt(),
+                 const TtlOpt &ttl = TtlOpt())
 {
     const syldet_config_t *cfg = cfgs[0];
     wav::Info info;
@@ -131,6 +151,9 @@ int process_file(const std::string &path, const std::vector<syldet_config_t *> &
         std::fprintf(stderr, "No audio tracks found in %s.\n", path.c_str());
         return 1;
     }
+    // (like a track that cannot be written, this does not cost the detection lines)
+    const bool mux_refused = ttl.mux && !pcm16;
+    if (mux_refused) std::fprintf(stderr, "Unable to write %s: --ttl-mux takes 16-bit PCM at the network's sampling rate (%s).\n", ttl.path.c_str(), path.c_str());
     if (cfgs.size() > 1 && (size_t)C != cfgs.size()) {
         std::fprintf(stderr, "Unable to process %s: it has %d track(s), but %zu networks were given (one per track).\n", path.c_str(), C, cfgs.size());
         return 1;
@@ -155,6 +178,9 @@ int process_file(const std::string &path, const std::vector<syldet_config_t *> &
     std::vector<double> lv_in;                              // [C][M] mean squares
     std::vector<float> lv_out;                              // [C][M]
     std::vector<uint8_t> lv_empty;                          // [M] the reading holds no evaluation
+    std::vector<int16_t> ttl_track;                         // [S][C] or (--ttl-mux) [S][2 C]
+    std::vector<int64_t> ttl_idx, ttl_cnt;                  // [C][ttl_cap], [C]
+    int64_t ttl_cap = 1;
     int64_t lv_P = 1, lv_M = 0;
     int64_t E = 0, fed = 0;
     do {
@@ -209,8 +235,40 @@ int process_file(const std::string &path, const std::vector<syldet_config_t *> &
             return st == 0;
         };
         if (!meters(false)) { rc = 2; break; }
+        // the trigger tracks and their rising edges from the flags the run left on the device (no evaluation: no flag, zeros)
+        DevBuf d_ttl, d_ttl_idx, d_ttl_cnt, d_rows;
+        auto triggers = [&]() -> bool {
+            if (!ttl.any() || S <= 0) return true;
+            const int64_t N = ttl.width_samples(cfg->sampling_rate), lat = ttl.latency_samples(cfg->sampling_rate), nE = E > 0 ? E : 0;
+            if (!d_flags.p && !d_flags.alloc(1)) return false;
+            if (!ttl.path.empty() && !mux_refused) {
+                ttl_track.resize((size_t)S * C * (ttl.mux ? 2 : 1));
+                if (!d_ttl.alloc(ttl_track.size() * sizeof(int16_t))) return false;
+                if (ttl.mux) {
+                    // the recording as planar int16 rows, the layout syldet_run_device_s16 takes: from the frames already on the device
+                    if (!d_rows.alloc((size_t)C * S * sizeof(int16_t))) return false;
+                    st = syldet_deinterleave_device_s16((const int16_t *)d_inter.p, S, C, C, (int16_t *)d_rows.p, S, stream);
+                    if (!st) st = syldet_trigger_mux_device_s16(h, (const uint8_t *)d_flags.p, nE, ttl.buffer, N, lat, (const int16_t *)d_rows.p, S, (int16_t *)d_ttl.p, S, stream);
+                } else {
+                    st = syldet_trigger_interleaved_device_s16(h, (const uint8_t *)d_flags.p, nE, ttl.buffer, N, lat, (int16_t *)d_ttl.p, S, stream);
+                }
+                if (!st && hipMemcpyAsync(ttl_track.data(), d_ttl.p, ttl_track.size() * sizeof(int16_t), hipMemcpyDeviceToHost, stream) != hipSuccess) return false;
+            }
+            if (!st && !ttl.onsets.empty()) {
+                ttl_cap = std::max<int64_t>(1, std::min<int64_t>(nE, S / ttl.buffer + 1));
+                ttl_idx.assign((size_t)C * (size_t)ttl_cap, 0);
+                ttl_cnt.assign((size_t)C, 0);
+                if (!d_ttl_idx.alloc(ttl_idx.size() * sizeof(int64_t)) || !d_ttl_cnt.alloc(ttl_cnt.size() * sizeof(int64_t))) return false;
+                st = syldet_trigger_onsets_device(h, (const uint8_t *)d_flags.p, nE, ttl.buffer, N, lat, S, (int64_t *)d_ttl_idx.p, ttl_cap, (int64_t *)d_ttl_cnt.p, stream);
+                if (!st && (hipMemcpyAsync(ttl_idx.data(), d_ttl_idx.p, ttl_idx.size() * sizeof(int64_t), hipMemcpyDeviceToHost, stream) != hipSuccess ||
+                            hipMemcpyAsync(ttl_cnt.data(), d_ttl_cnt.p, ttl_cnt.size() * sizeof(int64_t), hipMemcpyDeviceToHost, stream) != hipSuccess)) return false;
+            }
+            if (st) std::fprintf(stderr, "Unable to make the trigger track of %s: %s: %s\n", path.c_str(), syldet_strerror(st), syldet_last_error());
+            return st == 0;
+        };
         if (E <= 0) {                                       // shorter than one evaluation: no events
-            if (!levels.path.empty() && hipStreamSynchronize(stream) != hipSuccess) rc = 2;
+            if (!triggers()) { rc = 2; break; }
+            if ((!levels.path.empty() || ttl.any()) && hipStreamSynchronize(stream) != hipSuccess) rc = 2;
             break;
         }
         if (!d_out.alloc((size_t)C * E * n_out * sizeof(float)) || !d_flags.alloc((size_t)C * E)) { rc = 2; break; }
@@ -234,6 +292,7 @@ int process_file(const std::string &path, const std::vector<syldet_config_t *> &
             if (hipMemcpyAsync(track.data(), d_track.p, track.size() * sizeof(int16_t), hipMemcpyDeviceToHost, stream) != hipSuccess) { rc = 2; break; }
         }
         if (!meters(true)) { rc = 2; break; }
+        if (!triggers()) { rc = 2; break; }
         out.resize((size_t)C * E * n_out);
         flags.resize((size_t)C * E);
         if (hipMemcpyAsync(out.data(), d_out.p, out.size() * sizeof(float), hipMemcpyDeviceToHost, stream) != hipSuccess ||
@@ -276,9 +335,36 @@ int process_file(const std::string &path, const std::vector<syldet_config_t *> &
         std::fprintf(stderr, "Unable to write %s.\n", levels.path.c_str());
         return 3;
     };
+    // ... and the trigger tracks and their rising edges: track, sample, seconds
+    auto write_ttl = [&]() -> int {
+        int bad = mux_refused ? 3 : 0;
+        if (!ttl.path.empty() && !mux_refused) {
+            std::string werr;
+            if (!wav::write_s16(ttl.path, cfg->sampling_rate, ttl.mux ? 2 * C : C, fed, ttl_track.data(), werr)) {
+                std::fprintf(stderr, "Unable to write %s: %s\n", ttl.path.c_str(), werr.c_str());
+                bad = 3;
+            }
+        }
+        if (!ttl.onsets.empty()) {
+            FILE *f = std::fopen(ttl.onsets.c_str(), "w");
+            bool ok = f != nullptr;
+            for (int c = 0; ok && c < C && !ttl_cnt.empty(); c++)
+                for (int64_t i = 0; ok && i < std::min(ttl_cnt[(size_t)c], ttl_cap); i++) {
+                    const int64_t smp = ttl_idx[(size_t)c * (size_t)ttl_cap + (size_t)i];
+                    const std::string line = std::to_string(c) + "\t" + std::to_string(smp) + "\t" + number((double)smp / cfg->sampling_rate) + "\n";
+                    ok = std::fputs(line.c_str(), f) >= 0;
+                }
+            if (f && std::fclose(f) != 0) ok = false;
+            if (!ok) {
+                std::fprintf(stderr, "Unable to write %s.\n", ttl.onsets.c_str());
+                bad = 3;
+            }
+        }
+        return bad;
+    };
     auto write_files = [&]() -> int {
-        const int a = write_track(), b = write_levels();
-        return a ? a : b;
+        const int a = write_track(), b = write_levels(), c = write_ttl();
+        return a ? a : (b ? b : c);
     };
     if (rc) return rc;
     if (E <= 0) return write_files();
@@ -325,6 +411,8 @@ int main(int argc, char **argv)
     bool have_debounce = false, probe = false;
     LevelsOpt levels;
     bool have_levels = false, have_levels_option = false;
+    TtlOpt ttl;
+    bool have_ttl = false, have_ttl_onsets = false, have_ttl_option = false, have_ttl_width = false, have_ttl_steps = false;
     int device = 0;
     int64_t chunk = 8192;
     auto value = [&](int &i, const char *name) -> const char * {
@@ -387,6 +475,50 @@ int main(int argc, char **argv)
             }
             have_levels_option = true;
         }
+        else if (a == "--ttl") {
+            ttl.path = value(i, "--ttl");
+            have_ttl = true;
+        } else if (a == "--ttl-onsets") {
+            ttl.onsets = value(i, "--ttl-onsets");
+            have_ttl_onsets = true;
+        } else if (a == "--ttl-mux") {
+            ttl.mux = true;
+        } else if (a == "--ttl-width" || a == "--ttl-latency") {
+            const bool w = a == "--ttl-width";
+            const char *v = value(i, a.c_str());
+            char *end = nullptr;
+            const double x = std::strtod(v, &end);
+            if (end == v || *end != 0 || !(w ? x > 0.0 : x >= 0.0) || x > 1e15) {
+                std::fprintf(stderr, w ? "--ttl-width takes a positive number of seconds.\n" : "--ttl-latency takes a number of seconds, 0 or more.\n");
+                usage(stdout);
+                return kExUsage;
+            }
+            (w ? ttl.width : ttl.latency) = x;
+            have_ttl_option = true;
+            if (w) have_ttl_width = true;
+        } else if (a == "--ttl-steps") {
+            const char *v = value(i, "--ttl-steps");
+            char *end = nullptr;
+            const long k = std::strtol(v, &end, 10);
+            if (end == v || *end != 0 || k < 1 || k > (1L << 24)) {
+                std::fprintf(stderr, "--ttl-steps takes a number of buffers, 1 or more.\n");
+                usage(stdout);
+                return kExUsage;
+            }
+            ttl.steps = k;
+            have_ttl_option = have_ttl_steps = true;
+        } else if (a == "--ttl-buffer") {
+            const char *v = value(i, "--ttl-buffer");
+            char *end = nullptr;
+            const long k = std::strtol(v, &end, 10);
+            if (end == v || *end != 0 || k < 8 || k > 4096 || (k & (k - 1)) != 0) {
+                std::fprintf(stderr, "--ttl-buffer takes a power of two from 8 to 4096.\n");
+                usage(stdout);
+                return kExUsage;
+            }
+            ttl.buffer = (int)k;
+            have_ttl_option = true;
+        }
         else if (a == "--format") {
             const std::string f = value(i, "--format");
             if (f != "shortest" && f != "swift4") { usage(stdout); return kExUsage; }
@@ -440,6 +572,26 @@ int main(int argc, char **argv)
         usage(stdout);
         return kExUsage;
     }
+    if ((have_ttl && (audio.size() != 1 || ttl.path.empty())) || (have_ttl_onsets && (audio.size() != 1 || ttl.onsets.empty()))) {   // one rig, one recording
+        std::fprintf(stderr, "--ttl and --ttl-onsets write the triggers of exactly one audio file (-a).\n");
+        usage(stdout);
+        return kExUsage;
+    }
+    if (ttl.mux && !have_ttl) {
+        std::fprintf(stderr, "--ttl-mux needs --ttl <out.wav>.\n");
+        usage(stdout);
+        return kExUsage;
+    }
+    if (have_ttl_option && !have_ttl && !have_ttl_onsets) {
+        std::fprintf(stderr, "--ttl-width, --ttl-steps, --ttl-buffer and --ttl-latency need --ttl <out.wav> or --ttl-onsets <out.tsv>.\n");
+        usage(stdout);
+        return kExUsage;
+    }
+    if (have_ttl_width && have_ttl_steps) {
+        std::fprintf(stderr, "--ttl-width and --ttl-steps both set the pulse's width: give one.\n");
+        usage(stdout);
+        return kExUsage;
+    }
     std::vector<syldet_config_t *> cfgs;
     for (const std::string &n : net) {
         syldet_config_t *cfg = nullptr;
@@ -459,11 +611,22 @@ int main(int argc, char **argv)
                 usage(stdout);
                 return kExUsage;
             }
+    if (ttl.any()) {                                        // (before the GPU is opened)
+        const double rate = cfgs[0]->sampling_rate;
+        const int64_t N = ttl.width_samples(rate), lat = ttl.latency_samples(rate);
+        if (N < 1 || N > (1ll << 24) || lat > (1ll << 24)) {
+            if (N < 1) std::fprintf(stderr, "--ttl-width: shorter than one sample at %s Hz.\n", swift_number(rate).c_str());
+            else std::fprintf(stderr, "The pulse's width and --ttl-latency may be 16777216 samples at most.\n");
+            for (syldet_config_t *k : cfgs) syldet_config_free(k);
+            usage(stdout);
+            return kExUsage;
+        }
+    }
     int rc = 0;
     for (const std::string &p : audio) {
         if (audio.size() > 1) std::printf("%s\n", p.c_str());   // main.swift:122-124
         std::fflush(stdout);
-        const int r = process_file(p, cfgs, device, debounce, have_debounce, chunk, simulate, simulate_output, levels);
+        const int r = process_file(p, cfgs, device, debounce, have_debounce, chunk, simulate, simulate_output, levels, ttl);
         if (r == 2) rc = 2;                                 // device trouble is fatal for the exit code; an unreadable file is skipped
         else if (r == 3 && rc == 0) rc = 1;                 // ... and so is a track that could not be written
     }

@@ -314,6 +314,25 @@ hipError_t launch_trace_s16(const float *outputs, int64_t n_evals, int n_out, in
 hipError_t launch_trace_interleaved_s16(const float *outputs, int64_t n_evals, int n_out, int k, const float *thr, int C,
                                         int16_t *frames, int64_t n_frames, int64_t first_index, int64_t hop, hipStream_t stream);
 
+// ---- the TTL trigger track (kernels_trigger.hip; Processor.swift:128-148, AudioInterface.swift:13-40, :442-445) ----
+// B' of include/syldet.h: entries of one channel's last_seen row for a recording of n_samples (-1: too long for 32-bit buffers)
+int64_t trigger_buffers(int64_t n_samples, int L);
+// flags [C][n_evals] -> last_seen [C][B'] int32: the greatest seen buffer <= b, or -1 (trigger_scan_kernel)
+hipError_t launch_trigger_scan(const uint8_t *flags, int64_t n_evals, int C, int L, int64_t n_samples, int64_t first_index, int64_t hop,
+                               int *last_seen, hipStream_t stream);
+// last_seen -> track [C][stride] (the first n_samples of each row): fp32 1.0f / 0.0f, int16 32767 / 0 (trigger_kernel)
+hipError_t launch_trigger(const int *last_seen, int C, int L, int64_t N, int64_t Lat, float *track, int64_t n_samples, int64_t stride,
+                          hipStream_t stream);
+hipError_t launch_trigger_s16(const int *last_seen, int C, int L, int64_t N, int64_t Lat, int16_t *track, int64_t n_samples, int64_t stride,
+                              hipStream_t stream);
+// the int16 form frame-major: samples == nullptr, frames [n_frames][C] (one channel: the planar kernel); else frames [n_frames][2 C],
+// channel c's audio (samples [C][sample_stride] int16, copied bit for bit) at lane 2 c and its trigger at 2 c + 1
+hipError_t launch_trigger_interleaved_s16(const int *last_seen, int C, int L, int64_t N, int64_t Lat, const int16_t *samples,
+                                          int64_t sample_stride, int16_t *frames, int64_t n_frames, hipStream_t stream);
+// the rising edges' sample numbers in order, indices [C][capacity] and counts [C] as launch_detections writes them
+hipError_t launch_trigger_onsets(const int *last_seen, int C, int L, int64_t N, int64_t Lat, int64_t n_samples, int64_t *indices,
+                                 int64_t capacity, int64_t *counts, hipStream_t stream);
+
 // ---- the level meters (kernels_levels.hip; Processor.swift:111-113, :138, :158-184) ----
 // what a workgroup of levels_in_kernel leaves of a reading that reaches into a neighbour: the greatest mean square of its buffers
 // that is not NaN (-1: none), and the reading's first value where the workgroup holds its first buffer

@@ -28,6 +28,8 @@ struct ChannelStream {
     std::atomic<uint64_t> tail{0};           // producer: total samples ever appended
     std::atomic<uint64_t> head{0};           // consumer: first sample of the next evaluation
     std::atomic<int64_t> frames_done{0};     // STFT frames the reference would have extracted so far
+    std::atomic<int64_t> trigger_high{0};    // outputHighFor (AudioInterface.swift:442-445): samples the TTL output stays high; set by
+                                             // syldet_trigger_arm, counted down by syldet_trigger_render (any thread each)
     // consumer side only
     std::deque<std::vector<float>> ready;    // evaluated outputs not yet handed out
     std::vector<float> last;                 // lastOutputs

@@ -160,6 +160,18 @@ int syldet_convert_rate_device(const float *d_in, int64_t n_in, int64_t in_strid
     return SYLDET_OK;
 }
 
+int syldet_deinterleave_device_s16(const int16_t *d_interleaved, int64_t n_frames, int32_t total_channels, int32_t n_channels,
+                                   int16_t *d_out, int64_t out_stride, void *hip_stream)
+{
+    if (n_frames < 0 || total_channels <= 0 || n_channels <= 0 || n_channels > total_channels)
+        return fail(SYLDET_ERR_INVALID_ARGUMENT, "channel selection outside the interleaved layout");
+    if (n_frames == 0) return SYLDET_OK;
+    if (!d_interleaved || !d_out) return fail(SYLDET_ERR_INVALID_ARGUMENT, "NULL buffer");
+    if (out_stride < n_frames) return fail(SYLDET_ERR_INVALID_ARGUMENT, "out_stride must be >= n_frames");
+    SYLDET_HIP(launch_deinterleave_s16(d_interleaved, n_frames, total_channels, n_channels, d_out, out_stride, (hipStream_t)hip_stream));
+    return SYLDET_OK;
+}
+
 int syldet_deinterleave_device(const float *d_interleaved, int64_t n_frames, int32_t total_channels, int32_t first_channel,
                                int32_t n_channels, float *d_out, int64_t out_stride, void *hip_stream)
 {

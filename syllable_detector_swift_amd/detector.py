@@ -411,6 +411,198 @@ class SyllableDetector:
         tr = self.trace(outputs, int(samples.shape[1]), output=output, dtype=dtype, stream=stream)
         return tr, outputs, flags
 
+    # ---- the TTL trigger track (Processor.swift:128-148, AudioInterface.swift:13-40, :442-445) ---------
+    def triggerWidth(self, seconds: float = 0.001) -> int:
+        """Int(seconds * samplingRate), createHighOutput's width (AudioInterface.swift:444; syldet_trigger_width)."""
+        n = int(_abi.lib.syldet_trigger_width(float(seconds), float(self.config.samplingRate)))
+        if n < 1:
+            raise ValueError("a pulse of %r s is shorter than one sample at this rate" % (seconds,))
+        return n
+
+    def _trigger_args(self, flags, n_samples, bufferLength, width, latency):
+        torch = _torch()
+        n = int(n_samples)
+        if n < 0:
+            raise ValueError("n_samples must not be negative")
+        if not (flags.is_cuda and flags.dtype == torch.uint8 and flags.dim() == 2 and flags.shape[0] == self.channels
+                and flags.is_contiguous() and flags.device.index == self.device):
+            raise ValueError("flags must be a contiguous uint8 CUDA tensor [channels, n_evals] on the detector's device")
+        L = int(bufferLength)
+        N = self.triggerWidth() if width is None else int(width)
+        lat = int(latency)
+        if L < 8 or L > 4096 or L & (L - 1):
+            raise ValueError("bufferLength must be a power of two in [8, 4096]")
+        if not 1 <= N <= 1 << 24:
+            raise ValueError("width must be in [1, 2**24] samples")
+        if not 0 <= lat <= 1 << 24:
+            raise ValueError("latency must be in [0, 2**24] samples")
+        E = int(flags.shape[1])
+        # (an empty tensor has no address: a bank too short for one evaluation still gets its zeros)
+        src = flags if E > 0 else torch.zeros(1, dtype=torch.uint8, device=flags.device)
+        return n, L, N, lat, E, src
+
+    def triggerTrack(self, flags, n_samples: int, bufferLength: int = 32, width: Optional[int] = None, latency: int = 0,
+                     dtype=np.float32, interleaved: bool = False, out=None, stream=None):
+        """The TTL track the rig would have emitted (syldet_trigger_device*): flags [C, n_evals] (a uint8 CUDA tensor, as run()
+        returns it) -> track [C, n_samples], high for `width` samples (default triggerWidth(): 1 ms) from the render buffer behind
+        every callback buffer of bufferLength samples that made a flagged evaluation available, `latency` samples later; a
+        later detection inside a pulse extends it.  dtype np.float32: 1.0 / 0.0, the reference's floats; np.int16: 32767 / 0.
+        interleaved=True (int16 only): frames [n_samples, C], what a 16-bit WAV of C tracks stores.  `out` as in trace().
+        Asynchronous on `stream`."""
+        torch = _torch()
+        dt = self._trace_dtype(dtype, interleaved)
+        tdt = torch.float32 if dt == np.dtype(np.float32) else torch.int16
+        n, L, N, lat, E, src = self._trigger_args(flags, n_samples, bufferLength, width, latency)
+        if out is None:
+            out = torch.empty((n, self.channels) if interleaved else (self.channels, n), dtype=tdt, device=flags.device)
+        elif interleaved:
+            if not (out.is_cuda and out.dtype == tdt and tuple(out.shape) == (n, self.channels) and out.is_contiguous()
+                    and out.device == flags.device):
+                raise ValueError("out must be a contiguous int16 CUDA tensor [n_samples, channels] on the flags' device")
+        else:
+            if not (out.is_cuda and out.dtype == tdt and out.dim() == 2 and out.shape[0] == self.channels and out.shape[1] >= n
+                    and (out.shape[1] == 0 or out.stride(1) == 1) and (self.channels == 1 or out.stride(0) >= n)
+                    and out.device == flags.device):
+                raise ValueError("out must be a CUDA tensor [channels, >= n_samples] of the track's dtype with contiguous rows")
+        if n == 0:
+            return out
+        if interleaved:
+            check(_abi.lib.syldet_trigger_interleaved_device_s16(self._h, src.data_ptr(), E, L, N, lat, out.data_ptr(), n,
+                                                                 self._stream_ptr(stream)))
+        else:
+            fn = _abi.lib.syldet_trigger_device if dt == np.dtype(np.float32) else _abi.lib.syldet_trigger_device_s16
+            stride = int(out.stride(0)) if self.channels > 1 else max(int(out.shape[1]), n)
+            check(fn(self._h, src.data_ptr(), E, L, N, lat, out.data_ptr(), n, stride, self._stream_ptr(stream)))
+        return out
+
+    def triggerTrackPCM16(self, flags, n_samples: int, bufferLength: int = 32, width: Optional[int] = None, latency: int = 0,
+                          out=None, stream=None):
+        """triggerTrack() as 16-bit PCM rows [C, n_samples]: 32767 / 0 (syldet_trigger_device_s16)."""
+        return self.triggerTrack(flags, n_samples, bufferLength, width, latency, dtype=np.int16, out=out, stream=stream)
+
+    def triggerTrackInterleavedPCM16(self, flags, n_samples: int, bufferLength: int = 32, width: Optional[int] = None,
+                                     latency: int = 0, out=None, stream=None):
+        """triggerTrack() as 16-bit PCM frames [n_samples, C] (syldet_trigger_interleaved_device_s16)."""
+        return self.triggerTrack(flags, n_samples, bufferLength, width, latency, dtype=np.int16, interleaved=True, out=out, stream=stream)
+
+    def triggerMuxPCM16(self, flags, samples, bufferLength: int = 32, width: Optional[int] = None, latency: int = 0, out=None,
+                        stream=None):
+        """The file a DAQ would have recorded, for every channel at once (syldet_trigger_mux_device_s16): samples [C, S] (the int16
+        CUDA tensor runPCM16() takes) and flags -> frames [S, 2 C] int16, frame f = (audio[0][f], ttl[0][f], audio[1][f], ...);
+        the audio is copied bit for bit."""
+        torch = _torch()
+        if not (samples.is_cuda and samples.dtype == torch.int16 and samples.dim() == 2 and samples.shape[0] == self.channels
+                and (samples.shape[1] == 0 or samples.stride(1) == 1) and samples.device.index == self.device):
+            raise ValueError("samples must be a 2-D int16 CUDA tensor [channels, n_samples] with contiguous rows on the detector's device")
+        n, L, N, lat, E, src = self._trigger_args(flags, int(samples.shape[1]), bufferLength, width, latency)
+        if out is None:
+            out = torch.empty((n, 2 * self.channels), dtype=torch.int16, device=flags.device)
+        elif not (out.is_cuda and out.dtype == torch.int16 and tuple(out.shape) == (n, 2 * self.channels) and out.is_contiguous()
+                  and out.device == flags.device):
+            raise ValueError("out must be a contiguous int16 CUDA tensor [n_samples, 2 * channels] on the flags' device")
+        if n == 0:
+            return out
+        stride = int(samples.stride(0)) if self.channels > 1 else n
+        check(_abi.lib.syldet_trigger_mux_device_s16(self._h, src.data_ptr(), E, L, N, lat, samples.data_ptr(), stride, out.data_ptr(), n,
+                                                     self._stream_ptr(stream)))
+        return out
+
+    def triggerOnsets(self, flags, n_samples: int, bufferLength: int = 32, width: Optional[int] = None, latency: int = 0,
+                      capacity: Optional[int] = None, stream=None):
+        """The rising edges of triggerTrack() (syldet_trigger_onsets_device): flags [C, n_evals] -> (indices [C, capacity] i64,
+        counts [C] i64), the sample numbers in order and how many there are (the first min(count, capacity) are written, like
+        detections()).  capacity defaults to the most there can be."""
+        torch = _torch()
+        n, L, N, lat, E, src = self._trigger_args(flags, n_samples, bufferLength, width, latency)
+        cap = min(E, n // L + 1) if capacity is None else int(capacity)
+        if cap < 0:
+            raise ValueError("capacity must not be negative")
+        idx = torch.empty((self.channels, max(cap, 1)), dtype=torch.int64, device=flags.device)
+        cnt = torch.empty((self.channels,), dtype=torch.int64, device=flags.device)
+        check(_abi.lib.syldet_trigger_onsets_device(self._h, src.data_ptr(), E, L, N, lat, n, idx.data_ptr(), cap, cnt.data_ptr(),
+                                                    self._stream_ptr(stream)))
+        return idx, cnt
+
+    def _trigger_host_args(self, flags, n_samples, bufferLength, width):
+        n = int(n_samples)
+        if n < 0:
+            raise ValueError("n_samples must not be negative")
+        a = np.ascontiguousarray(flags, dtype=np.uint8)
+        if a.ndim != 2 or a.shape[0] != self.channels:
+            raise ValueError("flags must be [channels, n_evals]")
+        E = a.shape[1]
+        src = a if E > 0 else np.zeros(1, np.uint8)
+        return n, int(bufferLength), self.triggerWidth() if width is None else int(width), E, src
+
+    def triggerTrackHost(self, flags: np.ndarray, n_samples: int, bufferLength: int = 32, width: Optional[int] = None, latency: int = 0,
+                         dtype=np.float32) -> np.ndarray:
+        """triggerTrack() on host arrays, blocking (syldet_trigger / syldet_trigger_s16): flags [C, n_evals] -> [C, n_samples]."""
+        dt = self._trace_dtype(dtype, False)
+        n, L, N, E, src = self._trigger_host_args(flags, n_samples, bufferLength, width)
+        tr = np.zeros((self.channels, n), dt)
+        if dt == np.dtype(np.float32):
+            check(_abi.lib.syldet_trigger(self._h, src.ctypes.data_as(_abi.c_uint8_p), E, L, N, int(latency), tr.ctypes.data_as(_abi.c_float_p), n, n))
+        else:
+            check(_abi.lib.syldet_trigger_s16(self._h, src.ctypes.data_as(_abi.c_uint8_p), E, L, N, int(latency), tr.ctypes.data_as(_abi.c_int16_p), n, n))
+        return tr
+
+    def triggerOnsetsHost(self, flags: np.ndarray, n_samples: int, bufferLength: int = 32, width: Optional[int] = None, latency: int = 0,
+                          capacity: Optional[int] = None):
+        """triggerOnsets() on host arrays, blocking (syldet_trigger_onsets): -> a list of one int64 array of samples per channel."""
+        n, L, N, E, src = self._trigger_host_args(flags, n_samples, bufferLength, width)
+        cap = min(E, n // max(L, 1) + 1) if capacity is None else int(capacity)
+        idx = np.zeros((self.channels, max(cap, 1)), np.int64)
+        cnt = np.zeros((self.channels,), np.int64)
+        check(_abi.lib.syldet_trigger_onsets(self._h, src.ctypes.data_as(_abi.c_uint8_p), E, L, N, int(latency), n,
+                                             idx.ctypes.data_as(_abi.c_int64_p), cap, cnt.ctypes.data_as(_abi.c_int64_p)))
+        return [idx[c, :min(int(cnt[c]), cap)].copy() for c in range(self.channels)]
+
+    def triggerRehearse(self, flags, n_samples: int, bufferLength: int = 32, width: Optional[int] = None, latency: int = 0,
+                        dtype=np.int16, capacity: Optional[int] = None, out=None, stream=None):
+        """triggerTrack() (planar rows) and triggerOnsets() from one scan of the flags (syldet_trigger_rehearse_device*):
+        -> (track [C, n_samples], indices [C, capacity], counts [C])."""
+        torch = _torch()
+        dt = self._trace_dtype(dtype, False)
+        tdt = torch.float32 if dt == np.dtype(np.float32) else torch.int16
+        n, L, N, lat, E, src = self._trigger_args(flags, n_samples, bufferLength, width, latency)
+        if out is None:
+            out = torch.empty((self.channels, n), dtype=tdt, device=flags.device)
+        elif not (out.is_cuda and out.dtype == tdt and out.dim() == 2 and out.shape[0] == self.channels and out.shape[1] >= n
+                  and (out.shape[1] == 0 or out.stride(1) == 1) and (self.channels == 1 or out.stride(0) >= n)
+                  and out.device == flags.device):
+            raise ValueError("out must be a CUDA tensor [channels, >= n_samples] of the track's dtype with contiguous rows")
+        cap = min(E, n // L + 1) if capacity is None else int(capacity)
+        if cap < 0:
+            raise ValueError("capacity must not be negative")
+        idx = torch.empty((self.channels, max(cap, 1)), dtype=torch.int64, device=flags.device)
+        cnt = torch.empty((self.channels,), dtype=torch.int64, device=flags.device)
+        dst = out if out.numel() > 0 else torch.zeros(1, dtype=tdt, device=flags.device)
+        fn = _abi.lib.syldet_trigger_rehearse_device if dt == np.dtype(np.float32) else _abi.lib.syldet_trigger_rehearse_device_s16
+        stride = int(out.stride(0)) if self.channels > 1 else max(int(out.shape[1]), n)
+        check(fn(self._h, src.data_ptr(), E, L, N, lat, dst.data_ptr(), n, stride, idx.data_ptr(), cap, cnt.data_ptr(), self._stream_ptr(stream)))
+        return out, idx, cnt
+
+    def rehearse(self, samples, bufferLength: int = 32, width: Optional[int] = None, latency: int = 0, dtype=np.int16, stream=None):
+        """A recording through the rig in one call: run() followed by triggerRehearse() on device tensors (one scan of the flags
+        for the track and the onsets); samples [C, S] float32 -> (track [C, S], onsets [C, capacity], counts [C], outputs
+        [C, E, n_out], flags [C, E])."""
+        self._trace_dtype(dtype, False)
+        outputs, flags = self.run(samples, stream=stream)
+        track, onsets, counts = self.triggerRehearse(flags, int(samples.shape[1]), bufferLength, width, latency, dtype=dtype, stream=stream)
+        return track, onsets, counts, outputs, flags
+
+    def armTrigger(self, channel: int = 0, width: Optional[int] = None) -> None:
+        """createHighOutput (AudioInterface.swift:442-445): the channel's TTL output stays high for `width` samples (default
+        triggerWidth()) of the buffers rendered from now on -- set, not added to (syldet_trigger_arm)."""
+        check(_abi.lib.syldet_trigger_arm(self._h, int(channel), self.triggerWidth() if width is None else int(width)))
+
+    def renderTrigger(self, channel: int = 0, n_frames: int = 32) -> np.ndarray:
+        """renderOutput (AudioInterface.swift:13-40) for one channel: the next n_frames samples of its TTL output, float32 1.0 while
+        the armed pulse lasts and 0.0 behind it (syldet_trigger_render)."""
+        out = np.zeros(int(n_frames), np.float32)
+        check(_abi.lib.syldet_trigger_render(self._h, int(channel), out.ctypes.data_as(_abi.c_float_p), int(n_frames)))
+        return out
+
     # ---- the level meters (Processor.swift:111-113, :138, :158-184) ---------------------------
     def defaultBuffersPerReading(self, bufferLength: int = 32) -> int:
         """Buffers between two firings of the reference's 0.1 s timer (ViewControllerProcessor.swift:57):
