@@ -695,6 +695,54 @@ int64_t syldet_convert_rate_count(int64_t n_in, double rate_in, double rate_out)
 int syldet_convert_rate_device(const float *d_in, int64_t n_in, int64_t in_stride, int32_t n_channels, double rate_in,
                                double rate_out, float *d_out, int64_t out_stride, int64_t *n_out, void *hip_stream);
 
+/* The same step band-limited: what AVFoundation's delivery at the network's rate (audioSettings, SyllableDetector.swift:19-23,
+ * TrackDetector.swift:35) is and the linear form above is not -- linear interpolation does not filter before it decimates (48 ->
+ * 44.1 kHz folds 22.05-24 kHz back into the band) and droops the band by sinc^2(f / rate_in).  AVFoundation's converter is not
+ * specified; this library's convention is a Kaiser-windowed sinc evaluated at exact fp64 positions, zeros beyond both ends:
+ *     Z   zero_crossings, the half width in zero crossings   4 <= Z <= 64       default 32
+ *     b   beta, the Kaiser window's                          0 <= b <= 20       default 12.0 (about 117 dB of stop band)
+ *     r   rolloff                                            0 <  r <= 1        default 0.9
+ *     s      = min(1, rate_out / rate_in) * r         the cutoff as a fraction of the input's Nyquist frequency
+ *     H      = Z / s                                  the half width in input samples
+ *     p_i    = i * rate_in / rate_out                 fp64, i = 0 .. n_out - 1, n_out = syldet_convert_rate_count(n_in, ...)
+ *     h(t)   = s * sinc(s t) * I0(b sqrt(1 - (t / H)^2)) / I0(b)  for |t| < H, else 0;  sinc(x) = sin(pi x) / (pi x)
+ *     out[i] = sum over k = ceil(p_i - H) .. floor(p_i + H) of x[k] * h(p_i - k),   x[k] = 0 for k outside [0, n_in)
+ * No renormalisation at DC: the gain error is the design's own ripple, at the level of the stop band.  The output length is the
+ * linear form's, so nothing behind the converter changes shape.  rate_in == rate_out is a low-pass at r of Nyquist, not a copy.
+ * At the default Z the transition band is about 0.12 of the sampling rate wide and centred on the cutoff; with r = 0.9 the stop
+ * band begins about 1 % above the new Nyquist frequency.
+ *
+ * syldet_sinc_defaults writes the defaults (NULL: skipped).  syldet_sinc_coefficient is h(t) in fp64, NaN for parameters the
+ * device calls refuse; syldet_sinc_taps is 2 floor(H) + 1, the number of taps of an output that falls on an input sample (an
+ * output between two samples may read one more: floor(2 H) + 1 at most), or -1 for such parameters.  These three are host
+ * functions and need no device.                                                                                              */
+void syldet_sinc_defaults(int32_t *zero_crossings, double *beta, double *rolloff);
+double syldet_sinc_coefficient(double t, double rate_in, double rate_out, int32_t zero_crossings, double beta, double rolloff);
+int64_t syldet_sinc_taps(double rate_in, double rate_out, int32_t zero_crossings, double rolloff);
+/* in [C][in_stride] -> out [C][out_stride] fp32, asynchronous on the stream, on the current device; *n_out (host, may be NULL) =
+ * syldet_convert_rate_count(n_in, ...).  The _s16 form takes the rows syldet_deinterleave_device_s16 writes, x meaning
+ * float(x) * 2^-15, and gives the bits of the fp32 form fed those floats.  Stateless: an output depends on its own row, its
+ * index and the parameters alone -- the channel count and the strides do not change its bits, nor does the run.  The device
+ * evaluates h through an fp32 table of the unit filter sinc(tau) * kaiser(tau / Z) (at least 512 entries a zero crossing,
+ * interpolated linearly, the sum in fp32 in the order of k): for every output |out - exact| <= T 2^-24 A + 2^-21 X with T the
+ * number of k in the sum above, A = sum |h x| and X = sum |x|.  The bound as a whole is the contract, not its terms: a
+ * coefficient next to the centre may be up to 1.6e-6 from the exact one, the others far closer than 2^-21.  That table, 64 KiB (Z <= 32) or 128 KiB, sits on the device in
+ * a cache keyed by (Z, beta) and the device: the first call for a parameter set on a device builds it on the host and makes a
+ * blocking copy, as syldet_trace* does for its threshold table; later calls only queue the kernel.  The cache keeps 16 tables
+ * and gives up the oldest for a new one (which waits for the device).  These calls take no handle, so syldet_timings does not
+ * list their kernel (convert_rate_sinc_kernel); time it with events on the stream.
+ * Statuses, before any device is touched: SYLDET_ERR_INVALID_ARGUMENT for a NULL buffer, n_in < 0, n_channels outside
+ * [1, 65535], a rate that is not positive, Z, beta or rolloff outside the ranges above and (n_channels > 1) a stride below its
+ * row; SYLDET_ERR_UNSUPPORTED for rate_in / rate_out outside [1/16, 16], which bounds the inputs a workgroup stages, and for
+ * H > 65536 (a rolloff below 1/64 at the widest filter and ratio): an output costs 2 H taps, and the limit bounds a launch's
+ * run time.  n_in == 0 writes nothing and sets *n_out = 0.            */
+int syldet_convert_rate_sinc_device(const float *d_in, int64_t n_in, int64_t in_stride, int32_t n_channels, double rate_in,
+                                    double rate_out, int32_t zero_crossings, double beta, double rolloff, float *d_out,
+                                    int64_t out_stride, int64_t *n_out, void *hip_stream);
+int syldet_convert_rate_sinc_device_s16(const int16_t *d_in, int64_t n_in, int64_t in_stride, int32_t n_channels, double rate_in,
+                                        double rate_out, int32_t zero_crossings, double beta, double rolloff, float *d_out,
+                                        int64_t out_stride, int64_t *n_out, void *hip_stream);
+
 #ifdef __cplusplus
 }
 #endif

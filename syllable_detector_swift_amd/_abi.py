@@ -185,6 +185,13 @@ SIGNATURES = {
     "syldet_resample_device": (C.c_int, [Handle, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_int64, c_int64_p, C.c_void_p]),
     "syldet_convert_rate_count": (C.c_int64, [C.c_int64, C.c_double, C.c_double]),
     "syldet_convert_rate_device": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_double, C.c_double, C.c_void_p, C.c_int64, c_int64_p, C.c_void_p]),
+    "syldet_sinc_defaults": (None, [c_int32_p, c_double_p, c_double_p]),
+    "syldet_sinc_coefficient": (C.c_double, [C.c_double, C.c_double, C.c_double, C.c_int32, C.c_double, C.c_double]),
+    "syldet_sinc_taps": (C.c_int64, [C.c_double, C.c_double, C.c_int32, C.c_double]),
+    "syldet_convert_rate_sinc_device": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_double, C.c_double, C.c_int32, C.c_double, C.c_double,
+                                                  C.c_void_p, C.c_int64, c_int64_p, C.c_void_p]),
+    "syldet_convert_rate_sinc_device_s16": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_double, C.c_double, C.c_int32, C.c_double, C.c_double,
+                                                      C.c_void_p, C.c_int64, c_int64_p, C.c_void_p]),
     "syldet_resample": (C.c_int, [Handle, c_float_p, C.c_int64, C.c_int64, c_float_p, C.c_int64, c_int64_p]),
     "syldet_host_alloc": (C.c_int, [C.c_size_t, c_void_pp]),
     "syldet_host_free": (C.c_int, [C.c_void_p]),

@@ -12,7 +12,9 @@
 //
 // Differences a user can see: the reference decodes anything AVFoundation can, this tool reads WAV; the
 // reference has Core Audio deliver the network's rate (SyllableDetector.swift:19-23), this tool converts the decoded
-// file by linear interpolation with fp64 positions (syldet_convert_rate_device); events of different channels are interleaved buffer by buffer like the
+// file itself: by linear interpolation with fp64 positions (syldet_convert_rate_device; the default) or, with --resample sinc,
+// band-limited, which is what Core Audio's delivery is (syldet_convert_rate_sinc_device; a 16-bit file stays int16 up to the
+// converter); events of different channels are interleaved buffer by buffer like the
 // reference's read loop (main.swift:126-130), with --chunk frames per buffer (AVAssetReader's buffer size is
 // not specified; 8192 is what it typically vends for linear PCM).
 
@@ -38,13 +40,15 @@ constexpr int kExUsage = 64;   // EX_USAGE, main.swift:40
 void usage(FILE *to)
 {
     std::fprintf(to,
-                 "Usage: syllable-detector-cli -n <net> [-a <audio>]... [-d <seconds>] [--device <k>] [--chunk <frames>] [--format <shortest|swift4>] [--simulate <out.wav>] [--simulate-output <k>] [--levels <out.tsv>] [--levels-buffer <L>] [--levels-period <seconds>] [--ttl <out.wav>] [--ttl-mux] [--ttl-width <seconds>] [--ttl-steps <n>] [--ttl-buffer <L>] [--ttl-latency <seconds>] [--ttl-onsets <out.tsv>] [--probe]\n"
+                 "Usage: syllable-detector-cli -n <net> [-a <audio>]... [-d <seconds>] [--device <k>] [--chunk <frames>] [--format <shortest|swift4>] [--resample <linear|sinc>] [--resample-quality <Z,beta,rolloff>] [--simulate <out.wav>] [--simulate-output <k>] [--levels <out.tsv>] [--levels-buffer <L>] [--levels-period <seconds>] [--ttl <out.wav>] [--ttl-mux] [--ttl-width <seconds>] [--ttl-steps <n>] [--ttl-buffer <L>] [--ttl-latency <seconds>] [--ttl-onsets <out.tsv>] [--probe]\n"
                  "  -n, --net <net>:\n      Path to trained network file.  Given k > 1 times: each file must have exactly k tracks, and track t runs network t (one mixed bank; the networks must share the sampling rate, window length, window overlap, time range and number of outputs).\n"
                  "  -a, --audio <audio>:\n      Path to the audio file to process.\n"
                  "  -d, --debounce <seconds>:\n      Number of seconds to debounce triggers.\n"
                  "      --device <k>:\n      HIP device to run on (default 0).\n"
                  "      --chunk <frames>:\n      Frames per decode buffer when interleaving events of several channels (default 8192; 0: channel by channel).\n"
                  "      --format <shortest|swift4>:\n      How numbers are printed: the shortest digits that round-trip (Swift 4.2 and later; default) or 15 / 6 significant digits (Swift 4.0, the toolchain the project declares: the example line below).\n"
+                 "      --resample <linear|sinc>:\n      How a file at another sampling rate than the network's is converted: linear interpolation between two neighbours (default) or a band-limited Kaiser-windowed sinc, which filters before it decimates and keeps the band's level.\n"
+                 "      --resample-quality <Z,beta,rolloff>:\n      The sinc converter's half width in zero crossings (4 to 64), the Kaiser window's beta (0 to 20) and the cutoff as a fraction of the lower Nyquist frequency (above 0, at most 1); default 32,12,0.9.\n"
                  "      --simulate <out.wav>:\n      Also write the Simulator's output track of every track of the (one) audio file as a 16-bit WAV at the network's sampling rate: the chosen output as a fraction of its threshold (0 = 0, threshold and above = 32767), held from one evaluation to the next.\n"
                  "      --simulate-output <k>:\n      The network output --simulate follows (default 0).\n"
                  "      --levels <out.tsv>:\n      Also write the level meters of every track of the (one) audio file, one line per reading and track, tab separated: the track, the time of the reading's end in seconds, the input RMS (the loudest buffer of the reading), the output level (the greatest first output evaluated in the reading; empty for a reading without an evaluation).\n"
@@ -124,6 +128,14 @@ struct TtlOpt {
     int64_t latency_samples(double rate) const { const double x = latency * rate; return x < 9e18 ? (int64_t)x : INT64_MAX; }
 };
 
+// --resample / --resample-quality: how a file at another rate is brought to the network's (the step the reference's tool leaves to
+// AVFoundation, SyllableDetector.swift:19-23, TrackDetector.swift:35)
+struct ResampleOpt {
+    bool sinc = false;                                     // false: syldet_convert_rate_device
+    int32_t zero_crossings = 0;                            // syldet_sinc_defaults unless --resample-quality
+    double beta = 0.0, rolloff = 0.0;
+};
+
 // cfgs: one network for every track, or (k > 1) network t for track t of a file of exactly k tracks, through one mixed bank
 // (syldet_create_mixed): the networks share the evaluation clock, so the events are found and printed as for one
 // simulate: a path for the Simulator's output track (ViewControllerSimulator.swift:251-344) of every track, made on the device from
@@ -131,7 +143,7 @@ struct TtlOpt {
 // was fed, at the network's rate; empty: none
 int process_file(const std::string &path, const std::vector<syldet_config_t *> &cfgs, int device, double debounce_s, bool have_debounce, int64_t chunk,
                  const std::string &simulate = std::string(), int simulate_output = 0, const LevelsOpt &levels = LevelsOpt(),
-                 const TtlOpt &ttl = TtlOpt())
+                 const TtlOpt &ttl = TtlOpt(), const ResampleOpt &conv = ResampleOpt())
 {
     const syldet_config_t *cfg = cfgs[0];
     wav::Info info;
@@ -140,9 +152,12 @@ int process_file(const std::string &path, const std::vector<syldet_config_t *> &
     std::string err;
     // 16-bit PCM at the network's rate goes to the device as stored (syldet_run_interleaved_device_s16: the fp32 call's results
     // on x / 32768, half the bytes); any other file is decoded to fp32 here
-    const bool pcm16 = wav::probe(path, info, err) && info.format == 1 && info.bits == 16 && info.rate == cfgs[0]->sampling_rate;
+    const bool file16 = wav::probe(path, info, err) && info.format == 1 && info.bits == 16;
+    const bool pcm16 = file16 && info.rate == cfgs[0]->sampling_rate;
+    // ... and so does 16-bit PCM at another rate on its way to the band-limited converter, which reads int16 rows itself
+    const bool raw16 = pcm16 || (file16 && conv.sinc);
     err.clear();
-    if (pcm16 ? !wav::read_s16(path, info, frames16, err) : !wav::read(path, info, frames, err)) {
+    if (raw16 ? !wav::read_s16(path, info, frames16, err) : !wav::read(path, info, frames, err)) {
         std::fprintf(stderr, "Unable to read %s: %s\n", path.c_str(), err.c_str());
         return 1;
     }
@@ -187,19 +202,26 @@ int process_file(const std::string &path, const std::vector<syldet_config_t *> &
         if (hipSetDevice(device) != hipSuccess || hipStreamCreate(&stream) != hipSuccess) { rc = 2; break; }
         const int64_t n = info.frames;
         DevBuf d_inter, d_planar, d_res, d_out, d_flags;
-        const size_t in_bytes = (size_t)n * C * (pcm16 ? sizeof(int16_t) : sizeof(float));
+        const size_t in_bytes = (size_t)n * C * (raw16 ? sizeof(int16_t) : sizeof(float));
         if (!d_inter.alloc(in_bytes)) { rc = 2; break; }
-        if (hipMemcpyAsync(d_inter.p, pcm16 ? (const void *)frames16.data() : (const void *)frames.data(), in_bytes, hipMemcpyHostToDevice, stream) != hipSuccess) { rc = 2; break; }
+        if (hipMemcpyAsync(d_inter.p, raw16 ? (const void *)frames16.data() : (const void *)frames.data(), in_bytes, hipMemcpyHostToDevice, stream) != hipSuccess) { rc = 2; break; }
         int64_t S = n, res_stride = 0;
         int st = 0;
         if (resample) {
             // The reference's tool has AVFoundation deliver every track at the network's rate (SyllableDetector.swift:19-23,
             // TrackDetector.swift:35); here: linear interpolation of the whole decoded file with fp64 positions
-            // (syldet_convert_rate_device; ResamplerLinear is the live path's streaming object, not a file converter)
+            // (syldet_convert_rate_device; ResamplerLinear is the live path's streaming object, not a file converter) or, with
+            // --resample sinc, the band-limited converter -- on the int16 rows of a 16-bit file, which never become fp32 input
             res_stride = syldet_convert_rate_count(n, info.rate, cfg->sampling_rate);
-            if (!d_planar.alloc((size_t)C * n * sizeof(float)) || !d_res.alloc((size_t)C * (res_stride > 0 ? res_stride : 1) * sizeof(float))) { rc = 2; break; }
-            st = syldet_deinterleave_device((const float *)d_inter.p, n, C, 0, C, (float *)d_planar.p, n, stream);
-            if (!st) st = syldet_convert_rate_device((const float *)d_planar.p, n, n, C, info.rate, cfg->sampling_rate, (float *)d_res.p, res_stride, &S, stream);
+            if (!d_planar.alloc((size_t)C * n * (raw16 ? sizeof(int16_t) : sizeof(float))) || !d_res.alloc((size_t)C * (res_stride > 0 ? res_stride : 1) * sizeof(float))) { rc = 2; break; }
+            if (raw16) {
+                st = syldet_deinterleave_device_s16((const int16_t *)d_inter.p, n, C, C, (int16_t *)d_planar.p, n, stream);
+                if (!st) st = syldet_convert_rate_sinc_device_s16((const int16_t *)d_planar.p, n, n, C, info.rate, cfg->sampling_rate, conv.zero_crossings, conv.beta, conv.rolloff, (float *)d_res.p, res_stride, &S, stream);
+            } else {
+                st = syldet_deinterleave_device((const float *)d_inter.p, n, C, 0, C, (float *)d_planar.p, n, stream);
+                if (!st && conv.sinc) st = syldet_convert_rate_sinc_device((const float *)d_planar.p, n, n, C, info.rate, cfg->sampling_rate, conv.zero_crossings, conv.beta, conv.rolloff, (float *)d_res.p, res_stride, &S, stream);
+                else if (!st) st = syldet_convert_rate_device((const float *)d_planar.p, n, n, C, info.rate, cfg->sampling_rate, (float *)d_res.p, res_stride, &S, stream);
+            }
             if (st) {
                 std::fprintf(stderr, "Unable to process %s: %s: %s\n", path.c_str(), syldet_strerror(st), syldet_last_error());
                 rc = 2;
@@ -409,6 +431,9 @@ int main(int argc, char **argv)
     int simulate_output = 0;
     double debounce = 0.0;
     bool have_debounce = false, probe = false;
+    ResampleOpt conv;
+    bool have_resample_quality = false;
+    syldet_sinc_defaults(&conv.zero_crossings, &conv.beta, &conv.rolloff);
     LevelsOpt levels;
     bool have_levels = false, have_levels_option = false;
     TtlOpt ttl;
@@ -435,6 +460,29 @@ int main(int argc, char **argv)
         } else if (a == "--device") device = std::atoi(value(i, "--device"));
         else if (a == "--chunk") chunk = std::atoll(value(i, "--chunk"));
         else if (a == "--probe") probe = true;
+        else if (a == "--resample") {
+            const std::string m = value(i, "--resample");
+            if (m != "linear" && m != "sinc") {
+                std::fprintf(stderr, "--resample takes linear or sinc.\n");
+                usage(stdout);
+                return kExUsage;
+            }
+            conv.sinc = m == "sinc";
+        } else if (a == "--resample-quality") {
+            // Z,beta,rolloff: three numbers, nothing else, inside the converter's ranges (syldet_sinc_taps knows Z's and rolloff's)
+            const char *v = value(i, "--resample-quality");
+            char *e1 = nullptr, *e2 = nullptr, *e3 = nullptr;
+            const long z = std::strtol(v, &e1, 10);
+            const double b = e1 != v && *e1 == ',' ? std::strtod(e1 + 1, &e2) : 0.0;
+            const double r = e2 && e2 != e1 + 1 && *e2 == ',' ? std::strtod(e2 + 1, &e3) : 0.0;
+            if (!e3 || e3 == e2 + 1 || *e3 != 0 || z < 4 || z > 64 || !(b >= 0.0 && b <= 20.0) || !(r > 0.0 && r <= 1.0)) {
+                std::fprintf(stderr, "--resample-quality takes Z,beta,rolloff: 4 to 64 zero crossings, beta from 0 to 20, a rolloff above 0 and at most 1.\n");
+                usage(stdout);
+                return kExUsage;
+            }
+            conv.zero_crossings = (int32_t)z; conv.beta = b; conv.rolloff = r;
+            have_resample_quality = true;
+        }
         else if (a == "--simulate") {
             simulate = value(i, "--simulate");
             have_simulate = true;
@@ -552,6 +600,11 @@ int main(int argc, char **argv)
         usage(stdout);
         return kExUsage;
     }
+    if (have_resample_quality && !conv.sinc) {
+        std::fprintf(stderr, "--resample-quality needs --resample sinc.\n");
+        usage(stdout);
+        return kExUsage;
+    }
     if (have_simulate && (audio.size() != 1 || simulate.empty())) {   // the Simulator takes one recording (simulateNetwork(_:withAudio:writeTo:), ViewControllerSimulator.swift:135)
         std::fprintf(stderr, "--simulate writes the track of exactly one audio file (-a).\n");
         usage(stdout);
@@ -626,7 +679,7 @@ int main(int argc, char **argv)
     for (const std::string &p : audio) {
         if (audio.size() > 1) std::printf("%s\n", p.c_str());   // main.swift:122-124
         std::fflush(stdout);
-        const int r = process_file(p, cfgs, device, debounce, have_debounce, chunk, simulate, simulate_output, levels, ttl);
+        const int r = process_file(p, cfgs, device, debounce, have_debounce, chunk, simulate, simulate_output, levels, ttl, conv);
         if (r == 2) rc = 2;                                 // device trouble is fatal for the exit code; an unreadable file is skipped
         else if (r == 3 && rc == 0) rc = 1;                 // ... and so is a track that could not be written
     }

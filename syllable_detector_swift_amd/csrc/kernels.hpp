@@ -293,6 +293,20 @@ hipError_t launch_resample_linear(const float *in, int64_t n_in, int64_t in_stri
 // whole-recording rate conversion, fp64 positions (offline input: no carry)
 hipError_t launch_convert_rate(const float *in, int64_t n_in, int64_t in_stride, float *out, int64_t n_out, int64_t out_stride,
                                int C, double step, hipStream_t stream);
+// ---- band-limited whole-recording rate conversion (kernels_sinc.hip; the sinc convention of include/syldet.h) ----
+constexpr int kSincPerThread = 4;                     // outputs a thread, 256 apart
+constexpr int kSincBlockOut = 256 * kSincPerThread;   // consecutive outputs of one row a workgroup
+constexpr int kSincStage = 4000;                      // input samples staged in LDS at a time
+// entries N of the unit filter's table over [0, Z]: at least 512 a zero crossing, a multiple of 4; the table holds N + 4 floats,
+// g[j] = sinc(j Z / N) * kaiser(j / N) for j < N and zeros from g[N] on
+inline int sinc_table_entries(int Z) { return Z <= 32 ? 16384 : 32768; }
+// in [C][in_stride] -> out [C][out_stride]; H = Z / s (|H| <= 65536), scale = float(s), table on the device, 16-byte aligned
+hipError_t launch_convert_rate_sinc(const float *in, int64_t n_in, int64_t in_stride, float *out, int64_t n_out,
+                                    int64_t out_stride, int C, double rate_in, double rate_out, double H, float scale,
+                                    const float *table, int N, hipStream_t stream);
+hipError_t launch_convert_rate_sinc_s16(const int16_t *in, int64_t n_in, int64_t in_stride, float *out, int64_t n_out,
+                                        int64_t out_stride, int C, double rate_in, double rate_out, double H, float scale,
+                                        const float *table, int N, hipStream_t stream);
 // frame-major [n_frames][total] -> channel-major rows of channels first .. first+C-1
 hipError_t launch_deinterleave(const float *in, int64_t n_frames, int total, int first, int C, float *out,
                                int64_t out_stride, hipStream_t stream);

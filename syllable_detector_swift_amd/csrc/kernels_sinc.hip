@@ -1,0 +1,131 @@
+// kernels_sinc.hip -- band-limited whole-recording rate conversion (the sinc convention of include/syldet.h), the step the
+// reference's tool leaves to AVFoundation (audioSettings, Common/SyllableDetector.swift:19-23, handed to
+// AVAssetReaderTrackOutput at SyllableDetectorCLI/TrackDetector.swift:35):
+//   convert_rate_sinc_kernel<float>     fp32 rows in, fp32 rows out
+//   convert_rate_sinc_kernel<int16_t>   16-bit PCM rows in (x means float(x) * 2^-15), the same arithmetic on the same floats
+//
+// A workgroup owns kSincBlockOut consecutive outputs of one row.  It copies the unit filter g (sinc(tau) * kaiser(tau / Z) at
+// kSincTable(Z) + 1 equally spaced points of [0, Z], built by the host in fp64) into LDS once, then walks the inputs its outputs
+// read, [floor(p_first - H), ceil(p_last + H)] cut to the row, in stretches of kSincStage samples staged in LDS (int16 widened
+// as it is staged; outside the row the sum has no terms, which is what zeros there would add).  A thread owns kSincPerThread
+// outputs, 256 apart, so that neighbouring lanes read neighbouring inputs and store neighbouring outputs.  Per tap: two LDS reads of g, one of x, no transcendental --
+//   t = float(floor(p) - k) + float(p - floor(p))      one rounding: the relative error of t is 2^-24 at every distance
+//   u = min(|t| * (N / H), N);  j = int(u);  c = g[j] + (u - j) * (g[j + 1] - g[j]);  acc += x[k] * c        k ascending
+// and out = s * acc.  p = i * rate_in / rate_out is fp64 from i for every output, so an output's bits depend on its own row,
+// its index and the parameters alone: not on the channel count, the strides, the workgroup it fell into or the run.
+//
+// gfx950 only.  wave = 64.  Compiled with -ffp-contract=off (see the Makefile): the two forms share their bits by construction.
+
+#include "kernels.hpp"
+
+namespace sd {
+
+namespace {
+
+template <typename T> __device__ __forceinline__ float sinc_sample(T v);
+template <> __device__ __forceinline__ float sinc_sample<float>(float v) { return v; }
+template <> __device__ __forceinline__ float sinc_sample<int16_t>(int16_t v) { return (float)v * (1.0f / 32768.0f); }
+
+template <typename T>
+__global__ void __launch_bounds__(256)
+convert_rate_sinc_kernel(const T *__restrict__ in, int64_t n_in, int64_t in_stride, float *__restrict__ out, int64_t n_out,
+                         int64_t out_stride, double rate_in, double rate_out, double H, float scale, float idx_scale,
+                         const float *__restrict__ table, int N)
+{
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    float *g = reinterpret_cast<float *>(smem);              // [N + 4]: g[N] = 0 (sinc(Z) = 0), then zeros
+    float *xs = g + (N + 4);                                 // [kSincStage]
+    const int tid = threadIdx.x;
+    const T *row = in + (int64_t)blockIdx.y * in_stride;
+    float *dst = out + (int64_t)blockIdx.y * out_stride;
+    const int64_t i0 = (int64_t)blockIdx.x * kSincBlockOut;
+    const int64_t i_last = min(i0 + (int64_t)kSincBlockOut, n_out) - 1;      // >= i0: the grid covers n_out exactly
+
+    for (int e = tid; e < (N + 4) / 4; e += 256)             // (the table's buffer is 16-byte aligned and N % 4 == 0)
+        reinterpret_cast<float4 *>(g)[e] = reinterpret_cast<const float4 *>(table)[e];
+
+    // this thread's outputs: position, first and last tap (cut to the row), running sum
+    int64_t pf[kSincPerThread], k_lo[kSincPerThread], k_hi[kSincPerThread];
+    float frac[kSincPerThread], acc[kSincPerThread];
+#pragma unroll
+    for (int r = 0; r < kSincPerThread; r++) {
+        const int64_t i = i0 + tid + (int64_t)r * 256;
+        const double p = (double)i * rate_in / rate_out;
+        const double fl = floor(p);
+        pf[r] = (int64_t)fl;
+        frac[r] = (float)(p - fl);
+        k_lo[r] = max((int64_t)ceil(p - H), (int64_t)0);
+        k_hi[r] = i <= i_last ? min((int64_t)floor(p + H), n_in - 1) : (int64_t)-1;      // past the row's end: no tap
+        acc[r] = 0.0f;
+    }
+    // the inputs the workgroup reads (positions grow with i: the first output reaches furthest back, the last furthest on)
+    const int64_t lo = max((int64_t)floor((double)i0 * rate_in / rate_out - H), (int64_t)0);
+    const int64_t hi = min((int64_t)ceil((double)i_last * rate_in / rate_out + H), n_in - 1);
+    const float n_f = (float)N;
+
+    for (int64_t base = lo; base <= hi; base += kSincStage) {
+        __syncthreads();                                     // the table is in; the stretch before this one is read out
+        const int64_t end = min(base + kSincStage - 1, hi);                              // 0 <= base <= end <= n_in - 1
+        for (int e = tid; e <= (int)(end - base); e += 256) xs[e] = sinc_sample<T>(row[base + e]);
+        __syncthreads();
+#pragma unroll
+        for (int r = 0; r < kSincPerThread; r++) {
+            const int64_t ka = max(k_lo[r], base), kb = min(k_hi[r], end);
+            if (ka > kb) continue;
+            const int n = (int)(kb - ka) + 1;
+            int m = (int)(pf[r] - ka);                       // |m| <= H + 1 < 2^17
+            const float *x = xs + (int)(ka - base);
+            const float f = frac[r];
+            float a = acc[r];
+            for (int q = 0; q < n; q++, m--) {
+                const float t = (float)m + f;
+                const float u = fminf(fabsf(t) * idx_scale, n_f);
+                const int j = (int)u;                        // 0 .. N; g[N + 1] is a zero
+                const float w = u - (float)j;
+                const float g0 = g[j], g1 = g[j + 1];
+                const float c = g0 + w * (g1 - g0);
+                a = a + x[q] * c;
+            }
+            acc[r] = a;
+        }
+    }
+#pragma unroll
+    for (int r = 0; r < kSincPerThread; r++) {
+        const int64_t i = i0 + tid + (int64_t)r * 256;
+        if (i <= i_last) dst[i] = scale * acc[r];
+    }
+}
+
+template <typename T>
+hipError_t launch_sinc(const T *in, int64_t n_in, int64_t in_stride, float *out, int64_t n_out, int64_t out_stride, int C,
+                       double rate_in, double rate_out, double H, float scale, const float *table, int N, hipStream_t stream)
+{
+    if (n_out <= 0 || C <= 0) return hipSuccess;
+    auto kern = convert_rate_sinc_kernel<T>;
+    const int lds = (N + 4 + kSincStage) * (int)sizeof(float);
+    // 80 KB (Z <= 32: two workgroups a CU) or 144 KB (one); the attribute is per device, so it is set on every launch
+    hipError_t st = hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+    if (st != hipSuccess) return st;
+    dim3 grid((unsigned)((n_out + kSincBlockOut - 1) / kSincBlockOut), (unsigned)C);
+    hipLaunchKernelGGL(kern, grid, dim3(256), (size_t)lds, stream, in, n_in, in_stride, out, n_out, out_stride, rate_in, rate_out,
+                       H, scale, (float)((double)N / H), table, N);
+    return hipGetLastError();
+}
+
+}  // namespace
+
+hipError_t launch_convert_rate_sinc(const float *in, int64_t n_in, int64_t in_stride, float *out, int64_t n_out,
+                                    int64_t out_stride, int C, double rate_in, double rate_out, double H, float scale,
+                                    const float *table, int N, hipStream_t stream)
+{
+    return launch_sinc<float>(in, n_in, in_stride, out, n_out, out_stride, C, rate_in, rate_out, H, scale, table, N, stream);
+}
+
+hipError_t launch_convert_rate_sinc_s16(const int16_t *in, int64_t n_in, int64_t in_stride, float *out, int64_t n_out,
+                                        int64_t out_stride, int C, double rate_in, double rate_out, double H, float scale,
+                                        const float *table, int N, hipStream_t stream)
+{
+    return launch_sinc<int16_t>(in, n_in, in_stride, out, n_out, out_stride, C, rate_in, rate_out, H, scale, table, N, stream);
+}
+
+}  // namespace sd

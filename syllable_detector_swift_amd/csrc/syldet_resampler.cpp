@@ -1,15 +1,18 @@
 // syldet_resampler.cpp -- ResamplerLinear (Common/Resampler.swift:20-76) for a bank of channels on the
 // device, and the stand-alone de-interleave entry point.  The resampling state that depends only on
 // sizes (`offset`) lives on the host and is advanced with the reference's own fp32 operations; the
-// per-channel carry (`last`) lives on the device next to the data.
+// per-channel carry (`last`) lives on the device next to the data.  The two stateless whole-recording converters are here too:
+// the linear one and the band-limited one (a Kaiser-windowed sinc: its design, its fp64 coefficient and its table cache).
 
 #include <hip/hip_runtime.h>
 
 #include <cmath>
 #include <cstring>
 #include <memory>
+#include <mutex>
 #include <new>
 #include <string>
+#include <vector>
 
 #include "kernels.hpp"
 #include "syldet_internal.hpp"
@@ -158,6 +161,159 @@ int syldet_convert_rate_device(const float *d_in, int64_t n_in, int64_t in_strid
     SYLDET_HIP(launch_convert_rate(d_in, n_in, in_stride, d_out, n, out_stride, n_channels, rate_in / rate_out, (hipStream_t)hip_stream));
     if (n_out) *n_out = n;
     return SYLDET_OK;
+}
+
+}  // extern "C"
+
+// ---- the band-limited converter (the sinc convention of include/syldet.h) ----
+namespace {
+
+constexpr double kPi = 3.14159265358979323846;
+constexpr double kSincMaxHalfWidth = 65536.0;          // H = Z / s: every output costs 2 H taps, so this bounds a launch's run time
+
+// I0 by its power series, sum ((x / 2)^k / k!)^2: every term positive, so no cancellation; x <= 20 ends within 60 terms
+double bessel_i0(double x)
+{
+    const double q = 0.25 * x * x;
+    double term = 1.0, sum = 1.0;
+    for (int k = 1; k < 500; k++) {
+        term *= q / ((double)k * (double)k);
+        sum += term;
+        if (term < 1e-18 * sum) break;
+    }
+    return sum;
+}
+
+double sinc_pi(double x)
+{
+    const double y = kPi * x;
+    return y == 0.0 ? 1.0 : std::sin(y) / y;
+}
+
+// s and H of the convention; the statuses of the device calls, in their order
+int sinc_design(double rate_in, double rate_out, int32_t Z, double beta, double rho, double *s, double *H)
+{
+    if (!(rate_in > 0.0) || !(rate_out > 0.0) || !std::isfinite(rate_in) || !std::isfinite(rate_out))
+        return fail(SYLDET_ERR_INVALID_ARGUMENT, "sampling rates must be positive");
+    if (Z < 4 || Z > 64) return fail(SYLDET_ERR_INVALID_ARGUMENT, "zero_crossings must be in [4, 64]");
+    if (!(beta >= 0.0 && beta <= 20.0)) return fail(SYLDET_ERR_INVALID_ARGUMENT, "beta must be in [0, 20]");
+    if (!(rho > 0.0 && rho <= 1.0)) return fail(SYLDET_ERR_INVALID_ARGUMENT, "rolloff must be in (0, 1]");
+    const double ratio = rate_in / rate_out;
+    if (!(ratio >= 1.0 / 16.0 && ratio <= 16.0)) return fail(SYLDET_ERR_UNSUPPORTED, "rate_in / rate_out must be in [1/16, 16]");
+    *s = (rate_out / rate_in < 1.0 ? rate_out / rate_in : 1.0) * rho;
+    *H = (double)Z / *s;
+    if (!(*H <= kSincMaxHalfWidth)) return fail(SYLDET_ERR_UNSUPPORTED, "the filter's half width Z / s exceeds 65536 input samples");
+    return SYLDET_OK;
+}
+
+// The unit filter's table on the device, one per (device, Z, beta), made on the first call that needs it (a blocking copy) and
+// kept for the life of the process; at most kSincTables of them, the oldest given up once a new one is in place.  The caller
+// holds g_sinc_mutex from the lookup to the end of its launch: hipFree waits for the work already queued, so a table is never
+// freed between a lookup and the launch that reads it.
+struct SincTable { int device; int Z; double beta; float *d; };
+constexpr size_t kSincTables = 16;
+std::mutex g_sinc_mutex;
+std::vector<SincTable> g_sinc_tables;
+
+int sinc_table(int Z, double beta, const float **out, int *entries)
+{
+    int device = 0;
+    SYLDET_HIP(hipGetDevice(&device));
+    const int N = sinc_table_entries(Z);
+    *entries = N;
+    for (const SincTable &t : g_sinc_tables)
+        if (t.device == device && t.Z == Z && t.beta == beta) { *out = t.d; return SYLDET_OK; }
+    std::vector<float> g((size_t)N + 4, 0.0f);
+    const double i0b = bessel_i0(beta);
+    for (int j = 0; j < N; j++) {
+        const double u = (double)j / (double)N;
+        g[(size_t)j] = (float)(sinc_pi(u * (double)Z) * bessel_i0(beta * std::sqrt(1.0 - u * u)) / i0b);
+    }
+    float *d = nullptr;
+    SYLDET_HIP(hipMalloc((void **)&d, g.size() * sizeof(float)));
+    hipError_t e = hipMemcpy(d, g.data(), g.size() * sizeof(float), hipMemcpyHostToDevice);
+    if (e != hipSuccess) {
+        (void)hipFree(d);
+        return fail(SYLDET_ERR_DEVICE, std::string("hipMemcpy of the filter table: ") + hipGetErrorString(e));
+    }
+    if (g_sinc_tables.size() >= kSincTables) {
+        (void)hipFree(g_sinc_tables.front().d);
+        g_sinc_tables.erase(g_sinc_tables.begin());
+    }
+    g_sinc_tables.push_back({device, Z, beta, d});
+    *out = d;
+    return SYLDET_OK;
+}
+
+template <typename T>
+int convert_rate_sinc(const T *d_in, int64_t n_in, int64_t in_stride, int32_t n_channels, double rate_in, double rate_out,
+                      int32_t Z, double beta, double rho, float *d_out, int64_t out_stride, int64_t *n_out, void *hip_stream)
+{
+    if (n_out) *n_out = 0;
+    if (n_in < 0 || n_channels <= 0 || n_channels > 65535) return fail(SYLDET_ERR_INVALID_ARGUMENT, "n_in must be >= 0, n_channels in [1, 65535]");
+    if (!d_in || !d_out) return fail(SYLDET_ERR_INVALID_ARGUMENT, "NULL buffer");
+    double s = 0.0, H = 0.0;
+    // (the ranges before the ratio: a bad parameter is an invalid argument at any ratio)
+    if (int st = sinc_design(rate_in, rate_out, Z, beta, rho, &s, &H)) return st;
+    const int64_t n = syldet_convert_rate_count(n_in, rate_in, rate_out);
+    if (n_channels > 1 && (in_stride < n_in || out_stride < n)) return fail(SYLDET_ERR_INVALID_ARGUMENT, "row strides must cover the rows");
+    if (n <= 0) return SYLDET_OK;
+    const float *table = nullptr;
+    int N = 0;
+    std::lock_guard<std::mutex> lock(g_sinc_mutex);          // from the table's lookup to the end of the launch (see sinc_table)
+    if (int st = sinc_table(Z, beta, &table, &N)) return st;
+    if constexpr (sizeof(T) == 2)
+        SYLDET_HIP(launch_convert_rate_sinc_s16(d_in, n_in, in_stride, d_out, n, out_stride, n_channels, rate_in, rate_out, H, (float)s,
+                                                table, N, (hipStream_t)hip_stream));
+    else
+        SYLDET_HIP(launch_convert_rate_sinc(d_in, n_in, in_stride, d_out, n, out_stride, n_channels, rate_in, rate_out, H, (float)s,
+                                            table, N, (hipStream_t)hip_stream));
+    if (n_out) *n_out = n;
+    return SYLDET_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+void syldet_sinc_defaults(int32_t *zero_crossings, double *beta, double *rolloff)
+{
+    if (zero_crossings) *zero_crossings = 32;
+    if (beta) *beta = 12.0;
+    if (rolloff) *rolloff = 0.9;
+}
+
+double syldet_sinc_coefficient(double t, double rate_in, double rate_out, int32_t zero_crossings, double beta, double rolloff)
+{
+    double s = 0.0, H = 0.0;
+    if (sinc_design(rate_in, rate_out, zero_crossings, beta, rolloff, &s, &H)) return std::nan("");
+    if (t != t) return t;
+    const double u = t / H;
+    if (!(std::fabs(t) < H)) return 0.0;
+    return s * sinc_pi(s * t) * bessel_i0(beta * std::sqrt(1.0 - u * u)) / bessel_i0(beta);
+}
+
+int64_t syldet_sinc_taps(double rate_in, double rate_out, int32_t zero_crossings, double rolloff)
+{
+    double s = 0.0, H = 0.0;
+    if (sinc_design(rate_in, rate_out, zero_crossings, 0.0, rolloff, &s, &H)) return -1;
+    return 2 * (int64_t)std::floor(H) + 1;
+}
+
+int syldet_convert_rate_sinc_device(const float *d_in, int64_t n_in, int64_t in_stride, int32_t n_channels, double rate_in,
+                                    double rate_out, int32_t zero_crossings, double beta, double rolloff, float *d_out,
+                                    int64_t out_stride, int64_t *n_out, void *hip_stream)
+{
+    return convert_rate_sinc<float>(d_in, n_in, in_stride, n_channels, rate_in, rate_out, zero_crossings, beta, rolloff, d_out,
+                                    out_stride, n_out, hip_stream);
+}
+
+int syldet_convert_rate_sinc_device_s16(const int16_t *d_in, int64_t n_in, int64_t in_stride, int32_t n_channels, double rate_in,
+                                        double rate_out, int32_t zero_crossings, double beta, double rolloff, float *d_out,
+                                        int64_t out_stride, int64_t *n_out, void *hip_stream)
+{
+    return convert_rate_sinc<int16_t>(d_in, n_in, in_stride, n_channels, rate_in, rate_out, zero_crossings, beta, rolloff, d_out,
+                                      out_stride, n_out, hip_stream);
 }
 
 int syldet_deinterleave_device_s16(const int16_t *d_interleaved, int64_t n_frames, int32_t total_channels, int32_t n_channels,

@@ -3,6 +3,10 @@
 Same surface as the reference class -- `ResamplerLinear(fromRate:toRate:)`, `resampleVector`, `resampleArray`
 -- over libsyldet's `syldet_resample*`; state (fractional offset, last sample of every channel) carries over
 between calls exactly as in the reference.
+
+`convertRate` is the whole-recording converter of the file path (the step the reference's tool leaves to AVFoundation,
+Common/SyllableDetector.swift:19-23): linear interpolation at fp64 positions, or the band-limited Kaiser-windowed sinc whose
+convention include/syldet.h states; `sincCoefficient` and `sincTaps` are that convention's host functions.
 """
 import ctypes as C
 
@@ -25,6 +29,68 @@ def deinterleave(frames, first_channel: int = 0, channels=None, stream=None):
     check(_abi.lib.syldet_deinterleave_device(frames.data_ptr(), n, total, int(first_channel), channels, out.data_ptr(), n,
                                               int(s.cuda_stream)))
     return out
+
+
+def sincDefaults():
+    """(zeroCrossings, beta, rolloff) a call without them uses."""
+    z, b, r = C.c_int32(0), C.c_double(0.0), C.c_double(0.0)
+    _abi.lib.syldet_sinc_defaults(C.byref(z), C.byref(b), C.byref(r))
+    return int(z.value), float(b.value), float(r.value)
+
+
+def _sinc_quality(zeroCrossings, beta, rolloff):
+    z, b, r = sincDefaults()
+    return (z if zeroCrossings is None else int(zeroCrossings), b if beta is None else float(beta),
+            r if rolloff is None else float(rolloff))
+
+
+def sincCoefficient(t: float, fromRate: float, toRate: float, zeroCrossings=None, beta=None, rolloff=None) -> float:
+    """h(t) of the sinc convention in fp64 (t in input samples); NaN for parameters the converter refuses.  No device."""
+    z, b, r = _sinc_quality(zeroCrossings, beta, rolloff)
+    return float(_abi.lib.syldet_sinc_coefficient(float(t), float(fromRate), float(toRate), z, b, r))
+
+
+def sincTaps(fromRate: float, toRate: float, zeroCrossings=None, rolloff=None) -> int:
+    """2 floor(H) + 1, the input samples an output on an input sample reads (one more may fit between two); -1 for parameters
+    the converter refuses.  No device."""
+    z, _, r = _sinc_quality(zeroCrossings, None, rolloff)
+    return int(_abi.lib.syldet_sinc_taps(float(fromRate), float(toRate), z, r))
+
+
+def convertRate(rows, fromRate: float, toRate: float, method: str = "linear", zeroCrossings=None, beta=None, rolloff=None,
+                stream=None):
+    """rows [C, n] (or [n]) CUDA tensor at fromRate -> float32 rows [C, n_out] at toRate, asynchronous on `stream`.
+
+    method "linear": syldet_convert_rate_device (float32 rows).  method "sinc": the band-limited converter, float32 rows or the
+    int16 rows of 16-bit PCM (x meaning x / 32768; the float32 call's bits); zeroCrossings, beta and rolloff default to
+    sincDefaults().  The first sinc call for a (zeroCrossings, beta) on a device copies the filter's table there and blocks."""
+    import torch
+    if method not in ("linear", "sinc"):
+        raise ValueError("method must be 'linear' or 'sinc'")
+    if method == "linear" and not (zeroCrossings is None and beta is None and rolloff is None):
+        raise ValueError("zeroCrossings, beta and rolloff belong to method='sinc'")
+    x = rows if rows.dim() == 2 else rows.reshape(1, -1)
+    kinds = (torch.float32, torch.int16) if method == "sinc" else (torch.float32,)
+    if not (x.is_cuda and x.dtype in kinds and x.dim() == 2 and x.shape[0] >= 1 and (x.shape[1] == 0 or x.stride(1) == 1)):
+        raise ValueError("rows must be a %s CUDA tensor with one contiguous row per channel" % " or ".join(str(k) for k in kinds))
+    channels, n_in = int(x.shape[0]), int(x.shape[1])
+    n_out = int(_abi.lib.syldet_convert_rate_count(n_in, float(fromRate), float(toRate)))
+    out = torch.empty((channels, n_out), dtype=torch.float32, device=x.device)
+    if n_in == 0 and float(fromRate) > 0 and float(toRate) > 0:      # an empty recording: no buffer to hand over
+        return out if rows.dim() == 2 else out.reshape(-1)
+    got = C.c_int64(0)
+    s = stream if stream is not None else torch.cuda.current_stream(x.device)
+    with torch.cuda.device(x.device):
+        if method == "linear":
+            check(_abi.lib.syldet_convert_rate_device(x.data_ptr(), n_in, int(x.stride(0)), channels, float(fromRate), float(toRate),
+                                                      out.data_ptr(), max(n_out, 1), C.byref(got), int(s.cuda_stream)))
+        else:
+            z, b, r = _sinc_quality(zeroCrossings, beta, rolloff)
+            fn = _abi.lib.syldet_convert_rate_sinc_device_s16 if x.dtype == torch.int16 else _abi.lib.syldet_convert_rate_sinc_device
+            check(fn(x.data_ptr(), n_in, int(x.stride(0)), channels, float(fromRate), float(toRate), z, b, r,
+                     out.data_ptr(), max(n_out, 1), C.byref(got), int(s.cuda_stream)))
+    assert got.value == n_out
+    return out if rows.dim() == 2 else out.reshape(-1)
 
 
 class ResamplerLinear:
