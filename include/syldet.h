@@ -743,6 +743,64 @@ int syldet_convert_rate_sinc_device_s16(const int16_t *d_in, int64_t n_in, int64
                                         double rate_out, int32_t zero_crossings, double beta, double rolloff, float *d_out,
                                         int64_t out_stride, int64_t *n_out, void *hip_stream);
 
+/* The band-limited converter as a stream: ResamplerSinc, a second conformer of the reference's Resampler protocol
+ * (Common/Resampler.swift:12-15; Processor.swift:115-120 puts one in front of appendAudioData when the device's rate is not the
+ * network's).  The contract has no tolerance: however a recording is cut into pushes, the concatenated outputs of the pushes
+ * and the flush are syldet_convert_rate_sinc_device's on the whole rows, bit for bit.  Everything is the convention above; only
+ * the emission rule is new:
+ *     N          input samples received so far (per channel), M outputs emitted so far
+ *     p_i        = (double)i * rate_in / rate_out, i absolute (counted from the stream's first output); H, s, the taps and the
+ *                order of the sum are those of syldet_convert_rate_sinc_device
+ *     ready      output i is emitted as soon as floor(p_i + H) <= N - 1: every tap it will ever have is present, so the whole-
+ *                recording form's cut at the row's end is not active and its bits cannot depend on what comes later.  The
+ *                predicate is evaluated in fp64 in the kernel's order of operations and is monotone in i; ready(N) is the number of
+ *                outputs that satisfy it, and after every push M = ready(N) <= syldet_convert_rate_count(N, ...).
+ *     flush      ends the recording at N samples: emits i = M .. syldet_convert_rate_count(N, ...) - 1 with their taps cut at
+ *                N - 1, as the whole-recording call does at a row's end.  The stream is then finished: a push is refused
+ *                (SYLDET_ERR_INVALID_ARGUMENT) until syldet_sinc_resampler_reset; another flush emits nothing.
+ *     history    the next output reads inputs from max(ceil(p_M - H), 0) on, never more than ceil(2 H) + 2 samples behind N; the
+ *                handle keeps that many per channel on the device as fp32 (two buffers, used in turn).  An int16 push is widened
+ *                as it is kept (x * 2^-15, exact), so fp32 and int16 pushes may alternate on one handle.
+ *     latency    outputs trail inputs by H input samples: 35.6 (0.74 ms) at 48 -> 44.1 kHz with the defaults, 8.9 at Z = 8.
+ * syldet_sinc_ready is ready(n_in_total) in host arithmetic, no device; -1 for parameters the device calls refuse.
+ *
+ * syldet_sinc_resampler_create checks its arguments as syldet_convert_rate_sinc_device does (same ranges, same statuses; then
+ * SYLDET_ERR_NO_DEVICE), builds the handle's OWN copy of the filter's table (the same floats as the stateless calls' cache, which
+ * gives up its oldest table and so cannot lend one) and the history, and blocks.  reset: N = M = 0, not finished.  position
+ * reads N, M and whether the stream is finished (any pointer may be NULL).  count: the outputs a push of n_in samples would emit
+ * now; flush_count: those a flush would.
+ *
+ * The device calls: in [C][in_stride] (fp32, or int16 meaning x * 2^-15) -> out [C][out_stride] fp32, *n_out (host, may be NULL)
+ * the outputs per channel this call emitted, which is syldet_sinc_resampler_count taken before it.  N and M are host arithmetic:
+ * a device push never synchronises, never allocates and never copies from the host; it queues at most two kernels
+ * (convert_rate_sinc_stream_kernel when it emits, sinc_carry_kernel for the history).  ALL device work of one handle must be on
+ * one stream, or ordered by the caller: a push reads the history the push before it wrote.  The pushed rows must stay valid until
+ * that work has run.  Statuses, decided before any device is touched and before any state changes -- a refused call leaves N, M
+ * and the history as they were, and a correct call after it gives the right bits: SYLDET_ERR_INVALID_ARGUMENT for a NULL handle,
+ * n_in < 0, a push on a finished stream, a NULL input with n_in > 0, a NULL output when the call emits something (d_out may be
+ * NULL only when it emits nothing) and, with more than one channel, a stride below its row (in_stride < n_in, out_stride < the
+ * count).  n_in == 0 is legal and emits nothing.
+ *
+ * syldet_sinc_resample and syldet_sinc_resampler_flush take host buffers and block (resampleArray's shape, as syldet_resample
+ * is for the linear one), on a stream of the handle's own.                                                                  */
+typedef struct syldet_sinc_resampler syldet_sinc_resampler_t;
+int64_t syldet_sinc_ready(int64_t n_in_total, double rate_in, double rate_out, int32_t zero_crossings, double rolloff);
+int syldet_sinc_resampler_create(double rate_in, double rate_out, int32_t n_channels, int32_t device, int32_t zero_crossings,
+                                 double beta, double rolloff, syldet_sinc_resampler_t **out);
+int syldet_sinc_resampler_destroy(syldet_sinc_resampler_t *r);
+int syldet_sinc_resampler_reset(syldet_sinc_resampler_t *r);
+int syldet_sinc_resampler_position(const syldet_sinc_resampler_t *r, int64_t *n_in_total, int64_t *n_out_total, int32_t *finished);
+int64_t syldet_sinc_resampler_count(const syldet_sinc_resampler_t *r, int64_t n_in);
+int64_t syldet_sinc_resampler_flush_count(const syldet_sinc_resampler_t *r);
+int syldet_sinc_resample_device(syldet_sinc_resampler_t *r, const float *d_in, int64_t n_in, int64_t in_stride, float *d_out,
+                                int64_t out_stride, int64_t *n_out, void *hip_stream);
+int syldet_sinc_resample_device_s16(syldet_sinc_resampler_t *r, const int16_t *d_in, int64_t n_in, int64_t in_stride, float *d_out,
+                                    int64_t out_stride, int64_t *n_out, void *hip_stream);
+int syldet_sinc_resampler_flush_device(syldet_sinc_resampler_t *r, float *d_out, int64_t out_stride, int64_t *n_out, void *hip_stream);
+int syldet_sinc_resample(syldet_sinc_resampler_t *r, const float *in, int64_t n_in, int64_t in_stride, float *out,
+                         int64_t out_stride, int64_t *n_out);
+int syldet_sinc_resampler_flush(syldet_sinc_resampler_t *r, float *out, int64_t out_stride, int64_t *n_out);
+
 #ifdef __cplusplus
 }
 #endif

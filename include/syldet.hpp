@@ -463,4 +463,72 @@ private:
     int channels_;
 };
 
+// ResamplerSinc: the band-limited converter (syldet_convert_rate_sinc_device's convention) as a second conformer of the
+// reference's Resampler protocol (Resampler.swift:12-15), for `channels` streams fed in lock-step.  Push blocks of any sizes,
+// then flush: the concatenated outputs are the whole-recording call's, bit for bit.  Quality arguments below zero take
+// syldet_sinc_defaults'.  All device work of one object belongs on one stream.
+class ResamplerSinc {
+public:
+    ResamplerSinc(double fromRate, double toRate, int channels = 1, int device = 0, int zeroCrossings = -1, double beta = -1.0,
+                  double rolloff = -1.0) : channels_(channels)
+    {
+        int32_t z = 0;
+        double b = 0.0, r = 0.0;
+        syldet_sinc_defaults(&z, &b, &r);
+        check(syldet_sinc_resampler_create(fromRate, toRate, channels, device, zeroCrossings < 0 ? z : zeroCrossings, beta < 0.0 ? b : beta,
+                                           rolloff < 0.0 ? r : rolloff, &r_));
+    }
+    ~ResamplerSinc() { syldet_sinc_resampler_destroy(r_); }
+    ResamplerSinc(const ResamplerSinc &) = delete;
+    ResamplerSinc &operator=(const ResamplerSinc &) = delete;
+
+    // host rows [channels][n] -> [channels][returned length], blocking
+    std::vector<float> resampleArray(const std::vector<float> &arr)
+    {
+        const int64_t n = (int64_t)(arr.size() / (size_t)channels_), m = syldet_sinc_resampler_count(r_, n);
+        std::vector<float> out((size_t)channels_ * (size_t)m);
+        int64_t got = 0;
+        check(syldet_sinc_resample(r_, arr.data(), n, n, out.data(), m > 0 ? m : 1, &got));
+        return out;
+    }
+    // the recording's last outputs, host rows [channels][returned length]; the stream is finished until reset()
+    std::vector<float> flush()
+    {
+        const int64_t m = syldet_sinc_resampler_flush_count(r_);
+        std::vector<float> out((size_t)channels_ * (size_t)m);
+        int64_t got = 0;
+        check(syldet_sinc_resampler_flush(r_, out.data(), m > 0 ? m : 1, &got));
+        return out;
+    }
+    // device rows, asynchronous on `hipStream`
+    int64_t resampleVector(const float *d_data, int64_t n, int64_t stride, float *d_out, int64_t out_stride, void *hipStream)
+    {
+        int64_t got = 0;
+        check(syldet_sinc_resample_device(r_, d_data, n, stride, d_out, out_stride, &got, hipStream));
+        return got;
+    }
+    int64_t resampleVectorPCM16(const int16_t *d_data, int64_t n, int64_t stride, float *d_out, int64_t out_stride, void *hipStream)
+    {
+        int64_t got = 0;
+        check(syldet_sinc_resample_device_s16(r_, d_data, n, stride, d_out, out_stride, &got, hipStream));
+        return got;
+    }
+    int64_t flushDevice(float *d_out, int64_t out_stride, void *hipStream)
+    {
+        int64_t got = 0;
+        check(syldet_sinc_resampler_flush_device(r_, d_out, out_stride, &got, hipStream));
+        return got;
+    }
+    void reset() { check(syldet_sinc_resampler_reset(r_)); }
+    int64_t countOutput(int64_t n) const { return syldet_sinc_resampler_count(r_, n); }
+    int64_t countFlush() const { return syldet_sinc_resampler_flush_count(r_); }
+    int64_t samplesIn() const { int64_t n = 0; check(syldet_sinc_resampler_position(r_, &n, nullptr, nullptr)); return n; }
+    int64_t samplesOut() const { int64_t m = 0; check(syldet_sinc_resampler_position(r_, nullptr, &m, nullptr)); return m; }
+    bool finished() const { int32_t f = 0; check(syldet_sinc_resampler_position(r_, nullptr, nullptr, &f)); return f != 0; }
+
+private:
+    syldet_sinc_resampler_t *r_ = nullptr;
+    int channels_;
+};
+
 }  // namespace syldetxx

@@ -11,11 +11,11 @@ from .config import (InvalidValue, MismatchedLength, MissingValue, NeuralNet, Ne
                      createWindow, frequencyIndexRange)
 from .bank import PinnedArray, ShardedSyllableDetectorBank, shard_table
 from .detector import SyllableDetector, configsCompatible, configsShareClock, fusedFormOfConfig
-from .resampler import ResamplerLinear, convertRate, deinterleave, sincCoefficient, sincDefaults, sincTaps
+from .resampler import ResamplerLinear, ResamplerSinc, sincReady, convertRate, deinterleave, sincCoefficient, sincDefaults, sincTaps
 
 __all__ = ["SyllableDetector", "SyllableDetectorConfig", "NeuralNet", "NeuralNetLayer", "ProcessingFunction",
            "ParseError", "UnableToOpenPath", "MissingValue", "InvalidValue", "MismatchedLength",
            "SyllableDetectorError", "frequencyIndexRange", "createWindow", "ResamplerLinear", "deinterleave",
-           "convertRate", "sincCoefficient", "sincTaps", "sincDefaults",
+           "convertRate", "ResamplerSinc", "sincReady", "sincCoefficient", "sincTaps", "sincDefaults",
            "ShardedSyllableDetectorBank", "PinnedArray", "shard_table", "configsCompatible",
            "configsShareClock", "fusedFormOfConfig"]

@@ -192,6 +192,18 @@ SIGNATURES = {
                                                   C.c_void_p, C.c_int64, c_int64_p, C.c_void_p]),
     "syldet_convert_rate_sinc_device_s16": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_double, C.c_double, C.c_int32, C.c_double, C.c_double,
                                                       C.c_void_p, C.c_int64, c_int64_p, C.c_void_p]),
+    "syldet_sinc_ready": (C.c_int64, [C.c_int64, C.c_double, C.c_double, C.c_int32, C.c_double]),
+    "syldet_sinc_resampler_create": (C.c_int, [C.c_double, C.c_double, C.c_int32, C.c_int32, C.c_int32, C.c_double, C.c_double, C.POINTER(Handle)]),
+    "syldet_sinc_resampler_destroy": (C.c_int, [Handle]),
+    "syldet_sinc_resampler_reset": (C.c_int, [Handle]),
+    "syldet_sinc_resampler_position": (C.c_int, [Handle, c_int64_p, c_int64_p, c_int32_p]),
+    "syldet_sinc_resampler_count": (C.c_int64, [Handle, C.c_int64]),
+    "syldet_sinc_resampler_flush_count": (C.c_int64, [Handle]),
+    "syldet_sinc_resample_device": (C.c_int, [Handle, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_int64, c_int64_p, C.c_void_p]),
+    "syldet_sinc_resample_device_s16": (C.c_int, [Handle, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_int64, c_int64_p, C.c_void_p]),
+    "syldet_sinc_resampler_flush_device": (C.c_int, [Handle, C.c_void_p, C.c_int64, c_int64_p, C.c_void_p]),
+    "syldet_sinc_resample": (C.c_int, [Handle, c_float_p, C.c_int64, C.c_int64, c_float_p, C.c_int64, c_int64_p]),
+    "syldet_sinc_resampler_flush": (C.c_int, [Handle, c_float_p, C.c_int64, c_int64_p]),
     "syldet_resample": (C.c_int, [Handle, c_float_p, C.c_int64, C.c_int64, c_float_p, C.c_int64, c_int64_p]),
     "syldet_host_alloc": (C.c_int, [C.c_size_t, c_void_pp]),
     "syldet_host_free": (C.c_int, [C.c_void_p]),

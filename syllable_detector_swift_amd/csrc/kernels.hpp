@@ -304,6 +304,17 @@ inline int sinc_table_entries(int Z) { return Z <= 32 ? 16384 : 32768; }
 hipError_t launch_convert_rate_sinc(const float *in, int64_t n_in, int64_t in_stride, float *out, int64_t n_out,
                                     int64_t out_stride, int C, double rate_in, double rate_out, double H, float scale,
                                     const float *table, int N, hipStream_t stream);
+// the streaming form: the outputs m0 .. m0 + n_emit - 1 of a stream of n_before samples so far into out[C][out_stride], read from
+// hist [C][L] (the last min(n_before, L) samples, fp32) and the pushed rows in [C][in_stride] of n_in samples (a flush: n_in = 0,
+// in unused); then, when n_in > 0, the next history into next [C][L] (another buffer).  At most two kernels.  sinc_stream.hpp
+hipError_t launch_sinc_stream_push(const float *hist, float *next, int64_t L, const float *in, int64_t n_in, int64_t in_stride,
+                                   int64_t n_before, float *out, int64_t out_stride, int64_t m0, int64_t n_emit, int C,
+                                   double rate_in, double rate_out, double H, float scale, const float *table, int N,
+                                   hipStream_t stream);
+hipError_t launch_sinc_stream_push_s16(const float *hist, float *next, int64_t L, const int16_t *in, int64_t n_in, int64_t in_stride,
+                                       int64_t n_before, float *out, int64_t out_stride, int64_t m0, int64_t n_emit, int C,
+                                       double rate_in, double rate_out, double H, float scale, const float *table, int N,
+                                       hipStream_t stream);
 hipError_t launch_convert_rate_sinc_s16(const int16_t *in, int64_t n_in, int64_t in_stride, float *out, int64_t n_out,
                                         int64_t out_stride, int C, double rate_in, double rate_out, double H, float scale,
                                         const float *table, int N, hipStream_t stream);

@@ -3,6 +3,8 @@
 // AVAssetReaderTrackOutput at SyllableDetectorCLI/TrackDetector.swift:35):
 //   convert_rate_sinc_kernel<float>     fp32 rows in, fp32 rows out
 //   convert_rate_sinc_kernel<int16_t>   16-bit PCM rows in (x means float(x) * 2^-15), the same arithmetic on the same floats
+//   convert_rate_sinc_stream_kernel<T>  the same outputs block by block (ResamplerSinc): what was kept plus what just arrived
+//   sinc_carry_kernel<T>                what the next block's outputs still need of both
 //
 // A workgroup owns kSincBlockOut consecutive outputs of one row.  It copies the unit filter g (sinc(tau) * kaiser(tau / Z) at
 // kSincTable(Z) + 1 equally spaced points of [0, Z], built by the host in fp64) into LDS once, then walks the inputs its outputs
@@ -17,6 +19,7 @@
 // gfx950 only.  wave = 64.  Compiled with -ffp-contract=off (see the Makefile): the two forms share their bits by construction.
 
 #include "kernels.hpp"
+#include "sinc_stream.hpp"
 
 namespace sd {
 
@@ -26,14 +29,42 @@ template <typename T> __device__ __forceinline__ float sinc_sample(T v);
 template <> __device__ __forceinline__ float sinc_sample<float>(float v) { return v; }
 template <> __device__ __forceinline__ float sinc_sample<int16_t>(int16_t v) { return (float)v * (1.0f / 32768.0f); }
 
+// Both kernels' dynamic LDS: the table g [N + 4] (g[N] = 0: sinc(Z) = 0, then zeros), then the staged samples xs [kSincStage].
+extern __shared__ __attribute__((aligned(16))) unsigned char sinc_smem[];
+
+// What the LDS allows, told to the compiler: 80 KB a workgroup of four waves is two waves a SIMD, 144 KB one.  Without it the
+// scheduler guards an occupancy of six that the LDS never grants and, to save registers, leaves some of the unrolled tap loops
+// waiting for each table read in turn instead of keeping four in flight -- which ones changes with unrelated edits (3.5 ms a loop
+// at 64 channels x 2^24 samples; MEASUREMENTS.md, "The streaming band-limited resampler").
+#define SINC_WAVES_PER_SIMD __attribute__((amdgpu_waves_per_eu(1, 2)))
+
+// The taps k = ka .. ka + n - 1 of one output, k ascending, added to its running sum a: xs[x0] is staged sample ka, m =
+// floor(p) - ka, f = float(p - floor(p)).  Both kernels' arithmetic is this function: their bits are the same by construction.
+// (It names the LDS itself instead of taking pointers, so that the compiler sees LDS accesses when it shapes the loop.)
+__device__ __forceinline__ float sinc_taps(int N, int x0, int n, int m, float f, float idx_scale, float n_f, float a)
+{
+    const float *g = reinterpret_cast<const float *>(sinc_smem);
+    const float *x = g + (N + 4) + x0;
+#pragma unroll 4                                             // (the shape the loop had inside the kernel: four taps and a remainder)
+    for (int q = 0; q < n; q++, m--) {
+        const float t = (float)m + f;
+        const float u = fminf(fabsf(t) * idx_scale, n_f);
+        const int j = (int)u;                                // 0 .. N; g[N + 1] is a zero
+        const float w = u - (float)j;
+        const float g0 = g[j], g1 = g[j + 1];
+        const float c = g0 + w * (g1 - g0);
+        a = a + x[q] * c;
+    }
+    return a;
+}
+
 template <typename T>
-__global__ void __launch_bounds__(256)
+__global__ void __launch_bounds__(256) SINC_WAVES_PER_SIMD
 convert_rate_sinc_kernel(const T *__restrict__ in, int64_t n_in, int64_t in_stride, float *__restrict__ out, int64_t n_out,
                          int64_t out_stride, double rate_in, double rate_out, double H, float scale, float idx_scale,
                          const float *__restrict__ table, int N)
 {
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    float *g = reinterpret_cast<float *>(smem);              // [N + 4]: g[N] = 0 (sinc(Z) = 0), then zeros
+    float *g = reinterpret_cast<float *>(sinc_smem);         // [N + 4]
     float *xs = g + (N + 4);                                 // [kSincStage]
     const int tid = threadIdx.x;
     const T *row = in + (int64_t)blockIdx.y * in_stride;
@@ -72,21 +103,8 @@ convert_rate_sinc_kernel(const T *__restrict__ in, int64_t n_in, int64_t in_stri
         for (int r = 0; r < kSincPerThread; r++) {
             const int64_t ka = max(k_lo[r], base), kb = min(k_hi[r], end);
             if (ka > kb) continue;
-            const int n = (int)(kb - ka) + 1;
-            int m = (int)(pf[r] - ka);                       // |m| <= H + 1 < 2^17
-            const float *x = xs + (int)(ka - base);
-            const float f = frac[r];
-            float a = acc[r];
-            for (int q = 0; q < n; q++, m--) {
-                const float t = (float)m + f;
-                const float u = fminf(fabsf(t) * idx_scale, n_f);
-                const int j = (int)u;                        // 0 .. N; g[N + 1] is a zero
-                const float w = u - (float)j;
-                const float g0 = g[j], g1 = g[j + 1];
-                const float c = g0 + w * (g1 - g0);
-                a = a + x[q] * c;
-            }
-            acc[r] = a;
+            // |floor(p) - ka| <= H + 1 < 2^17
+            acc[r] = sinc_taps(N, (int)(ka - base), (int)(kb - ka) + 1, (int)(pf[r] - ka), frac[r], idx_scale, n_f, acc[r]);
         }
     }
 #pragma unroll
@@ -94,6 +112,111 @@ convert_rate_sinc_kernel(const T *__restrict__ in, int64_t n_in, int64_t in_stri
         const int64_t i = i0 + tid + (int64_t)r * 256;
         if (i <= i_last) dst[i] = scale * acc[r];
     }
+}
+
+// The streaming form (the streaming sinc convention of include/syldet.h): the outputs m0 .. m0 + n_emit - 1 of a stream that had
+// n_before samples before this push, written to out[0 .. n_emit).  Inputs are addressed absolutely: sample k < n_before comes
+// from the handle's history row (fp32, the last min(n_before, L) samples), sample k >= n_before from the pushed row; the row ends
+// at n_end (n_before + the push's length; a flush: n_before, and `in` is never read).  sinc_stream.hpp holds the addressing.
+template <typename T>
+__global__ void __launch_bounds__(256) SINC_WAVES_PER_SIMD
+convert_rate_sinc_stream_kernel(const float *__restrict__ hist, int64_t L, const T *__restrict__ in, int64_t in_stride,
+                                int64_t n_before, int64_t n_end, float *__restrict__ out, int64_t out_stride, int64_t m0,
+                                int64_t n_emit, double rate_in, double rate_out, double H, float scale, float idx_scale,
+                                const float *__restrict__ table, int N)
+{
+    float *g = reinterpret_cast<float *>(sinc_smem);         // [N + 4]
+    float *xs = g + (N + 4);                                 // [kSincStage]
+    const int tid = threadIdx.x;
+    const float *hrow = hist + (int64_t)blockIdx.y * L;
+    const T *row = in + (int64_t)blockIdx.y * in_stride;
+    float *dst = out + (int64_t)blockIdx.y * out_stride;
+    const int64_t i0 = m0 + (int64_t)blockIdx.x * kSincBlockOut;
+    const int64_t i_last = min(i0 + (int64_t)kSincBlockOut, m0 + n_emit) - 1;            // >= i0: the grid covers n_emit exactly
+
+    for (int e = tid; e < (N + 4) / 4; e += 256)
+        reinterpret_cast<float4 *>(g)[e] = reinterpret_cast<const float4 *>(table)[e];
+
+    int64_t pf[kSincPerThread], k_lo[kSincPerThread], k_hi[kSincPerThread];
+    float frac[kSincPerThread], acc[kSincPerThread];
+#pragma unroll
+    for (int r = 0; r < kSincPerThread; r++) {
+        const int64_t i = i0 + tid + (int64_t)r * 256;
+        const double p = (double)i * rate_in / rate_out;
+        const double fl = floor(p);
+        pf[r] = (int64_t)fl;
+        frac[r] = (float)(p - fl);
+        k_lo[r] = max((int64_t)ceil(p - H), (int64_t)0);
+        k_hi[r] = i <= i_last ? min((int64_t)floor(p + H), n_end - 1) : (int64_t)-1;
+        acc[r] = 0.0f;
+    }
+    const int64_t lo = sinc_stream_stage_lo(i0, n_before, L, rate_in, rate_out, H);      // never before the history's first sample
+    const int64_t hi = sinc_stream_stage_hi(i_last, n_end, rate_in, rate_out, H);
+    const float n_f = (float)N;
+
+    for (int64_t base = lo; base <= hi; base += kSincStage) {
+        __syncthreads();
+        const int64_t end = min(base + kSincStage - 1, hi);  // hist_first <= base <= end <= n_end - 1
+        for (int e = tid; e <= (int)(end - base); e += 256) {
+            const int64_t k = base + e;
+            xs[e] = sinc_stream_in_history(k, n_before) ? hrow[sinc_stream_hist_offset(k, n_before, L)]
+                                                        : sinc_sample<T>(row[sinc_stream_push_offset(k, n_before)]);
+        }
+        __syncthreads();
+#pragma unroll
+        for (int r = 0; r < kSincPerThread; r++) {
+            const int64_t ka = max(k_lo[r], base), kb = min(k_hi[r], end);
+            if (ka > kb) continue;
+            acc[r] = sinc_taps(N, (int)(ka - base), (int)(kb - ka) + 1, (int)(pf[r] - ka), frac[r], idx_scale, n_f, acc[r]);
+        }
+    }
+#pragma unroll
+    for (int r = 0; r < kSincPerThread; r++) {
+        const int64_t i = i0 + tid + (int64_t)r * 256;
+        if (i <= i_last) dst[i - m0] = scale * acc[r];
+    }
+}
+
+// The next history, into the OTHER buffer (the kernel above reads the current one in the same push): the last min(n_before + n, L)
+// samples of history ++ push, the push widened as it is kept.
+template <typename T>
+__global__ void __launch_bounds__(256)
+sinc_carry_kernel(const float *__restrict__ hist, float *__restrict__ next, int64_t L, const T *__restrict__ in, int64_t in_stride,
+                  int64_t n_before, int64_t n)
+{
+    const int64_t j = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (j >= sinc_stream_hist_len(n_before + n, L)) return;
+    const int64_t k = sinc_stream_carry_sample(j, n_before, n, L);                       // hist_first(n_before) <= k < n_before + n
+    const float v = sinc_stream_in_history(k, n_before)
+                        ? hist[(int64_t)blockIdx.y * L + sinc_stream_hist_offset(k, n_before, L)]
+                        : sinc_sample<T>(in[(int64_t)blockIdx.y * in_stride + sinc_stream_push_offset(k, n_before)]);
+    next[(int64_t)blockIdx.y * L + j] = v;
+}
+
+template <typename T>
+hipError_t launch_sinc_stream(const float *hist, float *next, int64_t L, const T *in, int64_t n_in, int64_t in_stride,
+                              int64_t n_before, float *out, int64_t out_stride, int64_t m0, int64_t n_emit, int C, double rate_in,
+                              double rate_out, double H, float scale, const float *table, int N, hipStream_t stream)
+{
+    if (C <= 0) return hipSuccess;
+    if (n_emit > 0) {
+        auto kern = convert_rate_sinc_stream_kernel<T>;
+        const int lds = (N + 4 + kSincStage) * (int)sizeof(float);
+        hipError_t st = hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+        if (st != hipSuccess) return st;
+        dim3 grid((unsigned)((n_emit + kSincBlockOut - 1) / kSincBlockOut), (unsigned)C);
+        hipLaunchKernelGGL(kern, grid, dim3(256), (size_t)lds, stream, hist, L, in, in_stride, n_before, n_before + n_in, out,
+                           out_stride, m0, n_emit, rate_in, rate_out, H, scale, (float)((double)N / H), table, N);
+        st = hipGetLastError();
+        if (st != hipSuccess) return st;
+    }
+    if (n_in > 0) {
+        const int64_t len = sinc_stream_hist_len(n_before + n_in, L);
+        dim3 grid((unsigned)((len + 255) / 256), (unsigned)C);
+        hipLaunchKernelGGL(sinc_carry_kernel<T>, grid, dim3(256), 0, stream, hist, next, L, in, in_stride, n_before, n_in);
+        return hipGetLastError();
+    }
+    return hipSuccess;
 }
 
 template <typename T>
@@ -126,6 +249,24 @@ hipError_t launch_convert_rate_sinc_s16(const int16_t *in, int64_t n_in, int64_t
                                         const float *table, int N, hipStream_t stream)
 {
     return launch_sinc<int16_t>(in, n_in, in_stride, out, n_out, out_stride, C, rate_in, rate_out, H, scale, table, N, stream);
+}
+
+hipError_t launch_sinc_stream_push(const float *hist, float *next, int64_t L, const float *in, int64_t n_in, int64_t in_stride,
+                                   int64_t n_before, float *out, int64_t out_stride, int64_t m0, int64_t n_emit, int C,
+                                   double rate_in, double rate_out, double H, float scale, const float *table, int N,
+                                   hipStream_t stream)
+{
+    return launch_sinc_stream<float>(hist, next, L, in, n_in, in_stride, n_before, out, out_stride, m0, n_emit, C, rate_in, rate_out,
+                                     H, scale, table, N, stream);
+}
+
+hipError_t launch_sinc_stream_push_s16(const float *hist, float *next, int64_t L, const int16_t *in, int64_t n_in, int64_t in_stride,
+                                       int64_t n_before, float *out, int64_t out_stride, int64_t m0, int64_t n_emit, int C,
+                                       double rate_in, double rate_out, double H, float scale, const float *table, int N,
+                                       hipStream_t stream)
+{
+    return launch_sinc_stream<int16_t>(hist, next, L, in, n_in, in_stride, n_before, out, out_stride, m0, n_emit, C, rate_in, rate_out,
+                                       H, scale, table, N, stream);
 }
 
 }  // namespace sd

@@ -2,7 +2,8 @@
 // device, and the stand-alone de-interleave entry point.  The resampling state that depends only on
 // sizes (`offset`) lives on the host and is advanced with the reference's own fp32 operations; the
 // per-channel carry (`last`) lives on the device next to the data.  The two stateless whole-recording converters are here too:
-// the linear one and the band-limited one (a Kaiser-windowed sinc: its design, its fp64 coefficient and its table cache).
+// the linear one and the band-limited one (a Kaiser-windowed sinc: its design, its fp64 coefficient and its table cache) -- and
+// the band-limited one's streaming form, ResamplerSinc: the same outputs block by block (sinc_stream.hpp holds its arithmetic).
 
 #include <hip/hip_runtime.h>
 
@@ -15,6 +16,7 @@
 #include <vector>
 
 #include "kernels.hpp"
+#include "sinc_stream.hpp"
 #include "syldet_internal.hpp"
 
 using namespace sd;
@@ -206,6 +208,20 @@ int sinc_design(double rate_in, double rate_out, int32_t Z, double beta, double 
     return SYLDET_OK;
 }
 
+// The unit filter's table on the host: g[j] = sinc(j Z / N) * kaiser(j / N) for j < N = sinc_table_entries(Z), zeros from g[N] on
+// (N + 4 floats).  The one place its values are made: the cache below and every streaming handle copy these floats.
+std::vector<float> sinc_table_values(int Z, double beta)
+{
+    const int N = sinc_table_entries(Z);
+    std::vector<float> g((size_t)N + 4, 0.0f);
+    const double i0b = bessel_i0(beta);
+    for (int j = 0; j < N; j++) {
+        const double u = (double)j / (double)N;
+        g[(size_t)j] = (float)(sinc_pi(u * (double)Z) * bessel_i0(beta * std::sqrt(1.0 - u * u)) / i0b);
+    }
+    return g;
+}
+
 // The unit filter's table on the device, one per (device, Z, beta), made on the first call that needs it (a blocking copy) and
 // kept for the life of the process; at most kSincTables of them, the oldest given up once a new one is in place.  The caller
 // holds g_sinc_mutex from the lookup to the end of its launch: hipFree waits for the work already queued, so a table is never
@@ -223,12 +239,7 @@ int sinc_table(int Z, double beta, const float **out, int *entries)
     *entries = N;
     for (const SincTable &t : g_sinc_tables)
         if (t.device == device && t.Z == Z && t.beta == beta) { *out = t.d; return SYLDET_OK; }
-    std::vector<float> g((size_t)N + 4, 0.0f);
-    const double i0b = bessel_i0(beta);
-    for (int j = 0; j < N; j++) {
-        const double u = (double)j / (double)N;
-        g[(size_t)j] = (float)(sinc_pi(u * (double)Z) * bessel_i0(beta * std::sqrt(1.0 - u * u)) / i0b);
-    }
+    const std::vector<float> g = sinc_table_values(Z, beta);
     float *d = nullptr;
     SYLDET_HIP(hipMalloc((void **)&d, g.size() * sizeof(float)));
     hipError_t e = hipMemcpy(d, g.data(), g.size() * sizeof(float), hipMemcpyHostToDevice);
@@ -274,7 +285,264 @@ int convert_rate_sinc(const T *d_in, int64_t n_in, int64_t in_stride, int32_t n_
 
 }  // namespace
 
+// ---- the streaming form (the streaming sinc convention of include/syldet.h) ----
+struct syldet_sinc_resampler {
+    double rate_in = 0, rate_out = 0, beta = 0, rho = 0, s = 0, H = 0;
+    int Z = 0, channels = 0, device = 0;
+    int64_t L = 0;                   // the history's capacity a channel: ceil(2 H) + 2
+    int64_t n_in_total = 0;          // N
+    int64_t n_out_total = 0;         // M = ready(N) until the flush
+    bool finished = false;
+    float *d_table = nullptr;        // the handle's own copy of the unit filter's table
+    int entries = 0;
+    float *d_hist[2] = {nullptr, nullptr};     // [channels][L] each: the kernels of a push read one and write the other
+    int cur = 0;
+    float *d_in = nullptr, *d_out = nullptr;   // staging of the host-pointer entry points
+    size_t in_cap = 0, out_cap = 0;
+    hipStream_t stream = nullptr;
+};
+
+namespace {
+
+// The statuses of a push, in their order, and the number of outputs it emits; nothing is touched.
+int sinc_push_check(const syldet_sinc_resampler *r, bool have_in, int64_t n_in, int64_t in_stride, bool have_out, int64_t out_stride,
+                    int64_t *emit)
+{
+    *emit = 0;
+    if (n_in < 0) return fail(SYLDET_ERR_INVALID_ARGUMENT, "n_in must be >= 0");
+    if (r->finished) return fail(SYLDET_ERR_INVALID_ARGUMENT, "the stream is finished (flushed): reset it before the next push");
+    if (n_in == 0) return SYLDET_OK;
+    if (n_in > ((int64_t)1 << 62) - r->n_in_total) return fail(SYLDET_ERR_INVALID_ARGUMENT, "more than 2^62 samples in one stream");
+    if (!have_in) return fail(SYLDET_ERR_INVALID_ARGUMENT, "NULL buffer");
+    const int64_t n = sinc_stream_ready(r->n_in_total + n_in, r->rate_in, r->rate_out, r->H) - r->n_out_total;
+    if (n > 0 && !have_out) return fail(SYLDET_ERR_INVALID_ARGUMENT, "NULL buffer");
+    if (r->channels > 1 && (in_stride < n_in || (n > 0 && out_stride < n)))
+        return fail(SYLDET_ERR_INVALID_ARGUMENT, "row strides must cover the rows");
+    *emit = n;
+    return SYLDET_OK;
+}
+
+int sinc_flush_check(const syldet_sinc_resampler *r, bool have_out, int64_t out_stride, int64_t *emit)
+{
+    *emit = 0;
+    if (r->finished) return SYLDET_OK;                       // a second flush emits nothing
+    const int64_t n = syldet_convert_rate_count(r->n_in_total, r->rate_in, r->rate_out) - r->n_out_total;
+    if (n > 0 && !have_out) return fail(SYLDET_ERR_INVALID_ARGUMENT, "NULL buffer");
+    if (r->channels > 1 && n > 0 && out_stride < n) return fail(SYLDET_ERR_INVALID_ARGUMENT, "row strides must cover the rows");
+    *emit = n > 0 ? n : 0;
+    return SYLDET_OK;
+}
+
+template <typename T>
+int sinc_push_device(syldet_sinc_resampler *r, const T *d_in, int64_t n_in, int64_t in_stride, float *d_out, int64_t out_stride,
+                     int64_t *n_out, void *hip_stream)
+{
+    if (!r) return fail(SYLDET_ERR_INVALID_ARGUMENT, "NULL handle");
+    if (n_out) *n_out = 0;
+    int64_t emit = 0;
+    if (int st = sinc_push_check(r, d_in != nullptr, n_in, in_stride, d_out != nullptr, out_stride, &emit)) return st;
+    if (n_in == 0) return SYLDET_OK;
+    // host arithmetic is done; from here on only launches (no allocation, no copy, no wait)
+    SYLDET_HIP(hipSetDevice(r->device));
+    const float *hist = r->d_hist[r->cur];
+    float *next = r->d_hist[r->cur ^ 1];
+    if constexpr (sizeof(T) == 2)
+        SYLDET_HIP(launch_sinc_stream_push_s16(hist, next, r->L, d_in, n_in, in_stride, r->n_in_total, d_out, out_stride, r->n_out_total,
+                                               emit, r->channels, r->rate_in, r->rate_out, r->H, (float)r->s, r->d_table, r->entries,
+                                               (hipStream_t)hip_stream));
+    else
+        SYLDET_HIP(launch_sinc_stream_push(hist, next, r->L, d_in, n_in, in_stride, r->n_in_total, d_out, out_stride, r->n_out_total,
+                                           emit, r->channels, r->rate_in, r->rate_out, r->H, (float)r->s, r->d_table, r->entries,
+                                           (hipStream_t)hip_stream));
+    r->cur ^= 1;
+    r->n_in_total += n_in;
+    r->n_out_total += emit;
+    if (n_out) *n_out = emit;
+    return SYLDET_OK;
+}
+
+// the host-pointer entry points' staging rows: [channels][n] each, grown as needed
+int sinc_stage(syldet_sinc_resampler *r, int64_t n_in, int64_t n_out)
+{
+    const size_t C = (size_t)r->channels, ib = C * (size_t)n_in * sizeof(float), ob = C * (size_t)n_out * sizeof(float);
+    if (ib > r->in_cap) {
+        if (r->d_in) (void)hipFree(r->d_in);
+        r->d_in = nullptr; r->in_cap = 0;
+        SYLDET_HIP(hipMalloc((void **)&r->d_in, ib));
+        r->in_cap = ib;
+    }
+    if (ob > r->out_cap) {
+        if (r->d_out) (void)hipFree(r->d_out);
+        r->d_out = nullptr; r->out_cap = 0;
+        SYLDET_HIP(hipMalloc((void **)&r->d_out, ob));
+        r->out_cap = ob;
+    }
+    return SYLDET_OK;
+}
+
+}  // namespace
+
 extern "C" {
+
+int64_t syldet_sinc_ready(int64_t n_in_total, double rate_in, double rate_out, int32_t zero_crossings, double rolloff)
+{
+    double s = 0.0, H = 0.0;
+    if (sinc_design(rate_in, rate_out, zero_crossings, 0.0, rolloff, &s, &H)) return -1;
+    return sinc_stream_ready(n_in_total, rate_in, rate_out, H);
+}
+
+int syldet_sinc_resampler_create(double rate_in, double rate_out, int32_t n_channels, int32_t device, int32_t zero_crossings,
+                                 double beta, double rolloff, syldet_sinc_resampler_t **out)
+{
+    if (!out) return fail(SYLDET_ERR_INVALID_ARGUMENT, "NULL argument");
+    *out = nullptr;
+    if (n_channels <= 0 || n_channels > 65535) return fail(SYLDET_ERR_INVALID_ARGUMENT, "n_channels must be in [1, 65535]");
+    double s = 0.0, H = 0.0;
+    if (int st = sinc_design(rate_in, rate_out, zero_crossings, beta, rolloff, &s, &H)) return st;
+    int n_dev = 0;
+    hipError_t e = hipGetDeviceCount(&n_dev);
+    if (e != hipSuccess || n_dev <= 0)
+        return fail(SYLDET_ERR_NO_DEVICE, std::string("no HIP device: ") + (e != hipSuccess ? hipGetErrorString(e) : "count is 0"));
+    if (device < 0 || device >= n_dev) return fail(SYLDET_ERR_NO_DEVICE, "device index out of range");
+    std::unique_ptr<syldet_sinc_resampler> r(new (std::nothrow) syldet_sinc_resampler());
+    if (!r) return fail(SYLDET_ERR_OUT_OF_MEMORY, "out of memory");
+    r->rate_in = rate_in; r->rate_out = rate_out; r->beta = beta; r->rho = rolloff; r->s = s; r->H = H;
+    r->Z = zero_crossings; r->channels = n_channels; r->device = device;
+    r->L = sinc_stream_history(H);
+    r->entries = sinc_table_entries(zero_crossings);
+    auto bring_up = [&]() -> int {
+        SYLDET_HIP(hipSetDevice(device));
+        const std::vector<float> g = sinc_table_values(zero_crossings, beta);
+        SYLDET_HIP(hipMalloc((void **)&r->d_table, g.size() * sizeof(float)));
+        SYLDET_HIP(hipMemcpy(r->d_table, g.data(), g.size() * sizeof(float), hipMemcpyHostToDevice));
+        const size_t hb = (size_t)n_channels * (size_t)r->L * sizeof(float);
+        for (int b = 0; b < 2; b++) {
+            SYLDET_HIP(hipMalloc((void **)&r->d_hist[b], hb));
+            SYLDET_HIP(hipMemset(r->d_hist[b], 0, hb));
+        }
+        SYLDET_HIP(hipStreamCreateWithFlags(&r->stream, hipStreamNonBlocking));
+        SYLDET_HIP(hipDeviceSynchronize());                  // the table and the zeros are in place before any stream reads them
+        return SYLDET_OK;
+    };
+    if (int st = bring_up()) {
+        syldet_sinc_resampler_destroy(r.release());
+        return st;
+    }
+    *out = r.release();
+    return SYLDET_OK;
+}
+
+int syldet_sinc_resampler_destroy(syldet_sinc_resampler_t *r)
+{
+    if (!r) return SYLDET_OK;
+    (void)hipSetDevice(r->device);
+    if (r->stream) { (void)hipStreamSynchronize(r->stream); (void)hipStreamDestroy(r->stream); }
+    if (r->d_table) (void)hipFree(r->d_table);               // (hipFree waits for the work already queued)
+    for (int b = 0; b < 2; b++)
+        if (r->d_hist[b]) (void)hipFree(r->d_hist[b]);
+    if (r->d_in) (void)hipFree(r->d_in);
+    if (r->d_out) (void)hipFree(r->d_out);
+    delete r;
+    return SYLDET_OK;
+}
+
+int syldet_sinc_resampler_reset(syldet_sinc_resampler_t *r)
+{
+    if (!r) return fail(SYLDET_ERR_INVALID_ARGUMENT, "NULL handle");
+    r->n_in_total = 0; r->n_out_total = 0; r->finished = false;      // (an empty history: nothing of the buffers is read)
+    return SYLDET_OK;
+}
+
+int syldet_sinc_resampler_position(const syldet_sinc_resampler_t *r, int64_t *n_in_total, int64_t *n_out_total, int32_t *finished)
+{
+    if (!r) return fail(SYLDET_ERR_INVALID_ARGUMENT, "NULL handle");
+    if (n_in_total) *n_in_total = r->n_in_total;
+    if (n_out_total) *n_out_total = r->n_out_total;
+    if (finished) *finished = r->finished ? 1 : 0;
+    return SYLDET_OK;
+}
+
+int64_t syldet_sinc_resampler_count(const syldet_sinc_resampler_t *r, int64_t n_in)
+{
+    if (!r || n_in <= 0 || r->finished || n_in > ((int64_t)1 << 62) - r->n_in_total) return 0;
+    return sinc_stream_ready(r->n_in_total + n_in, r->rate_in, r->rate_out, r->H) - r->n_out_total;
+}
+
+int64_t syldet_sinc_resampler_flush_count(const syldet_sinc_resampler_t *r)
+{
+    if (!r || r->finished) return 0;
+    const int64_t n = syldet_convert_rate_count(r->n_in_total, r->rate_in, r->rate_out) - r->n_out_total;
+    return n > 0 ? n : 0;
+}
+
+int syldet_sinc_resample_device(syldet_sinc_resampler_t *r, const float *d_in, int64_t n_in, int64_t in_stride, float *d_out,
+                                int64_t out_stride, int64_t *n_out, void *hip_stream)
+{
+    return sinc_push_device<float>(r, d_in, n_in, in_stride, d_out, out_stride, n_out, hip_stream);
+}
+
+int syldet_sinc_resample_device_s16(syldet_sinc_resampler_t *r, const int16_t *d_in, int64_t n_in, int64_t in_stride, float *d_out,
+                                    int64_t out_stride, int64_t *n_out, void *hip_stream)
+{
+    return sinc_push_device<int16_t>(r, d_in, n_in, in_stride, d_out, out_stride, n_out, hip_stream);
+}
+
+int syldet_sinc_resampler_flush_device(syldet_sinc_resampler_t *r, float *d_out, int64_t out_stride, int64_t *n_out, void *hip_stream)
+{
+    if (!r) return fail(SYLDET_ERR_INVALID_ARGUMENT, "NULL handle");
+    if (n_out) *n_out = 0;
+    int64_t emit = 0;
+    if (int st = sinc_flush_check(r, d_out != nullptr, out_stride, &emit)) return st;
+    if (emit > 0) {
+        SYLDET_HIP(hipSetDevice(r->device));
+        // the row ends at N: no pushed rows, no carry
+        SYLDET_HIP(launch_sinc_stream_push(r->d_hist[r->cur], r->d_hist[r->cur ^ 1], r->L, nullptr, 0, 0, r->n_in_total, d_out, out_stride,
+                                           r->n_out_total, emit, r->channels, r->rate_in, r->rate_out, r->H, (float)r->s, r->d_table,
+                                           r->entries, (hipStream_t)hip_stream));
+    }
+    r->n_out_total += emit;
+    r->finished = true;
+    if (n_out) *n_out = emit;
+    return SYLDET_OK;
+}
+
+int syldet_sinc_resample(syldet_sinc_resampler_t *r, const float *in, int64_t n_in, int64_t in_stride, float *out, int64_t out_stride,
+                         int64_t *n_out)
+{
+    if (!r) return fail(SYLDET_ERR_INVALID_ARGUMENT, "NULL handle");
+    if (n_out) *n_out = 0;
+    int64_t emit = 0;
+    if (int st = sinc_push_check(r, in != nullptr, n_in, in_stride, out != nullptr, out_stride, &emit)) return st;
+    if (n_in == 0) return SYLDET_OK;
+    SYLDET_HIP(hipSetDevice(r->device));
+    if (int st = sinc_stage(r, n_in, emit)) return st;
+    const size_t C = (size_t)r->channels;
+    SYLDET_HIP(hipMemcpy2DAsync(r->d_in, (size_t)n_in * sizeof(float), in, (size_t)(C > 1 ? in_stride : n_in) * sizeof(float),
+                                (size_t)n_in * sizeof(float), C, hipMemcpyHostToDevice, r->stream));
+    if (int st = sinc_push_device<float>(r, r->d_in, n_in, n_in, r->d_out, emit, n_out, r->stream)) return st;
+    if (emit > 0)
+        SYLDET_HIP(hipMemcpy2DAsync(out, (size_t)(C > 1 ? out_stride : emit) * sizeof(float), r->d_out, (size_t)emit * sizeof(float),
+                                    (size_t)emit * sizeof(float), C, hipMemcpyDeviceToHost, r->stream));
+    SYLDET_HIP(hipStreamSynchronize(r->stream));
+    return SYLDET_OK;
+}
+
+int syldet_sinc_resampler_flush(syldet_sinc_resampler_t *r, float *out, int64_t out_stride, int64_t *n_out)
+{
+    if (!r) return fail(SYLDET_ERR_INVALID_ARGUMENT, "NULL handle");
+    if (n_out) *n_out = 0;
+    int64_t emit = 0;
+    if (int st = sinc_flush_check(r, out != nullptr, out_stride, &emit)) return st;
+    SYLDET_HIP(hipSetDevice(r->device));
+    if (int st = sinc_stage(r, 0, emit)) return st;
+    if (int st = syldet_sinc_resampler_flush_device(r, r->d_out, emit, n_out, r->stream)) return st;
+    const size_t C = (size_t)r->channels;
+    if (emit > 0)
+        SYLDET_HIP(hipMemcpy2DAsync(out, (size_t)(C > 1 ? out_stride : emit) * sizeof(float), r->d_out, (size_t)emit * sizeof(float),
+                                    (size_t)emit * sizeof(float), C, hipMemcpyDeviceToHost, r->stream));
+    SYLDET_HIP(hipStreamSynchronize(r->stream));
+    return SYLDET_OK;
+}
 
 void syldet_sinc_defaults(int32_t *zero_crossings, double *beta, double *rolloff)
 {
