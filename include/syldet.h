@@ -801,6 +801,82 @@ int syldet_sinc_resample(syldet_sinc_resampler_t *r, const float *in, int64_t n_
                          int64_t out_stride, int64_t *n_out);
 int syldet_sinc_resampler_flush(syldet_sinc_resampler_t *r, float *out, int64_t out_stride, int64_t *n_out);
 
+/* ---- packed recordings: many recordings of different lengths through one bank ----
+ * The reference's tool opens one file after another and runs each file's tracks alone (SyllableDetectorCLI/main.swift:63-130).
+ * A run's results do not depend on where it starts as long as the start is a multiple of hop (evaluation e reads samples
+ * [e hop, (e + T - 1) hop + gap + W) of its row), so recordings laid end to end in a bank's rows, each from a multiple of hop, go
+ * through syldet_run_device* unchanged: recording k at row offset o_k has its evaluation e at row evaluation o_k / hop + e, with
+ * the values it would have had alone -- bit for bit on the fold kernel, the generic engine and the 1024-point kernel; the
+ * pass-scaled fused kernels and the wide engine keep their 1e-5 (1e-2) contract, not bit identity (their scale is per pass).
+ * Row evaluations outside every [first_eval, first_eval + n_evals) straddle two recordings or a pad and mean nothing.
+ * THE PLAN (host only, no device is touched), for K recordings of n_samples[k] samples on the C channels of h:
+ *   P_k       = ceil(n_k / hop) hop                        the padded length
+ *   n_evals_k = max(0, syldet_count_evals(h, n_k))
+ *   recordings are placed in order of P_k descending, ties by index ascending; each goes to the ELIGIBLE row with the least
+ *   samples placed so far (its fill), ties to the lowest row; slots[k].offset = that fill (a multiple of hop), and the row's fill
+ *   grows by P_k;  slots[k].first_eval = offset / hop;  slots[k].n_samples = n_k
+ *   *row_samples = the greatest fill, rounded up to a multiple of 8 (rows stay whole 4-byte words as int16 and 16-byte quads as fp32)
+ *   *row_evals   = max(0, syldet_count_evals(h, *row_samples)); first_eval + n_evals <= *row_evals for every recording that has an
+ *                  evaluation (one without may lie behind the row's last evaluation: nothing of it is ever read)
+ *   *fill        = sum n_k / (C *row_samples)   (0 where *row_samples is 0)
+ * Guarantee (greedy placement): *row_samples <= ceil(sum P_k / C) + max P_k + 7 where every row is eligible for every recording
+ * (with several networks: for each network's own rows and recordings).
+ * Eligibility: on a plain bank every row (network must be NULL or all zeros); on a syldet_create_multi / syldet_create_mixed bank
+ * recording k may only go to rows whose channel_net equals network[k] (network == NULL: SYLDET_ERR_INVALID_ARGUMENT; a network no
+ * row runs: SYLDET_ERR_UNSUPPORTED, syldet_last_error names it).  Zero-length recordings are legal (a slot without samples or
+ * evaluations).  SYLDET_ERR_INVALID_ARGUMENT: a NULL handle, n_recordings < 0, a NULL array with n_recordings > 0, a negative length
+ * or network.  slots, row_samples, row_evals and fill may each be NULL.  A sharded bank (syldet_sharded_t) has no packed form: no
+ * entry point takes one, and the language bindings answer SYLDET_ERR_UNSUPPORTED.
+ * THE HANDLE keeps the plan and its tables on the device of h (h must outlive it), so that the device calls are launches only:
+ * they do not allocate, synchronise or copy -- with one exception, stated here: the sources (src_offset, src_step: host arrays of
+ * K entries) are kept by the handle, and a load whose sources differ from the kept ones (the first load always) waits for the
+ * stream of the handle's last load and uploads them with one blocking copy first.  Loading again from the same layout -- the
+ * next batch of a tool that reuses its upload buffer, a measurement loop -- is one launch.
+ *   syldet_recordings_load_device*   sample i of recording k is d_src[src_offset[k] + i src_step[k]] (step 1: a planar recording;
+ *       step n: one track of an n-track file uploaded as its WAV stores it -- the call is also the de-interleave; src_step NULL:
+ *       all 1; steps >= 1, offsets >= 0).  Writes every element [0, row_samples) of every row of d_rows [C][channel_stride]: a
+ *       recording's sample, or +0 in the pads behind each recording and in the tail of shorter rows (junk evaluations read the
+ *       pads: anything non-finite there would send them through the exact recomputation); [row_samples, channel_stride) is left
+ *       untouched.  Any hop, any source offset, any step; 16-byte accesses where the rows are 16-byte aligned (base and stride)
+ *       and, for the reads, 16, 8 or 4 bytes an access where a recording is contiguous, as its source address allows -- one
+ *       element at a time elsewhere.  ("recordings_load_kernel")
+ *   syldet_recordings_events_device  d_outputs [C][row_evals][n_out] and d_flags [C][row_evals] as syldet_run_device* wrote them
+ *       for the packed rows -> for recording k exactly what syldet_detections_device gives on that recording's flags alone
+ *       (idx = first_index + e hop with e counted from the recording's first evaluation, debounce_until = -1 at its start):
+ *       d_indices [K][capacity], d_counts [K] (may exceed capacity), and d_values [K][capacity][n_out], the outputs of each
+ *       detection's evaluation.  d_outputs and d_values may be NULL together (indices only).  One wave a recording, the scan of
+ *       syldet_detections_device; row evaluations outside the recordings are never read.  ("recordings_events_kernel")
+ * Statuses of the device calls, before any device is touched: SYLDET_ERR_INVALID_ARGUMENT for a NULL handle or pointer (but
+ * the optional ones), channel_stride < row_samples, a negative offset, a step < 1, capacity < 0, d_outputs without d_values or
+ * the reverse.  The handle follows the bank's rule of one stream at a time.                                                   */
+typedef struct {
+    int32_t row;             /* the bank row the recording lies in */
+    int64_t offset;          /* its first sample in that row, a multiple of hop */
+    int64_t first_eval;      /* offset / hop: the row evaluation that is its evaluation 0 */
+    int64_t n_evals;
+    int64_t n_samples;
+} syldet_slot_t;
+typedef struct syldet_recordings syldet_recordings_t;
+int syldet_recordings_plan(const syldet_t *h, const int64_t *n_samples, const int32_t *network, int32_t n_recordings,
+                           syldet_slot_t *slots, int64_t *row_samples, int64_t *row_evals, double *fill);
+/* the same plan from the host alone, for a machine without a device: a bank of n_channels channels on cfg's evaluation clock (any
+ * of the bank's networks: they share it); channel_net as syldet_create_multi / syldet_create_mixed take it, NULL for a plain bank */
+int syldet_recordings_plan_of_config(const syldet_config_t *cfg, int32_t n_channels, const int32_t *channel_net, const int64_t *n_samples,
+                                     const int32_t *network, int32_t n_recordings, syldet_slot_t *slots, int64_t *row_samples,
+                                     int64_t *row_evals, double *fill);
+int syldet_recordings_create(const syldet_t *h, const int64_t *n_samples, const int32_t *network, int32_t n_recordings,
+                             syldet_recordings_t **out);
+int syldet_recordings_destroy(syldet_recordings_t *r);
+/* slots: n_recordings entries, in the caller's order */
+int syldet_recordings_slots(const syldet_recordings_t *r, syldet_slot_t *slots);
+int syldet_recordings_shape(const syldet_recordings_t *r, int32_t *n_recordings, int64_t *row_samples, int64_t *row_evals, double *fill);
+int syldet_recordings_load_device(syldet_recordings_t *r, const float *d_src, const int64_t *src_offset, const int32_t *src_step,
+                                  float *d_rows, int64_t channel_stride, void *hip_stream);
+int syldet_recordings_load_device_s16(syldet_recordings_t *r, const int16_t *d_src, const int64_t *src_offset, const int32_t *src_step,
+                                      int16_t *d_rows, int64_t channel_stride, void *hip_stream);
+int syldet_recordings_events_device(syldet_recordings_t *r, const float *d_outputs, const uint8_t *d_flags, double debounce_seconds,
+                                    int64_t *d_indices, float *d_values, int64_t capacity, int64_t *d_counts, void *hip_stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -78,6 +78,12 @@ class Geometry(C.Structure):
                 ("engine", C.c_int32)]
 
 
+class Slot(C.Structure):
+    """syldet_slot_t: where a recording lies in a bank's packed rows."""
+    _fields_ = [("row", C.c_int32), ("offset", C.c_int64), ("first_eval", C.c_int64), ("n_evals", C.c_int64),
+                ("n_samples", C.c_int64)]
+
+
 class Shard(C.Structure):
     _fields_ = [("device", C.c_int32), ("first_channel", C.c_int32), ("channels", C.c_int32),
                 ("part", C.c_int32), ("parts", C.c_int32)]
@@ -225,6 +231,17 @@ SIGNATURES = {
     "syldet_sharded_rccl_ranks": (C.c_int32, [Handle]),
     "syldet_sharded_connect": (C.c_int, [Handle]),
     "syldet_sharded_launcher_threads": (C.c_int32, [Handle]),
+    "syldet_recordings_plan": (C.c_int, [Handle, c_int64_p, c_int32_p, C.c_int32, C.POINTER(Slot), c_int64_p, c_int64_p, c_double_p]),
+    "syldet_recordings_plan_of_config": (C.c_int, [Config_p, C.c_int32, c_int32_p, c_int64_p, c_int32_p, C.c_int32, C.POINTER(Slot), c_int64_p, c_int64_p,
+                                                   c_double_p]),
+    "syldet_recordings_create": (C.c_int, [Handle, c_int64_p, c_int32_p, C.c_int32, C.POINTER(Handle)]),
+    "syldet_recordings_destroy": (C.c_int, [Handle]),
+    "syldet_recordings_slots": (C.c_int, [Handle, C.POINTER(Slot)]),
+    "syldet_recordings_shape": (C.c_int, [Handle, c_int32_p, c_int64_p, c_int64_p, c_double_p]),
+    "syldet_recordings_load_device": (C.c_int, [Handle, C.c_void_p, c_int64_p, c_int32_p, C.c_void_p, C.c_int64, C.c_void_p]),
+    "syldet_recordings_load_device_s16": (C.c_int, [Handle, C.c_void_p, c_int64_p, c_int32_p, C.c_void_p, C.c_int64, C.c_void_p]),
+    "syldet_recordings_events_device": (C.c_int, [Handle, C.c_void_p, C.c_void_p, C.c_double, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p,
+                                                  C.c_void_p]),
 }
 
 

@@ -50,6 +50,12 @@ class ShardedSyllableDetectorBank:
             _abi.lib.syldet_sharded_destroy(self._h)
             self._h = None
 
+    def recordings(self, lengths, networks=None):
+        """Packed recordings (SyllableDetector.recordings) have no sharded form: a recording's row would have to be cut across
+        devices at evaluations that belong to nobody."""
+        from .config import SyllableDetectorError
+        raise SyllableDetectorError(_abi.ERR_UNSUPPORTED, "packed recordings on a sharded bank: use a SyllableDetector per device")
+
     def __del__(self):
         try:
             self.close()

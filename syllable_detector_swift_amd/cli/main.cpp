@@ -40,7 +40,7 @@ constexpr int kExUsage = 64;   // EX_USAGE, main.swift:40
 void usage(FILE *to)
 {
     std::fprintf(to,
-                 "Usage: syllable-detector-cli -n <net> [-a <audio>]... [-d <seconds>] [--device <k>] [--chunk <frames>] [--format <shortest|swift4>] [--resample <linear|sinc>] [--resample-quality <Z,beta,rolloff>] [--simulate <out.wav>] [--simulate-output <k>] [--levels <out.tsv>] [--levels-buffer <L>] [--levels-period <seconds>] [--ttl <out.wav>] [--ttl-mux] [--ttl-width <seconds>] [--ttl-steps <n>] [--ttl-buffer <L>] [--ttl-latency <seconds>] [--ttl-onsets <out.tsv>] [--probe]\n"
+                 "Usage: syllable-detector-cli -n <net> [-a <audio>]... [-d <seconds>] [--device <k>] [--chunk <frames>] [--format <shortest|swift4>] [--resample <linear|sinc>] [--resample-quality <Z,beta,rolloff>] [--simulate <out.wav>] [--simulate-output <k>] [--levels <out.tsv>] [--levels-buffer <L>] [--levels-period <seconds>] [--ttl <out.wav>] [--ttl-mux] [--ttl-width <seconds>] [--ttl-steps <n>] [--ttl-buffer <L>] [--ttl-latency <seconds>] [--ttl-onsets <out.tsv>] [--batch] [--batch-rows <N>] [--batch-bytes <B>] [--probe]\n"
                  "  -n, --net <net>:\n      Path to trained network file.  Given k > 1 times: each file must have exactly k tracks, and track t runs network t (one mixed bank; the networks must share the sampling rate, window length, window overlap, time range and number of outputs).\n"
                  "  -a, --audio <audio>:\n      Path to the audio file to process.\n"
                  "  -d, --debounce <seconds>:\n      Number of seconds to debounce triggers.\n"
@@ -61,6 +61,9 @@ void usage(FILE *to)
                  "      --ttl-buffer <L>:\n      Samples per input and output buffer: a power of two from 8 to 4096 (default 32).\n"
                  "      --ttl-latency <seconds>:\n      Delay of the output behind the input (default 0).\n"
                  "      --ttl-onsets <out.tsv>:\n      Also write the rising edges of the trigger tracks, one line each, tab separated: the track, the sample, the time in seconds.\n"
+                 "      --batch:\n      Run the audio files through one detector bank instead of one bank a file: every track of every file becomes a recording in the bank's rows, and only the detections come back from the GPU. The output is the same.\n"
+                 "      --batch-rows <N>:\n      Rows of the bank under --batch (default 64; no more than there are tracks).\n"
+                 "      --batch-bytes <B>:\n      Consecutive files share a batch until their samples pass B bytes (default 2147483648).\n"
                  "      --probe:\n      Only print what the audio files contain; does not touch the GPU.\n"
                  "The command line will write a comma-separated list of detection events (when the network has at least one output above threshold) to standard out. For example, it might output:\n"
                  "\n\t0,1593298,36.1292063492063,0.918557\n\n"
@@ -420,6 +423,201 @@ int process_file(const std::string &path, const std::vector<syldet_config_t *> &
     return write_files();
 }
 
+// --batch: the -a files through ONE bank instead of a bank a file (syldet_recordings_*: every track of every file of a batch is a
+// recording laid into the bank's rows; the reference's tool runs them one after another on one core, main.swift:63-130).  Only
+// the detections and their outputs come back from the device.  What is printed is what the loop over process_file prints.
+struct BatchOpt {
+    bool on = false;
+    long rows = 64;
+    long long bytes = 2ll << 30;
+};
+
+struct BatchFile {
+    std::string path;
+    wav::Info info;
+    std::vector<float> f32;                                 // the frames as decoded, or (a 16-bit file at the network's rate) ...
+    std::vector<int16_t> s16;                               // ... as stored
+    bool is16 = false;
+    size_t bytes() const { return is16 ? s16.size() * sizeof(int16_t) : f32.size() * sizeof(float); }
+};
+
+// One batch: returns 0, or 2 for device trouble (no line of the batch is printed then, but the files' names are)
+int run_batch(std::vector<BatchFile> &files, const std::vector<syldet_config_t *> &cfgs, int device, double debounce_s, int64_t chunk,
+              long max_rows, bool headers)
+{
+    if (files.empty()) return 0;
+    const syldet_config_t *cfg = cfgs[0];
+    bool all16 = true;
+    for (const BatchFile &f : files) all16 = all16 && f.is16;
+    std::vector<int64_t> lengths, src_offset;
+    std::vector<int32_t> network, src_step;
+    std::vector<int64_t> file_at(files.size());             // where a file's frames lie in the upload, in elements (whole 16 bytes)
+    int64_t total = 0;
+    for (size_t i = 0; i < files.size(); i++) {
+        BatchFile &f = files[i];
+        if (!all16 && f.is16) {                             // wav::read's value of a 16-bit sample
+            f.f32.resize(f.s16.size());
+            for (size_t j = 0; j < f.s16.size(); j++) f.f32[j] = (float)f.s16[j] * (1.0f / 32768.0f);
+            f.s16.clear();
+            f.is16 = false;
+        }
+        file_at[i] = total;
+        for (int t = 0; t < f.info.channels; t++) {
+            lengths.push_back(f.info.frames);
+            network.push_back(t);
+            src_offset.push_back(total + t);
+            src_step.push_back(f.info.channels);
+        }
+        total += (f.info.frames * f.info.channels + 7) / 8 * 8;
+    }
+    const int32_t K = (int32_t)lengths.size();
+    const int n_nets = (int)cfgs.size();
+    const int C = (int)std::max<long>(n_nets, std::min<long>(max_rows, K));
+    syldet_t *h = nullptr;
+    syldet_recordings_t *r = nullptr;
+    hipStream_t stream = nullptr;
+    std::vector<int32_t> row_net((size_t)C);
+    for (int c = 0; c < C; c++) row_net[(size_t)c] = c % n_nets;
+    std::vector<int64_t> idx, cnt((size_t)K, 0);
+    std::vector<float> val;
+    int64_t cap = 1;
+    int n_out = 0;
+    int rc = 0;
+    do {
+        if (int st = n_nets > 1 ? syldet_create_mixed(cfgs.data(), n_nets, row_net.data(), C, device, SYLDET_ENGINE_AUTO, &h)
+                                : syldet_create(cfg, C, device, SYLDET_ENGINE_AUTO, &h)) {
+            std::fprintf(stderr, "Unable to create the detector: %s: %s\n", syldet_strerror(st), syldet_last_error());
+            rc = 2;
+            break;
+        }
+        syldet_geometry_t g;
+        syldet_get_geometry(h, &g);
+        n_out = g.outputs;
+        int st = syldet_recordings_create(h, lengths.data(), n_nets > 1 ? network.data() : nullptr, K, &r);
+        int64_t row_samples = 0, row_evals = 0;
+        if (!st) st = syldet_recordings_shape(r, nullptr, &row_samples, &row_evals, nullptr);
+        if (st) {
+            std::fprintf(stderr, "Unable to plan the batch: %s: %s\n", syldet_strerror(st), syldet_last_error());
+            rc = 2;
+            break;
+        }
+        if (row_evals <= 0) break;                          // every file shorter than one evaluation: no events
+        if (hipSetDevice(device) != hipSuccess || hipStreamCreate(&stream) != hipSuccess) { rc = 2; break; }
+        const size_t el = all16 ? sizeof(int16_t) : sizeof(float);
+        DevBuf d_src, d_rows, d_out, d_flags, d_idx, d_val, d_cnt;
+        if (!d_src.alloc((size_t)total * el) || !d_rows.alloc((size_t)C * row_samples * el) || !d_out.alloc((size_t)C * row_evals * n_out * sizeof(float)) ||
+            !d_flags.alloc((size_t)C * row_evals) || !d_cnt.alloc((size_t)K * sizeof(int64_t))) { rc = 2; break; }
+        bool ok = true;
+        for (size_t i = 0; ok && i < files.size(); i++) {
+            const BatchFile &f = files[i];
+            ok = hipMemcpyAsync((char *)d_src.p + (size_t)file_at[i] * el, all16 ? (const void *)f.s16.data() : (const void *)f.f32.data(), f.bytes(),
+                                hipMemcpyHostToDevice, stream) == hipSuccess;
+        }
+        if (!ok) { rc = 2; break; }
+        if (all16) {
+            st = syldet_recordings_load_device_s16(r, (const int16_t *)d_src.p, src_offset.data(), src_step.data(), (int16_t *)d_rows.p, row_samples, stream);
+            if (!st) st = syldet_run_device_s16(h, (const int16_t *)d_rows.p, row_samples, row_samples, (float *)d_out.p, (uint8_t *)d_flags.p, stream);
+        } else {
+            st = syldet_recordings_load_device(r, (const float *)d_src.p, src_offset.data(), src_step.data(), (float *)d_rows.p, row_samples, stream);
+            if (!st) st = syldet_run_device(h, (const float *)d_rows.p, row_samples, row_samples, (float *)d_out.p, (uint8_t *)d_flags.p, stream);
+        }
+        // the counts first (a scan of the flags), then the detections themselves into tables of the size they need
+        if (!st) st = syldet_recordings_events_device(r, nullptr, (const uint8_t *)d_flags.p, debounce_s, nullptr, nullptr, 0, (int64_t *)d_cnt.p, stream);
+        if (st) {
+            std::fprintf(stderr, "Unable to process the batch: %s: %s\n", syldet_strerror(st), syldet_last_error());
+            rc = 2;
+            break;
+        }
+        if (hipMemcpyAsync(cnt.data(), d_cnt.p, cnt.size() * sizeof(int64_t), hipMemcpyDeviceToHost, stream) != hipSuccess ||
+            hipStreamSynchronize(stream) != hipSuccess) { rc = 2; break; }
+        cap = std::max<int64_t>(1, *std::max_element(cnt.begin(), cnt.end()));
+        idx.resize((size_t)K * (size_t)cap);
+        val.resize((size_t)K * (size_t)cap * (size_t)n_out);
+        if (!d_idx.alloc(idx.size() * sizeof(int64_t)) || !d_val.alloc(val.size() * sizeof(float))) { rc = 2; break; }
+        st = syldet_recordings_events_device(r, (const float *)d_out.p, (const uint8_t *)d_flags.p, debounce_s, (int64_t *)d_idx.p, (float *)d_val.p, cap,
+                                             (int64_t *)d_cnt.p, stream);
+        if (st) {
+            std::fprintf(stderr, "Unable to process the batch: %s: %s\n", syldet_strerror(st), syldet_last_error());
+            rc = 2;
+            break;
+        }
+        if (hipMemcpyAsync(idx.data(), d_idx.p, idx.size() * sizeof(int64_t), hipMemcpyDeviceToHost, stream) != hipSuccess ||
+            hipMemcpyAsync(val.data(), d_val.p, val.size() * sizeof(float), hipMemcpyDeviceToHost, stream) != hipSuccess ||
+            hipStreamSynchronize(stream) != hipSuccess) { rc = 2; break; }
+    } while (false);
+    if (rc == 2 && hipPeekAtLastError() != hipSuccess) std::fprintf(stderr, "Unable to process the batch: %s\n", hipGetErrorString(hipGetLastError()));
+    if (stream) (void)hipStreamDestroy(stream);
+    syldet_recordings_destroy(r);
+    syldet_destroy(h);
+    // file by file, the lines process_file prints: the tracks' events interleaved buffer by buffer (main.swift:126-130)
+    int32_t k0 = 0;
+    for (const BatchFile &f : files) {
+        if (headers) std::printf("%s\n", f.path.c_str());  // main.swift:122-124
+        std::vector<Event> events;
+        for (int c = 0; !rc && c < f.info.channels; c++)
+            for (int64_t i = 0; i < cnt[(size_t)(k0 + c)]; i++) {
+                const int64_t smp = idx[(size_t)(k0 + c) * (size_t)cap + (size_t)i];
+                events.push_back({chunk > 0 ? (smp - 1) / chunk : 0, c, smp, i});
+            }
+        std::stable_sort(events.begin(), events.end(), [](const Event &a, const Event &b) {
+            if (a.buffer != b.buffer) return a.buffer < b.buffer;
+            if (a.channel != b.channel) return a.channel < b.channel;
+            return a.sample < b.sample;
+        });
+        for (const Event &ev : events) {
+            std::string line = std::to_string(ev.channel) + "," + std::to_string(ev.sample) + "," + number((double)ev.sample / cfg->sampling_rate);
+            for (int o = 0; o < n_out; o++) line += "," + number(val[((size_t)(k0 + ev.channel) * (size_t)cap + (size_t)ev.eval) * n_out + o]);
+            std::puts(line.c_str());
+        }
+        std::fflush(stdout);
+        k0 += f.info.channels;
+    }
+    files.clear();
+    return rc;
+}
+
+// The loop over the -a files under --batch: consecutive files that can share a bank (readable, at the network's rate, the right
+// number of tracks) gather until their samples pass opt.bytes; any other file ends the batch and is processed alone in its place.
+int process_batched(const std::vector<std::string> &audio, const std::vector<syldet_config_t *> &cfgs, int device, double debounce_s, bool have_debounce,
+                    int64_t chunk, const BatchOpt &opt, const ResampleOpt &conv)
+{
+    int rc = 0;
+    const bool headers = audio.size() > 1;
+    const double deb = have_debounce ? debounce_s : 0.0;
+    std::vector<BatchFile> files;
+    size_t held = 0;
+    auto flush = [&]() {
+        if (run_batch(files, cfgs, device, deb, chunk, opt.rows, headers) == 2) rc = 2;
+        held = 0;
+    };
+    for (const std::string &p : audio) {
+        BatchFile f;
+        f.path = p;
+        std::string err;
+        const bool probed = wav::probe(p, f.info, err);
+        if (probed && f.info.rate == cfgs[0]->sampling_rate && f.info.channels > 0 && f.info.frames > 0 &&
+            (cfgs.size() == 1 || (size_t)f.info.channels == cfgs.size())) {
+            f.is16 = f.info.format == 1 && f.info.bits == 16;
+            err.clear();
+            if (f.is16 ? wav::read_s16(p, f.info, f.s16, err) : wav::read(p, f.info, f.f32, err)) {
+                held += f.bytes();
+                files.push_back(std::move(f));
+                if ((long long)held >= opt.bytes) flush();
+                continue;
+            }
+        }
+        // another rate, unreadable, no tracks, the wrong number of tracks: exactly as without --batch, in its place
+        flush();
+        if (headers) std::printf("%s\n", p.c_str());
+        std::fflush(stdout);
+        const int r = process_file(p, cfgs, device, debounce_s, have_debounce, chunk, std::string(), 0, LevelsOpt(), TtlOpt(), conv);
+        if (r == 2) rc = 2;
+        else if (r == 3 && rc == 0) rc = 1;
+    }
+    flush();
+    return rc;
+}
+
 }  // namespace
 
 int main(int argc, char **argv)
@@ -440,6 +638,8 @@ int main(int argc, char **argv)
     bool have_ttl = false, have_ttl_onsets = false, have_ttl_option = false, have_ttl_width = false, have_ttl_steps = false;
     int device = 0;
     int64_t chunk = 8192;
+    BatchOpt batch;
+    bool have_batch_option = false;
     auto value = [&](int &i, const char *name) -> const char * {
         if (i + 1 >= argc) {
             std::fprintf(stderr, "Missing value for %s.\n", name);
@@ -460,6 +660,21 @@ int main(int argc, char **argv)
         } else if (a == "--device") device = std::atoi(value(i, "--device"));
         else if (a == "--chunk") chunk = std::atoll(value(i, "--chunk"));
         else if (a == "--probe") probe = true;
+        else if (a == "--batch") batch.on = true;
+        else if (a == "--batch-rows" || a == "--batch-bytes") {
+            const bool rows = a == "--batch-rows";
+            const char *v = value(i, a.c_str());
+            char *end = nullptr;
+            const long long k = std::strtoll(v, &end, 10);
+            if (end == v || *end != 0 || k < 1 || (rows && k > 65535)) {
+                std::fprintf(stderr, rows ? "--batch-rows takes a number of rows from 1 to 65535.\n" : "--batch-bytes takes a number of bytes, 1 or more.\n");
+                usage(stdout);
+                return kExUsage;
+            }
+            if (rows) batch.rows = (long)k;
+            else batch.bytes = k;
+            have_batch_option = true;
+        }
         else if (a == "--resample") {
             const std::string m = value(i, "--resample");
             if (m != "linear" && m != "sinc") {
@@ -645,6 +860,16 @@ int main(int argc, char **argv)
         usage(stdout);
         return kExUsage;
     }
+    if (have_batch_option && !batch.on) {
+        std::fprintf(stderr, "--batch-rows and --batch-bytes need --batch.\n");
+        usage(stdout);
+        return kExUsage;
+    }
+    if (batch.on && (have_simulate || have_levels || have_ttl || have_ttl_onsets)) {   // those take exactly one file and a bank of its own
+        std::fprintf(stderr, "--batch runs many files through one bank; --simulate, --levels, --ttl and --ttl-onsets take exactly one file: give one or the other.\n");
+        usage(stdout);
+        return kExUsage;
+    }
     std::vector<syldet_config_t *> cfgs;
     for (const std::string &n : net) {
         syldet_config_t *cfg = nullptr;
@@ -674,6 +899,11 @@ int main(int argc, char **argv)
             usage(stdout);
             return kExUsage;
         }
+    }
+    if (batch.on) {
+        const int brc = process_batched(audio, cfgs, device, debounce, have_debounce, chunk, batch, conv);
+        for (syldet_config_t *c : cfgs) syldet_config_free(c);
+        return brc;
     }
     int rc = 0;
     for (const std::string &p : audio) {

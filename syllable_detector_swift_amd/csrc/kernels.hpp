@@ -377,6 +377,33 @@ hipError_t launch_levels_fold(const void *scratch, bool s16, int C, int64_t n_sa
 hipError_t launch_levels_out(const float *outputs, int64_t n_evals, int n_out, int k, int C, int64_t n_samples, int L, int64_t P,
                              int64_t need, int64_t hop, int T, float *levels, hipStream_t stream);
 
+// ---- packed recordings (kernels_recordings.hip; syldet_recordings_* of include/syldet.h) ----
+// One slot of the plan as the load kernel reads it: the table is sorted by (row, offset), row c's slots are
+// [row_begin[c], row_begin[c + 1]).  Sample i of the slot is src[src_offset + i src_step].
+struct RecSlotDev {
+    int64_t offset, n_samples, src_offset;
+    int32_t src_step, pad;
+};
+// ... and as the events kernel reads it, in the caller's order of recordings
+struct RecEventDev {
+    int64_t first_eval, n_evals;
+    int32_t row, pad;
+};
+constexpr int kRecTile = 8192;               // samples of a row one workgroup of recordings_load_kernel writes
+struct RecLoadDesc {
+    const RecSlotDev *slots;
+    const int32_t *row_begin;                // [C + 1]
+    const int32_t *tile_first;               // [C][tiles]: the last slot of the row that starts at or before the tile (row_begin[c + 1]: none)
+    int tiles;                               // ceil(row_samples / kRecTile)
+    int64_t row_samples;                     // a multiple of 8
+};
+// rows [C][stride] (the first row_samples of each) <- the recordings' samples and +0 everywhere else; fp32 or (s16) int16
+hipError_t launch_recordings_load(const RecLoadDesc &d, const void *src, bool s16, void *rows, int64_t stride, int C, hipStream_t stream);
+// indices [K][capacity], values [K][capacity][n_out] (or null), counts [K] <- flags [C][row_evals], outputs [C][row_evals][n_out] (or null)
+hipError_t launch_recordings_events(const RecEventDev *desc, int K, int64_t row_evals, int n_out, const float *outputs, const uint8_t *flags,
+                                    int64_t first_index, int64_t hop, int64_t debounce_frames, int64_t *indices, float *values,
+                                    int64_t capacity, int64_t *counts, hipStream_t stream);
+
 // detection flags <-> bits (bit b of byte t of a row = flag 8 t + b), rows padded to whole bytes
 hipError_t launch_pack_flags(const uint8_t *flags, int64_t rows, int64_t row_len, uint8_t *bits, hipStream_t stream);
 hipError_t launch_unpack_flags(const uint8_t *bits, int64_t rows, int64_t row_len, uint8_t *flags, hipStream_t stream);

@@ -11,6 +11,7 @@
 //
 // gfx950 only: wave = 64 lanes, 256-thread workgroups.
 
+#include "detections_scan.hpp"
 #include "generic_eval.hpp"
 
 namespace sd {
@@ -709,23 +710,9 @@ detections_kernel(const uint8_t *__restrict__ flags, int64_t E, int64_t first_in
     const int lane = threadIdx.x;
     const uint8_t *fl = flags + (int64_t)c * E;
     int64_t *out = indices ? indices + (int64_t)c * capacity : nullptr;
-    int64_t until = -1;      // debounceUntil :30
-    int64_t n = 0;
-    for (int64_t e0 = 0; e0 < E; e0 += kWave) {
-        const int64_t e = e0 + lane;
-        const bool set = e < E && fl[e] != 0;
-        const int64_t idx = first_index + e * hop;               // curOutput :67-68
-        unsigned long long mask = __ballot(set && until < idx);  // hasDetection && debounceUntil < curOutput :80
-        while (mask) {
-            const int l = __ffsll((long long)mask) - 1;
-            const int64_t hit = first_index + (e0 + l) * hop;
-            if (lane == 0 && out && n < capacity) out[n] = hit;
-            n++;
-            until = hit + debounce_frames;                       // :99
-            const unsigned long long later = (l == 63) ? 0ull : (~0ull << (l + 1));
-            mask = __ballot(set && until < idx) & later;
-        }
-    }
+    const int64_t n = debounce_scan(fl, E, first_index, hop, debounce_frames, lane, [&](int64_t i, int64_t, int64_t hit) {
+        if (lane == 0 && out && i < capacity) out[i] = hit;
+    });
     if (lane == 0 && counts) counts[c] = n;
 }
 

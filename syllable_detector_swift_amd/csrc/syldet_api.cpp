@@ -231,6 +231,7 @@ struct syldet {
     // channels' streaming state, the stream and the profile.
     std::vector<std::unique_ptr<syldet, int (*)(syldet_t *)>> classes;
     std::vector<int> class_of, local_of;   // [C] a channel's class, and its index among that class's channels
+    std::vector<int> bank_net;             // [C] the caller's channel_net (what syldet_recordings_plan's eligibility reads: sd::bank_info)
     // ... and in a class handle: its channels' bank rows, ascending, and the bank it belongs to (what the timers record into)
     std::vector<int> rows;
     DeviceBuffer d_row_of;            // [channels] int: rows
@@ -1251,6 +1252,12 @@ int choose_engine(syldet *h, int engine)
 
 }  // namespace
 
+void sd::bank_info(const syldet_t *h, sd::BankInfo *out)
+{
+    *out = sd::BankInfo{h->channels, h->device, h->cfg.view.sampling_rate, h->cfg.view.window_length, h->cfg.view.time_range, h->geom,
+                        !h->classes.empty() ? h->bank_net.data() : h->net_of.empty() ? nullptr : h->net_of.data()};
+}
+
 extern "C" {
 
 int syldet_create(const syldet_config_t *cfg, int32_t n_channels, int32_t device, int32_t engine, syldet_t **out)
@@ -1592,6 +1599,7 @@ int syldet_create_mixed(const syldet_config_t *const *cfgs, int32_t n_nets, cons
         }
         h->class_of = std::move(class_of);
         h->local_of = std::move(local_of);
+        h->bank_net.assign(channel_net, channel_net + n_channels);
         for (int32_t c = 0; c < n_channels; c++) {
             const syldet_config_t *v = cfgs[channel_net[c]];
             h->chan_thr0.push_back(v->thresholds[0]);

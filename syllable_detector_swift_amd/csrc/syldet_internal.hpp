@@ -42,4 +42,15 @@ float sum_squares_tree(const int16_t *x, int64_t n, int64_t step);
 // is L a buffer length the level meters take (a power of two in [8, 4096])?
 inline bool levels_buffer_ok(int64_t L) { return L >= 8 && L <= 4096 && (L & (L - 1)) == 0; }
 
+// What the host-side files beside syldet_api.cpp need of a handle (syldet_recordings.cpp): channel_net is the caller's table of
+// syldet_create_multi / syldet_create_mixed ([channels], the handle's own memory), NULL on a plain bank.
+struct BankInfo {
+    int channels, device;
+    double sampling_rate;
+    int window_length, time_range;
+    syldet_geometry_t geom;
+    const int *channel_net;
+};
+void bank_info(const syldet_t *h, BankInfo *out);
+
 }  // namespace sd

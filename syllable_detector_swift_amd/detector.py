@@ -798,6 +798,60 @@ class SyllableDetector:
         check(_abi.lib.syldet_last_fused_form(self._h, C.byref(kernel), params))
         return int(kernel.value), tuple(int(v) for v in params)
 
+    # ---- packed recordings: many recordings of different lengths through this bank ---------
+    def planRecordings(self, lengths, networks=None):
+        """syldet_recordings_plan, host only: (slots, rowSamples, rowEvaluations, fill) for recordings of these lengths (and, on a
+        multi / mixed bank, these networks) -- slots as a list of (row, offset, first_eval, n_evals, n_samples)."""
+        n, net = _recording_args(lengths, networks)
+        slots = (_abi.Slot * max(1, n.size))()
+        rs, re_, fill = C.c_int64(), C.c_int64(), C.c_double()
+        check(_abi.lib.syldet_recordings_plan(self._h, n.ctypes.data_as(_abi.c_int64_p), None if net is None else net.ctypes.data_as(_abi.c_int32_p),
+                                              n.size, slots, C.byref(rs), C.byref(re_), C.byref(fill)))
+        return [_slot_tuple(slots[k]) for k in range(n.size)], rs.value, re_.value, fill.value
+
+    def recordings(self, lengths, networks=None) -> "Recordings":
+        """The plan with its tables on the device (syldet_recordings_create): lay recordings of these lengths end to end in the
+        bank's rows with load(), run the rows through run() / runPCM16(), take each recording's results out with view() and
+        events()."""
+        return Recordings(self, lengths, networks)
+
+    def runRecordings(self, arrays, debounce: float = 0.0, networks=None):
+        """Recordings of any lengths in one pass: one upload, load, run / runPCM16, events and one download.  `arrays`: 1-D
+        (mono) or [frames, tracks] numpy arrays, all float32 or all int16 (16-bit PCM); every track is a recording, in order
+        (`networks`, on a multi / mixed bank: one entry a track).  Returns, per recording, (indices int64 [n], values float32
+        [n, outputs]): its debounced detections and the outputs of their evaluations."""
+        torch = _torch()
+        arrays = [np.asarray(a) for a in arrays]
+        dtypes = {a.dtype for a in arrays}
+        if arrays and dtypes not in ({np.dtype(np.float32)}, {np.dtype(np.int16)}):
+            raise ValueError("arrays must be all float32 or all int16")
+        s16 = bool(arrays) and arrays[0].dtype == np.int16
+        lengths, offsets, steps, pos = [], [], [], 0
+        for a in arrays:
+            if a.ndim not in (1, 2):
+                raise ValueError("each array is 1-D (mono) or [frames, tracks]")
+            tracks = 1 if a.ndim == 1 else a.shape[1]
+            for t in range(tracks):
+                lengths.append(a.shape[0])
+                offsets.append(pos + t)
+                steps.append(tracks)
+            pos += (a.size + 7) // 8 * 8                          # every file from a whole 16 bytes
+        flat = np.zeros(max(pos, 8), np.int16 if s16 else np.float32)
+        pos = 0
+        for a in arrays:
+            flat[pos:pos + a.size] = np.ascontiguousarray(a).reshape(-1)
+            pos += (a.size + 7) // 8 * 8
+        n_out = self.geometry.outputs
+        with self.recordings(lengths, networks) as rec:
+            if rec.rowEvaluations <= 0:
+                return [(np.zeros(0, np.int64), np.zeros((0, n_out), np.float32)) for _ in lengths]
+            rows = rec.load(torch.from_numpy(flat).to("cuda:%d" % self.device), offsets, steps)
+            out, fl = (self.runPCM16 if s16 else self.run)(rows)
+            idx, val, cnt = rec.events(out, fl, debounce)
+            torch.cuda.current_stream(self.device).synchronize()
+            idx, val, cnt = idx.cpu().numpy(), val.cpu().numpy(), cnt.cpu().numpy()
+        return [(idx[k, :cnt[k]].copy(), val[k, :cnt[k]].copy()) for k in range(len(lengths))]
+
     # ---- batch, host arrays -------------------------------------------------------
     def runHost(self, samples: np.ndarray, outputs: Optional[np.ndarray] = None, flags: Optional[np.ndarray] = None) -> Tuple[np.ndarray, np.ndarray]:
         """syldet_run: the batch call on host arrays, pipelined along time inside the library.  `outputs` / `flags`: arrays to
@@ -842,6 +896,132 @@ class SyllableDetector:
         check(_abi.lib.syldet_detections(self._h, f.ctypes.data_as(_abi.c_uint8_p), E, float(debounce),
                                          idx.ctypes.data_as(_abi.c_int64_p), cap, cnt.ctypes.data_as(_abi.c_int64_p)))
         return idx, cnt
+
+
+def _recording_args(lengths, networks):
+    n = np.ascontiguousarray(lengths, dtype=np.int64).reshape(-1)
+    net = None if networks is None else np.ascontiguousarray(networks, dtype=np.int32).reshape(-1)
+    if net is not None and net.size != n.size:
+        raise ValueError("one network per recording")
+    return n, net
+
+
+def _slot_tuple(s):
+    return (int(s.row), int(s.offset), int(s.first_eval), int(s.n_evals), int(s.n_samples))
+
+
+def planRecordings(config: SyllableDetectorConfig, channels: int, lengths, channelNetworks=None, networks=None):
+    """syldet_recordings_plan_of_config: the plan a bank of `channels` channels on config's evaluation clock makes for recordings
+    of these lengths -- from the host alone, no device needed.  channelNetworks: the bank's network per channel (multi / mixed
+    banks; None: a plain bank), networks: the network of each recording.  (slots, rowSamples, rowEvaluations, fill) as
+    SyllableDetector.planRecordings."""
+    n, net = _recording_args(lengths, networks)
+    cn = None if channelNetworks is None else np.ascontiguousarray(channelNetworks, dtype=np.int32).reshape(-1)
+    if cn is not None and cn.size != int(channels):
+        raise ValueError("one network per channel")
+    c, keep = config.to_abi()
+    slots = (_abi.Slot * max(1, n.size))()
+    rs, re_, fill = C.c_int64(), C.c_int64(), C.c_double()
+    check(_abi.lib.syldet_recordings_plan_of_config(C.byref(c), int(channels), None if cn is None else cn.ctypes.data_as(_abi.c_int32_p),
+                                                    n.ctypes.data_as(_abi.c_int64_p), None if net is None else net.ctypes.data_as(_abi.c_int32_p),
+                                                    n.size, slots, C.byref(rs), C.byref(re_), C.byref(fill)))
+    del keep
+    return [_slot_tuple(slots[k]) for k in range(n.size)], rs.value, re_.value, fill.value
+
+
+class Recordings:
+    """Recordings of different lengths laid end to end in the rows of one bank (syldet_recordings_*; the reference's tool runs
+    them one file after another, SyllableDetectorCLI/main.swift:63-130).  slots[k] = (row, offset, first_eval, n_evals,
+    n_samples) of recording k; rows are rowSamples long and yield rowEvaluations evaluations; fill is the share of the rows'
+    samples that are audio.  The detector must outlive it."""
+
+    def __init__(self, detector: SyllableDetector, lengths, networks=None):
+        self.detector = detector
+        n, net = _recording_args(lengths, networks)
+        self._h = _abi.Handle()
+        check(_abi.lib.syldet_recordings_create(detector._h, n.ctypes.data_as(_abi.c_int64_p),
+                                                None if net is None else net.ctypes.data_as(_abi.c_int32_p), n.size, C.byref(self._h)))
+        self.count = int(n.size)
+        slots = (_abi.Slot * max(1, self.count))()
+        check(_abi.lib.syldet_recordings_slots(self._h, slots))
+        self.slots = [_slot_tuple(slots[k]) for k in range(self.count)]
+        rs, re_, fill = C.c_int64(), C.c_int64(), C.c_double()
+        check(_abi.lib.syldet_recordings_shape(self._h, None, C.byref(rs), C.byref(re_), C.byref(fill)))
+        self.rowSamples, self.rowEvaluations, self.fill = rs.value, re_.value, fill.value
+
+    def close(self):
+        if getattr(self, "_h", None):
+            _abi.lib.syldet_recordings_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def load(self, src, offsets, steps=None, out=None, stream=None):
+        """The rows [C, rowSamples] from `src`, a 1-D float32 or int16 CUDA tensor: sample i of recording k is
+        src[offsets[k] + i * steps[k]] (steps None: all 1; step n takes one track of an n-track file as its WAV stores it);
+        everything else in the rows is +0.  `out`: rows to write into, [C, >= rowSamples] of src's dtype (what lies beyond
+        rowSamples is left alone).  Asynchronous on `stream`; the same offsets and steps again make it one launch."""
+        torch = _torch()
+        det = self.detector
+        if not (src.is_cuda and src.dim() == 1 and src.is_contiguous() and src.dtype in (torch.float32, torch.int16)
+                and src.device.index == det.device):
+            raise ValueError("src must be a contiguous 1-D float32 or int16 CUDA tensor on the detector's device")
+        off = np.ascontiguousarray(offsets, dtype=np.int64).reshape(-1)
+        stp = np.ones(self.count, np.int32) if steps is None else np.ascontiguousarray(steps, dtype=np.int32).reshape(-1)
+        if off.size != self.count or stp.size != self.count:
+            raise ValueError("one offset (and step) per recording")
+        n = np.array([s[4] for s in self.slots], np.int64)
+        if self.count and (off.min() < 0 or stp.min() < 1 or int((off + np.maximum(n - 1, 0) * stp)[n > 0].max(initial=-1)) >= src.numel()):
+            raise ValueError("a recording reaches outside src")
+        if out is None:
+            out = torch.empty((det.channels, self.rowSamples), dtype=src.dtype, device=src.device)
+        elif not (out.is_cuda and out.dtype == src.dtype and out.dim() == 2 and out.shape[0] == det.channels and out.shape[1] >= self.rowSamples
+                  and out.stride(1) == 1 and out.device == src.device):
+            raise ValueError("out must be [channels, >= rowSamples] of src's dtype on its device, rows contiguous")
+        fn = _abi.lib.syldet_recordings_load_device_s16 if src.dtype == torch.int16 else _abi.lib.syldet_recordings_load_device
+        stride = int(out.stride(0)) if det.channels > 1 else int(out.shape[1])
+        check(fn(self._h, src.data_ptr(), off.ctypes.data_as(_abi.c_int64_p), stp.ctypes.data_as(_abi.c_int32_p), out.data_ptr(), stride,
+                 det._stream_ptr(stream)))
+        return out
+
+    def view(self, tensor, k: int):
+        """The part of a [C, rowEvaluations, ...] result (outputs, flags) that belongs to recording k: [n_evals, ...], no copy."""
+        row, _, first, n_evals, _ = self.slots[k]
+        return tensor[row, first:first + n_evals]
+
+    def events(self, outputs, flags, debounce: float = 0.0, capacity: Optional[int] = None, stream=None):
+        """outputs [C, rowEvaluations, n_out] (or None), flags [C, rowEvaluations] as run() wrote them for the loaded rows ->
+        (indices [K, capacity] i64, values [K, capacity, n_out] f32 or None, counts [K] i64): each recording's detections as
+        detections() gives them on its flags alone -- sample numbers from the recording's start, debounce restarting with it --
+        and the outputs of each detection's evaluation.  counts may exceed capacity (default: the longest recording's
+        evaluations)."""
+        torch = _torch()
+        det = self.detector
+        E, n_out = self.rowEvaluations, det.geometry.outputs
+        if not (flags.is_cuda and flags.dtype == torch.uint8 and tuple(flags.shape) == (det.channels, E) and flags.is_contiguous()
+                and flags.device.index == det.device):
+            raise ValueError("flags must be a contiguous uint8 CUDA tensor [channels, rowEvaluations] on the detector's device")
+        if outputs is not None and not (outputs.is_cuda and outputs.dtype == torch.float32 and tuple(outputs.shape) == (det.channels, E, n_out)
+                                        and outputs.is_contiguous() and outputs.device == flags.device):
+            raise ValueError("outputs must be a contiguous float32 CUDA tensor [channels, rowEvaluations, outputs] on the flags' device")
+        cap = max([s[3] for s in self.slots], default=0) if capacity is None else int(capacity)
+        idx = torch.empty((self.count, max(cap, 1)), dtype=torch.int64, device=flags.device)
+        val = None if outputs is None else torch.empty((self.count, max(cap, 1), n_out), dtype=torch.float32, device=flags.device)
+        cnt = torch.zeros((self.count,), dtype=torch.int64, device=flags.device)
+        check(_abi.lib.syldet_recordings_events_device(self._h, None if outputs is None else outputs.data_ptr(), flags.data_ptr(), float(debounce),
+                                                       idx.data_ptr(), None if val is None else val.data_ptr(), cap, cnt.data_ptr(),
+                                                       det._stream_ptr(stream)))
+        return idx, val, cnt
 
 
 def _pcm16(data) -> np.ndarray:
