@@ -271,8 +271,9 @@ bool make_fused_plan(const syldet_config_t &c, const syldet_geometry_t &g, Fused
             // (HOP; hopk_schedule.hpp) -- eleven slots close the slot pattern with the period of four tiles.  They take no more
             // of the wave's share than the RC slots above (the rows of tap products move up behind them).
             d.s_hopk_rc = 0;
+            d.s_pairstep = 0;
             if (hop == hopk::kHop && W == hopk::kWindow && HQ == 1 && d.s_padp == 0 && s_waves == kFusedSBlock / 64 && RC >= hopk::kRing && fits(hopk::kRing))
-                d.s_hopk_rc = hopk::kRing;
+                d.s_hopk_rc = hopk::kRing, d.s_pairstep = 1;     // (... and keeps the two waves of a SIMD in step: pair_progress.hpp)
             const int K2 = W / 64, c0 = W / 2;
             // A operands, lane l: row l & 15 of its tile, k = 8 (l >> 4) + j -> folded position m = 32 ks + k.
             // s rows (real part): w[c0 + m] cos(2 pi k m / N), half of it at m = 0 (s[0] = 2 x[c0]);

@@ -224,10 +224,13 @@ struct FusedDesc {
     int force_classic;          // the handle was created under SYLDET_FUSED_CLASSIC=1: the 8-wave kernel where both take the shape
     int no_fold;                // the handle was created under SYLDET_FUSED_NOFOLD=1: not the symmetric-fold kernel
     int ko;                     // diagnostic build only: knock-out mask (SYLDET_FUSED_KO)
-    int s_hopk_rc;              // hop 132 under a 256-sample window, one quad of units, the plain ring: the slots of the ring whose schedule is compiled in
+    short s_hopk_rc;            // hop 132 under a 256-sample window, one quad of units, the plain ring: the slots of the ring whose schedule is compiled in
                                 // (kernels_fused_s.hip, HOP; hopk_schedule.hpp), or 0 -- the shape has no such form, or the handle was created under
                                 // SYLDET_FUSED_HOPK=0 (A/B runs).  The launcher's alone; it sits in the padding in front of `stamps`: the kernels' arguments stay where they were.
-    unsigned long long *stamps; // diagnostic build only: [workgroups][16] phase cycle sums, else null
+    short s_pairstep;           // the HOP form keeps the two waves of a SIMD in step (pair_progress.hpp): 1, or 0 -- the handle was created under
+                                // SYLDET_FUSED_PAIRSTEP=0 (A/B runs).  Read by the HOP instantiations alone.  It shares s_hopk_rc's word (there is no
+                                // padding left in front of `stamps`), so the kernels' arguments stay where they were.
+    unsigned long long *stamps; // diagnostic build only: [workgroups][16] phase cycle sums (the fold kernel: 16 sums, then a record a wave), else null
 };
 // What the fold kernel reads of ONE network, for multi-network handles (syldet_create_multi): everything else of FusedDesc is
 // the shape, which compatible networks share.  A workgroup reads nets[net_of[its channel]] once, before its tiles.

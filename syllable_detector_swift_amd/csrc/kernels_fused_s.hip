@@ -41,6 +41,7 @@
 
 #include "fused_common.hpp"
 #include "hopk_schedule.hpp"
+#include "pair_progress.hpp"
 
 namespace sd {
 
@@ -51,6 +52,7 @@ using namespace fused_dev;
 constexpr int kTile = kFusedSTileFrames;       // 16 frames per wave and tile
 
 typedef __attribute__((address_space(3))) void lds_void;
+typedef __attribute__((address_space(3))) unsigned lds_u32;
 
 // a * 1 - (the half `hi` or `lo` of h) in fp32: the remainder of a value behind its f16 rounding, exact
 __device__ __forceinline__ float rem_lo(float a, unsigned h)
@@ -159,6 +161,30 @@ __device__ __forceinline__ void hopk_issue(__amdgpu_buffer_rsrc_t in_rs, unsigne
 // value; all four lane groups hold the same statistics to the bit).  The arithmetic is the run-time form's, instruction for
 // instruction on the same values: outputs and flags are bit-identical (tests/test_hopk_gpu.py).  SYLDET_FUSED_HOPK=0 keeps
 // the run-time hop.
+// ... and the HOP form keeps the two waves of a SIMD IN STEP (pair_progress.hpp; MEASUREMENTS, "The fold kernel's pairs kept in
+// step").  Waves w and w ^ 4 of the workgroup share a SIMD, nothing in the kernel makes them wait for each other, and at equal
+// priority the SIMD's arbiter gives the older one its vector slots first, tile after tile: it retires early and the younger
+// finishes its segment alone, at a lone wave's rate, while half the SIMD's wave slots stand empty.  So each wave keeps ONE word
+// in the spare tail of its LDS share: it publishes the tile it is on, reads its partner's word with the tile's ring reads (the
+// wait that covers those covers it), and runs at s_setprio 1 while it is behind the partner, at s_setprio 0 otherwise -- whoever
+// has fallen behind wins the arbitration, and both retire within a tile or so.  Nothing waits: no barrier, no spin, no sleep.
+// A partner without a segment, one that has finished, or a word not yet written (the LDS is not zeroed at launch) can only
+// change which priority a wave runs at -- its speed, never what it computes or that it ends.  All 64 lanes store the same value
+// to the same address (no lane-masked branch); the priority is a uniform scalar branch around two s_setprio.  The words are
+// exchanged every tile and the priority is decided ONCE A PERIOD of four tiles (ph == 0).  Both frequencies were measured
+// (MEASUREMENTS; profiles/pairstep_ab.txt): decided every tile a pair ends within 1.7 tiles and the kernel gains 1.9 .. 2.2 % on
+// the parent's -- the priority changes hands every tile or two; decided once a period a pair ends within 2 .. 2.6 tiles and the
+// kernel gains 2.5 .. 3.1 %.  SYLDET_FUSED_PAIRSTEP=0 (FusedDesc::s_pairstep) turns it off with a uniform branch.
+#ifdef SYLDET_S_PAIR_GATED             // (diagnostic build: the words exchanged once a period too, not only the priority decided)
+constexpr bool kPairGated = true;
+#else
+constexpr bool kPairGated = false;
+#endif
+#ifdef SYLDET_S_PAIR_EVERY             // (diagnostic build: tools/variant_libs.sh kernels_fused_s.hip pairevery -DSYLDET_S_PAIR_EVERY)
+constexpr bool kPairEvery = true;
+#else
+constexpr bool kPairEvery = false;
+#endif
 template <int K2, bool GEN, int HQ, int NW, int PADP = 0, bool F2 = false, int NT = 1, bool SPECT = false, bool MN = false, bool S16 = false, int HOP = 0>
 __global__ void __launch_bounds__(64 * NW, 1)
 fused_s_kernel(const FusedDesc d, const float *__restrict__ samples, int64_t stride, int64_t s_eff, int64_t E,
@@ -182,6 +208,10 @@ fused_s_kernel(const FusedDesc d, const float *__restrict__ samples, int64_t str
     // this wave's segment of the channel
     const int64_t e_b = ((int64_t)blockIdx.x * kWaves + wave) * d.s_seg_evals;
     if (e_b >= E) return;
+#ifdef SYLDET_S_STAMPS                // (diagnostic build: where and when this wave ran -- the record it writes behind its last tile)
+    const unsigned long long st_rt_begin = __builtin_amdgcn_s_memrealtime();
+    const unsigned st_hw_id = __builtin_amdgcn_s_getreg(4 | (31 << 11)), st_xcc_id = __builtin_amdgcn_s_getreg(20 | (31 << 11));   // HW_ID, XCC_ID: all 32 bits
+#endif
     const int64_t e_e = (e_b + d.s_seg_evals < E) ? e_b + d.s_seg_evals : E;
     const int seg_len = (int)(e_e - e_b);
     const int tiles = (seg_len + (T - 1) + kTile - 1) / kTile;
@@ -200,6 +230,15 @@ fused_s_kernel(const FusedDesc d, const float *__restrict__ samples, int64_t str
     constexpr int kSub = PADP > 1 ? 256 / PADP : 1;   // padded pieces of a chunk of 256 floats
     constexpr int kChunkB = CS8 ? 1280 : 1024 + (PADP > 1 ? 16 * kSub : 0);
     auto sk = [](int i) { return PADP > 1 ? 4 * (i / (PADP > 1 ? PADP : 1)) : 0; };   // padding (floats) in front of position i of a frame / of the ring
+    // (HOP) the progress words of this wave and of the other wave on its SIMD (pair_progress.hpp); this wave's starts at tile 0
+    volatile lds_u32 *pp_mine = nullptr, *pp_peer = nullptr;
+    const bool pair_on = HOP != 0 && __builtin_amdgcn_readfirstlane((int)d.s_pairstep) != 0;     // (uniform: a scalar branch)
+    if constexpr (HOP != 0) {
+        static_assert(HOP == 0 || NW == pairp::kWaves, "the pairing is the eight-wave workgroup's");
+        pp_mine = (volatile lds_u32 *)(lds_void *)(smem + pairp::word_address(wave, d.s_lds_wave));
+        pp_peer = (volatile lds_u32 *)(lds_void *)(smem + pairp::word_address(pairp::partner_of(wave), d.s_lds_wave));
+        if (pair_on) *pp_mine = 0u;
+    }
     float *ring = reinterpret_cast<float *>(wbase);
     const int16_t *ring16 = reinterpret_cast<const int16_t *>(wbase);   // (S16)
     const int PS = d.s_pstride, TP = d.s_tp;          // floats per frame row: 4 TP tap products, sum of squares, floor weight, padding
@@ -438,6 +477,15 @@ fused_s_kernel(const FusedDesc d, const float *__restrict__ samples, int64_t str
         //   [120-m0, 128-m0), [248-m0, 256-m0) and the words x[128-m0], x[256-m0]; x[64] and x[192] for the self-paired position
         floatx4 P1[2][2], P3[2][2], P2[2][2], P4[2][2];
         float P2w[2], P4w[2], x64 = 0.0f, x192 = 0.0f;
+        unsigned pp_t = 0u;                           // (HOP) the tile the SIMD's other wave is on
+        if constexpr (HOP != 0) {
+            // (the words go out and come in every tile -- two LDS instructions among the tile's ring reads; gating them by the
+            // phase as well made the compiler copy the whole tile for phase 0, at 8 bytes of scratch in the multi-network twin)
+            if (pair_on && (kPairEvery || !kPairGated || ph == 0)) {
+                *pp_mine = (unsigned)t;
+                pp_t = *pp_peer;
+            }
+        }
         if (F2) {
 #pragma unroll
             // (padded ring: position i of the frame sits at fp[i + sk(i)]; the quads lie inside one piece each, so the padding
@@ -490,6 +538,11 @@ fused_s_kernel(const FusedDesc d, const float *__restrict__ samples, int64_t str
             // of arithmetic ahead of their use
             SD_STAMP(st_lg, asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"));
             if constexpr (HOP != 0) {
+                // behind the partner: win the SIMD's arbitration until level with it again
+                if (pair_on && (kPairEvery || ph == 0)) {
+                    if ((int)__builtin_amdgcn_readfirstlane(pp_t) > t) __builtin_amdgcn_s_setprio(1);
+                    else __builtin_amdgcn_s_setprio(0);
+                }
                 // what the next tile reads beyond this one: one straight-line case a phase
                 static_assert(hopk::kPeriod == 4, "one case a phase");
                 if (t + 1 < tiles) {
@@ -1079,6 +1132,13 @@ fused_s_kernel(const FusedDesc d, const float *__restrict__ samples, int64_t str
         atomicAdd(d.stamps + 2, st_lg);
         atomicAdd(d.stamps + 3, (unsigned long long)tiles);
         atomicAdd(d.stamps + 4, 1ull);
+        // this wave's record (syldet_api.cpp reads them back): plain stores from this one lane
+        const unsigned wg = blockIdx.y * gridDim.x + blockIdx.x;
+        unsigned long long *rec = d.stamps + 16 + 4 * ((size_t)wg * kWaves + (size_t)wave);
+        rec[0] = (unsigned long long)st_hw_id | ((unsigned long long)(st_xcc_id & 15u) << 32) | ((unsigned long long)wave << 40) | ((unsigned long long)kWaves << 44);
+        rec[1] = st_rt_begin;
+        rec[2] = __builtin_amdgcn_s_memrealtime();
+        rec[3] = (unsigned long long)tiles | ((unsigned long long)wg << 32);
     }
 #endif
 #undef SD_STAMP
@@ -1100,6 +1160,9 @@ hipError_t launch_one(const FusedDesc &d, const float *samples, int64_t stride, 
         if (d.hop == hopk::kHop && d.s_hopk_rc != 0) {
             if (d.s_hopk_rc != hopk::kRing || (d.s_hopk_rc + 1) * 1024 + ((d.T - 1 + kTile) * d.s_pstride + 8 * HQ + 128) * 4 > d.s_lds_wave)
                 return hipErrorInvalidValue;                             // (the plan's ring is not the compiled one)
+            // ... nor may a progress word lie on ring, mirror, rows, zero quads or the lane-group table (pair_progress.hpp)
+            static_assert(HQ == 1 && NW == pairp::kWaves && pairp::table_end(1, 0) == (hopk::kRing + 1) * 1024 + (8 * HQ + 128) * 4, "pair_progress.hpp describes this layout");
+            if (d.s_pairstep != 0 && !pairp::fits(d.T, d.s_pstride, d.s_lds_wave)) return hipErrorInvalidValue;
             kern = fused_s_kernel<K2, GEN, HQ, NW, PADP, F2, NT, SPECT, MN, S16, hopk::kHop>;
         }
     }

@@ -119,6 +119,7 @@ struct syldet {
         bool fused_pad128 = false;    // SYLDET_FUSED_PAD128: hop 128 on the fold kernel's padded pieces, not the staggered chunks (round 6)
         bool fused_nofold2 = false;   // SYLDET_FUSED_NOFOLD2: the fold kernel's once-folded form where the twice-folded one takes the shape
         bool fused_nohopk = false;    // SYLDET_FUSED_HOPK=0: the fold kernel's run-time hop where the compile-time schedule (hop 132) takes the shape
+        bool fused_nopairstep = false;   // SYLDET_FUSED_PAIRSTEP=0: the compile-time-hop form without the progress words that keep a SIMD's two waves in step
         bool fused_stamps = false;    // SYLDET_FUSED_STAMPS: the stamped diagnostic instantiation
         int fused_ko = 0;             // SYLDET_FUSED_KO=<mask>: knock-out instantiation
         long long host_chunk = 0;     // SYLDET_HOST_CHUNK_BYTES=<n>: bytes of input per stage of the host-pointer pipeline (tests force seams with it)
@@ -142,6 +143,7 @@ struct syldet {
             fused_nofold = std::getenv("SYLDET_FUSED_NOFOLD") != nullptr;
             fused_nofold2 = std::getenv("SYLDET_FUSED_NOFOLD2") != nullptr;
             fused_nohopk = std::getenv("SYLDET_FUSED_HOPK") != nullptr && std::atoi(std::getenv("SYLDET_FUSED_HOPK")) == 0;
+            fused_nopairstep = std::getenv("SYLDET_FUSED_PAIRSTEP") != nullptr && std::atoi(std::getenv("SYLDET_FUSED_PAIRSTEP")) == 0;
             fused_pad128 = std::getenv("SYLDET_FUSED_PAD128") != nullptr;
             fused_stamps = std::getenv("SYLDET_FUSED_STAMPS") != nullptr;
             fused_ko = std::getenv("SYLDET_FUSED_KO") ? std::atoi(std::getenv("SYLDET_FUSED_KO")) : 0;
@@ -793,6 +795,7 @@ bool dft_route_for(const syldet *h, int64_t J, int C, bool for_network, const in
     d.ko = 0;
     d.no_fold2 = h->sw.fused_nofold2 ? 1 : 0;
     if (h->sw.fused_nohopk) d.s_hopk_rc = 0;
+    if (h->sw.fused_nopairstep) d.s_pairstep = 0;
     d.no_cs8 = h->sw.fused_pad128 ? 1 : 0;
     // the fold kernel's spectrogram instantiation where the plan allows it (rows under 2 GiB: its 32-bit byte offsets)
     fold = !h->sw.fused_nofold && fused_s_spectrogram_applicable(d) && ((J - 1) * (int64_t)d.hop + d.gap + d.W) * 4 < 0x7fffffffll;
@@ -855,6 +858,7 @@ bool fused_route_for(const syldet *h, int64_t J, int64_t E, int C, FusedDesc &d)
         d.no_fold = h->sw.fused_nofold ? 1 : 0;
         d.no_fold2 = h->sw.fused_nofold2 ? 1 : 0;
         if (h->sw.fused_nohopk) d.s_hopk_rc = 0;
+        if (h->sw.fused_nopairstep) d.s_pairstep = 0;
         d.no_cs8 = h->sw.fused_pad128 ? 1 : 0;
         // Which fused kernel THIS batch gets is known only now (the fold kernel addresses a row with 32-bit byte offsets; a
         // diagnostic switch may rule it out).  The batch takes the fused route only if that kernel can run it (plans whose hop
@@ -950,22 +954,41 @@ int run_on_stream(syldet *h, Samples x, int64_t S, int64_t stride, int C, float 
         // diagnostic only: SYLDET_FUSED_STAMPS=1 runs the stamped instantiation and prints where a
         // workgroup pass spends its cycles (never set in tests or the benchmark)
         if (h->sw.fused_stamps && fused_s_has_stamps() && fused_choice(d, J) == 2) {
-            // the fold kernel's stamped build (-DSYLDET_S_STAMPS): shader clocks its waves spend waiting, summed over all waves
-            if (int st = h->d_stamps.reserve(16 * sizeof(unsigned long long))) return st;
-            SYLDET_HIP(hipMemsetAsync(h->d_stamps.ptr, 0, 16 * sizeof(unsigned long long), stream));
+            // the fold kernel's stamped build (-DSYLDET_S_STAMPS): shader clocks its waves spend waiting, summed over all waves in
+            // 16 words, and behind them one record of four words a wave slot of the grid (kernels_fused_s.hip writes them):
+            //   [0] hardware id register | XCC id << 32 | wave << 40 | waves a workgroup << 44
+            //   [1], [2] the 100 MHz clock at the wave's entry and after its last tile     [3] its tiles | workgroup << 32
+            // (a wave without a segment leaves zeros).  SYLDET_FUSED_STAMPS_FILE=<path>: the records as text, one line a wave
+            // (tools/wave_skew.py reads them).
+            const int64_t segs = (E + d.s_seg_evals - 1) / d.s_seg_evals;
+            const size_t n_rec = (size_t)(segs + 8) * (size_t)C, n = 16 + 4 * n_rec;
+            if (int st = h->d_stamps.reserve(n * sizeof(unsigned long long))) return st;
+            SYLDET_HIP(hipMemsetAsync(h->d_stamps.ptr, 0, n * sizeof(unsigned long long), stream));
             d.stamps = (unsigned long long *)h->d_stamps.ptr;
             {
                 KernelTimer t(h, stream, "fused_s_kernel");
                 SYLDET_HIP(launch_fused(d, d_samples, stride, C, S, J, E, d_outputs, d_flags, stream));
             }
-            unsigned long long host[16];
-            SYLDET_HIP(hipMemcpyAsync(host, h->d_stamps.ptr, sizeof(host), hipMemcpyDeviceToHost, stream));
+            std::vector<unsigned long long> host(n);
+            SYLDET_HIP(hipMemcpyAsync(host.data(), h->d_stamps.ptr, n * sizeof(unsigned long long), hipMemcpyDeviceToHost, stream));
             SYLDET_HIP(hipStreamSynchronize(stream));
             const double w = (double)host[4], tl = (double)host[3];
             std::fprintf(stderr, "[syldet stamps] fold kernel: %.0f waves, %.1f tiles each; per tile: %.0f clocks in all, %.0f waiting for the samples' DMA (%.1f %%), "
                                  "%.0f waiting for the LDS reads of the samples (%.1f %%)\n",
                          w, tl / w, (double)host[0] / tl, (double)host[1] / tl, 100.0 * (double)host[1] / (double)host[0], (double)host[2] / tl,
                          100.0 * (double)host[2] / (double)host[0]);
+            if (const char *path = std::getenv("SYLDET_FUSED_STAMPS_FILE")) {
+                if (FILE *f = std::fopen(path, "w")) {
+                    std::fprintf(f, "# workgroup wave waves hw_id xcc_id begin_10ns end_10ns tiles\n");
+                    for (size_t r = 0; r < n_rec; r++) {
+                        const unsigned long long *q = host.data() + 16 + 4 * r;
+                        if ((q[3] & 0xffffffffull) == 0) continue;
+                        std::fprintf(f, "%llu %llu %llu %llu %llu %llu %llu %llu\n", q[3] >> 32, (q[0] >> 40) & 15, (q[0] >> 44) & 15, q[0] & 0xffffffffull,
+                                     (q[0] >> 32) & 15, q[1], q[2], q[3] & 0xffffffffull);
+                    }
+                    std::fclose(f);
+                }
+            }
             return SYLDET_OK;
         }
         if (h->sw.fused_stamps) {
