@@ -877,6 +877,69 @@ int syldet_recordings_load_device_s16(syldet_recordings_t *r, const int16_t *d_s
 int syldet_recordings_events_device(syldet_recordings_t *r, const float *d_outputs, const uint8_t *d_flags, double debounce_seconds,
                                     int64_t *d_indices, float *d_values, int64_t capacity, int64_t *d_counts, void *hip_stream);
 
+/* ---- threshold calibration: score a run against labelled times ----
+ * Which threshold to ship, and how late and how jittery the trigger is at it: the reference leaves the question to MATLAB
+ * (convert_to_text.m:70-72 only copies trigger_thresholds in).  Here the outputs of a run, which are on the device already, are
+ * scored for K candidate thresholds in one launch.  Under debounce hits and false positives do not move monotonically with the
+ * threshold (a low one fires early on noise and the debounce swallows the real crossing), so every threshold runs the debounce
+ * scan of TrackDetector.swift:65-100 for itself.  THE CONVENTION is the library's own (as the sinc converter's and the meters'):
+ * A DETECTOR is one channel of a bank, or one recording of a syldet_recordings_t.  Its evaluations e = 0 .. E-1 have the sample
+ * numbers idx_e = first_index + e hop; for a recording e and the samples count from its own start (the numbering of
+ * syldet_detections_device and syldet_recordings_events_device).  For one detector, one output o and one threshold theta (a double):
+ *   flag      flag_e = Double(out[e][o]) >= theta.  NaN never fires.  Only output o counts, whatever the handle's rule.
+ *   debounce  until = -1 at the detector's start; a detection is emitted iff flag_e && until < idx_e, and then
+ *             until = idx_e + Int(debounce_seconds * samplingRate).
+ *   labels    detector d has sorted sample numbers t_0 < .. < t_{n-1} and every detector the tolerance of m >= 0 samples.  The
+ *             windows [t_j - m, t_j + m] must be disjoint: t_{j+1} - t_j > 2 m (else SYLDET_ERR_INVALID_ARGUMENT, and
+ *             syldet_last_error names the detector and the label).  A label may lie before sample 0 or behind the detector's end.
+ *   class     each emitted detection falls in exactly one: in window j and j not yet hit at this theta -- a HIT, which adds
+ *             idx - t_j to the offset sum and its square to the squared-offset sum; in window j and j already hit -- a REPEAT;
+ *             in no window -- a FALSE POSITIVE.
+ *   result    table [D][K][6], int64, the columns SYLDET_SCORE_* below.  Always detections = hits + false_positives + repeats;
+ *             the misses are n_d - hits.  Integer arithmetic throughout: device, host and any model of the above agree exactly.
+ * Limits: 1 <= K <= SYLDET_SCORE_MAX_THRESHOLDS; thresholds may be +-inf or beyond FLT_MAX, NaN is refused; 0 <= m <= 2^20;
+ * debounce_seconds * samplingRate must be a number of magnitude below 2^62.
+ * (The device compares in fp32 against the smallest float >= theta, +inf beyond FLT_MAX, computed at creation: exact, because
+ * float -> double is exact.)
+ *   syldet_scorer_create   h: the bank; r: NULL (one detector a channel, D = its channels) or a packed-recordings handle of h
+ *       (D = its recordings); thresholds [K]; labels: all detectors' labels end to end, detector d's at [label_begin[d],
+ *       label_begin[d + 1]) (label_begin [D + 1], starting at 0 and not decreasing; labels may be NULL where there are none).
+ *       Everything is validated before any device is touched; then thresholds, labels and, for recordings, the slots' (row,
+ *       first_eval, n_evals) are uploaded once.  h, and r if given, must outlive the scorer.
+ *   syldet_score_device    d_outputs as syldet_run_device* wrote them: [C][n_evals][n_out] without r; with r n_evals must equal
+ *       row_evals, and recording k reads only its own [first_eval, first_eval + n_evals_k) of its row.  d_table [D][K][6].  One
+ *       launch ("score_kernel": one wave a detector and group of 64 thresholds, a lane a threshold); it never allocates,
+ *       synchronises or copies, and follows the bank's rule of one stream at a time.  SYLDET_ERR_INVALID_ARGUMENT: NULL pointers,
+ *       output outside [0, n_out), n_evals < 0, a wrong n_evals with r.  Plain, multi-network and mixed banks; a sharded bank
+ *       has none.  One detector is one sequential chain: it is not split along time, the parallelism is detectors x groups.
+ *   syldet_score_host      host only: one detector in plain C++ (the text the kernel's lanes run, one threshold after another):
+ *       evaluation e's value is values[e value_stride]; table [K][6].
+ *   syldet_score_choose    host only: sums table [D][K][6] over the detectors (n_labels [D]: each detector's label count) into
+ *       totals [K][6] (may be NULL); cost_k = misses_k + false_positive_cost (false_positives_k + repeats_k) in double (costs
+ *       [K], may be NULL; false_positive_cost is not NaN); *best = the lowest k of the smallest cost.                            */
+#define SYLDET_SCORE_DETECTIONS         0
+#define SYLDET_SCORE_HITS               1
+#define SYLDET_SCORE_FALSE_POSITIVES    2
+#define SYLDET_SCORE_REPEATS            3
+#define SYLDET_SCORE_SUM_OFFSET         4
+#define SYLDET_SCORE_SUM_OFFSET_SQUARED 5
+#define SYLDET_SCORE_COLUMNS            6
+#define SYLDET_SCORE_MAX_THRESHOLDS     4096
+#define SYLDET_SCORE_MAX_TOLERANCE      1048576
+typedef struct syldet_scorer syldet_scorer_t;
+int syldet_scorer_create(const syldet_t *h, const syldet_recordings_t *r, const double *thresholds, int32_t n_thresholds,
+                         const int64_t *labels, const int64_t *label_begin, int64_t tolerance_samples, double debounce_seconds,
+                         syldet_scorer_t **out);
+int syldet_scorer_destroy(syldet_scorer_t *s);
+int syldet_scorer_shape(const syldet_scorer_t *s, int32_t *n_detectors, int32_t *n_thresholds, int64_t *n_labels);
+int syldet_score_device(syldet_scorer_t *s, const float *d_outputs, int64_t n_evals, int32_t output, int64_t *d_table,
+                        void *hip_stream);
+int syldet_score_host(const float *values, int64_t n_evals, int64_t value_stride, const double *thresholds, int32_t n_thresholds,
+                      const int64_t *labels, int64_t n_labels, int64_t tolerance_samples, int64_t first_index, int64_t hop,
+                      int64_t debounce_frames, int64_t *table);
+int syldet_score_choose(const int64_t *table, int32_t n_detectors, int32_t n_thresholds, const int64_t *n_labels,
+                        double false_positive_cost, int32_t *best, int64_t *totals, double *costs);
+
 #ifdef __cplusplus
 }
 #endif

@@ -10,7 +10,8 @@ from .config import (InvalidValue, MismatchedLength, MissingValue, NeuralNet, Ne
                      ProcessingFunction, SyllableDetectorConfig, SyllableDetectorError, UnableToOpenPath,
                      createWindow, frequencyIndexRange)
 from .bank import PinnedArray, ShardedSyllableDetectorBank, shard_table
-from .detector import Recordings, SyllableDetector, configsCompatible, configsShareClock, fusedFormOfConfig, planRecordings
+from .detector import (Recordings, Scorer, SyllableDetector, chooseThreshold, configsCompatible, configsShareClock, fusedFormOfConfig,
+                       planRecordings, scoreHost)
 from .resampler import ResamplerLinear, ResamplerSinc, sincReady, convertRate, deinterleave, sincCoefficient, sincDefaults, sincTaps
 
 __all__ = ["SyllableDetector", "SyllableDetectorConfig", "NeuralNet", "NeuralNetLayer", "ProcessingFunction",
@@ -18,4 +19,4 @@ __all__ = ["SyllableDetector", "SyllableDetectorConfig", "NeuralNet", "NeuralNet
            "SyllableDetectorError", "frequencyIndexRange", "createWindow", "ResamplerLinear", "deinterleave",
            "convertRate", "ResamplerSinc", "sincReady", "sincCoefficient", "sincTaps", "sincDefaults",
            "ShardedSyllableDetectorBank", "PinnedArray", "shard_table", "configsCompatible",
-           "configsShareClock", "fusedFormOfConfig", "Recordings", "planRecordings"]
+           "configsShareClock", "fusedFormOfConfig", "Recordings", "planRecordings", "Scorer", "scoreHost", "chooseThreshold"]

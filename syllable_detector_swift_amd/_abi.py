@@ -91,6 +91,12 @@ class Shard(C.Structure):
 
 EXCHANGE_RCCL, EXCHANGE_PEER_COPY = 0, 1
 
+# columns of a score table row (SYLDET_SCORE_*)
+SCORE_DETECTIONS, SCORE_HITS, SCORE_FALSE_POSITIVES, SCORE_REPEATS, SCORE_SUM_OFFSET, SCORE_SUM_OFFSET_SQUARED = 0, 1, 2, 3, 4, 5
+SCORE_COLUMNS = 6
+SCORE_MAX_THRESHOLDS = 4096
+SCORE_MAX_TOLERANCE = 1 << 20
+
 Handle = C.c_void_p
 Config_p = C.POINTER(Config)
 c_void_pp = C.POINTER(C.c_void_p)
@@ -242,6 +248,13 @@ SIGNATURES = {
     "syldet_recordings_load_device_s16": (C.c_int, [Handle, C.c_void_p, c_int64_p, c_int32_p, C.c_void_p, C.c_int64, C.c_void_p]),
     "syldet_recordings_events_device": (C.c_int, [Handle, C.c_void_p, C.c_void_p, C.c_double, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p,
                                                   C.c_void_p]),
+    "syldet_scorer_create": (C.c_int, [Handle, Handle, c_double_p, C.c_int32, c_int64_p, c_int64_p, C.c_int64, C.c_double, C.POINTER(Handle)]),
+    "syldet_scorer_destroy": (C.c_int, [Handle]),
+    "syldet_scorer_shape": (C.c_int, [Handle, c_int32_p, c_int32_p, c_int64_p]),
+    "syldet_score_device": (C.c_int, [Handle, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p]),
+    "syldet_score_host": (C.c_int, [c_float_p, C.c_int64, C.c_int64, c_double_p, C.c_int32, c_int64_p, C.c_int64, C.c_int64, C.c_int64, C.c_int64,
+                                    C.c_int64, c_int64_p]),
+    "syldet_score_choose": (C.c_int, [c_int64_p, C.c_int32, C.c_int32, c_int64_p, C.c_double, c_int32_p, c_int64_p, c_double_p]),
 }
 
 

@@ -27,6 +27,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <map>
 #include <string>
 #include <vector>
 
@@ -40,7 +41,7 @@ constexpr int kExUsage = 64;   // EX_USAGE, main.swift:40
 void usage(FILE *to)
 {
     std::fprintf(to,
-                 "Usage: syllable-detector-cli -n <net> [-a <audio>]... [-d <seconds>] [--device <k>] [--chunk <frames>] [--format <shortest|swift4>] [--resample <linear|sinc>] [--resample-quality <Z,beta,rolloff>] [--simulate <out.wav>] [--simulate-output <k>] [--levels <out.tsv>] [--levels-buffer <L>] [--levels-period <seconds>] [--ttl <out.wav>] [--ttl-mux] [--ttl-width <seconds>] [--ttl-steps <n>] [--ttl-buffer <L>] [--ttl-latency <seconds>] [--ttl-onsets <out.tsv>] [--batch] [--batch-rows <N>] [--batch-bytes <B>] [--probe]\n"
+                 "Usage: syllable-detector-cli -n <net> [-a <audio>]... [-d <seconds>] [--device <k>] [--chunk <frames>] [--format <shortest|swift4>] [--resample <linear|sinc>] [--resample-quality <Z,beta,rolloff>] [--simulate <out.wav>] [--simulate-output <k>] [--levels <out.tsv>] [--levels-buffer <L>] [--levels-period <seconds>] [--ttl <out.wav>] [--ttl-mux] [--ttl-width <seconds>] [--ttl-steps <n>] [--ttl-buffer <L>] [--ttl-latency <seconds>] [--ttl-onsets <out.tsv>] [--batch] [--batch-rows <N>] [--batch-bytes <B>] [--score <labels.tsv> --score-out <table.tsv>] [--score-thresholds <lo:hi:n>] [--score-tolerance <seconds>] [--score-cost <c>] [--score-output <k>] [--probe]\n"
                  "  -n, --net <net>:\n      Path to trained network file.  Given k > 1 times: each file must have exactly k tracks, and track t runs network t (one mixed bank; the networks must share the sampling rate, window length, window overlap, time range and number of outputs).\n"
                  "  -a, --audio <audio>:\n      Path to the audio file to process.\n"
                  "  -d, --debounce <seconds>:\n      Number of seconds to debounce triggers.\n"
@@ -64,6 +65,12 @@ void usage(FILE *to)
                  "      --batch:\n      Run the audio files through one detector bank instead of one bank a file: every track of every file becomes a recording in the bank's rows, and only the detections come back from the GPU. The output is the same.\n"
                  "      --batch-rows <N>:\n      Rows of the bank under --batch (default 64; no more than there are tracks).\n"
                  "      --batch-bytes <B>:\n      Consecutive files share a batch until their samples pass B bytes (default 2147483648).\n"
+                 "      --score <labels.tsv>:\n      Under --batch, also score every track against labelled times for a grid of candidate thresholds: lines of file, track and sample, tab separated (the file as -a names it, the sample counted from the file's start at the network's sampling rate). Needs --score-out.\n"
+                 "      --score-out <table.tsv>:\n      Where --score writes its table, one line per threshold, tab separated: threshold, detections, hits, misses, false positives, repeats, the mean and the standard deviation of the hits' offsets in samples, the cost; a last line names the threshold of the smallest cost.\n"
+                 "      --score-thresholds <lo:hi:n>:\n      The grid: n thresholds from lo to hi (default 0:1:101; at most 4096).\n"
+                 "      --score-tolerance <seconds>:\n      A detection this close to a label is a hit (default 0.02).\n"
+                 "      --score-cost <c>:\n      The cost of a false positive or a repeat; a miss costs 1 (default 1).\n"
+                 "      --score-output <k>:\n      The network output --score compares with the thresholds (default 0).\n"
                  "      --probe:\n      Only print what the audio files contain; does not touch the GPU.\n"
                  "The command line will write a comma-separated list of detection events (when the network has at least one output above threshold) to standard out. For example, it might output:\n"
                  "\n\t0,1593298,36.1292063492063,0.918557\n\n"
@@ -441,9 +448,62 @@ struct BatchFile {
     size_t bytes() const { return is16 ? s16.size() * sizeof(int16_t) : f32.size() * sizeof(float); }
 };
 
+// --score: threshold calibration (syldet_scorer_*): every track of every batched file scored against its labelled samples for
+// a grid of candidate thresholds, on the outputs the batch leaves on the device.  The batches' tables add up on the host.
+struct ScoreOpt {
+    std::string labels_path, out_path;
+    double lo = 0.0, hi = 1.0, tolerance = 0.02, cost = 1.0;
+    long n = 101;
+    int output = 0;
+    bool on() const { return !labels_path.empty(); }
+};
+
+struct ScoreRun {
+    std::vector<double> thresholds;
+    int output = 0;
+    int64_t tolerance = 0;                                  // samples
+    std::map<std::string, std::map<long, std::vector<int64_t>>> labels;   // file as -a names it -> track -> sorted samples
+    std::vector<int64_t> totals;                            // [K][6], summed over every scored track
+    int64_t n_labels = 0;                                   // ... and their labels
+    bool failed = false;
+};
+
+// LABELS: lines of file<TAB>track<TAB>sample (the sample counted from the file's start, at the network's rate)
+bool read_labels(const std::string &path, ScoreRun &run, std::string &err)
+{
+    FILE *f = std::fopen(path.c_str(), "rb");
+    if (!f) { err = "unable to open " + path; return false; }
+    std::string text;
+    char buf[65536];
+    for (size_t n; (n = std::fread(buf, 1, sizeof buf, f)) > 0;) text.append(buf, n);
+    std::fclose(f);
+    size_t at = 0;
+    for (long line = 1; at < text.size(); line++) {
+        size_t end = text.find('\n', at);
+        if (end == std::string::npos) end = text.size();
+        std::string l = text.substr(at, end - at);
+        at = end + 1;
+        if (!l.empty() && l.back() == '\r') l.pop_back();
+        if (l.empty() || l[0] == '#') continue;
+        const size_t t2 = l.rfind('\t'), t1 = t2 == std::string::npos || t2 == 0 ? std::string::npos : l.rfind('\t', t2 - 1);
+        char *e1 = nullptr, *e2 = nullptr;
+        const std::string track = t1 == std::string::npos ? "" : l.substr(t1 + 1, t2 - t1 - 1), sample = t1 == std::string::npos ? "" : l.substr(t2 + 1);
+        const long trk = std::strtol(track.c_str(), &e1, 10);
+        const long long smp = std::strtoll(sample.c_str(), &e2, 10);
+        if (t1 == std::string::npos || t1 == 0 || track.empty() || sample.empty() || *e1 || *e2 || trk < 0) {
+            err = path + ", line " + std::to_string(line) + ": not file<TAB>track<TAB>sample";
+            return false;
+        }
+        run.labels[l.substr(0, t1)][trk].push_back((int64_t)smp);
+    }
+    for (auto &file : run.labels)
+        for (auto &track : file.second) std::sort(track.second.begin(), track.second.end());
+    return true;
+}
+
 // One batch: returns 0, or 2 for device trouble (no line of the batch is printed then, but the files' names are)
 int run_batch(std::vector<BatchFile> &files, const std::vector<syldet_config_t *> &cfgs, int device, double debounce_s, int64_t chunk,
-              long max_rows, bool headers)
+              long max_rows, bool headers, ScoreRun *score)
 {
     if (files.empty()) return 0;
     const syldet_config_t *cfg = cfgs[0];
@@ -483,6 +543,22 @@ int run_batch(std::vector<BatchFile> &files, const std::vector<syldet_config_t *
     int64_t cap = 1;
     int n_out = 0;
     int rc = 0;
+    // --score: the recordings' labels in the recordings' order (a track without labels, or with an evaluation-less file, still
+    // counts: its labels are misses at every threshold)
+    std::vector<int64_t> score_labels, score_begin(1, 0);
+    if (score) {
+        for (const BatchFile &f : files) {
+            const auto of_file = score->labels.find(f.path);
+            for (int t = 0; t < f.info.channels; t++) {
+                if (of_file != score->labels.end()) {
+                    const auto of_track = of_file->second.find(t);
+                    if (of_track != of_file->second.end()) score_labels.insert(score_labels.end(), of_track->second.begin(), of_track->second.end());
+                }
+                score_begin.push_back((int64_t)score_labels.size());
+            }
+        }
+        score->n_labels += (int64_t)score_labels.size();
+    }
     do {
         if (int st = n_nets > 1 ? syldet_create_mixed(cfgs.data(), n_nets, row_net.data(), C, device, SYLDET_ENGINE_AUTO, &h)
                                 : syldet_create(cfg, C, device, SYLDET_ENGINE_AUTO, &h)) {
@@ -544,11 +620,34 @@ int run_batch(std::vector<BatchFile> &files, const std::vector<syldet_config_t *
         if (hipMemcpyAsync(idx.data(), d_idx.p, idx.size() * sizeof(int64_t), hipMemcpyDeviceToHost, stream) != hipSuccess ||
             hipMemcpyAsync(val.data(), d_val.p, val.size() * sizeof(float), hipMemcpyDeviceToHost, stream) != hipSuccess ||
             hipStreamSynchronize(stream) != hipSuccess) { rc = 2; break; }
+        if (score && !score->failed) {
+            // the thresholds' tables of every recording in one launch over the outputs that are on the device already
+            const int32_t n_thr = (int32_t)score->thresholds.size();
+            syldet_scorer_t *sc = nullptr;
+            DevBuf d_table;
+            std::vector<int64_t> table((size_t)K * (size_t)n_thr * SYLDET_SCORE_COLUMNS);
+            st = syldet_scorer_create(h, r, score->thresholds.data(), n_thr, score_labels.data(), score_begin.data(), score->tolerance, debounce_s, &sc);
+            if (!st && !d_table.alloc(table.size() * sizeof(int64_t))) { syldet_scorer_destroy(sc); rc = 2; break; }
+            if (!st) st = syldet_score_device(sc, (const float *)d_out.p, row_evals, score->output, (int64_t *)d_table.p, stream);
+            if (st) {
+                std::fprintf(stderr, "Unable to score the batch: %s: %s\n", syldet_strerror(st), syldet_last_error());
+                score->failed = true;
+            } else if (hipMemcpyAsync(table.data(), d_table.p, table.size() * sizeof(int64_t), hipMemcpyDeviceToHost, stream) != hipSuccess ||
+                       hipStreamSynchronize(stream) != hipSuccess) {
+                syldet_scorer_destroy(sc);
+                rc = 2;
+                break;
+            } else {
+                for (size_t i = 0; i < table.size(); i++) score->totals[i % ((size_t)n_thr * SYLDET_SCORE_COLUMNS)] += table[i];
+            }
+            syldet_scorer_destroy(sc);
+        }
     } while (false);
     if (rc == 2 && hipPeekAtLastError() != hipSuccess) std::fprintf(stderr, "Unable to process the batch: %s\n", hipGetErrorString(hipGetLastError()));
     if (stream) (void)hipStreamDestroy(stream);
     syldet_recordings_destroy(r);
     syldet_destroy(h);
+    if (rc && score) score->failed = true;                  // (a table without this batch would be another archive's)
     // file by file, the lines process_file prints: the tracks' events interleaved buffer by buffer (main.swift:126-130)
     int32_t k0 = 0;
     for (const BatchFile &f : files) {
@@ -576,10 +675,46 @@ int run_batch(std::vector<BatchFile> &files, const std::vector<syldet_config_t *
     return rc;
 }
 
+// TABLE: one line per threshold -- threshold detections hits misses false_positives repeats mean_offset sd_offset cost, tab
+// separated, the offsets in samples (mean and deviation of the hits' offsets from the two sums, in double; nan without a hit) --
+// and a last line "# best <threshold>" (syldet_score_choose: the lowest threshold of the smallest cost)
+bool write_score_table(const ScoreOpt &opt, const ScoreRun &run)
+{
+    const int32_t K = (int32_t)run.thresholds.size();
+    std::vector<double> costs((size_t)K);
+    int32_t best = 0;
+    if (int st = syldet_score_choose(run.totals.data(), 1, K, &run.n_labels, opt.cost, &best, nullptr, costs.data())) {
+        std::fprintf(stderr, "Unable to choose a threshold: %s: %s\n", syldet_strerror(st), syldet_last_error());
+        return false;
+    }
+    FILE *f = std::fopen(opt.out_path.c_str(), "wb");
+    if (!f) {
+        std::fprintf(stderr, "Unable to write %s.\n", opt.out_path.c_str());
+        return false;
+    }
+    for (int32_t k = 0; k < K; k++) {
+        const int64_t *t = run.totals.data() + (size_t)k * SYLDET_SCORE_COLUMNS;
+        const int64_t hits = t[SYLDET_SCORE_HITS];
+        std::fprintf(f, "%.17g\t%lld\t%lld\t%lld\t%lld\t%lld\t", run.thresholds[(size_t)k], (long long)t[SYLDET_SCORE_DETECTIONS], (long long)hits,
+                     (long long)(run.n_labels - hits), (long long)t[SYLDET_SCORE_FALSE_POSITIVES], (long long)t[SYLDET_SCORE_REPEATS]);
+        if (hits > 0) {
+            const double mean = (double)t[SYLDET_SCORE_SUM_OFFSET] / (double)hits;
+            const double square = mean * mean;              // (a statement of its own: no fused multiply-subtract below)
+            const double var = (double)t[SYLDET_SCORE_SUM_OFFSET_SQUARED] / (double)hits - square;
+            std::fprintf(f, "%.17g\t%.17g\t", mean, std::sqrt(var > 0.0 ? var : 0.0));
+        } else {
+            std::fputs("nan\tnan\t", f);
+        }
+        std::fprintf(f, "%.17g\n", costs[(size_t)k]);
+    }
+    std::fprintf(f, "# best %.17g\n", run.thresholds[(size_t)best]);
+    return std::fclose(f) == 0;
+}
+
 // The loop over the -a files under --batch: consecutive files that can share a bank (readable, at the network's rate, the right
 // number of tracks) gather until their samples pass opt.bytes; any other file ends the batch and is processed alone in its place.
 int process_batched(const std::vector<std::string> &audio, const std::vector<syldet_config_t *> &cfgs, int device, double debounce_s, bool have_debounce,
-                    int64_t chunk, const BatchOpt &opt, const ResampleOpt &conv)
+                    int64_t chunk, const BatchOpt &opt, const ResampleOpt &conv, ScoreRun *score)
 {
     int rc = 0;
     const bool headers = audio.size() > 1;
@@ -587,7 +722,7 @@ int process_batched(const std::vector<std::string> &audio, const std::vector<syl
     std::vector<BatchFile> files;
     size_t held = 0;
     auto flush = [&]() {
-        if (run_batch(files, cfgs, device, deb, chunk, opt.rows, headers) == 2) rc = 2;
+        if (run_batch(files, cfgs, device, deb, chunk, opt.rows, headers, score) == 2) rc = 2;
         held = 0;
     };
     for (const std::string &p : audio) {
@@ -608,6 +743,7 @@ int process_batched(const std::vector<std::string> &audio, const std::vector<syl
         }
         // another rate, unreadable, no tracks, the wrong number of tracks: exactly as without --batch, in its place
         flush();
+        if (score && score->labels.count(p)) std::fprintf(stderr, "--score: %s does not go through the bank; its labels are left out.\n", p.c_str());
         if (headers) std::printf("%s\n", p.c_str());
         std::fflush(stdout);
         const int r = process_file(p, cfgs, device, debounce_s, have_debounce, chunk, std::string(), 0, LevelsOpt(), TtlOpt(), conv);
@@ -640,6 +776,8 @@ int main(int argc, char **argv)
     int64_t chunk = 8192;
     BatchOpt batch;
     bool have_batch_option = false;
+    ScoreOpt score;
+    bool have_score = false, have_score_option = false;
     auto value = [&](int &i, const char *name) -> const char * {
         if (i + 1 >= argc) {
             std::fprintf(stderr, "Missing value for %s.\n", name);
@@ -674,6 +812,50 @@ int main(int argc, char **argv)
             if (rows) batch.rows = (long)k;
             else batch.bytes = k;
             have_batch_option = true;
+        }
+        else if (a == "--score") { score.labels_path = value(i, "--score"); have_score = true; }
+        else if (a == "--score-out") { score.out_path = value(i, "--score-out"); have_score_option = true; }
+        else if (a == "--score-thresholds") {
+            // lo:hi:n, the grid lo + (hi - lo) i / (n - 1)
+            const std::string v = value(i, "--score-thresholds");
+            const size_t c1 = v.find(':'), c2 = c1 == std::string::npos ? c1 : v.find(':', c1 + 1);
+            char *e1 = nullptr, *e2 = nullptr, *e3 = nullptr;
+            const std::string lo = v.substr(0, c1), hi = c2 == std::string::npos ? "" : v.substr(c1 + 1, c2 - c1 - 1), n = c2 == std::string::npos ? "" : v.substr(c2 + 1);
+            score.lo = std::strtod(lo.c_str(), &e1);
+            score.hi = std::strtod(hi.c_str(), &e2);
+            score.n = std::strtol(n.c_str(), &e3, 10);
+            if (lo.empty() || hi.empty() || n.empty() || *e1 || *e2 || *e3 || std::isnan(score.lo) || std::isnan(score.hi) || score.n < 1 ||
+                score.n > SYLDET_SCORE_MAX_THRESHOLDS) {
+                std::fprintf(stderr, "--score-thresholds takes lo:hi:n, two numbers and a count from 1 to %d.\n", SYLDET_SCORE_MAX_THRESHOLDS);
+                usage(stdout);
+                return kExUsage;
+            }
+            have_score_option = true;
+        }
+        else if (a == "--score-tolerance" || a == "--score-cost") {
+            const bool tol = a == "--score-tolerance";
+            const char *v = value(i, a.c_str());
+            char *end = nullptr;
+            const double x = std::strtod(v, &end);
+            if (end == v || *end != 0 || !(x >= 0.0) || std::isinf(x)) {
+                std::fprintf(stderr, "%s takes a number, 0 or more.\n", a.c_str());
+                usage(stdout);
+                return kExUsage;
+            }
+            (tol ? score.tolerance : score.cost) = x;
+            have_score_option = true;
+        }
+        else if (a == "--score-output") {
+            const char *v = value(i, "--score-output");
+            char *end = nullptr;
+            const long k = std::strtol(v, &end, 10);
+            if (end == v || *end != 0 || k < 0 || k > 65535) {
+                std::fprintf(stderr, "--score-output takes the number of a network output, 0 or more.\n");
+                usage(stdout);
+                return kExUsage;
+            }
+            score.output = (int)k;
+            have_score_option = true;
         }
         else if (a == "--resample") {
             const std::string m = value(i, "--resample");
@@ -870,6 +1052,30 @@ int main(int argc, char **argv)
         usage(stdout);
         return kExUsage;
     }
+    if (have_score && !batch.on) {                          // the scorer's detectors are the recordings of a batch
+        std::fprintf(stderr, "--score needs --batch.\n");
+        usage(stdout);
+        return kExUsage;
+    }
+    if (have_score_option && !have_score) {
+        std::fprintf(stderr, "--score-out, --score-thresholds, --score-tolerance, --score-cost and --score-output need --score <labels.tsv>.\n");
+        usage(stdout);
+        return kExUsage;
+    }
+    if (have_score && (score.labels_path.empty() || score.out_path.empty())) {
+        std::fprintf(stderr, "--score <labels.tsv> needs --score-out <table.tsv>.\n");
+        usage(stdout);
+        return kExUsage;
+    }
+    ScoreRun scoring;
+    if (have_score) {
+        std::string err;
+        if (!read_labels(score.labels_path, scoring, err)) {
+            std::fprintf(stderr, "--score: %s.\n", err.c_str());
+            usage(stdout);
+            return kExUsage;
+        }
+    }
     std::vector<syldet_config_t *> cfgs;
     for (const std::string &n : net) {
         syldet_config_t *cfg = nullptr;
@@ -900,9 +1106,30 @@ int main(int argc, char **argv)
             return kExUsage;
         }
     }
+    if (have_score) {                                       // (before the GPU is opened)
+        const double tol = score.tolerance * cfgs[0]->sampling_rate;
+        bool ok = tol <= (double)SYLDET_SCORE_MAX_TOLERANCE;
+        if (!ok) std::fprintf(stderr, "--score-tolerance may be %d samples at most.\n", SYLDET_SCORE_MAX_TOLERANCE);
+        for (syldet_config_t *c : cfgs)
+            if (ok && score.output >= c->n_thresholds) {
+                std::fprintf(stderr, "--score-output %d: the network has %d output(s).\n", score.output, c->n_thresholds);
+                ok = false;
+            }
+        if (!ok) {
+            for (syldet_config_t *k : cfgs) syldet_config_free(k);
+            usage(stdout);
+            return kExUsage;
+        }
+        scoring.tolerance = (int64_t)tol;
+        scoring.output = score.output;
+        for (long i = 0; i < score.n; i++) scoring.thresholds.push_back(score.n > 1 ? score.lo + (score.hi - score.lo) * (double)i / (double)(score.n - 1) : score.lo);
+        scoring.totals.assign((size_t)score.n * SYLDET_SCORE_COLUMNS, 0);
+    }
     if (batch.on) {
-        const int brc = process_batched(audio, cfgs, device, debounce, have_debounce, chunk, batch, conv);
+        int brc = process_batched(audio, cfgs, device, debounce, have_debounce, chunk, batch, conv, have_score ? &scoring : nullptr);
         for (syldet_config_t *c : cfgs) syldet_config_free(c);
+        // the table last, and only a whole one; standard output and the status are those of the run without --score
+        if (have_score && (scoring.failed || !write_score_table(score, scoring)) && brc == 0) brc = 1;
         return brc;
     }
     int rc = 0;

@@ -407,6 +407,22 @@ hipError_t launch_recordings_events(const RecEventDev *desc, int K, int64_t row_
                                     int64_t first_index, int64_t hop, int64_t debounce_frames, int64_t *indices, float *values,
                                     int64_t capacity, int64_t *counts, hipStream_t stream);
 
+// ---- threshold calibration (kernels_score.hip; syldet_score_device of include/syldet.h) ----
+// What a scorer keeps on the device.  A detector is a channel (slots == nullptr: its evaluations are row `det`) or a recording
+// (slots [D]: its own part of its row).
+struct ScoreDesc {
+    const float *thresholds;                 // [K] the smallest float >= each threshold (score_scan.hpp)
+    const float *group_least;                // [ceil(K / 64)] the least of each group of 64
+    const int64_t *labels;                   // every detector's sorted labels, end to end
+    const int64_t *label_begin;              // [D + 1] detector d's labels are [label_begin[d], label_begin[d + 1])
+    const RecEventDev *slots;
+    int K;
+    int64_t tolerance, debounce_frames;
+};
+// table [D][K][6] int64 <- output `output` of outputs [rows][n_evals][n_out]; one launch (score_kernel)
+hipError_t launch_score(const ScoreDesc &d, int D, const float *outputs, int64_t n_evals, int n_out, int output, int64_t first_index,
+                        int64_t hop, int64_t *table, hipStream_t stream);
+
 // detection flags <-> bits (bit b of byte t of a row = flag 8 t + b), rows padded to whole bytes
 hipError_t launch_pack_flags(const uint8_t *flags, int64_t rows, int64_t row_len, uint8_t *bits, hipStream_t stream);
 hipError_t launch_unpack_flags(const uint8_t *bits, int64_t rows, int64_t row_len, uint8_t *flags, hipStream_t stream);

@@ -852,6 +852,13 @@ class SyllableDetector:
             idx, val, cnt = idx.cpu().numpy(), val.cpu().numpy(), cnt.cpu().numpy()
         return [(idx[k, :cnt[k]].copy(), val[k, :cnt[k]].copy()) for k in range(len(lengths))]
 
+    # ---- threshold calibration: score a run against labelled times -------------------------
+    def scorer(self, thresholds, labels, tolerance: int, debounce: float = 0.0) -> "Scorer":
+        """A Scorer over this bank's channels (syldet_scorer_create): labels[c] are channel c's labelled sample numbers, a
+        detection within `tolerance` samples of one is a hit; score(outputs) then gives, for every channel and every candidate
+        threshold, detections, hits, false positives, repeats and the hits' offset sums, in one launch."""
+        return Scorer(self, thresholds, labels, tolerance, debounce)
+
     # ---- batch, host arrays -------------------------------------------------------
     def runHost(self, samples: np.ndarray, outputs: Optional[np.ndarray] = None, flags: Optional[np.ndarray] = None) -> Tuple[np.ndarray, np.ndarray]:
         """syldet_run: the batch call on host arrays, pipelined along time inside the library.  `outputs` / `flags`: arrays to
@@ -1022,6 +1029,130 @@ class Recordings:
                                                        idx.data_ptr(), None if val is None else val.data_ptr(), cap, cnt.data_ptr(),
                                                        det._stream_ptr(stream)))
         return idx, val, cnt
+
+    def scorer(self, thresholds, labels, tolerance: int, debounce: float = 0.0) -> "Scorer":
+        """A Scorer whose detectors are these recordings: labels[k], the labelled sample numbers of recording k, count from its
+        own start (SyllableDetector.scorer)."""
+        return Scorer(self.detector, thresholds, labels, tolerance, debounce, recordings=self)
+
+
+def _score_args(thresholds, labels):
+    thr = np.ascontiguousarray(thresholds, dtype=np.float64).reshape(-1)
+    labels = [np.ascontiguousarray(t, dtype=np.int64).reshape(-1) for t in labels]
+    begin = np.zeros(len(labels) + 1, np.int64)
+    np.cumsum([t.size for t in labels], out=begin[1:])
+    flat = np.concatenate(labels) if labels else np.zeros(0, np.int64)
+    return thr, np.ascontiguousarray(flat, dtype=np.int64), begin
+
+
+class Scorer:
+    """Threshold calibration (syldet_scorer_*, include/syldet.h "threshold calibration"): thresholds, labels and tolerance kept
+    on the device, so that score() is one launch over outputs that are there already.  A detector is a channel of the bank, or
+    (made by Recordings.scorer) a recording.  labels: a list of arrays, one per detector, of sorted sample numbers; tolerance in
+    samples; debounce in seconds.  The detector (and the Recordings) must outlive it."""
+
+    def __init__(self, detector: SyllableDetector, thresholds, labels, tolerance: int, debounce: float = 0.0, recordings: Optional[Recordings] = None):
+        self.detector = detector
+        self.recordings = recordings
+        labels = list(labels)
+        D = recordings.count if recordings is not None else detector.channels
+        if len(labels) != D:
+            raise ValueError("one array of labels per detector (%d given, %d detectors)" % (len(labels), D))
+        thr, flat, begin = _score_args(thresholds, labels)
+        self.thresholds = thr.copy()
+        self.labelCounts = np.diff(begin)
+        self.tolerance, self.debounce = int(tolerance), float(debounce)
+        self._h = _abi.Handle()
+        check(_abi.lib.syldet_scorer_create(detector._h, None if recordings is None else recordings._h, thr.ctypes.data_as(_abi.c_double_p), thr.size,
+                                            flat.ctypes.data_as(_abi.c_int64_p), begin.ctypes.data_as(_abi.c_int64_p), self.tolerance, self.debounce,
+                                            C.byref(self._h)))
+        d, k, n = C.c_int32(), C.c_int32(), C.c_int64()
+        check(_abi.lib.syldet_scorer_shape(self._h, C.byref(d), C.byref(k), C.byref(n)))
+        self.count, self.thresholdCount, self.labelCount = d.value, k.value, n.value
+
+    def close(self):
+        if getattr(self, "_h", None):
+            _abi.lib.syldet_scorer_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def score(self, outputs, output: int = 0, out=None, stream=None):
+        """outputs [C, n_evals, n_out] as run() wrote them (for recordings: of the packed rows, n_evals = rowEvaluations) ->
+        table [D, K, 6] int64 on the device: per detector and threshold (detections, hits, false positives, repeats, the sum of
+        the hits' offsets in samples, the sum of their squares), scoring output `output`.  Asynchronous on `stream`."""
+        torch = _torch()
+        det = self.detector
+        n_out = det.geometry.outputs
+        if not (outputs.is_cuda and outputs.dtype == torch.float32 and outputs.dim() == 3 and outputs.shape[0] == det.channels
+                and outputs.shape[2] == n_out and outputs.is_contiguous() and outputs.device.index == det.device):
+            raise ValueError("outputs must be a contiguous float32 CUDA tensor [channels, n_evals, outputs] on the detector's device")
+        if self.recordings is not None and outputs.shape[1] != self.recordings.rowEvaluations:
+            raise ValueError("outputs must hold the packed rows' %d evaluations" % self.recordings.rowEvaluations)
+        if not 0 <= int(output) < n_out:
+            raise ValueError("output must be in [0, %d)" % n_out)
+        want = (self.count, self.thresholdCount, _abi.SCORE_COLUMNS)
+        if out is None:
+            out = torch.zeros(want, dtype=torch.int64, device=outputs.device)
+        elif not (out.is_cuda and out.dtype == torch.int64 and tuple(out.shape) == want and out.is_contiguous() and out.device == outputs.device):
+            raise ValueError("out must be a contiguous int64 CUDA tensor of shape %s on the outputs' device" % (want,))
+        check(_abi.lib.syldet_score_device(self._h, outputs.data_ptr(), int(outputs.shape[1]), int(output), out.data_ptr(), det._stream_ptr(stream)))
+        return out
+
+    def choose(self, table, falsePositiveCost: float = 1.0):
+        """(k, threshold, totals [K, 6], costs [K]) of a table of score(): the tables summed over the detectors, cost_k = misses_k
+        + falsePositiveCost (false positives_k + repeats_k), and the lowest k of the smallest cost (syldet_score_choose).  A
+        device table is waited for and downloaded."""
+        if hasattr(table, "is_cuda"):
+            table = table.cpu().numpy()
+        k, totals, costs = chooseThreshold(table, self.labelCounts, falsePositiveCost)
+        return k, float(self.thresholds[k]), totals, costs
+
+
+def scoreHost(values, thresholds, labels, tolerance: int, firstIndex: int, hop: int, debounceFrames: int = 0) -> np.ndarray:
+    """syldet_score_host: one detector scored on the host, no device needed.  values: a 1-D float32 array (a strided view such as
+    outputs[c, :, o] is read in place), labels: its sorted labelled sample numbers -> table [K, 6] int64."""
+    v = np.asarray(values)
+    if v.dtype != np.float32 or v.ndim != 1:
+        raise ValueError("values must be a 1-D float32 array")
+    if v.size > 1 and (v.strides[0] <= 0 or v.strides[0] % 4):
+        v = np.ascontiguousarray(v)
+    stride = v.strides[0] // 4 if v.size > 1 else 1
+    thr, flat, _ = _score_args(thresholds, [labels])
+    table = np.zeros((thr.size, _abi.SCORE_COLUMNS), np.int64)
+    check(_abi.lib.syldet_score_host(C.cast(v.ctypes.data, _abi.c_float_p), v.size, stride, thr.ctypes.data_as(_abi.c_double_p), thr.size,
+                                     flat.ctypes.data_as(_abi.c_int64_p), flat.size, int(tolerance), int(firstIndex), int(hop), int(debounceFrames),
+                                     table.ctypes.data_as(_abi.c_int64_p)))
+    return table
+
+
+def chooseThreshold(table, labelCounts, falsePositiveCost: float = 1.0):
+    """syldet_score_choose: table [D, K, 6] (or [K, 6]: one detector) and each detector's label count -> (k, totals [K, 6] int64,
+    costs [K] float64): the lowest k of the smallest misses + falsePositiveCost (false positives + repeats)."""
+    t = np.ascontiguousarray(table, dtype=np.int64)
+    if t.ndim == 2:
+        t = t[None]
+    if t.ndim != 3 or t.shape[2] != _abi.SCORE_COLUMNS:
+        raise ValueError("table must be [detectors, thresholds, %d]" % _abi.SCORE_COLUMNS)
+    n = np.ascontiguousarray(labelCounts, dtype=np.int64).reshape(-1)
+    if n.size != t.shape[0]:
+        raise ValueError("one label count per detector")
+    best = C.c_int32()
+    totals = np.zeros((t.shape[1], _abi.SCORE_COLUMNS), np.int64)
+    costs = np.zeros(t.shape[1], np.float64)
+    check(_abi.lib.syldet_score_choose(t.ctypes.data_as(_abi.c_int64_p), t.shape[0], t.shape[1], n.ctypes.data_as(_abi.c_int64_p), float(falsePositiveCost),
+                                       C.byref(best), totals.ctypes.data_as(_abi.c_int64_p), costs.ctypes.data_as(_abi.c_double_p)))
+    return int(best.value), totals, costs
 
 
 def _pcm16(data) -> np.ndarray:
