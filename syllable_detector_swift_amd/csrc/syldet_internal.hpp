@@ -13,6 +13,15 @@ namespace sd {
 void set_error(const std::string &msg);
 int fail(int status, const std::string &msg);
 
+// A HIP call that must succeed: the call's text and the runtime's message become the last error, the status SYLDET_ERR_DEVICE
+// (for the files that include the HIP runtime's header).
+#define SYLDET_HIP(expr)                                                                         \
+    do {                                                                                         \
+        hipError_t _e = (expr);                                                                  \
+        if (_e != hipSuccess)                                                                    \
+            return fail(SYLDET_ERR_DEVICE, std::string(#expr) + ": " + hipGetErrorString(_e));  \
+    } while (0)
+
 // Deep, self-owned copy of a syldet_config_t.  `view` points into the vectors.
 struct OwnedConfig {
     syldet_config_t view{};
@@ -42,7 +51,7 @@ float sum_squares_tree(const int16_t *x, int64_t n, int64_t step);
 // is L a buffer length the level meters take (a power of two in [8, 4096])?
 inline bool levels_buffer_ok(int64_t L) { return L >= 8 && L <= 4096 && (L & (L - 1)) == 0; }
 
-// What the host-side files beside syldet_api.cpp need of a handle (syldet_recordings.cpp): channel_net is the caller's table of
+// What the host-side files that do not include syldet_handle.hpp need of a handle (syldet_recordings.cpp, syldet_score.cpp): channel_net is the caller's table of
 // syldet_create_multi / syldet_create_mixed ([channels], the handle's own memory), NULL on a plain bank.
 struct BankInfo {
     int channels, device;

@@ -16,13 +16,6 @@
 
 using sd::fail;
 
-#define SYLDET_HIP(expr)                                                                         \
-    do {                                                                                         \
-        hipError_t _e = (expr);                                                                  \
-        if (_e != hipSuccess)                                                                    \
-            return fail(SYLDET_ERR_DEVICE, std::string(#expr) + ": " + hipGetErrorString(_e));  \
-    } while (0)
-
 struct syldet_recordings {
     sd::BankInfo bank{};
     int K = 0;

@@ -21,13 +21,6 @@
 
 using namespace sd;
 
-#define SYLDET_HIP(expr)                                                                         \
-    do {                                                                                         \
-        hipError_t _e = (expr);                                                                  \
-        if (_e != hipSuccess)                                                                    \
-            return fail(SYLDET_ERR_DEVICE, std::string(#expr) + ": " + hipGetErrorString(_e));  \
-    } while (0)
-
 struct syldet_resampler {
     double rate_in = 0, rate_out = 0;
     int channels = 0, device = 0;

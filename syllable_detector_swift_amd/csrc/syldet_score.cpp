@@ -16,13 +16,6 @@
 
 using sd::fail;
 
-#define SYLDET_HIP(expr)                                                                         \
-    do {                                                                                         \
-        hipError_t _e = (expr);                                                                  \
-        if (_e != hipSuccess)                                                                    \
-            return fail(SYLDET_ERR_DEVICE, std::string(#expr) + ": " + hipGetErrorString(_e));  \
-    } while (0)
-
 static_assert(SYLDET_SCORE_COLUMNS == sd::kScoreColumns && SYLDET_SCORE_DETECTIONS == sd::kScoreDetections && SYLDET_SCORE_HITS == sd::kScoreHits &&
               SYLDET_SCORE_FALSE_POSITIVES == sd::kScoreFalsePositives && SYLDET_SCORE_REPEATS == sd::kScoreRepeats &&
               SYLDET_SCORE_SUM_OFFSET == sd::kScoreSumOffset && SYLDET_SCORE_SUM_OFFSET_SQUARED == sd::kScoreSumOffsetSquared,

@@ -30,13 +30,6 @@
 
 using namespace sd;
 
-#define SYLDET_HIP(expr)                                                                         \
-    do {                                                                                         \
-        hipError_t _e = (expr);                                                                  \
-        if (_e != hipSuccess)                                                                    \
-            return fail(SYLDET_ERR_DEVICE, std::string(#expr) + ": " + hipGetErrorString(_e));  \
-    } while (0)
-
 namespace {
 
 // ---- librccl, on demand ------------------------------------------------------------------------------------------

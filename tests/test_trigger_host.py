@@ -214,7 +214,7 @@ def test_arm_and_render_literally_under_asan_and_ubsan(tmp_path):
     r = subprocess.run([str(exe)], capture_output=True, text=True, timeout=120)
     assert r.returncode == 0 and r.stdout.strip() == "ok" and not r.stderr, (r.returncode, r.stdout, r.stderr)
     # the library's two functions are that header's
-    api = open(os.path.join(ROOT, "syllable_detector_swift_amd", "csrc", "syldet_api.cpp")).read()
+    api = open(os.path.join(ROOT, "syllable_detector_swift_amd", "csrc", "syldet_trigger.cpp")).read()
     assert "trigger_pulse_arm(" in api and "trigger_pulse_render(" in api
 
 

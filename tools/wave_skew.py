@@ -6,7 +6,7 @@
 
 Needs a stamped build of the library (-DSYLDET_S_STAMPS; a directory under syllable_detector_swift_amd/): every wave then leaves
 a record -- its SIMD and CU from the hardware-id register, the 100 MHz clock at its entry and after its last tile, its tiles
-(syldet_api.cpp writes them to SYLDET_FUSED_STAMPS_FILE).  Each variant runs in a child process of its own: 100 launches for
+(syldet_run.cpp writes them to SYLDET_FUSED_STAMPS_FILE).  Each variant runs in a child process of its own: 100 launches for
 the clock governor's ramp, then three that are recorded.  Prints, per recorded launch: which wave indices share a SIMD, the
 distribution of (end of the pair's first wave) / (end of its second) over all SIMD pairs, the spread of the workgroups' ends
 over CUs and XCDs, and the start ramp.  The stamped kernel carries two clock reads a wait more than the shipped one: the shape
