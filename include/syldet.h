@@ -877,6 +877,44 @@ int syldet_recordings_load_device_s16(syldet_recordings_t *r, const int16_t *d_s
 int syldet_recordings_events_device(syldet_recordings_t *r, const float *d_outputs, const uint8_t *d_flags, double debounce_seconds,
                                     int64_t *d_indices, float *d_values, int64_t capacity, int64_t *d_counts, void *hip_stream);
 
+/* ---- packed recordings at other rates: convert as the rows load ----
+ * An archive is rarely at one rate.  These calls are syldet_recordings_load_device for recordings that are each at a rate of their
+ * own: every recording of the plan is brought to the network's rate by the band-limited converter (the sinc convention above)
+ * straight into its place in the rows, in ONE launch ("recordings_load_sinc_kernel"), instead of one
+ * syldet_convert_rate_sinc_device call a recording into scratch rows and a load that copies them again.
+ *   src_samples[k]   the length of recording k at its own rate src_rate[k]; sample j of it is d_src[src_offset[k] + j src_step[k]],
+ *                    exactly as in syldet_recordings_load_device (the call is still the de-interleave)
+ *   THE PLAN is made as before, from lengths at the network's rate `rate` (the bank's sampling rate): the caller passes
+ *                    n_k = syldet_convert_rate_count(src_samples[k], src_rate[k], rate) to syldet_recordings_create, and the call
+ *                    refuses (SYLDET_ERR_INVALID_ARGUMENT, syldet_last_error names the recording) any k whose slots[k].n_samples
+ *                    differs from that count
+ *   d_rows           always fp32 [C][channel_stride]; an int16 source means x * 2^-15, as everywhere else in the library
+ * THE CONTRACT:
+ *   a recording at another rate   for every k with src_rate[k] != rate and every i < n_k, d_rows[row_k][offset_k + i] holds the bits
+ *       syldet_convert_rate_sinc_device (_s16) writes at output i when it is given that recording alone as one contiguous row
+ *       with the same (zero_crossings, beta, rolloff): the same table, the same fp64 position p_i = (double)i * src_rate[k] / rate
+ *       with i counted from the recording's start, the same taps in the same order
+ *   a recording at the network's rate   where src_rate[k] == rate the samples are copied (widened for int16), not low-passed
+ *   everywhere else   every other element of [0, row_samples) of every row is +0; [row_samples, channel_stride) is left untouched
+ *   downstream   by the packed-rows property above, on the fold kernel, the generic engine and the 1024-point kernel each
+ *       recording's outputs and flags are then bit for bit those of converting it alone and running it alone
+ * Statuses, decided before any device is touched, in this order: the argument checks of syldet_recordings_load_device (src_samples
+ * and src_rate may be NULL only without recordings); SYLDET_ERR_INVALID_ARGUMENT for src_samples[k] < 0 or a rate that is not
+ * positive and finite; the statuses of syldet_convert_rate_sinc_device for zero_crossings, beta or rolloff out of range; then, for
+ * each recording in turn, SYLDET_ERR_UNSUPPORTED for src_rate[k] / rate outside [1/16, 16] or H > 65536 (only where src_rate[k] !=
+ * rate) and SYLDET_ERR_INVALID_ARGUMENT for a length that differs from the plan's -- syldet_last_error names the recording.
+ * The launch rule is the plain load's: the handle keeps the sources, which here include src_samples, src_rate and the quality (kept
+ * apart from the plain load's, so the two may take turns); a load whose sources differ from the kept ones waits for the stream of
+ * the handle's last converting load and uploads its tables -- K + C words, never a list of workgroups -- with one blocking copy;
+ * the same layout again is one launch without allocation, synchronisation or copy.  The filter's table comes from the (Z, beta)
+ * cache of syldet_convert_rate_sinc_device, with its blocking copy on first use.                                               */
+int syldet_recordings_load_sinc_device(syldet_recordings_t *r, const float *d_src, const int64_t *src_offset, const int32_t *src_step,
+                                       const int64_t *src_samples, const double *src_rate, int32_t zero_crossings, double beta,
+                                       double rolloff, float *d_rows, int64_t channel_stride, void *hip_stream);
+int syldet_recordings_load_sinc_device_s16(syldet_recordings_t *r, const int16_t *d_src, const int64_t *src_offset, const int32_t *src_step,
+                                           const int64_t *src_samples, const double *src_rate, int32_t zero_crossings, double beta,
+                                           double rolloff, float *d_rows, int64_t channel_stride, void *hip_stream);
+
 /* ---- threshold calibration: score a run against labelled times ----
  * Which threshold to ship, and how late and how jittery the trigger is at it: the reference leaves the question to MATLAB
  * (convert_to_text.m:70-72 only copies trigger_thresholds in).  Here the outputs of a run, which are on the device already, are

@@ -11,7 +11,7 @@ from .config import (InvalidValue, MismatchedLength, MissingValue, NeuralNet, Ne
                      createWindow, frequencyIndexRange)
 from .bank import PinnedArray, ShardedSyllableDetectorBank, shard_table
 from .detector import (Recordings, Scorer, SyllableDetector, chooseThreshold, configsCompatible, configsShareClock, fusedFormOfConfig,
-                       planRecordings, scoreHost)
+                       planRecordings, recordingLengths, scoreHost)
 from .resampler import ResamplerLinear, ResamplerSinc, sincReady, convertRate, deinterleave, sincCoefficient, sincDefaults, sincTaps
 
 __all__ = ["SyllableDetector", "SyllableDetectorConfig", "NeuralNet", "NeuralNetLayer", "ProcessingFunction",
@@ -19,4 +19,4 @@ __all__ = ["SyllableDetector", "SyllableDetectorConfig", "NeuralNet", "NeuralNet
            "SyllableDetectorError", "frequencyIndexRange", "createWindow", "ResamplerLinear", "deinterleave",
            "convertRate", "ResamplerSinc", "sincReady", "sincCoefficient", "sincTaps", "sincDefaults",
            "ShardedSyllableDetectorBank", "PinnedArray", "shard_table", "configsCompatible",
-           "configsShareClock", "fusedFormOfConfig", "Recordings", "planRecordings", "Scorer", "scoreHost", "chooseThreshold"]
+           "configsShareClock", "fusedFormOfConfig", "Recordings", "planRecordings", "recordingLengths", "Scorer", "scoreHost", "chooseThreshold"]

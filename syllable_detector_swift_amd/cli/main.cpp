@@ -14,8 +14,8 @@
 // reference has Core Audio deliver the network's rate (SyllableDetector.swift:19-23), this tool converts the decoded
 // file itself: by linear interpolation with fp64 positions (syldet_convert_rate_device; the default) or, with --resample sinc,
 // band-limited, which is what Core Audio's delivery is (syldet_convert_rate_sinc_device; a 16-bit file stays int16 up to the
-// converter); events of different channels are interleaved buffer by buffer like the
-// reference's read loop (main.swift:126-130), with --chunk frames per buffer (AVAssetReader's buffer size is
+// converter; under --batch such files join the bank and are converted as its rows load, syldet_recordings_load_sinc_device);
+// events of different channels are interleaved buffer by buffer like the reference's read loop (main.swift:126-130), with --chunk frames per buffer (AVAssetReader's buffer size is
 // not specified; 8192 is what it typically vends for linear PCM).
 
 #include <hip/hip_runtime.h>
@@ -62,10 +62,10 @@ void usage(FILE *to)
                  "      --ttl-buffer <L>:\n      Samples per input and output buffer: a power of two from 8 to 4096 (default 32).\n"
                  "      --ttl-latency <seconds>:\n      Delay of the output behind the input (default 0).\n"
                  "      --ttl-onsets <out.tsv>:\n      Also write the rising edges of the trigger tracks, one line each, tab separated: the track, the sample, the time in seconds.\n"
-                 "      --batch:\n      Run the audio files through one detector bank instead of one bank a file: every track of every file becomes a recording in the bank's rows, and only the detections come back from the GPU. The output is the same.\n"
+                 "      --batch:\n      Run the audio files through one detector bank instead of one bank a file: every track of every file becomes a recording in the bank's rows, and only the detections come back from the GPU. The output is the same. A file at another sampling rate than the network's joins the bank under --resample sinc (its rate within a sixteenth and sixteen times the network's): it is converted as the rows load, and a batch that holds such a file runs as 32-bit float. Under --resample linear (the default), or outside that range, such a file ends the batch and runs alone, as without --batch.\n"
                  "      --batch-rows <N>:\n      Rows of the bank under --batch (default 64; no more than there are tracks).\n"
-                 "      --batch-bytes <B>:\n      Consecutive files share a batch until their samples pass B bytes (default 2147483648).\n"
-                 "      --score <labels.tsv>:\n      Under --batch, also score every track against labelled times for a grid of candidate thresholds: lines of file, track and sample, tab separated (the file as -a names it, the sample counted from the file's start at the network's sampling rate). Needs --score-out.\n"
+                 "      --batch-bytes <B>:\n      Consecutive files share a batch until their samples pass B bytes (default 2147483648); a file that is converted counts with the bytes it has at its own rate.\n"
+                 "      --score <labels.tsv>:\n      Under --batch, also score every track against labelled times for a grid of candidate thresholds: lines of file, track and sample, tab separated (the file as -a names it, the sample counted from the file's start at the network's sampling rate, also for a file at another rate). A file that does not go through the bank (see --batch) is left out, with a message. Needs --score-out.\n"
                  "      --score-out <table.tsv>:\n      Where --score writes its table, one line per threshold, tab separated: threshold, detections, hits, misses, false positives, repeats, the mean and the standard deviation of the hits' offsets in samples, the cost; a last line names the threshold of the smallest cost.\n"
                  "      --score-thresholds <lo:hi:n>:\n      The grid: n thresholds from lo to hi (default 0:1:101; at most 4096).\n"
                  "      --score-tolerance <seconds>:\n      A detection this close to a label is a hit (default 0.02).\n"
@@ -442,9 +442,10 @@ struct BatchOpt {
 struct BatchFile {
     std::string path;
     wav::Info info;
-    std::vector<float> f32;                                 // the frames as decoded, or (a 16-bit file at the network's rate) ...
+    std::vector<float> f32;                                 // the frames as decoded, or (a 16-bit file) ...
     std::vector<int16_t> s16;                               // ... as stored
     bool is16 = false;
+    bool convert = false;                                   // at another rate than the network's: converted as the rows load (--resample sinc)
     size_t bytes() const { return is16 ? s16.size() * sizeof(int16_t) : f32.size() * sizeof(float); }
 };
 
@@ -503,13 +504,19 @@ bool read_labels(const std::string &path, ScoreRun &run, std::string &err)
 
 // One batch: returns 0, or 2 for device trouble (no line of the batch is printed then, but the files' names are)
 int run_batch(std::vector<BatchFile> &files, const std::vector<syldet_config_t *> &cfgs, int device, double debounce_s, int64_t chunk,
-              long max_rows, bool headers, ScoreRun *score)
+              long max_rows, bool headers, ScoreRun *score, const ResampleOpt &conv)
 {
     if (files.empty()) return 0;
     const syldet_config_t *cfg = cfgs[0];
-    bool all16 = true;
-    for (const BatchFile &f : files) all16 = all16 && f.is16;
-    std::vector<int64_t> lengths, src_offset;
+    bool all16 = true, converting = false;
+    for (const BatchFile &f : files) {
+        all16 = all16 && f.is16;
+        converting = converting || f.convert;
+    }
+    // a batch that holds a file at another rate: every recording is planned with its length at the network's rate and loaded
+    // through the converting load (syldet_recordings_load_sinc_device*: the files at the network's rate are copied), fp32 rows
+    std::vector<int64_t> lengths, src_offset, src_samples;
+    std::vector<double> src_rate;
     std::vector<int32_t> network, src_step;
     std::vector<int64_t> file_at(files.size());             // where a file's frames lie in the upload, in elements (whole 16 bytes)
     int64_t total = 0;
@@ -523,7 +530,9 @@ int run_batch(std::vector<BatchFile> &files, const std::vector<syldet_config_t *
         }
         file_at[i] = total;
         for (int t = 0; t < f.info.channels; t++) {
-            lengths.push_back(f.info.frames);
+            lengths.push_back(converting ? syldet_convert_rate_count(f.info.frames, f.info.rate, cfg->sampling_rate) : f.info.frames);
+            src_samples.push_back(f.info.frames);
+            src_rate.push_back(f.info.rate);
             network.push_back(t);
             src_offset.push_back(total + t);
             src_step.push_back(f.info.channels);
@@ -581,7 +590,7 @@ int run_batch(std::vector<BatchFile> &files, const std::vector<syldet_config_t *
         if (hipSetDevice(device) != hipSuccess || hipStreamCreate(&stream) != hipSuccess) { rc = 2; break; }
         const size_t el = all16 ? sizeof(int16_t) : sizeof(float);
         DevBuf d_src, d_rows, d_out, d_flags, d_idx, d_val, d_cnt;
-        if (!d_src.alloc((size_t)total * el) || !d_rows.alloc((size_t)C * row_samples * el) || !d_out.alloc((size_t)C * row_evals * n_out * sizeof(float)) ||
+        if (!d_src.alloc((size_t)total * el) || !d_rows.alloc((size_t)C * row_samples * (converting ? sizeof(float) : el)) || !d_out.alloc((size_t)C * row_evals * n_out * sizeof(float)) ||
             !d_flags.alloc((size_t)C * row_evals) || !d_cnt.alloc((size_t)K * sizeof(int64_t))) { rc = 2; break; }
         bool ok = true;
         for (size_t i = 0; ok && i < files.size(); i++) {
@@ -590,7 +599,13 @@ int run_batch(std::vector<BatchFile> &files, const std::vector<syldet_config_t *
                                 hipMemcpyHostToDevice, stream) == hipSuccess;
         }
         if (!ok) { rc = 2; break; }
-        if (all16) {
+        if (converting) {
+            st = all16 ? syldet_recordings_load_sinc_device_s16(r, (const int16_t *)d_src.p, src_offset.data(), src_step.data(), src_samples.data(), src_rate.data(),
+                                                                conv.zero_crossings, conv.beta, conv.rolloff, (float *)d_rows.p, row_samples, stream)
+                       : syldet_recordings_load_sinc_device(r, (const float *)d_src.p, src_offset.data(), src_step.data(), src_samples.data(), src_rate.data(),
+                                                            conv.zero_crossings, conv.beta, conv.rolloff, (float *)d_rows.p, row_samples, stream);
+            if (!st) st = syldet_run_device(h, (const float *)d_rows.p, row_samples, row_samples, (float *)d_out.p, (uint8_t *)d_flags.p, stream);
+        } else if (all16) {
             st = syldet_recordings_load_device_s16(r, (const int16_t *)d_src.p, src_offset.data(), src_step.data(), (int16_t *)d_rows.p, row_samples, stream);
             if (!st) st = syldet_run_device_s16(h, (const int16_t *)d_rows.p, row_samples, row_samples, (float *)d_out.p, (uint8_t *)d_flags.p, stream);
         } else {
@@ -711,8 +726,9 @@ bool write_score_table(const ScoreOpt &opt, const ScoreRun &run)
     return std::fclose(f) == 0;
 }
 
-// The loop over the -a files under --batch: consecutive files that can share a bank (readable, at the network's rate, the right
-// number of tracks) gather until their samples pass opt.bytes; any other file ends the batch and is processed alone in its place.
+// The loop over the -a files under --batch: consecutive files that can share a bank (readable, the right number of tracks, at the
+// network's rate or -- under --resample sinc -- at a rate the band-limited converter takes) gather until their samples pass
+// opt.bytes; any other file ends the batch and is processed alone in its place.
 int process_batched(const std::vector<std::string> &audio, const std::vector<syldet_config_t *> &cfgs, int device, double debounce_s, bool have_debounce,
                     int64_t chunk, const BatchOpt &opt, const ResampleOpt &conv, ScoreRun *score)
 {
@@ -722,7 +738,7 @@ int process_batched(const std::vector<std::string> &audio, const std::vector<syl
     std::vector<BatchFile> files;
     size_t held = 0;
     auto flush = [&]() {
-        if (run_batch(files, cfgs, device, deb, chunk, opt.rows, headers, score) == 2) rc = 2;
+        if (run_batch(files, cfgs, device, deb, chunk, opt.rows, headers, score, conv) == 2) rc = 2;
         held = 0;
     };
     for (const std::string &p : audio) {
@@ -730,7 +746,10 @@ int process_batched(const std::vector<std::string> &audio, const std::vector<syl
         f.path = p;
         std::string err;
         const bool probed = wav::probe(p, f.info, err);
-        if (probed && f.info.rate == cfgs[0]->sampling_rate && f.info.channels > 0 && f.info.frames > 0 &&
+        // (syldet_sinc_taps is -1 for what the converter refuses: a ratio outside [1/16, 16], a filter too wide)
+        f.convert = probed && f.info.rate != cfgs[0]->sampling_rate;
+        const bool rate_ok = probed && (!f.convert || (conv.sinc && syldet_sinc_taps(f.info.rate, cfgs[0]->sampling_rate, conv.zero_crossings, conv.rolloff) >= 0));
+        if (probed && rate_ok && f.info.channels > 0 && f.info.frames > 0 &&
             (cfgs.size() == 1 || (size_t)f.info.channels == cfgs.size())) {
             f.is16 = f.info.format == 1 && f.info.bits == 16;
             err.clear();
@@ -741,7 +760,7 @@ int process_batched(const std::vector<std::string> &audio, const std::vector<syl
                 continue;
             }
         }
-        // another rate, unreadable, no tracks, the wrong number of tracks: exactly as without --batch, in its place
+        // another rate that does not join the bank, unreadable, no tracks, the wrong number of tracks: exactly as without --batch, in its place
         flush();
         if (score && score->labels.count(p)) std::fprintf(stderr, "--score: %s does not go through the bank; its labels are left out.\n", p.c_str());
         if (headers) std::printf("%s\n", p.c_str());

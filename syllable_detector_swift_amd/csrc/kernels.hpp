@@ -407,6 +407,31 @@ hipError_t launch_recordings_events(const RecEventDev *desc, int K, int64_t row_
                                     int64_t first_index, int64_t hop, int64_t debounce_frames, int64_t *indices, float *values,
                                     int64_t capacity, int64_t *counts, hipStream_t stream);
 
+// ---- packed recordings at other rates (kernels_recordings_sinc.hip; syldet_recordings_load_sinc_device* of include/syldet.h) ----
+// One slot of the plan as the converting load reads it, in the order of RecSlotDev's table.  Its span is [offset, span_end): up to
+// the next recording's offset in the row, or to row_samples behind the row's last.  Positions [offset, offset + n_out) are the
+// recording's outputs (copy: its own samples, n_out <= n_in), the rest of the span is +0.
+struct RecSincDev {
+    int64_t offset, n_out, span_end, src_offset, n_in;
+    double rate_in, H;                       // the recording's rate; H = Z / s of its design
+    float scale, idx_scale;                  // float(s); float(N / H)
+    int32_t src_step, copy;                  // copy: at the network's rate, not converted
+};
+struct RecSincDesc {
+    const RecSincDev *slots;
+    const int32_t *row_begin;                // [C + 1] (RecLoadDesc's)
+    // row c's slots own consecutive workgroups of the row: slot row_begin[c] + j the workgroups [wg[j], wg[j + 1]) with wg =
+    // wg_begin + row_begin[c] + c, n_c + 1 entries a row (wg[0] = 0, wg[n_c] the row's count): K + C words in all, which the
+    // kernel searches with its block index
+    const int32_t *wg_begin;
+    int grid_x;                              // the greatest count of a row; ceil(row_samples / kSincBlockOut) where a row has no recording
+    int64_t row_samples;
+};
+// rows [C][stride] fp32 (the first row_samples of each) <- every recording converted to rate_out (or copied), +0 everywhere else;
+// src fp32 or (s16) int16; table: the unit filter's N + 4 floats on the device, 16-byte aligned
+hipError_t launch_recordings_load_sinc(const RecSincDesc &d, const void *src, bool s16, double rate_out, const float *table, int N,
+                                       float *rows, int64_t stride, int C, hipStream_t stream);
+
 // ---- threshold calibration (kernels_score.hip; syldet_score_device of include/syldet.h) ----
 // What a scorer keeps on the device.  A detector is a channel (slots == nullptr: its evaluations are row `det`) or a recording
 // (slots [D]: its own part of its row).

@@ -62,4 +62,14 @@ struct BankInfo {
 };
 void bank_info(const syldet_t *h, BankInfo *out);
 
+// The band-limited converter's host side (syldet_resampler.cpp), for the packed recordings' converting load (syldet_recordings.cpp).
+// sinc_quality: the ranges of Z, beta and rolloff (SYLDET_ERR_INVALID_ARGUMENT).  sinc_design: s and H of the sinc convention of
+// include/syldet.h with the statuses of syldet_convert_rate_sinc_device in their order -- the rates, sinc_quality, the ratio, H.
+int sinc_quality(int32_t Z, double beta, double rho);
+int sinc_design(double rate_in, double rate_out, int32_t Z, double beta, double rho, double *s, double *H);
+// Calls use(table, entries, ctx) with the unit filter's table of (Z, beta) on the current device (the cache of
+// syldet_convert_rate_sinc_device: a blocking copy on first use), holding the cache's lock until use returns: use queues the
+// launch that reads the table.  Returns use's status, or the lookup's.
+int sinc_table_use(int32_t Z, double beta, int (*use)(const float *table, int entries, void *ctx), void *ctx);
+
 }  // namespace sd

@@ -1,9 +1,10 @@
 // syldet_recordings.cpp -- packed recordings (include/syldet.h, "packed recordings"): the plan that lays many recordings of
-// different lengths end to end in a bank's rows, and the handle that keeps the plan's tables on the device so that the two
-// device calls (kernels_recordings.hip) are launches only.
+// different lengths end to end in a bank's rows, and the handle that keeps the plan's tables on the device so that the
+// device calls (kernels_recordings.hip; kernels_recordings_sinc.hip for recordings at other rates) are launches only.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <cmath>
 #include <cstring>
 #include <memory>
 #include <new>
@@ -28,9 +29,23 @@ struct syldet_recordings {
     std::vector<int64_t> src_offset;         // [K] the sources the device table holds (empty: none yet)
     std::vector<int32_t> src_step;
     hipStream_t last_load = nullptr;
-    void *d_blob = nullptr;                  // table | events | row_begin | tile_first
+    void *d_blob = nullptr;                  // table | events | row_begin | tile_first | the converting load's slots | its workgroup prefixes
     sd::RecLoadDesc load{};
     const sd::RecEventDev *d_events = nullptr;
+    // the converting load (syldet_recordings_load_sinc_device*): its own kept sources and tables, so that plain and converting
+    // loads may take turns on one handle
+    std::vector<int32_t> row_begin;          // [C + 1] the table's rows
+    bool sinc_kept = false;
+    hipStream_t sinc_last_load = nullptr;
+    std::vector<int64_t> sinc_offset, sinc_samples;   // [K]
+    std::vector<int32_t> sinc_step;
+    std::vector<double> sinc_rate;
+    int32_t sinc_Z = 0;
+    double sinc_beta = 0.0, sinc_rho = 0.0;
+    std::vector<char> sinc_host;             // slots [K] | prefixes [K + C]: what one copy uploads
+    size_t sinc_wg_at = 0;                   // where the prefixes begin in it (and behind d_sinc)
+    char *d_sinc = nullptr;                  // (inside d_blob)
+    sd::RecSincDesc sinc{};
 };
 
 namespace {
@@ -136,6 +151,115 @@ int load_impl(syldet_recordings_t *r, const void *d_src, bool s16, const int64_t
     return SYLDET_OK;
 }
 
+// ---- the converting load: recordings at other rates brought to the network's as the rows load ----
+struct SincLaunch {
+    syldet_recordings_t *r;
+    const void *d_src;
+    bool s16;
+    float *d_rows;
+    int64_t stride;
+    hipStream_t stream;
+};
+
+int sinc_launch(const float *table, int entries, void *ctx)
+{
+    const SincLaunch &a = *(const SincLaunch *)ctx;
+    SYLDET_HIP(sd::launch_recordings_load_sinc(a.r->sinc, a.d_src, a.s16, a.r->bank.sampling_rate, table, entries, a.d_rows, a.stride,
+                                               a.r->bank.channels, a.stream));
+    return SYLDET_OK;
+}
+
+int load_sinc_impl(syldet_recordings_t *r, const void *d_src, bool s16, const int64_t *src_offset, const int32_t *src_step,
+                   const int64_t *src_samples, const double *src_rate, int32_t Z, double beta, double rho, float *d_rows,
+                   int64_t channel_stride, hipStream_t stream)
+{
+    if (!r || !d_rows || (r->K > 0 && (!d_src || !src_offset || !src_samples || !src_rate))) return fail(SYLDET_ERR_INVALID_ARGUMENT, "NULL argument");
+    if (channel_stride < r->row_samples) return fail(SYLDET_ERR_INVALID_ARGUMENT, "channel_stride below row_samples");
+    const int K = r->K;
+    const double rate = r->bank.sampling_rate;
+    for (int k = 0; k < K; k++) {
+        const int32_t step = src_step ? src_step[k] : 1;
+        if (src_offset[k] < 0 || step < 1) return fail(SYLDET_ERR_INVALID_ARGUMENT, "a negative source offset or a step below 1 (recording " + std::to_string(k) + ")");
+    }
+    for (int k = 0; k < K; k++) {
+        if (src_samples[k] < 0) return fail(SYLDET_ERR_INVALID_ARGUMENT, "src_samples[" + std::to_string(k) + "] is negative");
+        if (!(src_rate[k] > 0.0) || !std::isfinite(src_rate[k]))
+            return fail(SYLDET_ERR_INVALID_ARGUMENT, "src_rate[" + std::to_string(k) + "] is not a positive sampling rate");
+    }
+    if (int st = sd::sinc_quality(Z, beta, rho)) return st;
+    bool same = r->sinc_kept && r->sinc_Z == Z && r->sinc_beta == beta && r->sinc_rho == rho;
+    for (int k = 0; k < K; k++) {
+        if (src_rate[k] != rate) {
+            double s = 0.0, H = 0.0;
+            if (int st = sd::sinc_design(src_rate[k], rate, Z, beta, rho, &s, &H))
+                return fail(st, std::string(syldet_last_error()) + " (recording " + std::to_string(k) + ")");
+        }
+        const int64_t n = syldet_convert_rate_count(src_samples[k], src_rate[k], rate);
+        // (a copied recording reads its first n samples: n <= src_samples whatever the division rounds to)
+        if (n != r->slots[(size_t)k].n_samples || (src_rate[k] == rate && n > src_samples[k]))
+            return fail(SYLDET_ERR_INVALID_ARGUMENT, "recording " + std::to_string(k) + " was planned with " + std::to_string(r->slots[(size_t)k].n_samples) +
+                                                         " samples, but its " + std::to_string(src_samples[k]) + " source samples make " + std::to_string(n) +
+                                                         " at the network's rate (syldet_convert_rate_count)");
+        same = same && r->sinc_offset[(size_t)k] == src_offset[k] && r->sinc_step[(size_t)k] == (src_step ? src_step[k] : 1) &&
+               r->sinc_samples[(size_t)k] == src_samples[k] && r->sinc_rate[(size_t)k] == src_rate[k];
+    }
+    if (r->row_samples == 0) return SYLDET_OK;
+    // (a row's workgroups: one for every kSincBlockOut positions and at most one more a recording)
+    if (r->row_samples / sd::kSincBlockOut + K + 1 > 0x7fffffff) return fail(SYLDET_ERR_UNSUPPORTED, "rows too long for one launch of the converting load");
+    SYLDET_HIP(hipSetDevice(r->bank.device));
+    if (!same) {
+        // new sources: the tables are re-made behind the last converting load that reads them (the one copy the header speaks of)
+        if (r->sinc_kept) SYLDET_HIP(hipStreamSynchronize(r->sinc_last_load));
+        r->sinc_kept = false;
+        r->sinc_offset.assign(src_offset, src_offset + K);   // (reserved by syldet_recordings_create: no allocation)
+        r->sinc_step.assign((size_t)K, 1);
+        if (src_step) r->sinc_step.assign(src_step, src_step + K);
+        r->sinc_samples.assign(src_samples, src_samples + K);
+        r->sinc_rate.assign(src_rate, src_rate + K);
+        r->sinc_Z = Z; r->sinc_beta = beta; r->sinc_rho = rho;
+        const int C = r->bank.channels;
+        const int N = sd::sinc_table_entries(Z);
+        sd::RecSincDev *slots = (sd::RecSincDev *)r->sinc_host.data();
+        int32_t *wg = (int32_t *)(r->sinc_host.data() + r->sinc_wg_at);
+        int64_t grid = 0;
+        for (int c = 0; c < C; c++) {
+            const int sb = r->row_begin[(size_t)c], se = r->row_begin[(size_t)c + 1];
+            int64_t at = 0;                                  // workgroups of the row so far
+            for (int i = sb; i < se; i++) {
+                const int k = r->order[(size_t)i];
+                sd::RecSincDev &d = slots[i];
+                d = sd::RecSincDev{};
+                d.offset = r->table[(size_t)i].offset;
+                d.n_out = r->table[(size_t)i].n_samples;
+                d.span_end = i + 1 < se ? r->table[(size_t)i + 1].offset : r->row_samples;
+                d.src_offset = src_offset[k];
+                d.n_in = src_samples[k];
+                d.src_step = src_step ? src_step[k] : 1;
+                d.rate_in = src_rate[k];
+                d.copy = src_rate[k] == rate;
+                if (!d.copy) {
+                    double s = 0.0;
+                    (void)sd::sinc_design(src_rate[k], rate, Z, beta, rho, &s, &d.H);    // (checked above)
+                    d.scale = (float)s;
+                    d.idx_scale = (float)((double)N / d.H);  // as launch_sinc (kernels_sinc.hip) makes it
+                }
+                wg[i + c] = (int32_t)at;
+                at += (d.span_end - d.offset + sd::kSincBlockOut - 1) / sd::kSincBlockOut;
+            }
+            if (se > sb) wg[se + c] = (int32_t)at;
+            else at = (r->row_samples + sd::kSincBlockOut - 1) / sd::kSincBlockOut;      // a row without a recording: +0
+            grid = std::max(grid, at);
+        }
+        r->sinc.grid_x = (int)grid;
+        hipError_t e = hipMemcpy(r->d_sinc, r->sinc_host.data(), r->sinc_host.size(), hipMemcpyHostToDevice);
+        if (e != hipSuccess) return fail(SYLDET_ERR_DEVICE, std::string("hipMemcpy: ") + hipGetErrorString(e));
+        r->sinc_kept = true;
+    }
+    r->sinc_last_load = stream;
+    SincLaunch a{r, d_src, s16, d_rows, channel_stride, stream};
+    return sd::sinc_table_use(Z, beta, sinc_launch, &a);
+}
+
 }  // namespace
 
 extern "C" {
@@ -239,8 +363,21 @@ int syldet_recordings_create(const syldet_t *h, const int64_t *n_samples, const 
     }
     const size_t n_table = up16(r->table.size() * sizeof(sd::RecSlotDev)), n_events = up16(events.size() * sizeof(sd::RecEventDev)),
                  n_begin = up16(row_begin.size() * sizeof(int32_t)), n_tiles = up16(tile_first.size() * sizeof(int32_t));
+    // the converting load's tables, K + C words: room for them now, so that no load ever allocates
+    r->sinc_wg_at = up16(r->table.size() * sizeof(sd::RecSincDev));
+    const size_t n_sinc = r->sinc_wg_at + up16((r->table.size() + (size_t)b.channels) * sizeof(int32_t));
+    try {
+        r->row_begin = row_begin;
+        r->sinc_host.assign(n_sinc, 0);
+        r->sinc_offset.reserve((size_t)r->K);
+        r->sinc_samples.reserve((size_t)r->K);
+        r->sinc_step.reserve((size_t)r->K);
+        r->sinc_rate.reserve((size_t)r->K);
+    } catch (const std::bad_alloc &) {
+        return fail(SYLDET_ERR_OUT_OF_MEMORY, "out of memory");
+    }
     SYLDET_HIP(hipSetDevice(b.device));
-    hipError_t e = hipMalloc(&r->d_blob, n_table + n_events + n_begin + n_tiles + 16);
+    hipError_t e = hipMalloc(&r->d_blob, n_table + n_events + n_begin + n_tiles + n_sinc + 16);
     if (e != hipSuccess) {
         r->d_blob = nullptr;
         return fail(e == hipErrorOutOfMemory ? SYLDET_ERR_OUT_OF_MEMORY : SYLDET_ERR_DEVICE, std::string("hipMalloc: ") + hipGetErrorString(e));
@@ -252,6 +389,8 @@ int syldet_recordings_create(const syldet_t *h, const int64_t *n_samples, const 
     r->load = sd::RecLoadDesc{(const sd::RecSlotDev *)base, (const int32_t *)(base + n_table + n_events),
                               (const int32_t *)(base + n_table + n_events + n_begin), tiles, r->row_samples};
     r->d_events = (const sd::RecEventDev *)(base + n_table);
+    r->d_sinc = base + n_table + n_events + n_begin + n_tiles;
+    r->sinc = sd::RecSincDesc{(const sd::RecSincDev *)r->d_sinc, r->load.row_begin, (const int32_t *)(r->d_sinc + r->sinc_wg_at), 0, r->row_samples};
     *out = r.release();
     return SYLDET_OK;
 }
@@ -294,6 +433,22 @@ int syldet_recordings_load_device_s16(syldet_recordings_t *r, const int16_t *d_s
                                       int16_t *d_rows, int64_t channel_stride, void *hip_stream)
 {
     return load_impl(r, d_src, true, src_offset, src_step, d_rows, channel_stride, (hipStream_t)hip_stream);
+}
+
+int syldet_recordings_load_sinc_device(syldet_recordings_t *r, const float *d_src, const int64_t *src_offset, const int32_t *src_step,
+                                       const int64_t *src_samples, const double *src_rate, int32_t zero_crossings, double beta, double rolloff,
+                                       float *d_rows, int64_t channel_stride, void *hip_stream)
+{
+    return load_sinc_impl(r, d_src, false, src_offset, src_step, src_samples, src_rate, zero_crossings, beta, rolloff, d_rows, channel_stride,
+                          (hipStream_t)hip_stream);
+}
+
+int syldet_recordings_load_sinc_device_s16(syldet_recordings_t *r, const int16_t *d_src, const int64_t *src_offset, const int32_t *src_step,
+                                           const int64_t *src_samples, const double *src_rate, int32_t zero_crossings, double beta,
+                                           double rolloff, float *d_rows, int64_t channel_stride, void *hip_stream)
+{
+    return load_sinc_impl(r, d_src, true, src_offset, src_step, src_samples, src_rate, zero_crossings, beta, rolloff, d_rows, channel_stride,
+                          (hipStream_t)hip_stream);
 }
 
 int syldet_recordings_events_device(syldet_recordings_t *r, const float *d_outputs, const uint8_t *d_flags, double debounce_seconds,

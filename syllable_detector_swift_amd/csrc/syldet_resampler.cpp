@@ -185,14 +185,24 @@ double sinc_pi(double x)
     return y == 0.0 ? 1.0 : std::sin(y) / y;
 }
 
-// s and H of the convention; the statuses of the device calls, in their order
-int sinc_design(double rate_in, double rate_out, int32_t Z, double beta, double rho, double *s, double *H)
+}  // namespace
+
+// the ranges of the quality (syldet_internal.hpp)
+int sd::sinc_quality(int32_t Z, double beta, double rho)
 {
-    if (!(rate_in > 0.0) || !(rate_out > 0.0) || !std::isfinite(rate_in) || !std::isfinite(rate_out))
-        return fail(SYLDET_ERR_INVALID_ARGUMENT, "sampling rates must be positive");
     if (Z < 4 || Z > 64) return fail(SYLDET_ERR_INVALID_ARGUMENT, "zero_crossings must be in [4, 64]");
     if (!(beta >= 0.0 && beta <= 20.0)) return fail(SYLDET_ERR_INVALID_ARGUMENT, "beta must be in [0, 20]");
     if (!(rho > 0.0 && rho <= 1.0)) return fail(SYLDET_ERR_INVALID_ARGUMENT, "rolloff must be in (0, 1]");
+    return SYLDET_OK;
+}
+
+// s and H of the convention; the statuses of the device calls, in their order (syldet_internal.hpp: the packed recordings'
+// converting load designs every recording through this function too, so its scalars are these doubles)
+int sd::sinc_design(double rate_in, double rate_out, int32_t Z, double beta, double rho, double *s, double *H)
+{
+    if (!(rate_in > 0.0) || !(rate_out > 0.0) || !std::isfinite(rate_in) || !std::isfinite(rate_out))
+        return fail(SYLDET_ERR_INVALID_ARGUMENT, "sampling rates must be positive");
+    if (int st = sinc_quality(Z, beta, rho)) return st;
     const double ratio = rate_in / rate_out;
     if (!(ratio >= 1.0 / 16.0 && ratio <= 16.0)) return fail(SYLDET_ERR_UNSUPPORTED, "rate_in / rate_out must be in [1/16, 16]");
     *s = (rate_out / rate_in < 1.0 ? rate_out / rate_in : 1.0) * rho;
@@ -200,6 +210,8 @@ int sinc_design(double rate_in, double rate_out, int32_t Z, double beta, double 
     if (!(*H <= kSincMaxHalfWidth)) return fail(SYLDET_ERR_UNSUPPORTED, "the filter's half width Z / s exceeds 65536 input samples");
     return SYLDET_OK;
 }
+
+namespace {
 
 // The unit filter's table on the host: g[j] = sinc(j Z / N) * kaiser(j / N) for j < N = sinc_table_entries(Z), zeros from g[N] on
 // (N + 4 floats).  The one place its values are made: the cache below and every streaming handle copy these floats.
@@ -277,6 +289,15 @@ int convert_rate_sinc(const T *d_in, int64_t n_in, int64_t in_stride, int32_t n_
 }
 
 }  // namespace
+
+int sd::sinc_table_use(int32_t Z, double beta, int (*use)(const float *table, int entries, void *ctx), void *ctx)
+{
+    const float *table = nullptr;
+    int N = 0;
+    std::lock_guard<std::mutex> lock(g_sinc_mutex);          // from the table's lookup to the end of the launch (see sinc_table)
+    if (int st = sinc_table(Z, beta, &table, &N)) return st;
+    return use(table, N, ctx);
+}
 
 // ---- the streaming form (the streaming sinc convention of include/syldet.h) ----
 struct syldet_sinc_resampler {

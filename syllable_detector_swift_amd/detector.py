@@ -815,19 +815,31 @@ class SyllableDetector:
         events()."""
         return Recordings(self, lengths, networks)
 
-    def runRecordings(self, arrays, debounce: float = 0.0, networks=None):
+    def runRecordings(self, arrays, debounce: float = 0.0, networks=None, rates=None, resample=None, zeroCrossings=None, beta=None,
+                      rolloff=None):
         """Recordings of any lengths in one pass: one upload, load, run / runPCM16, events and one download.  `arrays`: 1-D
         (mono) or [frames, tracks] numpy arrays, all float32 or all int16 (16-bit PCM); every track is a recording, in order
         (`networks`, on a multi / mixed bank: one entry a track).  Returns, per recording, (indices int64 [n], values float32
-        [n, outputs]): its debounced detections and the outputs of their evaluations."""
+        [n, outputs]): its debounced detections and the outputs of their evaluations.
+        `rates`: the sampling rate of every array (None: all at the network's, and nothing else changes).  With rates,
+        resample="sinc" is required: the plan is made from recordingLengths of the arrays' lengths, the rows are loaded through
+        Recordings.loadSinc (band-limited conversion as they load; an array at the network's rate is copied) and run as fp32 --
+        per recording what convertRate(method="sinc"), run and detections give on it alone.  zeroCrossings, beta, rolloff: the
+        converter's quality (None: sincDefaults())."""
         torch = _torch()
+        if rates is None and (resample is not None or zeroCrossings is not None or beta is not None or rolloff is not None):
+            raise ValueError("resample, zeroCrossings, beta and rolloff belong to rates")
+        if rates is not None and resample != "sinc":
+            raise ValueError("recordings at rates of their own need resample='sinc' (there is no linear-interpolation load)")
         arrays = [np.asarray(a) for a in arrays]
         dtypes = {a.dtype for a in arrays}
         if arrays and dtypes not in ({np.dtype(np.float32)}, {np.dtype(np.int16)}):
             raise ValueError("arrays must be all float32 or all int16")
         s16 = bool(arrays) and arrays[0].dtype == np.int16
-        lengths, offsets, steps, pos = [], [], [], 0
-        for a in arrays:
+        if rates is not None and len(rates) != len(arrays):
+            raise ValueError("one rate per array")
+        lengths, offsets, steps, track_rates, pos = [], [], [], [], 0
+        for i, a in enumerate(arrays):
             if a.ndim not in (1, 2):
                 raise ValueError("each array is 1-D (mono) or [frames, tracks]")
             tracks = 1 if a.ndim == 1 else a.shape[1]
@@ -835,6 +847,8 @@ class SyllableDetector:
                 lengths.append(a.shape[0])
                 offsets.append(pos + t)
                 steps.append(tracks)
+                if rates is not None:
+                    track_rates.append(float(rates[i]))
             pos += (a.size + 7) // 8 * 8                          # every file from a whole 16 bytes
         flat = np.zeros(max(pos, 8), np.int16 if s16 else np.float32)
         pos = 0
@@ -842,11 +856,17 @@ class SyllableDetector:
             flat[pos:pos + a.size] = np.ascontiguousarray(a).reshape(-1)
             pos += (a.size + 7) // 8 * 8
         n_out = self.geometry.outputs
-        with self.recordings(lengths, networks) as rec:
+        planned = lengths if rates is None else recordingLengths(lengths, track_rates, self.config.samplingRate)
+        with self.recordings(planned, networks) as rec:
             if rec.rowEvaluations <= 0:
                 return [(np.zeros(0, np.int64), np.zeros((0, n_out), np.float32)) for _ in lengths]
-            rows = rec.load(torch.from_numpy(flat).to("cuda:%d" % self.device), offsets, steps)
-            out, fl = (self.runPCM16 if s16 else self.run)(rows)
+            if rates is None:
+                rows = rec.load(torch.from_numpy(flat).to("cuda:%d" % self.device), offsets, steps)
+                out, fl = (self.runPCM16 if s16 else self.run)(rows)
+            else:
+                rows = rec.loadSinc(torch.from_numpy(flat).to("cuda:%d" % self.device), offsets, lengths, track_rates, steps, zeroCrossings, beta,
+                                    rolloff)
+                out, fl = self.run(rows)
             idx, val, cnt = rec.events(out, fl, debounce)
             torch.cuda.current_stream(self.device).synchronize()
             idx, val, cnt = idx.cpu().numpy(), val.cpu().numpy(), cnt.cpu().numpy()
@@ -911,6 +931,16 @@ def _recording_args(lengths, networks):
     if net is not None and net.size != n.size:
         raise ValueError("one network per recording")
     return n, net
+
+
+def recordingLengths(sourceSamples, sourceRates, rate: float):
+    """syldet_convert_rate_count per entry, host only: the lengths at the network's `rate` of recordings of sourceSamples[k]
+    samples at sourceRates[k] -- what a plan for Recordings.loadSinc is made from."""
+    n = np.ascontiguousarray(sourceSamples, dtype=np.int64).reshape(-1)
+    r = np.ascontiguousarray(sourceRates, dtype=np.float64).reshape(-1)
+    if n.size != r.size:
+        raise ValueError("one rate per recording")
+    return [int(_abi.lib.syldet_convert_rate_count(int(a), float(b), float(rate))) for a, b in zip(n, r)]
 
 
 def _slot_tuple(s):
@@ -999,6 +1029,40 @@ class Recordings:
         stride = int(out.stride(0)) if det.channels > 1 else int(out.shape[1])
         check(fn(self._h, src.data_ptr(), off.ctypes.data_as(_abi.c_int64_p), stp.ctypes.data_as(_abi.c_int32_p), out.data_ptr(), stride,
                  det._stream_ptr(stream)))
+        return out
+
+    def loadSinc(self, src, offsets, sourceSamples, sourceRates, steps=None, zeroCrossings=None, beta=None, rolloff=None, out=None, stream=None):
+        """load() for recordings that are each at a rate of their own (syldet_recordings_load_sinc_device*): recording k has
+        sourceSamples[k] samples at sourceRates[k], sample j at src[offsets[k] + j * steps[k]], and this Recordings was planned
+        from recordingLengths(sourceSamples, sourceRates, the network's rate).  Returns float32 rows [C, rowSamples] whatever
+        src's dtype (int16: x / 32768): every recording at another rate converted band-limited in place, with the bits
+        convertRate(method="sinc") gives on it alone; one at the network's rate copied; +0 everywhere else.  One launch.
+        zeroCrossings, beta, rolloff: None for sincDefaults().  `out`: float32 rows [C, >= rowSamples] to write into."""
+        torch = _torch()
+        from .resampler import _sinc_quality
+        det = self.detector
+        if not (src.is_cuda and src.dim() == 1 and src.is_contiguous() and src.dtype in (torch.float32, torch.int16)
+                and src.device.index == det.device):
+            raise ValueError("src must be a contiguous 1-D float32 or int16 CUDA tensor on the detector's device")
+        off = np.ascontiguousarray(offsets, dtype=np.int64).reshape(-1)
+        stp = np.ones(self.count, np.int32) if steps is None else np.ascontiguousarray(steps, dtype=np.int32).reshape(-1)
+        n = np.ascontiguousarray(sourceSamples, dtype=np.int64).reshape(-1)
+        rates = np.ascontiguousarray(sourceRates, dtype=np.float64).reshape(-1)
+        if off.size != self.count or stp.size != self.count or n.size != self.count or rates.size != self.count:
+            raise ValueError("one offset, length and rate (and step) per recording")
+        if self.count and (off.min() < 0 or stp.min() < 1 or n.min() < 0 or
+                           int((off + np.maximum(n - 1, 0) * stp)[n > 0].max(initial=-1)) >= src.numel()):
+            raise ValueError("a recording reaches outside src")
+        if out is None:
+            out = torch.empty((det.channels, self.rowSamples), dtype=torch.float32, device=src.device)
+        elif not (out.is_cuda and out.dtype == torch.float32 and out.dim() == 2 and out.shape[0] == det.channels and out.shape[1] >= self.rowSamples
+                  and out.stride(1) == 1 and out.device == src.device):
+            raise ValueError("out must be float32 [channels, >= rowSamples] on src's device, rows contiguous")
+        z, b, r = _sinc_quality(zeroCrossings, beta, rolloff)
+        fn = _abi.lib.syldet_recordings_load_sinc_device_s16 if src.dtype == torch.int16 else _abi.lib.syldet_recordings_load_sinc_device
+        stride = int(out.stride(0)) if det.channels > 1 else int(out.shape[1])
+        check(fn(self._h, src.data_ptr(), off.ctypes.data_as(_abi.c_int64_p), stp.ctypes.data_as(_abi.c_int32_p), n.ctypes.data_as(_abi.c_int64_p),
+                 rates.ctypes.data_as(_abi.c_double_p), z, b, r, out.data_ptr(), stride, det._stream_ptr(stream)))
         return out
 
     def view(self, tensor, k: int):
