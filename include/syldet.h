@@ -915,6 +915,68 @@ int syldet_recordings_load_sinc_device_s16(syldet_recordings_t *r, const int16_t
                                            const int64_t *src_samples, const double *src_rate, int32_t zero_crossings, double beta,
                                            double rolloff, float *d_rows, int64_t channel_stride, void *hip_stream);
 
+/* ---- packed recordings: every recording's output track and trigger track ----
+ * The two per-sample products of a run -- the Simulator's output track (syldet_trace*) and the TTL trigger track
+ * (syldet_trigger*) -- for every recording of a packed bank, written straight to a destination of the recording's own, in a
+ * fixed number of launches whatever K is.  d_outputs is [C][row_evals][n_out] and d_flags [C][row_evals], as syldet_run_device*
+ * wrote them for the packed rows.
+ * DESTINATIONS mirror the loads' sources: element i of recording k, 0 <= i < n_k = slots[k].n_samples, goes to
+ * d_dst[dst_offset[k] + i dst_step[k]] (host arrays of K entries; dst_step NULL: all 1).  Step 1 is a planar track; step n with
+ * offsets base + t writes track t of an n-track file's frames, so the call is also the interleave.  No other element of d_dst is
+ * written; dst_elements is the size of d_dst in elements.  Destinations of different recordings that share an element are the
+ * caller's error: which value lands there is unspecified, and nothing outside d_dst is touched.
+ * THE CONTRACT is identity with the calls for one recording:
+ *   trace     recording k's elements are, bit for bit, what syldet_trace_device (_s16) writes for n_samples = n_k when it is given
+ *             that recording's n_evals_k outputs alone, on a one-channel handle of the recording's network: the hold starts at
+ *             first_index counted from the recording's own sample 0, samples behind first_index + n_evals_k hop are 0, and the
+ *             division is by Float(thresholds[output]) of the network of the recording's row (plain, multi-network and mixed banks)
+ *   trigger   recording k's elements are those of syldet_trigger_device (_s16) on that recording's flags alone with n_samples =
+ *             n_k: the buffers b(e) = (D + e hop - 1) / L are counted with e and the samples from the recording's own start, a
+ *             pulse armed near a recording's end is cut at n_k and never reaches the next recording of the row, and a row
+ *             evaluation outside every recording is never read
+ *   onsets    d_indices [K][capacity] and d_counts [K] are those of syldet_trigger_onsets_device on the recording alone; the
+ *             counts may exceed the capacity, only the first min(count, capacity) indices are written
+ *   a recording without samples writes nothing; one without evaluations writes zeros.
+ * Statuses, decided before any device is touched: SYLDET_ERR_INVALID_ARGUMENT for a NULL handle or required pointer, `output`
+ * outside [0, outputs), the limits of buffer_length, width_samples and latency_samples stated for syldet_trigger*, a negative
+ * offset, a step < 1, capacity < 0, dst_elements < 0, and any k with n_k > 0 and dst_offset[k] + (n_k - 1) dst_step[k] >=
+ * dst_elements (syldet_last_error names the recording).
+ * THE LAUNCH RULE is the loads': the handle keeps the destination layout (dst_offset, dst_step), apart from the loads' sources,
+ * so loads and track calls may take turns.  A call whose layout differs from the kept one (the first always) waits for the
+ * stream of the handle's last track call and uploads the layout once, with a blocking copy; the same layout again is launches
+ * only, without allocation, synchronisation or copy.  One layout is kept for the trace and the trigger calls together (a tool
+ * writes both products to buffers of one shape); calls with layouts of their own may alternate, each then uploads.  The trigger
+ * calls need a table last_seen per recording, B'_k = ceil((n_k + L - 1) / L) entries, the recordings' tables end to end: a
+ * prefix of K + 1 entries is uploaded when buffer_length changes, and the tables are scratch the handle keeps and grows -- the
+ * exception already stated for syldet_trigger*.  The first trace of an output uploads the bank's threshold table of that
+ * output, as syldet_trace* does.  Launches, by the names syldet_timings lists:
+ *   trace           "recordings_trace_kernel"
+ *   trigger track   "recordings_trigger_scan_kernel", "recordings_trigger_kernel"
+ *   onsets          "recordings_trigger_scan_kernel", "recordings_trigger_onsets_kernel"
+ * The expansion kernels are balanced by rows, not by recordings; where dst_step is 1 they store 16 bytes at a time in groups
+ * aligned to the destination (a recording's head and tail element by element), for any other step element by element.  The
+ * scan is one workgroup a recording: no workgroup waits for another.  A sharded bank has no packed form, as before.
+ * STREAMS AND THREADS.  The handle waits only for the stream of its LAST track call before it rewrites a table (the loads have
+ * the same rule), so track calls of one handle on different streams must be ordered by the caller: with a kernel of an earlier
+ * call still running on another stream, a call with a changed layout or buffer_length may overwrite what that kernel reads.
+ * The track calls also WRITE to the bank h the handle was created from, although syldet_recordings_create takes it const: the
+ * first trace of an output makes the bank's threshold table of that output, and every call records into the bank's profile
+ * (syldet_profile).  So the bank's rule of one caller at a time covers them too: two syldet_recordings_t of one bank, or one of
+ * them and the bank itself, must not be used from two threads at once.                                                        */
+int syldet_recordings_trace_device(syldet_recordings_t *r, const float *d_outputs, int32_t output, float *d_dst, int64_t dst_elements,
+                                   const int64_t *dst_offset, const int32_t *dst_step, void *hip_stream);
+int syldet_recordings_trace_device_s16(syldet_recordings_t *r, const float *d_outputs, int32_t output, int16_t *d_dst, int64_t dst_elements,
+                                       const int64_t *dst_offset, const int32_t *dst_step, void *hip_stream);
+int syldet_recordings_trigger_device(syldet_recordings_t *r, const uint8_t *d_flags, int32_t buffer_length, int64_t width_samples,
+                                     int64_t latency_samples, float *d_dst, int64_t dst_elements, const int64_t *dst_offset,
+                                     const int32_t *dst_step, void *hip_stream);
+int syldet_recordings_trigger_device_s16(syldet_recordings_t *r, const uint8_t *d_flags, int32_t buffer_length, int64_t width_samples,
+                                         int64_t latency_samples, int16_t *d_dst, int64_t dst_elements, const int64_t *dst_offset,
+                                         const int32_t *dst_step, void *hip_stream);
+int syldet_recordings_trigger_onsets_device(syldet_recordings_t *r, const uint8_t *d_flags, int32_t buffer_length, int64_t width_samples,
+                                            int64_t latency_samples, int64_t *d_indices, int64_t capacity, int64_t *d_counts,
+                                            void *hip_stream);
+
 /* ---- threshold calibration: score a run against labelled times ----
  * Which threshold to ship, and how late and how jittery the trigger is at it: the reference leaves the question to MATLAB
  * (convert_to_text.m:70-72 only copies trigger_thresholds in).  Here the outputs of a run, which are on the device already, are

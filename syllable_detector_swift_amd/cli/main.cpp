@@ -7,6 +7,8 @@
 // file's rate differs from the network's] -> fused STFT + network kernel -> flags/outputs -> host.
 // 16-bit PCM at the network's rate crosses the bus and is de-interleaved as int16 (the library's *_s16 entry points give
 // the fp32 path's bits on x / 32768, which is what the decoder would have produced).
+// --simulate-dir / --ttl-dir / --ttl-onsets-dir write the same files for any number of audio files; under --batch a batch's tracks are
+// made by syldet_recordings_trace_device_s16 / syldet_recordings_trigger*_device_s16 straight into every file's frames.
 // --simulate <out.wav> also writes what the reference's Simulator writes (ViewControllerSimulator.swift:251-344): the chosen output
 // over its threshold, held between evaluations, as a 16-bit WAV of every track (syldet_trace_interleaved_device_s16).
 //
@@ -27,7 +29,9 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <filesystem>
 #include <map>
+#include <set>
 #include <string>
 #include <vector>
 
@@ -41,7 +45,7 @@ constexpr int kExUsage = 64;   // EX_USAGE, main.swift:40
 void usage(FILE *to)
 {
     std::fprintf(to,
-                 "Usage: syllable-detector-cli -n <net> [-a <audio>]... [-d <seconds>] [--device <k>] [--chunk <frames>] [--format <shortest|swift4>] [--resample <linear|sinc>] [--resample-quality <Z,beta,rolloff>] [--simulate <out.wav>] [--simulate-output <k>] [--levels <out.tsv>] [--levels-buffer <L>] [--levels-period <seconds>] [--ttl <out.wav>] [--ttl-mux] [--ttl-width <seconds>] [--ttl-steps <n>] [--ttl-buffer <L>] [--ttl-latency <seconds>] [--ttl-onsets <out.tsv>] [--batch] [--batch-rows <N>] [--batch-bytes <B>] [--score <labels.tsv> --score-out <table.tsv>] [--score-thresholds <lo:hi:n>] [--score-tolerance <seconds>] [--score-cost <c>] [--score-output <k>] [--probe]\n"
+                 "Usage: syllable-detector-cli -n <net> [-a <audio>]... [-d <seconds>] [--device <k>] [--chunk <frames>] [--format <shortest|swift4>] [--resample <linear|sinc>] [--resample-quality <Z,beta,rolloff>] [--simulate <out.wav>] [--simulate-output <k>] [--levels <out.tsv>] [--levels-buffer <L>] [--levels-period <seconds>] [--ttl <out.wav>] [--ttl-mux] [--ttl-width <seconds>] [--ttl-steps <n>] [--ttl-buffer <L>] [--ttl-latency <seconds>] [--ttl-onsets <out.tsv>] [--simulate-dir <dir>] [--ttl-dir <dir>] [--ttl-onsets-dir <dir>] [--batch] [--batch-rows <N>] [--batch-bytes <B>] [--score <labels.tsv> --score-out <table.tsv>] [--score-thresholds <lo:hi:n>] [--score-tolerance <seconds>] [--score-cost <c>] [--score-output <k>] [--probe]\n"
                  "  -n, --net <net>:\n      Path to trained network file.  Given k > 1 times: each file must have exactly k tracks, and track t runs network t (one mixed bank; the networks must share the sampling rate, window length, window overlap, time range and number of outputs).\n"
                  "  -a, --audio <audio>:\n      Path to the audio file to process.\n"
                  "  -d, --debounce <seconds>:\n      Number of seconds to debounce triggers.\n"
@@ -62,9 +66,10 @@ void usage(FILE *to)
                  "      --ttl-buffer <L>:\n      Samples per input and output buffer: a power of two from 8 to 4096 (default 32).\n"
                  "      --ttl-latency <seconds>:\n      Delay of the output behind the input (default 0).\n"
                  "      --ttl-onsets <out.tsv>:\n      Also write the rising edges of the trigger tracks, one line each, tab separated: the track, the sample, the time in seconds.\n"
+                 "      --simulate-dir <dir>, --ttl-dir <dir>, --ttl-onsets-dir <dir>:\n      --simulate, --ttl and --ttl-onsets for any number of audio files, with or without --batch: for an audio file p the file written is <dir>/<the file name of p> (the onsets: that name with .tsv behind it), exactly what the option for one file writes for p alone. The directory is made if it is not there; two audio files of the same name are refused. Under --batch a batch's tracks are made on the GPU in one pass and come back in one download per product.\n"
                  "      --batch:\n      Run the audio files through one detector bank instead of one bank a file: every track of every file becomes a recording in the bank's rows, and only the detections come back from the GPU. The output is the same. A file at another sampling rate than the network's joins the bank under --resample sinc (its rate within a sixteenth and sixteen times the network's): it is converted as the rows load, and a batch that holds such a file runs as 32-bit float. Under --resample linear (the default), or outside that range, such a file ends the batch and runs alone, as without --batch.\n"
                  "      --batch-rows <N>:\n      Rows of the bank under --batch (default 64; no more than there are tracks).\n"
-                 "      --batch-bytes <B>:\n      Consecutive files share a batch until their samples pass B bytes (default 2147483648); a file that is converted counts with the bytes it has at its own rate.\n"
+                 "      --batch-bytes <B>:\n      Consecutive files share a batch until their samples pass B bytes (default 2147483648); a file that is converted counts with the bytes it has at its own rate. Each track product (--simulate-dir, --ttl-dir) adds 2 bytes per sample at the network's rate to what a batch holds on the device.\n"
                  "      --score <labels.tsv>:\n      Under --batch, also score every track against labelled times for a grid of candidate thresholds: lines of file, track and sample, tab separated (the file as -a names it, the sample counted from the file's start at the network's sampling rate, also for a file at another rate). A file that does not go through the bank (see --batch) is left out, with a message. Needs --score-out.\n"
                  "      --score-out <table.tsv>:\n      Where --score writes its table, one line per threshold, tab separated: threshold, detections, hits, misses, false positives, repeats, the mean and the standard deviation of the hits' offsets in samples, the cost; a last line names the threshold of the smallest cost.\n"
                  "      --score-thresholds <lo:hi:n>:\n      The grid: n thresholds from lo to hi (default 0:1:101; at most 4096).\n"
@@ -137,6 +142,39 @@ struct TtlOpt {
     int64_t width_samples(double rate) const { return steps > 0 ? (int64_t)steps * buffer : syldet_trigger_width(width, rate); }
     int64_t latency_samples(double rate) const { const double x = latency * rate; return x < 9e18 ? (int64_t)x : INT64_MAX; }
 };
+
+// --simulate-dir / --ttl-dir / --ttl-onsets-dir: the per-sample products of every audio file, each under its file's name
+struct TrackDirs {
+    std::string simulate, ttl, onsets;                     // empty: none
+    bool any() const { return !simulate.empty() || !ttl.empty() || !onsets.empty(); }
+    static std::string name_of(const std::string &path)
+    {
+        const size_t at = path.find_last_of('/');
+        return at == std::string::npos ? path : path.substr(at + 1);
+    }
+    static std::string in(const std::string &dir, const std::string &path, const char *suffix = "")
+    {
+        return dir.empty() ? std::string() : dir + "/" + name_of(path) + suffix;
+    }
+    // what process_file takes for one audio file
+    std::string simulate_for(const std::string &path, const std::string &single) const { return simulate.empty() ? single : in(simulate, path); }
+    template <class Ttl>
+    Ttl ttl_for(const std::string &path, Ttl t) const
+    {
+        if (!ttl.empty()) t.path = in(ttl, path);
+        if (!onsets.empty()) t.onsets = in(onsets, path, ".tsv");
+        return t;
+    }
+    void make() const                                      // (a directory that cannot be made: the writes fail, and cost what they cost)
+    {
+        std::error_code ec;
+        for (const std::string *d : {&simulate, &ttl, &onsets})
+            if (!d->empty()) std::filesystem::create_directories(*d, ec);
+    }
+};
+
+// the rising edges as --ttl-onsets writes them: track, sample, seconds
+bool write_onsets(const std::string &path, int C, const int64_t *idx, const int64_t *cnt, int64_t cap, double rate);
 
 // --resample / --resample-quality: how a file at another rate is brought to the network's (the step the reference's tool leaves to
 // AVFoundation, SyllableDetector.swift:19-23, TrackDetector.swift:35)
@@ -378,16 +416,7 @@ int process_file(const std::string &path, const std::vector<syldet_config_t *> &
             }
         }
         if (!ttl.onsets.empty()) {
-            FILE *f = std::fopen(ttl.onsets.c_str(), "w");
-            bool ok = f != nullptr;
-            for (int c = 0; ok && c < C && !ttl_cnt.empty(); c++)
-                for (int64_t i = 0; ok && i < std::min(ttl_cnt[(size_t)c], ttl_cap); i++) {
-                    const int64_t smp = ttl_idx[(size_t)c * (size_t)ttl_cap + (size_t)i];
-                    const std::string line = std::to_string(c) + "\t" + std::to_string(smp) + "\t" + number((double)smp / cfg->sampling_rate) + "\n";
-                    ok = std::fputs(line.c_str(), f) >= 0;
-                }
-            if (f && std::fclose(f) != 0) ok = false;
-            if (!ok) {
+            if (!write_onsets(ttl.onsets, ttl_cnt.empty() ? 0 : C, ttl_idx.data(), ttl_cnt.data(), ttl_cap, cfg->sampling_rate)) {
                 std::fprintf(stderr, "Unable to write %s.\n", ttl.onsets.c_str());
                 bad = 3;
             }
@@ -430,9 +459,26 @@ int process_file(const std::string &path, const std::vector<syldet_config_t *> &
     return write_files();
 }
 
+bool write_onsets(const std::string &path, int C, const int64_t *idx, const int64_t *cnt, int64_t cap, double rate)
+{
+    FILE *f = std::fopen(path.c_str(), "w");
+    bool ok = f != nullptr;
+    for (int c = 0; ok && c < C; c++)
+        for (int64_t i = 0; ok && i < std::min(cnt[(size_t)c], cap); i++) {
+            const int64_t smp = idx[(size_t)c * (size_t)cap + (size_t)i];
+            const std::string line = std::to_string(c) + "\t" + std::to_string(smp) + "\t" + number((double)smp / rate) + "\n";
+            ok = std::fputs(line.c_str(), f) >= 0;
+        }
+    if (f && std::fclose(f) != 0) ok = false;
+    return ok;
+}
+
 // --batch: the -a files through ONE bank instead of a bank a file (syldet_recordings_*: every track of every file of a batch is a
 // recording laid into the bank's rows; the reference's tool runs them one after another on one core, main.swift:63-130).  Only
-// the detections and their outputs come back from the device.  What is printed is what the loop over process_file prints.
+// the detections and their outputs come back from the device -- and, under --simulate-dir / --ttl-dir / --ttl-onsets-dir, every
+// file's tracks: one device buffer a product, every file's frame-major int16 frames [n][tracks] end to end, each file from a multiple
+// of 8 elements, written by ONE call a product (step = the file's track count, offset = the file's base + the track) and brought
+// back in one download.  What is printed is what the loop over process_file prints.
 struct BatchOpt {
     bool on = false;
     long rows = 64;
@@ -502,9 +548,10 @@ bool read_labels(const std::string &path, ScoreRun &run, std::string &err)
     return true;
 }
 
-// One batch: returns 0, or 2 for device trouble (no line of the batch is printed then, but the files' names are)
+// One batch: returns 0, 2 for device trouble (no line of the batch is printed then, but the files' names are), or 3: the lines are
+// out, a track is not
 int run_batch(std::vector<BatchFile> &files, const std::vector<syldet_config_t *> &cfgs, int device, double debounce_s, int64_t chunk,
-              long max_rows, bool headers, ScoreRun *score, const ResampleOpt &conv)
+              long max_rows, bool headers, ScoreRun *score, const ResampleOpt &conv, const TrackDirs &dirs, int simulate_output, const TtlOpt &ttl)
 {
     if (files.empty()) return 0;
     const syldet_config_t *cfg = cfgs[0];
@@ -540,6 +587,32 @@ int run_batch(std::vector<BatchFile> &files, const std::vector<syldet_config_t *
         total += (f.info.frames * f.info.channels + 7) / 8 * 8;
     }
     const int32_t K = (int32_t)lengths.size();
+    // the tracks' destination: file i's frames [n_i][tracks] at frames_at[i], n_i its length at the network's rate
+    std::vector<int64_t> dst_offset, frames_at(files.size());
+    std::vector<int32_t> dst_step;
+    int64_t dst_total = 0;
+    for (size_t i = 0, k = 0; i < files.size(); i++) {
+        const int tracks = files[i].info.channels;
+        frames_at[i] = dst_total;
+        for (int t = 0; t < tracks; t++) {
+            dst_offset.push_back(dst_total + t);
+            dst_step.push_back(tracks);
+        }
+        dst_total += (lengths[k] * tracks + 7) / 8 * 8;
+        k += (size_t)tracks;
+    }
+    std::vector<int16_t> sim_frames, ttl_frames;            // (zeros where no file of the batch has an evaluation)
+    std::vector<int64_t> on_idx, on_cnt;
+    int64_t on_cap = 1;
+    try {
+        if (!dirs.simulate.empty()) sim_frames.assign((size_t)dst_total, 0);
+        if (!dirs.ttl.empty()) ttl_frames.assign((size_t)dst_total, 0);
+        if (!dirs.onsets.empty()) on_cnt.assign((size_t)K, 0);
+    } catch (const std::bad_alloc &) {
+        std::fprintf(stderr, "Unable to process the batch: out of memory.\n");
+        files.clear();
+        return 2;
+    }
     const int n_nets = (int)cfgs.size();
     const int C = (int)std::max<long>(n_nets, std::min<long>(max_rows, K));
     syldet_t *h = nullptr;
@@ -657,6 +730,37 @@ int run_batch(std::vector<BatchFile> &files, const std::vector<syldet_config_t *
             }
             syldet_scorer_destroy(sc);
         }
+        // the tracks of every file of the batch, from the outputs and flags that are on the device
+        if (dirs.any()) {
+            DevBuf d_sim, d_ttl, d_on_idx, d_on_cnt;
+            const int64_t N = ttl.width_samples(cfg->sampling_rate), lat = ttl.latency_samples(cfg->sampling_rate);
+            if (!dirs.simulate.empty()) {
+                if (!d_sim.alloc((size_t)dst_total * sizeof(int16_t))) { rc = 2; break; }
+                st = syldet_recordings_trace_device_s16(r, (const float *)d_out.p, simulate_output, (int16_t *)d_sim.p, dst_total, dst_offset.data(), dst_step.data(), stream);
+                if (!st && hipMemcpyAsync(sim_frames.data(), d_sim.p, (size_t)dst_total * sizeof(int16_t), hipMemcpyDeviceToHost, stream) != hipSuccess) { rc = 2; break; }
+            }
+            if (!st && !dirs.ttl.empty()) {
+                if (!d_ttl.alloc((size_t)dst_total * sizeof(int16_t))) { rc = 2; break; }
+                st = syldet_recordings_trigger_device_s16(r, (const uint8_t *)d_flags.p, ttl.buffer, N, lat, (int16_t *)d_ttl.p, dst_total, dst_offset.data(), dst_step.data(), stream);
+                if (!st && hipMemcpyAsync(ttl_frames.data(), d_ttl.p, (size_t)dst_total * sizeof(int16_t), hipMemcpyDeviceToHost, stream) != hipSuccess) { rc = 2; break; }
+            }
+            if (!st && !dirs.onsets.empty()) {
+                std::vector<syldet_slot_t> slots((size_t)K);
+                st = syldet_recordings_slots(r, slots.data());
+                for (const syldet_slot_t &sl : slots) on_cap = std::max<int64_t>(on_cap, std::min<int64_t>(sl.n_evals, sl.n_samples / ttl.buffer + 1));
+                on_idx.assign((size_t)K * (size_t)on_cap, 0);
+                if (!d_on_idx.alloc(on_idx.size() * sizeof(int64_t)) || !d_on_cnt.alloc(on_cnt.size() * sizeof(int64_t))) { rc = 2; break; }
+                if (!st) st = syldet_recordings_trigger_onsets_device(r, (const uint8_t *)d_flags.p, ttl.buffer, N, lat, (int64_t *)d_on_idx.p, on_cap, (int64_t *)d_on_cnt.p, stream);
+                if (!st && (hipMemcpyAsync(on_idx.data(), d_on_idx.p, on_idx.size() * sizeof(int64_t), hipMemcpyDeviceToHost, stream) != hipSuccess ||
+                            hipMemcpyAsync(on_cnt.data(), d_on_cnt.p, on_cnt.size() * sizeof(int64_t), hipMemcpyDeviceToHost, stream) != hipSuccess)) { rc = 2; break; }
+            }
+            if (st) {
+                std::fprintf(stderr, "Unable to make the tracks of the batch: %s: %s\n", syldet_strerror(st), syldet_last_error());
+                rc = 2;
+                break;
+            }
+            if (hipStreamSynchronize(stream) != hipSuccess) { rc = 2; break; }
+        }
     } while (false);
     if (rc == 2 && hipPeekAtLastError() != hipSuccess) std::fprintf(stderr, "Unable to process the batch: %s\n", hipGetErrorString(hipGetLastError()));
     if (stream) (void)hipStreamDestroy(stream);
@@ -665,6 +769,7 @@ int run_batch(std::vector<BatchFile> &files, const std::vector<syldet_config_t *
     if (rc && score) score->failed = true;                  // (a table without this batch would be another archive's)
     // file by file, the lines process_file prints: the tracks' events interleaved buffer by buffer (main.swift:126-130)
     int32_t k0 = 0;
+    bool unwritten = false;
     for (const BatchFile &f : files) {
         if (headers) std::printf("%s\n", f.path.c_str());  // main.swift:122-124
         std::vector<Event> events;
@@ -684,10 +789,30 @@ int run_batch(std::vector<BatchFile> &files, const std::vector<syldet_config_t *
             std::puts(line.c_str());
         }
         std::fflush(stdout);
+        // the file's tracks behind its lines, which a failing write must not cost (process_file's order and its messages)
+        if (!rc && dirs.any()) {
+            const size_t i = (size_t)(&f - files.data());
+            const int tracks = f.info.channels;
+            const int64_t n = lengths[(size_t)k0];
+            std::string werr;
+            const std::string sim = TrackDirs::in(dirs.simulate, f.path), trg = TrackDirs::in(dirs.ttl, f.path), ons = TrackDirs::in(dirs.onsets, f.path, ".tsv");
+            if (!sim.empty() && !wav::write_s16(sim, cfg->sampling_rate, tracks, n, sim_frames.data() + frames_at[i], werr)) {
+                std::fprintf(stderr, "Unable to write %s: %s\n", sim.c_str(), werr.c_str());
+                unwritten = true;
+            }
+            if (!trg.empty() && !wav::write_s16(trg, cfg->sampling_rate, tracks, n, ttl_frames.data() + frames_at[i], werr)) {
+                std::fprintf(stderr, "Unable to write %s: %s\n", trg.c_str(), werr.c_str());
+                unwritten = true;
+            }
+            if (!ons.empty() && !write_onsets(ons, tracks, on_idx.empty() ? nullptr : on_idx.data() + (size_t)k0 * (size_t)on_cap, on_cnt.data() + k0, on_cap, cfg->sampling_rate)) {
+                std::fprintf(stderr, "Unable to write %s.\n", ons.c_str());
+                unwritten = true;
+            }
+        }
         k0 += f.info.channels;
     }
     files.clear();
-    return rc;
+    return rc ? rc : (unwritten ? 3 : 0);
 }
 
 // TABLE: one line per threshold -- threshold detections hits misses false_positives repeats mean_offset sd_offset cost, tab
@@ -730,7 +855,7 @@ bool write_score_table(const ScoreOpt &opt, const ScoreRun &run)
 // network's rate or -- under --resample sinc -- at a rate the band-limited converter takes) gather until their samples pass
 // opt.bytes; any other file ends the batch and is processed alone in its place.
 int process_batched(const std::vector<std::string> &audio, const std::vector<syldet_config_t *> &cfgs, int device, double debounce_s, bool have_debounce,
-                    int64_t chunk, const BatchOpt &opt, const ResampleOpt &conv, ScoreRun *score)
+                    int64_t chunk, const BatchOpt &opt, const ResampleOpt &conv, ScoreRun *score, const TrackDirs &dirs, int simulate_output, const TtlOpt &ttl)
 {
     int rc = 0;
     const bool headers = audio.size() > 1;
@@ -738,7 +863,9 @@ int process_batched(const std::vector<std::string> &audio, const std::vector<syl
     std::vector<BatchFile> files;
     size_t held = 0;
     auto flush = [&]() {
-        if (run_batch(files, cfgs, device, deb, chunk, opt.rows, headers, score, conv) == 2) rc = 2;
+        const int r = run_batch(files, cfgs, device, deb, chunk, opt.rows, headers, score, conv, dirs, simulate_output, ttl);
+        if (r == 2) rc = 2;
+        else if (r == 3 && rc == 0) rc = 1;
         held = 0;
     };
     for (const std::string &p : audio) {
@@ -765,7 +892,8 @@ int process_batched(const std::vector<std::string> &audio, const std::vector<syl
         if (score && score->labels.count(p)) std::fprintf(stderr, "--score: %s does not go through the bank; its labels are left out.\n", p.c_str());
         if (headers) std::printf("%s\n", p.c_str());
         std::fflush(stdout);
-        const int r = process_file(p, cfgs, device, debounce_s, have_debounce, chunk, std::string(), 0, LevelsOpt(), TtlOpt(), conv);
+        const int r = process_file(p, cfgs, device, debounce_s, have_debounce, chunk, dirs.simulate_for(p, std::string()), simulate_output, LevelsOpt(),
+                                   dirs.any() ? dirs.ttl_for(p, ttl) : TtlOpt(), conv);
         if (r == 2) rc = 2;
         else if (r == 3 && rc == 0) rc = 1;
     }
@@ -795,6 +923,8 @@ int main(int argc, char **argv)
     int64_t chunk = 8192;
     BatchOpt batch;
     bool have_batch_option = false;
+    TrackDirs dirs;
+    bool have_simulate_dir = false, have_ttl_dir = false, have_onsets_dir = false;
     ScoreOpt score;
     bool have_score = false, have_score_option = false;
     auto value = [&](int &i, const char *name) -> const char * {
@@ -902,6 +1032,15 @@ int main(int argc, char **argv)
         else if (a == "--simulate") {
             simulate = value(i, "--simulate");
             have_simulate = true;
+        } else if (a == "--simulate-dir") {
+            dirs.simulate = value(i, "--simulate-dir");
+            have_simulate_dir = true;
+        } else if (a == "--ttl-dir") {
+            dirs.ttl = value(i, "--ttl-dir");
+            have_ttl_dir = true;
+        } else if (a == "--ttl-onsets-dir") {
+            dirs.onsets = value(i, "--ttl-onsets-dir");
+            have_onsets_dir = true;
         } else if (a == "--simulate-output") {
             const char *v = value(i, "--simulate-output");
             char *end = nullptr;
@@ -1026,8 +1165,33 @@ int main(int argc, char **argv)
         usage(stdout);
         return kExUsage;
     }
-    if (have_simulate_output && !have_simulate) {
-        std::fprintf(stderr, "--simulate-output needs --simulate <out.wav>.\n");
+    if ((have_simulate_dir && dirs.simulate.empty()) || (have_ttl_dir && dirs.ttl.empty()) || (have_onsets_dir && dirs.onsets.empty())) {
+        std::fprintf(stderr, "--simulate-dir, --ttl-dir and --ttl-onsets-dir take the name of a directory.\n");
+        usage(stdout);
+        return kExUsage;
+    }
+    if ((have_simulate && have_simulate_dir) || (have_ttl && have_ttl_dir) || (have_ttl_onsets && have_onsets_dir)) {
+        std::fprintf(stderr, "--simulate-dir, --ttl-dir and --ttl-onsets-dir write what --simulate, --ttl and --ttl-onsets write, for every audio file: give the one or the other.\n");
+        usage(stdout);
+        return kExUsage;
+    }
+    if (dirs.any()) {                                       // every audio file's products go under its own name
+        std::set<std::string> names;
+        for (const std::string &p : audio)
+            if (!names.insert(TrackDirs::name_of(p)).second) {
+                std::fprintf(stderr, "--simulate-dir, --ttl-dir and --ttl-onsets-dir name their files after the audio files: two of those are called %s.\n",
+                             TrackDirs::name_of(p).c_str());
+                usage(stdout);
+                return kExUsage;
+            }
+    }
+    if (ttl.mux && batch.on) {
+        std::fprintf(stderr, "--ttl-mux is not available under --batch.\n");
+        usage(stdout);
+        return kExUsage;
+    }
+    if (have_simulate_output && !have_simulate && !have_simulate_dir) {
+        std::fprintf(stderr, "--simulate-output needs --simulate <out.wav> or --simulate-dir <dir>.\n");
         usage(stdout);
         return kExUsage;
     }
@@ -1046,13 +1210,13 @@ int main(int argc, char **argv)
         usage(stdout);
         return kExUsage;
     }
-    if (ttl.mux && !have_ttl) {
-        std::fprintf(stderr, "--ttl-mux needs --ttl <out.wav>.\n");
+    if (ttl.mux && !have_ttl && !have_ttl_dir) {
+        std::fprintf(stderr, "--ttl-mux needs --ttl <out.wav> or --ttl-dir <dir>.\n");
         usage(stdout);
         return kExUsage;
     }
-    if (have_ttl_option && !have_ttl && !have_ttl_onsets) {
-        std::fprintf(stderr, "--ttl-width, --ttl-steps, --ttl-buffer and --ttl-latency need --ttl <out.wav> or --ttl-onsets <out.tsv>.\n");
+    if (have_ttl_option && !have_ttl && !have_ttl_onsets && !have_ttl_dir && !have_onsets_dir) {
+        std::fprintf(stderr, "--ttl-width, --ttl-steps, --ttl-buffer and --ttl-latency need --ttl <out.wav>, --ttl-onsets <out.tsv>, --ttl-dir <dir> or --ttl-onsets-dir <dir>.\n");
         usage(stdout);
         return kExUsage;
     }
@@ -1066,8 +1230,13 @@ int main(int argc, char **argv)
         usage(stdout);
         return kExUsage;
     }
-    if (batch.on && (have_simulate || have_levels || have_ttl || have_ttl_onsets)) {   // those take exactly one file and a bank of its own
-        std::fprintf(stderr, "--batch runs many files through one bank; --simulate, --levels, --ttl and --ttl-onsets take exactly one file: give one or the other.\n");
+    if (batch.on && have_levels) {                          // (the meters of a packed bank's recordings are not built)
+        std::fprintf(stderr, "--levels is not available under --batch: it takes exactly one file and a bank of its own.\n");
+        usage(stdout);
+        return kExUsage;
+    }
+    if (batch.on && (have_simulate || have_ttl || have_ttl_onsets)) {   // those name one file; under --batch every file's tracks go to a directory
+        std::fprintf(stderr, "--batch runs many files through one bank; --simulate, --ttl and --ttl-onsets take exactly one file: give --simulate-dir, --ttl-dir and --ttl-onsets-dir instead.\n");
         usage(stdout);
         return kExUsage;
     }
@@ -1106,7 +1275,7 @@ int main(int argc, char **argv)
         cfg->rule = SYLDET_RULE_ANY;                        // any output above its threshold, TrackDetector.swift:72-77
         cfgs.push_back(cfg);
     }
-    if (have_simulate)                                      // (before the GPU is opened)
+    if (have_simulate || have_simulate_dir)                 // (before the GPU is opened)
         for (syldet_config_t *c : cfgs)
             if (simulate_output >= c->n_thresholds) {
                 std::fprintf(stderr, "--simulate-output %d: the network has %d output(s).\n", simulate_output, c->n_thresholds);
@@ -1114,7 +1283,7 @@ int main(int argc, char **argv)
                 usage(stdout);
                 return kExUsage;
             }
-    if (ttl.any()) {                                        // (before the GPU is opened)
+    if (ttl.any() || have_ttl_dir || have_onsets_dir) {     // (before the GPU is opened)
         const double rate = cfgs[0]->sampling_rate;
         const int64_t N = ttl.width_samples(rate), lat = ttl.latency_samples(rate);
         if (N < 1 || N > (1ll << 24) || lat > (1ll << 24)) {
@@ -1145,17 +1314,19 @@ int main(int argc, char **argv)
         scoring.totals.assign((size_t)score.n * SYLDET_SCORE_COLUMNS, 0);
     }
     if (batch.on) {
-        int brc = process_batched(audio, cfgs, device, debounce, have_debounce, chunk, batch, conv, have_score ? &scoring : nullptr);
+        dirs.make();
+        int brc = process_batched(audio, cfgs, device, debounce, have_debounce, chunk, batch, conv, have_score ? &scoring : nullptr, dirs, simulate_output, ttl);
         for (syldet_config_t *c : cfgs) syldet_config_free(c);
         // the table last, and only a whole one; standard output and the status are those of the run without --score
         if (have_score && (scoring.failed || !write_score_table(score, scoring)) && brc == 0) brc = 1;
         return brc;
     }
     int rc = 0;
+    dirs.make();
     for (const std::string &p : audio) {
         if (audio.size() > 1) std::printf("%s\n", p.c_str());   // main.swift:122-124
         std::fflush(stdout);
-        const int r = process_file(p, cfgs, device, debounce, have_debounce, chunk, simulate, simulate_output, levels, ttl, conv);
+        const int r = process_file(p, cfgs, device, debounce, have_debounce, chunk, dirs.simulate_for(p, simulate), simulate_output, levels, dirs.ttl_for(p, ttl), conv);
         if (r == 2) rc = 2;                                 // device trouble is fatal for the exit code; an unreadable file is skipped
         else if (r == 3 && rc == 0) rc = 1;                 // ... and so is a track that could not be written
     }

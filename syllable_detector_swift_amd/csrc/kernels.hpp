@@ -432,6 +432,36 @@ struct RecSincDesc {
 hipError_t launch_recordings_load_sinc(const RecSincDesc &d, const void *src, bool s16, double rate_out, const float *table, int N,
                                        float *rows, int64_t stride, int C, hipStream_t stream);
 
+// ---- packed recordings: the per-sample tracks (kernels_recordings_tracks.hip; syldet_recordings_trace_device* and
+// syldet_recordings_trigger*_device* of include/syldet.h) ----
+// Where one slot's track goes, in the order of RecSlotDev's table: element i at dst[dst_offset + i dst_step].  k: the recording, its
+// index in the caller's order (RecEventDev's, ls_begin's, n_samples').
+struct RecTrackDev {
+    int64_t dst_offset;
+    int32_t dst_step, k;
+};
+struct RecTrackDesc {
+    RecLoadDesc load;                        // the plan's slots, rows and tiles: the load's own tables
+    const RecEventDev *events;               // [K]
+    const RecTrackDev *dst;                  // [K] the kept destination layout
+    const int32_t *ls_begin;                 // [K + 1] recording k's last_seen table is entries [ls_begin[k], ls_begin[k + 1]) (the kept L)
+    const int64_t *n_samples;                // [K]
+    int K;
+    int64_t row_evals;
+};
+// outputs [C][row_evals][n_out], thr [C] -> every recording's trace at its destination; dst fp32 or (s16) int16
+hipError_t launch_recordings_trace(const RecTrackDesc &d, int C, const float *outputs, int n_out, int k, const float *thr, void *dst, bool s16,
+                                   int64_t first_index, int64_t hop, hipStream_t stream);
+// flags [C][row_evals] -> last_seen: every recording's table (trigger_buffers(n_k, L) entries), end to end
+hipError_t launch_recordings_trigger_scan(const RecTrackDesc &d, const uint8_t *flags, int L, int64_t first_index, int64_t hop, int *last_seen,
+                                          hipStream_t stream);
+// last_seen -> every recording's trigger track at its destination
+hipError_t launch_recordings_trigger(const RecTrackDesc &d, int C, const int *last_seen, int L, int64_t N, int64_t Lat, void *dst, bool s16,
+                                     hipStream_t stream);
+// last_seen -> indices [K][capacity], counts [K]
+hipError_t launch_recordings_trigger_onsets(const RecTrackDesc &d, const int *last_seen, int L, int64_t N, int64_t Lat, int64_t *indices,
+                                            int64_t capacity, int64_t *counts, hipStream_t stream);
+
 // ---- threshold calibration (kernels_score.hip; syldet_score_device of include/syldet.h) ----
 // What a scorer keeps on the device.  A detector is a channel (slots == nullptr: its evaluations are row `det`) or a recording
 // (slots [D]: its own part of its row).

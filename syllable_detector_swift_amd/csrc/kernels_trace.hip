@@ -13,6 +13,7 @@
 #include <algorithm>
 
 #include "kernels.hpp"
+#include "track_values.hpp"   // div_magic, magic_for, trace_word
 
 // the division, the product with 32767 and the rounding each round on their own: this file is compiled with
 // -ffp-contract=off (see the Makefile) and without any fast-math flag -- `/` is the correctly rounded fp32 division
@@ -26,27 +27,6 @@ constexpr int kTraceSpanBytes = 16384;    // bytes of one channel's row per work
 constexpr int kTraceEvals = 4096;         // evaluations a workgroup's samples may touch (a hop of 1 halves the int16 span: trace_span)
 constexpr int kTraceTileCh = 64;          // interleaved: channels per tile ...
 constexpr int kTraceTileEvals = 128;      // ... and evaluations per channel a tile may touch (its frames: trace_tile_frames)
-
-// n / d for n d < 2^32 as one multiplication (magic = ceil(2^32 / d)); magic == 0: d == 1 or a pair too large for it
-__device__ __forceinline__ unsigned div_magic(unsigned n, unsigned d, unsigned magic)
-{
-    return magic ? __umulhi(n, magic) : n / d;
-}
-
-// The 32-bit word LDS holds for evaluation e of a row: the value's bits (fp32 trace) or its 16-bit sample (int16 trace).
-// Evaluations past n_evals are 0 (samples behind the last hold).
-template <bool S16>
-__device__ __forceinline__ unsigned trace_word(const float *__restrict__ row, int64_t e, int64_t n_evals, int n_out, float thr)
-{
-    if (e >= n_evals) return 0u;
-    float v = row[e * n_out] / thr;
-    if (v > 1.0f) v = 1.0f;                    // :323-325
-    if (v < 0.0f) v = 0.0f;                    // :326-328
-    if (!S16) return __float_as_uint(v);
-    // this project's 16-bit form: rint(v * 32767), ties to even, NaN -> 0 (v is in [0, 1] or NaN here)
-    const float x = (v != v) ? 0.0f : v;
-    return (unsigned)(int)rintf(x * 32767.0f);
-}
 
 // Planar rows.  Workgroup (b, c) writes the samples [head + b span, head + (b + 1) span) of row c, where `head` (< 16 bytes) is
 // what lies in front of the row's first 16-byte line; workgroup 0 also writes the head.  Every lane stores one aligned group
@@ -201,13 +181,6 @@ trace_interleaved_s16_kernel(const float *__restrict__ outputs, int64_t n_evals,
                 if (j < n) reinterpret_cast<uint16_t *>(p)[j] = (uint16_t)w[j];
         }
     }
-}
-
-// ceil(2^32 / d) where n / d == umulhi(n, magic) for every n < bound (n d < 2^32), else 0: the kernels divide then
-unsigned magic_for(uint64_t bound, unsigned d)
-{
-    if (d <= 1 || bound * d >= (1ull << 32)) return 0u;
-    return (unsigned)(((1ull << 32) + d - 1) / d);
 }
 
 // samples per workgroup of the planar kernel: a span of n samples (and a head of up to 7) touches at most (n + 5) / hop + 2

@@ -28,6 +28,7 @@
 #include <algorithm>
 
 #include "kernels.hpp"
+#include "track_values.hpp"   // the scan, trigger_high and the onsets of one recording
 
 namespace sd {
 
@@ -35,31 +36,9 @@ namespace {
 
 constexpr int kTrigSpanBytes = 16384;     // bytes of one channel's row per workgroup (planar): the trace's span (kTraceSpanBytes)
 constexpr int kTrigSlice = kTrigSpanBytes / 2 / 8 + 8;   // table entries a span may touch: span / L + 2 at L = 8, int16, and slack
-constexpr int kScanItems = 8;             // buffers a lane scans in a row ...
-constexpr int kScanChunk = 256 * kScanItems;   // ... and a workgroup per step
 constexpr int kTrigTileCh = 64;           // interleaved: channels per tile ...
 constexpr int kTrigTileFrames = 256;      // ... and frames (a multiple of 8: whole 16-byte groups for any channel count)
 constexpr int kTrigTileSlice = kTrigTileFrames / 8 + 2;   // table entries of one channel a tile may touch (L = 8)
-
-// inclusive scan of one int a lane over the 256 lanes of a workgroup (Hillis-Steele in LDS); MAX: maximum, else sum
-template <bool MAX>
-__device__ __forceinline__ int block_scan(int v, int *buf, int tid)
-{
-    buf[tid] = v;
-    __syncthreads();
-#pragma unroll
-    for (int d = 1; d < 256; d <<= 1) {
-        const int o = tid >= d ? buf[tid - d] : (MAX ? -1 : 0);
-        __syncthreads();
-        v = MAX ? max(v, o) : v + o;
-        buf[tid] = v;
-        __syncthreads();
-    }
-    return v;
-}
-
-// ceil(a / d) for d >= 1, 0 for a <= 0
-__device__ __forceinline__ int64_t ceil_div_pos(int64_t a, int64_t d) { return a <= 0 ? 0 : (a + d - 1) / d; }
 
 // One workgroup a channel.  A chunk of buffers [b0, b0 + kScanChunk): the evaluations that become available in them are read
 // once, in order (a byte a lane), and mark their buffer in LDS; then a max-scan along the chunk with the carry of the chunks before.
@@ -72,48 +51,7 @@ trigger_scan_kernel(const uint8_t *__restrict__ flags, int64_t n_evals, int64_t 
     const int c = blockIdx.x, tid = threadIdx.x;
     const uint8_t *fl = flags + (int64_t)c * n_evals;
     int *out = last_seen + (int64_t)c * Bp;
-    int carry = -1;
-    for (int b0 = 0; b0 < Bp; b0 += kScanChunk) {
-        const int nb = min(kScanChunk, Bp - b0);
-        for (int i = tid; i < kScanChunk; i += 256) seen[i] = -1;
-        __syncthreads();
-        // evaluations e with b0 <= b(e) < b0 + nb:  D + e hop - 1 >= b0 L  <=>  e >= ceil((b0 L + 1 - D) / hop)
-        const int64_t e_lo = min(ceil_div_pos(((int64_t)b0 << lgL) + 1 - D, hop), n_evals);
-        const int64_t e_hi = min(ceil_div_pos(((int64_t)(b0 + nb) << lgL) + 1 - D, hop), n_evals);
-        for (int64_t e = e_lo + tid; e < e_hi; e += 256)
-            if (fl[e] != 0) {
-                const int64_t b = max(D + e * hop - 1, (int64_t)0) >> lgL;
-                const int64_t i = b - b0;
-                if (i >= 0 && i < nb) seen[i] = (int)b;        // (lanes that meet in a buffer write the same value)
-            }
-        __syncthreads();
-        int run = -1;
-#pragma unroll
-        for (int j = 0; j < kScanItems; j++) {
-            run = max(run, seen[tid * kScanItems + j]);
-            seen[tid * kScanItems + j] = run;
-        }
-        const int incl = block_scan<true>(run, buf, tid);
-        (void)incl;
-        const int before = max(carry, tid > 0 ? buf[tid - 1] : -1);
-        const int total = buf[255];
-#pragma unroll
-        for (int j = 0; j < kScanItems; j++) seen[tid * kScanItems + j] = max(seen[tid * kScanItems + j], before);
-        __syncthreads();
-        for (int i = tid; i < nb; i += 256) out[b0 + i] = seen[i];
-        carry = max(carry, total);
-        __syncthreads();
-    }
-}
-
-// one sample of the closed form: the table through `at` (an index into the channel's last_seen row, already clamped)
-template <class At>
-__device__ __forceinline__ bool trigger_high(int64_t s, int64_t Lat, int lgL, int64_t N, At at)
-{
-    const int64_t u = s - Lat;
-    if (u < ((int64_t)1 << lgL)) return false;
-    const int b = at((u >> lgL) - 1);
-    return b >= 0 && s < (((int64_t)b + 1) << lgL) + Lat + N;
+    trigger_scan_row(fl, n_evals, D, hop, lgL, out, Bp, seen, buf, tid);
 }
 
 // Planar rows; the structure of trace_kernel.  Workgroup (b, c) writes the samples [head + b span, head + (b + 1) span) of row c,
@@ -279,35 +217,7 @@ trigger_onsets_kernel(const int *__restrict__ last_seen, int Bp, int lgL, int64_
     const int c = blockIdx.x, tid = threadIdx.x;
     const int *row = last_seen + (int64_t)c * Bp;
     int64_t *idx = indices + (int64_t)c * capacity;
-    const int64_t K = N >> lgL;
-    int64_t carry = 0;
-    for (int b0 = 0; b0 < Bp; b0 += kScanChunk) {
-        const int first = b0 + tid * kScanItems;
-        unsigned mask = 0u;
-        int prev = (first > 0 && first <= Bp) ? row[first - 1] : -1;
-#pragma unroll
-        for (int j = 0; j < kScanItems; j++) {
-            const int b = first + j;
-            if (b < Bp) {
-                const int cur = row[b];
-                const int64_t t = (((int64_t)b + 1) << lgL) + Lat;
-                if (cur == b && t < n_samples && (prev < 0 || (int64_t)prev < (int64_t)b - K)) mask |= 1u << j;
-                prev = cur;
-            }
-        }
-        const int mine = __popc(mask);
-        const int incl = block_scan<false>(mine, buf, tid);
-        const int total = buf[255];
-        int64_t at = carry + (incl - mine);
-#pragma unroll
-        for (int j = 0; j < kScanItems; j++)
-            if (mask & (1u << j)) {
-                if (at < capacity) idx[at] = (((int64_t)(first + j) + 1) << lgL) + Lat;
-                at++;
-            }
-        carry += total;
-        __syncthreads();
-    }
+    const int64_t carry = trigger_onsets_row(row, Bp, lgL, N, Lat, n_samples, idx, capacity, buf, tid);
     if (tid == 0) counts[c] = carry;
 }
 

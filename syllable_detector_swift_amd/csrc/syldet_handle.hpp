@@ -318,5 +318,7 @@ void forget_call(const syldet *h);    // the handle is going: the thread's last 
 int run_on_stream(syldet *h, Samples x, int64_t S, int64_t stride, int C, float *d_outputs, uint8_t *d_flags, hipStream_t stream,
                   const int *d_net_of = nullptr, const int *d_row_of = nullptr);
 int interleaved_args(const syldet *h, int64_t n_frames, int32_t total_channels);
+// syldet_trace.cpp: the [C] fp32 table Float(thresholds[k]) of every channel's own network, on the device (the current one is the handle's)
+int trace_thresholds(syldet *h, int k, const float **out);
 
 }  // namespace sd

@@ -1,6 +1,7 @@
 // syldet_recordings.cpp -- packed recordings (include/syldet.h, "packed recordings"): the plan that lays many recordings of
 // different lengths end to end in a bank's rows, and the handle that keeps the plan's tables on the device so that the
-// device calls (kernels_recordings.hip; kernels_recordings_sinc.hip for recordings at other rates) are launches only.
+// device calls (kernels_recordings.hip; kernels_recordings_sinc.hip for recordings at other rates) are launches only.  The handle
+// itself is in syldet_recordings.hpp; its per-sample tracks are in syldet_recordings_tracks.cpp.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -12,41 +13,9 @@
 #include <string>
 #include <vector>
 
-#include "kernels.hpp"
-#include "syldet_internal.hpp"
+#include "syldet_recordings.hpp"
 
 using sd::fail;
-
-struct syldet_recordings {
-    sd::BankInfo bank{};
-    int K = 0;
-    std::vector<syldet_slot_t> slots;        // [K] the caller's order
-    int64_t row_samples = 0, row_evals = 0;
-    double fill = 0.0;
-    // the load kernel's table: slots sorted by (row, offset); order[i] = the recording of table entry i
-    std::vector<sd::RecSlotDev> table;
-    std::vector<int32_t> order;
-    std::vector<int64_t> src_offset;         // [K] the sources the device table holds (empty: none yet)
-    std::vector<int32_t> src_step;
-    hipStream_t last_load = nullptr;
-    void *d_blob = nullptr;                  // table | events | row_begin | tile_first | the converting load's slots | its workgroup prefixes
-    sd::RecLoadDesc load{};
-    const sd::RecEventDev *d_events = nullptr;
-    // the converting load (syldet_recordings_load_sinc_device*): its own kept sources and tables, so that plain and converting
-    // loads may take turns on one handle
-    std::vector<int32_t> row_begin;          // [C + 1] the table's rows
-    bool sinc_kept = false;
-    hipStream_t sinc_last_load = nullptr;
-    std::vector<int64_t> sinc_offset, sinc_samples;   // [K]
-    std::vector<int32_t> sinc_step;
-    std::vector<double> sinc_rate;
-    int32_t sinc_Z = 0;
-    double sinc_beta = 0.0, sinc_rho = 0.0;
-    std::vector<char> sinc_host;             // slots [K] | prefixes [K + C]: what one copy uploads
-    size_t sinc_wg_at = 0;                   // where the prefixes begin in it (and behind d_sinc)
-    char *d_sinc = nullptr;                  // (inside d_blob)
-    sd::RecSincDesc sinc{};
-};
 
 namespace {
 
@@ -320,9 +289,11 @@ int syldet_recordings_create(const syldet_t *h, const int64_t *n_samples, const 
     std::unique_ptr<syldet_recordings, int (*)(syldet_recordings_t *)> r(nullptr, syldet_recordings_destroy);
     std::vector<sd::RecEventDev> events;
     std::vector<int32_t> row_begin, tile_first;
+    std::vector<int64_t> lengths;
     int tiles = 0;
     try {
         r.reset(new syldet_recordings());
+        r->h = const_cast<syldet_t *>(h);
         r->bank = b;
         r->K = n_recordings;
         r->slots = std::move(p.slots);
@@ -373,16 +344,27 @@ int syldet_recordings_create(const syldet_t *h, const int64_t *n_samples, const 
         r->sinc_samples.reserve((size_t)r->K);
         r->sinc_step.reserve((size_t)r->K);
         r->sinc_rate.reserve((size_t)r->K);
+        // the tracks' tables likewise
+        r->track_offset.reserve((size_t)r->K);
+        r->track_step.reserve((size_t)r->K);
+        r->track_host.assign((size_t)r->K, sd::RecTrackDev{});
+        r->ls_host.assign((size_t)r->K + 1, 0);
+        for (int k = 0; k < r->K; k++) lengths.push_back(r->slots[(size_t)k].n_samples);
     } catch (const std::bad_alloc &) {
         return fail(SYLDET_ERR_OUT_OF_MEMORY, "out of memory");
     }
+    // ... and the tracks': destinations [K] | last_seen prefix [K + 1] | lengths [K]
+    const size_t n_track = up16(r->table.size() * sizeof(sd::RecTrackDev)), n_ls = up16((r->table.size() + 1) * sizeof(int32_t)),
+                 n_len = up16(r->table.size() * sizeof(int64_t));
     SYLDET_HIP(hipSetDevice(b.device));
-    hipError_t e = hipMalloc(&r->d_blob, n_table + n_events + n_begin + n_tiles + n_sinc + 16);
+    hipError_t e = hipMalloc(&r->d_blob, n_table + n_events + n_begin + n_tiles + n_sinc + n_track + n_ls + n_len + 16);
     if (e != hipSuccess) {
         r->d_blob = nullptr;
         return fail(e == hipErrorOutOfMemory ? SYLDET_ERR_OUT_OF_MEMORY : SYLDET_ERR_DEVICE, std::string("hipMalloc: ") + hipGetErrorString(e));
     }
     char *base = (char *)r->d_blob;
+    // (the slots without sources: the track calls read their offsets and lengths, and may come before any load)
+    if (!r->table.empty()) SYLDET_HIP(hipMemcpy(base, r->table.data(), r->table.size() * sizeof(sd::RecSlotDev), hipMemcpyHostToDevice));
     if (!events.empty()) SYLDET_HIP(hipMemcpy(base + n_table, events.data(), events.size() * sizeof(sd::RecEventDev), hipMemcpyHostToDevice));
     SYLDET_HIP(hipMemcpy(base + n_table + n_events, row_begin.data(), row_begin.size() * sizeof(int32_t), hipMemcpyHostToDevice));
     if (!tile_first.empty()) SYLDET_HIP(hipMemcpy(base + n_table + n_events + n_begin, tile_first.data(), tile_first.size() * sizeof(int32_t), hipMemcpyHostToDevice));
@@ -391,6 +373,11 @@ int syldet_recordings_create(const syldet_t *h, const int64_t *n_samples, const 
     r->d_events = (const sd::RecEventDev *)(base + n_table);
     r->d_sinc = base + n_table + n_events + n_begin + n_tiles;
     r->sinc = sd::RecSincDesc{(const sd::RecSincDev *)r->d_sinc, r->load.row_begin, (const int32_t *)(r->d_sinc + r->sinc_wg_at), 0, r->row_samples};
+    char *tracks = r->d_sinc + n_sinc;
+    r->d_track = (sd::RecTrackDev *)tracks;
+    r->d_ls_begin = (int32_t *)(tracks + n_track);
+    if (!lengths.empty()) SYLDET_HIP(hipMemcpy(tracks + n_track + n_ls, lengths.data(), lengths.size() * sizeof(int64_t), hipMemcpyHostToDevice));
+    r->track = sd::RecTrackDesc{r->load, r->d_events, r->d_track, r->d_ls_begin, (const int64_t *)(tracks + n_track + n_ls), r->K, r->row_evals};
     *out = r.release();
     return SYLDET_OK;
 }
@@ -401,6 +388,10 @@ int syldet_recordings_destroy(syldet_recordings_t *r)
     if (r->d_blob) {
         (void)hipSetDevice(r->bank.device);
         (void)hipFree(r->d_blob);
+    }
+    if (r->d_last_seen) {
+        (void)hipSetDevice(r->bank.device);
+        (void)hipFree(r->d_last_seen);
     }
     delete r;
     return SYLDET_OK;

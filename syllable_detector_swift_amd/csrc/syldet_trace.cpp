@@ -13,7 +13,7 @@ static int trace_args(const syldet *h, const void *outputs, int64_t n_evals, int
 }
 
 // Float(thresholds[k]) of every channel's own network on the device: made on the first trace of output k, kept by the handle
-static int trace_thresholds(syldet *h, int k, const float **out)
+int sd::trace_thresholds(syldet *h, int k, const float **out)
 {
     try {
         if (h->d_trace_thr.empty()) h->d_trace_thr.resize((size_t)h->geom.outputs);

@@ -816,7 +816,7 @@ class SyllableDetector:
         return Recordings(self, lengths, networks)
 
     def runRecordings(self, arrays, debounce: float = 0.0, networks=None, rates=None, resample=None, zeroCrossings=None, beta=None,
-                      rolloff=None):
+                      rolloff=None, tracks=None, output: int = 0, bufferLength: int = 32, width: Optional[int] = None, latency: int = 0):
         """Recordings of any lengths in one pass: one upload, load, run / runPCM16, events and one download.  `arrays`: 1-D
         (mono) or [frames, tracks] numpy arrays, all float32 or all int16 (16-bit PCM); every track is a recording, in order
         (`networks`, on a multi / mixed bank: one entry a track).  Returns, per recording, (indices int64 [n], values float32
@@ -825,8 +825,15 @@ class SyllableDetector:
         resample="sinc" is required: the plan is made from recordingLengths of the arrays' lengths, the rows are loaded through
         Recordings.loadSinc (band-limited conversion as they load; an array at the network's rate is copied) and run as fp32 --
         per recording what convertRate(method="sinc"), run and detections give on it alone.  zeroCrossings, beta, rolloff: the
-        converter's quality (None: sincDefaults())."""
+        converter's quality (None: sincDefaults()).
+        `tracks`: None, or names out of ("trace", "ttl"): the per-sample tracks of the same run (Recordings.trace of `output`,
+        Recordings.triggerTrack with bufferLength, width, latency), as 16-bit PCM at the network's rate.  The call then returns
+        (events, tracks): events what it returns without, tracks a dict of a list per name, one int16 array a recording in the
+        caller's order."""
         torch = _torch()
+        names = () if tracks is None else tuple(tracks)
+        if any(t not in ("trace", "ttl") for t in names):
+            raise ValueError("tracks are 'trace' and 'ttl'")
         if rates is None and (resample is not None or zeroCrossings is not None or beta is not None or rolloff is not None):
             raise ValueError("resample, zeroCrossings, beta and rolloff belong to rates")
         if rates is not None and resample != "sinc":
@@ -842,11 +849,11 @@ class SyllableDetector:
         for i, a in enumerate(arrays):
             if a.ndim not in (1, 2):
                 raise ValueError("each array is 1-D (mono) or [frames, tracks]")
-            tracks = 1 if a.ndim == 1 else a.shape[1]
-            for t in range(tracks):
+            n_tracks = 1 if a.ndim == 1 else a.shape[1]
+            for t in range(n_tracks):
                 lengths.append(a.shape[0])
                 offsets.append(pos + t)
-                steps.append(tracks)
+                steps.append(n_tracks)
                 if rates is not None:
                     track_rates.append(float(rates[i]))
             pos += (a.size + 7) // 8 * 8                          # every file from a whole 16 bytes
@@ -859,7 +866,8 @@ class SyllableDetector:
         planned = lengths if rates is None else recordingLengths(lengths, track_rates, self.config.samplingRate)
         with self.recordings(planned, networks) as rec:
             if rec.rowEvaluations <= 0:
-                return [(np.zeros(0, np.int64), np.zeros((0, n_out), np.float32)) for _ in lengths]
+                none = [(np.zeros(0, np.int64), np.zeros((0, n_out), np.float32)) for _ in lengths]
+                return none if tracks is None else (none, {t: [np.zeros(n, np.int16) for n in planned] for t in names})
             if rates is None:
                 rows = rec.load(torch.from_numpy(flat).to("cuda:%d" % self.device), offsets, steps)
                 out, fl = (self.runPCM16 if s16 else self.run)(rows)
@@ -868,9 +876,14 @@ class SyllableDetector:
                                     rolloff)
                 out, fl = self.run(rows)
             idx, val, cnt = rec.events(out, fl, debounce)
+            made = {}
+            for t in names:
+                made[t] = rec.trace(out, output) if t == "trace" else rec.triggerTrack(fl, bufferLength, width, latency)
             torch.cuda.current_stream(self.device).synchronize()
             idx, val, cnt = idx.cpu().numpy(), val.cpu().numpy(), cnt.cpu().numpy()
-        return [(idx[k, :cnt[k]].copy(), val[k, :cnt[k]].copy()) for k in range(len(lengths))]
+            made = {t: [rec.trackView(v, k).copy() for k in range(rec.count)] for t, v in ((t, v.cpu().numpy()) for t, v in made.items())}
+        events = [(idx[k, :cnt[k]].copy(), val[k, :cnt[k]].copy()) for k in range(len(lengths))]
+        return events if tracks is None else (events, made)
 
     # ---- threshold calibration: score a run against labelled times -------------------------
     def scorer(self, thresholds, labels, tolerance: int, debounce: float = 0.0) -> "Scorer":
@@ -1093,6 +1106,120 @@ class Recordings:
                                                        idx.data_ptr(), None if val is None else val.data_ptr(), cap, cnt.data_ptr(),
                                                        det._stream_ptr(stream)))
         return idx, val, cnt
+
+    # ---- every recording's output track and trigger track (syldet_recordings_trace_device*, syldet_recordings_trigger*_device*) ----
+    def _track_steps(self, steps):
+        stp = np.ones(self.count, np.int32) if steps is None else np.ascontiguousarray(steps, dtype=np.int32).reshape(-1)
+        if stp.size != self.count:
+            raise ValueError("one step per recording")
+        if self.count and stp.min() < 1:
+            raise ValueError("steps must be at least 1")
+        return stp
+
+    def trackLayout(self, steps=None, align: int = 8):
+        """The default destination of the tracks: the recordings end to end in the caller's order, each from a multiple of
+        `align` elements (8 int16 elements are 16 bytes).  Recording k of n_k samples takes (n_k - 1) * steps[k] + 1 elements
+        (steps None: all 1, so n_k).  Returns (offsets, total): offsets an int64 array [K], total the elements in all.  Host only."""
+        a = int(align)
+        if a < 1:
+            raise ValueError("align must be at least 1")
+        stp = self._track_steps(steps)
+        off, pos = np.zeros(self.count, np.int64), 0
+        for k, s in enumerate(self.slots):
+            pos = (pos + a - 1) // a * a
+            off[k] = pos
+            pos += (s[4] - 1) * int(stp[k]) + 1 if s[4] > 0 else 0
+        return off, pos
+
+    def _track_dst(self, dtype, offsets, steps, out, device):
+        torch = _torch()
+        dt = SyllableDetector._trace_dtype(dtype, False)
+        tdt = torch.float32 if dt == np.dtype(np.float32) else torch.int16
+        stp = self._track_steps(steps)
+        if offsets is None:
+            off, total = self.trackLayout(stp)
+        else:
+            off = np.ascontiguousarray(offsets, dtype=np.int64).reshape(-1)
+            if off.size != self.count:
+                raise ValueError("one offset per recording")
+            if self.count and off.min() < 0:
+                raise ValueError("offsets must not be negative")
+            n = np.array([s[4] for s in self.slots], np.int64)
+            total = int((off + np.maximum(n - 1, 0) * stp + 1)[n > 0].max(initial=0))
+        if out is None:
+            out = torch.zeros((total,), dtype=tdt, device=device)
+        elif not (out.is_cuda and out.dtype == tdt and out.dim() == 1 and out.is_contiguous() and out.device == device):
+            raise ValueError("out must be a contiguous 1-D CUDA tensor of the track's dtype on the detector's device")
+        elif out.numel() < total:
+            raise ValueError("a recording's track reaches outside out")
+        return dt, off, stp, out
+
+    def trace(self, outputs, output: int = 0, dtype=np.int16, offsets=None, steps=None, out=None, stream=None):
+        """Every recording's output track in one launch (syldet_recordings_trace_device*): outputs [C, rowEvaluations, n_out] as
+        run() wrote them for the loaded rows -> a 1-D tensor in which element i of recording k lies at offsets[k] + i * steps[k],
+        with the values SyllableDetector.trace() gives on that recording alone.  offsets None: trackLayout(steps); steps None:
+        all 1; step n with offsets base + t writes track t of an n-track file's frames.  `out`: the tensor to write into (only the
+        recordings' own elements are written); None: a new one, zero elsewhere.  dtype np.int16 or np.float32."""
+        torch = _torch()
+        det = self.detector
+        E, n_out = self.rowEvaluations, det.geometry.outputs
+        if not (outputs.is_cuda and outputs.dtype == torch.float32 and tuple(outputs.shape) == (det.channels, E, n_out)
+                and outputs.is_contiguous() and outputs.device.index == det.device):
+            raise ValueError("outputs must be a contiguous float32 CUDA tensor [channels, rowEvaluations, outputs] on the detector's device")
+        dt, off, stp, out = self._track_dst(dtype, offsets, steps, out, outputs.device)
+        fn = _abi.lib.syldet_recordings_trace_device if dt == np.dtype(np.float32) else _abi.lib.syldet_recordings_trace_device_s16
+        check(fn(self._h, outputs.data_ptr() if E > 0 else None, int(output), out.data_ptr() if out.numel() else None, int(out.numel()),
+                 off.ctypes.data_as(_abi.c_int64_p), stp.ctypes.data_as(_abi.c_int32_p), det._stream_ptr(stream)))
+        return out
+
+    def _track_flags(self, flags, bufferLength, width, latency):
+        torch = _torch()
+        det = self.detector
+        if not (flags.is_cuda and flags.dtype == torch.uint8 and tuple(flags.shape) == (det.channels, self.rowEvaluations)
+                and flags.is_contiguous() and flags.device.index == det.device):
+            raise ValueError("flags must be a contiguous uint8 CUDA tensor [channels, rowEvaluations] on the detector's device")
+        N = det.triggerWidth() if width is None else int(width)
+        return int(bufferLength), N, int(latency)
+
+    def triggerTrack(self, flags, bufferLength: int = 32, width: Optional[int] = None, latency: int = 0, dtype=np.int16, offsets=None,
+                     steps=None, out=None, stream=None):
+        """Every recording's TTL trigger track (syldet_recordings_trigger_device*: a scan and an expansion): flags
+        [C, rowEvaluations] as run() wrote them -> the destination of trace(), with the values SyllableDetector.triggerTrack()
+        gives on that recording's flags alone; a pulse never reaches the next recording of a row."""
+        det = self.detector
+        L, N, lat = self._track_flags(flags, bufferLength, width, latency)
+        dt, off, stp, out = self._track_dst(dtype, offsets, steps, out, flags.device)
+        fn = _abi.lib.syldet_recordings_trigger_device if dt == np.dtype(np.float32) else _abi.lib.syldet_recordings_trigger_device_s16
+        check(fn(self._h, flags.data_ptr() if self.rowEvaluations > 0 else None, L, N, lat, out.data_ptr() if out.numel() else None,
+                 int(out.numel()), off.ctypes.data_as(_abi.c_int64_p), stp.ctypes.data_as(_abi.c_int32_p), det._stream_ptr(stream)))
+        return out
+
+    def triggerOnsets(self, flags, bufferLength: int = 32, width: Optional[int] = None, latency: int = 0, capacity: Optional[int] = None,
+                      stream=None):
+        """The rising edges of every recording's trigger track (syldet_recordings_trigger_onsets_device): (indices [K, capacity]
+        i64, counts [K] i64), sample numbers from each recording's own start, in order; counts may exceed capacity (default: the
+        most a recording can have)."""
+        torch = _torch()
+        det = self.detector
+        L, N, lat = self._track_flags(flags, bufferLength, width, latency)
+        if L < 1:
+            raise ValueError("bufferLength must be a power of two in [8, 4096]")
+        cap = max([min(s[3], s[4] // L + 1) for s in self.slots], default=0) if capacity is None else int(capacity)
+        if cap < 0:
+            raise ValueError("capacity must not be negative")
+        idx = torch.empty((self.count, cap), dtype=torch.int64, device=flags.device)       # (capacity 0: counts only, no index is written)
+        cnt = torch.zeros((self.count,), dtype=torch.int64, device=flags.device)
+        check(_abi.lib.syldet_recordings_trigger_onsets_device(self._h, flags.data_ptr() if self.rowEvaluations > 0 else None, L, N, lat,
+                                                               idx.data_ptr() if idx.numel() else None, cap, cnt.data_ptr() if self.count else None,
+                                                               det._stream_ptr(stream)))
+        return idx, cnt
+
+    def trackView(self, tensor, k: int, offsets=None, steps=None):
+        """Recording k's elements of a track tensor (or array) written with these offsets and steps: [n_k], no copy."""
+        stp = self._track_steps(steps)
+        off = self.trackLayout(stp)[0] if offsets is None else np.ascontiguousarray(offsets, dtype=np.int64).reshape(-1)
+        n, o, s = self.slots[k][4], int(off[k]), int(stp[k])
+        return tensor[o:o + (n - 1) * s + 1:s] if n > 0 else tensor[o:o]
 
     def scorer(self, thresholds, labels, tolerance: int, debounce: float = 0.0) -> "Scorer":
         """A Scorer whose detectors are these recordings: labels[k], the labelled sample numbers of recording k, count from its
