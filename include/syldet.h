@@ -977,6 +977,61 @@ int syldet_recordings_trigger_onsets_device(syldet_recordings_t *r, const uint8_
                                             int64_t latency_samples, int64_t *d_indices, int64_t capacity, int64_t *d_counts,
                                             void *hip_stream);
 
+/* ---- packed recordings: every recording's level meters ----
+ * The third batch product of a run -- the level meters of a row (syldet_levels*, syldet_output_levels*) -- for every recording
+ * of a packed bank, in a fixed number of launches whatever K is.  L = buffer_length, P = buffers_per_reading, with the limits
+ * stated for syldet_levels*.
+ * THE LAYOUT (syldet_recordings_levels_layout: host only, no device is touched): recording k of n_k = slots[k].n_samples samples
+ * has M_k = syldet_levels_count(n_k, L, P) readings (0 for a recording without samples); they are elements
+ * [reading_first[k], reading_first[k + 1]) of the result arrays, in the caller's order of recordings, and *n_readings =
+ * reading_first[K].  reading_first (K + 1 entries) may be NULL.
+ *   syldet_recordings_levels_device*         d_rows [C][channel_stride] fp32 or (_s16) int16: the rows syldet_recordings_load_device*
+ *       or syldet_recordings_load_sinc_device* wrote -> d_mean_square [n_readings] fp64
+ *   syldet_recordings_output_levels_device   d_outputs [C][row_evals][n_out] as syldet_run_device* wrote it for the packed rows
+ *       -> d_levels [n_readings] fp32
+ * `capacity` is the size of the result array in elements; no element past n_readings is written.
+ * THE CONTRACT is identity with the calls for one recording:
+ *   input meter    recording k's M_k mean squares are, bit for bit, what syldet_levels_device (_s16) writes for that recording
+ *       alone (a one-channel handle, n_samples = n_k, the same L and P): buffers are counted from the recording's own sample 0,
+ *       buffer b is its samples [b L, min((b + 1) L, n_k)), the last one divides by its own length, sum_squares_tree runs in
+ *       index order from the recording's start (not the row's), and P is clamped to the recording's own buffer count as the
+ *       one-recording call clamps it.  A reading is NaN exactly where the one-recording call's is (the payload bits of a NaN are
+ *       not part of the contract).  Nothing outside a recording is ever read as part of it -- not a pad, not the next recording
+ *       of the row, not the tail of a short row: a short last buffer is masked at n_k, not trusted to find zeros.
+ *   output meter   recording k's M_k values are those of syldet_output_levels_device on the recording's n_evals_k outputs alone
+ *       with n_samples = n_k: the evaluation range of reading m is syldet_levels_eval_range's for (n_k, n_evals_k), read at row
+ *       evaluations first_eval_k + e; 0 for a reading without an evaluation.  Row evaluations outside every recording are never
+ *       read.  Plain, multi-network and mixed banks alike: `output` is checked against, and n_out taken from, the bank's outputs,
+ *       as syldet_output_levels_device does.
+ * Statuses, decided before any device is touched: SYLDET_ERR_INVALID_ARGUMENT for a NULL handle or pointer (d_outputs may be NULL
+ * where row_evals is 0), channel_stride < row_samples, an L that is not a power of two in [8, 4096], P < 1, `output` outside
+ * [0, outputs), and capacity < n_readings (syldet_last_error says how many are needed).  A refused call writes nothing.
+ * THE LAUNCH RULE is the tracks': the handle keeps (L, P) and, on the device, the reading prefix of that pair (K + 1 words, and
+ * the same K starts once more in the order of the plan's table), apart from the tracks' and the loads' tables.  A call whose
+ * (L, P) differs from the kept pair (the first always) waits for the stream of the handle's last levels call and uploads once,
+ * with a blocking copy; the same pair again is launches only, without allocation, synchronisation or copy.  One pair is kept for
+ * the two meters together.  No scratch: a reading that crosses workgroups is made with one vector atomic maximum a workgroup on
+ * the bits of its mean squares (non-negative doubles order as unsigned integers; a NaN first value goes in as the canonical quiet
+ * NaN, above +inf), over a table set to +0 first -- exact, the same bits whatever the order, and no workgroup waits for another.
+ * Launches, by the names syldet_timings lists:
+ *   input meter    "recordings_levels_zero_kernel" (only where rows are longer than one tile of 8192 samples: the +0 the atomics
+ *                  need), "recordings_levels_in_kernel"
+ *   output meter   "recordings_levels_out_kernel"
+ * The input meter is balanced by rows, not by recordings; it loads 16 bytes a lane where a recording's first sample is 16-byte
+ * aligned in device memory, 8 or 4 bytes an access where it is aligned to that, one element at a time elsewhere (and for a
+ * recording's last partial group).  A sharded bank has no packed form, as before.
+ * STREAMS AND THREADS: as stated for the tracks.  Levels calls of one handle on different streams must be ordered by the caller,
+ * and every call records into the profile of the bank h the handle was created from, so the bank's rule of one caller at a time
+ * covers them too.                                                                                                          */
+int syldet_recordings_levels_layout(const syldet_recordings_t *r, int32_t buffer_length, int64_t buffers_per_reading,
+                                    int64_t *reading_first, int64_t *n_readings);
+int syldet_recordings_levels_device(syldet_recordings_t *r, const float *d_rows, int64_t channel_stride, int32_t buffer_length,
+                                    int64_t buffers_per_reading, double *d_mean_square, int64_t capacity, void *hip_stream);
+int syldet_recordings_levels_device_s16(syldet_recordings_t *r, const int16_t *d_rows, int64_t channel_stride, int32_t buffer_length,
+                                        int64_t buffers_per_reading, double *d_mean_square, int64_t capacity, void *hip_stream);
+int syldet_recordings_output_levels_device(syldet_recordings_t *r, const float *d_outputs, int32_t output, int32_t buffer_length,
+                                           int64_t buffers_per_reading, float *d_levels, int64_t capacity, void *hip_stream);
+
 /* ---- threshold calibration: score a run against labelled times ----
  * Which threshold to ship, and how late and how jittery the trigger is at it: the reference leaves the question to MATLAB
  * (convert_to_text.m:70-72 only copies trigger_thresholds in).  Here the outputs of a run, which are on the device already, are

@@ -260,6 +260,10 @@ SIGNATURES = {
                                                        c_int32_p, C.c_void_p]),
     "syldet_recordings_trigger_onsets_device": (C.c_int, [Handle, C.c_void_p, C.c_int32, C.c_int64, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p,
                                                           C.c_void_p]),
+    "syldet_recordings_levels_layout": (C.c_int, [Handle, C.c_int32, C.c_int64, c_int64_p, c_int64_p]),
+    "syldet_recordings_levels_device": (C.c_int, [Handle, C.c_void_p, C.c_int64, C.c_int32, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p]),
+    "syldet_recordings_levels_device_s16": (C.c_int, [Handle, C.c_void_p, C.c_int64, C.c_int32, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p]),
+    "syldet_recordings_output_levels_device": (C.c_int, [Handle, C.c_void_p, C.c_int32, C.c_int32, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p]),
     "syldet_scorer_create": (C.c_int, [Handle, Handle, c_double_p, C.c_int32, c_int64_p, c_int64_p, C.c_int64, C.c_double, C.POINTER(Handle)]),
     "syldet_scorer_destroy": (C.c_int, [Handle]),
     "syldet_scorer_shape": (C.c_int, [Handle, c_int32_p, c_int32_p, c_int64_p]),

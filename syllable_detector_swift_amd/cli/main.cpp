@@ -9,6 +9,8 @@
 // the fp32 path's bits on x / 32768, which is what the decoder would have produced).
 // --simulate-dir / --ttl-dir / --ttl-onsets-dir write the same files for any number of audio files; under --batch a batch's tracks are
 // made by syldet_recordings_trace_device_s16 / syldet_recordings_trigger*_device_s16 straight into every file's frames.
+// --levels-dir writes every file's --levels table likewise; under --batch by syldet_recordings_levels_device* /
+// syldet_recordings_output_levels_device on the batch's packed rows.
 // --simulate <out.wav> also writes what the reference's Simulator writes (ViewControllerSimulator.swift:251-344): the chosen output
 // over its threshold, held between evaluations, as a 16-bit WAV of every track (syldet_trace_interleaved_device_s16).
 //
@@ -57,6 +59,7 @@ void usage(FILE *to)
                  "      --simulate <out.wav>:\n      Also write the Simulator's output track of every track of the (one) audio file as a 16-bit WAV at the network's sampling rate: the chosen output as a fraction of its threshold (0 = 0, threshold and above = 32767), held from one evaluation to the next.\n"
                  "      --simulate-output <k>:\n      The network output --simulate follows (default 0).\n"
                  "      --levels <out.tsv>:\n      Also write the level meters of every track of the (one) audio file, one line per reading and track, tab separated: the track, the time of the reading's end in seconds, the input RMS (the loudest buffer of the reading), the output level (the greatest first output evaluated in the reading; empty for a reading without an evaluation).\n"
+                 "      --levels-dir <dir>:\n      Write what --levels writes for every audio file, as <dir>/<the audio file's name>.tsv, for any number of files; under --batch the readings come from the batch's packed rows in a fixed number of launches, and only the tables come back from the device.\n"
                  "      --levels-buffer <L>:\n      Samples per buffer of the input meter: a power of two from 8 to 4096 (default 32).\n"
                  "      --levels-period <seconds>:\n      Time between two readings (default 0.1); a reading is a whole number of buffers, at least one.\n"
                  "      --ttl <out.wav>:\n      Also write the TTL trigger track of every track of the (one) audio file as a 16-bit WAV at the network's sampling rate: 32767 for the pulse's width from the output buffer behind every input buffer in which a detection became available, 0 elsewhere.\n"
@@ -146,6 +149,7 @@ struct TtlOpt {
 // --simulate-dir / --ttl-dir / --ttl-onsets-dir: the per-sample products of every audio file, each under its file's name
 struct TrackDirs {
     std::string simulate, ttl, onsets;                     // empty: none
+    std::string levels;                                    // --levels-dir: every file's level table, <name>.tsv (not a track: any() leaves it out)
     bool any() const { return !simulate.empty() || !ttl.empty() || !onsets.empty(); }
     static std::string name_of(const std::string &path)
     {
@@ -165,10 +169,16 @@ struct TrackDirs {
         if (!onsets.empty()) t.onsets = in(onsets, path, ".tsv");
         return t;
     }
+    template <class Levels>
+    Levels levels_for(const std::string &path, Levels l) const
+    {
+        if (!levels.empty()) l.path = in(levels, path, ".tsv");
+        return l;
+    }
     void make() const                                      // (a directory that cannot be made: the writes fail, and cost what they cost)
     {
         std::error_code ec;
-        for (const std::string *d : {&simulate, &ttl, &onsets})
+        for (const std::string *d : {&simulate, &ttl, &onsets, &levels})
             if (!d->empty()) std::filesystem::create_directories(*d, ec);
     }
 };
@@ -551,7 +561,8 @@ bool read_labels(const std::string &path, ScoreRun &run, std::string &err)
 // One batch: returns 0, 2 for device trouble (no line of the batch is printed then, but the files' names are), or 3: the lines are
 // out, a track is not
 int run_batch(std::vector<BatchFile> &files, const std::vector<syldet_config_t *> &cfgs, int device, double debounce_s, int64_t chunk,
-              long max_rows, bool headers, ScoreRun *score, const ResampleOpt &conv, const TrackDirs &dirs, int simulate_output, const TtlOpt &ttl)
+              long max_rows, bool headers, ScoreRun *score, const ResampleOpt &conv, const TrackDirs &dirs, int simulate_output, const TtlOpt &ttl,
+              const LevelsOpt &levels)
 {
     if (files.empty()) return 0;
     const syldet_config_t *cfg = cfgs[0];
@@ -604,6 +615,15 @@ int run_batch(std::vector<BatchFile> &files, const std::vector<syldet_config_t *
     std::vector<int16_t> sim_frames, ttl_frames;            // (zeros where no file of the batch has an evaluation)
     std::vector<int64_t> on_idx, on_cnt;
     int64_t on_cap = 1;
+    // --levels-dir: the two tables of every recording, flat as syldet_recordings_levels_layout lays them, and which readings have
+    // no evaluation
+    const bool metering = !dirs.levels.empty();
+    const double lv_per = levels.period * cfg->sampling_rate / (double)levels.buffer;
+    const int64_t lv_P = lv_per >= 1.0 ? (lv_per < 9e18 ? (int64_t)lv_per : INT64_MAX) : 1;   // (process_file's)
+    std::vector<int64_t> lv_first((size_t)K + 1, 0);
+    std::vector<double> lv_in;
+    std::vector<float> lv_out;
+    std::vector<char> lv_empty;
     try {
         if (!dirs.simulate.empty()) sim_frames.assign((size_t)dst_total, 0);
         if (!dirs.ttl.empty()) ttl_frames.assign((size_t)dst_total, 0);
@@ -659,7 +679,8 @@ int run_batch(std::vector<BatchFile> &files, const std::vector<syldet_config_t *
             rc = 2;
             break;
         }
-        if (row_evals <= 0) break;                          // every file shorter than one evaluation: no events
+        const bool ran = row_evals > 0;
+        if (!ran && !metering) break;                       // every file shorter than one evaluation: no events (the input meter reads them all the same)
         if (hipSetDevice(device) != hipSuccess || hipStreamCreate(&stream) != hipSuccess) { rc = 2; break; }
         const size_t el = all16 ? sizeof(int16_t) : sizeof(float);
         DevBuf d_src, d_rows, d_out, d_flags, d_idx, d_val, d_cnt;
@@ -677,13 +698,50 @@ int run_batch(std::vector<BatchFile> &files, const std::vector<syldet_config_t *
                                                                 conv.zero_crossings, conv.beta, conv.rolloff, (float *)d_rows.p, row_samples, stream)
                        : syldet_recordings_load_sinc_device(r, (const float *)d_src.p, src_offset.data(), src_step.data(), src_samples.data(), src_rate.data(),
                                                             conv.zero_crossings, conv.beta, conv.rolloff, (float *)d_rows.p, row_samples, stream);
-            if (!st) st = syldet_run_device(h, (const float *)d_rows.p, row_samples, row_samples, (float *)d_out.p, (uint8_t *)d_flags.p, stream);
+            if (!st && ran) st = syldet_run_device(h, (const float *)d_rows.p, row_samples, row_samples, (float *)d_out.p, (uint8_t *)d_flags.p, stream);
         } else if (all16) {
             st = syldet_recordings_load_device_s16(r, (const int16_t *)d_src.p, src_offset.data(), src_step.data(), (int16_t *)d_rows.p, row_samples, stream);
-            if (!st) st = syldet_run_device_s16(h, (const int16_t *)d_rows.p, row_samples, row_samples, (float *)d_out.p, (uint8_t *)d_flags.p, stream);
+            if (!st && ran) st = syldet_run_device_s16(h, (const int16_t *)d_rows.p, row_samples, row_samples, (float *)d_out.p, (uint8_t *)d_flags.p, stream);
         } else {
             st = syldet_recordings_load_device(r, (const float *)d_src.p, src_offset.data(), src_step.data(), (float *)d_rows.p, row_samples, stream);
-            if (!st) st = syldet_run_device(h, (const float *)d_rows.p, row_samples, row_samples, (float *)d_out.p, (uint8_t *)d_flags.p, stream);
+            if (!st && ran) st = syldet_run_device(h, (const float *)d_rows.p, row_samples, row_samples, (float *)d_out.p, (uint8_t *)d_flags.p, stream);
+        }
+        // the level tables of every file of the batch: the input meter on the very rows that are run (int16 rows for 16-bit files, fp32
+        // rows for float files and for converted ones), the output meter on the outputs the run left; only the two tables come back
+        DevBuf d_lv_in, d_lv_out;
+        if (!st && metering) {
+            int64_t n_readings = 0;
+            std::vector<syldet_slot_t> slots((size_t)std::max<int32_t>(K, 1));
+            st = syldet_recordings_levels_layout(r, levels.buffer, lv_P, lv_first.data(), &n_readings);
+            if (!st) st = syldet_recordings_slots(r, slots.data());
+            if (!st) {
+                lv_in.assign((size_t)n_readings, 0.0);
+                lv_out.assign((size_t)n_readings, 0.0f);
+                lv_empty.assign((size_t)n_readings, 1);
+                for (int32_t k = 0; k < K; k++)
+                    for (int64_t m = 0; m < lv_first[(size_t)k + 1] - lv_first[(size_t)k]; m++) {
+                        int64_t first = 0, count = 0;
+                        if (syldet_levels_eval_range(h, slots[(size_t)k].n_samples, slots[(size_t)k].n_evals, levels.buffer, lv_P, m, &first, &count) == SYLDET_OK)
+                            lv_empty[(size_t)(lv_first[(size_t)k] + m)] = count == 0;
+                    }
+                if (!d_lv_in.alloc((size_t)n_readings * sizeof(double)) || !d_lv_out.alloc((size_t)n_readings * sizeof(float))) { rc = 2; break; }
+            }
+            if (!st && n_readings > 0) {
+                st = all16 && !converting ? syldet_recordings_levels_device_s16(r, (const int16_t *)d_rows.p, row_samples, levels.buffer, lv_P, (double *)d_lv_in.p, n_readings, stream)
+                                          : syldet_recordings_levels_device(r, (const float *)d_rows.p, row_samples, levels.buffer, lv_P, (double *)d_lv_in.p, n_readings, stream);
+                if (!st) st = syldet_recordings_output_levels_device(r, ran ? (const float *)d_out.p : nullptr, 0, levels.buffer, lv_P, (float *)d_lv_out.p, n_readings, stream);
+                if (!st && (hipMemcpyAsync(lv_in.data(), d_lv_in.p, lv_in.size() * sizeof(double), hipMemcpyDeviceToHost, stream) != hipSuccess ||
+                            hipMemcpyAsync(lv_out.data(), d_lv_out.p, lv_out.size() * sizeof(float), hipMemcpyDeviceToHost, stream) != hipSuccess)) { rc = 2; break; }
+            }
+            if (st) {
+                std::fprintf(stderr, "Unable to meter the batch: %s: %s\n", syldet_strerror(st), syldet_last_error());
+                rc = 2;
+                break;
+            }
+            if (!ran) {
+                if (hipStreamSynchronize(stream) != hipSuccess) rc = 2;
+                break;
+            }
         }
         // the counts first (a scan of the flags), then the detections themselves into tables of the size they need
         if (!st) st = syldet_recordings_events_device(r, nullptr, (const uint8_t *)d_flags.p, debounce_s, nullptr, nullptr, 0, (int64_t *)d_cnt.p, stream);
@@ -809,6 +867,27 @@ int run_batch(std::vector<BatchFile> &files, const std::vector<syldet_config_t *
                 unwritten = true;
             }
         }
+        // ... and its level table, line for line what process_file writes: reading by reading, track by track
+        if (!rc && metering) {
+            const std::string tsv = TrackDirs::in(dirs.levels, f.path, ".tsv");
+            const int tracks = f.info.channels;
+            const int64_t fed = lengths[(size_t)k0], M = lv_first[(size_t)k0 + 1] - lv_first[(size_t)k0];
+            const int64_t PL = std::min(lv_P, (fed + levels.buffer - 1) / levels.buffer) * levels.buffer;
+            FILE *out = std::fopen(tsv.c_str(), "w");
+            bool ok = out != nullptr;
+            for (int64_t m = 0; ok && m < M; m++)
+                for (int c = 0; ok && c < tracks; c++) {
+                    const size_t at = (size_t)(lv_first[(size_t)(k0 + c)] + m);
+                    const std::string line = std::to_string(c) + "\t" + number((double)std::min((m + 1) * PL, fed) / cfg->sampling_rate) + "\t" +
+                                             number(std::sqrt(lv_in[at])) + "\t" + (lv_empty[at] ? std::string() : number(lv_out[at])) + "\n";
+                    ok = std::fputs(line.c_str(), out) >= 0;
+                }
+            if (out && std::fclose(out) != 0) ok = false;
+            if (!ok) {
+                std::fprintf(stderr, "Unable to write %s.\n", tsv.c_str());
+                unwritten = true;
+            }
+        }
         k0 += f.info.channels;
     }
     files.clear();
@@ -855,7 +934,8 @@ bool write_score_table(const ScoreOpt &opt, const ScoreRun &run)
 // network's rate or -- under --resample sinc -- at a rate the band-limited converter takes) gather until their samples pass
 // opt.bytes; any other file ends the batch and is processed alone in its place.
 int process_batched(const std::vector<std::string> &audio, const std::vector<syldet_config_t *> &cfgs, int device, double debounce_s, bool have_debounce,
-                    int64_t chunk, const BatchOpt &opt, const ResampleOpt &conv, ScoreRun *score, const TrackDirs &dirs, int simulate_output, const TtlOpt &ttl)
+                    int64_t chunk, const BatchOpt &opt, const ResampleOpt &conv, ScoreRun *score, const TrackDirs &dirs, int simulate_output, const TtlOpt &ttl,
+                    const LevelsOpt &levels)
 {
     int rc = 0;
     const bool headers = audio.size() > 1;
@@ -863,7 +943,7 @@ int process_batched(const std::vector<std::string> &audio, const std::vector<syl
     std::vector<BatchFile> files;
     size_t held = 0;
     auto flush = [&]() {
-        const int r = run_batch(files, cfgs, device, deb, chunk, opt.rows, headers, score, conv, dirs, simulate_output, ttl);
+        const int r = run_batch(files, cfgs, device, deb, chunk, opt.rows, headers, score, conv, dirs, simulate_output, ttl, levels);
         if (r == 2) rc = 2;
         else if (r == 3 && rc == 0) rc = 1;
         held = 0;
@@ -892,8 +972,8 @@ int process_batched(const std::vector<std::string> &audio, const std::vector<syl
         if (score && score->labels.count(p)) std::fprintf(stderr, "--score: %s does not go through the bank; its labels are left out.\n", p.c_str());
         if (headers) std::printf("%s\n", p.c_str());
         std::fflush(stdout);
-        const int r = process_file(p, cfgs, device, debounce_s, have_debounce, chunk, dirs.simulate_for(p, std::string()), simulate_output, LevelsOpt(),
-                                   dirs.any() ? dirs.ttl_for(p, ttl) : TtlOpt(), conv);
+        const int r = process_file(p, cfgs, device, debounce_s, have_debounce, chunk, dirs.simulate_for(p, std::string()), simulate_output,
+                                   dirs.levels.empty() ? LevelsOpt() : dirs.levels_for(p, levels), dirs.any() ? dirs.ttl_for(p, ttl) : TtlOpt(), conv);
         if (r == 2) rc = 2;
         else if (r == 3 && rc == 0) rc = 1;
     }
@@ -924,7 +1004,7 @@ int main(int argc, char **argv)
     BatchOpt batch;
     bool have_batch_option = false;
     TrackDirs dirs;
-    bool have_simulate_dir = false, have_ttl_dir = false, have_onsets_dir = false;
+    bool have_simulate_dir = false, have_ttl_dir = false, have_onsets_dir = false, have_levels_dir = false;
     ScoreOpt score;
     bool have_score = false, have_score_option = false;
     auto value = [&](int &i, const char *name) -> const char * {
@@ -1035,6 +1115,9 @@ int main(int argc, char **argv)
         } else if (a == "--simulate-dir") {
             dirs.simulate = value(i, "--simulate-dir");
             have_simulate_dir = true;
+        } else if (a == "--levels-dir") {
+            dirs.levels = value(i, "--levels-dir");
+            have_levels_dir = true;
         } else if (a == "--ttl-dir") {
             dirs.ttl = value(i, "--ttl-dir");
             have_ttl_dir = true;
@@ -1175,11 +1258,21 @@ int main(int argc, char **argv)
         usage(stdout);
         return kExUsage;
     }
-    if (dirs.any()) {                                       // every audio file's products go under its own name
+    if (have_levels_dir && dirs.levels.empty()) {
+        std::fprintf(stderr, "--levels-dir takes the name of a directory.\n");
+        usage(stdout);
+        return kExUsage;
+    }
+    if (have_levels && have_levels_dir) {
+        std::fprintf(stderr, "--levels-dir writes what --levels writes, for every audio file: give the one or the other.\n");
+        usage(stdout);
+        return kExUsage;
+    }
+    if (dirs.any() || have_levels_dir) {                    // every audio file's products go under its own name
         std::set<std::string> names;
         for (const std::string &p : audio)
             if (!names.insert(TrackDirs::name_of(p)).second) {
-                std::fprintf(stderr, "--simulate-dir, --ttl-dir and --ttl-onsets-dir name their files after the audio files: two of those are called %s.\n",
+                std::fprintf(stderr, "--simulate-dir, --ttl-dir, --ttl-onsets-dir and --levels-dir name their files after the audio files: two of those are called %s.\n",
                              TrackDirs::name_of(p).c_str());
                 usage(stdout);
                 return kExUsage;
@@ -1200,8 +1293,8 @@ int main(int argc, char **argv)
         usage(stdout);
         return kExUsage;
     }
-    if (have_levels_option && !have_levels) {
-        std::fprintf(stderr, "--levels-buffer and --levels-period need --levels <out.tsv>.\n");
+    if (have_levels_option && !have_levels && !have_levels_dir) {
+        std::fprintf(stderr, "--levels-buffer and --levels-period need --levels <out.tsv> or --levels-dir <dir>.\n");
         usage(stdout);
         return kExUsage;
     }
@@ -1230,7 +1323,7 @@ int main(int argc, char **argv)
         usage(stdout);
         return kExUsage;
     }
-    if (batch.on && have_levels) {                          // (the meters of a packed bank's recordings are not built)
+    if (batch.on && have_levels) {                          // (one table, one file; a batch's tables go to --levels-dir)
         std::fprintf(stderr, "--levels is not available under --batch: it takes exactly one file and a bank of its own.\n");
         usage(stdout);
         return kExUsage;
@@ -1315,7 +1408,8 @@ int main(int argc, char **argv)
     }
     if (batch.on) {
         dirs.make();
-        int brc = process_batched(audio, cfgs, device, debounce, have_debounce, chunk, batch, conv, have_score ? &scoring : nullptr, dirs, simulate_output, ttl);
+        int brc = process_batched(audio, cfgs, device, debounce, have_debounce, chunk, batch, conv, have_score ? &scoring : nullptr, dirs, simulate_output, ttl,
+                                  levels);
         for (syldet_config_t *c : cfgs) syldet_config_free(c);
         // the table last, and only a whole one; standard output and the status are those of the run without --score
         if (have_score && (scoring.failed || !write_score_table(score, scoring)) && brc == 0) brc = 1;
@@ -1326,7 +1420,8 @@ int main(int argc, char **argv)
     for (const std::string &p : audio) {
         if (audio.size() > 1) std::printf("%s\n", p.c_str());   // main.swift:122-124
         std::fflush(stdout);
-        const int r = process_file(p, cfgs, device, debounce, have_debounce, chunk, dirs.simulate_for(p, simulate), simulate_output, levels, dirs.ttl_for(p, ttl), conv);
+        const int r = process_file(p, cfgs, device, debounce, have_debounce, chunk, dirs.simulate_for(p, simulate), simulate_output, dirs.levels_for(p, levels),
+                                   dirs.ttl_for(p, ttl), conv);
         if (r == 2) rc = 2;                                 // device trouble is fatal for the exit code; an unreadable file is skipped
         else if (r == 3 && rc == 0) rc = 1;                 // ... and so is a track that could not be written
     }

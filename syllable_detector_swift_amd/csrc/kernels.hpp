@@ -462,6 +462,26 @@ hipError_t launch_recordings_trigger(const RecTrackDesc &d, int C, const int *la
 hipError_t launch_recordings_trigger_onsets(const RecTrackDesc &d, const int *last_seen, int L, int64_t N, int64_t Lat, int64_t *indices,
                                             int64_t capacity, int64_t *counts, hipStream_t stream);
 
+// ---- packed recordings: the level meters (kernels_recordings_levels.hip; syldet_recordings_levels_device* and
+// syldet_recordings_output_levels_device of include/syldet.h) ----
+struct RecLevelsDesc {
+    RecLoadDesc load;                        // the plan's slots, rows and tiles: the load's own tables
+    const RecEventDev *events;               // [K]
+    const int64_t *n_samples;                // [K]
+    const int64_t *reading_first;            // [K + 1] recording k's readings are [reading_first[k], reading_first[k + 1]) (the kept L, P)
+    const int64_t *slot_first;               // [K] the same starts in the order of RecSlotDev's table
+    int K;
+    int64_t row_evals, n_readings;           // n_readings = reading_first[K]
+};
+// mean_square [n_readings] <- +0: in front of launch_recordings_levels_in wherever a row has two tiles (a reading may cross them)
+hipError_t launch_recordings_levels_zero(double *mean_square, int64_t n_readings, hipStream_t stream);
+// rows [C][stride] fp32 or (s16) int16 -> mean_square [n_readings] fp64: every recording's launch_levels_in, alone
+hipError_t launch_recordings_levels_in(const RecLevelsDesc &d, int C, const void *rows, bool s16, int64_t stride, int L, int64_t P,
+                                       double *mean_square, hipStream_t stream);
+// outputs [C][row_evals][n_out] -> levels [n_readings] fp32: every recording's launch_levels_out, alone
+hipError_t launch_recordings_levels_out(const RecLevelsDesc &d, int C, const float *outputs, int n_out, int k, int L, int64_t P, int64_t need,
+                                        int64_t hop, int T, float *levels, hipStream_t stream);
+
 // ---- threshold calibration (kernels_score.hip; syldet_score_device of include/syldet.h) ----
 // What a scorer keeps on the device.  A detector is a channel (slots == nullptr: its evaluations are row `det`) or a recording
 // (slots [D]: its own part of its row).

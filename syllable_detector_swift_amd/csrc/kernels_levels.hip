@@ -15,8 +15,10 @@
 #include <algorithm>
 
 #include "kernels.hpp"
+#include "levels_values.hpp"
 
-// a square, an addition: each rounds on its own -- this file is compiled with -ffp-contract=off (see the Makefile)
+// a square, an addition: each rounds on its own -- this file is compiled with -ffp-contract=off (see the Makefile).  The value
+// arithmetic itself is in levels_values.hpp, which the packed recordings' meters (kernels_recordings_levels.hip) share.
 
 namespace sd {
 
@@ -25,57 +27,6 @@ namespace {
 constexpr int kLevelsPasses = 8;                        // 16-byte loads a lane has in flight
 constexpr int kLevelsSpanBytes = 256 * 16 * kLevelsPasses;   // bytes of one channel's row per workgroup: 8192 fp32 / 16384 int16
                                                         // samples, whole buffers for every L <= 4096
-
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-
-// p + (p of lane ^ D).  Distances 1 and 2 are quad permutations; 4 and 8 are the mirrors of 8 and 16 lanes, which are the xor
-// exchanges here because the lanes of a group of D already hold one value; 16 and 32 go through the permute network.
-template <int D>
-__device__ __forceinline__ float xor_add(float p)
-{
-    if constexpr (D == 1) return p + __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(p), 0xB1, 0xf, 0xf, false));
-    else if constexpr (D == 2) return p + __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(p), 0x4E, 0xf, 0xf, false));
-    else if constexpr (D == 4) return p + __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(p), 0x141, 0xf, 0xf, false));
-    else if constexpr (D == 8) return p + __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(p), 0x140, 0xf, 0xf, false));
-    else return p + __shfl_xor(p, D);
-}
-
-// the 16 bytes of the group at sample s, element by element (rows off a 16-byte line, a row's last partial group): n live samples,
-// zeros behind them -- never read
-__device__ __forceinline__ u32x4 load_each(const float *row, int64_t s, int n)
-{
-    u32x4 v = {0u, 0u, 0u, 0u};
-#pragma unroll
-    for (int i = 0; i < 4; i++)
-        if (i < n) v[i] = __float_as_uint(row[s + i]);
-    return v;
-}
-__device__ __forceinline__ u32x4 load_each(const int16_t *row, int64_t s, int n)
-{
-    u32x4 v = {0u, 0u, 0u, 0u};
-#pragma unroll
-    for (int i = 0; i < 8; i++)
-        if (i < n) v[i >> 1] |= (unsigned)(uint16_t)row[s + i] << (16 * (i & 1));
-    return v;
-}
-
-// the tree over a lane's group: (x0^2 + x1^2) + (x2^2 + x3^2), and for eight int16 one level more
-template <typename T>
-__device__ __forceinline__ float group_sum(u32x4 v)
-{
-    if constexpr (sizeof(T) == 4) {
-        const float a = __uint_as_float(v[0]), b = __uint_as_float(v[1]), c = __uint_as_float(v[2]), d = __uint_as_float(v[3]);
-        return (a * a + b * b) + (c * c + d * d);
-    } else {
-        float q[8];
-#pragma unroll
-        for (int i = 0; i < 8; i++) {
-            const float x = (float)(int16_t)(uint16_t)(v[i >> 1] >> (16 * (i & 1))) * (1.0f / 32768.0f);   // exact
-            q[i] = x * x;
-        }
-        return ((q[0] + q[1]) + (q[2] + q[3])) + ((q[4] + q[5]) + (q[6] + q[7]));
-    }
-}
 
 }  // namespace
 
@@ -108,22 +59,12 @@ levels_in_kernel(const T *__restrict__ samples, int64_t n_samples, int64_t strid
     const int lead = min(lpb, 64), lead_shift = __ffs(lead) - 1;
 #pragma unroll
     for (int j = 0; j < kLevelsPasses; j++) {
-        float p = group_sum<T>(raw[j]);
-        if (lpb > 1) p = xor_add<1>(p);
-        if (lpb > 2) p = xor_add<2>(p);
-        if (lpb > 4) p = xor_add<4>(p);
-        if (lpb > 8) p = xor_add<8>(p);
-        if (lpb > 16) p = xor_add<16>(p);
-        if (lpb > 32) p = xor_add<32>(p);
+        const float p = lanes_sum<T>(raw[j], lpb);
         if ((tid & (lead - 1)) == 0) sums[(j * 256 + tid) >> lead_shift] = p;
     }
     __syncthreads();
     // buffers longer than a wave's reach: r consecutive wave sums each, the tree's upper levels in LDS
-    const int r = L > kReach ? L / kReach : 1;
-    for (int d = 1; d < r; d <<= 1) {
-        if (tid < kSpan / kReach / (2 * d)) sums[2 * d * tid] += sums[2 * d * tid + d];
-        __syncthreads();
-    }
+    const int r = lds_tree<kSpan, kReach>(sums, L, tid);
     const int bpb = kSpan / L;
     const int64_t b0 = (int64_t)blockIdx.x * bpb, bE = min(b0 + bpb, B);
     // Double(sum) / Double(length): the row's last buffer divides by its own length
@@ -144,11 +85,7 @@ levels_in_kernel(const T *__restrict__ samples, int64_t n_samples, int64_t strid
         // short readings: a lane each
         for (int i = tid; i < nr; i += 256) {
             const int64_t m = m0 + i, lo = max(m * P, b0), hi = min((m + 1) * P, bE);
-            double best = -1.0;
-            for (int64_t b = lo; b < hi; b++) {
-                const double v = value(b);
-                if (v == v && v > best) best = v;
-            }
+            const double best = best_of_lane(lo, hi, value);
             emit(m, lo, best);
         }
     } else {
@@ -156,16 +93,7 @@ levels_in_kernel(const T *__restrict__ samples, int64_t n_samples, int64_t strid
         const int lane = tid & 63;
         for (int i = tid >> 6; i < nr; i += 4) {
             const int64_t m = m0 + i, lo = max(m * P, b0), hi = min((m + 1) * P, bE);
-            double best = -1.0;
-            for (int64_t b = lo + lane; b < hi; b += 64) {
-                const double v = value(b);
-                if (v == v && v > best) best = v;
-            }
-#pragma unroll
-            for (int d = 32; d >= 1; d >>= 1) {
-                const double o = __shfl_xor(best, d);
-                if (o > best) best = o;
-            }
+            const double best = best_of_wave(lo, hi, lane, value);
             if (lane == 0) emit(m, lo, best);
         }
     }
@@ -207,34 +135,10 @@ __global__ void __launch_bounds__(256)
 levels_out_kernel(const float *__restrict__ outputs, int64_t n_evals, int n_out, int k, int64_t n_samples, int64_t PL, int64_t need,
                   int64_t hop, int T, float *__restrict__ levels, int64_t M)
 {
-    const int c = blockIdx.y, lane = WAVE ? (int)(threadIdx.x & 63) : 0, step = WAVE ? 64 : 1;
+    const int c = blockIdx.y, lane = WAVE ? (int)(threadIdx.x & 63) : 0;
     const int64_t m = WAVE ? (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6) : (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (m >= M) return;
-    auto ce = [&](int64_t s) {
-        const int64_t J = s < need ? 0 : (s - need) / hop + 1;
-        return min(J >= T ? J - T + 1 : (int64_t)0, n_evals);
-    };
-    const int64_t e0 = ce(min(m * PL, n_samples)), e1 = ce(min((m + 1) * PL, n_samples));
-    const float *row = outputs + (int64_t)c * n_evals * n_out + k;
-    float result = 0.0f;
-    if (e0 < e1) {
-        const float first = row[e0 * n_out];
-        float best = 0.0f;
-        int64_t at = -1;                               // where `best` is from (-1: no value yet)
-        for (int64_t e = e0 + lane; e < e1; e += step) {
-            const float v = row[e * n_out];
-            if (v == v && (at < 0 || v > best)) { best = v; at = e; }
-        }
-        if (WAVE) {
-#pragma unroll
-            for (int d = 32; d >= 1; d >>= 1) {
-                const float ob = __shfl_xor(best, d);
-                const long long oa = __shfl_xor((long long)at, d);
-                if (oa >= 0 && (at < 0 || ob > best || (ob == best && oa < at))) { best = ob; at = oa; }
-            }
-        }
-        result = first != first ? first : best;
-    }
+    const float result = levels_out_value<WAVE>(outputs + (int64_t)c * n_evals * n_out + k, n_evals, n_out, m, n_samples, PL, need, hop, T, lane);
     if (lane == 0) levels[(int64_t)c * M + m] = result;
 }
 

@@ -1,7 +1,8 @@
 // syldet_recordings.cpp -- packed recordings (include/syldet.h, "packed recordings"): the plan that lays many recordings of
 // different lengths end to end in a bank's rows, and the handle that keeps the plan's tables on the device so that the
 // device calls (kernels_recordings.hip; kernels_recordings_sinc.hip for recordings at other rates) are launches only.  The handle
-// itself is in syldet_recordings.hpp; its per-sample tracks are in syldet_recordings_tracks.cpp.
+// itself is in syldet_recordings.hpp; its per-sample tracks are in syldet_recordings_tracks.cpp,
+// its level meters in syldet_recordings_levels.cpp.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -349,6 +350,8 @@ int syldet_recordings_create(const syldet_t *h, const int64_t *n_samples, const 
         r->track_step.reserve((size_t)r->K);
         r->track_host.assign((size_t)r->K, sd::RecTrackDev{});
         r->ls_host.assign((size_t)r->K + 1, 0);
+        // ... and the level meters'
+        r->levels_host.assign(2 * (size_t)r->K + 1, 0);
         for (int k = 0; k < r->K; k++) lengths.push_back(r->slots[(size_t)k].n_samples);
     } catch (const std::bad_alloc &) {
         return fail(SYLDET_ERR_OUT_OF_MEMORY, "out of memory");
@@ -356,8 +359,10 @@ int syldet_recordings_create(const syldet_t *h, const int64_t *n_samples, const 
     // ... and the tracks': destinations [K] | last_seen prefix [K + 1] | lengths [K]
     const size_t n_track = up16(r->table.size() * sizeof(sd::RecTrackDev)), n_ls = up16((r->table.size() + 1) * sizeof(int32_t)),
                  n_len = up16(r->table.size() * sizeof(int64_t));
+    // ... and the level meters': reading_first [K + 1] | slot_first [K]
+    const size_t n_levels = up16((2 * r->table.size() + 1) * sizeof(int64_t));
     SYLDET_HIP(hipSetDevice(b.device));
-    hipError_t e = hipMalloc(&r->d_blob, n_table + n_events + n_begin + n_tiles + n_sinc + n_track + n_ls + n_len + 16);
+    hipError_t e = hipMalloc(&r->d_blob, n_table + n_events + n_begin + n_tiles + n_sinc + n_track + n_ls + n_len + n_levels + 16);
     if (e != hipSuccess) {
         r->d_blob = nullptr;
         return fail(e == hipErrorOutOfMemory ? SYLDET_ERR_OUT_OF_MEMORY : SYLDET_ERR_DEVICE, std::string("hipMalloc: ") + hipGetErrorString(e));
@@ -378,6 +383,8 @@ int syldet_recordings_create(const syldet_t *h, const int64_t *n_samples, const 
     r->d_ls_begin = (int32_t *)(tracks + n_track);
     if (!lengths.empty()) SYLDET_HIP(hipMemcpy(tracks + n_track + n_ls, lengths.data(), lengths.size() * sizeof(int64_t), hipMemcpyHostToDevice));
     r->track = sd::RecTrackDesc{r->load, r->d_events, r->d_track, r->d_ls_begin, (const int64_t *)(tracks + n_track + n_ls), r->K, r->row_evals};
+    r->d_levels_first = (int64_t *)(tracks + n_track + n_ls + n_len);
+    r->levels = sd::RecLevelsDesc{r->load, r->d_events, r->track.n_samples, r->d_levels_first, r->d_levels_first + r->K + 1, r->K, r->row_evals, 0};
     *out = r.release();
     return SYLDET_OK;
 }

@@ -1,5 +1,6 @@
 // syldet_recordings.hpp -- the packed-recordings handle (struct syldet_recordings) for the host files that share it:
-// syldet_recordings.cpp (the plan, the loads, the events) and syldet_recordings_tracks.cpp (the per-sample tracks).  Not installed.
+// syldet_recordings.cpp (the plan, the loads, the events), syldet_recordings_tracks.cpp (the per-sample tracks) and
+// syldet_recordings_levels.cpp (the level meters).  Not installed.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -54,4 +55,11 @@ struct syldet_recordings {
     void *d_last_seen = nullptr;             // the scan's tables end to end: scratch the handle keeps and grows
     size_t last_seen_cap = 0;
     sd::RecTrackDesc track{};
+    // the level meters (syldet_recordings_levels.cpp): the kept (L, P) and its reading prefix, apart from the tracks' tables
+    int32_t levels_L = 0;                    // 0: none kept yet
+    int64_t levels_P = 0;
+    hipStream_t levels_last = nullptr;       // the stream of the last levels call
+    std::vector<int64_t> levels_host;        // reading_first [K + 1] | slot_first [K]: what one copy uploads
+    int64_t *d_levels_first = nullptr;       // (inside d_blob)
+    sd::RecLevelsDesc levels{};
 };

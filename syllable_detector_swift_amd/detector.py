@@ -816,7 +816,8 @@ class SyllableDetector:
         return Recordings(self, lengths, networks)
 
     def runRecordings(self, arrays, debounce: float = 0.0, networks=None, rates=None, resample=None, zeroCrossings=None, beta=None,
-                      rolloff=None, tracks=None, output: int = 0, bufferLength: int = 32, width: Optional[int] = None, latency: int = 0):
+                      rolloff=None, tracks=None, output: int = 0, bufferLength: int = 32, width: Optional[int] = None, latency: int = 0,
+                      levels=None):
         """Recordings of any lengths in one pass: one upload, load, run / runPCM16, events and one download.  `arrays`: 1-D
         (mono) or [frames, tracks] numpy arrays, all float32 or all int16 (16-bit PCM); every track is a recording, in order
         (`networks`, on a multi / mixed bank: one entry a track).  Returns, per recording, (indices int64 [n], values float32
@@ -829,7 +830,11 @@ class SyllableDetector:
         `tracks`: None, or names out of ("trace", "ttl"): the per-sample tracks of the same run (Recordings.trace of `output`,
         Recordings.triggerTrack with bufferLength, width, latency), as 16-bit PCM at the network's rate.  The call then returns
         (events, tracks): events what it returns without, tracks a dict of a list per name, one int16 array a recording in the
-        caller's order."""
+        caller's order.
+        `levels`: None, or (bufferLength, buffersPerReading) of the level meters (buffersPerReading None: the 0.1 s timer): the
+        two tables of the same run, from the very rows that were run (Recordings.levels, Recordings.outputLevels of `output`).
+        The call then returns one element more, behind the events (and the tracks, if any): a dict with "input", a list of one
+        float64 array of MEAN SQUARES a recording, and "output", one float32 array a recording."""
         torch = _torch()
         names = () if tracks is None else tuple(tracks)
         if any(t not in ("trace", "ttl") for t in names):
@@ -865,25 +870,41 @@ class SyllableDetector:
         n_out = self.geometry.outputs
         planned = lengths if rates is None else recordingLengths(lengths, track_rates, self.config.samplingRate)
         with self.recordings(planned, networks) as rec:
-            if rec.rowEvaluations <= 0:
-                none = [(np.zeros(0, np.int64), np.zeros((0, n_out), np.float32)) for _ in lengths]
-                return none if tracks is None else (none, {t: [np.zeros(n, np.int16) for n in planned] for t in names})
-            if rates is None:
-                rows = rec.load(torch.from_numpy(flat).to("cuda:%d" % self.device), offsets, steps)
-                out, fl = (self.runPCM16 if s16 else self.run)(rows)
-            else:
-                rows = rec.loadSinc(torch.from_numpy(flat).to("cuda:%d" % self.device), offsets, lengths, track_rates, steps, zeroCrossings, beta,
-                                    rolloff)
-                out, fl = self.run(rows)
-            idx, val, cnt = rec.events(out, fl, debounce)
-            made = {}
-            for t in names:
-                made[t] = rec.trace(out, output) if t == "trace" else rec.triggerTrack(fl, bufferLength, width, latency)
-            torch.cuda.current_stream(self.device).synchronize()
-            idx, val, cnt = idx.cpu().numpy(), val.cpu().numpy(), cnt.cpu().numpy()
-            made = {t: [rec.trackView(v, k).copy() for k in range(rec.count)] for t, v in ((t, v.cpu().numpy()) for t, v in made.items())}
-        events = [(idx[k, :cnt[k]].copy(), val[k, :cnt[k]].copy()) for k in range(len(lengths))]
-        return events if tracks is None else (events, made)
+            ran = rec.rowEvaluations > 0
+            if not ran:
+                events = [(np.zeros(0, np.int64), np.zeros((0, n_out), np.float32)) for _ in lengths]
+                made = {t: [np.zeros(n, np.int16) for n in planned] for t in names}
+            tables = None
+            if ran or (levels is not None and rec.rowSamples > 0):
+                if rates is None:
+                    rows = rec.load(torch.from_numpy(flat).to("cuda:%d" % self.device), offsets, steps)
+                else:
+                    rows = rec.loadSinc(torch.from_numpy(flat).to("cuda:%d" % self.device), offsets, lengths, track_rates, steps, zeroCrossings,
+                                        beta, rolloff)
+                if ran:
+                    out, fl = (self.runPCM16 if rows.dtype == torch.int16 else self.run)(rows)
+                    idx, val, cnt = rec.events(out, fl, debounce)
+                    made = {}
+                    for t in names:
+                        made[t] = rec.trace(out, output) if t == "trace" else rec.triggerTrack(fl, bufferLength, width, latency)
+                else:
+                    out = torch.zeros((self.channels, 0, n_out), dtype=torch.float32, device=rows.device)
+                if levels is not None:
+                    tables = (rec.levels(rows, levels[0], levels[1]), rec.outputLevels(out, output, levels[0], levels[1]))
+                torch.cuda.current_stream(self.device).synchronize()
+                if ran:
+                    idx, val, cnt = idx.cpu().numpy(), val.cpu().numpy(), cnt.cpu().numpy()
+                    made = {t: [rec.trackView(v, k).copy() for k in range(rec.count)] for t, v in ((t, v.cpu().numpy()) for t, v in made.items())}
+                    events = [(idx[k, :cnt[k]].copy(), val[k, :cnt[k]].copy()) for k in range(len(lengths))]
+            if levels is not None:
+                if tables is None:                            # (no recording has a sample)
+                    tables = (np.zeros(0, np.float64), np.zeros(0, np.float32))
+                else:
+                    tables = tuple(t.cpu().numpy() for t in tables)
+                first = rec.levelsLayout(levels[0], levels[1])
+                tables = {name: [t[first[k]:first[k + 1]].copy() for k in range(rec.count)] for name, t in zip(("input", "output"), tables)}
+        result = (events,) + (() if tracks is None else (made,)) + (() if levels is None else (tables,))
+        return result[0] if len(result) == 1 else result
 
     # ---- threshold calibration: score a run against labelled times -------------------------
     def scorer(self, thresholds, labels, tolerance: int, debounce: float = 0.0) -> "Scorer":
@@ -1220,6 +1241,80 @@ class Recordings:
         off = self.trackLayout(stp)[0] if offsets is None else np.ascontiguousarray(offsets, dtype=np.int64).reshape(-1)
         n, o, s = self.slots[k][4], int(off[k]), int(stp[k])
         return tensor[o:o + (n - 1) * s + 1:s] if n > 0 else tensor[o:o]
+
+    # ---- every recording's level meters (syldet_recordings_levels_device*, syldet_recordings_output_levels_device) ----
+    def _levels_pair(self, bufferLength, buffersPerReading):
+        L = int(bufferLength)
+        P = self.detector.defaultBuffersPerReading(L) if buffersPerReading is None else int(buffersPerReading)
+        if int(_abi.lib.syldet_levels_count(0, L, P)) < 0:
+            raise ValueError("bufferLength must be a power of two in [8, 4096] and buffersPerReading >= 1")
+        return L, P
+
+    def levelsLayout(self, bufferLength: int = 32, buffersPerReading: Optional[int] = None):
+        """Where every recording's readings lie in the flat tables of levels() and outputLevels() (the arithmetic of
+        syldet_recordings_levels_layout): an int64 array [K + 1], recording k's syldet_levels_count(n_k, L, P) readings are
+        elements [first[k], first[k + 1]), first[K] the readings in all.  buffersPerReading None: the 0.1 s timer
+        (SyllableDetector.defaultBuffersPerReading).  Host only."""
+        L, P = self._levels_pair(bufferLength, buffersPerReading)
+        kept = self.__dict__.setdefault("_levels_first", {})       # (a pair's prefix is made once: the calls below ask for it every time)
+        if (L, P) not in kept:
+            first = np.zeros(self.count + 1, np.int64)
+            for k, s in enumerate(self.slots):
+                first[k + 1] = first[k] + int(_abi.lib.syldet_levels_count(int(s[4]), L, P))
+            first.setflags(write=False)
+            kept[(L, P)] = first
+        return kept[(L, P)]
+
+    def _levels_out(self, dtype, total, out, device):
+        torch = _torch()
+        if out is None:
+            return torch.empty((total,), dtype=dtype, device=device)
+        if not (out.is_cuda and out.dtype == dtype and out.dim() == 1 and out.is_contiguous() and out.device == device):
+            raise ValueError("out must be a contiguous 1-D CUDA tensor of the table's dtype on the detector's device")
+        return out
+
+    def levels(self, rows, bufferLength: int = 32, buffersPerReading: Optional[int] = None, out=None, stream=None):
+        """Every recording's input meter (syldet_recordings_levels_device*): rows [C, >= rowSamples] float32 or int16 as load() /
+        loadSinc() wrote them -> the fp64 MEAN SQUARES of the readings, flat over the recordings as levelsLayout() lays them,
+        with the bits SyllableDetector.levels() / levelsPCM16() gives on each recording alone.  `out`: a float64 tensor of at
+        least that many elements to write into.  Asynchronous on `stream`; the same pair again is launches only."""
+        torch = _torch()
+        det = self.detector
+        if not (rows.is_cuda and rows.dtype in (torch.float32, torch.int16) and rows.dim() == 2 and rows.shape[0] == det.channels
+                and rows.shape[1] >= self.rowSamples and rows.stride(1) == 1 and rows.device.index == det.device):
+            raise ValueError("rows must be a float32 or int16 CUDA tensor [channels, >= rowSamples] on the detector's device, rows contiguous")
+        L, P = self._levels_pair(bufferLength, buffersPerReading)
+        total = int(self.levelsLayout(L, P)[-1])
+        out = self._levels_out(torch.float64, total, out, rows.device)
+        if total > 0:                                          # (a table too small is the library's refusal)
+            fn = _abi.lib.syldet_recordings_levels_device_s16 if rows.dtype == torch.int16 else _abi.lib.syldet_recordings_levels_device
+            stride = int(rows.stride(0)) if det.channels > 1 else int(rows.shape[1])
+            check(fn(self._h, rows.data_ptr(), stride, L, P, out.data_ptr() if out.numel() else None, int(out.numel()), det._stream_ptr(stream)))
+        return out
+
+    def outputLevels(self, outputs, output: int = 0, bufferLength: int = 32, buffersPerReading: Optional[int] = None, out=None, stream=None):
+        """Every recording's output meter (syldet_recordings_output_levels_device): outputs [C, rowEvaluations, n_out] as run()
+        wrote them for the loaded rows -> float32, flat as levelsLayout() lays them, with the values
+        SyllableDetector.outputLevels() gives on each recording's evaluations alone (0 for a reading without one)."""
+        torch = _torch()
+        det = self.detector
+        E, n_out = self.rowEvaluations, det.geometry.outputs
+        if not (outputs.is_cuda and outputs.dtype == torch.float32 and tuple(outputs.shape) == (det.channels, E, n_out)
+                and outputs.is_contiguous() and outputs.device.index == det.device):
+            raise ValueError("outputs must be a contiguous float32 CUDA tensor [channels, rowEvaluations, outputs] on the detector's device")
+        L, P = self._levels_pair(bufferLength, buffersPerReading)
+        total = int(self.levelsLayout(L, P)[-1])
+        out = self._levels_out(torch.float32, total, out, outputs.device)
+        if total > 0:                                          # (a table too small is the library's refusal)
+            check(_abi.lib.syldet_recordings_output_levels_device(self._h, outputs.data_ptr() if E > 0 else None, int(output), L, P,
+                                                                  out.data_ptr() if out.numel() else None, int(out.numel()),
+                                                                  det._stream_ptr(stream)))
+        return out
+
+    def levelsView(self, tensor, k: int, bufferLength: int = 32, buffersPerReading: Optional[int] = None):
+        """Recording k's readings of a table levels() or outputLevels() made with this pair (tensor or array): [M_k], no copy."""
+        first = self.levelsLayout(bufferLength, buffersPerReading)
+        return tensor[int(first[k]):int(first[k + 1])]
 
     def scorer(self, thresholds, labels, tolerance: int, debounce: float = 0.0) -> "Scorer":
         """A Scorer whose detectors are these recordings: labels[k], the labelled sample numbers of recording k, count from its
