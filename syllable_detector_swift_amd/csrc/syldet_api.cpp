@@ -489,18 +489,8 @@ bool normalised_chain(const syldet_config_t &c)
                                  c.input_fns[0].kind == SYLDET_FN_NORMALIZESTD);
 }
 
-int64_t count_frames(const syldet *h, int64_t S)
-{
-    const int64_t need = (int64_t)h->geom.gap + h->cfg.view.window_length;   // :286-288
-    if (S < need) return 0;
-    return (S - need) / h->geom.hop + 1;                                     // consume hop per frame :299-302
-}
-int64_t count_evals(const syldet *h, int64_t S)
-{
-    const int64_t J = count_frames(h, S);
-    const int T = h->cfg.view.time_range;
-    return J >= T ? J - T + 1 : 0;                                           // SyllableDetector.swift:164-178
-}
+int64_t count_frames(const syldet *h, int64_t S) { return count_frames(h->geom, h->cfg.view.window_length, S); }
+int64_t count_evals(const syldet *h, int64_t S) { return count_evals(h->geom, h->cfg.view.window_length, h->cfg.view.time_range, S); }
 
 // Would a handle of this one network, created under AUTO, run its batches on the fold kernel (syldet_create's rule plus the
 // launcher's choice, the SYLDET_* switches included)?  `fused_ok`: the fold kernel takes the shape at all (SYLDET_ENGINE_FUSED).

@@ -50,8 +50,25 @@ float sum_squares_tree(const float *x, int64_t n, int64_t step);
 float sum_squares_tree(const int16_t *x, int64_t n, int64_t step);
 // is L a buffer length the level meters take (a power of two in [8, 4096])?
 inline bool levels_buffer_ok(int64_t L) { return L >= 8 && L <= 4096 && (L & (L - 1)) == 0; }
+// ... and the refusal of one that is not, for every call that takes a buffer length (the meters, the trigger, the packed recordings' too)
+inline int buffer_length_arg(int64_t L)
+{
+    return levels_buffer_ok(L) ? SYLDET_OK : fail(SYLDET_ERR_INVALID_ARGUMENT, "buffer_length must be a power of two in [8, 4096]");
+}
 
-// What the host-side files that do not include syldet_handle.hpp need of a handle (syldet_recordings.cpp, syldet_score.cpp): channel_net is the caller's table of
+// syldet_count_frames and syldet_count_evals from the clock alone: a handle's, or a configuration's (syldet_recordings_plan_of_config)
+inline int64_t count_frames(const syldet_geometry_t &g, int window_length, int64_t S)
+{
+    const int64_t need = (int64_t)g.gap + window_length;    // :286-288
+    return S < need ? 0 : (S - need) / g.hop + 1;            // consume hop per frame :299-302
+}
+inline int64_t count_evals(const syldet_geometry_t &g, int window_length, int time_range, int64_t S)
+{
+    const int64_t J = count_frames(g, window_length, S);
+    return J >= time_range ? J - time_range + 1 : 0;         // SyllableDetector.swift:164-178
+}
+
+// What the packed recordings' plan and the scorer need of a bank -- a handle's, or (syldet_recordings_plan_of_config) a configuration's without one: channel_net is the caller's table of
 // syldet_create_multi / syldet_create_mixed ([channels], the handle's own memory), NULL on a plain bank.
 struct BankInfo {
     int channels, device;

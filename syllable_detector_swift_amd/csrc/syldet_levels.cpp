@@ -47,7 +47,7 @@ float sum_squares_tree(const int16_t *x, int64_t n, int64_t step) { return tree(
 
 static int levels_geometry_args(int32_t L, int64_t P)
 {
-    if (!levels_buffer_ok(L)) return fail(SYLDET_ERR_INVALID_ARGUMENT, "buffer_length must be a power of two in [8, 4096]");
+    if (int st = buffer_length_arg(L)) return st;
     if (P < 1) return fail(SYLDET_ERR_INVALID_ARGUMENT, "buffers_per_reading must be >= 1");
     return SYLDET_OK;
 }

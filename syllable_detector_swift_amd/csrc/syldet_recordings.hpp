@@ -3,63 +3,105 @@
 // syldet_recordings_levels.cpp (the level meters).  Not installed.
 #pragma once
 
-#include <hip/hip_runtime.h>
+#include "syldet_handle.hpp"
 
-#include <cstdint>
-#include <vector>
+namespace sd {
 
-#include "kernels.hpp"
-#include "syldet_internal.hpp"
+// A table on the device that stays valid while its key is unchanged.  The owner compares the key: a call with the kept key is
+// launches only, one with another key (the first always) re-makes the table; every call notes the stream that reads it.
+template <class T>
+struct KeptTable {
+    std::vector<T> host;             // what one copy uploads (sized by syldet_recordings_create: no call allocates)
+    T *dev = nullptr;                // (inside the handle's block)
+    bool kept = false;
+    hipStream_t last = nullptr;      // the stream of the last call that may still read dev
 
-struct syldet_recordings {
-    sd::BankInfo bank{};
-    int K = 0;
-    std::vector<syldet_slot_t> slots;        // [K] the caller's order
-    int64_t row_samples = 0, row_evals = 0;
-    double fill = 0.0;
-    // the load kernel's table: slots sorted by (row, offset); order[i] = the recording of table entry i
-    std::vector<sd::RecSlotDev> table;
-    std::vector<int32_t> order;
-    std::vector<int64_t> src_offset;         // [K] the sources the device table holds (empty: none yet)
-    std::vector<int32_t> src_step;
-    hipStream_t last_load = nullptr;
-    void *d_blob = nullptr;                  // table | events | row_begin | tile_first | the converting load's slots | its workgroup prefixes
-    sd::RecLoadDesc load{};
-    const sd::RecEventDev *d_events = nullptr;
-    // the converting load (syldet_recordings_load_sinc_device*): its own kept sources and tables, so that plain and converting
-    // loads may take turns on one handle
-    std::vector<int32_t> row_begin;          // [C + 1] the table's rows
-    bool sinc_kept = false;
-    hipStream_t sinc_last_load = nullptr;
-    std::vector<int64_t> sinc_offset, sinc_samples;   // [K]
-    std::vector<int32_t> sinc_step;
-    std::vector<double> sinc_rate;
-    int32_t sinc_Z = 0;
-    double sinc_beta = 0.0, sinc_rho = 0.0;
-    std::vector<char> sinc_host;             // slots [K] | prefixes [K + C]: what one copy uploads
-    size_t sinc_wg_at = 0;                   // where the prefixes begin in it (and behind d_sinc)
-    char *d_sinc = nullptr;                  // (inside d_blob)
-    sd::RecSincDesc sinc{};
-    // the per-sample tracks (syldet_recordings_tracks.cpp): the kept destination layout and the kept buffer length, apart from
-    // the loads' sources, so loads and track calls may take turns
-    syldet_t *h = nullptr;                   // the bank (it outlives this handle): its thresholds and its profile
-    bool track_kept = false;
-    hipStream_t track_last = nullptr;        // the stream of the last track call
-    std::vector<int64_t> track_offset;       // [K] the destinations the device table holds
-    std::vector<int32_t> track_step;
-    std::vector<sd::RecTrackDev> track_host; // [K] in the table's order: what one copy uploads
-    int32_t track_L = 0;                     // the buffer length ls_begin was made for (0: none yet)
-    std::vector<int32_t> ls_host;            // [K + 1]
-    sd::RecTrackDev *d_track = nullptr;      // (inside d_blob)
-    int32_t *d_ls_begin = nullptr;           // (inside d_blob)
-    void *d_last_seen = nullptr;             // the scan's tables end to end: scratch the handle keeps and grows
-    size_t last_seen_cap = 0;
-    sd::RecTrackDesc track{};
-    // the level meters (syldet_recordings_levels.cpp): the kept (L, P) and its reading prefix, apart from the tracks' tables
-    int32_t levels_L = 0;                    // 0: none kept yet
-    int64_t levels_P = 0;
-    hipStream_t levels_last = nullptr;       // the stream of the last levels call
-    std::vector<int64_t> levels_host;        // reading_first [K + 1] | slot_first [K]: what one copy uploads
-    int64_t *d_levels_first = nullptr;       // (inside d_blob)
-    sd::RecLevelsDesc levels{};
+    // Waits for the last reader, has fill() make `host` (its status ends the call), uploads once with a blocking copy -- the one
+    // copy include/syldet.h speaks of -- and is kept only once that succeeded.  also: wait although nothing is kept (the last
+    // call read a table beside this one).
+    template <class Fill>
+    int remake(Fill fill, bool also = false)
+    {
+        if (kept || also) SYLDET_HIP(hipStreamSynchronize(last));
+        kept = false;
+        if (int st = fill()) return st;
+        hipError_t e = hipMemcpy(dev, host.data(), host.size() * sizeof(T), hipMemcpyHostToDevice);
+        if (e != hipSuccess) return fail(SYLDET_ERR_DEVICE, std::string("hipMemcpy: ") + hipGetErrorString(e));
+        kept = true;
+        return SYLDET_OK;
+    }
+    void read_on(hipStream_t stream) { last = stream; }
 };
+
+}  // namespace sd
+
+// Each group: its key (where the table is not its own key), its kept table, its descriptor.
+struct syldet_recordings {
+    syldet_t *h = nullptr;                   // the bank (it outlives this handle): its thresholds and its profile
+    sd::BankInfo bank{};
+    sd::DeviceBuffer blob;                   // every table below in one block (recordings_blob.hpp)
+
+    struct Plan {                            // made by syldet_recordings_create, never changed
+        int K = 0;
+        std::vector<syldet_slot_t> slots;    // [K] the caller's order
+        int64_t row_samples = 0, row_evals = 0;
+        double fill = 0.0;
+        std::vector<int32_t> order;          // order[i] = the recording of table entry i (the slots sorted by (row, offset))
+        std::vector<int32_t> row_begin;      // [C + 1] the table's rows
+        const sd::RecEventDev *d_events = nullptr;
+    } plan;
+
+    // The plain load (syldet_recordings_load_device*).  Its table holds whole RecSlotDev entries, which the track and level kernels
+    // read as well (RecLoadDesc): re-making it under them is sound only because the fields they read, offset and n_samples, are
+    // rewritten with the values they hold already.
+    struct Load {
+        sd::KeptTable<sd::RecSlotDev> table; // [K] in `order`; on the device without sources from create on
+        sd::RecLoadDesc desc{};
+    } load;
+
+    // The converting load (syldet_recordings_load_sinc_device*): tables of its own, so that plain and converting loads may take
+    // turns on one handle.
+    struct Sinc {
+        int32_t Z = 0;
+        double beta = 0.0, rho = 0.0;
+        sd::KeptTable<char> table;           // RecSincDev [K] in `order` | workgroup prefixes [K + C]
+        size_t wg_at = 0;                    // where the prefixes begin in it
+        sd::RecSincDesc desc{};
+    } sinc;
+
+    // The per-sample tracks (syldet_recordings_tracks.cpp): tables apart from the loads', so loads and track calls may take turns.
+    // Both tables wait for the last track call, whichever of them it read.
+    struct Tracks {
+        sd::KeptTable<sd::RecTrackDev> layout;   // [K] in `order`: the destinations
+        int32_t L = 0;
+        sd::KeptTable<int32_t> ls_begin;     // [K + 1] the last_seen prefix of buffer length L
+        sd::DeviceBuffer last_seen;          // the scan's tables end to end: scratch the handle keeps and grows, outside the block
+        sd::RecTrackDesc desc{};
+        void read_on(hipStream_t stream) { layout.last = ls_begin.last = stream; }
+    } tracks;
+
+    // The level meters (syldet_recordings_levels.cpp): the reading prefix of (L, P), apart from the tracks' tables.
+    struct Levels {
+        int32_t L = 0;
+        int64_t P = 0;
+        sd::KeptTable<int64_t> first;        // reading_first [K + 1] | slot_first [K]
+        sd::RecLevelsDesc desc{};
+    } levels;
+};
+
+namespace sd {
+
+// The checks the calls on a handle share, with the texts tests and the tool match on.
+inline int stride_arg(const syldet_recordings *r, int64_t channel_stride)
+{
+    return channel_stride < r->plan.row_samples ? fail(SYLDET_ERR_INVALID_ARGUMENT, "channel_stride below row_samples") : SYLDET_OK;
+}
+inline int source_args(int K, const int64_t *src_offset, const int32_t *src_step)   // (NULL step: all 1)
+{
+    for (int k = 0; k < K; k++)
+        if (src_offset[k] < 0 || (src_step && src_step[k] < 1))
+            return fail(SYLDET_ERR_INVALID_ARGUMENT, "a negative source offset or a step below 1 (recording " + std::to_string(k) + ")");
+    return SYLDET_OK;
+}
+
+}  // namespace sd

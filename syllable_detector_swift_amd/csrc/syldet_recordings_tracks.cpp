@@ -2,7 +2,6 @@
 // recordings: the per-sample tracks"; kernels_recordings_tracks.hip).  The handle (syldet_recordings.hpp) keeps the destination
 // layout and the last_seen prefix on the device, beside the plan's tables, so that a call with the kept layout is launches only.
 
-#include "syldet_handle.hpp"
 #include "syldet_recordings.hpp"
 
 namespace {
@@ -11,9 +10,9 @@ namespace {
 int layout_args(const syldet_recordings_t *r, const void *d_dst, int64_t dst_elements, const int64_t *dst_offset, const int32_t *dst_step)
 {
     if (dst_elements < 0) return fail(SYLDET_ERR_INVALID_ARGUMENT, "dst_elements is negative");
-    if (r->K > 0 && !dst_offset) return fail(SYLDET_ERR_INVALID_ARGUMENT, "NULL argument");
-    for (int k = 0; k < r->K; k++) {
-        const int64_t step = dst_step ? dst_step[k] : 1, n = r->slots[(size_t)k].n_samples;
+    if (r->plan.K > 0 && !dst_offset) return fail(SYLDET_ERR_INVALID_ARGUMENT, "NULL argument");
+    for (int k = 0; k < r->plan.K; k++) {
+        const int64_t step = dst_step ? dst_step[k] : 1, n = r->plan.slots[(size_t)k].n_samples;
         if (dst_offset[k] < 0 || step < 1)
             return fail(SYLDET_ERR_INVALID_ARGUMENT, "a negative destination offset or a step below 1 (recording " + std::to_string(k) + ")");
         // offset + (n - 1) step < dst_elements, without overflow
@@ -28,90 +27,71 @@ int layout_args(const syldet_recordings_t *r, const void *d_dst, int64_t dst_ele
 
 int trigger_limits(int32_t L, int64_t N, int64_t latency)
 {
-    if (!levels_buffer_ok(L)) return fail(SYLDET_ERR_INVALID_ARGUMENT, "buffer_length must be a power of two in [8, 4096]");
+    if (int st = buffer_length_arg(L)) return st;
     if (N < 1 || N > ((int64_t)1 << 24)) return fail(SYLDET_ERR_INVALID_ARGUMENT, "width_samples must be in [1, 2^24]");
     if (latency < 0 || latency > ((int64_t)1 << 24)) return fail(SYLDET_ERR_INVALID_ARGUMENT, "latency_samples must be in [0, 2^24]");
     return SYLDET_OK;
 }
 
-// The kept destination layout: a layout that differs from it (the first always) waits for the stream of the last track call, which
-// may still read the table, and uploads once with a blocking copy.
+// The kept destination layout: a layout that differs from it (the first always) is uploaded behind the last track call.
 int keep_layout(syldet_recordings_t *r, const int64_t *dst_offset, const int32_t *dst_step)
 {
-    const int K = r->K;
-    bool same = r->track_kept;
-    for (int k = 0; k < K && same; k++)
-        same = r->track_offset[(size_t)k] == dst_offset[k] && r->track_step[(size_t)k] == (dst_step ? dst_step[k] : 1);
-    if (same || K == 0) return SYLDET_OK;
-    if (r->track_kept) SYLDET_HIP(hipStreamSynchronize(r->track_last));
-    r->track_kept = false;
-    r->track_offset.assign(dst_offset, dst_offset + K);      // (reserved by syldet_recordings_create: no allocation)
-    r->track_step.assign((size_t)K, 1);
-    if (dst_step) r->track_step.assign(dst_step, dst_step + K);
-    for (size_t i = 0; i < r->table.size(); i++) {
-        const int32_t k = r->order[i];
-        r->track_host[i] = sd::RecTrackDev{r->track_offset[(size_t)k], r->track_step[(size_t)k], k};
-    }
-    hipError_t e = hipMemcpy(r->d_track, r->track_host.data(), r->track_host.size() * sizeof(sd::RecTrackDev), hipMemcpyHostToDevice);
-    if (e != hipSuccess) return fail(SYLDET_ERR_DEVICE, std::string("hipMemcpy: ") + hipGetErrorString(e));
-    r->track_kept = true;
-    return SYLDET_OK;
+    // the key is the table itself: entry i holds the destination of recording order[i]
+    KeptTable<RecTrackDev> &t = r->tracks.layout;
+    const std::vector<int32_t> &order = r->plan.order;
+    auto entry = [&](size_t i) { return RecTrackDev{dst_offset[order[i]], dst_step ? dst_step[order[i]] : 1, order[i]}; };
+    bool same = t.kept;
+    for (size_t i = 0; i < order.size() && same; i++) same = t.host[i].dst_offset == entry(i).dst_offset && t.host[i].dst_step == entry(i).dst_step;
+    if (same || order.empty()) return SYLDET_OK;
+    return t.remake([&]() -> int {
+        for (size_t i = 0; i < order.size(); i++) t.host[i] = entry(i);
+        return SYLDET_OK;
+    });
 }
 
 // The kept buffer length: recording k's last_seen table has B'_k = trigger_buffers(n_k, L) entries, the tables lie end to end, and
-// the prefix of K + 1 entries is uploaded when L changes; the tables themselves are scratch the handle keeps and grows.
+// the prefix of K + 1 entries is uploaded when L changes -- behind the last track call, one that read the layout alone too; the
+// tables themselves are scratch the handle keeps and grows.
 int keep_buffers(syldet_recordings_t *r, int32_t L)
 {
-    const int K = r->K;
-    if (r->track_L == L || K == 0) return SYLDET_OK;
+    syldet_recordings::Tracks &t = r->tracks;
+    const std::vector<syldet_slot_t> &slots = r->plan.slots;
+    const size_t K = slots.size();
+    if ((t.ls_begin.kept && t.L == L) || K == 0) return SYLDET_OK;
     int64_t total = 0;
-    for (int k = 0; k < K; k++) {
-        const int64_t Bp = trigger_buffers(r->slots[(size_t)k].n_samples, L);
+    for (size_t k = 0; k < K; k++) {
+        const int64_t Bp = trigger_buffers(slots[k].n_samples, L);
         if (Bp < 0 || total + Bp > 0x7fffffffLL) return fail(SYLDET_ERR_UNSUPPORTED, "more than 2^31 buffers in all recordings");
         total += Bp;
     }
-    if (r->track_L != 0 || r->track_kept) SYLDET_HIP(hipStreamSynchronize(r->track_last));
-    r->track_L = 0;
-    total = 0;
-    for (int k = 0; k < K; k++) {
-        r->ls_host[(size_t)k] = (int32_t)total;
-        total += trigger_buffers(r->slots[(size_t)k].n_samples, L);
-    }
-    r->ls_host[(size_t)K] = (int32_t)total;
-    const size_t bytes = (size_t)total * sizeof(int);
-    if (bytes > r->last_seen_cap) {
-        if (r->d_last_seen) (void)hipFree(r->d_last_seen);
-        r->d_last_seen = nullptr;
-        r->last_seen_cap = 0;
-        hipError_t e = hipMalloc(&r->d_last_seen, bytes);
-        if (e != hipSuccess) {
-            r->d_last_seen = nullptr;
-            return fail(e == hipErrorOutOfMemory ? SYLDET_ERR_OUT_OF_MEMORY : SYLDET_ERR_DEVICE, std::string("hipMalloc: ") + hipGetErrorString(e));
+    return t.ls_begin.remake([&]() -> int {
+        t.L = L;
+        int32_t at = 0;
+        for (size_t k = 0; k < K; k++) {
+            t.ls_begin.host[k] = at;
+            at += (int32_t)trigger_buffers(slots[k].n_samples, L);
         }
-        r->last_seen_cap = bytes;
-    }
-    hipError_t e = hipMemcpy(r->d_ls_begin, r->ls_host.data(), r->ls_host.size() * sizeof(int32_t), hipMemcpyHostToDevice);
-    if (e != hipSuccess) return fail(SYLDET_ERR_DEVICE, std::string("hipMemcpy: ") + hipGetErrorString(e));
-    r->track_L = L;
-    return SYLDET_OK;
+        t.ls_begin.host[K] = at;
+        return t.last_seen.reserve((size_t)at * sizeof(int));
+    }, t.layout.kept);
 }
 
 int trace_impl(syldet_recordings_t *r, const float *d_outputs, int32_t output, void *d_dst, bool s16, int64_t dst_elements,
                const int64_t *dst_offset, const int32_t *dst_step, hipStream_t stream)
 {
-    if (!r || (r->K > 0 && r->row_evals > 0 && !d_outputs)) return fail(SYLDET_ERR_INVALID_ARGUMENT, "NULL argument");
+    if (!r || (r->plan.K > 0 && r->plan.row_evals > 0 && !d_outputs)) return fail(SYLDET_ERR_INVALID_ARGUMENT, "NULL argument");
     if (output < 0 || output >= r->bank.geom.outputs) return fail(SYLDET_ERR_INVALID_ARGUMENT, "output outside [0, outputs)");
     if (int st = layout_args(r, d_dst, dst_elements, dst_offset, dst_step)) return st;
-    if (r->K == 0 || r->row_samples == 0) return SYLDET_OK;
+    if (r->plan.K == 0 || r->plan.row_samples == 0) return SYLDET_OK;
     syldet *h = r->h;
     SYLDET_HIP(hipSetDevice(r->bank.device));
     if (int st = keep_layout(r, dst_offset, dst_step)) return st;
     const float *thr = nullptr;
     if (int st = trace_thresholds(h, output, &thr)) return st;
-    r->track_last = stream;
+    r->tracks.read_on(stream);
     h->prof_begin();
     KernelTimer t(h, stream, "recordings_trace_kernel");
-    SYLDET_HIP(launch_recordings_trace(r->track, r->bank.channels, d_outputs, r->bank.geom.outputs, output, thr, d_dst, s16, r->bank.geom.first_index,
+    SYLDET_HIP(launch_recordings_trace(r->tracks.desc, r->bank.channels, d_outputs, r->bank.geom.outputs, output, thr, d_dst, s16, r->bank.geom.first_index,
                                        r->bank.geom.hop, stream));
     return SYLDET_OK;
 }
@@ -121,25 +101,25 @@ int trigger_begin(syldet_recordings_t *r, const uint8_t *d_flags, int32_t L, hip
 {
     SYLDET_HIP(hipSetDevice(r->bank.device));
     if (int st = keep_buffers(r, L)) return st;
-    r->track_last = stream;
+    r->tracks.read_on(stream);
     r->h->prof_begin();
     KernelTimer t(r->h, stream, "recordings_trigger_scan_kernel");
-    SYLDET_HIP(launch_recordings_trigger_scan(r->track, d_flags, L, r->bank.geom.first_index, r->bank.geom.hop, (int *)r->d_last_seen, stream));
+    SYLDET_HIP(launch_recordings_trigger_scan(r->tracks.desc, d_flags, L, r->bank.geom.first_index, r->bank.geom.hop, (int *)r->tracks.last_seen.ptr, stream));
     return SYLDET_OK;
 }
 
 int trigger_impl(syldet_recordings_t *r, const uint8_t *d_flags, int32_t L, int64_t N, int64_t latency, void *d_dst, bool s16, int64_t dst_elements,
                  const int64_t *dst_offset, const int32_t *dst_step, hipStream_t stream)
 {
-    if (!r || (r->K > 0 && r->row_evals > 0 && !d_flags)) return fail(SYLDET_ERR_INVALID_ARGUMENT, "NULL argument");
+    if (!r || (r->plan.K > 0 && r->plan.row_evals > 0 && !d_flags)) return fail(SYLDET_ERR_INVALID_ARGUMENT, "NULL argument");
     if (int st = trigger_limits(L, N, latency)) return st;
     if (int st = layout_args(r, d_dst, dst_elements, dst_offset, dst_step)) return st;
-    if (r->K == 0 || r->row_samples == 0) return SYLDET_OK;
+    if (r->plan.K == 0 || r->plan.row_samples == 0) return SYLDET_OK;
     SYLDET_HIP(hipSetDevice(r->bank.device));
     if (int st = keep_layout(r, dst_offset, dst_step)) return st;
     if (int st = trigger_begin(r, d_flags, L, stream)) return st;
     KernelTimer t(r->h, stream, "recordings_trigger_kernel");
-    SYLDET_HIP(launch_recordings_trigger(r->track, r->bank.channels, (const int *)r->d_last_seen, L, N, latency, d_dst, s16, stream));
+    SYLDET_HIP(launch_recordings_trigger(r->tracks.desc, r->bank.channels, (const int *)r->tracks.last_seen.ptr, L, N, latency, d_dst, s16, stream));
     return SYLDET_OK;
 }
 
@@ -178,14 +158,15 @@ int syldet_recordings_trigger_device_s16(syldet_recordings_t *r, const uint8_t *
 int syldet_recordings_trigger_onsets_device(syldet_recordings_t *r, const uint8_t *d_flags, int32_t buffer_length, int64_t width_samples,
                                             int64_t latency_samples, int64_t *d_indices, int64_t capacity, int64_t *d_counts, void *hip_stream)
 {
-    if (!r || (r->K > 0 && r->row_evals > 0 && !d_flags) || (r->K > 0 && !d_counts) || capacity < 0 || (r->K > 0 && capacity > 0 && !d_indices))
+    if (!r || (r->plan.K > 0 && r->plan.row_evals > 0 && !d_flags) || (r->plan.K > 0 && !d_counts) || capacity < 0 ||
+        (r->plan.K > 0 && capacity > 0 && !d_indices))
         return fail(SYLDET_ERR_INVALID_ARGUMENT, "bad argument");
     if (int st = trigger_limits(buffer_length, width_samples, latency_samples)) return st;
-    if (r->K == 0) return SYLDET_OK;
+    if (r->plan.K == 0) return SYLDET_OK;
     hipStream_t stream = (hipStream_t)hip_stream;
     if (int st = trigger_begin(r, d_flags, buffer_length, stream)) return st;
     KernelTimer t(r->h, stream, "recordings_trigger_onsets_kernel");
-    SYLDET_HIP(launch_recordings_trigger_onsets(r->track, (const int *)r->d_last_seen, buffer_length, width_samples, latency_samples, d_indices,
+    SYLDET_HIP(launch_recordings_trigger_onsets(r->tracks.desc, (const int *)r->tracks.last_seen.ptr, buffer_length, width_samples, latency_samples, d_indices,
                                                 capacity, d_counts, stream));
     return SYLDET_OK;
 }

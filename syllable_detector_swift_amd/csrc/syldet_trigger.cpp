@@ -7,7 +7,7 @@ static int trigger_args(const syldet *h, const void *flags, int64_t n_evals, int
 {
     if (!h || !flags) return fail(SYLDET_ERR_INVALID_ARGUMENT, "NULL argument");
     if (n_evals < 0 || n_samples < 0) return fail(SYLDET_ERR_INVALID_ARGUMENT, "negative size");
-    if (!levels_buffer_ok(L)) return fail(SYLDET_ERR_INVALID_ARGUMENT, "buffer_length must be a power of two in [8, 4096]");
+    if (int st = buffer_length_arg(L)) return st;
     if (N < 1 || N > ((int64_t)1 << 24)) return fail(SYLDET_ERR_INVALID_ARGUMENT, "width_samples must be in [1, 2^24]");
     if (latency < 0 || latency > ((int64_t)1 << 24)) return fail(SYLDET_ERR_INVALID_ARGUMENT, "latency_samples must be in [0, 2^24]");
     if (trigger_buffers(n_samples, L) < 0) return fail(SYLDET_ERR_INVALID_ARGUMENT, "n_samples: more than 2^31 buffers");

@@ -140,6 +140,18 @@ def test_a_sharded_bank_has_no_packed_form():
     assert ei.value.status == _abi.ERR_UNSUPPORTED
 
 
+def test_the_handles_block_layout_under_asan_and_ubsan(tmp_path):
+    exe = tmp_path / "recordings_blob"
+    subprocess.run(["g++", "-std=c++17", "-O1", "-g", "-Wall", "-Werror", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined",
+                    "-I" + os.path.join(ROOT, "syllable_detector_swift_amd", "csrc"), os.path.join(ROOT, "tests", "cpp", "recordings_blob_test.cpp"),
+                    "-o", str(exe)], check=True)
+    r = subprocess.run([str(exe)], capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0 and r.stdout.strip() == "ok" and not r.stderr, (r.returncode, r.stdout, r.stderr)
+    # the handle's block is that header's
+    text = open(os.path.join(ROOT, "syllable_detector_swift_amd", "csrc", "syldet_recordings.cpp")).read()
+    assert "RecBlob " in text and "up16(" not in text
+
+
 @pytest.mark.parametrize("extra,needle", [
     (["--simulate", "x.wav"], b"--batch"), (["--levels", "x.tsv"], b"--batch"), (["--ttl", "x.wav"], b"--batch"),
     (["--ttl-onsets", "x.tsv"], b"--batch")])
