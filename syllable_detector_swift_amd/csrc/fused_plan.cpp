@@ -17,6 +17,7 @@
 #include <cstdlib>
 #include <cstring>
 
+#include "exact_reciprocal.hpp"
 #include "fused_plan.hpp"
 #include "hopk_schedule.hpp"
 
@@ -513,6 +514,13 @@ bool make_fused_plan(const syldet_config_t &c, const syldet_geometry_t &g, Fused
         p.out_params.push_back(f.y);
         p.out_params.insert(p.out_params.end(), f.gains, f.gains + n_out);
         p.out_params.insert(p.out_params.end(), f.x_offsets, f.x_offsets + n_out);
+    }
+    // ... and behind a lone output map, for the fold kernel (the other kernels read n_out_fns maps and stop): its gains as
+    // reciprocals where those are exact (exact_reciprocal.hpp), else 0.  The lean form's launcher multiplies where output 0's is.
+    d.s_out_rcp = 0;
+    if (c.n_output_fns == 1) {
+        for (int o = 0; o < n_out; o++) p.out_params.push_back(exact_reciprocal_f32(c.output_fns[0].gains[o]));
+        d.s_out_rcp = (n_out == 1 && p.out_params.back() != 0.0f) ? 1 : 0;
     }
     // ---- precision guard (kernels.hpp, FixItem).  Sensitivity of an output to the network's input vector u, as a bound:
     // |dz_h| <= ||W'_h||_2 ||du||_2 (W' = W0 o a, the folded first layer in true units), transfer slopes <= 1 (LogSig 1/4),

@@ -204,7 +204,8 @@ struct FusedDesc {
     const float *bias0;         // [H]  b0 + W0 . (constant part of the input maps)
     const float *rvec;          // [H]  (W0 o a) . 1
     const float *w1, *b1;       // layer 1, row-major [n_out][H] (2-layer nets)
-    const float *out_params;    // per output fn: y, gain[n_out], xoff[n_out]
+    const float *out_params;    // per output fn: y, gain[n_out], xoff[n_out]; behind a lone output fn, for the fold kernel: rcp[n_out], 1 / gain
+                                // where that is exact, else 0 (fused_plan.cpp, exact_reciprocal.hpp)
     const double *thresholds;   // [n_out]
     float *spect_out;           // spectrogram instantiation only: [C][J][F] columns
     int spect_power;            //   0: |X|, 1: |X|^2
@@ -227,9 +228,12 @@ struct FusedDesc {
     short s_hopk_rc;            // hop 132 under a 256-sample window, one quad of units, the plain ring: the slots of the ring whose schedule is compiled in
                                 // (kernels_fused_s.hip, HOP; hopk_schedule.hpp), or 0 -- the shape has no such form, or the handle was created under
                                 // SYLDET_FUSED_HOPK=0 (A/B runs).  The launcher's alone; it sits in the padding in front of `stamps`: the kernels' arguments stay where they were.
-    short s_pairstep;           // the HOP form keeps the two waves of a SIMD in step (pair_progress.hpp): 1, or 0 -- the handle was created under
+    signed char s_pairstep;     // the HOP form keeps the two waves of a SIMD in step (pair_progress.hpp): 1, or 0 -- the handle was created under
                                 // SYLDET_FUSED_PAIRSTEP=0 (A/B runs).  Read by the HOP instantiations alone.  It shares s_hopk_rc's word (there is no
                                 // padding left in front of `stamps`), so the kernels' arguments stay where they were.
+    signed char s_out_rcp;      // the lean form's output gain is a power of two whose reciprocal is exact (exact_reciprocal.hpp): 1, and out_params
+                                // holds 1 / gain behind the output map; else 0. The launcher's alone (it picks the HOP instantiation that
+                                // multiplies instead of dividing: the same bits); the upper byte of what was s_pairstep's short.
     unsigned long long *stamps; // diagnostic build only: [workgroups][16] phase cycle sums (the fold kernel: 16 sums, then a record a wave), else null
 };
 // What the fold kernel reads of ONE network, for multi-network handles (syldet_create_multi): everything else of FusedDesc is

@@ -185,7 +185,12 @@ constexpr bool kPairEvery = true;
 #else
 constexpr bool kPairEvery = false;
 #endif
-template <int K2, bool GEN, int HQ, int NW, int PADP = 0, bool F2 = false, int NT = 1, bool SPECT = false, bool MN = false, bool S16 = false, int HOP = 0>
+// RCP: the lean output map (y - oa) / og + ob with og a power of two multiplies by 1 / og, which is exact: one multiplication where
+// the division is ten instructions, and the same correctly rounded result (exact_reciprocal.hpp;
+// FusedDesc::s_out_rcp).  One more instantiation: the example class on one network at the compile-time hop, where the launcher
+// picks it; every other form divides.
+template <int K2, bool GEN, int HQ, int NW, int PADP = 0, bool F2 = false, int NT = 1, bool SPECT = false, bool MN = false, bool S16 = false, int HOP = 0,
+          bool RCP = false>
 __global__ void __launch_bounds__(64 * NW, 1)
 fused_s_kernel(const FusedDesc d, const float *__restrict__ samples, int64_t stride, int64_t s_eff, int64_t E,
                float *__restrict__ outputs, uint8_t *__restrict__ flags, const FusedNet *__restrict__ nets, const int *__restrict__ net_of,
@@ -195,6 +200,7 @@ fused_s_kernel(const FusedDesc d, const float *__restrict__ samples, int64_t str
     static_assert(!S16 || (K2 == 4 && F2 && PADP == 0 && NT == 1 && HQ == 1 && NW == 8 && !SPECT), "16-bit PCM: the twice-folded form on the plain ring");
     static_assert(HOP == 0 || (HOP == hopk::kHop && K2 == 4 && F2 && PADP == 0 && NT == 1 && HQ == 1 && NW == 8 && !SPECT && !S16 && kFusedSTileFrames == hopk::kTileFrames),
                   "a compile-time hop: 132, the twice-folded form on the plain fp32 ring, one quad of units on eight waves");
+    static_assert(!RCP || (HOP != 0 && !GEN && !MN), "the exact reciprocal: the example class on one network at the compile-time hop");
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const int tid = threadIdx.x;
     const int lane = tid & 63;
@@ -248,6 +254,13 @@ fused_s_kernel(const FusedDesc d, const float *__restrict__ samples, int64_t str
     // loop's working set only if the constants that depend on the lane group alone wait in LDS (4 groups x 20 floats behind the
     // zero quad) and are fetched where they are used -- otherwise 28 registers go to scratch.
     constexpr bool kTbl = HQ == 2 && NW == 8;
+    // The evaluation reads a row's statistics as the pair {st0, fw} where the form uses no more (the example class; with GEN the
+    // normaliser is a run-time fact and st1 is read): a compile-time choice, the rows' layout is the same.
+#ifdef SYLDET_S_STAT_QUADS             // (diagnostic build: tools/variant_libs.sh kernels_fused_s.hip statquads -DSYLDET_S_STAT_QUADS)
+    constexpr bool kStatPairs = false;
+#else
+    constexpr bool kStatPairs = !GEN;
+#endif
     float *gtab = zquad + 8 * HQ + 32 * g;
     {
         const int nz = ((T - 1 + kTile) * PS + 8 * HQ + 128) / 4;          // (+ the table of lane-group constants, where there is one)
@@ -390,6 +403,7 @@ fused_s_kernel(const FusedDesc d, const float *__restrict__ samples, int64_t str
     if (d.n_out_fns == 1) {
         const int o = (GEN && g < n_out) ? g : 0;
         lean_oa = SD_NET(out_params)[0]; lean_og = SD_NET(out_params)[1 + o]; lean_ob = SD_NET(out_params)[1 + n_out + o];
+        if constexpr (RCP) lean_og = SD_NET(out_params)[1 + 2 * n_out + o];      // (1 / gain, exact: the launcher saw s_out_rcp)
     }
     // this lane group's hidden units: 4 q + g
     float b0g[HQ], w1g[HQ], w1o[4][HQ], rvg[HQ];      // (rvg: (W0 o a) . 1, what the normalisers' offset meets)
@@ -919,8 +933,18 @@ fused_s_kernel(const FusedDesc d, const float *__restrict__ samples, int64_t str
             for (int tt = 0; tt < 3; tt++)
 #pragma unroll
                 for (int q = 0; q < HQ; q++) pv[tt][q] = *reinterpret_cast<const floatx4 *>(pv_p[tt] + 4 * q);
-            const floatx4 s0 = *reinterpret_cast<const floatx4 *>(sv_p[0]), s1 = *reinterpret_cast<const floatx4 *>(sv_p[1]),
-                          s2 = *reinterpret_cast<const floatx4 *>(sv_p[2]);
+            // The statistics quads {st0, fw, st1, 0} at the width the form uses.  Without GEN only st0 and fw are read: as quads the
+            // three destinations overlap where registers are short (the dead halves may share), and each read then waits for the one
+            // before it -- two LDS round trips in series in the tile's dependent chain.  As pairs every word is live: three reads, one wait.
+            floatx4 s0, s1, s2;
+            if constexpr (kStatPairs) {
+                const floatx2 a0 = *reinterpret_cast<const floatx2 *>(sv_p[0]), a1 = *reinterpret_cast<const floatx2 *>(sv_p[1]),
+                              a2 = *reinterpret_cast<const floatx2 *>(sv_p[2]);
+                s0 = floatx4{a0[0], a0[1], 0.0f, 0.0f}; s1 = floatx4{a1[0], a1[1], 0.0f, 0.0f}; s2 = floatx4{a2[0], a2[1], 0.0f, 0.0f};
+            } else {
+                s0 = *reinterpret_cast<const floatx4 *>(sv_p[0]); s1 = *reinterpret_cast<const floatx4 *>(sv_p[1]);
+                s2 = *reinterpret_cast<const floatx4 *>(sv_p[2]);
+            }
             sq0[0] = s0[0]; sq0[1] = s1[0]; sq0[2] = s2[0];
 #pragma unroll
             for (int q = 0; q < HQ; q++) zp[q] = pv[0][q] + pv[1][q] + pv[2][q];
@@ -1054,7 +1078,18 @@ fused_s_kernel(const FusedDesc d, const float *__restrict__ samples, int64_t str
                 othr = *reinterpret_cast<const double *>(tp + 4);
             }
             float y = transfer_fn(tf1, ysum + ob1);
-            y = (y - ooa) / oog + oob;
+            if constexpr (RCP) {
+                // oog is 1 / gain, a power of two: the product is the correctly rounded quotient, as the division's result is --
+                // rounded on its own (no multiply-add: where the product leaves the normal range the two would differ)
+                const float ym = y - ooa;
+                {
+#pragma clang fp contract(off)
+                    const float yq = ym * oog;
+                    y = yq + oob;
+                }
+            } else {
+                y = (y - ooa) / oog + oob;
+            }
             yv = y;
             hit = counts && (double)y >= othr;
             if (multi) {
@@ -1164,6 +1199,11 @@ hipError_t launch_one(const FusedDesc &d, const float *samples, int64_t stride, 
             static_assert(HQ == 1 && NW == pairp::kWaves && pairp::table_end(1, 0) == (hopk::kRing + 1) * 1024 + (8 * HQ + 128) * 4, "pair_progress.hpp describes this layout");
             if (d.s_pairstep != 0 && !pairp::fits(d.T, d.s_pstride, d.s_lds_wave)) return hipErrorInvalidValue;
             kern = fused_s_kernel<K2, GEN, HQ, NW, PADP, F2, NT, SPECT, MN, S16, hopk::kHop>;
+#ifndef SYLDET_S_NO_RCP                // (diagnostic build: tools/variant_libs.sh kernels_fused_s.hip norcp -DSYLDET_S_NO_RCP -- the division)
+            // ... and where the plan found the output gain's reciprocal exact, the instantiation that multiplies by it (RCP)
+            if constexpr (!GEN && !MN)
+                if (d.s_out_rcp != 0 && d.n_out_fns == 1) kern = fused_s_kernel<K2, GEN, HQ, NW, PADP, F2, NT, SPECT, MN, S16, hopk::kHop, true>;
+#endif
         }
     }
     constexpr int kWaves = NW;
