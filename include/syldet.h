@@ -915,6 +915,63 @@ int syldet_recordings_load_sinc_device_s16(syldet_recordings_t *r, const int16_t
                                            const int64_t *src_samples, const double *src_rate, int32_t zero_crossings, double beta,
                                            double rolloff, float *d_rows, int64_t channel_stride, void *hip_stream);
 
+/* ---- packed recordings: the files' own sample formats ----
+ * The reference asks AVFoundation for 32-bit float linear PCM whatever a file holds (audioSettings, Common/SyllableDetector.swift:19-23);
+ * the calls below stand in for that delivery: the source of a load is the files' own bytes, and every recording of a plan is
+ * decoded from its own little-endian format, de-interleaved and placed in the fp32 rows in ONE launch -- a batch of 16- and 24-bit
+ * files is uploaded as it is stored, not widened on the host and uploaded as fp32.
+ * THE CONVENTION (csrc/pcm_values.hpp: one text for the host, the kernels and a stand-alone test):
+ *   SYLDET_PCM_U8   1 byte   (float)(b - 128) * 2^-7
+ *   SYLDET_PCM_S16  2 bytes  (float)v * 2^-15
+ *   SYLDET_PCM_S24  3 bytes  (float)v * 2^-23      (v sign-extended from bit 23; exact in fp32)
+ *   SYLDET_PCM_S32  4 bytes  (float)v * 2^-31      (= (float)((double)v / 2^31): a power-of-two scale commutes with the rounding)
+ *   SYLDET_PCM_F32  4 bytes  the bits, copied (NaN payloads included)
+ *   SYLDET_PCM_F64  8 bytes  (float)d, round to nearest even, fp32 subnormal results kept
+ * -- the values the tool's WAV reader gives for the same bytes.  Little endian only.
+ *   syldet_pcm_sample_bytes   the bytes of one sample; 0 for an unknown format
+ *   syldet_pcm_decode         out[i] = the `format` value at bytes + i byte_step for i < n (byte_step >= the sample's bytes; any
+ *       address: the host reads byte-wise).  SYLDET_ERR_INVALID_ARGUMENT for an unknown format, n < 0, a NULL array with n > 0, a
+ *       step below the sample's bytes.  Host only.
+ * THE DEVICE CALLS.  Sample i of recording k is the src_format[k] value at byte d_src + src_byte_offset[k] + i src_byte_step[k]; a
+ * step of tracks * sample_bytes takes one track of an interleaved file as its `data` chunk stores it (src_byte_step NULL: every
+ * recording contiguous).  d_src holds src_bytes bytes.
+ *   syldet_recordings_load_pcm_device        every element [0, row_samples) of every row holds, bit for bit, what
+ *       syldet_recordings_load_device writes from the fp32 array syldet_pcm_decode makes of the same bytes -- +0 in the pads and in
+ *       empty rows included; [row_samples, channel_stride) is left untouched.  ("recordings_load_pcm_kernel": the grid and tile
+ *       walk of recordings_load_kernel; a contiguous recording is read 8 (S16), 12 (S24), 16 (S32, F32), 32 (F64) or 4 (U8) bytes
+ *       for four samples as its address allows, everything else sample by sample)
+ *   syldet_recordings_load_sinc_pcm_device   the bits of syldet_recordings_load_sinc_device on those decoded fp32 arrays: the same
+ *       table, the same fp64 positions, the same taps; a recording at the network's rate is decoded and copied
+ * Reads: no byte outside the bytes of the recordings' own samples is read, and no access of several bytes is off a multiple of
+ * its size (a group of four contiguous S24 samples: exactly its 12 bytes, from a multiple of 4).
+ * Statuses, decided before any device is touched, in this order: the argument checks of syldet_recordings_load_device (offsets >= 0,
+ * steps >= 1, ...); then SYLDET_ERR_INVALID_ARGUMENT, syldet_last_error naming the recording, for an unknown format, a
+ * src_byte_step[k] below the sample's bytes, an address d_src + src_byte_offset[k] or a step that is no multiple of the sample's
+ * size for S16, S32, F32 or F64 (U8 and S24 take any), a recording whose last sample byte lies at or beyond src_bytes (the plan's
+ * n_samples of them; for the converting form src_samples[k]); then, for the converting form, the statuses of
+ * syldet_recordings_load_sinc_device in its order.  syldet_pcm_check_sources makes the checks of this paragraph from the host alone
+ * (n_samples: the samples read of each recording; src: the address d_src will have, never read).
+ * The launch rule is the existing one: the handle keeps the sources, with the formats and the unit (bytes or elements) part of the
+ * comparison, in the tables of the plain and of the converting load; the same layout again is one launch without allocation,
+ * synchronisation or copy, and these calls and the four above may take turns on one handle, each writing its own bits.          */
+#define SYLDET_PCM_U8  1
+#define SYLDET_PCM_S16 2
+#define SYLDET_PCM_S24 3
+#define SYLDET_PCM_S32 4
+#define SYLDET_PCM_F32 5
+#define SYLDET_PCM_F64 6
+int32_t syldet_pcm_sample_bytes(int32_t format);
+int syldet_pcm_decode(int32_t format, const void *bytes, int64_t n, int64_t byte_step, float *out);
+int syldet_pcm_check_sources(const void *src, int64_t src_bytes, const int64_t *src_byte_offset, const int32_t *src_byte_step,
+                             const int32_t *src_format, const int64_t *n_samples, int32_t n_recordings);
+int syldet_recordings_load_pcm_device(syldet_recordings_t *r, const void *d_src, int64_t src_bytes, const int64_t *src_byte_offset,
+                                      const int32_t *src_byte_step, const int32_t *src_format, float *d_rows, int64_t channel_stride,
+                                      void *hip_stream);
+int syldet_recordings_load_sinc_pcm_device(syldet_recordings_t *r, const void *d_src, int64_t src_bytes, const int64_t *src_byte_offset,
+                                           const int32_t *src_byte_step, const int32_t *src_format, const int64_t *src_samples,
+                                           const double *src_rate, int32_t zero_crossings, double beta, double rolloff, float *d_rows,
+                                           int64_t channel_stride, void *hip_stream);
+
 /* ---- packed recordings: every recording's output track and trigger track ----
  * The two per-sample products of a run -- the Simulator's output track (syldet_trace*) and the TTL trigger track
  * (syldet_trigger*) -- for every recording of a packed bank, written straight to a destination of the recording's own, in a

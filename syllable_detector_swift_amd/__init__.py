@@ -10,8 +10,9 @@ from .config import (InvalidValue, MismatchedLength, MissingValue, NeuralNet, Ne
                      ProcessingFunction, SyllableDetectorConfig, SyllableDetectorError, UnableToOpenPath,
                      createWindow, frequencyIndexRange)
 from .bank import PinnedArray, ShardedSyllableDetectorBank, shard_table
-from .detector import (Recordings, Scorer, SyllableDetector, chooseThreshold, configsCompatible, configsShareClock, fusedFormOfConfig,
-                       planRecordings, recordingLengths, scoreHost)
+from ._abi import PCM_F32, PCM_F64, PCM_S16, PCM_S24, PCM_S32, PCM_U8
+from .detector import (PCM24, Recordings, Scorer, SyllableDetector, chooseThreshold, configsCompatible, configsShareClock, fusedFormOfConfig,
+                       pcmDecode, pcmSampleBytes, planRecordings, recordingLengths, scoreHost)
 from .resampler import ResamplerLinear, ResamplerSinc, sincReady, convertRate, deinterleave, sincCoefficient, sincDefaults, sincTaps
 
 __all__ = ["SyllableDetector", "SyllableDetectorConfig", "NeuralNet", "NeuralNetLayer", "ProcessingFunction",
@@ -19,4 +20,5 @@ __all__ = ["SyllableDetector", "SyllableDetectorConfig", "NeuralNet", "NeuralNet
            "SyllableDetectorError", "frequencyIndexRange", "createWindow", "ResamplerLinear", "deinterleave",
            "convertRate", "ResamplerSinc", "sincReady", "sincCoefficient", "sincTaps", "sincDefaults",
            "ShardedSyllableDetectorBank", "PinnedArray", "shard_table", "configsCompatible",
-           "configsShareClock", "fusedFormOfConfig", "Recordings", "planRecordings", "recordingLengths", "Scorer", "scoreHost", "chooseThreshold"]
+           "configsShareClock", "fusedFormOfConfig", "Recordings", "planRecordings", "recordingLengths", "Scorer", "scoreHost", "chooseThreshold",
+           "PCM_U8", "PCM_S16", "PCM_S24", "PCM_S32", "PCM_F32", "PCM_F64", "PCM24", "pcmDecode", "pcmSampleBytes"]

@@ -40,6 +40,7 @@ FN_L2NORMALIZE, FN_NORMALIZE, FN_NORMALIZESTD, FN_MAPMINMAX, FN_MAPSTD = 0, 1, 2
 TF_TANSIG, TF_LOGSIG, TF_PURELIN, TF_SATLIN = 0, 1, 2, 3
 RULE_FIRST, RULE_ANY = 0, 1
 ENGINE_AUTO, ENGINE_GENERIC, ENGINE_FUSED, ENGINE_WIDE_BF16 = 0, 1, 2, 3
+PCM_U8, PCM_S16, PCM_S24, PCM_S32, PCM_F32, PCM_F64 = 1, 2, 3, 4, 5, 6     # SYLDET_PCM_*: a file's own sample format
 
 c_float_p = C.POINTER(C.c_float)
 c_double_p = C.POINTER(C.c_double)
@@ -250,6 +251,12 @@ SIGNATURES = {
                                                      C.c_void_p, C.c_int64, C.c_void_p]),
     "syldet_recordings_load_sinc_device_s16": (C.c_int, [Handle, C.c_void_p, c_int64_p, c_int32_p, c_int64_p, c_double_p, C.c_int32, C.c_double,
                                                          C.c_double, C.c_void_p, C.c_int64, C.c_void_p]),
+    "syldet_pcm_sample_bytes": (C.c_int32, [C.c_int32]),
+    "syldet_pcm_decode": (C.c_int, [C.c_int32, C.c_void_p, C.c_int64, C.c_int64, c_float_p]),
+    "syldet_pcm_check_sources": (C.c_int, [C.c_void_p, C.c_int64, c_int64_p, c_int32_p, c_int32_p, c_int64_p, C.c_int32]),
+    "syldet_recordings_load_pcm_device": (C.c_int, [Handle, C.c_void_p, C.c_int64, c_int64_p, c_int32_p, c_int32_p, C.c_void_p, C.c_int64, C.c_void_p]),
+    "syldet_recordings_load_sinc_pcm_device": (C.c_int, [Handle, C.c_void_p, C.c_int64, c_int64_p, c_int32_p, c_int32_p, c_int64_p, c_double_p, C.c_int32,
+                                                         C.c_double, C.c_double, C.c_void_p, C.c_int64, C.c_void_p]),
     "syldet_recordings_events_device": (C.c_int, [Handle, C.c_void_p, C.c_void_p, C.c_double, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p,
                                                   C.c_void_p]),
     "syldet_recordings_trace_device": (C.c_int, [Handle, C.c_void_p, C.c_int32, C.c_void_p, C.c_int64, c_int64_p, c_int32_p, C.c_void_p]),

@@ -498,11 +498,17 @@ struct BatchOpt {
 struct BatchFile {
     std::string path;
     wav::Info info;
-    std::vector<float> f32;                                 // the frames as decoded, or (a 16-bit file) ...
-    std::vector<int16_t> s16;                               // ... as stored
+    std::vector<unsigned char> raw;                         // the frames as the file's data chunk stores them (wav::read_raw)
     bool is16 = false;
     bool convert = false;                                   // at another rate than the network's: converted as the rows load (--resample sinc)
-    size_t bytes() const { return is16 ? s16.size() * sizeof(int16_t) : f32.size() * sizeof(float); }
+    // what --batch counts: the bytes of the rows the file's samples make at its own rate (int16 rows for a 16-bit file, else fp32)
+    size_t bytes() const { return (size_t)info.frames * (size_t)info.channels * (is16 ? sizeof(int16_t) : sizeof(float)); }
+    int sample_bytes() const { return info.bits / 8; }
+    int32_t format() const                                  // SYLDET_PCM_* of the file's samples
+    {
+        if (info.format == 3) return info.bits == 32 ? SYLDET_PCM_F32 : SYLDET_PCM_F64;
+        return info.bits == 8 ? SYLDET_PCM_U8 : info.bits == 16 ? SYLDET_PCM_S16 : info.bits == 24 ? SYLDET_PCM_S24 : SYLDET_PCM_S32;
+    }
 };
 
 // --score: threshold calibration (syldet_scorer_*): every track of every batched file scored against its labelled samples for
@@ -572,30 +578,31 @@ int run_batch(std::vector<BatchFile> &files, const std::vector<syldet_config_t *
         converting = converting || f.convert;
     }
     // a batch that holds a file at another rate: every recording is planned with its length at the network's rate and loaded
-    // through the converting load (syldet_recordings_load_sinc_device*: the files at the network's rate are copied), fp32 rows
+    // through the converting load (syldet_recordings_load_sinc_device_s16, syldet_recordings_load_sinc_pcm_device: the files at the
+    // network's rate are copied), fp32 rows.
+    // The upload is the files' data chunks as they are stored.  A batch of 16-bit files is an int16 array (int16 rows, as ever);
+    // any other batch is bytes, every file in its own sample format, decoded as the rows load (syldet_recordings_load_pcm_device):
+    // no sample is converted on the host.
     std::vector<int64_t> lengths, src_offset, src_samples;
     std::vector<double> src_rate;
-    std::vector<int32_t> network, src_step;
-    std::vector<int64_t> file_at(files.size());             // where a file's frames lie in the upload, in elements (whole 16 bytes)
+    std::vector<int32_t> network, src_step, src_format;
+    const size_t el = all16 ? sizeof(int16_t) : 1;          // the unit of the offsets and steps: int16 elements, or bytes
+    std::vector<int64_t> file_at(files.size());             // where a file's frames lie in the upload, in that unit (whole 16 bytes)
     int64_t total = 0;
     for (size_t i = 0; i < files.size(); i++) {
-        BatchFile &f = files[i];
-        if (!all16 && f.is16) {                             // wav::read's value of a 16-bit sample
-            f.f32.resize(f.s16.size());
-            for (size_t j = 0; j < f.s16.size(); j++) f.f32[j] = (float)f.s16[j] * (1.0f / 32768.0f);
-            f.s16.clear();
-            f.is16 = false;
-        }
+        const BatchFile &f = files[i];
+        const int64_t sample = all16 ? 1 : f.sample_bytes();
         file_at[i] = total;
         for (int t = 0; t < f.info.channels; t++) {
             lengths.push_back(converting ? syldet_convert_rate_count(f.info.frames, f.info.rate, cfg->sampling_rate) : f.info.frames);
             src_samples.push_back(f.info.frames);
             src_rate.push_back(f.info.rate);
             network.push_back(t);
-            src_offset.push_back(total + t);
-            src_step.push_back(f.info.channels);
+            src_offset.push_back(total + t * sample);
+            src_step.push_back((int32_t)(f.info.channels * sample));
+            src_format.push_back(f.format());
         }
-        total += (f.info.frames * f.info.channels + 7) / 8 * 8;
+        total += ((int64_t)(f.raw.size() / el) + (int64_t)(16 / el) - 1) / (int64_t)(16 / el) * (int64_t)(16 / el);
     }
     const int32_t K = (int32_t)lengths.size();
     // the tracks' destination: file i's frames [n_i][tracks] at frames_at[i], n_i its length at the network's rate
@@ -682,28 +689,26 @@ int run_batch(std::vector<BatchFile> &files, const std::vector<syldet_config_t *
         const bool ran = row_evals > 0;
         if (!ran && !metering) break;                       // every file shorter than one evaluation: no events (the input meter reads them all the same)
         if (hipSetDevice(device) != hipSuccess || hipStreamCreate(&stream) != hipSuccess) { rc = 2; break; }
-        const size_t el = all16 ? sizeof(int16_t) : sizeof(float);
         DevBuf d_src, d_rows, d_out, d_flags, d_idx, d_val, d_cnt;
-        if (!d_src.alloc((size_t)total * el) || !d_rows.alloc((size_t)C * row_samples * (converting ? sizeof(float) : el)) || !d_out.alloc((size_t)C * row_evals * n_out * sizeof(float)) ||
+        if (!d_src.alloc((size_t)total * el) || !d_rows.alloc((size_t)C * row_samples * (converting || !all16 ? sizeof(float) : sizeof(int16_t))) || !d_out.alloc((size_t)C * row_evals * n_out * sizeof(float)) ||
             !d_flags.alloc((size_t)C * row_evals) || !d_cnt.alloc((size_t)K * sizeof(int64_t))) { rc = 2; break; }
         bool ok = true;
         for (size_t i = 0; ok && i < files.size(); i++) {
             const BatchFile &f = files[i];
-            ok = hipMemcpyAsync((char *)d_src.p + (size_t)file_at[i] * el, all16 ? (const void *)f.s16.data() : (const void *)f.f32.data(), f.bytes(),
-                                hipMemcpyHostToDevice, stream) == hipSuccess;
+            ok = hipMemcpyAsync((char *)d_src.p + (size_t)file_at[i] * el, f.raw.data(), f.raw.size(), hipMemcpyHostToDevice, stream) == hipSuccess;
         }
         if (!ok) { rc = 2; break; }
         if (converting) {
             st = all16 ? syldet_recordings_load_sinc_device_s16(r, (const int16_t *)d_src.p, src_offset.data(), src_step.data(), src_samples.data(), src_rate.data(),
                                                                 conv.zero_crossings, conv.beta, conv.rolloff, (float *)d_rows.p, row_samples, stream)
-                       : syldet_recordings_load_sinc_device(r, (const float *)d_src.p, src_offset.data(), src_step.data(), src_samples.data(), src_rate.data(),
-                                                            conv.zero_crossings, conv.beta, conv.rolloff, (float *)d_rows.p, row_samples, stream);
+                       : syldet_recordings_load_sinc_pcm_device(r, d_src.p, total, src_offset.data(), src_step.data(), src_format.data(), src_samples.data(),
+                                                                src_rate.data(), conv.zero_crossings, conv.beta, conv.rolloff, (float *)d_rows.p, row_samples, stream);
             if (!st && ran) st = syldet_run_device(h, (const float *)d_rows.p, row_samples, row_samples, (float *)d_out.p, (uint8_t *)d_flags.p, stream);
         } else if (all16) {
             st = syldet_recordings_load_device_s16(r, (const int16_t *)d_src.p, src_offset.data(), src_step.data(), (int16_t *)d_rows.p, row_samples, stream);
             if (!st && ran) st = syldet_run_device_s16(h, (const int16_t *)d_rows.p, row_samples, row_samples, (float *)d_out.p, (uint8_t *)d_flags.p, stream);
         } else {
-            st = syldet_recordings_load_device(r, (const float *)d_src.p, src_offset.data(), src_step.data(), (float *)d_rows.p, row_samples, stream);
+            st = syldet_recordings_load_pcm_device(r, d_src.p, total, src_offset.data(), src_step.data(), src_format.data(), (float *)d_rows.p, row_samples, stream);
             if (!st && ran) st = syldet_run_device(h, (const float *)d_rows.p, row_samples, row_samples, (float *)d_out.p, (uint8_t *)d_flags.p, stream);
         }
         // the level tables of every file of the batch: the input meter on the very rows that are run (int16 rows for 16-bit files, fp32
@@ -960,7 +965,7 @@ int process_batched(const std::vector<std::string> &audio, const std::vector<syl
             (cfgs.size() == 1 || (size_t)f.info.channels == cfgs.size())) {
             f.is16 = f.info.format == 1 && f.info.bits == 16;
             err.clear();
-            if (f.is16 ? wav::read_s16(p, f.info, f.s16, err) : wav::read(p, f.info, f.f32, err)) {
+            if (wav::read_raw(p, f.info, f.raw, err)) {
                 held += f.bytes();
                 files.push_back(std::move(f));
                 if ((long long)held >= opt.bytes) flush();

@@ -135,6 +135,22 @@ inline bool read_s16(const std::string &path, Info &info, std::vector<int16_t> &
     return true;
 }
 
+// Reads the header and the sample data as the `data` chunk stores it: frames * channels samples of bits / 8 bytes each, little
+// endian, interleaved -- what the library's loads of the files' own bytes take (syldet_recordings_load_pcm_device), with the values
+// read() gives.
+inline bool read_raw(const std::string &path, Info &info, std::vector<unsigned char> &out, std::string &err)
+{
+    if (!probe(path, info, err)) return false;
+    FILE *f = std::fopen(path.c_str(), "rb");
+    if (!f) { err = "cannot open file"; return false; }
+    out.resize((size_t)info.frames * (size_t)info.channels * ((size_t)info.bits / 8));
+    std::fseek(f, (long)info.data_offset, SEEK_SET);
+    const size_t got = std::fread(out.data(), 1, out.size(), f);
+    std::fclose(f);
+    if (got != out.size()) { err = "truncated sample data"; return false; }
+    return true;
+}
+
 // Writes `frames` frames of `channels` interleaved 16-bit samples as a canonical WAV: the 44-byte header (RIFF, a 16-byte PCM fmt
 // chunk, data), little endian.  Refuses what a RIFF size field cannot hold (the file would pass 4 GiB).
 inline bool write_s16(const std::string &path, double rate, int channels, int64_t frames, const int16_t *data, std::string &err)

@@ -386,10 +386,11 @@ hipError_t launch_levels_out(const float *outputs, int64_t n_evals, int n_out, i
 
 // ---- packed recordings (kernels_recordings.hip; syldet_recordings_* of include/syldet.h) ----
 // One slot of the plan as the load kernel reads it: the table is sorted by (row, offset), row c's slots are
-// [row_begin[c], row_begin[c + 1]).  Sample i of the slot is src[src_offset + i src_step].
+// [row_begin[c], row_begin[c + 1]).  Sample i of the slot is src[src_offset + i src_step] -- or, for a source of the files' own bytes
+// (format: one of pcm_values.hpp's, else 0), the `format` value at byte src_offset + i src_step.
 struct RecSlotDev {
     int64_t offset, n_samples, src_offset;
-    int32_t src_step, pad;
+    int32_t src_step, format;
 };
 // ... and as the events kernel reads it, in the caller's order of recordings
 struct RecEventDev {
@@ -406,6 +407,8 @@ struct RecLoadDesc {
 };
 // rows [C][stride] (the first row_samples of each) <- the recordings' samples and +0 everywhere else; fp32 or (s16) int16
 hipError_t launch_recordings_load(const RecLoadDesc &d, const void *src, bool s16, void *rows, int64_t stride, int C, hipStream_t stream);
+// the same rows, fp32, from the files' own bytes: every slot decoded from its format (kernels_recordings_pcm.hip)
+hipError_t launch_recordings_load_pcm(const RecLoadDesc &d, const void *src, float *rows, int64_t stride, int C, hipStream_t stream);
 // indices [K][capacity], values [K][capacity][n_out] (or null), counts [K] <- flags [C][row_evals], outputs [C][row_evals][n_out] (or null)
 hipError_t launch_recordings_events(const RecEventDev *desc, int K, int64_t row_evals, int n_out, const float *outputs, const uint8_t *flags,
                                     int64_t first_index, int64_t hop, int64_t debounce_frames, int64_t *indices, float *values,
@@ -419,7 +422,8 @@ struct RecSincDev {
     int64_t offset, n_out, span_end, src_offset, n_in;
     double rate_in, H;                       // the recording's rate; H = Z / s of its design
     float scale, idx_scale;                  // float(s); float(N / H)
-    int32_t src_step, copy;                  // copy: at the network's rate, not converted
+    int32_t src_step;
+    int16_t copy, format;                    // copy: at the network's rate, not converted; format: RecSlotDev's (a byte source), else 0
 };
 struct RecSincDesc {
     const RecSincDev *slots;
@@ -435,6 +439,9 @@ struct RecSincDesc {
 // src fp32 or (s16) int16; table: the unit filter's N + 4 floats on the device, 16-byte aligned
 hipError_t launch_recordings_load_sinc(const RecSincDesc &d, const void *src, bool s16, double rate_out, const float *table, int N,
                                        float *rows, int64_t stride, int C, hipStream_t stream);
+// ... and src the files' own bytes, every slot in its format
+hipError_t launch_recordings_load_sinc_pcm(const RecSincDesc &d, const void *src, double rate_out, const float *table, int N, float *rows,
+                                           int64_t stride, int C, hipStream_t stream);
 
 // ---- packed recordings: the per-sample tracks (kernels_recordings_tracks.hip; syldet_recordings_trace_device* and
 // syldet_recordings_trigger*_device* of include/syldet.h) ----

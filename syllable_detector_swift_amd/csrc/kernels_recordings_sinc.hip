@@ -5,6 +5,9 @@
 //
 //   recordings_load_sinc_kernel<float>     fp32 sources
 //   recordings_load_sinc_kernel<int16_t>   16-bit PCM sources (x means float(x) * 2^-15), widened as they are staged
+//   recordings_load_sinc_kernel<uint8_t>   the files' own bytes (syldet_recordings_load_sinc_pcm_device): src_offset and src_step
+//                                          count bytes, and a sample is the slot's format's value (pcm_values.hpp) -- the slot is
+//                                          the workgroup's, so the format decides a scalar branch
 //
 // grid (workgroups of the fullest row, C).  Row c's slots own consecutive workgroups of the row, kSincBlockOut row positions of a
 // slot's span [offset, span_end) each; the workgroup finds its slot by a binary search of the row's prefix table with its block
@@ -19,11 +22,18 @@
 // gfx950 only.  wave = 64.  Compiled with -ffp-contract=off, as kernels_sinc.hip is (see the Makefile).
 
 #include "kernels.hpp"
+#include "pcm_values.hpp"
 #include "sinc_taps.hpp"
 
 namespace sd {
 
 namespace {
+
+// the sample at in[at] (fp32, int16), or the `format` value at byte `at` of in
+template <typename T>
+__device__ __forceinline__ float rec_sample(const T *__restrict__ in, int64_t at, int) { return sinc_sample<T>(in[at]); }
+template <>
+__device__ __forceinline__ float rec_sample<uint8_t>(const uint8_t *__restrict__ in, int64_t at, int format) { return pcm_value(format, in + at); }
 
 template <typename T>
 __global__ void __launch_bounds__(256) SINC_WAVES_PER_SIMD
@@ -61,6 +71,7 @@ recordings_load_sinc_kernel(RecSincDesc d, const T *__restrict__ src, double rat
     const int64_t span = s.span_end - s.offset;                              // > i0
     const int64_t n_out = s.n_out, n_in = s.n_in;
     const int64_t step = s.src_step;
+    const int format = s.format;
     const T *in = src + s.src_offset;
     float *dst = row + s.offset;
 
@@ -68,7 +79,7 @@ recordings_load_sinc_kernel(RecSincDesc d, const T *__restrict__ src, double rat
 #pragma unroll
         for (int r = 0; r < kSincPerThread; r++) {
             const int64_t i = i0 + tid + (int64_t)r * 256;
-            if (i < span) dst[i] = i < n_out ? sinc_sample<T>(in[i * step]) : 0.0f;      // (copy: n_out <= n_in)
+            if (i < span) dst[i] = i < n_out ? rec_sample<T>(in, i * step, format) : 0.0f;      // (copy: n_out <= n_in)
         }
         return;
     }
@@ -101,7 +112,7 @@ recordings_load_sinc_kernel(RecSincDesc d, const T *__restrict__ src, double rat
     for (int64_t base = in_lo; base <= in_hi; base += kSincStage) {
         __syncthreads();                                     // the table is in; the stretch before this one is read out
         const int64_t end = min(base + kSincStage - 1, in_hi);                           // 0 <= base <= end <= n_in - 1
-        for (int e = tid; e <= (int)(end - base); e += 256) xs[e] = sinc_sample<T>(in[(base + e) * step]);
+        for (int e = tid; e <= (int)(end - base); e += 256) xs[e] = rec_sample<T>(in, (base + e) * step, format);
         __syncthreads();
 #pragma unroll
         for (int r = 0; r < kSincPerThread; r++) {
@@ -141,6 +152,13 @@ hipError_t launch_recordings_load_sinc(const RecSincDesc &d, const void *src, bo
     if (C <= 0 || d.grid_x <= 0) return hipSuccess;
     return s16 ? load_sinc_as<int16_t>(d, src, rate_out, table, N, rows, stride, C, stream)
                : load_sinc_as<float>(d, src, rate_out, table, N, rows, stride, C, stream);
+}
+
+hipError_t launch_recordings_load_sinc_pcm(const RecSincDesc &d, const void *src, double rate_out, const float *table, int N, float *rows,
+                                           int64_t stride, int C, hipStream_t stream)
+{
+    if (C <= 0 || d.grid_x <= 0) return hipSuccess;
+    return load_sinc_as<uint8_t>(d, src, rate_out, table, N, rows, stride, C, stream);
 }
 
 }  // namespace sd

@@ -1,6 +1,7 @@
 // syldet_recordings.cpp -- packed recordings (include/syldet.h, "packed recordings"): the plan that lays many recordings of
 // different lengths end to end in a bank's rows, and the handle that keeps the plan's tables on the device so that the
-// device calls (kernels_recordings.hip; kernels_recordings_sinc.hip for recordings at other rates) are launches only.  The handle
+// device calls (kernels_recordings.hip; kernels_recordings_sinc.hip for recordings at other rates; kernels_recordings_pcm.hip for
+// the files' own bytes) are launches only.  The handle
 // itself is in syldet_recordings.hpp, the layout of its device block in recordings_blob.hpp; its per-sample tracks are in
 // syldet_recordings_tracks.cpp, its level meters in syldet_recordings_levels.cpp.
 #include <numeric>
@@ -63,19 +64,22 @@ int make_plan(const BankInfo &b, const int64_t *n_samples, const int32_t *networ
     return SYLDET_OK;
 }
 
-int load_impl(syldet_recordings_t *r, const void *d_src, bool s16, const int64_t *src_offset, const int32_t *src_step, void *d_rows,
-              int64_t channel_stride, hipStream_t stream)
+int load_impl(syldet_recordings_t *r, const void *d_src, bool s16, const PcmSrc *pcm, const int64_t *src_offset, const int32_t *src_step,
+              void *d_rows, int64_t channel_stride, hipStream_t stream)
 {
-    if (!r || !d_rows || (r->plan.K > 0 && (!d_src || !src_offset))) return fail(SYLDET_ERR_INVALID_ARGUMENT, "NULL argument");
+    if (!r || !d_rows || (r->plan.K > 0 && (!d_src || !src_offset || (pcm && !pcm->format)))) return fail(SYLDET_ERR_INVALID_ARGUMENT, "NULL argument");
     if (int st = stride_arg(r, channel_stride)) return st;
     if (int st = source_args(r->plan.K, src_offset, src_step)) return st;
+    if (pcm)
+        if (int st = pcm_args(r->plan.K, d_src, *pcm, src_offset, src_step, [&](int k) { return r->plan.slots[(size_t)k].n_samples; })) return st;
     if (r->plan.row_samples == 0) return SYLDET_OK;
     // the key is the table itself: entry i holds the sources of recording order[i]
     KeptTable<RecSlotDev> &t = r->load.table;
     const std::vector<int32_t> &order = r->plan.order;
-    auto step = [&](size_t i) { return src_step ? src_step[order[i]] : 1; };
+    auto step = [&](size_t i) { return step_of(pcm, src_step, order[i]); };
     bool same = t.kept;
-    for (size_t i = 0; i < order.size() && same; i++) same = t.host[i].src_offset == src_offset[order[i]] && t.host[i].src_step == step(i);
+    for (size_t i = 0; i < order.size() && same; i++)
+        same = t.host[i].src_offset == src_offset[order[i]] && t.host[i].src_step == step(i) && t.host[i].format == format_of(pcm, order[i]);
     SYLDET_HIP(hipSetDevice(r->bank.device));
     if (!same) {
         // new sources: the table is re-made behind the last plain load that reads it
@@ -83,13 +87,20 @@ int load_impl(syldet_recordings_t *r, const void *d_src, bool s16, const int64_t
             for (size_t i = 0; i < order.size(); i++) {
                 t.host[i].src_offset = src_offset[order[i]];
                 t.host[i].src_step = step(i);
+                t.host[i].format = format_of(pcm, order[i]);
             }
             return SYLDET_OK;
         });
         if (st) return st;
     }
     t.read_on(stream);
-    SYLDET_HIP(launch_recordings_load(r->load.desc, d_src, s16, d_rows, channel_stride, r->bank.channels, stream));
+    if (!pcm) {
+        SYLDET_HIP(launch_recordings_load(r->load.desc, d_src, s16, d_rows, channel_stride, r->bank.channels, stream));
+        return SYLDET_OK;
+    }
+    r->h->prof_begin();
+    KernelTimer timer(r->h, stream, "recordings_load_pcm_kernel");
+    SYLDET_HIP(launch_recordings_load_pcm(r->load.desc, d_src, (float *)d_rows, channel_stride, r->bank.channels, stream));
     return SYLDET_OK;
 }
 
@@ -97,7 +108,7 @@ int load_impl(syldet_recordings_t *r, const void *d_src, bool s16, const int64_t
 struct SincLaunch {
     syldet_recordings_t *r;
     const void *d_src;
-    bool s16;
+    bool s16, pcm;
     float *d_rows;
     int64_t stride;
     hipStream_t stream;
@@ -106,22 +117,29 @@ struct SincLaunch {
 int sinc_launch(const float *table, int entries, void *ctx)
 {
     const SincLaunch &a = *(const SincLaunch *)ctx;
-    SYLDET_HIP(launch_recordings_load_sinc(a.r->sinc.desc, a.d_src, a.s16, a.r->bank.sampling_rate, table, entries, a.d_rows, a.stride,
-                                           a.r->bank.channels, a.stream));
+    if (a.pcm)
+        SYLDET_HIP(launch_recordings_load_sinc_pcm(a.r->sinc.desc, a.d_src, a.r->bank.sampling_rate, table, entries, a.d_rows, a.stride,
+                                                   a.r->bank.channels, a.stream));
+    else
+        SYLDET_HIP(launch_recordings_load_sinc(a.r->sinc.desc, a.d_src, a.s16, a.r->bank.sampling_rate, table, entries, a.d_rows, a.stride,
+                                               a.r->bank.channels, a.stream));
     return SYLDET_OK;
 }
 
-int load_sinc_impl(syldet_recordings_t *r, const void *d_src, bool s16, const int64_t *src_offset, const int32_t *src_step,
+int load_sinc_impl(syldet_recordings_t *r, const void *d_src, bool s16, const PcmSrc *pcm, const int64_t *src_offset, const int32_t *src_step,
                    const int64_t *src_samples, const double *src_rate, int32_t Z, double beta, double rho, float *d_rows,
                    int64_t channel_stride, hipStream_t stream)
 {
-    if (!r || !d_rows || (r->plan.K > 0 && (!d_src || !src_offset || !src_samples || !src_rate))) return fail(SYLDET_ERR_INVALID_ARGUMENT, "NULL argument");
+    if (!r || !d_rows || (r->plan.K > 0 && (!d_src || !src_offset || !src_samples || !src_rate || (pcm && !pcm->format))))
+        return fail(SYLDET_ERR_INVALID_ARGUMENT, "NULL argument");
     if (int st = stride_arg(r, channel_stride)) return st;
     const Plan &p = r->plan;
     syldet_recordings::Sinc &s = r->sinc;
     const int K = p.K;
     const double rate = r->bank.sampling_rate;
     if (int st = source_args(K, src_offset, src_step)) return st;
+    if (pcm)
+        if (int st = pcm_args(K, d_src, *pcm, src_offset, src_step, [&](int k) { return src_samples[k]; })) return st;
     for (int k = 0; k < K; k++) {
         if (src_samples[k] < 0) return fail(SYLDET_ERR_INVALID_ARGUMENT, "src_samples[" + std::to_string(k) + "] is negative");
         if (!(src_rate[k] > 0.0) || !std::isfinite(src_rate[k]))
@@ -146,11 +164,12 @@ int load_sinc_impl(syldet_recordings_t *r, const void *d_src, bool s16, const in
     if (p.row_samples / kSincBlockOut + K + 1 > 0x7fffffff) return fail(SYLDET_ERR_UNSUPPORTED, "rows too long for one launch of the converting load");
     // the key is the quality and the table itself: slot i holds the sources of recording order[i]
     RecSincDev *slots = (RecSincDev *)s.table.host.data();
-    auto step = [&](int k) { return src_step ? src_step[k] : 1; };
+    auto step = [&](int k) { return step_of(pcm, src_step, k); };
     bool same = s.table.kept && s.Z == Z && s.beta == beta && s.rho == rho;
     for (int i = 0; i < K && same; i++) {
         const int k = p.order[(size_t)i];
-        same = slots[i].src_offset == src_offset[k] && slots[i].src_step == step(k) && slots[i].n_in == src_samples[k] && slots[i].rate_in == src_rate[k];
+        same = slots[i].src_offset == src_offset[k] && slots[i].src_step == step(k) && slots[i].n_in == src_samples[k] && slots[i].rate_in == src_rate[k] &&
+               slots[i].format == format_of(pcm, k);
     }
     SYLDET_HIP(hipSetDevice(r->bank.device));
     if (!same) {
@@ -175,6 +194,7 @@ int load_sinc_impl(syldet_recordings_t *r, const void *d_src, bool s16, const in
                     d.src_offset = src_offset[k];
                     d.n_in = src_samples[k];
                     d.src_step = step(k);
+                    d.format = (int16_t)format_of(pcm, k);
                     d.rate_in = src_rate[k];
                     d.copy = src_rate[k] == rate;
                     if (!d.copy) {
@@ -196,7 +216,7 @@ int load_sinc_impl(syldet_recordings_t *r, const void *d_src, bool s16, const in
         if (st) return st;
     }
     s.table.read_on(stream);
-    SincLaunch a{r, d_src, s16, d_rows, channel_stride, stream};
+    SincLaunch a{r, d_src, s16, pcm != nullptr, d_rows, channel_stride, stream};
     return sinc_table_use(Z, beta, sinc_launch, &a);
 }
 
@@ -364,20 +384,20 @@ int syldet_recordings_shape(const syldet_recordings_t *r, int32_t *n_recordings,
 int syldet_recordings_load_device(syldet_recordings_t *r, const float *d_src, const int64_t *src_offset, const int32_t *src_step,
                                   float *d_rows, int64_t channel_stride, void *hip_stream)
 {
-    return load_impl(r, d_src, false, src_offset, src_step, d_rows, channel_stride, (hipStream_t)hip_stream);
+    return load_impl(r, d_src, false, nullptr, src_offset, src_step, d_rows, channel_stride, (hipStream_t)hip_stream);
 }
 
 int syldet_recordings_load_device_s16(syldet_recordings_t *r, const int16_t *d_src, const int64_t *src_offset, const int32_t *src_step,
                                       int16_t *d_rows, int64_t channel_stride, void *hip_stream)
 {
-    return load_impl(r, d_src, true, src_offset, src_step, d_rows, channel_stride, (hipStream_t)hip_stream);
+    return load_impl(r, d_src, true, nullptr, src_offset, src_step, d_rows, channel_stride, (hipStream_t)hip_stream);
 }
 
 int syldet_recordings_load_sinc_device(syldet_recordings_t *r, const float *d_src, const int64_t *src_offset, const int32_t *src_step,
                                        const int64_t *src_samples, const double *src_rate, int32_t zero_crossings, double beta, double rolloff,
                                        float *d_rows, int64_t channel_stride, void *hip_stream)
 {
-    return load_sinc_impl(r, d_src, false, src_offset, src_step, src_samples, src_rate, zero_crossings, beta, rolloff, d_rows, channel_stride,
+    return load_sinc_impl(r, d_src, false, nullptr, src_offset, src_step, src_samples, src_rate, zero_crossings, beta, rolloff, d_rows, channel_stride,
                           (hipStream_t)hip_stream);
 }
 
@@ -385,8 +405,26 @@ int syldet_recordings_load_sinc_device_s16(syldet_recordings_t *r, const int16_t
                                            const int64_t *src_samples, const double *src_rate, int32_t zero_crossings, double beta,
                                            double rolloff, float *d_rows, int64_t channel_stride, void *hip_stream)
 {
-    return load_sinc_impl(r, d_src, true, src_offset, src_step, src_samples, src_rate, zero_crossings, beta, rolloff, d_rows, channel_stride,
+    return load_sinc_impl(r, d_src, true, nullptr, src_offset, src_step, src_samples, src_rate, zero_crossings, beta, rolloff, d_rows, channel_stride,
                           (hipStream_t)hip_stream);
+}
+
+int syldet_recordings_load_pcm_device(syldet_recordings_t *r, const void *d_src, int64_t src_bytes, const int64_t *src_byte_offset,
+                                      const int32_t *src_byte_step, const int32_t *src_format, float *d_rows, int64_t channel_stride,
+                                      void *hip_stream)
+{
+    const PcmSrc pcm{src_bytes, src_format};
+    return load_impl(r, d_src, false, &pcm, src_byte_offset, src_byte_step, d_rows, channel_stride, (hipStream_t)hip_stream);
+}
+
+int syldet_recordings_load_sinc_pcm_device(syldet_recordings_t *r, const void *d_src, int64_t src_bytes, const int64_t *src_byte_offset,
+                                           const int32_t *src_byte_step, const int32_t *src_format, const int64_t *src_samples,
+                                           const double *src_rate, int32_t zero_crossings, double beta, double rolloff, float *d_rows,
+                                           int64_t channel_stride, void *hip_stream)
+{
+    const PcmSrc pcm{src_bytes, src_format};
+    return load_sinc_impl(r, d_src, false, &pcm, src_byte_offset, src_byte_step, src_samples, src_rate, zero_crossings, beta, rolloff, d_rows,
+                          channel_stride, (hipStream_t)hip_stream);
 }
 
 int syldet_recordings_events_device(syldet_recordings_t *r, const float *d_outputs, const uint8_t *d_flags, double debounce_seconds,

@@ -3,6 +3,7 @@
 // syldet_recordings_levels.cpp (the level meters).  Not installed.
 #pragma once
 
+#include "pcm_values.hpp"
 #include "syldet_handle.hpp"
 
 namespace sd {
@@ -101,6 +102,39 @@ inline int source_args(int K, const int64_t *src_offset, const int32_t *src_step
     for (int k = 0; k < K; k++)
         if (src_offset[k] < 0 || (src_step && src_step[k] < 1))
             return fail(SYLDET_ERR_INVALID_ARGUMENT, "a negative source offset or a step below 1 (recording " + std::to_string(k) + ")");
+    return SYLDET_OK;
+}
+
+// A source of the files' own bytes (syldet_recordings_load_pcm_device, syldet_recordings_load_sinc_pcm_device): src_offset and
+// src_step count bytes, and recording k's samples are format[k] values (pcm_values.hpp).  NULL where the source is an array of
+// elements (the fp32 and int16 calls): format 0 in the kept tables, so a byte source never compares equal to one of elements.
+struct PcmSrc {
+    int64_t bytes;
+    const int32_t *format;
+};
+inline int format_of(const PcmSrc *pcm, int k) { return pcm ? pcm->format[k] : 0; }
+inline int32_t step_of(const PcmSrc *pcm, const int32_t *src_step, int k)     // (NULL steps: contiguous recordings)
+{
+    return src_step ? src_step[k] : pcm ? pcm_sample_bytes(pcm->format[k]) : 1;
+}
+
+// The refusals of a byte source, behind the plain load's own checks: count(k) samples of recording k are read (none where <= 0)
+template <class Count>
+int pcm_args(int K, const void *d_src, const PcmSrc &pcm, const int64_t *src_offset, const int32_t *src_step, Count count)
+{
+    if (pcm.bytes < 0) return fail(SYLDET_ERR_INVALID_ARGUMENT, "src_bytes is negative");
+    for (int k = 0; k < K; k++) {
+        auto rec = [k]() { return " (recording " + std::to_string(k) + ")"; };
+        const int64_t size = pcm_sample_bytes(pcm.format[k]), step = step_of(&pcm, src_step, k);
+        if (size == 0) return fail(SYLDET_ERR_INVALID_ARGUMENT, "src_format " + std::to_string(pcm.format[k]) + " is no sample format" + rec());
+        if (step < size) return fail(SYLDET_ERR_INVALID_ARGUMENT, "src_byte_step " + std::to_string(step) + " is below the " + std::to_string(size) + " bytes of a sample" + rec());
+        if (pcm.format[k] != kPcmU8 && pcm.format[k] != kPcmS24 && (((uintptr_t)d_src + (uintptr_t)src_offset[k]) % (uintptr_t)size != 0 || step % size != 0))
+            return fail(SYLDET_ERR_INVALID_ARGUMENT, "an address or a step that is no multiple of the " + std::to_string(size) + " bytes of a sample" + rec());
+        const int64_t n = count(k);
+        // the last sample byte is offset + (n - 1) step + size - 1 < src_bytes
+        if (n > 0 && (pcm.bytes < size || src_offset[k] > pcm.bytes - size || n - 1 > (pcm.bytes - size - src_offset[k]) / step))
+            return fail(SYLDET_ERR_INVALID_ARGUMENT, "the samples reach beyond src_bytes" + rec());
+    }
     return SYLDET_OK;
 }
 

@@ -819,7 +819,10 @@ class SyllableDetector:
                       rolloff=None, tracks=None, output: int = 0, bufferLength: int = 32, width: Optional[int] = None, latency: int = 0,
                       levels=None):
         """Recordings of any lengths in one pass: one upload, load, run / runPCM16, events and one download.  `arrays`: 1-D
-        (mono) or [frames, tracks] numpy arrays, all float32 or all int16 (16-bit PCM); every track is a recording, in order
+        (mono) or [frames, tracks] numpy arrays, all float32 or all int16 (16-bit PCM: int16 rows) -- or, each in its own sample
+        format, any of uint8 (offset binary), int16, int32, float32, float64 and PCM24 (packed 24-bit): such a list is uploaded as
+        its own bytes and decoded as the rows load (Recordings.loadPCM, with rates Recordings.loadSincPCM; fp32 rows), with the
+        results of the same recordings given as float32; every track is a recording, in order
         (`networks`, on a multi / mixed bank: one entry a track).  Returns, per recording, (indices int64 [n], values float32
         [n, outputs]): its debounced detections and the outputs of their evaluations.
         `rates`: the sampling rate of every array (None: all at the network's, and nothing else changes).  With rates,
@@ -843,30 +846,45 @@ class SyllableDetector:
             raise ValueError("resample, zeroCrossings, beta and rolloff belong to rates")
         if rates is not None and resample != "sinc":
             raise ValueError("recordings at rates of their own need resample='sinc' (there is no linear-interpolation load)")
-        arrays = [np.asarray(a) for a in arrays]
-        dtypes = {a.dtype for a in arrays}
-        if arrays and dtypes not in ({np.dtype(np.float32)}, {np.dtype(np.int16)}):
-            raise ValueError("arrays must be all float32 or all int16")
-        s16 = bool(arrays) and arrays[0].dtype == np.int16
+        arrays = [a if isinstance(a, PCM24) else np.asarray(a) for a in arrays]
+        dtypes = {None if isinstance(a, PCM24) else a.dtype for a in arrays}
+        # one dtype, float32 or int16: arrays of elements, as ever; anything else: every array's own bytes, each in its format
+        pcm = bool(arrays) and dtypes not in ({np.dtype(np.float32)}, {np.dtype(np.int16)})
+        if pcm and not all(d is None or d in _PCM_OF_DTYPE for d in dtypes):
+            raise ValueError("arrays are uint8, int16, int32, float32 or float64 numpy arrays, or PCM24")
+        s16 = bool(arrays) and not pcm and arrays[0].dtype == np.int16
         if rates is not None and len(rates) != len(arrays):
             raise ValueError("one rate per array")
-        lengths, offsets, steps, track_rates, pos = [], [], [], [], 0
+        lengths, offsets, steps, formats, track_rates, pos = [], [], [], [], [], 0
+        # (in elements, or for arrays in their own formats in bytes: every file from a whole 16 bytes either way)
+        unit = 16 if pcm else 8
         for i, a in enumerate(arrays):
-            if a.ndim not in (1, 2):
-                raise ValueError("each array is 1-D (mono) or [frames, tracks]")
-            n_tracks = 1 if a.ndim == 1 else a.shape[1]
+            if isinstance(a, PCM24):
+                n_frames, n_tracks, fmt, size, n_units = a.frames, a.tracks, _abi.PCM_S24, 3, a.bytes.size
+            else:
+                if a.ndim not in (1, 2):
+                    raise ValueError("each array is 1-D (mono) or [frames, tracks]")
+                n_frames, n_tracks = a.shape[0], 1 if a.ndim == 1 else a.shape[1]
+                fmt = _PCM_OF_DTYPE[a.dtype] if pcm else 0
+                size = a.dtype.itemsize if pcm else 1
+                n_units = a.size * size
             for t in range(n_tracks):
-                lengths.append(a.shape[0])
-                offsets.append(pos + t)
-                steps.append(n_tracks)
+                lengths.append(n_frames)
+                offsets.append(pos + t * size)
+                steps.append(n_tracks * size)
+                formats.append(fmt)
                 if rates is not None:
                     track_rates.append(float(rates[i]))
-            pos += (a.size + 7) // 8 * 8                          # every file from a whole 16 bytes
-        flat = np.zeros(max(pos, 8), np.int16 if s16 else np.float32)
+            pos += (n_units + unit - 1) // unit * unit
+        flat = np.zeros(max(pos, unit), np.uint8 if pcm else np.int16 if s16 else np.float32)
         pos = 0
         for a in arrays:
-            flat[pos:pos + a.size] = np.ascontiguousarray(a).reshape(-1)
-            pos += (a.size + 7) // 8 * 8
+            if pcm:
+                raw = a.bytes.reshape(-1) if isinstance(a, PCM24) else np.ascontiguousarray(a).astype(a.dtype.newbyteorder("<"), copy=False).reshape(-1).view(np.uint8)
+            else:
+                raw = np.ascontiguousarray(a).reshape(-1)
+            flat[pos:pos + raw.size] = raw
+            pos += (raw.size + unit - 1) // unit * unit
         n_out = self.geometry.outputs
         planned = lengths if rates is None else recordingLengths(lengths, track_rates, self.config.samplingRate)
         with self.recordings(planned, networks) as rec:
@@ -876,7 +894,12 @@ class SyllableDetector:
                 made = {t: [np.zeros(n, np.int16) for n in planned] for t in names}
             tables = None
             if ran or (levels is not None and rec.rowSamples > 0):
-                if rates is None:
+                if pcm and rates is None:
+                    rows = rec.loadPCM(torch.from_numpy(flat).to("cuda:%d" % self.device), offsets, steps, formats)
+                elif pcm:
+                    rows = rec.loadSincPCM(torch.from_numpy(flat).to("cuda:%d" % self.device), offsets, steps, formats, lengths, track_rates,
+                                           zeroCrossings, beta, rolloff)
+                elif rates is None:
                     rows = rec.load(torch.from_numpy(flat).to("cuda:%d" % self.device), offsets, steps)
                 else:
                     rows = rec.loadSinc(torch.from_numpy(flat).to("cuda:%d" % self.device), offsets, lengths, track_rates, steps, zeroCrossings,
@@ -975,6 +998,49 @@ def recordingLengths(sourceSamples, sourceRates, rate: float):
     if n.size != r.size:
         raise ValueError("one rate per recording")
     return [int(_abi.lib.syldet_convert_rate_count(int(a), float(b), float(rate))) for a, b in zip(n, r)]
+
+
+# ---- the files' own sample formats (syldet_pcm_*: include/syldet.h, "packed recordings: the files' own sample formats") ----
+_PCM_OF_DTYPE = {np.dtype(np.uint8): _abi.PCM_U8, np.dtype(np.int16): _abi.PCM_S16, np.dtype(np.int32): _abi.PCM_S32,
+                 np.dtype(np.float32): _abi.PCM_F32, np.dtype(np.float64): _abi.PCM_F64}
+
+
+class PCM24:
+    """Packed 24-bit PCM as a WAV stores it, for runRecordings: a uint8 array [frames, tracks, 3] (or [frames, 3], mono), little
+    endian, sample = the three bytes sign-extended, meaning v * 2**-23."""
+
+    def __init__(self, array):
+        a = np.ascontiguousarray(array)
+        if a.dtype != np.uint8 or a.ndim not in (2, 3) or a.shape[-1] != 3:
+            raise ValueError("PCM24 takes a uint8 array [frames, tracks, 3] or [frames, 3]")
+        self.bytes = a
+        self.frames = int(a.shape[0])
+        self.tracks = 1 if a.ndim == 2 else int(a.shape[1])
+
+
+def pcmSampleBytes(format: int) -> int:
+    """syldet_pcm_sample_bytes: the bytes of one sample of a PCM_* format (0: no such format)."""
+    return int(_abi.lib.syldet_pcm_sample_bytes(int(format)))
+
+
+def pcmDecode(data, format: int, n: Optional[int] = None, byteStep: Optional[int] = None) -> np.ndarray:
+    """syldet_pcm_decode, host only: the n float32 values of the `format` samples at data[i * byteStep] (data: bytes or a uint8
+    array; byteStep None: contiguous samples; n None: as many as data holds) -- the values every load of the files' own bytes
+    writes, and the tool's WAV reader gives."""
+    raw = np.ascontiguousarray(np.frombuffer(data, np.uint8) if isinstance(data, (bytes, bytearray, memoryview)) else data)
+    if raw.dtype != np.uint8:
+        raise ValueError("data must be bytes or a uint8 array")
+    raw = raw.reshape(-1)
+    size = pcmSampleBytes(format)
+    step = size if byteStep is None else int(byteStep)
+    if n is None:
+        n = 0 if size == 0 or step < size or raw.size < size else (raw.size - size) // step + 1
+    n = int(n)
+    if size and step >= size and n > 0 and (n - 1) * step + size > raw.size:
+        raise ValueError("the samples reach beyond data")
+    out = np.empty(max(n, 0), np.float32)
+    check(_abi.lib.syldet_pcm_decode(int(format), raw.ctypes.data, n, step, out.ctypes.data_as(_abi.c_float_p)))
+    return out
 
 
 def _slot_tuple(s):
@@ -1097,6 +1163,57 @@ class Recordings:
         stride = int(out.stride(0)) if det.channels > 1 else int(out.shape[1])
         check(fn(self._h, src.data_ptr(), off.ctypes.data_as(_abi.c_int64_p), stp.ctypes.data_as(_abi.c_int32_p), n.ctypes.data_as(_abi.c_int64_p),
                  rates.ctypes.data_as(_abi.c_double_p), z, b, r, out.data_ptr(), stride, det._stream_ptr(stream)))
+        return out
+
+    def _pcm_args(self, src, byteOffsets, byteSteps, formats, out):
+        torch = _torch()
+        det = self.detector
+        if not (src.is_cuda and src.dim() == 1 and src.is_contiguous() and src.dtype == torch.uint8 and src.device.index == det.device):
+            raise ValueError("src must be a contiguous 1-D uint8 CUDA tensor on the detector's device")
+        off = np.ascontiguousarray(byteOffsets, dtype=np.int64).reshape(-1)
+        fmt = np.ascontiguousarray(formats, dtype=np.int32).reshape(-1)
+        if fmt.size != self.count or off.size != self.count:
+            raise ValueError("one byte offset and format (and byte step) per recording")
+        stp = (np.array([pcmSampleBytes(f) for f in fmt], np.int32) if byteSteps is None
+               else np.ascontiguousarray(byteSteps, dtype=np.int32).reshape(-1))
+        if stp.size != self.count:
+            raise ValueError("one byte offset and format (and byte step) per recording")
+        if out is None:
+            out = torch.empty((det.channels, self.rowSamples), dtype=torch.float32, device=src.device)
+        elif not (out.is_cuda and out.dtype == torch.float32 and out.dim() == 2 and out.shape[0] == det.channels and out.shape[1] >= self.rowSamples
+                  and out.stride(1) == 1 and out.device == src.device):
+            raise ValueError("out must be float32 [channels, >= rowSamples] on src's device, rows contiguous")
+        stride = int(out.stride(0)) if det.channels > 1 else int(out.shape[1])
+        return off, stp, fmt, out, stride
+
+    def loadPCM(self, src, byteOffsets, byteSteps, formats, out=None, stream=None):
+        """load() from the files' own bytes (syldet_recordings_load_pcm_device): `src` a 1-D uint8 CUDA tensor, sample i of recording
+        k the formats[k] value (PCM_U8 ... PCM_F64) at byte byteOffsets[k] + i * byteSteps[k] (byteSteps None: contiguous
+        recordings; a step of tracks * sample bytes takes one track of an interleaved file).  Returns float32 rows [C, rowSamples]
+        with the bits load() gives on pcmDecode's float32 of the same bytes; what the library refuses (an unknown format, a step
+        below a sample, a misaligned S16 / S32 / F32 / F64 address, samples beyond src) raises SyllableDetectorError before the
+        rows are touched.  One launch; the same layout again makes it a launch only."""
+        off, stp, fmt, out, stride = self._pcm_args(src, byteOffsets, byteSteps, formats, out)
+        check(_abi.lib.syldet_recordings_load_pcm_device(self._h, src.data_ptr(), int(src.numel()), off.ctypes.data_as(_abi.c_int64_p),
+                                                         stp.ctypes.data_as(_abi.c_int32_p), fmt.ctypes.data_as(_abi.c_int32_p), out.data_ptr(), stride,
+                                                         self.detector._stream_ptr(stream)))
+        return out
+
+    def loadSincPCM(self, src, byteOffsets, byteSteps, formats, sourceSamples, sourceRates, zeroCrossings=None, beta=None, rolloff=None, out=None,
+                    stream=None):
+        """loadSinc() from the files' own bytes (syldet_recordings_load_sinc_pcm_device): the layout of loadPCM, recording k with
+        sourceSamples[k] samples at sourceRates[k]; the bits of loadSinc() on pcmDecode's float32 of the same bytes."""
+        from .resampler import _sinc_quality
+        off, stp, fmt, out, stride = self._pcm_args(src, byteOffsets, byteSteps, formats, out)
+        n = np.ascontiguousarray(sourceSamples, dtype=np.int64).reshape(-1)
+        rates = np.ascontiguousarray(sourceRates, dtype=np.float64).reshape(-1)
+        if n.size != self.count or rates.size != self.count:
+            raise ValueError("one length and rate per recording")
+        z, b, r = _sinc_quality(zeroCrossings, beta, rolloff)
+        check(_abi.lib.syldet_recordings_load_sinc_pcm_device(self._h, src.data_ptr(), int(src.numel()), off.ctypes.data_as(_abi.c_int64_p),
+                                                              stp.ctypes.data_as(_abi.c_int32_p), fmt.ctypes.data_as(_abi.c_int32_p),
+                                                              n.ctypes.data_as(_abi.c_int64_p), rates.ctypes.data_as(_abi.c_double_p), z, b, r,
+                                                              out.data_ptr(), stride, self.detector._stream_ptr(stream)))
         return out
 
     def view(self, tensor, k: int):
