@@ -809,6 +809,10 @@ int syldet_sinc_resampler_flush(syldet_sinc_resampler_t *r, float *out, int64_t 
  * the values it would have had alone -- bit for bit on the fold kernel, the generic engine and the 1024-point kernel; the
  * pass-scaled fused kernels and the wide engine keep their 1e-5 (1e-2) contract, not bit identity (their scale is per pass).
  * Row evaluations outside every [first_eval, first_eval + n_evals) straddle two recordings or a pad and mean nothing.
+ * THE COLUMNS follow the same rule (frame j reads samples [j hop, j hop + gap + W) of its row): syldet_spectrogram_device on the
+ * packed rows gives recording k's columns at row frames [first_eval, first_eval + syldet_count_frames(h, n_k)), with the values
+ * syldet_spectrogram_device gives on that recording alone -- bit for bit on the fold kernel and the generic engine; row frames
+ * outside those ranges straddle two recordings or a pad.
  * THE PLAN (host only, no device is touched), for K recordings of n_samples[k] samples on the C channels of h:
  *   P_k       = ceil(n_k / hop) hop                        the padded length
  *   n_evals_k = max(0, syldet_count_evals(h, n_k))
@@ -1151,6 +1155,98 @@ int syldet_score_host(const float *values, int64_t n_evals, int64_t value_stride
                       int64_t debounce_frames, int64_t *table);
 int syldet_score_choose(const int64_t *table, int32_t n_detectors, int32_t n_thresholds, const int64_t *n_labels,
                         double false_positive_cost, int32_t *best, int64_t *totals, double *costs);
+
+/* ---- event-aligned windows: spectrogram, output and audio at each event ----
+ * The figure a lab draws to judge a detector is the aligned stack: the spectrogram around every detection (or every label), one
+ * window an event, their mean (a sharp mean is low jitter), and the same stack of the network's output.  The reference has no
+ * counterpart; the arrays it would be cut from -- columns, outputs, samples -- are on the device already, and these calls cut
+ * every event's window out of them in one launch, for a bank's channels or for all recordings of a packed plan.  THE CONVENTION
+ * is the library's own (as the meters' and the scorer's):
+ * A DETECTOR is a channel of a bank, or a recording of a packed-recordings handle (the scorer's definition).
+ * An EVENT is any int64 sample number s counted from the detector's own start, |s| < 2^62: a detection index of
+ *   syldet_detections_device or syldet_recordings_events_device, a label, anything else -- in any order, repeated, before 0 or
+ *   behind the detector's end.
+ * A SOURCE is one of three arrays that lie on the device, each of `width` floats a UNIT, with the anchor rule
+ *   u0 = floor((s - origin) / step)   (a floor also for a negative numerator):
+ *     source                array                                                      unit        width  origin      step  a detector's units U_d
+ *     SYLDET_ALIGN_COLUMNS  [C][n_frames][bins] as syldet_spectrogram_device wrote it  frame       bins   gap + W     hop   syldet_count_frames of its samples
+ *     SYLDET_ALIGN_OUTPUTS  [C][n_evals][n_out] as syldet_run_device* wrote it         evaluation  n_out  first_index hop   its n_evals
+ *     SYLDET_ALIGN_SAMPLES  fp32 rows [C][channel_stride]                              sample      1      0           1     its n_samples
+ *   For a detection s = first_index + e hop the anchor evaluation is e and the anchor frame is e + T - 1, the newest column the
+ *   network saw: with before = T - 1, after = 0 a COLUMNS window is exactly the network's input in spectrogram values.
+ *   (A channel of a bank has the n_units of the call; a recording its own part of its row.)
+ * THE WINDOW of an event is the units u0 - before .. u0 + after, n = before + after + 1 of them; 0 <= before, after and
+ *   n width <= SYLDET_ALIGN_MAX_WINDOW.  An element whose unit lies in [0, U_d) of its own detector is PRESENT and is a bit copy
+ *   of the source; every other element is the caller's `fill` float (NaN, 0, ...).  For a packed recording with slot sl, unit u is
+ *   unit sl.first_eval + u of row sl.row for COLUMNS and OUTPUTS, and sample sl.offset + u of it for SAMPLES: frames and
+ *   evaluations between two recordings, pads and the next recording of the row are never read.
+ * THE RESULT is d_windows [N][n][width] fp32; detector d's j-th event is window event_begin[d] + j.  event_begin is a host array of
+ *   D + 1 entries, from 0 and not decreasing (as the scorer's label_begin), N = event_begin[D].  The events are on the device, at
+ *   d_events[d event_stride + j] -- the [D][capacity] tables of the detection calls as they are -- or, with event_stride == 0,
+ *   flat at d_events[event_begin[d] + j].  Every element of d_windows is written exactly once, nothing behind N n width.
+ * STACK STATISTICS.  group [D] (host, int32, 0 <= g < G) puts every detector on a stack.  A group's events are ordered by detector
+ *   ascending, then event index ascending, and numbered i = 0, 1, ...  For every position p of the n width elements:
+ *     count[g][p]   int64: the events of the group whose element p is present (by the window rule, whatever the value or the fill)
+ *     sum[g][p], sumsq[g][p]   fp64, over those events IN BLOCKS OF SYLDET_ALIGN_BLOCK CONSECUTIVE i: inside a block the values
+ *                   (their squares, taken in fp64: exact for an fp32 value, so a fused multiply-add changes nothing) are added one
+ *                   after another in order, from +0.0; the blocks' results are added one after another in block order, from +0.0.
+ *                   Absent elements add nothing; NaN propagates.
+ *   A fixed tree: device, host and any model of the above agree to the bit.  Mean and variance are the caller's divisions.
+ *   syldet_aligner_create    h: the bank; r: NULL (D = its channels) or a packed-recordings handle of h (D = its recordings).
+ *       Everything is validated before any device is touched; for recordings the slots' (row, first unit, units) are uploaded
+ *       once.  h, and r if given, must outlive the aligner.
+ *   syldet_aligner_shape     D, n and width
+ *   syldet_align_anchor      host only: origin, step and width of a source on h (each may be NULL)
+ *   syldet_align_device      d_src: the source array, n_units units a row (with r: the rows' row_evals for OUTPUTS,
+ *       syldet_count_frames(h, row_samples) for COLUMNS, row_samples for SAMPLES), rows row_stride ELEMENTS apart (0: n_units
+ *       width; for SAMPLES the channel_stride).  One launch ("align_windows_kernel": a window is one contiguous span of the source
+ *       copied to one contiguous span of d_windows with fill on either side -- csrc/align_span.hpp, one text for the kernel, the host
+ *       and a stand-alone test; a wave takes a short window, a workgroup a long one; 16 bytes a lane where the destination's
+ *       address allows, element by element at its ends and at the clipped ends of the span).
+ *   syldet_align_stats_device   the statistics of the windows the aligner's LAST syldet_align_device call wrote (d_windows: that
+ *       call's result, event_begin: that call's -- anything else is SYLDET_ERR_INVALID_ARGUMENT; the kernel left each window's
+ *       present span with the aligner, which is what `count` goes by; only event_begin can be compared: a second windows call with
+ *       the same event_begin but other events, another source or n_units replaces the spans, and statistics of the FIRST call's
+ *       d_windows would then go by the wrong spans without a status -- take the statistics before the next windows call).  d_count, d_sum, d_sumsq [G][n][width].  Two launches
+ *       ("align_stats_kernel": a thread owns a position of one block of a group and walks its windows in order;
+ *       "align_combine_kernel": a group's blocks in order).
+ *   syldet_align_host        host only, one detector in plain C++ (the text the kernel runs): src holds the detector's n_units
+ *       units; windows [n_events][n][width]; present [n_events][2], may be NULL: each window's first present ELEMENT and the number
+ *       of present elements.  origin in [0, 2^32), step in [1, 2^31).
+ *   syldet_align_stats_host  host only, one group: the block tree over n_events windows of window_elements elements in the order
+ *       given, present as syldet_align_host wrote it; count, sum, sumsq [window_elements].
+ * Statuses, decided before any device is touched.  SYLDET_ERR_INVALID_ARGUMENT: a NULL handle or pointer (the device arrays may be
+ * NULL where there is no event, d_src where n_units is 0), an unknown source, a negative before or after, a window above the limit, a wrong n_units with r,
+ * a row_stride smaller than a row needs, an event_begin that does not start at 0 or that decreases, an event_stride that is not 0
+ * and is smaller than a detector's event count, a group outside [0, G), G < 1.  SYLDET_ERR_UNSUPPORTED: COLUMNS on a mixed bank
+ * of more than one class, as syldet_spectrogram* answers there (OUTPUTS and SAMPLES work on every kind of bank); more than
+ * 2^31 - 1 windows or 2^40 window elements in one call.  A sharded bank
+ * has none: no entry point takes one, and the language bindings answer SYLDET_ERR_UNSUPPORTED.
+ * THE LAUNCH RULE is that of the recordings' load sources: the aligner keeps event_begin and, for the statistics, the group order
+ * on the device.  A call whose host arrays differ from the kept ones (the first always) waits for the stream of the aligner's last
+ * call, sizes what depends on them -- the spans [N], the order [N], the blocks' partials, scratch the aligner keeps and grows --
+ * and uploads them with one blocking copy; the same arrays again are launches only: no allocation, no synchronisation, no copy.
+ * One stream at a time, as the bank; every call records into the profile of h (syldet_profile), so the bank's rule of one caller
+ * at a time covers the aligner too.                                                                                            */
+#define SYLDET_ALIGN_COLUMNS    0
+#define SYLDET_ALIGN_OUTPUTS    1
+#define SYLDET_ALIGN_SAMPLES    2
+#define SYLDET_ALIGN_MAX_WINDOW 1048576
+#define SYLDET_ALIGN_BLOCK      256
+typedef struct syldet_aligner syldet_aligner_t;
+int syldet_aligner_create(const syldet_t *h, const syldet_recordings_t *r, int32_t source, int64_t before, int64_t after,
+                          syldet_aligner_t **out);
+int syldet_aligner_destroy(syldet_aligner_t *a);
+int syldet_aligner_shape(const syldet_aligner_t *a, int32_t *n_detectors, int64_t *n_units_per_window, int32_t *width);
+int syldet_align_anchor(const syldet_t *h, int32_t source, int64_t *origin, int64_t *step, int32_t *width);
+int syldet_align_device(syldet_aligner_t *a, const float *d_src, int64_t n_units, int64_t row_stride, const int64_t *d_events,
+                        int64_t event_stride, const int64_t *event_begin, float fill, float *d_windows, void *hip_stream);
+int syldet_align_stats_device(syldet_aligner_t *a, const float *d_windows, const int64_t *event_begin, const int32_t *group,
+                              int32_t n_groups, int64_t *d_count, double *d_sum, double *d_sumsq, void *hip_stream);
+int syldet_align_host(const float *src, int64_t n_units, int32_t width, int64_t origin, int64_t step, int64_t before, int64_t after,
+                      const int64_t *events, int64_t n_events, float fill, float *windows, int64_t *present);
+int syldet_align_stats_host(const float *windows, const int64_t *present, int64_t n_events, int64_t window_elements, int64_t *count,
+                            double *sum, double *sumsq);
 
 #ifdef __cplusplus
 }

@@ -10,8 +10,8 @@ from .config import (InvalidValue, MismatchedLength, MissingValue, NeuralNet, Ne
                      ProcessingFunction, SyllableDetectorConfig, SyllableDetectorError, UnableToOpenPath,
                      createWindow, frequencyIndexRange)
 from .bank import PinnedArray, ShardedSyllableDetectorBank, shard_table
-from ._abi import PCM_F32, PCM_F64, PCM_S16, PCM_S24, PCM_S32, PCM_U8
-from .detector import (PCM24, Recordings, Scorer, SyllableDetector, chooseThreshold, configsCompatible, configsShareClock, fusedFormOfConfig,
+from ._abi import ALIGN_COLUMNS, ALIGN_OUTPUTS, ALIGN_SAMPLES, PCM_F32, PCM_F64, PCM_S16, PCM_S24, PCM_S32, PCM_U8
+from .detector import (PCM24, Aligner, Recordings, Scorer, SyllableDetector, alignHost, alignStatsHost, chooseThreshold, configsCompatible, configsShareClock, fusedFormOfConfig,
                        pcmDecode, pcmSampleBytes, planRecordings, recordingLengths, scoreHost)
 from .resampler import ResamplerLinear, ResamplerSinc, sincReady, convertRate, deinterleave, sincCoefficient, sincDefaults, sincTaps
 
@@ -21,4 +21,5 @@ __all__ = ["SyllableDetector", "SyllableDetectorConfig", "NeuralNet", "NeuralNet
            "convertRate", "ResamplerSinc", "sincReady", "sincCoefficient", "sincTaps", "sincDefaults",
            "ShardedSyllableDetectorBank", "PinnedArray", "shard_table", "configsCompatible",
            "configsShareClock", "fusedFormOfConfig", "Recordings", "planRecordings", "recordingLengths", "Scorer", "scoreHost", "chooseThreshold",
-           "PCM_U8", "PCM_S16", "PCM_S24", "PCM_S32", "PCM_F32", "PCM_F64", "PCM24", "pcmDecode", "pcmSampleBytes"]
+           "PCM_U8", "PCM_S16", "PCM_S24", "PCM_S32", "PCM_F32", "PCM_F64", "PCM24", "pcmDecode", "pcmSampleBytes",
+           "Aligner", "alignHost", "alignStatsHost", "ALIGN_COLUMNS", "ALIGN_OUTPUTS", "ALIGN_SAMPLES"]

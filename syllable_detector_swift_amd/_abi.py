@@ -98,6 +98,11 @@ SCORE_COLUMNS = 6
 SCORE_MAX_THRESHOLDS = 4096
 SCORE_MAX_TOLERANCE = 1 << 20
 
+# sources of event-aligned windows (SYLDET_ALIGN_*)
+ALIGN_COLUMNS, ALIGN_OUTPUTS, ALIGN_SAMPLES = 0, 1, 2
+ALIGN_MAX_WINDOW = 1 << 20
+ALIGN_BLOCK = 256
+
 Handle = C.c_void_p
 Config_p = C.POINTER(Config)
 c_void_pp = C.POINTER(C.c_void_p)
@@ -278,6 +283,15 @@ SIGNATURES = {
     "syldet_score_host": (C.c_int, [c_float_p, C.c_int64, C.c_int64, c_double_p, C.c_int32, c_int64_p, C.c_int64, C.c_int64, C.c_int64, C.c_int64,
                                     C.c_int64, c_int64_p]),
     "syldet_score_choose": (C.c_int, [c_int64_p, C.c_int32, C.c_int32, c_int64_p, C.c_double, c_int32_p, c_int64_p, c_double_p]),
+    "syldet_aligner_create": (C.c_int, [Handle, Handle, C.c_int32, C.c_int64, C.c_int64, C.POINTER(Handle)]),
+    "syldet_aligner_destroy": (C.c_int, [Handle]),
+    "syldet_aligner_shape": (C.c_int, [Handle, c_int32_p, c_int64_p, c_int32_p]),
+    "syldet_align_anchor": (C.c_int, [Handle, C.c_int32, c_int64_p, c_int64_p, c_int32_p]),
+    "syldet_align_device": (C.c_int, [Handle, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_int64, c_int64_p, C.c_float, C.c_void_p, C.c_void_p]),
+    "syldet_align_stats_device": (C.c_int, [Handle, C.c_void_p, c_int64_p, c_int32_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "syldet_align_host": (C.c_int, [c_float_p, C.c_int64, C.c_int32, C.c_int64, C.c_int64, C.c_int64, C.c_int64, c_int64_p, C.c_int64, C.c_float,
+                                    c_float_p, c_int64_p]),
+    "syldet_align_stats_host": (C.c_int, [c_float_p, c_int64_p, C.c_int64, C.c_int64, c_int64_p, c_double_p, c_double_p]),
 }
 
 

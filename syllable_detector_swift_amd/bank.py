@@ -56,6 +56,11 @@ class ShardedSyllableDetectorBank:
         from .config import SyllableDetectorError
         raise SyllableDetectorError(_abi.ERR_UNSUPPORTED, "packed recordings on a sharded bank: use a SyllableDetector per device")
 
+    def aligner(self, source, before: int, after: int):
+        """Event-aligned windows (SyllableDetector.aligner) have no sharded form: the source arrays lie on several devices."""
+        from .config import SyllableDetectorError
+        raise SyllableDetectorError(_abi.ERR_UNSUPPORTED, "event-aligned windows on a sharded bank: use a SyllableDetector per device")
+
     def __del__(self):
         try:
             self.close()

@@ -47,7 +47,7 @@ constexpr int kExUsage = 64;   // EX_USAGE, main.swift:40
 void usage(FILE *to)
 {
     std::fprintf(to,
-                 "Usage: syllable-detector-cli -n <net> [-a <audio>]... [-d <seconds>] [--device <k>] [--chunk <frames>] [--format <shortest|swift4>] [--resample <linear|sinc>] [--resample-quality <Z,beta,rolloff>] [--simulate <out.wav>] [--simulate-output <k>] [--levels <out.tsv>] [--levels-buffer <L>] [--levels-period <seconds>] [--ttl <out.wav>] [--ttl-mux] [--ttl-width <seconds>] [--ttl-steps <n>] [--ttl-buffer <L>] [--ttl-latency <seconds>] [--ttl-onsets <out.tsv>] [--simulate-dir <dir>] [--ttl-dir <dir>] [--ttl-onsets-dir <dir>] [--batch] [--batch-rows <N>] [--batch-bytes <B>] [--score <labels.tsv> --score-out <table.tsv>] [--score-thresholds <lo:hi:n>] [--score-tolerance <seconds>] [--score-cost <c>] [--score-output <k>] [--probe]\n"
+                 "Usage: syllable-detector-cli -n <net> [-a <audio>]... [-d <seconds>] [--device <k>] [--chunk <frames>] [--format <shortest|swift4>] [--resample <linear|sinc>] [--resample-quality <Z,beta,rolloff>] [--simulate <out.wav>] [--simulate-output <k>] [--levels <out.tsv>] [--levels-buffer <L>] [--levels-period <seconds>] [--ttl <out.wav>] [--ttl-mux] [--ttl-width <seconds>] [--ttl-steps <n>] [--ttl-buffer <L>] [--ttl-latency <seconds>] [--ttl-onsets <out.tsv>] [--simulate-dir <dir>] [--ttl-dir <dir>] [--ttl-onsets-dir <dir>] [--batch] [--batch-rows <N>] [--batch-bytes <B>] [--score <labels.tsv> --score-out <table.tsv>] [--score-thresholds <lo:hi:n>] [--score-tolerance <seconds>] [--score-cost <c>] [--score-output <k>] [--align-dir <dir>] [--align <columns|outputs|samples>] [--align-at <detections|labels>] [--align-before <units>] [--align-after <units>] [--probe]\n"
                  "  -n, --net <net>:\n      Path to trained network file.  Given k > 1 times: each file must have exactly k tracks, and track t runs network t (one mixed bank; the networks must share the sampling rate, window length, window overlap, time range and number of outputs).\n"
                  "  -a, --audio <audio>:\n      Path to the audio file to process.\n"
                  "  -d, --debounce <seconds>:\n      Number of seconds to debounce triggers.\n"
@@ -72,13 +72,17 @@ void usage(FILE *to)
                  "      --simulate-dir <dir>, --ttl-dir <dir>, --ttl-onsets-dir <dir>:\n      --simulate, --ttl and --ttl-onsets for any number of audio files, with or without --batch: for an audio file p the file written is <dir>/<the file name of p> (the onsets: that name with .tsv behind it), exactly what the option for one file writes for p alone. The directory is made if it is not there; two audio files of the same name are refused. Under --batch a batch's tracks are made on the GPU in one pass and come back in one download per product.\n"
                  "      --batch:\n      Run the audio files through one detector bank instead of one bank a file: every track of every file becomes a recording in the bank's rows, and only the detections come back from the GPU. The output is the same. A file at another sampling rate than the network's joins the bank under --resample sinc (its rate within a sixteenth and sixteen times the network's): it is converted as the rows load, and a batch that holds such a file runs as 32-bit float. Under --resample linear (the default), or outside that range, such a file ends the batch and runs alone, as without --batch.\n"
                  "      --batch-rows <N>:\n      Rows of the bank under --batch (default 64; no more than there are tracks).\n"
-                 "      --batch-bytes <B>:\n      Consecutive files share a batch until their samples pass B bytes (default 2147483648); a file that is converted counts with the bytes it has at its own rate. Each track product (--simulate-dir, --ttl-dir) adds 2 bytes per sample at the network's rate to what a batch holds on the device.\n"
+                 "      --batch-bytes <B>:\n      Consecutive files share a batch until their samples pass B bytes (default 2147483648); a file that is converted counts with the bytes it has at its own rate. Each track product (--simulate-dir, --ttl-dir) adds 2 bytes per sample at the network's rate to what a batch holds on the device; what --align-dir is cut from counts towards B (see there).\n"
                  "      --score <labels.tsv>:\n      Under --batch, also score every track against labelled times for a grid of candidate thresholds: lines of file, track and sample, tab separated (the file as -a names it, the sample counted from the file's start at the network's sampling rate, also for a file at another rate). A file that does not go through the bank (see --batch) is left out, with a message. Needs --score-out.\n"
                  "      --score-out <table.tsv>:\n      Where --score writes its table, one line per threshold, tab separated: threshold, detections, hits, misses, false positives, repeats, the mean and the standard deviation of the hits' offsets in samples, the cost; a last line names the threshold of the smallest cost.\n"
                  "      --score-thresholds <lo:hi:n>:\n      The grid: n thresholds from lo to hi (default 0:1:101; at most 4096).\n"
                  "      --score-tolerance <seconds>:\n      A detection this close to a label is a hit (default 0.02).\n"
                  "      --score-cost <c>:\n      The cost of a false positive or a repeat; a miss costs 1 (default 1).\n"
                  "      --score-output <k>:\n      The network output --score compares with the thresholds (default 0).\n"
+                 "      --align-dir <dir>:\n      Also write, for every audio file p, the windows of a source around every event of every track: <dir>/<the file name of p>.npy (NumPy format 1.0, little-endian float32, shape [events][units][width], all tracks' events in track order; elements outside the track are NaN) and <dir>/<that name>.tsv (one line per window: track, sample, seconds); and behind the last file <dir>/count.npy (int64), <dir>/sum.npy and <dir>/sumsq.npy (float64), shape [networks][units][width]: per position the number of windows that hold it and the sums of their values and squares, one stack per -n network over all files in command-line order. With or without --batch, the same bytes. Under --batch what the windows are cut from counts towards --batch-bytes: 4 + 4 x bins / hop bytes per sample for the columns (4.88 for the example network: the fp32 rows and their columns), 4 for the samples, nothing for the outputs.\n"
+                 "      --align <columns|outputs|samples>:\n      What the windows are cut from: the spectrogram's columns (default; a unit is a frame of the band's bins), the network's outputs (a unit is an evaluation) or the samples at the network's rate.\n"
+                 "      --align-at <detections|labels>:\n      The events: the detections that are printed (default), or the labelled samples of the file given with --score (which then needs neither --batch nor --score-out).\n"
+                 "      --align-before <units>, --align-after <units>:\n      Units of the source in front of and behind the event's own unit (default: the network's time range less one, each; with --align columns --align-before <time range - 1> --align-after 0 a detection's window is the network's input).\n"
                  "      --probe:\n      Only print what the audio files contain; does not touch the GPU.\n"
                  "The command line will write a comma-separated list of detection events (when the network has at least one output above threshold) to standard out. For example, it might output:\n"
                  "\n\t0,1593298,36.1292063492063,0.918557\n\n"
@@ -194,6 +198,180 @@ struct ResampleOpt {
     double beta = 0.0, rolloff = 0.0;
 };
 
+// --align-dir: event-aligned windows (syldet_aligner_*, syldet_align_device): for every audio file the units of a source around
+// every detection (or label) of every track, one window an event, as <dir>/<name>.npy with <name>.tsv beside it; and, over all files
+// in command-line order, the stack statistics of every network's events as <dir>/count.npy, sum.npy and sumsq.npy.  The stacks are
+// added on the host in the library's tree (blocks of SYLDET_ALIGN_BLOCK events through syldet_align_stats_host, the blocks in
+// order), fed file by file, so that they do not depend on how the files were batched.
+struct AlignOpt {
+    std::string dir;                                       // empty: none
+    int source = SYLDET_ALIGN_COLUMNS;
+    bool at_labels = false;
+    long before = -1, after = -1;                          // < 0: timeRange - 1
+};
+
+struct AlignRun {
+    AlignOpt opt;
+    const std::map<std::string, std::map<long, std::vector<int64_t>>> *labels = nullptr;   // --align-at labels: --score's file
+    int64_t before = 0, after = 0, n = 0;
+    int width = 1, networks = 1;
+    struct Stack {
+        std::vector<int64_t> count;
+        std::vector<double> sum, sumsq;
+        std::vector<float> block;                          // the windows of the block being gathered
+        std::vector<int64_t> present;
+        int64_t held = 0;
+    };
+    std::vector<Stack> stacks;
+    bool failed = false;
+    int64_t L() const { return n * width; }
+};
+AlignRun *g_align = nullptr;                               // --align-dir was given
+
+// NumPy format 1.0, little endian, C order
+bool write_npy(const std::string &path, const char *descr, const std::vector<int64_t> &shape, const void *data, size_t bytes)
+{
+    std::string dict = std::string("{'descr': '") + descr + "', 'fortran_order': False, 'shape': (";
+    for (size_t i = 0; i < shape.size(); i++) dict += std::to_string(shape[i]) + (shape.size() == 1 || i + 1 < shape.size() ? "," : "") + (i + 1 < shape.size() ? " " : "");
+    dict += "), }";
+    while ((10 + dict.size() + 1) % 64 != 0) dict += ' ';
+    dict += '\n';
+    FILE *f = std::fopen(path.c_str(), "wb");
+    if (!f) return false;
+    const unsigned char head[10] = {0x93, 'N', 'U', 'M', 'P', 'Y', 1, 0, (unsigned char)(dict.size() & 255), (unsigned char)(dict.size() >> 8)};
+    bool ok = std::fwrite(head, 1, 10, f) == 10 && std::fwrite(dict.data(), 1, dict.size(), f) == dict.size() && (bytes == 0 || std::fwrite(data, 1, bytes, f) == bytes);
+    if (std::fclose(f) != 0) ok = false;
+    return ok;
+}
+
+// one block of a stack into its totals: the block alone through the library's tree (one block: its own sums), then total + block
+void align_flush(AlignRun &run, AlignRun::Stack &st)
+{
+    if (st.held == 0) return;
+    const size_t L = (size_t)run.L();
+    std::vector<int64_t> c(L);
+    std::vector<double> s(L), q(L);
+    if (syldet_align_stats_host(st.block.data(), st.present.data(), st.held, (int64_t)L, c.data(), s.data(), q.data())) {
+        std::fprintf(stderr, "Unable to add the aligned windows: %s: %s\n", syldet_strerror(SYLDET_ERR_INVALID_ARGUMENT), syldet_last_error());
+        run.failed = true;
+    }
+    for (size_t p = 0; p < L; p++) {
+        st.count[p] += c[p];
+        st.sum[p] = st.sum[p] + s[p];
+        st.sumsq[p] = st.sumsq[p] + q[p];
+    }
+    st.held = 0;
+}
+
+// The windows of one bank's detectors -- a batch's recordings (r), or a file's tracks (r NULL) -- in one launch, and back: windows
+// [N][n][width] with detector d's events from begin[d].  d_src: the source on the device, n_units units a row.
+bool align_windows(AlignRun &run, syldet_t *h, syldet_recordings_t *r, const float *d_src, int64_t n_units, int64_t row_stride,
+                   const std::vector<std::vector<int64_t>> &events, hipStream_t stream, std::vector<float> &windows, std::vector<int64_t> &begin)
+{
+    begin.assign(1, 0);
+    std::vector<int64_t> flat;
+    for (const std::vector<int64_t> &e : events) {
+        flat.insert(flat.end(), e.begin(), e.end());
+        begin.push_back((int64_t)flat.size());
+    }
+    const int64_t N = begin.back();
+    windows.assign((size_t)N * (size_t)run.L(), 0.0f);
+    syldet_aligner_t *a = nullptr;
+    int st = syldet_aligner_create(h, r, run.opt.source, run.before, run.after, &a);
+    DevBuf d_events, d_windows;
+    bool ok = true;
+    if (!st && N > 0) {
+        ok = d_events.alloc(flat.size() * sizeof(int64_t)) && d_windows.alloc(windows.size() * sizeof(float)) &&
+             hipMemcpyAsync(d_events.p, flat.data(), flat.size() * sizeof(int64_t), hipMemcpyHostToDevice, stream) == hipSuccess;
+        if (ok) st = syldet_align_device(a, d_src, n_units, row_stride, (const int64_t *)d_events.p, 0, begin.data(), std::nanf(""), (float *)d_windows.p, stream);
+        if (ok && !st) ok = hipMemcpyAsync(windows.data(), d_windows.p, windows.size() * sizeof(float), hipMemcpyDeviceToHost, stream) == hipSuccess;
+    }
+    if (ok && hipStreamSynchronize(stream) != hipSuccess) ok = false;
+    syldet_aligner_destroy(a);
+    if (st) std::fprintf(stderr, "Unable to align the events: %s: %s\n", syldet_strerror(st), syldet_last_error());
+    return ok && st == 0;
+}
+
+// One audio file's windows and their table, and its events into the networks' stacks: track by track, event by event.  units[t]:
+// the units of the source that track t has (what decides which elements of a window are present).  0, or 3: a file is not written.
+int align_write_file(AlignRun &run, const std::string &path, const std::vector<std::vector<int64_t>> &events, const std::vector<int64_t> &units,
+                     const float *windows, int64_t origin, int64_t step, double rate)
+{
+    const int64_t L = run.L();
+    int64_t N = 0;
+    for (const std::vector<int64_t> &e : events) N += (int64_t)e.size();
+    const std::string npy = TrackDirs::in(run.opt.dir, path, ".npy"), tsv = TrackDirs::in(run.opt.dir, path, ".tsv");
+    int bad = 0;
+    if (!write_npy(npy, "<f4", {N, run.n, (int64_t)run.width}, windows, (size_t)N * (size_t)L * sizeof(float))) {
+        std::fprintf(stderr, "Unable to write %s.\n", npy.c_str());
+        bad = 3;
+    }
+    FILE *f = std::fopen(tsv.c_str(), "w");
+    bool ok = f != nullptr;
+    int64_t w = 0;
+    for (size_t t = 0; t < events.size(); t++) {
+        AlignRun::Stack &st = run.stacks[run.networks > 1 ? t % (size_t)run.networks : 0];
+        for (const int64_t s : events[t]) {
+            if (ok) ok = std::fputs((std::to_string(t) + "\t" + std::to_string(s) + "\t" + number((double)s / rate) + "\n").c_str(), f) >= 0;
+            // the present elements of the window: the units u0 - before .. u0 + after that lie in [0, units) (include/syldet.h)
+            const int64_t c = s < -(((int64_t)1 << 62) - 1) ? -(((int64_t)1 << 62) - 1) : s > ((int64_t)1 << 62) - 1 ? ((int64_t)1 << 62) - 1 : s;
+            int64_t u0 = (c - origin) / step;
+            if (u0 * step > c - origin) u0--;                // a floor, also for a negative numerator
+            const int64_t lo = u0 - run.before, first = std::max<int64_t>(lo, 0), last = std::min<int64_t>(u0 + run.after, units[t] - 1);
+            st.block.insert(st.block.end(), windows + w * L, windows + (w + 1) * L);
+            st.present.push_back(last >= first ? (first - lo) * run.width : 0);
+            st.present.push_back(last >= first ? (last - first + 1) * run.width : 0);
+            w++;
+            if (++st.held == SYLDET_ALIGN_BLOCK) {
+                align_flush(run, st);
+                st.block.clear();
+                st.present.clear();
+            }
+        }
+    }
+    if (f && std::fclose(f) != 0) ok = false;
+    if (!ok) {
+        std::fprintf(stderr, "Unable to write %s.\n", tsv.c_str());
+        bad = 3;
+    }
+    return bad;
+}
+
+// the three stack files, behind the last audio file
+bool align_finish(AlignRun &run)
+{
+    const size_t L = (size_t)run.L();
+    std::vector<int64_t> count;
+    std::vector<double> sum, sumsq;
+    for (AlignRun::Stack &st : run.stacks) {
+        align_flush(run, st);
+        count.insert(count.end(), st.count.begin(), st.count.end());
+        sum.insert(sum.end(), st.sum.begin(), st.sum.end());
+        sumsq.insert(sumsq.end(), st.sumsq.begin(), st.sumsq.end());
+    }
+    const std::vector<int64_t> shape = {(int64_t)run.networks, run.n, (int64_t)run.width};
+    bool ok = !run.failed;
+    for (int i = 0; i < 3; i++) {
+        const std::string path = run.opt.dir + (i == 0 ? "/count.npy" : i == 1 ? "/sum.npy" : "/sumsq.npy");
+        const void *data = i == 0 ? (const void *)count.data() : i == 1 ? (const void *)sum.data() : (const void *)sumsq.data();
+        if (!write_npy(path, i == 0 ? "<i8" : "<f8", shape, data, L * run.stacks.size() * 8)) {
+            std::fprintf(stderr, "Unable to write %s.\n", path.c_str());
+            ok = false;
+        }
+    }
+    return ok;
+}
+
+// the events --align-at names for one track of one file: its labels (--score's file), or the detections given
+std::vector<int64_t> align_events_of(const AlignRun &run, const std::string &path, int track, const std::vector<int64_t> &detections)
+{
+    if (!run.opt.at_labels) return detections;
+    const auto of_file = run.labels->find(path);
+    if (of_file == run.labels->end()) return {};
+    const auto of_track = of_file->second.find(track);
+    return of_track == of_file->second.end() ? std::vector<int64_t>() : of_track->second;
+}
+
 // cfgs: one network for every track, or (k > 1) network t for track t of a file of exactly k tracks, through one mixed bank
 // (syldet_create_mixed): the networks share the evaluation clock, so the events are found and printed as for one
 // simulate: a path for the Simulator's output track (ViewControllerSimulator.swift:251-344) of every track, made on the device from
@@ -256,6 +434,13 @@ int process_file(const std::string &path, const std::vector<syldet_config_t *> &
     int64_t ttl_cap = 1;
     int64_t lv_P = 1, lv_M = 0;
     int64_t E = 0, fed = 0;
+    // --align-dir: every track's events, their windows, and what decides presence
+    std::vector<std::vector<int64_t>> al_events;
+    std::vector<int64_t> al_units, al_begin;
+    std::vector<float> al_windows;
+    int64_t al_origin = 0, al_step = 1;
+    bool al_made = false;
+    const int64_t debounce_of_file = have_debounce ? (int64_t)(debounce_s * cfg->sampling_rate) : 0;   // Int(newValue * samplingRate), TrackDetector.swift:24
     do {
         if (hipSetDevice(device) != hipSuccess || hipStreamCreate(&stream) != hipSuccess) { rc = 2; break; }
         const int64_t n = info.frames;
@@ -346,9 +531,71 @@ int process_file(const std::string &path, const std::vector<syldet_config_t *> &
             if (st) std::fprintf(stderr, "Unable to make the trigger track of %s: %s: %s\n", path.c_str(), syldet_strerror(st), syldet_last_error());
             return st == 0;
         };
+        // the windows of every track's events (--align-dir), from arrays on the device: the outputs the run left, the fp32 rows the
+        // detector was fed, or their columns (syldet_spectrogram_device).  Behind the download of the flags: the detections are made
+        // from them as below.
+        DevBuf d_al_rows, d_al_cols;
+        auto aligned = [&]() -> bool {
+            if (!g_align) return true;
+            AlignRun &run = *g_align;
+            if (syldet_align_anchor(h, run.opt.source, &al_origin, &al_step, nullptr)) {
+                std::fprintf(stderr, "Unable to align the events of %s: %s: %s\n", path.c_str(), syldet_strerror(SYLDET_ERR_UNSUPPORTED), syldet_last_error());
+                return true;                                // (no files for it: write_files reports them)
+            }
+            al_events.assign((size_t)C, std::vector<int64_t>());
+            for (int c = 0; c < C; c++) {
+                std::vector<int64_t> found;
+                int64_t until = -1;
+                for (int64_t e = 0; !run.opt.at_labels && e < E; e++) {
+                    const int64_t idx = (int64_t)g.first_index + e * (int64_t)g.hop;
+                    if (!flags[(size_t)c * E + e] || !(until < idx)) continue;
+                    until = idx + debounce_of_file;
+                    found.push_back(idx);
+                }
+                al_events[(size_t)c] = align_events_of(run, path, c, found);
+            }
+            const float *rows = nullptr, *src = nullptr;
+            int64_t stride = S, n_units = 0, row_stride = 0;
+            if (run.opt.source != SYLDET_ALIGN_OUTPUTS) {
+                if (resample) {
+                    rows = (const float *)d_res.p;
+                    stride = res_stride;
+                } else {
+                    // the file's tracks as fp32 rows: what the detector was fed (16-bit PCM: x * 2^-15, exact)
+                    std::vector<float> planar((size_t)C * (size_t)S);
+                    for (int64_t i = 0; i < S; i++)
+                        for (int c = 0; c < C; c++)
+                            planar[(size_t)c * (size_t)S + (size_t)i] = raw16 ? (float)frames16[(size_t)i * C + c] * (1.0f / 32768.0f) : frames[(size_t)i * C + c];
+                    if (!d_al_rows.alloc(planar.size() * sizeof(float)) || hipMemcpy(d_al_rows.p, planar.data(), planar.size() * sizeof(float), hipMemcpyHostToDevice) != hipSuccess) return false;
+                    rows = (const float *)d_al_rows.p;
+                }
+            }
+            const int64_t J = std::max<int64_t>(0, syldet_count_frames(h, S));
+            if (run.opt.source == SYLDET_ALIGN_SAMPLES) {
+                src = rows;
+                n_units = S;
+                row_stride = stride;
+            } else if (run.opt.source == SYLDET_ALIGN_COLUMNS) {
+                if (!d_al_cols.alloc((size_t)C * (size_t)J * (size_t)run.width * sizeof(float))) return false;
+                if (J > 0) st = syldet_spectrogram_device(h, rows, S, stride, (float *)d_al_cols.p, stream);
+                if (st) {
+                    std::fprintf(stderr, "Unable to align the events of %s: %s: %s\n", path.c_str(), syldet_strerror(st), syldet_last_error());
+                    return false;
+                }
+                src = (const float *)d_al_cols.p;
+                n_units = J;
+            } else {
+                src = (const float *)d_out.p;
+                n_units = E > 0 ? E : 0;
+            }
+            al_units.assign((size_t)C, n_units);
+            al_made = align_windows(run, h, nullptr, src, n_units, row_stride, al_events, stream, al_windows, al_begin);
+            return al_made;
+        };
         if (E <= 0) {                                       // shorter than one evaluation: no events
             if (!triggers()) { rc = 2; break; }
             if ((!levels.path.empty() || ttl.any()) && hipStreamSynchronize(stream) != hipSuccess) rc = 2;
+            if (!rc) (void)aligned();                      // (windows that cannot be made do not cost the lines: write_files reports them)
             break;
         }
         if (!d_out.alloc((size_t)C * E * n_out * sizeof(float)) || !d_flags.alloc((size_t)C * E)) { rc = 2; break; }
@@ -378,6 +625,7 @@ int process_file(const std::string &path, const std::vector<syldet_config_t *> &
         if (hipMemcpyAsync(out.data(), d_out.p, out.size() * sizeof(float), hipMemcpyDeviceToHost, stream) != hipSuccess ||
             hipMemcpyAsync(flags.data(), d_flags.p, flags.size(), hipMemcpyDeviceToHost, stream) != hipSuccess ||
             hipStreamSynchronize(stream) != hipSuccess) { rc = 2; break; }
+        (void)aligned();
     } while (false);
     if (rc == 2 && hipPeekAtLastError() != hipSuccess) std::fprintf(stderr, "Unable to process %s: %s\n", path.c_str(), hipGetErrorString(hipGetLastError()));
     if (stream) (void)hipStreamDestroy(stream);
@@ -433,15 +681,21 @@ int process_file(const std::string &path, const std::vector<syldet_config_t *> &
         }
         return bad;
     };
+    // ... and the windows at the events, with their table (and the events into the stacks)
+    auto write_aligned = [&]() -> int {
+        if (!g_align) return 0;
+        if (!al_made) return 3;
+        return align_write_file(*g_align, path, al_events, al_units, al_windows.data(), al_origin, al_step, cfg->sampling_rate);
+    };
     auto write_files = [&]() -> int {
-        const int a = write_track(), b = write_levels(), c = write_ttl();
-        return a ? a : (b ? b : c);
+        const int a = write_track(), b = write_levels(), c = write_ttl(), d = write_aligned();
+        return a ? a : (b ? b : (c ? c : d));
     };
     if (rc) return rc;
     if (E <= 0) return write_files();
 
     // events: sample number of evaluation e = first_index + e*hop (TrackDetector.swift:39-43,67-68); debounce :80,:99
-    const int64_t debounce_frames = have_debounce ? (int64_t)(debounce_s * cfg->sampling_rate) : 0;   // Int(newValue * samplingRate), :24
+    const int64_t debounce_frames = debounce_of_file;
     std::vector<Event> events;
     for (int c = 0; c < C; c++) {
         int64_t until = -1;
@@ -631,6 +885,12 @@ int run_batch(std::vector<BatchFile> &files, const std::vector<syldet_config_t *
     std::vector<double> lv_in;
     std::vector<float> lv_out;
     std::vector<char> lv_empty;
+    // --align-dir: every recording's events, their windows (recording k's from al_begin[k]), and what decides presence
+    std::vector<std::vector<int64_t>> al_events;
+    std::vector<int64_t> al_units, al_begin;
+    std::vector<float> al_windows;
+    int64_t al_origin = 0, al_step = 1;
+    bool al_made = false;
     try {
         if (!dirs.simulate.empty()) sim_frames.assign((size_t)dst_total, 0);
         if (!dirs.ttl.empty()) ttl_frames.assign((size_t)dst_total, 0);
@@ -687,7 +947,7 @@ int run_batch(std::vector<BatchFile> &files, const std::vector<syldet_config_t *
             break;
         }
         const bool ran = row_evals > 0;
-        if (!ran && !metering) break;                       // every file shorter than one evaluation: no events (the input meter reads them all the same)
+        if (!ran && !metering && !g_align) break;                       // every file shorter than one evaluation: no events (the input meter reads them all the same)
         if (hipSetDevice(device) != hipSuccess || hipStreamCreate(&stream) != hipSuccess) { rc = 2; break; }
         DevBuf d_src, d_rows, d_out, d_flags, d_idx, d_val, d_cnt;
         if (!d_src.alloc((size_t)total * el) || !d_rows.alloc((size_t)C * row_samples * (converting || !all16 ? sizeof(float) : sizeof(int16_t))) || !d_out.alloc((size_t)C * row_evals * n_out * sizeof(float)) ||
@@ -711,6 +971,61 @@ int run_batch(std::vector<BatchFile> &files, const std::vector<syldet_config_t *
             st = syldet_recordings_load_pcm_device(r, d_src.p, total, src_offset.data(), src_step.data(), src_format.data(), (float *)d_rows.p, row_samples, stream);
             if (!st && ran) st = syldet_run_device(h, (const float *)d_rows.p, row_samples, row_samples, (float *)d_out.p, (uint8_t *)d_flags.p, stream);
         }
+        // --align-dir: the windows of every recording's events, from the batch's arrays on the device (the outputs; the fp32 rows -- a
+        // batch of 16-bit files is loaded once more, as fp32, from the same upload --; the rows' columns), in one launch
+        DevBuf d_al_rows, d_al_cols;
+        auto aligned = [&]() -> bool {
+            if (!g_align || st) return true;
+            AlignRun &run = *g_align;
+            if (syldet_align_anchor(h, run.opt.source, &al_origin, &al_step, nullptr)) {
+                std::fprintf(stderr, "Unable to align the events of the batch: %s: %s\n", syldet_strerror(SYLDET_ERR_UNSUPPORTED), syldet_last_error());
+                return true;
+            }
+            al_events.clear();
+            int32_t k = 0;
+            for (const BatchFile &f : files)
+                for (int t = 0; t < f.info.channels; t++, k++) {
+                    std::vector<int64_t> found;
+                    for (int64_t i = 0; ran && !run.opt.at_labels && i < cnt[(size_t)k]; i++) found.push_back(idx[(size_t)k * (size_t)cap + (size_t)i]);
+                    al_events.push_back(align_events_of(run, f.path, t, found));
+                }
+            std::vector<syldet_slot_t> slots((size_t)std::max<int32_t>(K, 1));
+            int ast = syldet_recordings_slots(r, slots.data());
+            const float *rows = (const float *)d_rows.p, *src = nullptr;
+            int64_t n_units = 0;
+            if (!ast && run.opt.source != SYLDET_ALIGN_OUTPUTS && all16 && !converting) {
+                std::vector<int64_t> off2(src_offset);
+                std::vector<int32_t> step2(src_step);
+                for (int64_t &o : off2) o *= 2;
+                for (int32_t &q : step2) q *= 2;
+                if (!d_al_rows.alloc((size_t)C * (size_t)row_samples * sizeof(float))) return false;
+                ast = syldet_recordings_load_pcm_device(r, d_src.p, total * 2, off2.data(), step2.data(), src_format.data(), (float *)d_al_rows.p, row_samples, stream);
+                rows = (const float *)d_al_rows.p;
+            }
+            const int64_t J = std::max<int64_t>(0, syldet_count_frames(h, row_samples));
+            al_units.assign((size_t)K, 0);
+            if (run.opt.source == SYLDET_ALIGN_SAMPLES) {
+                src = rows;
+                n_units = row_samples;
+                for (int32_t i = 0; i < K; i++) al_units[(size_t)i] = slots[(size_t)i].n_samples;
+            } else if (run.opt.source == SYLDET_ALIGN_COLUMNS) {
+                if (!d_al_cols.alloc((size_t)C * (size_t)J * (size_t)run.width * sizeof(float))) return false;
+                if (!ast && J > 0) ast = syldet_spectrogram_device(h, rows, row_samples, row_samples, (float *)d_al_cols.p, stream);
+                src = (const float *)d_al_cols.p;
+                n_units = J;
+                for (int32_t i = 0; i < K; i++) al_units[(size_t)i] = std::max<int64_t>(0, syldet_count_frames(h, slots[(size_t)i].n_samples));
+            } else {
+                src = (const float *)d_out.p;
+                n_units = row_evals;
+                for (int32_t i = 0; i < K; i++) al_units[(size_t)i] = slots[(size_t)i].n_evals;
+            }
+            if (ast) {
+                std::fprintf(stderr, "Unable to align the events of the batch: %s: %s\n", syldet_strerror(ast), syldet_last_error());
+                return true;
+            }
+            al_made = align_windows(run, h, r, src, n_units, 0, al_events, stream, al_windows, al_begin);
+            return true;
+        };
         // the level tables of every file of the batch: the input meter on the very rows that are run (int16 rows for 16-bit files, fp32
         // rows for float files and for converted ones), the output meter on the outputs the run left; only the two tables come back
         DevBuf d_lv_in, d_lv_out;
@@ -743,10 +1058,10 @@ int run_batch(std::vector<BatchFile> &files, const std::vector<syldet_config_t *
                 rc = 2;
                 break;
             }
-            if (!ran) {
-                if (hipStreamSynchronize(stream) != hipSuccess) rc = 2;
-                break;
-            }
+        }
+        if (!st && !ran) {                                  // no file of the batch has an evaluation: no events (labels may still be aligned)
+            if (!aligned() || hipStreamSynchronize(stream) != hipSuccess) rc = 2;
+            break;
         }
         // the counts first (a scan of the flags), then the detections themselves into tables of the size they need
         if (!st) st = syldet_recordings_events_device(r, nullptr, (const uint8_t *)d_flags.p, debounce_s, nullptr, nullptr, 0, (int64_t *)d_cnt.p, stream);
@@ -793,6 +1108,7 @@ int run_batch(std::vector<BatchFile> &files, const std::vector<syldet_config_t *
             }
             syldet_scorer_destroy(sc);
         }
+        if (!aligned()) { rc = 2; break; }
         // the tracks of every file of the batch, from the outputs and flags that are on the device
         if (dirs.any()) {
             DevBuf d_sim, d_ttl, d_on_idx, d_on_cnt;
@@ -872,6 +1188,15 @@ int run_batch(std::vector<BatchFile> &files, const std::vector<syldet_config_t *
                 unwritten = true;
             }
         }
+        // ... its windows at the events, with their table (process_file's files)
+        if (!rc && g_align) {
+            const int tracks = f.info.channels;
+            if (!al_made) unwritten = true;
+            else if (align_write_file(*g_align, f.path, std::vector<std::vector<int64_t>>(al_events.begin() + k0, al_events.begin() + k0 + tracks),
+                                      std::vector<int64_t>(al_units.begin() + k0, al_units.begin() + k0 + tracks),
+                                      al_windows.data() + (size_t)al_begin[(size_t)k0] * (size_t)g_align->L(), al_origin, al_step, cfg->sampling_rate))
+                unwritten = true;
+        }
         // ... and its level table, line for line what process_file writes: reading by reading, track by track
         if (!rc && metering) {
             const std::string tsv = TrackDirs::in(dirs.levels, f.path, ".tsv");
@@ -947,6 +1272,14 @@ int process_batched(const std::vector<std::string> &audio, const std::vector<syl
     const double deb = have_debounce ? debounce_s : 0.0;
     std::vector<BatchFile> files;
     size_t held = 0;
+    // what --align-dir adds to a batch on the device, per sample at the file's rate: the columns (4 x bins / hop bytes), the fp32 rows
+    // the samples are cut from (4 bytes), nothing for the outputs
+    double align_bytes_per_sample = 0.0;
+    if (g_align) {
+        syldet_geometry_t g;
+        if (syldet_config_geometry(cfgs[0], &g) == SYLDET_OK)
+            align_bytes_per_sample = g_align->opt.source == SYLDET_ALIGN_COLUMNS ? 4.0 + 4.0 * g.bins / g.hop : g_align->opt.source == SYLDET_ALIGN_SAMPLES ? 4.0 : 0.0;
+    }
     auto flush = [&]() {
         const int r = run_batch(files, cfgs, device, deb, chunk, opt.rows, headers, score, conv, dirs, simulate_output, ttl, levels);
         if (r == 2) rc = 2;
@@ -966,7 +1299,7 @@ int process_batched(const std::vector<std::string> &audio, const std::vector<syl
             f.is16 = f.info.format == 1 && f.info.bits == 16;
             err.clear();
             if (wav::read_raw(p, f.info, f.raw, err)) {
-                held += f.bytes();
+                held += f.bytes() + (size_t)((double)f.info.frames * (double)f.info.channels * align_bytes_per_sample);
                 files.push_back(std::move(f));
                 if ((long long)held >= opt.bytes) flush();
                 continue;
@@ -1012,6 +1345,8 @@ int main(int argc, char **argv)
     bool have_simulate_dir = false, have_ttl_dir = false, have_onsets_dir = false, have_levels_dir = false;
     ScoreOpt score;
     bool have_score = false, have_score_option = false;
+    AlignOpt align;
+    bool have_align_dir = false, have_align_option = false;
     auto value = [&](int &i, const char *name) -> const char * {
         if (i + 1 >= argc) {
             std::fprintf(stderr, "Missing value for %s.\n", name);
@@ -1090,6 +1425,33 @@ int main(int argc, char **argv)
             }
             score.output = (int)k;
             have_score_option = true;
+        }
+        else if (a == "--align-dir") {
+            align.dir = value(i, "--align-dir");
+            have_align_dir = true;
+        } else if (a == "--align" || a == "--align-at") {
+            const bool src = a == "--align";
+            const std::string v = value(i, a.c_str());
+            if (src ? (v != "columns" && v != "outputs" && v != "samples") : (v != "detections" && v != "labels")) {
+                std::fprintf(stderr, src ? "--align takes columns, outputs or samples.\n" : "--align-at takes detections or labels.\n");
+                usage(stdout);
+                return kExUsage;
+            }
+            if (src) align.source = v == "columns" ? SYLDET_ALIGN_COLUMNS : v == "outputs" ? SYLDET_ALIGN_OUTPUTS : SYLDET_ALIGN_SAMPLES;
+            else align.at_labels = v == "labels";
+            have_align_option = true;
+        } else if (a == "--align-before" || a == "--align-after") {
+            const bool b = a == "--align-before";
+            const char *v = value(i, a.c_str());
+            char *end = nullptr;
+            const long k = std::strtol(v, &end, 10);
+            if (end == v || *end != 0 || k < 0 || k > SYLDET_ALIGN_MAX_WINDOW) {
+                std::fprintf(stderr, "--align-before and --align-after take a number of units, 0 or more.\n");
+                usage(stdout);
+                return kExUsage;
+            }
+            (b ? align.before : align.after) = k;
+            have_align_option = true;
         }
         else if (a == "--resample") {
             const std::string m = value(i, "--resample");
@@ -1273,6 +1635,30 @@ int main(int argc, char **argv)
         usage(stdout);
         return kExUsage;
     }
+    if (have_align_dir && align.dir.empty()) {
+        std::fprintf(stderr, "--align-dir takes the name of a directory.\n");
+        usage(stdout);
+        return kExUsage;
+    }
+    if (have_align_option && !have_align_dir) {
+        std::fprintf(stderr, "--align, --align-at, --align-before and --align-after need --align-dir <dir>.\n");
+        usage(stdout);
+        return kExUsage;
+    }
+    if (align.at_labels && !have_score) {
+        std::fprintf(stderr, "--align-at labels needs --score <labels.tsv>.\n");
+        usage(stdout);
+        return kExUsage;
+    }
+    if (have_align_dir) {                                   // every audio file's windows go under its own name, beside the three stack files
+        std::set<std::string> names = {"count", "sum", "sumsq"};
+        for (const std::string &p : audio)
+            if (!names.insert(TrackDirs::name_of(p)).second) {
+                std::fprintf(stderr, "--align-dir names its files after the audio files (and count, sum, sumsq): two of those are called %s.\n", TrackDirs::name_of(p).c_str());
+                usage(stdout);
+                return kExUsage;
+            }
+    }
     if (dirs.any() || have_levels_dir) {                    // every audio file's products go under its own name
         std::set<std::string> names;
         for (const std::string &p : audio)
@@ -1338,7 +1724,8 @@ int main(int argc, char **argv)
         usage(stdout);
         return kExUsage;
     }
-    if (have_score && !batch.on) {                          // the scorer's detectors are the recordings of a batch
+    const bool labels_only = have_score && !batch.on && align.at_labels && !have_score_option;   // --score as the file of --align-at labels
+    if (have_score && !batch.on && !labels_only) {          // the scorer's detectors are the recordings of a batch
         std::fprintf(stderr, "--score needs --batch.\n");
         usage(stdout);
         return kExUsage;
@@ -1348,7 +1735,7 @@ int main(int argc, char **argv)
         usage(stdout);
         return kExUsage;
     }
-    if (have_score && (score.labels_path.empty() || score.out_path.empty())) {
+    if (have_score && !labels_only && (score.labels_path.empty() || score.out_path.empty())) {
         std::fprintf(stderr, "--score <labels.tsv> needs --score-out <table.tsv>.\n");
         usage(stdout);
         return kExUsage;
@@ -1411,6 +1798,34 @@ int main(int argc, char **argv)
         for (long i = 0; i < score.n; i++) scoring.thresholds.push_back(score.n > 1 ? score.lo + (score.hi - score.lo) * (double)i / (double)(score.n - 1) : score.lo);
         scoring.totals.assign((size_t)score.n * SYLDET_SCORE_COLUMNS, 0);
     }
+    AlignRun aligning;
+    if (have_align_dir) {                                   // (before the GPU is opened)
+        syldet_geometry_t g;
+        const int gst = syldet_config_geometry(cfgs[0], &g);
+        aligning.opt = align;
+        aligning.labels = &scoring.labels;
+        aligning.before = align.before < 0 ? cfgs[0]->time_range - 1 : align.before;
+        aligning.after = align.after < 0 ? cfgs[0]->time_range - 1 : align.after;
+        aligning.n = aligning.before + aligning.after + 1;
+        aligning.width = align.source == SYLDET_ALIGN_COLUMNS ? g.bins : align.source == SYLDET_ALIGN_OUTPUTS ? cfgs[0]->n_thresholds : 1;
+        aligning.networks = (int)cfgs.size();
+        if (gst || aligning.width < 1 || aligning.L() > SYLDET_ALIGN_MAX_WINDOW) {
+            if (gst) std::fprintf(stderr, "Unable to use the network configuration: %s: %s\n", syldet_strerror(gst), syldet_last_error());
+            else std::fprintf(stderr, "--align-before and --align-after: a window may hold %d values at most.\n", SYLDET_ALIGN_MAX_WINDOW);
+            for (syldet_config_t *k : cfgs) syldet_config_free(k);
+            usage(stdout);
+            return kExUsage;
+        }
+        aligning.stacks.resize(cfgs.size());
+        for (AlignRun::Stack &st : aligning.stacks) {
+            st.count.assign((size_t)aligning.L(), 0);
+            st.sum.assign((size_t)aligning.L(), 0.0);
+            st.sumsq.assign((size_t)aligning.L(), 0.0);
+        }
+        std::error_code ec;
+        std::filesystem::create_directories(align.dir, ec);
+        g_align = &aligning;
+    }
     if (batch.on) {
         dirs.make();
         int brc = process_batched(audio, cfgs, device, debounce, have_debounce, chunk, batch, conv, have_score ? &scoring : nullptr, dirs, simulate_output, ttl,
@@ -1418,6 +1833,7 @@ int main(int argc, char **argv)
         for (syldet_config_t *c : cfgs) syldet_config_free(c);
         // the table last, and only a whole one; standard output and the status are those of the run without --score
         if (have_score && (scoring.failed || !write_score_table(score, scoring)) && brc == 0) brc = 1;
+        if (g_align && !align_finish(aligning) && brc == 0) brc = 1;
         return brc;
     }
     int rc = 0;
@@ -1431,5 +1847,6 @@ int main(int argc, char **argv)
         else if (r == 3 && rc == 0) rc = 1;                 // ... and so is a track that could not be written
     }
     for (syldet_config_t *c : cfgs) syldet_config_free(c);
+    if (g_align && !align_finish(aligning) && rc == 0) rc = 1;
     return rc;
 }

@@ -509,6 +509,40 @@ struct ScoreDesc {
 hipError_t launch_score(const ScoreDesc &d, int D, const float *outputs, int64_t n_evals, int n_out, int output, int64_t first_index,
                         int64_t hop, int64_t *table, hipStream_t stream);
 
+// ---- event-aligned windows (kernels_align.hip; syldet_align_device and syldet_align_stats_device of include/syldet.h) ----
+// A detector of a packed plan: its unit 0 is unit `base` of row `row`, and it has `units` units.
+struct AlignDetDev {
+    int64_t base, units;
+    int32_t row, pad;
+};
+// What an aligner keeps on the device for the windows.  dets == nullptr: detector d is row d, from unit 0, with the call's n_units.
+struct AlignDesc {
+    const AlignDetDev *dets;                 // [D]
+    const int64_t *event_begin;              // [D + 1] the kept prefix
+    int2 *spans;                             // [N] each window's present elements (first, count): what the statistics count by
+    int D, width;
+    int64_t origin, step, before, after;     // the source's anchor rule and the window (align_span.hpp)
+};
+// windows [N][n * width] <- src [rows][row_stride], events as include/syldet.h states them; one launch (align_windows_kernel)
+hipError_t launch_align_windows(const AlignDesc &d, const float *src, int64_t n_units, int64_t row_stride, const int64_t *events,
+                                int64_t event_stride, int64_t N, float fill, float *windows, hipStream_t stream);
+// ... and for the stack statistics: the events in group order, in blocks of 256.
+constexpr int kAlignBlock = 256;             // events a block of the statistics' tree
+struct AlignStatsDesc {
+    const int64_t *perm;                     // [N] the window of the group-ordered event i
+    const int64_t *group_begin;              // [G + 1] group g's events are i in [group_begin[g], group_begin[g + 1])
+    const int64_t *block_begin;              // [G + 1] ... and its blocks [block_begin[g], block_begin[g + 1])
+    const int32_t *block_group;              // [B]
+    const int2 *spans;                       // [N]
+    int64_t *part_count;                     // [B][L] the blocks' partials: scratch
+    double *part_sum, *part_sumsq;
+    int G;
+    int64_t B;
+};
+// part_* [B][L] <- windows [N][L] (align_stats_kernel), then count, sum, sumsq [G][L] <- part_* in block order (align_combine_kernel)
+hipError_t launch_align_stats(const AlignStatsDesc &d, const float *windows, int L, hipStream_t stream);
+hipError_t launch_align_combine(const AlignStatsDesc &d, int L, int64_t *count, double *sum, double *sumsq, hipStream_t stream);
+
 // detection flags <-> bits (bit b of byte t of a row = flag 8 t + b), rows padded to whole bytes
 hipError_t launch_pack_flags(const uint8_t *flags, int64_t rows, int64_t row_len, uint8_t *bits, hipStream_t stream);
 hipError_t launch_unpack_flags(const uint8_t *bits, int64_t rows, int64_t row_len, uint8_t *flags, hipStream_t stream);

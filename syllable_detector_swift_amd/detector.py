@@ -936,6 +936,14 @@ class SyllableDetector:
         threshold, detections, hits, false positives, repeats and the hits' offset sums, in one launch."""
         return Scorer(self, thresholds, labels, tolerance, debounce)
 
+    # ---- event-aligned windows: spectrogram, output and audio at each event -----------------
+    def aligner(self, source="columns", before: Optional[int] = None, after: Optional[int] = None) -> "Aligner":
+        """An Aligner over this bank's channels (syldet_aligner_create): windows(array, events) cuts, out of the columns
+        spectrogram() made, the outputs run() made or the sample rows -- `source`: "columns", "outputs", "samples" or
+        ALIGN_* -- the units `before` in front of to `after` behind every event's anchor unit, one window an event, in one
+        launch.  before, after: in units of the source, default timeRange - 1 each."""
+        return Aligner(self, source, before, after)
+
     # ---- batch, host arrays -------------------------------------------------------
     def runHost(self, samples: np.ndarray, outputs: Optional[np.ndarray] = None, flags: Optional[np.ndarray] = None) -> Tuple[np.ndarray, np.ndarray]:
         """syldet_run: the batch call on host arrays, pipelined along time inside the library.  `outputs` / `flags`: arrays to
@@ -1438,6 +1446,27 @@ class Recordings:
         own start (SyllableDetector.scorer)."""
         return Scorer(self.detector, thresholds, labels, tolerance, debounce, recordings=self)
 
+    # ---- the packed rows' columns, and windows of them at every recording's events ----
+    def spectrogram(self, rows, stream=None):
+        """rows [C, >= rowSamples] float32 as load*() wrote them -> columns [C, countFrames(rowSamples), bins]
+        (syldet_spectrogram_device on the packed rows): recording k's columns are columnsView(cols, k), bit for bit its
+        spectrogram alone on the fold kernel and the generic engine; row frames between recordings mean nothing."""
+        det = self.detector
+        if not (rows.dim() == 2 and rows.shape[1] >= self.rowSamples):
+            raise ValueError("rows must be [channels, >= rowSamples]")
+        return det.spectrogram(rows[:, :self.rowSamples], stream=stream)
+
+    def columnsView(self, cols, k: int):
+        """The part of spectrogram()'s columns that belongs to recording k: [countFrames(n_samples), bins], no copy."""
+        row, _, first, _, n = self.slots[k]
+        return cols[row, first:first + max(self.detector.countFrames(n), 0)]
+
+    def aligner(self, source="columns", before: Optional[int] = None, after: Optional[int] = None) -> "Aligner":
+        """An Aligner whose detectors are these recordings: events count from each recording's own start, and a window never
+        reads beyond its recording (SyllableDetector.aligner).  The arrays are those of the packed rows: spectrogram(rows),
+        the detector's run(rows) outputs, or the rows themselves."""
+        return Aligner(self.detector, source, before, after, recordings=self)
+
 
 def _score_args(thresholds, labels):
     thr = np.ascontiguousarray(thresholds, dtype=np.float64).reshape(-1)
@@ -1556,6 +1585,197 @@ def chooseThreshold(table, labelCounts, falsePositiveCost: float = 1.0):
     check(_abi.lib.syldet_score_choose(t.ctypes.data_as(_abi.c_int64_p), t.shape[0], t.shape[1], n.ctypes.data_as(_abi.c_int64_p), float(falsePositiveCost),
                                        C.byref(best), totals.ctypes.data_as(_abi.c_int64_p), costs.ctypes.data_as(_abi.c_double_p)))
     return int(best.value), totals, costs
+
+
+_ALIGN_SOURCES = {"columns": _abi.ALIGN_COLUMNS, "outputs": _abi.ALIGN_OUTPUTS, "samples": _abi.ALIGN_SAMPLES}
+
+
+def _align_source(source) -> int:
+    if isinstance(source, str):
+        if source not in _ALIGN_SOURCES:
+            raise ValueError("source must be one of %s" % sorted(_ALIGN_SOURCES))
+        return _ALIGN_SOURCES[source]
+    return int(source)
+
+
+class Aligner:
+    """Event-aligned windows (syldet_aligner_*, include/syldet.h "event-aligned windows"): for every event -- a detection index, a
+    label, any sample number counted from its detector's start -- the units of a source around the event's anchor unit, one window
+    an event, and the stack statistics of groups of windows.  A detector is a channel of the bank, or (made by Recordings.aligner)
+    a recording.  shape = (detectors, units a window, width).  The detector (and the Recordings) must outlive it."""
+
+    def __init__(self, detector: SyllableDetector, source="columns", before: Optional[int] = None, after: Optional[int] = None,
+                 recordings: Optional[Recordings] = None):
+        self.detector = detector
+        self.recordings = recordings
+        self.source = _align_source(source)
+        T = int(detector.config.timeRange)
+        self.before = T - 1 if before is None else int(before)
+        self.after = T - 1 if after is None else int(after)
+        self._h = _abi.Handle()
+        check(_abi.lib.syldet_aligner_create(detector._h, None if recordings is None else recordings._h, self.source, self.before, self.after,
+                                             C.byref(self._h)))
+        d, n, w = C.c_int32(), C.c_int64(), C.c_int32()
+        check(_abi.lib.syldet_aligner_shape(self._h, C.byref(d), C.byref(n), C.byref(w)))
+        self.shape = (d.value, n.value, w.value)
+        self.count = d.value
+        self._begin = None               # the event prefix of the last windows() call: what stats() describes
+
+    def close(self):
+        if getattr(self, "_h", None):
+            _abi.lib.syldet_aligner_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def _source_args(self, array):
+        """(n_units, row_stride in elements) of a source array, checked against the source's layout"""
+        torch = _torch()
+        det, width = self.detector, self.shape[2]
+        if not (array.is_cuda and array.dtype == torch.float32 and array.device.index == det.device):
+            raise ValueError("the source must be a float32 CUDA tensor on the detector's device")
+        if self.source == _abi.ALIGN_SAMPLES:
+            if not (array.dim() == 2 and array.shape[0] == det.channels and (array.shape[1] == 0 or array.stride(1) == 1)):
+                raise ValueError("samples must be [channels, n_samples], rows contiguous")
+            n_units = int(array.shape[1]) if self.recordings is None else self.recordings.rowSamples
+            if array.shape[1] < n_units:
+                raise ValueError("samples must hold the packed rows' %d samples" % n_units)
+            return n_units, (int(array.stride(0)) if det.channels > 1 else max(int(array.shape[1]), n_units))
+        if not (array.dim() == 3 and array.shape[0] == det.channels and array.shape[2] == width and array.is_contiguous()):
+            raise ValueError("the source must be a contiguous tensor [channels, units, %d]" % width)
+        return int(array.shape[1]), 0
+
+    def windows(self, array, events, counts=None, fill: float = float("nan"), out=None, stream=None):
+        """array: the source on the device -- columns [C, n_frames, bins], outputs [C, n_evals, n_out] or samples [C, S], for
+        recordings those of the packed rows.  events: the (indices [D, capacity], counts [D]) pair of detections() / events()
+        (pass counts=; a count beyond the capacity means the capacity), or a list of D arrays of sample numbers, or one flat
+        int64 CUDA tensor with counts.  -> windows [N, n, width] float32 on the device, detector d's j-th event at
+        eventBegin[d] + j; elements outside a detector's units are `fill`.  One launch; the same counts again make it a launch
+        only.  Asynchronous on `stream` (a counts tensor on the device is waited for and downloaded)."""
+        torch = _torch()
+        det = self.detector
+        n_units, row_stride = self._source_args(array)
+        D, n, width = self.shape
+        if counts is None:
+            if hasattr(events, "is_cuda"):
+                raise ValueError("an events tensor needs counts")
+            parts = [np.ascontiguousarray(e, dtype=np.int64).reshape(-1) for e in events]
+            if len(parts) != D:
+                raise ValueError("one array of events per detector (%d given, %d detectors)" % (len(parts), D))
+            cnt = np.array([p.size for p in parts], np.int64)
+            flat = np.concatenate(parts) if parts else np.zeros(0, np.int64)
+            ev = torch.from_numpy(np.ascontiguousarray(flat, dtype=np.int64)).to(array.device)
+            stride = 0
+        else:
+            cnt = (counts.cpu().numpy() if hasattr(counts, "is_cuda") else np.asarray(counts)).astype(np.int64).reshape(-1)
+            ev = events
+            if not (hasattr(ev, "is_cuda") and ev.is_cuda and ev.dtype == torch.int64 and ev.is_contiguous() and ev.device == array.device
+                    and ev.dim() in (1, 2)):
+                raise ValueError("events must be a contiguous int64 CUDA tensor [detectors, capacity] (or flat) on the source's device")
+            if cnt.size != D or (cnt.size and cnt.min() < 0):
+                raise ValueError("one count per detector, none negative")
+            if ev.dim() == 2:
+                if ev.shape[0] != D:
+                    raise ValueError("events must have one row per detector")
+                stride = int(ev.shape[1])
+                cnt = np.minimum(cnt, stride)
+            else:
+                stride = 0
+                if int(cnt.sum()) > ev.numel():
+                    raise ValueError("the counts reach beyond the events")
+        begin = np.zeros(D + 1, np.int64)
+        np.cumsum(cnt, out=begin[1:])
+        N = int(begin[-1])
+        want = (N, n, width)
+        if out is None:
+            out = torch.empty(want, dtype=torch.float32, device=array.device)
+        elif not (out.is_cuda and out.dtype == torch.float32 and tuple(out.shape) == want and out.is_contiguous() and out.device == array.device):
+            raise ValueError("out must be a contiguous float32 CUDA tensor of shape %s on the source's device" % (want,))
+        check(_abi.lib.syldet_align_device(self._h, array.data_ptr(), n_units, row_stride, ev.data_ptr(), stride, begin.ctypes.data_as(_abi.c_int64_p),
+                                           float(fill), out.data_ptr(), det._stream_ptr(stream)))
+        self._begin = begin
+        self.eventBegin = begin.copy()
+        # the launch may still be reading the events when this returns: they stay with the aligner until the next call, and a stream
+        # other than torch's current one is told to the allocator
+        self._events = ev
+        if stream is not None:
+            ev.record_stream(stream)
+        return out
+
+    def stats(self, windows, groups=None, groupCount: Optional[int] = None, stream=None):
+        """The stack statistics of the windows the last windows() call made: (count int64, sum float64, sumsq float64), each
+        [G, n, width] on the device.  groups: the stack of every detector (default: one stack of all), G = groupCount or
+        max(groups) + 1.  Sums run in blocks of 256 events in a fixed order, so they are the same bits every time, and those of
+        alignStatsHost; the mean is sum / count.  Presence is what the LAST windows() call found: call stats() before the next
+        windows() -- with the same counts but other events or another array that call replaces the spans, and statistics of an
+        earlier call's tensor would go by them without an error."""
+        torch = _torch()
+        if self._begin is None:
+            raise ValueError("stats() describes the windows of the last windows() call: there has been none")
+        D, n, width = self.shape
+        grp = np.zeros(D, np.int32) if groups is None else np.ascontiguousarray(groups, dtype=np.int32).reshape(-1)
+        if grp.size != D:
+            raise ValueError("one group per detector")
+        G = int(groupCount) if groupCount is not None else (int(grp.max()) + 1 if D else 1)
+        want = (int(self._begin[-1]), n, width)
+        if not (windows.is_cuda and windows.dtype == torch.float32 and tuple(windows.shape) == want and windows.is_contiguous()
+                and windows.device.index == self.detector.device):
+            raise ValueError("windows must be the contiguous float32 CUDA tensor of shape %s the last windows() call made" % (want,))
+        count = torch.empty((max(G, 0), n, width), dtype=torch.int64, device=windows.device)
+        total = torch.empty((max(G, 0), n, width), dtype=torch.float64, device=windows.device)
+        squares = torch.empty((max(G, 0), n, width), dtype=torch.float64, device=windows.device)
+        check(_abi.lib.syldet_align_stats_device(self._h, windows.data_ptr(), self._begin.ctypes.data_as(_abi.c_int64_p),
+                                                 grp.ctypes.data_as(_abi.c_int32_p), G, count.data_ptr(), total.data_ptr(), squares.data_ptr(),
+                                                 self.detector._stream_ptr(stream)))
+        return count, total, squares
+
+
+def alignHost(source, events, before: int, after: int, origin: int, step: int, fill: float = float("nan")):
+    """syldet_align_host: one detector's windows on the host, no device needed.  source: the detector's own units, [units, width]
+    (or [units]: width 1) float32; events: sample numbers; origin, step: the source's anchor rule u0 = floor((s - origin) / step)
+    -> (windows [n_events, before + after + 1, width] float32, present [n_events, 2] int64: each window's first present element
+    and the number of present elements)."""
+    a = np.asarray(source)
+    if a.dtype != np.float32 or a.ndim not in (1, 2):
+        raise ValueError("source must be a float32 array [units] or [units, width]")
+    a = np.ascontiguousarray(a if a.ndim == 2 else a[:, None])
+    width = int(a.shape[1])
+    ev = np.ascontiguousarray(events, dtype=np.int64).reshape(-1)
+    n = int(before) + int(after) + 1
+    windows = np.empty((ev.size, max(n, 0), max(width, 1)), np.float32)
+    present = np.zeros((ev.size, 2), np.int64)
+    check(_abi.lib.syldet_align_host(a.ctypes.data_as(_abi.c_float_p), a.shape[0], width, int(origin), int(step), int(before), int(after),
+                                     ev.ctypes.data_as(_abi.c_int64_p), ev.size, float(fill), windows.ctypes.data_as(_abi.c_float_p),
+                                     present.ctypes.data_as(_abi.c_int64_p)))
+    return windows, present
+
+
+def alignStatsHost(windows, present):
+    """syldet_align_stats_host: one stack on the host.  windows [events, ...] float32 and present [events, 2] as alignHost gave
+    them, in the stack's order -> (count int64, sum float64, sumsq float64), each of a window's shape."""
+    w = np.ascontiguousarray(windows, dtype=np.float32)
+    if w.ndim < 2:
+        raise ValueError("windows must be [events, ...]")
+    shape = w.shape[1:]
+    L = int(np.prod(shape))
+    pr = np.ascontiguousarray(present, dtype=np.int64).reshape(-1, 2)
+    if pr.shape[0] != w.shape[0]:
+        raise ValueError("one present pair per window")
+    count, total, squares = np.zeros(L, np.int64), np.zeros(L, np.float64), np.zeros(L, np.float64)
+    check(_abi.lib.syldet_align_stats_host(w.ctypes.data_as(_abi.c_float_p), pr.ctypes.data_as(_abi.c_int64_p), w.shape[0], L,
+                                           count.ctypes.data_as(_abi.c_int64_p), total.ctypes.data_as(_abi.c_double_p),
+                                           squares.ctypes.data_as(_abi.c_double_p)))
+    return count.reshape(shape), total.reshape(shape), squares.reshape(shape)
 
 
 def _pcm16(data) -> np.ndarray:
