@@ -1248,6 +1248,82 @@ int syldet_align_host(const float *src, int64_t n_units, int32_t width, int64_t 
 int syldet_align_stats_host(const float *windows, const int64_t *present, int64_t n_events, int64_t window_elements, int64_t *count,
                             double *sum, double *sumsq);
 
+/* ---- training: loss and gradient of a network over labelled recordings ----
+ * The reference's detector is "a simple Matlab neural network trained using the training code"; its only bridge is
+ * convert_to_text.m.  Everything training reads is on the device already -- the columns of syldet_spectrogram_device, labels as the
+ * scorer takes them -- and the N x I input matrix is those columns repeated timeRange times.  These calls give loss and gradient
+ * of the network's parameters over weighted, labelled evaluations straight from the columns; that matrix is never formed.  The
+ * optimiser is the caller's.  THE CONVENTION is the library's own (as the scorer's and the aligner's):
+ * A DETECTOR, its evaluations e and their sample numbers idx_e = first_index + e hop are the scorer's; for a recording e and the
+ *   samples count from its own start, and its evaluation e is evaluation slot.first_eval + e of row slot.row.  Evaluation e of a row
+ *   reads the I = timeRange x bins contiguous floats from frame e of that row of the columns (the aligner's COLUMNS window with
+ *   before = timeRange - 1, after = 0).
+ * PARAMETERS: one flat fp32 vector theta of P = H I + H + O H + O elements: layer0.weights [H][I], layer0.biases [H],
+ *   layer1.weights [O][H], layer1.biases [O], each weight block row-major as syldet_layer_t has it.  Everything else -- scaling,
+ *   the input functions and their map parameters, the two transfer functions, the output maps -- is read from the bank's
+ *   configuration at creation and is fixed.  theta comes with every call; the bank's own weights are never touched.
+ * FORWARD: what the generic engine computes for an evaluation, from the linear columns: scaling (linear / log / dB), the input
+ *   functions in file order (a normalize over range 0 fills -1, as the engines do), the two layers, the reverse output maps; all in
+ *   fp32 (the first layer's products are summed frame by frame, then the frames), giving y_e[o].
+ * TARGETS AND WEIGHTS: t [rows][n_evals][O] and w [rows][n_evals], fp32, on the device.  Evaluation e of a row is SELECTED iff
+ *   w > 0; a NaN weight is not selected.  An unselected evaluation contributes nothing WHATEVER ITS COLUMNS HOLD -- NaN, Inf, the
+ *   zeros between two packed recordings whose l2-normalised input is 0 / 0: this is a rule about selection, not a product with 0.
+ * RESULT: L = sum over the selected (row, e) of w sum_o (y[o] - t[o])^2; Wsum = the sum of the selected w; g = dL / dtheta with
+ *   the transfer derivatives TanSig 1 - h^2, LogSig h (1 - h), PureLin 1, SatLin 1 where 0 < a < 1 and else 0; the reverse output
+ *   maps are affine (1 / gain); no input function is differentiated, none has a trainable parameter.  d_loss: double [2] =
+ *   {L, Wsum}; d_gradient: float [P].  Dividing by Wsum is the caller's.
+ * REPRODUCIBLE: the same arrays through the same trainer give the same bits, call after call.  The grid and the order of every sum
+ *   are functions of the shapes alone, never of the device or of timing; there are no float atomics.  A row is cut into tiles of
+ *   `tile` evaluations (syldet_trainer_shape); workgroup g of G = min(tiles, a bound from P) takes the tiles g, g + G, .. in order,
+ *   adds each tile's fp32 sums into its fp64 partial, and a second kernel adds the G partials in order and rounds once to fp32.
+ * LIMITS of this version, anything else SYLDET_ERR_UNSUPPORTED at creation: a plain bank (one network: not multi-network, mixed or
+ *   sharded), exactly two layers, H <= SYLDET_TRAIN_MAX_HIDDEN, O <= SYLDET_TRAIN_MAX_OUTPUTS, and an input that fits the
+ *   kernel's local memory (290 and 1160 inputs do); any scaling, any input chain, any output chain.
+ *   syldet_trainer_create    h: the bank; r: NULL (D = its channels) or a packed-recordings handle of h (D = its recordings).  The
+ *       network's fixed part, for recordings the slots, and the partial sums' scratch are put on the device once.  h, and r if
+ *       given, must outlive the trainer.
+ *   syldet_trainer_shape     D, P, O and the tile (each may be NULL)
+ *   syldet_train_param_count host only: P of a configuration of two layers
+ *   syldet_train_targets_device   writes EVERY element of d_targets [rows][n_evals][O] and d_weights [rows][n_evals].  For evaluation
+ *       e of detector d: target[o] = 1.0 iff some label j of d with label_output[j] == o has |idx_e - t_j| <= half_width_samples,
+ *       else 0.0; weight = weight_positive if any target is 1, else weight_negative (either may be 0).  Every (row, e) that belongs
+ *       to no detector -- with r: between recordings and behind the last one -- gets target 0 and weight 0.  labels, label_begin
+ *       [D + 1] as the scorer's (host arrays; sorted per detector, they may repeat, overlap, lie before 0 or behind the end);
+ *       label_output [n_labels] int32 or NULL (all 0).  Integers and two constants only: device, host and any model agree to the
+ *       bit (csrc/train_targets.hpp: one text for the kernel, the host and a stand-alone test).  One launch
+ *       ("train_targets_kernel").  With r n_evals must be row_evals.
+ *   syldet_train_targets_host     host only, one detector in plain C++ (the text the kernel runs): targets [n_evals][n_out],
+ *       weights [n_evals].
+ *   syldet_train_gradient_device  d_columns [rows][n_frames][bins] as syldet_spectrogram_device wrote it, rows row_stride ELEMENTS
+ *       apart (0: n_frames bins); n_evals evaluations a row read n_evals + timeRange - 1 frames (with r: n_evals = row_evals and
+ *       n_frames = syldet_count_frames(h, row_samples)); d_params: theta.  Two launches ("train_gradient_kernel",
+ *       "train_combine_kernel").  Without a selected evaluation, or with n_evals = 0, L = 0, Wsum = 0 and g = 0 exactly.
+ * Statuses, decided before any device is touched; a refused call leaves d_loss and d_gradient as they were.
+ * SYLDET_ERR_INVALID_ARGUMENT: a NULL handle or pointer (the device arrays may be NULL where n_evals is 0), a negative n_evals or
+ * n_frames, a wrong n_evals or n_frames with r, fewer frames than the evaluations read, a row_stride smaller than a row needs, a
+ * label_begin that does not start at 0 or that decreases, unsorted labels, a label_output outside [0, O), a half width outside
+ * [0, 2^40], a class weight that is NaN or negative.
+ * THE LAUNCH RULE is the aligner's: the trainer keeps the labels on the device.  A targets call whose host arrays differ from the
+ * kept ones (the first always) waits for the stream of the trainer's last call and uploads them with one blocking copy; the same
+ * arrays again are a launch only.  syldet_train_gradient_device is always launches only: no allocation, no synchronisation, no
+ * copy.  One stream at a time, as the bank; every call records into the profile of h (syldet_profile).                         */
+#define SYLDET_TRAIN_MAX_HIDDEN  16
+#define SYLDET_TRAIN_MAX_OUTPUTS 4
+typedef struct syldet_trainer syldet_trainer_t;
+int syldet_trainer_create(const syldet_t *h, const syldet_recordings_t *r, syldet_trainer_t **out);
+int syldet_trainer_destroy(syldet_trainer_t *t);
+int syldet_trainer_shape(const syldet_trainer_t *t, int32_t *n_detectors, int64_t *n_params, int32_t *n_out, int32_t *tile);
+int syldet_train_param_count(const syldet_config_t *cfg, int64_t *n_params);
+int syldet_train_targets_device(syldet_trainer_t *t, const int64_t *labels, const int64_t *label_begin, const int32_t *label_output,
+                                int64_t half_width_samples, float weight_positive, float weight_negative, int64_t n_evals,
+                                float *d_targets, float *d_weights, void *hip_stream);
+int syldet_train_targets_host(const int64_t *labels, int64_t n_labels, const int32_t *label_output, int32_t n_out,
+                              int64_t half_width_samples, float weight_positive, float weight_negative, int64_t first_index,
+                              int64_t hop, int64_t n_evals, float *targets, float *weights);
+int syldet_train_gradient_device(syldet_trainer_t *t, const float *d_columns, int64_t n_frames, int64_t row_stride,
+                                 const float *d_params, const float *d_targets, const float *d_weights, int64_t n_evals,
+                                 double *d_loss, float *d_gradient, void *hip_stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -103,6 +103,9 @@ ALIGN_COLUMNS, ALIGN_OUTPUTS, ALIGN_SAMPLES = 0, 1, 2
 ALIGN_MAX_WINDOW = 1 << 20
 ALIGN_BLOCK = 256
 
+# the trainer's envelope (SYLDET_TRAIN_*)
+TRAIN_MAX_HIDDEN, TRAIN_MAX_OUTPUTS = 16, 4
+
 Handle = C.c_void_p
 Config_p = C.POINTER(Config)
 c_void_pp = C.POINTER(C.c_void_p)
@@ -292,6 +295,16 @@ SIGNATURES = {
     "syldet_align_host": (C.c_int, [c_float_p, C.c_int64, C.c_int32, C.c_int64, C.c_int64, C.c_int64, C.c_int64, c_int64_p, C.c_int64, C.c_float,
                                     c_float_p, c_int64_p]),
     "syldet_align_stats_host": (C.c_int, [c_float_p, c_int64_p, C.c_int64, C.c_int64, c_int64_p, c_double_p, c_double_p]),
+    "syldet_trainer_create": (C.c_int, [Handle, Handle, C.POINTER(Handle)]),
+    "syldet_trainer_destroy": (C.c_int, [Handle]),
+    "syldet_trainer_shape": (C.c_int, [Handle, c_int32_p, c_int64_p, c_int32_p, c_int32_p]),
+    "syldet_train_param_count": (C.c_int, [Config_p, c_int64_p]),
+    "syldet_train_targets_device": (C.c_int, [Handle, c_int64_p, c_int64_p, c_int32_p, C.c_int64, C.c_float, C.c_float, C.c_int64, C.c_void_p, C.c_void_p,
+                                              C.c_void_p]),
+    "syldet_train_targets_host": (C.c_int, [c_int64_p, C.c_int64, c_int32_p, C.c_int32, C.c_int64, C.c_float, C.c_float, C.c_int64, C.c_int64, C.c_int64,
+                                            c_float_p, c_float_p]),
+    "syldet_train_gradient_device": (C.c_int, [Handle, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p,
+                                               C.c_void_p, C.c_void_p]),
 }
 
 

@@ -61,6 +61,11 @@ class ShardedSyllableDetectorBank:
         from .config import SyllableDetectorError
         raise SyllableDetectorError(_abi.ERR_UNSUPPORTED, "event-aligned windows on a sharded bank: use a SyllableDetector per device")
 
+    def trainer(self):
+        """Training (SyllableDetector.trainer) has no sharded form: the columns lie on several devices."""
+        from .config import SyllableDetectorError
+        raise SyllableDetectorError(_abi.ERR_UNSUPPORTED, "training on a sharded bank: use a SyllableDetector per device")
+
     def __del__(self):
         try:
             self.close()

@@ -543,6 +543,48 @@ struct AlignStatsDesc {
 hipError_t launch_align_stats(const AlignStatsDesc &d, const float *windows, int L, hipStream_t stream);
 hipError_t launch_align_combine(const AlignStatsDesc &d, int L, int64_t *count, double *sum, double *sumsq, hipStream_t stream);
 
+// ---- training (kernels_train.hip; syldet_train_targets_device and syldet_train_gradient_device of include/syldet.h) ----
+// A detector of a packed plan as the targets kernel finds it: the table is sorted by (row, first_eval), row c's detectors are
+// [row_begin[c], row_begin[c + 1]).
+struct TrainDetDev {
+    int64_t first_eval, n_evals;
+    int32_t det, row;                        // the recording (the caller's order) and its bank row
+};
+struct TrainTargetsDesc {
+    const TrainDetDev *dets;                 // packed plans; nullptr: detector c is row c, all of it
+    const int32_t *row_begin;                // [rows + 1]
+    const int64_t *labels;                   // every detector's sorted labels, end to end
+    const int64_t *label_begin;              // [D + 1]
+    const int32_t *label_output;             // [n_labels], or nullptr: all 0
+    int rows, n_out;
+    int64_t first_index, hop, half_width;
+    float weight_positive, weight_negative;
+};
+// targets [rows][n_evals][n_out], weights [rows][n_evals]: every element written (train_targets.hpp)
+hipError_t launch_train_targets(const TrainTargetsDesc &d, int64_t n_evals, float *targets, float *weights, hipStream_t stream);
+// The network as the gradient kernel reads it: everything but the two layers' parameters, which come with every call.
+struct TrainDesc {
+    int F, T, I, H, O;                       // bins, timeRange, F T, hidden units, outputs
+    int tf0, tf1, scaling;
+    int n_in_fns, n_out_fns;
+    DevFn in_fns[kMaxFns], out_fns[kMaxFns]; // xoff / gain: offsets into maps
+    const float *maps;                       // the map functions' x offsets and gains
+    // the launch shape, a function of the numbers above alone (train_plan)
+    int HP;                                  // H padded to 4, 8 or 16
+    int threads, tile, FP;                   // threads a workgroup; evaluations a tile (<= threads); floats a staged frame (odd)
+    int lds_stage, lds_d1, lds_stats, lds_red, lds_sel, lds_total;   // byte offsets behind the transposed first layer
+    int max_groups;                          // the most workgroups a launch takes (each keeps P + 2 doubles of partial sums)
+};
+inline int train_param_count(int I, int H, int O) { return H * I + H + O * H + O; }
+bool train_plan(TrainDesc &d);               // false: the shape does not fit the kernel
+hipError_t train_prepare(const TrainDesc &d);    // on the trainer's device, once: the kernel's LDS above 64 KB allowed
+int train_groups(const TrainDesc &d, int rows, int64_t n_evals);   // workgroups of a launch: min(tiles, max_groups)
+// part [groups][P + 2] fp64 <- the groups' partial gradients, loss and weight sum (train_gradient_kernel); then loss [2], gradient [P]
+// <- the partials added in group order, rounded once (train_combine_kernel)
+hipError_t launch_train_gradient(const TrainDesc &d, const float *columns, int64_t row_stride, int rows, const float *params, const float *targets,
+                                 const float *weights, int64_t n_evals, double *part, hipStream_t stream);
+hipError_t launch_train_combine(const TrainDesc &d, int groups, const double *part, double *loss, float *gradient, hipStream_t stream);
+
 // detection flags <-> bits (bit b of byte t of a row = flag 8 t + b), rows padded to whole bytes
 hipError_t launch_pack_flags(const uint8_t *flags, int64_t rows, int64_t row_len, uint8_t *bits, hipStream_t stream);
 hipError_t launch_unpack_flags(const uint8_t *bits, int64_t rows, int64_t row_len, uint8_t *flags, hipStream_t stream);

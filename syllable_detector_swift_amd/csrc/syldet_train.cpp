@@ -1,0 +1,338 @@
+// syldet_train.cpp -- training (include/syldet.h, "training"; kernels_train.hip): the trainer that keeps a packed plan's detectors,
+// the caller's labels, the network's fixed part and the partial sums on the device, so that syldet_train_targets_device with the
+// same labels and every syldet_train_gradient_device are launches only; and the targets on the host (train_targets.hpp, one detector).
+
+#include "syldet_handle.hpp"
+#include "train_targets.hpp"
+
+static_assert(SYLDET_TRAIN_MAX_HIDDEN == sd::kTrainMaxHidden && SYLDET_TRAIN_MAX_OUTPUTS == sd::kTrainMaxOut, "the header's limits are the kernel's");
+
+struct syldet_trainer {
+    syldet_t *h = nullptr;                   // the bank (it outlives the trainer): its profile
+    sd::BankInfo bank{};
+    bool packed = false;
+    int D = 0, P = 0;
+    int64_t row_evals = 0, row_frames = 0;   // (packed) what n_evals and n_frames must be
+    sd::TrainDesc desc{};
+    sd::DeviceBuffer d_fixed;                // maps | (packed) TrainDetDev [D] | row_begin [rows + 1]
+    sd::DeviceBuffer d_part;                 // [max_groups][P + 2] fp64
+    const sd::TrainDetDev *d_dets = nullptr;
+    const int32_t *d_row_begin = nullptr;
+    hipStream_t last = nullptr;              // the stream of the last call that may still read the labels or write the partials
+    // the kept labels
+    bool has_labels = false, has_output = false;
+    std::vector<int64_t> begin, labels;      // [D + 1], [n_labels]
+    std::vector<int32_t> output;             // [n_labels]
+    sd::DeviceBuffer d_labels;               // label_begin | labels | label_output
+};
+
+namespace {
+
+int two_layers(const syldet_config_t &c, int *I, int *H, int *O)
+{
+    if (c.n_layers != 2 || !c.layers) return fail(SYLDET_ERR_UNSUPPORTED, "the trainer takes networks of exactly two layers");
+    if (c.layers[0].inputs < 1 || c.layers[0].outputs < 1 || c.layers[1].outputs < 1 || c.layers[1].inputs != c.layers[0].outputs)
+        return fail(SYLDET_ERR_LAYER_SHAPE, "the two layers do not fit each other");
+    *I = c.layers[0].inputs;
+    *H = c.layers[0].outputs;
+    *O = c.layers[1].outputs;
+    return SYLDET_OK;
+}
+
+int class_weights(float wp, float wn)
+{
+    if (!(wp >= 0.0f) || !(wn >= 0.0f)) return fail(SYLDET_ERR_INVALID_ARGUMENT, "a class weight is NaN or negative");
+    return SYLDET_OK;
+}
+
+int half_width_arg(int64_t hw)
+{
+    if (hw < 0 || hw > sd::kTrainMaxHalfWidth) return fail(SYLDET_ERR_INVALID_ARGUMENT, "half_width_samples must be in [0, 2^40]");
+    return SYLDET_OK;
+}
+
+int outputs_arg(const int32_t *label_output, int64_t n, int O)
+{
+    if (label_output)
+        for (int64_t j = 0; j < n; j++)
+            if (label_output[j] < 0 || label_output[j] >= O)
+                return fail(SYLDET_ERR_INVALID_ARGUMENT, "label_output[" + std::to_string(j) + "] = " + std::to_string(label_output[j]) + " is outside [0, " +
+                                                             std::to_string(O) + ")");
+    return SYLDET_OK;
+}
+
+size_t up16(size_t n) { return (n + 15) / 16 * 16; }
+
+}  // namespace
+
+extern "C" {
+
+int syldet_train_param_count(const syldet_config_t *cfg, int64_t *n_params)
+{
+    if (!cfg || !n_params) return fail(SYLDET_ERR_INVALID_ARGUMENT, "NULL argument");
+    int I = 0, H = 0, O = 0;
+    if (int st = two_layers(*cfg, &I, &H, &O)) return st;
+    *n_params = (int64_t)H * I + H + (int64_t)O * H + O;
+    return SYLDET_OK;
+}
+
+int syldet_trainer_create(const syldet_t *h, const syldet_recordings_t *r, syldet_trainer_t **out)
+{
+    if (!out) return fail(SYLDET_ERR_INVALID_ARGUMENT, "NULL argument");
+    *out = nullptr;
+    if (!h) return fail(SYLDET_ERR_INVALID_ARGUMENT, "NULL handle");
+    if (h->n_nets != 1 || !h->classes.empty() || h->root)
+        return fail(SYLDET_ERR_UNSUPPORTED, "the trainer takes a plain bank: one network, not a multi-network or mixed one");
+    const syldet_config_t &c = h->cfg.view;
+    int I = 0, H = 0, O = 0;
+    if (int st = two_layers(c, &I, &H, &O)) return st;
+    if (H > SYLDET_TRAIN_MAX_HIDDEN || O > SYLDET_TRAIN_MAX_OUTPUTS)
+        return fail(SYLDET_ERR_UNSUPPORTED, "the trainer takes up to " + std::to_string(SYLDET_TRAIN_MAX_HIDDEN) + " hidden units and " +
+                                                std::to_string(SYLDET_TRAIN_MAX_OUTPUTS) + " outputs (" + std::to_string(H) + " and " + std::to_string(O) + " given)");
+    if (c.n_input_fns > sd::kMaxFns || c.n_output_fns > sd::kMaxFns) return fail(SYLDET_ERR_UNSUPPORTED, "more than 8 processing functions");
+    sd::BankInfo b{};
+    sd::bank_info(h, &b);
+    sd::TrainDesc d{};
+    d.F = b.geom.bins;
+    d.T = b.time_range;
+    d.I = I;
+    d.H = H;
+    d.O = O;
+    d.tf0 = c.layers[0].transfer;
+    d.tf1 = c.layers[1].transfer;
+    d.scaling = c.scaling;
+    d.n_in_fns = c.n_input_fns;
+    d.n_out_fns = c.n_output_fns;
+    if (I != b.geom.inputs || O != b.geom.outputs || !sd::train_plan(d))
+        return fail(SYLDET_ERR_UNSUPPORTED, "a network of " + std::to_string(I) + " inputs (" + std::to_string(d.F) + " bins x " + std::to_string(d.T) +
+                                                " columns) does not fit the gradient kernel's local memory");
+    int32_t D = b.channels;
+    int64_t row_samples = 0, row_evals = 0;
+    if (r)
+        if (int st = syldet_recordings_shape(r, &D, &row_samples, &row_evals, nullptr)) return st;
+
+    std::unique_ptr<syldet_trainer, int (*)(syldet_trainer_t *)> t(nullptr, syldet_trainer_destroy);
+    std::vector<float> maps;
+    std::vector<sd::TrainDetDev> dets;
+    std::vector<int32_t> row_begin;
+    try {
+        t.reset(new syldet_trainer());
+        t->bank = b;
+        auto push = [&maps](const float *p, int n) {
+            const int at = (int)maps.size();
+            maps.insert(maps.end(), p, p + n);
+            return at;
+        };
+        for (int k = 0; k < c.n_input_fns; k++) {
+            const syldet_fn_t &f = c.input_fns[k];
+            d.in_fns[k].kind = f.kind;
+            d.in_fns[k].y = f.y;
+            if (f.kind >= SYLDET_FN_MAPMINMAX) {
+                d.in_fns[k].xoff = push(f.x_offsets, I);
+                d.in_fns[k].gain = push(f.gains, I);
+            }
+        }
+        for (int k = 0; k < c.n_output_fns; k++) {
+            const syldet_fn_t &f = c.output_fns[k];
+            d.out_fns[k].kind = f.kind;
+            d.out_fns[k].y = f.y;
+            d.out_fns[k].xoff = push(f.x_offsets, O);
+            d.out_fns[k].gain = push(f.gains, O);
+        }
+        t->begin.assign((size_t)D + 1, 0);
+        if (r) {
+            std::vector<syldet_slot_t> plan((size_t)D);
+            if (D > 0)
+                if (int st = syldet_recordings_slots(r, plan.data())) return st;
+            // the detectors by (row, first_eval): what the targets kernel searches (an empty recording in front of one that starts
+            // at the same evaluation, so that the last detector at or before an evaluation is the one that holds it)
+            for (int k = 0; k < D; k++) dets.push_back(sd::TrainDetDev{plan[(size_t)k].first_eval, plan[(size_t)k].n_evals, k, plan[(size_t)k].row});
+            std::stable_sort(dets.begin(), dets.end(), [](const sd::TrainDetDev &x, const sd::TrainDetDev &y) {
+                if (x.row != y.row) return x.row < y.row;
+                return x.first_eval != y.first_eval ? x.first_eval < y.first_eval : x.n_evals < y.n_evals;
+            });
+            row_begin.assign((size_t)b.channels + 1, 0);
+            for (const sd::TrainDetDev &e : dets) {
+                if (e.row < 0 || e.row >= b.channels || (e.n_evals > 0 && (e.first_eval < 0 || e.first_eval + e.n_evals > row_evals)))
+                    return fail(SYLDET_ERR_INVALID_ARGUMENT, "recording " + std::to_string(e.det) + " reaches beyond its row");
+                row_begin[(size_t)e.row + 1]++;
+            }
+            for (int c2 = 0; c2 < b.channels; c2++) row_begin[(size_t)c2 + 1] += row_begin[(size_t)c2];
+        }
+    } catch (const std::bad_alloc &) {
+        return fail(SYLDET_ERR_OUT_OF_MEMORY, "out of memory");
+    }
+    t->h = const_cast<syldet_t *>(h);
+    t->packed = r != nullptr;
+    t->D = D;
+    t->P = sd::train_param_count(I, H, O);
+    t->row_evals = row_evals;
+    t->row_frames = r ? std::max<int64_t>(0, sd::count_frames(b.geom, b.window_length, row_samples)) : 0;
+    if (r && row_evals > 0 && t->row_frames < row_evals + d.T - 1) return fail(SYLDET_ERR_INVALID_ARGUMENT, "the packed rows hold fewer frames than their evaluations read");
+
+    const size_t n_maps = up16(maps.size() * sizeof(float)), n_dets = up16(dets.size() * sizeof(sd::TrainDetDev)),
+                 n_rows = up16(row_begin.size() * sizeof(int32_t));
+    SYLDET_HIP(hipSetDevice(b.device));
+    SYLDET_HIP(sd::train_prepare(d));
+    if (int st = t->d_fixed.reserve(n_maps + n_dets + n_rows + 16)) return st;
+    if (int st = t->d_part.reserve((size_t)d.max_groups * ((size_t)t->P + 2) * sizeof(double))) return st;
+    char *base = (char *)t->d_fixed.ptr;
+    if (!maps.empty()) SYLDET_HIP(hipMemcpy(base, maps.data(), maps.size() * sizeof(float), hipMemcpyHostToDevice));
+    if (!dets.empty()) SYLDET_HIP(hipMemcpy(base + n_maps, dets.data(), dets.size() * sizeof(sd::TrainDetDev), hipMemcpyHostToDevice));
+    if (!row_begin.empty()) SYLDET_HIP(hipMemcpy(base + n_maps + n_dets, row_begin.data(), row_begin.size() * sizeof(int32_t), hipMemcpyHostToDevice));
+    d.maps = (const float *)base;
+    t->d_dets = r ? (const sd::TrainDetDev *)(base + n_maps) : nullptr;
+    t->d_row_begin = r ? (const int32_t *)(base + n_maps + n_dets) : nullptr;
+    t->desc = d;
+    *out = t.release();
+    return SYLDET_OK;
+}
+
+int syldet_trainer_destroy(syldet_trainer_t *t)
+{
+    if (!t) return SYLDET_OK;
+    if (t->d_fixed.ptr || t->d_part.ptr || t->d_labels.ptr) (void)hipSetDevice(t->bank.device);
+    t->d_fixed.release();
+    t->d_part.release();
+    t->d_labels.release();
+    delete t;
+    return SYLDET_OK;
+}
+
+int syldet_trainer_shape(const syldet_trainer_t *t, int32_t *n_detectors, int64_t *n_params, int32_t *n_out, int32_t *tile)
+{
+    if (!t) return fail(SYLDET_ERR_INVALID_ARGUMENT, "NULL argument");
+    if (n_detectors) *n_detectors = t->D;
+    if (n_params) *n_params = t->P;
+    if (n_out) *n_out = t->desc.O;
+    if (tile) *tile = t->desc.tile;
+    return SYLDET_OK;
+}
+
+int syldet_train_targets_device(syldet_trainer_t *t, const int64_t *labels, const int64_t *label_begin, const int32_t *label_output,
+                                int64_t half_width_samples, float weight_positive, float weight_negative, int64_t n_evals, float *d_targets,
+                                float *d_weights, void *hip_stream)
+{
+    if (!t) return fail(SYLDET_ERR_INVALID_ARGUMENT, "NULL handle");
+    if (!label_begin) return fail(SYLDET_ERR_INVALID_ARGUMENT, "NULL label_begin");
+    if (label_begin[0] != 0) return fail(SYLDET_ERR_INVALID_ARGUMENT, "label_begin[0] must be 0");
+    for (int d = 0; d < t->D; d++)
+        if (label_begin[d + 1] < label_begin[d]) return fail(SYLDET_ERR_INVALID_ARGUMENT, "label_begin[" + std::to_string(d + 1) + "] decreases");
+    const int64_t n_labels = label_begin[t->D];
+    if (n_labels > 0 && !labels) return fail(SYLDET_ERR_INVALID_ARGUMENT, "NULL labels");
+    for (int d = 0; d < t->D; d++)
+        for (int64_t j = label_begin[d]; j + 1 < label_begin[d + 1]; j++)
+            if (labels[j + 1] < labels[j])
+                return fail(SYLDET_ERR_INVALID_ARGUMENT, "detector " + std::to_string(d) + ": label " + std::to_string(j + 1 - label_begin[d]) + " is not sorted");
+    if (int st = outputs_arg(label_output, n_labels, t->desc.O)) return st;
+    if (int st = half_width_arg(half_width_samples)) return st;
+    if (int st = class_weights(weight_positive, weight_negative)) return st;
+    if (n_evals < 0) return fail(SYLDET_ERR_INVALID_ARGUMENT, "n_evals is negative");
+    if (t->packed && n_evals != t->row_evals)
+        return fail(SYLDET_ERR_INVALID_ARGUMENT, "n_evals must be the packed rows' " + std::to_string(t->row_evals) + " evaluations");
+    if (n_evals > ((int64_t)1 << 31)) return fail(SYLDET_ERR_UNSUPPORTED, "more than 2^31 evaluations a row");
+    const int rows = t->bank.channels;
+    if (n_evals > 0 && rows > 0 && (!d_targets || !d_weights)) return fail(SYLDET_ERR_INVALID_ARGUMENT, "NULL argument");
+    hipStream_t stream = (hipStream_t)hip_stream;
+    SYLDET_HIP(hipSetDevice(t->bank.device));
+    const size_t nb = ((size_t)t->D + 1) * sizeof(int64_t), nl = (size_t)n_labels * sizeof(int64_t), no = (size_t)n_labels * sizeof(int32_t);
+    const bool same = t->has_labels && std::memcmp(t->begin.data(), label_begin, nb) == 0 &&
+                      (n_labels == 0 || std::memcmp(t->labels.data(), labels, nl) == 0) && t->has_output == (label_output != nullptr) &&
+                      (!label_output || n_labels == 0 || std::memcmp(t->output.data(), label_output, no) == 0);
+    if (!same) {
+        // other labels than the kept ones (the first call always): behind the last call, one blocking copy
+        if (t->has_labels) SYLDET_HIP(hipStreamSynchronize(t->last));
+        t->has_labels = false;
+        try {
+            t->begin.assign(label_begin, label_begin + t->D + 1);
+            t->labels.assign(labels, labels + n_labels);
+            if (label_output) t->output.assign(label_output, label_output + n_labels);
+            else t->output.clear();
+        } catch (const std::bad_alloc &) {
+            return fail(SYLDET_ERR_OUT_OF_MEMORY, "out of memory");
+        }
+        if (int st = t->d_labels.reserve(up16(nb) + up16(nl) + up16(no) + 16)) return st;
+        char *base = (char *)t->d_labels.ptr;
+        SYLDET_HIP(hipMemcpy(base, label_begin, nb, hipMemcpyHostToDevice));
+        if (n_labels > 0) SYLDET_HIP(hipMemcpy(base + up16(nb), labels, nl, hipMemcpyHostToDevice));
+        if (n_labels > 0 && label_output) SYLDET_HIP(hipMemcpy(base + up16(nb) + up16(nl), label_output, no, hipMemcpyHostToDevice));
+        t->has_output = label_output != nullptr;
+        t->has_labels = true;
+    }
+    t->last = stream;
+    if (n_evals == 0 || rows == 0) return SYLDET_OK;
+    char *base = (char *)t->d_labels.ptr;
+    sd::TrainTargetsDesc d{};
+    d.dets = t->d_dets;
+    d.row_begin = t->d_row_begin;
+    d.label_begin = (const int64_t *)base;
+    d.labels = (const int64_t *)(base + up16(nb));
+    d.label_output = label_output ? (const int32_t *)(base + up16(nb) + up16(nl)) : nullptr;
+    d.rows = rows;
+    d.n_out = t->desc.O;
+    d.first_index = t->bank.geom.first_index;
+    d.hop = t->bank.geom.hop;
+    d.half_width = half_width_samples;
+    d.weight_positive = weight_positive;
+    d.weight_negative = weight_negative;
+    t->h->prof_begin();
+    KernelTimer timer(t->h, stream, "train_targets_kernel");
+    SYLDET_HIP(sd::launch_train_targets(d, n_evals, d_targets, d_weights, stream));
+    return SYLDET_OK;
+}
+
+int syldet_train_targets_host(const int64_t *labels, int64_t n_labels, const int32_t *label_output, int32_t n_out, int64_t half_width_samples,
+                              float weight_positive, float weight_negative, int64_t first_index, int64_t hop, int64_t n_evals, float *targets,
+                              float *weights)
+{
+    if (n_out < 1 || n_out > SYLDET_TRAIN_MAX_OUTPUTS) return fail(SYLDET_ERR_INVALID_ARGUMENT, "n_out must be in [1, " + std::to_string(SYLDET_TRAIN_MAX_OUTPUTS) + "]");
+    if (n_labels < 0 || n_evals < 0 || (n_labels > 0 && !labels) || (n_evals > 0 && (!targets || !weights)))
+        return fail(SYLDET_ERR_INVALID_ARGUMENT, "a NULL array or a negative count");
+    for (int64_t j = 0; j + 1 < n_labels; j++)
+        if (labels[j + 1] < labels[j]) return fail(SYLDET_ERR_INVALID_ARGUMENT, "label " + std::to_string(j + 1) + " is not sorted");
+    if (int st = outputs_arg(label_output, n_labels, n_out)) return st;
+    if (int st = half_width_arg(half_width_samples)) return st;
+    if (int st = class_weights(weight_positive, weight_negative)) return st;
+    if (hop < 1 || hop > ((int64_t)1 << 30) || n_evals > ((int64_t)1 << 31) || first_index <= -sd::kTrainIndexLimit / 2 || first_index >= sd::kTrainIndexLimit / 2)
+        return fail(SYLDET_ERR_INVALID_ARGUMENT, "hop outside [1, 2^30], more than 2^31 evaluations, or first_index out of range");
+    for (int64_t e = 0; e < n_evals; e++)
+        sd::train_target_write(sd::train_target_mask(first_index + e * hop, labels, label_output, n_labels, half_width_samples), n_out, weight_positive,
+                               weight_negative, targets + e * n_out, weights + e);
+    return SYLDET_OK;
+}
+
+int syldet_train_gradient_device(syldet_trainer_t *t, const float *d_columns, int64_t n_frames, int64_t row_stride, const float *d_params,
+                                 const float *d_targets, const float *d_weights, int64_t n_evals, double *d_loss, float *d_gradient, void *hip_stream)
+{
+    if (!t) return fail(SYLDET_ERR_INVALID_ARGUMENT, "NULL handle");
+    if (!d_params || !d_loss || !d_gradient) return fail(SYLDET_ERR_INVALID_ARGUMENT, "NULL argument");
+    if (n_evals < 0 || n_frames < 0) return fail(SYLDET_ERR_INVALID_ARGUMENT, "n_evals or n_frames is negative");
+    const sd::TrainDesc &d = t->desc;
+    if (t->packed && (n_evals != t->row_evals || n_frames != t->row_frames))
+        return fail(SYLDET_ERR_INVALID_ARGUMENT, "n_evals and n_frames must be the packed rows' " + std::to_string(t->row_evals) + " evaluations and " +
+                                                     std::to_string(t->row_frames) + " frames");
+    if (n_evals > 0 && n_frames < n_evals + d.T - 1)
+        return fail(SYLDET_ERR_INVALID_ARGUMENT, std::to_string(n_evals) + " evaluations read " + std::to_string(n_evals + d.T - 1) + " frames, " +
+                                                     std::to_string(n_frames) + " given");
+    if (n_frames > ((int64_t)1 << 40) / d.F) return fail(SYLDET_ERR_INVALID_ARGUMENT, "n_frames x bins is above 2^40");
+    if (row_stride == 0) row_stride = n_frames * d.F;
+    if (row_stride < n_frames * d.F)
+        return fail(SYLDET_ERR_INVALID_ARGUMENT, "row_stride " + std::to_string(row_stride) + " is below the " + std::to_string(n_frames * d.F) + " elements of a row");
+    const int rows = t->bank.channels;
+    if (n_evals > 0 && rows > 0 && (!d_columns || !d_targets || !d_weights)) return fail(SYLDET_ERR_INVALID_ARGUMENT, "NULL argument");
+    if ((int64_t)rows * ((n_evals + d.tile - 1) / d.tile) > 0x7fffffff) return fail(SYLDET_ERR_UNSUPPORTED, "more than 2^31 - 1 tiles");
+    hipStream_t stream = (hipStream_t)hip_stream;
+    SYLDET_HIP(hipSetDevice(t->bank.device));
+    t->last = stream;
+    const int groups = sd::train_groups(d, rows, n_evals);
+    t->h->prof_begin();
+    {
+        KernelTimer timer(t->h, stream, "train_gradient_kernel");
+        SYLDET_HIP(sd::launch_train_gradient(d, d_columns, row_stride, rows, d_params, d_targets, d_weights, n_evals, (double *)t->d_part.ptr, stream));
+    }
+    KernelTimer timer(t->h, stream, "train_combine_kernel");
+    SYLDET_HIP(sd::launch_train_combine(d, groups, (const double *)t->d_part.ptr, d_loss, d_gradient, stream));
+    return SYLDET_OK;
+}
+
+}  // extern "C"

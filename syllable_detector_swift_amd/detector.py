@@ -944,6 +944,13 @@ class SyllableDetector:
         launch.  before, after: in units of the source, default timeRange - 1 each."""
         return Aligner(self, source, before, after)
 
+    # ---- training: loss and gradient of the network over labelled evaluations --------------
+    def trainer(self) -> "Trainer":
+        """A Trainer over this bank's channels (syldet_trainer_create): targets and class weights from labels, and loss and
+        gradient of the two layers' parameters straight from the columns spectrogram() made.  A plain bank of a two-layer
+        network, up to 16 hidden units and 4 outputs."""
+        return Trainer(self)
+
     # ---- batch, host arrays -------------------------------------------------------
     def runHost(self, samples: np.ndarray, outputs: Optional[np.ndarray] = None, flags: Optional[np.ndarray] = None) -> Tuple[np.ndarray, np.ndarray]:
         """syldet_run: the batch call on host arrays, pipelined along time inside the library.  `outputs` / `flags`: arrays to
@@ -1467,6 +1474,12 @@ class Recordings:
         the detector's run(rows) outputs, or the rows themselves."""
         return Aligner(self.detector, source, before, after, recordings=self)
 
+    def trainer(self) -> "Trainer":
+        """A Trainer whose detectors are these recordings: labels count from each recording's own start, and whatever lies
+        between two recordings or behind the last one gets weight 0 and is never read (SyllableDetector.trainer).  The columns
+        are spectrogram(rows)."""
+        return Trainer(self.detector, recordings=self)
+
 
 def _score_args(thresholds, labels):
     thr = np.ascontiguousarray(thresholds, dtype=np.float64).reshape(-1)
@@ -1776,6 +1789,237 @@ def alignStatsHost(windows, present):
                                            count.ctypes.data_as(_abi.c_int64_p), total.ctypes.data_as(_abi.c_double_p),
                                            squares.ctypes.data_as(_abi.c_double_p)))
     return count.reshape(shape), total.reshape(shape), squares.reshape(shape)
+
+
+def _train_label_args(labels, labelOutputs):
+    """(flat labels, begin, flat outputs or None) of per-detector lists"""
+    _, flat, begin = _score_args([0.0], labels)
+    if labelOutputs is None:
+        return flat, begin, None
+    outs = [np.ascontiguousarray(o, dtype=np.int32).reshape(-1) for o in labelOutputs]
+    if len(outs) != len(begin) - 1 or any(o.size != n for o, n in zip(outs, np.diff(begin))):
+        raise ValueError("labelOutputs must hold one output per label, detector by detector")
+    return flat, begin, np.ascontiguousarray(np.concatenate(outs) if outs else np.zeros(0, np.int32), dtype=np.int32)
+
+
+class Trainer:
+    """Training (syldet_trainer_*, include/syldet.h "training"): loss and gradient of a two-layer network's parameters over
+    weighted, labelled evaluations, straight from the columns.  A detector is a channel of the bank, or (made by
+    Recordings.trainer) a recording.  shape = (detectors, parameters, outputs); the parameters are one flat float32 vector,
+    layer0.weights [H][I], layer0.biases [H], layer1.weights [O][H], layer1.biases [O]; everything else of the network is the
+    bank's configuration's.  The optimiser is torch's.  The detector (and the Recordings) must outlive it."""
+
+    def __init__(self, detector: SyllableDetector, recordings: Optional[Recordings] = None):
+        self.detector = detector
+        self.recordings = recordings
+        self._h = _abi.Handle()
+        check(_abi.lib.syldet_trainer_create(detector._h, None if recordings is None else recordings._h, C.byref(self._h)))
+        d, p, o, tile = C.c_int32(), C.c_int64(), C.c_int32(), C.c_int32()
+        check(_abi.lib.syldet_trainer_shape(self._h, C.byref(d), C.byref(p), C.byref(o), C.byref(tile)))
+        self.shape = (d.value, p.value, o.value)
+        self.count, self.paramCount, self.outputs, self.tile = d.value, p.value, o.value, tile.value
+
+    def close(self):
+        if getattr(self, "_h", None):
+            _abi.lib.syldet_trainer_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    # ---- parameters <-> configuration ----
+    def params(self, config: Optional[SyllableDetectorConfig] = None):
+        """The flat float32 parameter vector of a configuration's two layers (default: the bank's), on the detector's device."""
+        torch = _torch()
+        layers = (config or self.detector.config).net.layers
+        flat = np.concatenate([np.asarray(a, np.float32).reshape(-1) for L in layers for a in (L.weights, L.biases)])
+        if len(layers) != 2 or flat.size != self.paramCount:
+            raise ValueError("the configuration's layers do not have the trainer's %d parameters" % self.paramCount)
+        return torch.from_numpy(flat).to("cuda:%d" % self.detector.device)
+
+    def configWith(self, params) -> SyllableDetectorConfig:
+        """A deep copy of the bank's configuration with the two layers' weights and biases replaced by `params`."""
+        import copy
+        p = (params.detach().cpu().numpy() if hasattr(params, "detach") else np.asarray(params)).astype(np.float32).reshape(-1)
+        if p.size != self.paramCount:
+            raise ValueError("params must hold %d values" % self.paramCount)
+        cfg = copy.deepcopy(self.detector.config)
+        at = 0
+        for L in cfg.net.layers:
+            L.weights = p[at:at + L.outputs * L.inputs].reshape(L.outputs, L.inputs).copy()
+            at += L.outputs * L.inputs
+            L.biases = p[at:at + L.outputs].copy()
+            at += L.outputs
+        return cfg
+
+    # ---- targets ----
+    def _n_evals(self, n_evals):
+        if self.recordings is not None:
+            return self.recordings.rowEvaluations
+        if n_evals is None:
+            raise ValueError("n_evals is needed on a bank's channels")
+        return int(n_evals)
+
+    def targets(self, labels, halfWidth: int, weightPositive: float, weightNegative: float, labelOutputs=None, n_evals: Optional[int] = None,
+                stream=None):
+        """labels: a list of arrays, one per detector, of sorted labelled sample numbers (the scorer's); labelOutputs: each label's
+        output (default all 0) -> (targets [C, n_evals, O], weights [C, n_evals]) float32 on the device: a target is 1 within
+        halfWidth samples of a label of its output, an evaluation's weight weightPositive where any target is 1, else
+        weightNegative, and 0 wherever no detector is.  n_evals: evaluations a row (recordings: theirs).  One launch."""
+        torch = _torch()
+        det = self.detector
+        labels = list(labels)
+        if len(labels) != self.count:
+            raise ValueError("one array of labels per detector (%d given, %d detectors)" % (len(labels), self.count))
+        flat, begin, outs = _train_label_args(labels, labelOutputs)
+        E = self._n_evals(n_evals)
+        dev = "cuda:%d" % det.device
+        t = torch.empty((det.channels, E, self.outputs), dtype=torch.float32, device=dev)
+        w = torch.empty((det.channels, E), dtype=torch.float32, device=dev)
+        check(_abi.lib.syldet_train_targets_device(self._h, flat.ctypes.data_as(_abi.c_int64_p), begin.ctypes.data_as(_abi.c_int64_p),
+                                                   None if outs is None else outs.ctypes.data_as(_abi.c_int32_p), int(halfWidth), float(weightPositive),
+                                                   float(weightNegative), E, t.data_ptr(), w.data_ptr(), det._stream_ptr(stream)))
+        return t, w
+
+    # ---- loss and gradient ----
+    def _check(self, cols, params, targets, weights):
+        torch = _torch()
+        det = self.detector
+        bins = det.geometry.bins
+
+        def ok(x, dims):
+            return x.is_cuda and x.dtype == torch.float32 and x.dim() == dims and x.is_contiguous() and x.device.index == det.device
+
+        if not (ok(cols, 3) and cols.shape[0] == det.channels and cols.shape[2] == bins):
+            raise ValueError("cols must be a contiguous float32 CUDA tensor [channels, n_frames, %d] on the detector's device" % bins)
+        if not (ok(params, 1) and params.numel() == self.paramCount):
+            raise ValueError("params must be a contiguous float32 CUDA tensor of %d values" % self.paramCount)
+        if not (ok(weights, 2) and weights.shape[0] == det.channels):
+            raise ValueError("weights must be a contiguous float32 CUDA tensor [channels, n_evals]")
+        if not (ok(targets, 3) and tuple(targets.shape) == (det.channels, weights.shape[1], self.outputs)):
+            raise ValueError("targets must be a contiguous float32 CUDA tensor [channels, n_evals, %d]" % self.outputs)
+
+    def gradient(self, cols, params, targets, weights, out=None, stream=None):
+        """cols [C, n_frames, bins] as spectrogram() wrote them, params [P], targets and weights as targets() made them (or any
+        others of those shapes) -> (loss, weightSum, grad): two 0-dim float64 tensors -- the sum over the selected evaluations
+        (weight > 0) of w sum_o (y - t)^2, and the sum of their weights -- and dloss/dparams [P] float32, on the device.  Launches
+        only, the same bits for the same arrays.  out: a (float64 [2], float32 [P]) pair to write into.  Asynchronous on `stream`."""
+        torch = _torch()
+        self._check(cols, params, targets, weights)
+        if out is None:
+            out = (torch.empty(2, dtype=torch.float64, device=cols.device), torch.empty(self.paramCount, dtype=torch.float32, device=cols.device))
+        loss, grad = out
+        if not (loss.is_cuda and loss.dtype == torch.float64 and loss.numel() == 2 and loss.is_contiguous() and grad.is_cuda
+                and grad.dtype == torch.float32 and grad.numel() == self.paramCount and grad.is_contiguous()):
+            raise ValueError("out must be a (float64 [2], float32 [%d]) pair of contiguous CUDA tensors" % self.paramCount)
+        check(_abi.lib.syldet_train_gradient_device(self._h, cols.data_ptr(), int(cols.shape[1]), 0, params.data_ptr(), targets.data_ptr(),
+                                                    weights.data_ptr(), int(weights.shape[1]), loss.data_ptr(), grad.data_ptr(),
+                                                    self.detector._stream_ptr(stream)))
+        return loss[0], loss[1], grad
+
+    def fit(self, cols, targets, weights, params, steps: int, lr: float = 0.01):
+        """`steps` full-batch steps of torch.optim.Adam on the mean loss L / Wsum, from `params`: a leaf tensor whose .grad the
+        library fills.  -> (params [P] float32 on the device, the mean loss in front of every step as a list of floats)."""
+        torch = _torch()
+        p = params.detach().clone().requires_grad_(True)
+        opt = torch.optim.Adam([p], lr=lr)
+        out = (torch.empty(2, dtype=torch.float64, device=cols.device), torch.empty(self.paramCount, dtype=torch.float32, device=cols.device))
+        history = []
+        for _ in range(int(steps)):
+            loss, wsum, grad = self.gradient(cols, p.detach(), targets, weights, out=out)
+            scale = torch.where(wsum > 0, 1.0 / wsum, torch.zeros_like(wsum))
+            history.append(loss * scale)
+            p.grad = (grad * scale.to(torch.float32))
+            opt.step()
+        history = torch.stack(history).cpu().tolist() if history else []
+        return p.detach(), history
+
+    def fitInputMap(self, cols, events, chunk: int = 1 << 16) -> SyllableDetectorConfig:
+        """Refits the configuration's first mapminmax input function to data, as the MATLAB side does before it trains: the
+        network inputs at `events` (a list of arrays of sample numbers, one per detector; an event's input is the evaluation it
+        anchors, and an event whose input is not whole is left out) are cut with an Aligner (before = timeRange - 1, after = 0,
+        `chunk` events at a time), the functions in front of the map are applied with torch, and per input position
+        xOffsets = min, gains = 2 / (max - min) (1 where they are equal), yMin = -1.  -> a new configuration."""
+        import copy
+        torch = _torch()
+        det = self.detector
+        cfg = copy.deepcopy(det.config)
+        fns = cfg.net.inputProcessing
+        at = next((k for k, f in enumerate(fns) if f.function == "mapminmax"), None)
+        if at is None:
+            raise ValueError("the configuration has no mapminmax input function")
+        events = [np.ascontiguousarray(e, dtype=np.int64).reshape(-1) for e in events]
+        if len(events) != self.count:
+            raise ValueError("one array of events per detector (%d given, %d detectors)" % (len(events), self.count))
+        T = int(cfg.timeRange)
+        lo = hi = None
+        with Aligner(det, "columns", T - 1, 0, recordings=self.recordings) as al:
+            longest = max([e.size for e in events] + [0])
+            for c0 in range(0, longest, max(int(chunk) // max(self.count, 1), 1)):
+                part = [e[c0:c0 + max(int(chunk) // max(self.count, 1), 1)] for e in events]
+                x = al.windows(cols, part, fill=float("nan")).reshape(-1, T * det.geometry.bins)
+                x = x[~torch.isnan(x).any(dim=1)]
+                if x.shape[0] == 0:
+                    continue
+                if cfg.spectrogramScaling == "log":
+                    x = torch.log(x)
+                elif cfg.spectrogramScaling == "db":
+                    x = 20.0 * torch.log10(x)
+                for f in fns[:at]:
+                    if f.function == "l2normalize":
+                        x = x / torch.sqrt((x * x).sum(dim=1, keepdim=True))
+                    elif f.function == "normalize":
+                        mn, mx = x.min(dim=1, keepdim=True).values, x.max(dim=1, keepdim=True).values
+                        x = torch.where(mx > mn, (x - mn) * (2.0 / (mx - mn)) - 1.0, torch.full_like(x, -1.0))
+                    elif f.function == "normalizestd":
+                        x = (x - x.mean(dim=1, keepdim=True)) / x.std(dim=1, unbiased=False, keepdim=True)
+                    else:
+                        x = (x - torch.from_numpy(np.asarray(f.xOffsets, np.float32)).to(x.device)) * torch.from_numpy(np.asarray(f.gains, np.float32)).to(x.device) + float(f.y)
+                x = x[torch.isfinite(x).all(dim=1)]
+                if x.shape[0] == 0:
+                    continue
+                mn, mx = x.min(dim=0).values, x.max(dim=0).values
+                lo = mn if lo is None else torch.minimum(lo, mn)
+                hi = mx if hi is None else torch.maximum(hi, mx)
+        if lo is None:
+            raise ValueError("no event has a whole network input")
+        lo, hi = lo.cpu().numpy().astype(np.float32), hi.cpu().numpy().astype(np.float32)
+        rng = hi - lo
+        fns[at].xOffsets = lo
+        fns[at].gains = np.where(rng > 0, np.float32(2.0) / np.where(rng > 0, rng, 1), np.float32(1.0)).astype(np.float32)
+        fns[at].y = -1.0
+        return cfg
+
+
+def trainParamCount(config: SyllableDetectorConfig) -> int:
+    """syldet_train_param_count: the parameters H I + H + O H + O of a configuration of two layers, no device needed."""
+    c, keep = config.to_abi()
+    n = C.c_int64()
+    check(_abi.lib.syldet_train_param_count(C.byref(c), C.byref(n)))
+    del keep
+    return int(n.value)
+
+
+def trainTargetsHost(labels, n_evals: int, halfWidth: int, weightPositive: float, weightNegative: float, firstIndex: int, hop: int, outputs: int = 1,
+                     labelOutputs=None):
+    """syldet_train_targets_host: one detector's targets on the host, no device needed -> (targets [n_evals, outputs],
+    weights [n_evals]) float32."""
+    flat, _, outs = _train_label_args([labels], None if labelOutputs is None else [labelOutputs])
+    t = np.zeros((max(int(n_evals), 0), max(int(outputs), 0)), np.float32)
+    w = np.zeros(max(int(n_evals), 0), np.float32)
+    check(_abi.lib.syldet_train_targets_host(flat.ctypes.data_as(_abi.c_int64_p), flat.size, None if outs is None else outs.ctypes.data_as(_abi.c_int32_p),
+                                             int(outputs), int(halfWidth), float(weightPositive), float(weightNegative), int(firstIndex), int(hop),
+                                             int(n_evals), t.ctypes.data_as(_abi.c_float_p), w.ctypes.data_as(_abi.c_float_p)))
+    return t, w
 
 
 def _pcm16(data) -> np.ndarray:
