@@ -175,13 +175,17 @@ def test_python_argument_errors_need_no_device():
 
 
 def test_the_tools_batch_path_loads_the_files_own_bytes():
-    with open(os.path.join(ROOT, "syllable_detector_swift_amd", "cli", "main.cpp")) as f:
-        main = f.read()
-    with open(os.path.join(ROOT, "syllable_detector_swift_amd", "cli", "wav.hpp")) as f:
-        wav = f.read()
+    def text(name):
+        with open(os.path.join(ROOT, "syllable_detector_swift_amd", "cli", name)) as f:
+            return f.read()
+
+    main, wav, batch_hpp, one_hpp, shared = text("main.cpp"), text("wav.hpp"), text("batch.hpp"), text("one_file.hpp"), text("align.hpp")
     assert "inline bool read_raw(" in wav
-    batch = main[main.index("int run_batch("):main.index("int process_batched(")]
-    batched = main[main.index("int process_batched("):main.index("int main(")]
+    assert "process_batched(run)" in main and "#include \"batch.hpp\"" in main and "#include \"one_file.hpp\"" in batch_hpp and "#include \"align.hpp\"" in one_hpp
+    # the batch path: the plan, the stages and run_batch, with what they share with the one-file path; the gatherer: process_batched
+    batch = batch_hpp[batch_hpp.index("struct BatchPlan"):batch_hpp.index("int process_batched(")] + shared
+    batched = batch_hpp[batch_hpp.index("int process_batched("):]
+    assert "int run_batch(" in batch and "int load_and_run(" in batch and "BatchPlan plan_batch(" in batch
     assert "syldet_recordings_load_pcm_device(" in batch and "syldet_recordings_load_sinc_pcm_device(" in batch
     # an all-16-bit batch still runs int16 rows
     assert "syldet_recordings_load_device_s16(" in batch and "syldet_run_device_s16(" in batch and "syldet_recordings_load_sinc_device_s16(" in batch
@@ -189,5 +193,6 @@ def test_the_tools_batch_path_loads_the_files_own_bytes():
     assert "wav::read_raw(" in batched and "wav::read(" not in batched and "wav::read_s16(" not in batched
     assert "1.0f / 32768.0f" not in batch and "wav::read" not in batch and "syldet_pcm_decode" not in batch
     # the one-file path is the reader's, as before
-    one = main[main.index("int process_file("):main.index("struct BatchFile")]
+    one = one_hpp[one_hpp.index("struct OneFile"):] + shared
+    assert "int process_file(" in one and "int read_and_probe(" in one
     assert "wav::read(" in one and "read_raw" not in one
