@@ -1324,6 +1324,79 @@ int syldet_train_gradient_device(syldet_trainer_t *t, const float *d_columns, in
                                  const float *d_params, const float *d_targets, const float *d_weights, int64_t n_evals,
                                  double *d_loss, float *d_gradient, void *hip_stream);
 
+/* ---- template matching: find a syllable's occurrences in the columns ----
+ * The scorer, the aligner and the trainer all start from labels; in the workflow the reference belongs to, labels come from matching
+ * one exemplar of the syllable against the whole archive.  These calls do that on the columns that lie on the device: exemplar ->
+ * matches -> syldet_train_targets_device / the scorer / syldet_align_device.  THE CONVENTION is the library's own:
+ * A DETECTOR, its frames u in [0, U_d) and the placement of a packed recording's frames in its row are the aligner's
+ *   SYLDET_ALIGN_COLUMNS definitions.  The source is [rows][n_frames][bins] as syldet_spectrogram_device wrote it (linear values),
+ *   rows row_stride ELEMENTS apart (0: n_frames bins).
+ * THE TEMPLATE is n >= 1 frames of `bins` floats, every value finite, not all zero, n bins <= SYLDET_MATCH_MAX_TEMPLATE; bins must
+ *   be the bank's.  At creation the library makes t^ = fp32(t / ||t||_2), the norm and the division in fp64;
+ *   syldet_matcher_template returns t^, which is what every model uses.
+ * THE SCORE of position p of a detector, 0 <= p <= U_d - n, is the cosine between its window and the template:
+ *     s(p) = dot / sqrt(E),   dot = sum_{j < n, b < bins} t^[j][b] x[p + j][b],   E = sum_{j < n, b < bins} x[p + j][b]^2
+ *   in fp32; nothing is subtracted.  E == 0 gives +0.0 (silence matches nothing); a window that holds a NaN or an Inf gives NaN, a
+ *   window that holds neither the score of its own values; windows whose E would pass 2^100 are outside the contract.
+ *   A SCORE IS A FUNCTION OF ITS WINDOW'S VALUES AND t^ ALONE: it has the same bits wherever the window lies in a row, a tile, a
+ *   launch or a bank, so a packed recording's scores are its scores through a one-channel handle, bit for bit.  (dot is one chain
+ *   of fused multiply-adds a group of 4 bins -- groups g, g + 4, .. of the padded bins together, up to four such chains -- over
+ *   the window in (frame, bin) order from +0.0, the chains added in order; E is the sum, from the window's first frame on, of
+ *   the frames' energies, each a chain over its bins; frames outside the window only ever meet zeros, and a NaN or an Inf enters
+ *   the products as zero and reaches the score through E alone.)
+ * THE RESULT is d_scores [rows][n_frames] fp32, every element written exactly once: element first + p of a detector's row is s(p)
+ *   (first: 0 for a channel, slot.first_eval for a recording); every other element -- the last n - 1 positions of a detector, frames
+ *   between recordings, a row's tail, all positions of a detector shorter than the template -- is NaN.
+ * PEAKS.  Given threshold (not NaN; -inf allowed) and separation S (0 <= S <= SYLDET_MATCH_MAX_SEPARATION frames), position p is a
+ *   MATCH iff s(p) is not NaN, s(p) >= threshold, s(q) < s(p) for every non-NaN q in [p - S, p) and s(q) <= s(p) for every non-NaN q
+ *   in (p, p + S] of the same detector: the earliest position of a tie wins, a NaN neither matches nor suppresses.  A pure function of
+ *   the fp32 scores (csrc/match_peaks.hpp: one text for the kernel, the host and a stand-alone test).
+ * EVENTS.  A match at p with anchor frame a (0 <= a < n, fixed at creation; negative: n - 1) is the sample number
+ *   origin + (p + a) hop with origin and hop of syldet_align_anchor(COLUMNS): its anchor frame under the aligner is p + a, and with
+ *   a = n - 1 an aligner of before = n - 1, after = 0 cuts exactly the matched window.  d_events [D][capacity] int64 ascending,
+ *   d_counts [D] int64 (may exceed capacity), d_event_scores [D][capacity] fp32 or NULL: the detection calls' tables, which go as
+ *   they are into syldet_align_device (event_stride = capacity), the scorer and syldet_train_targets_device.
+ *   syldet_matcher_create    h: the bank; r: NULL (D = its channels) or a packed-recordings handle of h (D = its recordings).  t^ and,
+ *       for recordings, the slots go to the device once.  h, and r if given, must outlive the matcher.
+ *   syldet_matcher_shape     D, n, bins, the anchor, and whether the score kernel takes the matrix form (each may be NULL)
+ *   syldet_matcher_template  t^ [n][bins]
+ *   syldet_match_scores_device   one launch.  "match_scores_mfma_kernel": a workgroup stages the frames of 256 positions in LDS once
+ *       and takes dot on v_mfma_f32_16x16x4_f32 against a Toeplitz operand of the template, the frames' energies from the same
+ *       staged values; "match_scores_plain_kernel", one thread a position, where that tile does not fit 64 KB of LDS -- a function
+ *       of n and bins alone (29 bins at n = 91 and below take the matrix form).  With r n_frames must be
+ *       syldet_count_frames(h, row_samples).
+ *   syldet_match_peaks_device    one launch ("match_peaks_kernel": a workgroup a detector; maxima of blocks of 2^k positions, two of
+ *       which cover any S, so the work a position grows with log S; a scan places the events in order).
+ *   syldet_match_normalize_host  host only: t^ of a template
+ *   syldet_match_scores_host     host only, one detector: columns [n_frames][bins] -> scores [n_frames] as THE RESULT has them; fp32
+ *       in an order of the library's choice, which need not be the device's
+ *   syldet_match_peaks_host      host only, one detector in plain C++ (the text the kernel runs): scores [n_positions] -> events,
+ *       *count, event_scores (may be NULL); origin in [0, 2^32), hop in [1, 2^31).
+ * Statuses, decided before any device is touched; a refused call leaves its outputs as they were.  SYLDET_ERR_INVALID_ARGUMENT: a
+ * NULL handle or pointer (the device arrays may be NULL where n_frames is 0, d_events where capacity is 0), a template outside the
+ * rules above, other bins than the bank's, an anchor >= n, a negative n_frames or capacity, a wrong n_frames with r, a row_stride
+ * smaller than a row needs, a NaN threshold, a separation outside its range.  SYLDET_ERR_UNSUPPORTED: a mixed bank of more than one
+ * class, as syldet_spectrogram* answers there.  A sharded bank has none: the language bindings answer SYLDET_ERR_UNSUPPORTED.
+ * THE LAUNCH RULE: the matcher keeps t^ and the slots on the device from creation; both device calls are launches only -- no
+ * allocation, no synchronisation, no copy -- and their number does not depend on D.  One stream at a time, as the bank; every call
+ * records into the profile of h (syldet_profile) under its kernel's name.                                                        */
+#define SYLDET_MATCH_MAX_TEMPLATE   32768
+#define SYLDET_MATCH_MAX_SEPARATION 4096
+typedef struct syldet_matcher syldet_matcher_t;
+int syldet_matcher_create(const syldet_t *h, const syldet_recordings_t *r, const float *templ, int32_t n, int32_t bins, int32_t anchor,
+                          syldet_matcher_t **out);
+int syldet_matcher_destroy(syldet_matcher_t *m);
+int syldet_matcher_shape(const syldet_matcher_t *m, int32_t *n_detectors, int32_t *n, int32_t *bins, int32_t *anchor, int32_t *matrix_form);
+int syldet_matcher_template(const syldet_matcher_t *m, float *t_hat);
+int syldet_match_scores_device(syldet_matcher_t *m, const float *d_columns, int64_t n_frames, int64_t row_stride, float *d_scores,
+                               void *hip_stream);
+int syldet_match_peaks_device(syldet_matcher_t *m, const float *d_scores, int64_t n_frames, float threshold, int32_t separation,
+                              int64_t *d_events, int64_t capacity, int64_t *d_counts, float *d_event_scores, void *hip_stream);
+int syldet_match_normalize_host(const float *templ, int32_t n, int32_t bins, float *t_hat);
+int syldet_match_scores_host(const float *t_hat, int32_t n, int32_t bins, const float *columns, int64_t n_frames, float *scores);
+int syldet_match_peaks_host(const float *scores, int64_t n_positions, float threshold, int32_t separation, int64_t origin, int64_t hop,
+                            int32_t anchor, int64_t *events, int64_t capacity, int64_t *count, float *event_scores);
+
 #ifdef __cplusplus
 }
 #endif

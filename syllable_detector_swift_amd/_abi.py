@@ -106,6 +106,9 @@ ALIGN_BLOCK = 256
 # the trainer's envelope (SYLDET_TRAIN_*)
 TRAIN_MAX_HIDDEN, TRAIN_MAX_OUTPUTS = 16, 4
 
+# the matcher's limits (SYLDET_MATCH_*)
+MATCH_MAX_TEMPLATE, MATCH_MAX_SEPARATION = 32768, 4096
+
 Handle = C.c_void_p
 Config_p = C.POINTER(Config)
 c_void_pp = C.POINTER(C.c_void_p)
@@ -305,6 +308,17 @@ SIGNATURES = {
                                             c_float_p, c_float_p]),
     "syldet_train_gradient_device": (C.c_int, [Handle, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p,
                                                C.c_void_p, C.c_void_p]),
+    "syldet_matcher_create": (C.c_int, [Handle, Handle, c_float_p, C.c_int32, C.c_int32, C.c_int32, C.POINTER(Handle)]),
+    "syldet_matcher_destroy": (C.c_int, [Handle]),
+    "syldet_matcher_shape": (C.c_int, [Handle, c_int32_p, c_int32_p, c_int32_p, c_int32_p, c_int32_p]),
+    "syldet_matcher_template": (C.c_int, [Handle, c_float_p]),
+    "syldet_match_scores_device": (C.c_int, [Handle, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p]),
+    "syldet_match_peaks_device": (C.c_int, [Handle, C.c_void_p, C.c_int64, C.c_float, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p,
+                                            C.c_void_p]),
+    "syldet_match_normalize_host": (C.c_int, [c_float_p, C.c_int32, C.c_int32, c_float_p]),
+    "syldet_match_scores_host": (C.c_int, [c_float_p, C.c_int32, C.c_int32, c_float_p, C.c_int64, c_float_p]),
+    "syldet_match_peaks_host": (C.c_int, [c_float_p, C.c_int64, C.c_float, C.c_int32, C.c_int64, C.c_int64, C.c_int32, c_int64_p, C.c_int64,
+                                          c_int64_p, c_float_p]),
 }
 
 

@@ -66,6 +66,11 @@ class ShardedSyllableDetectorBank:
         from .config import SyllableDetectorError
         raise SyllableDetectorError(_abi.ERR_UNSUPPORTED, "training on a sharded bank: use a SyllableDetector per device")
 
+    def matcher(self, template, anchor=None):
+        """Template matching (SyllableDetector.matcher) has no sharded form: the columns lie on several devices."""
+        from .config import SyllableDetectorError
+        raise SyllableDetectorError(_abi.ERR_UNSUPPORTED, "template matching on a sharded bank: use a SyllableDetector per device")
+
     def __del__(self):
         try:
             self.close()

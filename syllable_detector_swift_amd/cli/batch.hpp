@@ -108,6 +108,8 @@ struct Batch {
     std::vector<uint8_t> lv_empty;
     // ... --align-dir: every recording's events, their windows (recording k's from al.begin[k]), and what decides presence
     Aligned al;
+    // ... --match: every recording's matches
+    std::vector<std::vector<int64_t>> matched;
     // --score: the recordings' labels in the recordings' order
     std::vector<int64_t> score_labels, score_begin{0};
 };
@@ -142,7 +144,7 @@ int load_and_run(Batch &b, BatchDevice &d)
     }
     const bool ran = b.ran = b.row_evals > 0;
     const int64_t rs = b.row_samples;
-    if (!ran && run.opt.dirs.levels.empty() && !run.align) return -1;   // every file shorter than one evaluation: no events (the input meter reads them all the same)
+    if (!ran && run.opt.dirs.levels.empty() && !run.align && !run.match) return -1;   // every file shorter than one evaluation: no events (the input meter reads them all the same)
     if (hipSetDevice(run.opt.device) != hipSuccess || hipStreamCreate(&b.stream) != hipSuccess) return 2;
     if (!d.d_src.alloc((size_t)p.total * p.el) || !d.d_rows.alloc((size_t)C * rs * (p.converting || !p.all16 ? sizeof(float) : sizeof(int16_t))) ||
         !d.d_out.alloc((size_t)C * b.row_evals * b.n_out * sizeof(float)) || !d.d_flags.alloc((size_t)C * b.row_evals) || !d.d_cnt.alloc((size_t)p.K * sizeof(int64_t))) return 2;
@@ -246,6 +248,40 @@ int batch_score(Batch &b, BatchDevice &d)
     return rc;
 }
 
+// The batch's rows as fp32 on the device: the rows the bank was fed, or -- a batch of 16-bit files -- loaded once more, as fp32, from
+// the same upload.  st: what the library said.  false: no memory.
+bool batch_rows(Batch &b, BatchDevice &d, const float *&rows, int &st)
+{
+    const BatchPlan &p = b.plan;
+    rows = (const float *)d.d_rows.p;
+    if (!(p.all16 && !p.converting)) return true;
+    if (!d.d_al_rows.p) {
+        std::vector<int64_t> off2(p.src_offset);
+        std::vector<int32_t> step2(p.src_step);
+        for (int64_t &o : off2) o *= 2;
+        for (int32_t &q : step2) q *= 2;
+        if (!d.d_al_rows.alloc((size_t)b.C * (size_t)b.row_samples * sizeof(float))) return false;
+        st = syldet_recordings_load_pcm_device(b.r, d.d_src.p, p.total * 2, off2.data(), step2.data(), p.src_format.data(), (float *)d.d_al_rows.p, b.row_samples, b.stream);
+    }
+    rows = (const float *)d.d_al_rows.p;
+    return true;
+}
+
+// --match: the matches of the template in every recording's columns, from the batch's fp32 rows.  false: device trouble.
+bool batch_matches(Batch &b, BatchDevice &d)
+{
+    if (!b.run.match) return true;
+    const float *rows = nullptr;
+    int st = 0;
+    if (!batch_rows(b, d, rows, st)) return false;
+    if (st) std::fprintf(stderr, "Unable to match the template in the batch: %s: %s\n", syldet_strerror(st), syldet_last_error());
+    if (st || !match_bank(*b.run.match, b.h, b.r, rows, b.row_samples, b.row_samples, b.C, b.plan.K, b.stream, b.matched)) {
+        b.run.match->failed = true;
+        b.matched.assign((size_t)b.plan.K, {});
+    }
+    return true;
+}
+
 // Stage 6, --align-dir: the windows of every recording's events, from the batch's arrays on the device (the outputs; the fp32 rows -- a
 // batch of 16-bit files is loaded once more, as fp32, from the same upload --; the rows' columns), in one launch.  false: no memory.
 bool batch_windows(Batch &b, BatchDevice &d)
@@ -266,15 +302,7 @@ bool batch_windows(Batch &b, BatchDevice &d)
     AlignSource src;
     src.st = syldet_recordings_slots(b.r, slots.data());
     AlignInput in{(const float *)d.d_rows.p, b.row_samples, b.row_samples, 0, (const float *)d.d_out.p, b.row_evals, b.C, {}, {}, b.stream};
-    if (!src.st && run.opt.source != SYLDET_ALIGN_OUTPUTS && p.all16 && !p.converting) {
-        std::vector<int64_t> off2(p.src_offset);
-        std::vector<int32_t> step2(p.src_step);
-        for (int64_t &o : off2) o *= 2;
-        for (int32_t &q : step2) q *= 2;
-        if (!d.d_al_rows.alloc((size_t)b.C * (size_t)b.row_samples * sizeof(float))) return false;
-        src.st = syldet_recordings_load_pcm_device(b.r, d.d_src.p, p.total * 2, off2.data(), step2.data(), p.src_format.data(), (float *)d.d_al_rows.p, b.row_samples, b.stream);
-        in.rows = (const float *)d.d_al_rows.p;
-    }
+    if (!src.st && run.opt.source != SYLDET_ALIGN_OUTPUTS && !batch_rows(b, d, in.rows, src.st)) return false;
     for (int32_t i = 0; i < p.K; i++) {
         in.samples.push_back(slots[(size_t)i].n_samples);
         in.evals.push_back(slots[(size_t)i].n_evals);
@@ -331,10 +359,10 @@ int batch_on_device(Batch &b, BatchDevice &d)
 {
     if (int rc = load_and_run(b, d)) return rc < 0 ? 0 : rc;
     if (int rc = batch_meters(b, d)) return rc;
-    if (!b.ran) return !batch_windows(b, d) || hipStreamSynchronize(b.stream) != hipSuccess ? 2 : 0;   // no file of the batch has an evaluation: no events (labels may still be aligned)
+    if (!b.ran) return !batch_windows(b, d) || !batch_matches(b, d) || hipStreamSynchronize(b.stream) != hipSuccess ? 2 : 0;   // no file of the batch has an evaluation: no events (labels may still be aligned)
     if (int rc = batch_events(b, d)) return rc;
     if (int rc = batch_score(b, d)) return rc;
-    if (!batch_windows(b, d)) return 2;
+    if (!batch_windows(b, d) || !batch_matches(b, d)) return 2;
     return batch_tracks(b, d);
 }
 
@@ -366,6 +394,7 @@ bool batch_write(const Batch &b, int rc)
         if (!write_track(TrackDirs::in(o.dirs.ttl, f.path), rate, tracks, n, b.ttl_frames.data() + p.frames_at[i])) written = false;
         if (!ons.empty() && !write_onsets(ons, tracks, b.on_idx.empty() ? nullptr : b.on_idx.data() + k0 * (size_t)b.on_cap, b.on_cnt.data() + k0, b.on_cap, rate)) written = false;
         if (b.run.align && align_write_file(*b.run.align, f.path, b.al, k0, tracks, rate)) written = false;
+        if (b.run.match) match_add_file(*b.run.match, f.path, b.matched, k0, tracks);
         if (!o.dirs.levels.empty()) {
             const LevelTable table{tracks, o.levels.buffer, b.lv_P, b.lv_first[k0 + 1] - b.lv_first[k0], n, b.lv_first.data() + k0, b.lv_in.data(), b.lv_out.data(), b.lv_empty.data()};
             if (!write_levels(TrackDirs::in(o.dirs.levels, f.path, ".tsv"), table, rate)) written = false;

@@ -2,6 +2,7 @@
 #pragma once
 
 #include "align.hpp"
+#include "match.hpp"
 #include "wav.hpp"
 
 namespace {
@@ -13,6 +14,7 @@ struct Run {
     double debounce_s;                                      // 0: none
     ScoreRun *score;                                        // null: no --score
     AlignRun *align;                                        // null: no --align-dir
+    MatchRun *match;                                        // null: no --match
 };
 
 // What process_file writes for one audio file besides its lines (an empty path: not that one)
@@ -84,6 +86,7 @@ struct OneFile {
     std::vector<int64_t> ttl_idx, ttl_cnt;                  // [C][ttl_cap], [C]
     int64_t ttl_cap = 1;
     Aligned al;                                             // --align-dir: every track's events, their windows
+    std::vector<std::vector<int64_t>> matched;              // --match: every track's matches
 };
 
 // ... and what it holds on the device while it runs
@@ -253,6 +256,42 @@ bool trace(OneFile &f, FileDevice &d)
     return hipMemcpyAsync(f.track.data(), d.d_track.p, f.track.size() * sizeof(int16_t), hipMemcpyDeviceToHost, f.stream) == hipSuccess;
 }
 
+// The file's tracks as fp32 rows on the device, what the detector was fed: the converter's rows, or (once) the decoded frames
+// (16-bit PCM: x * 2^-15, exact).  false: no memory.
+bool file_rows(OneFile &f, FileDevice &d, const float *&rows, int64_t &stride)
+{
+    const int C = f.C;
+    const int64_t S = f.S;
+    if (f.resample) {
+        rows = (const float *)d.d_res.p;
+        stride = f.res_stride;
+        return true;
+    }
+    stride = S;
+    if (!d.d_al_rows.p) {
+        std::vector<float> planar((size_t)C * (size_t)S);
+        for (int64_t i = 0; i < S; i++)
+            for (int c = 0; c < C; c++)
+                planar[(size_t)c * (size_t)S + (size_t)i] = f.raw16 ? (float)f.frames16[(size_t)i * C + c] * (1.0f / 32768.0f) : f.frames[(size_t)i * C + c];
+        if (!d.d_al_rows.alloc(planar.size() * sizeof(float)) || hipMemcpy(d.d_al_rows.p, planar.data(), planar.size() * sizeof(float), hipMemcpyHostToDevice) != hipSuccess) return false;
+    }
+    rows = (const float *)d.d_al_rows.p;
+    return true;
+}
+
+// ... the matches of the template in every track's columns (--match), from the fp32 rows the detector was fed
+void matches(OneFile &f, FileDevice &d)
+{
+    if (!f.run.match) return;
+    const float *rows = nullptr;
+    int64_t stride = f.S;
+    f.matched.assign((size_t)f.C, {});
+    if (!file_rows(f, d, rows, stride) || !match_bank(*f.run.match, f.h, nullptr, rows, f.S, stride, f.C, f.C, f.stream, f.matched)) {
+        std::fprintf(stderr, "Unable to match the template in %s.\n", f.path.c_str());
+        f.run.match->failed = true;
+    }
+}
+
 // ... the windows of every track's events (--align-dir), from arrays on the device: the outputs the run left, the fp32 rows the
 // detector was fed, or their columns (syldet_spectrogram_device).  Behind the download of the flags: the detections are made
 // from them.  (Windows that cannot be made do not cost the lines: write_files reports them.)
@@ -269,20 +308,7 @@ void windows(OneFile &f, FileDevice &d)
     f.al.events.clear();
     for (int c = 0; c < C; c++) f.al.events.push_back(align_events_of(run, f.path, c, f.found[(size_t)c].sample.data(), (int64_t)f.found[(size_t)c].sample.size()));
     AlignInput in{nullptr, S, S, 0, (const float *)d.d_out.p, f.E > 0 ? f.E : 0, C, {}, {}, f.stream};
-    if (run.opt.source != SYLDET_ALIGN_OUTPUTS) {
-        if (f.resample) {
-            in.rows = (const float *)d.d_res.p;
-            in.stride = f.res_stride;
-        } else {
-            // the file's tracks as fp32 rows: what the detector was fed (16-bit PCM: x * 2^-15, exact)
-            std::vector<float> planar((size_t)C * (size_t)S);
-            for (int64_t i = 0; i < S; i++)
-                for (int c = 0; c < C; c++)
-                    planar[(size_t)c * (size_t)S + (size_t)i] = f.raw16 ? (float)f.frames16[(size_t)i * C + c] * (1.0f / 32768.0f) : f.frames[(size_t)i * C + c];
-            if (!d.d_al_rows.alloc(planar.size() * sizeof(float)) || hipMemcpy(d.d_al_rows.p, planar.data(), planar.size() * sizeof(float), hipMemcpyHostToDevice) != hipSuccess) return;
-            in.rows = (const float *)d.d_al_rows.p;
-        }
-    }
+    if (run.opt.source != SYLDET_ALIGN_OUTPUTS && !file_rows(f, d, in.rows, in.stride)) return;
     in.samples_stride = in.stride;
     in.samples.assign((size_t)C, S);
     in.evals.assign((size_t)C, in.row_evals);
@@ -320,10 +346,12 @@ int on_device(OneFile &f, FileDevice &d)
         if (!triggers(f, d)) return 2;
         if ((!f.want.levels.path.empty() || f.want.ttl.any()) && hipStreamSynchronize(f.stream) != hipSuccess) return 2;
         windows(f, d);
+        matches(f, d);
         return 0;
     }
     if (!run_detector(f, d) || !trace(f, d) || !meters(f, d, true) || !triggers(f, d) || !download(f, d)) return 2;
     windows(f, d);
+    matches(f, d);
     return 0;
 }
 
@@ -350,6 +378,7 @@ int write_files(OneFile &f)
     if (!f.mux_refused && !write_track(ttl.path, rate, ttl.mux ? 2 * f.C : f.C, f.fed, f.ttl_track.data())) c = 3;
     if (!ttl.onsets.empty() && !write_onsets(ttl.onsets, f.ttl_cnt.empty() ? 0 : f.C, f.ttl_idx.data(), f.ttl_cnt.data(), f.ttl_cap, rate)) c = 3;
     const int w = f.run.align ? align_write_file(*f.run.align, f.path, f.al, 0, f.C, rate) : 0;
+    if (f.run.match) match_add_file(*f.run.match, f.path, f.matched, 0, f.C);
     return a ? a : (b ? b : (c ? c : w));
 }
 

@@ -585,6 +585,35 @@ hipError_t launch_train_gradient(const TrainDesc &d, const float *columns, int64
                                  const float *weights, int64_t n_evals, double *part, hipStream_t stream);
 hipError_t launch_train_combine(const TrainDesc &d, int groups, const double *part, double *loss, float *gradient, hipStream_t stream);
 
+// ---- template matching (kernels_match.hip; syldet_match_scores_device and syldet_match_peaks_device of include/syldet.h) ----
+// A detector of a packed plan: its frame 0 is frame `first` of row `row`, and it has `units` frames.
+struct MatchDetDev {
+    int64_t first, units;
+    int32_t det, row;
+};
+constexpr int kMatchTile = 256;              // positions a workgroup of the score kernels takes
+constexpr int kMatchChunk = 2048;            // positions a step of the peaks kernel takes
+struct MatchDesc {
+    const MatchDetDev *by_row;               // packed plans: sorted by (row, first), row c's detectors are [row_begin[c], row_begin[c + 1]);
+    const int32_t *row_begin;                //   nullptr: detector c is row c, all of it
+    const MatchDetDev *by_det;               // packed plans: [D] in the caller's order
+    const float *templ;                      // t^ [n][bins]
+    int rows, D, n, bins, anchor;
+    int64_t origin, hop;
+    // the score kernel's form, a function of n and bins alone (match_plan)
+    int matrix;                              // 1: the Toeplitz form on the matrix cores; 0: one thread a position, plain multiply-adds
+    int Fp, FT;                              // floats a staged frame (bins padded to 4); floats a staged template frame (4 x an odd number)
+    int lds_bytes;
+};
+void match_plan(MatchDesc &d);
+hipError_t match_prepare();                  // on the matcher's device, once: the peaks kernel's LDS above 64 KB allowed
+// scores [rows][n_frames] <- columns [rows][row_stride]: every element written once; one launch (match_scores_mfma_kernel or
+// match_scores_plain_kernel)
+hipError_t launch_match_scores(const MatchDesc &d, const float *columns, int64_t n_frames, int64_t row_stride, float *scores, hipStream_t stream);
+// events [D][capacity], counts [D], event_scores [D][capacity] or nullptr <- scores [rows][n_frames]; one launch (match_peaks_kernel)
+hipError_t launch_match_peaks(const MatchDesc &d, const float *scores, int64_t n_frames, float threshold, int separation, int64_t *events,
+                              int64_t capacity, int64_t *counts, float *event_scores, hipStream_t stream);
+
 // detection flags <-> bits (bit b of byte t of a row = flag 8 t + b), rows padded to whole bytes
 hipError_t launch_pack_flags(const uint8_t *flags, int64_t rows, int64_t row_len, uint8_t *bits, hipStream_t stream);
 hipError_t launch_unpack_flags(const uint8_t *bits, int64_t rows, int64_t row_len, uint8_t *flags, hipStream_t stream);

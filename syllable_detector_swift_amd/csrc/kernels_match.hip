@@ -1,0 +1,315 @@
+// kernels_match.hip -- template matching (syldet_match_scores_device, syldet_match_peaks_device of include/syldet.h): the cosine
+// between a normalised template t^ [n][bins] and the window of n frames at every position of every detector, and the matches
+// among the scores.
+//
+//   match_scores_mfma_kernel    A workgroup of four waves takes 256 consecutive frames of a row as positions and stages the 255 + n
+//                  frames their windows reach in LDS once, bins padded to a multiple of 4 with zeros by selection, frames behind
+//                  the row's end likewise.  A thread a frame then takes the frame's energy from the staged values (a chain of
+//                  fused multiply-adds over the bins) and replaces a NaN or an Inf by zero, so that a product with a zero of the
+//                  Toeplitz operand below cannot carry it into a window that does not hold it; the energy keeps it.  The inner
+//                  products run on v_mfma_f32_16x16x4_f32 in the Toeplitz arrangement: row m of the A operand is the frames from
+//                  16 m on, column i of the B operand the template shifted down by i frames (zeros by selection above and below
+//                  it), so accumulator element (m, i) is position 16 m + i: a chain of fused multiply-adds over the window in
+//                  (frame, bin) order in front of and behind which only zeros are added.  (n + 15) / n of the window's products,
+//                  no shuffle.  The waves share the k dimension by groups of 4 bins (wave w the groups w, w + 4, ..), every
+//                  group's chain is whole, and the waves' sums are added in wave order.  A thread a position adds them, sums
+//                  the window's n frame energies from its first frame on, and writes the score or the NaN of a position that
+//                  holds none.  LDS: staged frames are 16 m + f at (16 m + f) Fp + 4 m + .., so the 64 lanes of an A read
+//                  (m, k) hit 64 banks; the template's frames are 4 x an odd number of floats apart for the same reason.
+//   match_scores_plain_kernel   The same sums, one thread a position, from global memory: for shapes whose staged tile does not fit
+//                  64 KB of LDS.  Which of the two runs is a function of n and bins alone.
+//   match_peaks_kernel          A workgroup a detector walks its positions in steps of 2048: the scores' keys (match_peaks.hpp) of the
+//                  step and of S positions on either side go to LDS, log2 S passes of m[i] = max(m[i], m[i + 2^l]) make the maxima of
+//                  all windows of 2^k positions, two of which cover any window of S; a thread marks its 8 consecutive positions by
+//                  the rule, and a scan over the workgroup's counts places the events in order.
+//
+// gfx950 only: wave = 64 lanes.
+
+#include "kernels.hpp"
+#include "match_peaks.hpp"
+
+namespace sd {
+
+namespace {
+
+constexpr int kThreads = 256;
+constexpr int kOwn = kMatchChunk / kThreads;                 // positions a thread of the peaks kernel marks
+
+typedef float f4 __attribute__((ext_vector_type(4)));
+
+__device__ __forceinline__ bool finite_bits(float v) { return (__float_as_uint(v) & 0x7f800000u) != 0x7f800000u; }
+
+// Does position q of row `row` hold a score: does a detector's window of n frames begin there?
+__device__ __forceinline__ bool match_position(const MatchDesc &d, int row, int64_t q, int64_t n_frames)
+{
+    if (!d.by_row) return q + d.n <= n_frames;
+    int lo = d.row_begin[row], hi = d.row_begin[row + 1];
+    const int begin = lo;
+    while (lo < hi) {                                        // the first detector that starts behind q
+        const int mid = (lo + hi) >> 1;
+        if (d.by_row[mid].first <= q) lo = mid + 1;
+        else hi = mid;
+    }
+    if (lo == begin) return false;
+    const MatchDetDev e = d.by_row[lo - 1];
+    return q + d.n <= e.first + e.units;
+}
+
+// dot: the window's products with t^ (NaN and Inf taken as zero); E: its energy (which keeps them)
+__device__ __forceinline__ float match_score(float dot, float E)
+{
+    if (!finite_bits(E)) return __uint_as_float(0x7fc00000u);
+    if (E == 0.0f) return 0.0f;
+    return (dot + 0.0f) / sqrtf(E);                          // (-0.0 -> +0.0: zeros added behind a window may have done so already)
+}
+
+__global__ void __launch_bounds__(kThreads)
+match_scores_mfma_kernel(MatchDesc d, const float *__restrict__ columns, int64_t n_frames, int64_t row_stride, float *__restrict__ scores)
+{
+    extern __shared__ float match_lds[];
+    const int tid = (int)threadIdx.x, row = (int)blockIdx.y;
+    const int64_t p0 = (int64_t)blockIdx.x * kMatchTile;
+    const int n = d.n, bins = d.bins, Fp = d.Fp, FT = d.FT;
+    const int G = kMatchTile - 1 + n;                        // staged frames
+    float *X = match_lds;                                    // frame g, bin b at g Fp + 4 (g >> 4) + b
+    float *T = X + G * Fp + 4 * ((G + 15) >> 4);             // t^ frame j, bin b at j FT + b
+    float *Efr = T + n * FT;                                 // [G] the frames' energies
+    float *red = Efr + G;                                    // [4][256] the waves' sums
+    const float *__restrict__ src = columns + (int64_t)row * row_stride;
+
+    // (eight loads a thread in flight: one at a time, the tile's staging waits out a memory latency an element and takes longer
+    // than its matrix instructions)
+    constexpr int kStage = 8;
+    for (int base = tid; base < G * Fp; base += kThreads * kStage) {
+        float v[kStage];
+        int at[kStage];
+#pragma unroll
+        for (int u = 0; u < kStage; u++) {
+            const int idx = base + u * kThreads;
+            const int g = idx / Fp, b = idx - g * Fp;
+            const int64_t gf = p0 + g;
+            at[u] = idx < G * Fp ? idx + 4 * (g >> 4) : -1;
+            v[u] = 0.0f;
+            if (idx < G * Fp && b < bins && gf < n_frames) v[u] = src[gf * bins + b];
+        }
+#pragma unroll
+        for (int u = 0; u < kStage; u++)
+            if (at[u] >= 0) X[at[u]] = v[u];
+    }
+    for (int base = tid; base < n * FT; base += kThreads * kStage) {
+        float v[kStage];
+#pragma unroll
+        for (int u = 0; u < kStage; u++) {
+            const int idx = base + u * kThreads;
+            const int j = idx / FT, b = idx - j * FT;
+            v[u] = 0.0f;
+            if (idx < n * FT && b < bins) v[u] = d.templ[j * bins + b];
+        }
+#pragma unroll
+        for (int u = 0; u < kStage; u++)
+            if (base + u * kThreads < n * FT) T[base + u * kThreads] = v[u];
+    }
+    __syncthreads();
+    for (int g = tid; g < G; g += kThreads) {
+        float *x = X + g * Fp + 4 * (g >> 4);
+        float e = 0.0f;
+        for (int b = 0; b < bins; b++) {
+            const float v = x[b];
+            e = fmaf(v, v, e);
+            if (!finite_bits(v)) x[b] = 0.0f;
+        }
+        Efr[g] = e;
+    }
+    __syncthreads();
+
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63;
+    const int groups = Fp >> 2;
+    if (wave < groups) {
+        const int m = lane & 15, k = lane >> 4;              // A: row m, k; B: k, column m
+        const float *xa = X + (16 * m) * Fp + 4 * m + k;
+        f4 acc = {0.0f, 0.0f, 0.0f, 0.0f};
+        // the operands of step (f, bg): frame 16 m + f of the tile, and the template's frame f - m that column m meets there
+        // (in: column m's window holds frame f; the zero above and below the template is selected where the operand is used)
+        auto operands = [&](int f, int bg, float &a, float &b, bool &in) {
+            const int j = f - m;
+            in = (unsigned)j < (unsigned)n;
+            a = xa[f * Fp + 4 * (f >> 4) + 4 * bg];
+            b = T[(in ? j : 0) * FT + k + 4 * bg];
+        };
+        // every step's operands are read one step ahead of its matrix instruction
+        int f = 0, bg = wave;
+        float a, b;
+        bool in;
+        operands(f, bg, a, b, in);
+        for (;;) {
+            bg += 4;
+            if (bg >= groups) {
+                bg = wave;
+                f++;
+            }
+            const bool more = f < n + 15;
+            float a1 = 0.0f, b1 = 0.0f;
+            bool in1 = false;
+            if (more) operands(f, bg, a1, b1, in1);
+            acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a, in ? b : 0.0f, acc, 0, 0, 0);
+            if (!more) break;
+            a = a1;
+            b = b1;
+            in = in1;
+        }
+        for (int r = 0; r < 4; r++) red[wave * kMatchTile + 16 * (4 * (lane >> 4) + r) + (lane & 15)] = acc[r];
+    }
+    __syncthreads();
+
+    const int64_t q = p0 + tid;
+    if (q >= n_frames) return;
+    float s = __uint_as_float(0x7fc00000u);
+    if (match_position(d, row, q, n_frames)) {
+        const int nw = groups < 4 ? groups : 4;
+        float dot = red[tid];
+        for (int w = 1; w < nw; w++) dot = dot + red[w * kMatchTile + tid];
+        float E = 0.0f;
+        for (int j = 0; j < n; j++) E = E + Efr[tid + j];
+        s = match_score(dot, E);
+    }
+    scores[(int64_t)row * n_frames + q] = s;
+}
+
+__global__ void __launch_bounds__(kThreads)
+match_scores_plain_kernel(MatchDesc d, const float *__restrict__ columns, int64_t n_frames, int64_t row_stride, float *__restrict__ scores)
+{
+    const int row = (int)blockIdx.y;
+    const int64_t q = (int64_t)blockIdx.x * kMatchTile + (int)threadIdx.x;
+    if (q >= n_frames) return;
+    float s = __uint_as_float(0x7fc00000u);
+    if (match_position(d, row, q, n_frames)) {
+        const float *__restrict__ x = columns + (int64_t)row * row_stride + q * d.bins;
+        const float *__restrict__ t = d.templ;
+        float dot = 0.0f, E = 0.0f;
+        for (int j = 0; j < d.n; j++) {
+            float e = 0.0f;
+            for (int b = 0; b < d.bins; b++) {
+                const float v = x[j * d.bins + b];
+                e = fmaf(v, v, e);
+                dot = fmaf(finite_bits(v) ? v : 0.0f, t[j * d.bins + b], dot);
+            }
+            E = E + e;
+        }
+        s = match_score(dot, E);
+    }
+    scores[(int64_t)row * n_frames + q] = s;
+}
+
+__global__ void __launch_bounds__(kThreads)
+match_peaks_kernel(MatchDesc d, const float *__restrict__ scores, int64_t n_frames, uint32_t threshold_key, int S, int64_t *__restrict__ events,
+                   int64_t capacity, int64_t *__restrict__ counts, float *__restrict__ event_scores)
+{
+    extern __shared__ uint32_t match_keys[];
+    __shared__ int wave_sum[kThreads / 64];
+    const int tid = (int)threadIdx.x, det = (int)blockIdx.x;
+    int64_t row = det, first = 0, U = n_frames;
+    if (d.by_det) {
+        const MatchDetDev e = d.by_det[det];
+        row = e.row;
+        first = e.first;
+        U = e.units;
+    }
+    const int64_t P = U - d.n + 1;                           // the detector's positions
+    const int L = kMatchChunk + 2 * S, k = S ? match_level(S) : 0;
+    const float *__restrict__ s = scores + row * n_frames + first;
+    int64_t total = 0;
+    for (int64_t c0 = 0; c0 < P; c0 += kMatchChunk) {
+        uint32_t *cur = match_keys, *nxt = match_keys + L;
+        for (int i = tid; i < L; i += kThreads) {
+            const int64_t q = c0 - S + i;
+            cur[i] = q >= 0 && q < P ? match_key(s[q]) : 0u;
+        }
+        __syncthreads();
+        uint32_t key[kOwn];
+        for (int e = 0; e < kOwn; e++) key[e] = cur[S + tid * kOwn + e];
+        for (int lev = 0; lev < k; lev++) {                  // cur[i]: the largest key of [i, i + 2^lev)
+            const int h = 1 << lev;
+            for (int i = tid; i < L; i += kThreads) {
+                const uint32_t a = cur[i], b = i + h < L ? cur[i + h] : 0u;
+                nxt[i] = a > b ? a : b;
+            }
+            __syncthreads();
+            uint32_t *t = cur;
+            cur = nxt;
+            nxt = t;
+        }
+        unsigned flags = 0;
+        for (int e = 0; e < kOwn; e++) {
+            const int i = S + tid * kOwn + e;
+            if (c0 + tid * kOwn + e < P && match_rule(key[e], match_left(cur, i, S, k), match_right(cur, i, S, k), threshold_key)) flags |= 1u << e;
+        }
+        // the workgroup's matches in front of this thread's
+        const int mine = __popc(flags);
+        int incl = mine;
+        for (int o = 1; o < 64; o <<= 1) {
+            const int up = __shfl_up(incl, o);
+            if ((tid & 63) >= o) incl += up;
+        }
+        if ((tid & 63) == 63) wave_sum[tid >> 6] = incl;
+        __syncthreads();
+        int before = incl - mine, all = 0;
+        for (int w = 0; w < kThreads / 64; w++) {
+            if (w < (tid >> 6)) before += wave_sum[w];
+            all += wave_sum[w];
+        }
+        int64_t at = total + before;
+        for (int e = 0; e < kOwn; e++) {
+            if (!((flags >> e) & 1u)) continue;
+            const int64_t p = c0 + tid * kOwn + e;
+            if (at < capacity) {
+                events[(int64_t)det * capacity + at] = match_event(d.origin, d.hop, p, d.anchor);
+                if (event_scores) event_scores[(int64_t)det * capacity + at] = s[p];
+            }
+            at++;
+        }
+        total += all;
+        __syncthreads();                                     // (the keys and wave_sum are the next step's)
+    }
+    if (tid == 0) counts[det] = total;
+}
+
+}  // namespace
+
+void match_plan(MatchDesc &d)
+{
+    d.Fp = (d.bins + 3) / 4 * 4;
+    d.FT = ((d.Fp / 4) & 1) ? d.Fp : d.Fp + 4;
+    const int64_t G = kMatchTile - 1 + d.n;
+    const int64_t floats = G * d.Fp + 4 * ((G + 15) / 16) + (int64_t)d.n * d.FT + G + 4 * kMatchTile;
+    d.matrix = floats * 4 <= 64 * 1024;
+    d.lds_bytes = d.matrix ? (int)(floats * 4) : 0;
+}
+
+hipError_t match_prepare()
+{
+    return hipFuncSetAttribute((const void *)match_peaks_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
+                               2 * (kMatchChunk + 2 * kMatchMaxSeparation) * (int)sizeof(uint32_t));
+}
+
+hipError_t launch_match_scores(const MatchDesc &d, const float *columns, int64_t n_frames, int64_t row_stride, float *scores, hipStream_t stream)
+{
+    if (n_frames <= 0 || d.rows <= 0) return hipSuccess;
+    const dim3 grid((unsigned)((n_frames + kMatchTile - 1) / kMatchTile), (unsigned)d.rows);
+    if (d.matrix)
+        hipLaunchKernelGGL(match_scores_mfma_kernel, grid, dim3(kThreads), (size_t)d.lds_bytes, stream, d, columns, n_frames, row_stride, scores);
+    else
+        hipLaunchKernelGGL(match_scores_plain_kernel, grid, dim3(kThreads), 0, stream, d, columns, n_frames, row_stride, scores);
+    return hipGetLastError();
+}
+
+hipError_t launch_match_peaks(const MatchDesc &d, const float *scores, int64_t n_frames, float threshold, int separation, int64_t *events,
+                              int64_t capacity, int64_t *counts, float *event_scores, hipStream_t stream)
+{
+    if (d.D <= 0) return hipSuccess;
+    const size_t lds = 2 * (size_t)(kMatchChunk + 2 * separation) * sizeof(uint32_t);
+    hipLaunchKernelGGL(match_peaks_kernel, dim3((unsigned)d.D), dim3(kThreads), lds, stream, d, scores, n_frames, match_key(threshold), separation,
+                       events, capacity, counts, event_scores);
+    return hipGetLastError();
+}
+
+}  // namespace sd

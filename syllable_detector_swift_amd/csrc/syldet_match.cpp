@@ -1,0 +1,296 @@
+// syldet_match.cpp -- template matching (include/syldet.h, "template matching"; kernels_match.hip): the matcher that keeps the
+// normalised template and a packed plan's detectors on the device, so that syldet_match_scores_device and
+// syldet_match_peaks_device are launches only; and the host functions (match_peaks.hpp: the rule the kernel runs).
+
+#include <limits>
+
+#include "match_peaks.hpp"
+#include "syldet_handle.hpp"
+
+static_assert(SYLDET_MATCH_MAX_TEMPLATE == sd::kMatchMaxTemplate && SYLDET_MATCH_MAX_SEPARATION == sd::kMatchMaxSeparation,
+              "the header's limits are the kernels'");
+
+struct syldet_matcher {
+    syldet_t *h = nullptr;                   // the bank (it outlives the matcher): its profile
+    sd::BankInfo bank{};
+    bool packed = false;
+    int D = 0;
+    int64_t row_frames = 0;                  // (packed) what n_frames must be
+    std::vector<float> templ;                // t^ [n][bins]
+    sd::DeviceBuffer d_fixed;                // t^ | by_det [D] | by_row [D] | row_begin [rows + 1]
+    sd::MatchDesc desc{};
+};
+
+namespace {
+
+int template_args(const float *templ, int64_t n, int64_t bins)
+{
+    if (!templ) return fail(SYLDET_ERR_INVALID_ARGUMENT, "NULL template");
+    if (n < 1 || bins < 1 || n * bins > SYLDET_MATCH_MAX_TEMPLATE || n > SYLDET_MATCH_MAX_TEMPLATE || bins > SYLDET_MATCH_MAX_TEMPLATE)
+        return fail(SYLDET_ERR_INVALID_ARGUMENT, "a template of " + std::to_string(n) + " x " + std::to_string(bins) + " elements is outside [1, " +
+                                                     std::to_string(SYLDET_MATCH_MAX_TEMPLATE) + "]");
+    return SYLDET_OK;
+}
+
+// t^ = fp32(t / ||t||_2), the norm and the division in fp64
+int normalise(const float *templ, int n, int bins, float *out)
+{
+    double sq = 0.0;
+    for (int k = 0; k < n * bins; k++) {
+        if (!std::isfinite(templ[k])) return fail(SYLDET_ERR_INVALID_ARGUMENT, "template element " + std::to_string(k) + " is not finite");
+        sq += (double)templ[k] * (double)templ[k];
+    }
+    if (sq == 0.0) return fail(SYLDET_ERR_INVALID_ARGUMENT, "the template is all zero");
+    const double norm = std::sqrt(sq);
+    for (int k = 0; k < n * bins; k++) out[k] = (float)((double)templ[k] / norm);
+    return SYLDET_OK;
+}
+
+int peaks_args(float threshold, int32_t separation, int64_t capacity)
+{
+    if (threshold != threshold) return fail(SYLDET_ERR_INVALID_ARGUMENT, "the threshold is NaN");
+    if (separation < 0 || separation > SYLDET_MATCH_MAX_SEPARATION)
+        return fail(SYLDET_ERR_INVALID_ARGUMENT, "separation " + std::to_string(separation) + " is outside [0, " + std::to_string(SYLDET_MATCH_MAX_SEPARATION) + "]");
+    if (capacity < 0) return fail(SYLDET_ERR_INVALID_ARGUMENT, "capacity is negative");
+    return SYLDET_OK;
+}
+
+size_t up16(size_t n) { return (n + 15) / 16 * 16; }
+
+}  // namespace
+
+extern "C" {
+
+int syldet_matcher_create(const syldet_t *h, const syldet_recordings_t *r, const float *templ, int32_t n, int32_t bins, int32_t anchor,
+                          syldet_matcher_t **out)
+{
+    if (!out) return fail(SYLDET_ERR_INVALID_ARGUMENT, "NULL argument");
+    *out = nullptr;
+    if (!h) return fail(SYLDET_ERR_INVALID_ARGUMENT, "NULL handle");
+    if (int st = template_args(templ, n, bins)) return st;
+    if (h->classes.size() > 1) return fail(SYLDET_ERR_UNSUPPORTED, "columns of a mixed bank: its classes' columns are ragged");
+    sd::BankInfo b{};
+    sd::bank_info(h, &b);
+    if (bins != b.geom.bins)
+        return fail(SYLDET_ERR_INVALID_ARGUMENT, "the template has " + std::to_string(bins) + " bins, the bank's columns " + std::to_string(b.geom.bins));
+    if (anchor < 0) anchor = n - 1;
+    if (anchor >= n) return fail(SYLDET_ERR_INVALID_ARGUMENT, "anchor " + std::to_string(anchor) + " is outside [0, " + std::to_string(n) + ")");
+    int32_t D = b.channels;
+    int64_t row_samples = 0;
+    if (r)
+        if (int st = syldet_recordings_shape(r, &D, &row_samples, nullptr, nullptr)) return st;
+
+    std::unique_ptr<syldet_matcher, int (*)(syldet_matcher_t *)> m(nullptr, syldet_matcher_destroy);
+    std::vector<sd::MatchDetDev> by_det, by_row;
+    std::vector<int32_t> row_begin;
+    try {
+        m.reset(new syldet_matcher());
+        m->bank = b;
+        m->templ.assign((size_t)n * bins, 0.0f);
+        if (int st = normalise(templ, n, bins, m->templ.data())) return st;
+        if (r) {
+            m->row_frames = std::max<int64_t>(0, sd::count_frames(b.geom, b.window_length, row_samples));
+            std::vector<syldet_slot_t> plan((size_t)D);
+            if (D > 0)
+                if (int st = syldet_recordings_slots(r, plan.data())) return st;
+            for (int k = 0; k < D; k++) {
+                const syldet_slot_t &p = plan[(size_t)k];
+                const sd::MatchDetDev e{p.first_eval, std::max<int64_t>(0, sd::count_frames(b.geom, b.window_length, p.n_samples)), k, p.row};
+                if (e.row < 0 || e.row >= b.channels || (e.units > 0 && (e.first < 0 || e.first + e.units > m->row_frames)))
+                    return fail(SYLDET_ERR_INVALID_ARGUMENT, "recording " + std::to_string(k) + " reaches beyond its row");
+                by_det.push_back(e);
+            }
+            // by (row, first): what the score kernels search (a recording without frames in front of one that starts at the same
+            // frame, so that the last detector at or before a frame is the one that holds it)
+            by_row = by_det;
+            std::stable_sort(by_row.begin(), by_row.end(), [](const sd::MatchDetDev &x, const sd::MatchDetDev &y) {
+                if (x.row != y.row) return x.row < y.row;
+                return x.first != y.first ? x.first < y.first : x.units < y.units;
+            });
+            row_begin.assign((size_t)b.channels + 1, 0);
+            for (const sd::MatchDetDev &e : by_row) row_begin[(size_t)e.row + 1]++;
+            for (int c = 0; c < b.channels; c++) row_begin[(size_t)c + 1] += row_begin[(size_t)c];
+        }
+    } catch (const std::bad_alloc &) {
+        return fail(SYLDET_ERR_OUT_OF_MEMORY, "out of memory");
+    }
+    m->h = const_cast<syldet_t *>(h);
+    m->packed = r != nullptr;
+    m->D = D;
+    sd::MatchDesc &d = m->desc;
+    d.rows = b.channels;
+    d.D = D;
+    d.n = n;
+    d.bins = bins;
+    d.anchor = anchor;
+    d.origin = (int64_t)b.geom.gap + b.window_length;       // syldet_align_anchor(COLUMNS)
+    d.hop = b.geom.hop;
+    sd::match_plan(d);
+    // (measurement only, tools/match_timing.py: the plain form on a shape the matrix form takes)
+    if (const char *e = std::getenv("SYLDET_MATCH_PLAIN"))
+        if (e[0] == '1') d.matrix = 0;
+
+    const size_t n_t = up16(m->templ.size() * sizeof(float)), n_d = up16(by_det.size() * sizeof(sd::MatchDetDev)),
+                 n_r = up16(row_begin.size() * sizeof(int32_t));
+    SYLDET_HIP(hipSetDevice(b.device));
+    SYLDET_HIP(sd::match_prepare());
+    if (int st = m->d_fixed.reserve(n_t + 2 * n_d + n_r + 16)) return st;
+    char *base = (char *)m->d_fixed.ptr;
+    SYLDET_HIP(hipMemcpy(base, m->templ.data(), m->templ.size() * sizeof(float), hipMemcpyHostToDevice));
+    if (!by_det.empty()) {
+        SYLDET_HIP(hipMemcpy(base + n_t, by_det.data(), by_det.size() * sizeof(sd::MatchDetDev), hipMemcpyHostToDevice));
+        SYLDET_HIP(hipMemcpy(base + n_t + n_d, by_row.data(), by_row.size() * sizeof(sd::MatchDetDev), hipMemcpyHostToDevice));
+    }
+    if (!row_begin.empty()) SYLDET_HIP(hipMemcpy(base + n_t + 2 * n_d, row_begin.data(), row_begin.size() * sizeof(int32_t), hipMemcpyHostToDevice));
+    d.templ = (const float *)base;
+    d.by_det = r ? (const sd::MatchDetDev *)(base + n_t) : nullptr;
+    d.by_row = r ? (const sd::MatchDetDev *)(base + n_t + n_d) : nullptr;
+    d.row_begin = r ? (const int32_t *)(base + n_t + 2 * n_d) : nullptr;
+    *out = m.release();
+    return SYLDET_OK;
+}
+
+int syldet_matcher_destroy(syldet_matcher_t *m)
+{
+    if (!m) return SYLDET_OK;
+    if (m->d_fixed.ptr) (void)hipSetDevice(m->bank.device);
+    m->d_fixed.release();
+    delete m;
+    return SYLDET_OK;
+}
+
+int syldet_matcher_shape(const syldet_matcher_t *m, int32_t *n_detectors, int32_t *n, int32_t *bins, int32_t *anchor, int32_t *matrix_form)
+{
+    if (!m) return fail(SYLDET_ERR_INVALID_ARGUMENT, "NULL argument");
+    if (n_detectors) *n_detectors = m->D;
+    if (n) *n = m->desc.n;
+    if (bins) *bins = m->desc.bins;
+    if (anchor) *anchor = m->desc.anchor;
+    if (matrix_form) *matrix_form = m->desc.matrix;
+    return SYLDET_OK;
+}
+
+int syldet_matcher_template(const syldet_matcher_t *m, float *t_hat)
+{
+    if (!m || !t_hat) return fail(SYLDET_ERR_INVALID_ARGUMENT, "NULL argument");
+    std::memcpy(t_hat, m->templ.data(), m->templ.size() * sizeof(float));
+    return SYLDET_OK;
+}
+
+int syldet_match_scores_device(syldet_matcher_t *m, const float *d_columns, int64_t n_frames, int64_t row_stride, float *d_scores, void *hip_stream)
+{
+    if (!m) return fail(SYLDET_ERR_INVALID_ARGUMENT, "NULL handle");
+    if (n_frames < 0) return fail(SYLDET_ERR_INVALID_ARGUMENT, "n_frames is negative");
+    if (m->packed && n_frames != m->row_frames)
+        return fail(SYLDET_ERR_INVALID_ARGUMENT, "n_frames must be the packed rows' " + std::to_string(m->row_frames) + " frames");
+    if (n_frames > ((int64_t)1 << 40) / m->desc.bins) return fail(SYLDET_ERR_INVALID_ARGUMENT, "n_frames x bins is above 2^40");
+    if (row_stride == 0) row_stride = n_frames * m->desc.bins;
+    if (row_stride < n_frames * m->desc.bins)
+        return fail(SYLDET_ERR_INVALID_ARGUMENT, "row_stride " + std::to_string(row_stride) + " is below the " + std::to_string(n_frames * m->desc.bins) +
+                                                     " elements of a row");
+    if (n_frames > 0 && (!d_columns || !d_scores)) return fail(SYLDET_ERR_INVALID_ARGUMENT, "NULL argument");
+    if (n_frames == 0) return SYLDET_OK;
+    hipStream_t stream = (hipStream_t)hip_stream;
+    SYLDET_HIP(hipSetDevice(m->bank.device));
+    m->h->prof_begin();
+    KernelTimer t(m->h, stream, m->desc.matrix ? "match_scores_mfma_kernel" : "match_scores_plain_kernel");
+    SYLDET_HIP(sd::launch_match_scores(m->desc, d_columns, n_frames, row_stride, d_scores, stream));
+    return SYLDET_OK;
+}
+
+int syldet_match_peaks_device(syldet_matcher_t *m, const float *d_scores, int64_t n_frames, float threshold, int32_t separation, int64_t *d_events,
+                              int64_t capacity, int64_t *d_counts, float *d_event_scores, void *hip_stream)
+{
+    if (!m) return fail(SYLDET_ERR_INVALID_ARGUMENT, "NULL handle");
+    if (int st = peaks_args(threshold, separation, capacity)) return st;
+    if (n_frames < 0) return fail(SYLDET_ERR_INVALID_ARGUMENT, "n_frames is negative");
+    if (m->packed && n_frames != m->row_frames)
+        return fail(SYLDET_ERR_INVALID_ARGUMENT, "n_frames must be the packed rows' " + std::to_string(m->row_frames) + " frames");
+    if (m->D > 0 && (!d_counts || (n_frames > 0 && !d_scores) || (capacity > 0 && !d_events))) return fail(SYLDET_ERR_INVALID_ARGUMENT, "NULL argument");
+    if (m->D == 0) return SYLDET_OK;
+    hipStream_t stream = (hipStream_t)hip_stream;
+    SYLDET_HIP(hipSetDevice(m->bank.device));
+    m->h->prof_begin();
+    KernelTimer t(m->h, stream, "match_peaks_kernel");
+    SYLDET_HIP(sd::launch_match_peaks(m->desc, d_scores, n_frames, threshold, separation, d_events, capacity, d_counts, d_event_scores, stream));
+    return SYLDET_OK;
+}
+
+int syldet_match_normalize_host(const float *templ, int32_t n, int32_t bins, float *t_hat)
+{
+    if (int st = template_args(templ, n, bins)) return st;
+    if (!t_hat) return fail(SYLDET_ERR_INVALID_ARGUMENT, "NULL argument");
+    std::vector<float> tmp((size_t)n * bins);               // (a refused template leaves t_hat as it was)
+    if (int st = normalise(templ, n, bins, tmp.data())) return st;
+    std::memcpy(t_hat, tmp.data(), tmp.size() * sizeof(float));
+    return SYLDET_OK;
+}
+
+int syldet_match_scores_host(const float *t_hat, int32_t n, int32_t bins, const float *columns, int64_t n_frames, float *scores)
+{
+    if (int st = template_args(t_hat, n, bins)) return st;
+    if (n_frames < 0 || (n_frames > 0 && (!columns || !scores))) return fail(SYLDET_ERR_INVALID_ARGUMENT, "a NULL array or a negative count");
+    const float nan = std::numeric_limits<float>::quiet_NaN();
+    for (int64_t p = 0; p < n_frames; p++) {
+        if (p + n > n_frames) {
+            scores[p] = nan;
+            continue;
+        }
+        const float *x = columns + p * bins;
+        float dot = 0.0f, E = 0.0f;
+        for (int j = 0; j < n; j++) {
+            float e = 0.0f;
+            for (int b = 0; b < bins; b++) {
+                const float v = x[j * bins + b];
+                e = std::fmaf(v, v, e);
+                dot = std::fmaf(std::isfinite(v) ? v : 0.0f, t_hat[j * bins + b], dot);
+            }
+            E = E + e;
+        }
+        scores[p] = !std::isfinite(E) ? nan : E == 0.0f ? 0.0f : (dot + 0.0f) / std::sqrt(E);
+    }
+    return SYLDET_OK;
+}
+
+int syldet_match_peaks_host(const float *scores, int64_t n_positions, float threshold, int32_t separation, int64_t origin, int64_t hop, int32_t anchor,
+                            int64_t *events, int64_t capacity, int64_t *count, float *event_scores)
+{
+    if (int st = peaks_args(threshold, separation, capacity)) return st;
+    if (n_positions < 0 || !count || (n_positions > 0 && !scores) || (capacity > 0 && !events))
+        return fail(SYLDET_ERR_INVALID_ARGUMENT, "a NULL array or a negative count");
+    if (anchor < 0 || anchor >= SYLDET_MATCH_MAX_TEMPLATE || hop < 1 || hop >= ((int64_t)1 << 31) || origin < 0 || origin >= ((int64_t)1 << 32) ||
+        n_positions >= ((int64_t)1 << 31))
+        return fail(SYLDET_ERR_INVALID_ARGUMENT, "anchor outside [0, 32768), origin outside [0, 2^32), hop outside [1, 2^31) or 2^31 positions");
+    const int S = separation, k = S ? sd::match_level(S) : 0;
+    const int64_t L = n_positions + 2 * (int64_t)S;
+    std::vector<uint32_t> cur, nxt;
+    try {
+        // the keys with S absent positions on either side, then the maxima of every window of 2^k positions, pass by pass as the kernel
+        cur.assign((size_t)L, 0u);
+        nxt.assign((size_t)L, 0u);
+    } catch (const std::bad_alloc &) {
+        return fail(SYLDET_ERR_OUT_OF_MEMORY, "out of memory");
+    }
+    for (int64_t p = 0; p < n_positions; p++) cur[(size_t)(p + S)] = sd::match_key(scores[p]);
+    const std::vector<uint32_t> keys(cur.begin() + S, cur.begin() + S + n_positions);
+    for (int lev = 0; lev < k; lev++) {
+        const int64_t h = (int64_t)1 << lev;
+        for (int64_t i = 0; i < L; i++) nxt[(size_t)i] = std::max(cur[(size_t)i], i + h < L ? cur[(size_t)(i + h)] : 0u);
+        cur.swap(nxt);
+    }
+    const uint32_t tk = sd::match_key(threshold);
+    int64_t n = 0;
+    for (int64_t p = 0; p < n_positions; p++) {
+        const int64_t i = p + S;
+        if (!sd::match_rule(keys[(size_t)p], sd::match_left(cur.data(), i, S, k), sd::match_right(cur.data(), i, S, k), tk)) continue;
+        if (n < capacity) {
+            events[n] = sd::match_event(origin, hop, p, anchor);
+            if (event_scores) event_scores[n] = scores[p];
+        }
+        n++;
+    }
+    *count = n;
+    return SYLDET_OK;
+}
+
+}  // extern "C"

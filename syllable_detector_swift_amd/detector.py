@@ -951,6 +951,14 @@ class SyllableDetector:
         network, up to 16 hidden units and 4 outputs."""
         return Trainer(self)
 
+    # ---- template matching: a syllable's occurrences in the columns ------------------------
+    def matcher(self, template, anchor: Optional[int] = None) -> "Matcher":
+        """A Matcher over this bank's channels (syldet_matcher_create): scores(cols) is the cosine between `template`
+        [n, bins] and the window of n frames at every position of spectrogram()'s columns, peaks() the matches among them as
+        the event tables detections() makes, find() both.  anchor: the template's frame a match's sample number names
+        (default: its last, n - 1)."""
+        return Matcher(self, template, anchor)
+
     # ---- batch, host arrays -------------------------------------------------------
     def runHost(self, samples: np.ndarray, outputs: Optional[np.ndarray] = None, flags: Optional[np.ndarray] = None) -> Tuple[np.ndarray, np.ndarray]:
         """syldet_run: the batch call on host arrays, pipelined along time inside the library.  `outputs` / `flags`: arrays to
@@ -1480,6 +1488,12 @@ class Recordings:
         are spectrogram(rows)."""
         return Trainer(self.detector, recordings=self)
 
+    def matcher(self, template, anchor: Optional[int] = None) -> "Matcher":
+        """A Matcher whose detectors are these recordings: a window never reaches beyond its recording, matches are never
+        suppressed across two recordings of a row, and events count from each recording's own start (SyllableDetector.matcher).
+        The columns are spectrogram(rows)."""
+        return Matcher(self.detector, template, anchor, recordings=self)
+
 
 def _score_args(thresholds, labels):
     thr = np.ascontiguousarray(thresholds, dtype=np.float64).reshape(-1)
@@ -1789,6 +1803,142 @@ def alignStatsHost(windows, present):
                                            count.ctypes.data_as(_abi.c_int64_p), total.ctypes.data_as(_abi.c_double_p),
                                            squares.ctypes.data_as(_abi.c_double_p)))
     return count.reshape(shape), total.reshape(shape), squares.reshape(shape)
+
+
+class Matcher:
+    """Template matching (syldet_matcher_*, include/syldet.h "template matching"): the cosine between one normalised template and
+    the window at every position of the columns, and the matches among the scores.  A detector is a channel of the bank, or (made
+    by Recordings.matcher) a recording.  shape = (detectors, frames of the template, bins, anchor frame); template: the
+    normalised template t^ the scores are taken with; form: "matrix" or "plain", the score kernel this shape runs on.  The
+    detector (and the Recordings) must outlive it."""
+
+    def __init__(self, detector: SyllableDetector, template, anchor: Optional[int] = None, recordings: Optional[Recordings] = None):
+        self.detector = detector
+        self.recordings = recordings
+        t = np.asarray(template)
+        if t.ndim != 2 or t.dtype.kind != "f":
+            raise ValueError("the template must be a float array [frames, bins]")
+        t = np.ascontiguousarray(t, dtype=np.float32)
+        self._h = _abi.Handle()
+        check(_abi.lib.syldet_matcher_create(detector._h, None if recordings is None else recordings._h, t.ctypes.data_as(_abi.c_float_p),
+                                             t.shape[0], t.shape[1], -1 if anchor is None else int(anchor), C.byref(self._h)))
+        d, n, b, a, mf = C.c_int32(), C.c_int32(), C.c_int32(), C.c_int32(), C.c_int32()
+        check(_abi.lib.syldet_matcher_shape(self._h, C.byref(d), C.byref(n), C.byref(b), C.byref(a), C.byref(mf)))
+        self.shape = (d.value, n.value, b.value, a.value)
+        self.count, self.frames, self.bins, self.anchor = self.shape
+        self.form = "matrix" if mf.value else "plain"
+        self.template = np.empty((n.value, b.value), np.float32)
+        check(_abi.lib.syldet_matcher_template(self._h, self.template.ctypes.data_as(_abi.c_float_p)))
+
+    def close(self):
+        if getattr(self, "_h", None):
+            _abi.lib.syldet_matcher_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def scores(self, cols, out=None, stream=None):
+        """cols [C, n_frames, bins] float32 on the device as spectrogram() wrote them (rows may be a view with a larger stride)
+        -> scores [C, n_frames] float32: a detector's position p at its first frame + p, NaN wherever no window begins.  One
+        launch; a score has the same bits wherever its window lies.  Asynchronous on `stream`."""
+        torch = _torch()
+        det = self.detector
+        if not (cols.is_cuda and cols.dtype == torch.float32 and cols.device.index == det.device and cols.dim() == 3
+                and cols.shape[0] == det.channels and cols.shape[2] == self.bins):
+            raise ValueError("cols must be a float32 CUDA tensor [channels, n_frames, %d] on the detector's device" % self.bins)
+        J = int(cols.shape[1])
+        if J > 0 and not (cols.stride(2) == 1 and cols.stride(1) == self.bins):
+            raise ValueError("the frames of a row of cols must be contiguous")
+        row_stride = int(cols.stride(0)) if (det.channels > 1 and J > 0) else 0
+        want = (det.channels, J)
+        if out is None:
+            out = torch.empty(want, dtype=torch.float32, device=cols.device)
+        elif not (out.is_cuda and out.dtype == torch.float32 and tuple(out.shape) == want and out.is_contiguous() and out.device == cols.device):
+            raise ValueError("out must be a contiguous float32 CUDA tensor of shape %s on the columns' device" % (want,))
+        check(_abi.lib.syldet_match_scores_device(self._h, cols.data_ptr() if J else None, J, row_stride, out.data_ptr() if J else None,
+                                                  det._stream_ptr(stream)))
+        return out
+
+    def peaks(self, scores, threshold: float, separation: int, capacity: Optional[int] = None, withScores: bool = True, stream=None):
+        """scores [C, n_frames] as scores() made them -> (events [D, capacity] int64 ascending, counts [D] int64, eventScores
+        [D, capacity] float32 or None) on the device, the tables detections() makes: position p is a match iff its score is at
+        least `threshold`, above every score up to `separation` positions before it and not below any up to `separation` behind
+        it, NaN left out; its event is the sample number of frame p + anchor.  A count may exceed the capacity (default 1024).
+        One launch."""
+        torch = _torch()
+        det = self.detector
+        if not (scores.is_cuda and scores.dtype == torch.float32 and scores.dim() == 2 and scores.shape[0] == det.channels and scores.is_contiguous()
+                and scores.device.index == det.device):
+            raise ValueError("scores must be a contiguous float32 CUDA tensor [channels, n_frames] on the detector's device")
+        cap = 1024 if capacity is None else int(capacity)
+        D = self.count
+        events = torch.empty((D, max(cap, 0)), dtype=torch.int64, device=scores.device)
+        counts = torch.empty((D,), dtype=torch.int64, device=scores.device)
+        ev_scores = torch.empty((D, max(cap, 0)), dtype=torch.float32, device=scores.device) if withScores else None
+        J = int(scores.shape[1])
+        check(_abi.lib.syldet_match_peaks_device(self._h, scores.data_ptr() if J else None, J, float(threshold), int(separation),
+                                                 events.data_ptr() if events.numel() else None, cap, counts.data_ptr() if D else None,
+                                                 ev_scores.data_ptr() if (withScores and ev_scores.numel()) else None, det._stream_ptr(stream)))
+        return events, counts, ev_scores
+
+    def find(self, cols, threshold: float, separation: int, stream=None):
+        """scores() and peaks() -> (events, eventScores): two lists with one int64 and one float32 array a detector, every match
+        of it (the tables are made again with the largest count as capacity where the first capacity was too small)."""
+        s = self.scores(cols, stream=stream)
+        ev, cnt, es = self.peaks(s, threshold, separation, stream=stream)
+        c = cnt.cpu().numpy()
+        if c.size and int(c.max()) > ev.shape[1]:
+            ev, cnt, es = self.peaks(s, threshold, separation, capacity=int(c.max()), stream=stream)
+            c = cnt.cpu().numpy()
+        ev, es = ev.cpu().numpy(), es.cpu().numpy()
+        return [ev[d, :c[d]].copy() for d in range(self.count)], [es[d, :c[d]].copy() for d in range(self.count)]
+
+
+def matchNormalizeHost(template):
+    """syldet_match_normalize_host: t^ = float32(t / ||t||_2) of a template [frames, bins], norm and division in float64."""
+    t = np.ascontiguousarray(template, dtype=np.float32)
+    if t.ndim != 2:
+        raise ValueError("the template must be [frames, bins]")
+    out = np.empty_like(t)
+    check(_abi.lib.syldet_match_normalize_host(t.ctypes.data_as(_abi.c_float_p), t.shape[0], t.shape[1], out.ctypes.data_as(_abi.c_float_p)))
+    return out
+
+
+def matchScoresHost(templateHat, cols):
+    """syldet_match_scores_host: one detector's scores on the host, no device needed.  templateHat [n, bins] (a Matcher's
+    .template, or matchNormalizeHost's), cols [n_frames, bins] float32 -> scores [n_frames] float32, NaN in the last n - 1."""
+    t = np.ascontiguousarray(templateHat, dtype=np.float32)
+    x = np.ascontiguousarray(cols, dtype=np.float32)
+    if t.ndim != 2 or x.ndim != 2 or x.shape[1] != t.shape[1]:
+        raise ValueError("templateHat must be [n, bins] and cols [n_frames, bins]")
+    out = np.empty(x.shape[0], np.float32)
+    check(_abi.lib.syldet_match_scores_host(t.ctypes.data_as(_abi.c_float_p), t.shape[0], t.shape[1], x.ctypes.data_as(_abi.c_float_p), x.shape[0],
+                                            out.ctypes.data_as(_abi.c_float_p)))
+    return out
+
+
+def matchPeaksHost(scores, threshold: float, separation: int, origin: int, hop: int, anchor: int, capacity: Optional[int] = None):
+    """syldet_match_peaks_host: one detector's matches on the host, no device needed.  scores [positions] float32 -> (events
+    int64 [min(count, capacity)], count, eventScores float32): the rule and the event number the kernel runs."""
+    s = np.ascontiguousarray(scores, dtype=np.float32).reshape(-1)
+    cap = s.size if capacity is None else int(capacity)
+    events = np.zeros(max(cap, 0), np.int64)
+    ev_scores = np.zeros(max(cap, 0), np.float32)
+    n = C.c_int64()
+    check(_abi.lib.syldet_match_peaks_host(s.ctypes.data_as(_abi.c_float_p), s.size, float(threshold), int(separation), int(origin), int(hop), int(anchor),
+                                           events.ctypes.data_as(_abi.c_int64_p), cap, C.byref(n), ev_scores.ctypes.data_as(_abi.c_float_p)))
+    k = min(int(n.value), max(cap, 0))
+    return events[:k], int(n.value), ev_scores[:k]
 
 
 def _train_label_args(labels, labelOutputs):
