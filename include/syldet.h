@@ -1253,7 +1253,7 @@ int syldet_align_stats_host(const float *windows, const int64_t *present, int64_
  * convert_to_text.m.  Everything training reads is on the device already -- the columns of syldet_spectrogram_device, labels as the
  * scorer takes them -- and the N x I input matrix is those columns repeated timeRange times.  These calls give loss and gradient
  * of the network's parameters over weighted, labelled evaluations straight from the columns; that matrix is never formed.  The
- * optimiser is the caller's.  THE CONVENTION is the library's own (as the scorer's and the aligner's):
+ * optimiser is the caller's, or the one of "training from the tool" below.  THE CONVENTION is the library's own (as the scorer's and the aligner's):
  * A DETECTOR, its evaluations e and their sample numbers idx_e = first_index + e hop are the scorer's; for a recording e and the
  *   samples count from its own start, and its evaluation e is evaluation slot.first_eval + e of row slot.row.  Evaluation e of a row
  *   reads the I = timeRange x bins contiguous floats from frame e of that row of the columns (the aligner's COLUMNS window with
@@ -1323,6 +1323,77 @@ int syldet_train_targets_host(const int64_t *labels, int64_t n_labels, const int
 int syldet_train_gradient_device(syldet_trainer_t *t, const float *d_columns, int64_t n_frames, int64_t row_stride,
                                  const float *d_params, const float *d_targets, const float *d_weights, int64_t n_evals,
                                  double *d_loss, float *d_gradient, void *hip_stream);
+
+/* ---- training from the tool: the input map's range, an optimiser, seeded weights and the text writer ----
+ * The calls above give loss and gradient; these make the network: the mapminmax that MATLAB refits before it trains (without it the
+ * tanh units saturate), the optimiser's step, a fit that is launches only, a seeded start and the writer of the text format -- so
+ * that matches -> syldet_train_fit_device -> the scorer needs nothing but this header.  THE CONVENTION is the library's own:
+ * THE INPUT RANGE: for every input position i the least and the greatest value the position takes BEHIND THE INPUT FUNCTIONS IN
+ *   FRONT OF THE CONFIGURATION'S FIRST mapminmax -- scaling and functions evaluated as the gradient evaluates them, by the same
+ *   code -- over the CONTRIBUTING evaluations: those with weight > 0 (a NaN weight does not) whose I values there are all finite.
+ *   An evaluation that does not contribute contributes nothing whatever its columns hold (selection, as in the gradient).
+ *   d_range: float [2][I] = {least, greatest}, a zero written as +0.0; d_count: int64 [1], the contributing evaluations; with
+ *   none, {+inf, -inf} and 0.  The least and the greatest of finite values do not depend on order: the result is a function of
+ *   the arrays alone.  A bank without a mapminmax input function: SYLDET_ERR_UNSUPPORTED.
+ * THE INPUT MAP of a range: x_offsets = least, gains = fp32(2) / (greatest - least) in fp32, 1 where that difference is not above
+ *   0; yMin is -1 (syldet_train_input_map_host).  The trainer keeps ITS OWN COPY of the first mapminmax's parameters on the device:
+ *   syldet_trainer_set_input_map replaces them there (the bank and its configuration are not touched), later gradient, range and
+ *   fit calls of the trainer use them, syldet_trainer_input_map reads them back (index: the function's place in the chain).
+ * ADAM, on the moments m and v (2 P floats) the trainer keeps from creation.  Step number t >= 1; lr, beta1, beta2 and eps are
+ *   doubles (the usual defaults: 0.01, 0.9, 0.999, 1e-8).  On the host, in double: c1 = (float)(lr / (1 - pow(beta1, t))),
+ *   c2 = (float)(1 / sqrt(1 - pow(beta2, t))).  Per parameter, every operation rounded to fp32 on its own
+ *   (csrc/train_adam.hpp: one text for the kernel, the host and a stand-alone test, built without multiply-add contraction):
+ *       s = Wsum > 0 ? (float)(1.0 / Wsum) : 0.0f          (Wsum = d_loss[1], read on the device: nothing synchronises)
+ *       g = grad * s
+ *       m = (float)beta1 * m + (float)(1 - beta1) * g
+ *       v = (float)beta2 * v + (float)(1 - beta2) * (g * g)
+ *       p = p - c1 * (m / (sqrtf(v) * c2 + (float)eps))
+ *   At t = 1 the old m and v are NOT READ and count as 0: a fit needs no memset, and stale or NaN moments cannot leak.  Where Wsum
+ *   is not above 0 the parameters keep their bits (the moments follow the lines above with g = 0).  The mean loss written is
+ *   L / Wsum in double, 0 where Wsum is not above 0.
+ *   syldet_train_input_range_device   rows, detectors, tiles, n_evals, n_frames and row_stride are syldet_train_gradient_device's,
+ *       with r and without; so are the statuses.  Two launches ("train_range_kernel", "train_range_combine_kernel"): no
+ *       allocation, no synchronisation, no copy, no atomics; the partials lie in the scratch the gradient uses.
+ *   syldet_train_input_map_host       host only: range [2][I] -> x_offsets [I], gains [I].
+ *   syldet_trainer_set_input_map      waits for the stream of the trainer's last call and makes one blocking copy (the launch
+ *       rule of the targets call).  SYLDET_ERR_UNSUPPORTED without a mapminmax input function; a NaN y is refused.
+ *   syldet_trainer_input_map          each pointer may be NULL.
+ *   syldet_train_adam_device          one step on d_params [P] in place from d_loss [2] and d_gradient [P] as the gradient call
+ *       left them; d_mean_loss: double [1] or NULL.  One launch ("train_adam_kernel").
+ *   syldet_train_adam_host            host only, the same text: params, m, v [n_params] in place; loss [2]; mean_loss may be NULL.
+ *   syldet_train_fit_device           enqueues `steps` x (gradient, combine, step t = 1 .. steps): 3 x steps launches and nothing
+ *       else, with the loss and the gradient in the trainer's own scratch.  d_params [P] is updated in place, d_history [steps]
+ *       gets the mean loss in front of every step.  Parameters and history after k steps are bit for bit those of k separate
+ *       syldet_train_gradient_device + syldet_train_adam_device calls.  Every step is one call of the profile.
+ *   syldet_train_init_host            host only, theta [P] for (I, H, O): SplitMix64 from `seed` (state += 0x9E3779B97F4A7C15;
+ *       z = state; z = (z ^ z >> 30) * 0xBF58476D1CE4E5B9; z = (z ^ z >> 27) * 0x94D049BB133111EB; z ^= z >> 31), the k-th draw
+ *       u = fp32(z >> 40) * 2^-23 - 1 in [-1, 1), exact; in theta's order W1 = u * fp32(sqrt(3.0 / I)), b1 = u * 0.35f,
+ *       W2 = u * fp32(sqrt(3.0 / H)), b2 = 0 without draws.
+ *   syldet_train_config_with          a copy of cfg with the two layers' parameters replaced by params [n_params] (n_params must
+ *       be P) and, where x_offsets is not NULL, the first mapminmax input function's x_offsets, gains and y; freed by
+ *       syldet_config_free.
+ *   syldet_config_save_text           writes cfg in the text format syldet_config_load_text reads, numbers as "%.15g" (the
+ *       sampling rate and the frequency range as "%.1f"): what convert_to_text.m writes.  SYLDET_ERR_PARSE_OPEN: the file
+ *       cannot be written.
+ * Statuses, decided before any device is touched; a refused call leaves its results (and d_params) as they were.
+ * SYLDET_ERR_INVALID_ARGUMENT: what syldet_train_gradient_device refuses, a step outside [1, 2^31], steps outside [0, 2^31], an
+ * lr that is not finite, a beta outside [0, 1), an eps that is negative or not finite, a wrong n_params.                        */
+int syldet_train_input_range_device(syldet_trainer_t *t, const float *d_columns, int64_t n_frames, int64_t row_stride,
+                                    const float *d_weights, int64_t n_evals, float *d_range, int64_t *d_count, void *hip_stream);
+int syldet_train_input_map_host(const float *range, int32_t n_inputs, float *x_offsets, float *gains);
+int syldet_trainer_set_input_map(syldet_trainer_t *t, const float *x_offsets, const float *gains, float y);
+int syldet_trainer_input_map(const syldet_trainer_t *t, int32_t *index, float *x_offsets, float *gains, float *y);
+int syldet_train_adam_device(syldet_trainer_t *t, float *d_params, const double *d_loss, const float *d_gradient, int64_t step,
+                             double lr, double beta1, double beta2, double eps, double *d_mean_loss, void *hip_stream);
+int syldet_train_adam_host(float *params, float *m, float *v, const float *gradient, int64_t n_params, const double *loss,
+                           int64_t step, double lr, double beta1, double beta2, double eps, double *mean_loss);
+int syldet_train_fit_device(syldet_trainer_t *t, const float *d_columns, int64_t n_frames, int64_t row_stride,
+                            const float *d_targets, const float *d_weights, int64_t n_evals, float *d_params, int64_t steps,
+                            double lr, double beta1, double beta2, double eps, double *d_history, void *hip_stream);
+int syldet_train_init_host(uint64_t seed, int32_t n_inputs, int32_t n_hidden, int32_t n_outputs, float *theta);
+int syldet_train_config_with(const syldet_config_t *cfg, const float *params, int64_t n_params, const float *x_offsets,
+                             const float *gains, float y, syldet_config_t **out);
+int syldet_config_save_text(const syldet_config_t *cfg, const char *path);
 
 /* ---- template matching: find a syllable's occurrences in the columns ----
  * The scorer, the aligner and the trainer all start from labels; in the workflow the reference belongs to, labels come from matching

@@ -282,6 +282,25 @@ bool batch_matches(Batch &b, BatchDevice &d)
     return true;
 }
 
+// --train: the network trained on the batch's recordings, from the batch's fp32 rows.  A run whose files do not go through one batch
+// is known before its first batch runs (process_batched) and trains nothing; train_finish refuses it.  false: no memory.
+bool batch_train(Batch &b, BatchDevice &d)
+{
+    TrainRun *train = b.run.train;
+    if (!train) return true;
+    if (train->batches++ > 0 || train->several || train->outside || train->failed) return true;   // (refused: train_finish says why)
+    const float *rows = nullptr;
+    int st = 0;
+    if (!batch_rows(b, d, rows, st)) return false;
+    if (st) std::fprintf(stderr, "Unable to train on the batch: %s: %s\n", syldet_strerror(st), syldet_last_error());
+    std::vector<std::pair<std::string, int>> names;
+    for (const BatchFile &f : b.files)
+        for (int t = 0; t < f.info.channels; t++) names.emplace_back(f.path, t);
+    train->trained = !st && train_bank(*train, b.h, b.r, b.cfg, rows, b.row_samples, b.row_evals, b.C, names, b.stream);
+    train->failed = !train->trained;
+    return true;
+}
+
 // Stage 6, --align-dir: the windows of every recording's events, from the batch's arrays on the device (the outputs; the fp32 rows -- a
 // batch of 16-bit files is loaded once more, as fp32, from the same upload --; the rows' columns), in one launch.  false: no memory.
 bool batch_windows(Batch &b, BatchDevice &d)
@@ -359,10 +378,10 @@ int batch_on_device(Batch &b, BatchDevice &d)
 {
     if (int rc = load_and_run(b, d)) return rc < 0 ? 0 : rc;
     if (int rc = batch_meters(b, d)) return rc;
-    if (!b.ran) return !batch_windows(b, d) || !batch_matches(b, d) || hipStreamSynchronize(b.stream) != hipSuccess ? 2 : 0;   // no file of the batch has an evaluation: no events (labels may still be aligned)
+    if (!b.ran) return !batch_windows(b, d) || !batch_matches(b, d) || !batch_train(b, d) || hipStreamSynchronize(b.stream) != hipSuccess ? 2 : 0;   // no file of the batch has an evaluation: no events (labels may still be aligned)
     if (int rc = batch_events(b, d)) return rc;
     if (int rc = batch_score(b, d)) return rc;
-    if (!batch_windows(b, d) || !batch_matches(b, d)) return 2;
+    if (!batch_windows(b, d) || !batch_matches(b, d) || !batch_train(b, d)) return 2;
     return batch_tracks(b, d);
 }
 
@@ -482,12 +501,14 @@ int process_batched(const Run &run)
                 held += f.bytes() + (size_t)((double)f.info.frames * (double)f.info.channels * align_bytes_per_sample);
                 files.push_back(std::move(f));
                 if ((long long)held < o.batch.bytes) continue;
+                if (run.train && &p != &o.audio.back()) run.train->several = true;   // more files behind a full batch: nothing is trained
                 fold_status(rc, run_batch(run, files));
                 held = 0;
                 continue;
             }
         }
         // another rate that does not join the bank, unreadable, no tracks, the wrong number of tracks: exactly as without --batch, in its place
+        if (run.train) run.train->outside = true;          // (before the batch in front of it runs: nothing is trained)
         fold_status(rc, run_batch(run, files));
         held = 0;
         if (run.score && run.score->labels.count(p)) std::fprintf(stderr, "--score: %s does not go through the bank; its labels are left out.\n", p.c_str());

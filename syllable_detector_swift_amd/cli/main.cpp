@@ -10,6 +10,8 @@
 // --simulate-dir / --ttl-dir / --ttl-onsets-dir write the same files for any number of audio files; under --batch a batch's tracks are
 // made by syldet_recordings_trace_device_s16 / syldet_recordings_trigger*_device_s16 straight into every file's frames.
 // --match writes the occurrences of an exemplar in every track's columns as the labels --score reads (syldet_matcher_*).
+// --train trains the network on the one batch's recordings against such labels and writes it in the text format (syldet_trainer_*,
+// syldet_train_fit_device, syldet_config_save_text).
 // --levels-dir writes every file's --levels table likewise; under --batch by syldet_recordings_levels_device* /
 // syldet_recordings_output_levels_device on the batch's packed rows.
 // --simulate <out.wav> also writes what the reference's Simulator writes (ViewControllerSimulator.swift:251-344): the chosen output
@@ -99,8 +101,11 @@ int main(int argc, char **argv)
     MatchRun matching;
     if (o.has("--match"))
         if (const int rc = match_begin(matching, o.match, configs.v)) return rc;
+    TrainRun training;
+    if (o.has("--train"))
+        if (const int rc = train_begin(training, o.train, configs.v)) return rc;
     const Run run{o, configs.v, o.has("--debounce") ? o.debounce : 0.0, o.has("--score") ? &scoring : nullptr, o.has("--align-dir") ? &aligning : nullptr,
-                  o.has("--match") ? &matching : nullptr};
+                  o.has("--match") ? &matching : nullptr, o.has("--train") ? &training : nullptr};
     int rc = 0;
     o.dirs.make();
     if (o.batch.on) {
@@ -116,5 +121,6 @@ int main(int argc, char **argv)
     }
     if (run.align && !align_finish(aligning) && rc == 0) rc = 1;
     if (run.match && !match_finish(matching) && rc == 0) rc = 1;
+    if (run.train && !train_finish(training, configs.v[0]) && rc == 0) rc = 1;
     return rc;
 }

@@ -3,6 +3,7 @@
 
 #include "align.hpp"
 #include "match.hpp"
+#include "train.hpp"
 #include "wav.hpp"
 
 namespace {
@@ -15,6 +16,7 @@ struct Run {
     ScoreRun *score;                                        // null: no --score
     AlignRun *align;                                        // null: no --align-dir
     MatchRun *match;                                        // null: no --match
+    TrainRun *train = nullptr;                              // null: no --train
 };
 
 // What process_file writes for one audio file besides its lines (an empty path: not that one)

@@ -21,7 +21,7 @@ constexpr int kExUsage = 64;   // EX_USAGE, main.swift:40
 void usage(FILE *to)
 {
     std::fprintf(to,
-                 "Usage: syllable-detector-cli -n <net> [-a <audio>]... [-d <seconds>] [--device <k>] [--chunk <frames>] [--format <shortest|swift4>] [--resample <linear|sinc>] [--resample-quality <Z,beta,rolloff>] [--simulate <out.wav>] [--simulate-output <k>] [--levels <out.tsv>] [--levels-buffer <L>] [--levels-period <seconds>] [--ttl <out.wav>] [--ttl-mux] [--ttl-width <seconds>] [--ttl-steps <n>] [--ttl-buffer <L>] [--ttl-latency <seconds>] [--ttl-onsets <out.tsv>] [--simulate-dir <dir>] [--ttl-dir <dir>] [--ttl-onsets-dir <dir>] [--batch] [--batch-rows <N>] [--batch-bytes <B>] [--score <labels.tsv> --score-out <table.tsv>] [--score-thresholds <lo:hi:n>] [--score-tolerance <seconds>] [--score-cost <c>] [--score-output <k>] [--align-dir <dir>] [--align <columns|outputs|samples>] [--align-at <detections|labels>] [--align-before <units>] [--align-after <units>] [--match <template.npy> --match-out <matches.tsv>] [--match-threshold <v>] [--match-separation <seconds>] [--match-anchor <frame>] [--probe]\n"
+                 "Usage: syllable-detector-cli -n <net> [-a <audio>]... [-d <seconds>] [--device <k>] [--chunk <frames>] [--format <shortest|swift4>] [--resample <linear|sinc>] [--resample-quality <Z,beta,rolloff>] [--simulate <out.wav>] [--simulate-output <k>] [--levels <out.tsv>] [--levels-buffer <L>] [--levels-period <seconds>] [--ttl <out.wav>] [--ttl-mux] [--ttl-width <seconds>] [--ttl-steps <n>] [--ttl-buffer <L>] [--ttl-latency <seconds>] [--ttl-onsets <out.tsv>] [--simulate-dir <dir>] [--ttl-dir <dir>] [--ttl-onsets-dir <dir>] [--batch] [--batch-rows <N>] [--batch-bytes <B>] [--score <labels.tsv> --score-out <table.tsv>] [--score-thresholds <lo:hi:n>] [--score-tolerance <seconds>] [--score-cost <c>] [--score-output <k>] [--align-dir <dir>] [--align <columns|outputs|samples>] [--align-at <detections|labels>] [--align-before <units>] [--align-after <units>] [--match <template.npy> --match-out <matches.tsv>] [--match-threshold <v>] [--match-separation <seconds>] [--match-anchor <frame>] [--train <labels.tsv> --train-out <net.txt>] [--train-steps <n>] [--train-rate <lr>] [--train-width <seconds>] [--train-seed <s>] [--train-fit-map] [--train-output <k>] [--train-log <log.tsv>] [--probe]\n"
                  "  -n, --net <net>:\n      Path to trained network file.  Given k > 1 times: each file must have exactly k tracks, and track t runs network t (one mixed bank; the networks must share the sampling rate, window length, window overlap, time range and number of outputs).\n"
                  "  -a, --audio <audio>:\n      Path to the audio file to process.\n"
                  "  -d, --debounce <seconds>:\n      Number of seconds to debounce triggers.\n"
@@ -62,6 +62,15 @@ void usage(FILE *to)
                  "      --match-threshold <v>:\n      The least score of a match (default 0.77).\n"
                  "      --match-separation <seconds>:\n      No two matches of a track are closer than this (default: the template's length; at most 4096 frames).\n"
                  "      --match-anchor <frame>:\n      The template's frame whose sample a match names (default: its last).\n"
+                 "      --train <labels.tsv>:\n      Under --batch, also train the (one) network on the batch's recordings: lines of file, track and sample as --score reads and --match-out writes them, the labelled samples of one output. An evaluation within --train-width of a label is a positive, every other a negative; the two classes weigh a half each. Adam on the mean squared error, full batch, on the GPU. The detections printed are those of the network as given. All audio files must go through one batch: otherwise nothing is trained or written. Where the network cannot be written the exit status is 1 at least. Needs --train-out.\n"
+                 "      --train-out <net.txt>:\n      Where --train writes the trained network, in the text format -n reads.\n"
+                 "      --train-steps <n>:\n      Steps of the optimiser (default 200).\n"
+                 "      --train-rate <lr>:\n      The optimiser's learning rate (default 0.01).\n"
+                 "      --train-width <seconds>:\n      An evaluation this close to a label is a positive (default: one hop of the spectrogram).\n"
+                 "      --train-seed <s>:\n      Start from weights drawn from this seed instead of the network file's own.\n"
+                 "      --train-fit-map:\n      Refit the network's first mapminmax input function to the batch's columns before training, as the MATLAB training code does.\n"
+                 "      --train-output <k>:\n      The network output the labels belong to (default 0).\n"
+                 "      --train-log <log.tsv>:\n      Also write the mean loss in front of every step, one line a step (step, loss; tab separated) behind a first line, # positives <n> negatives <n>.\n"
                  "      --probe:\n      Only print what the audio files contain; does not touch the GPU.\n"
                  "The command line will write a comma-separated list of detection events (when the network has at least one output above threshold) to standard out. For example, it might output:\n"
                  "\n\t0,1593298,36.1292063492063,0.918557\n\n"
@@ -158,6 +167,17 @@ struct MatchOpt {
     long anchor = -1;                                       // < 0: the template's last frame
 };
 
+// --train: training (syldet_trainer_*, syldet_train_fit_device): the network of -n trained on the recordings of the one batch against
+// labelled samples, and written in the text format.  Standard output is that of the run without it.
+struct TrainOpt {
+    std::string labels_path, out_path, log_path;           // empty: none
+    long steps = 200;
+    double rate = 0.01, width = -1.0;                       // the half width in seconds; < 0: one hop
+    unsigned long long seed = 0;
+    bool has_seed = false, fit_map = false;
+    int output = 0;
+};
+
 // --batch: the -a files through ONE bank instead of a bank a file (syldet_recordings_*: every track of every file of a batch is a
 // recording laid into the bank's rows; the reference's tool runs them one after another on one core, main.swift:63-130).  Only
 // the detections and their outputs come back from the device -- and, under --simulate-dir / --ttl-dir / --ttl-onsets-dir, every
@@ -195,6 +215,7 @@ struct Options {
     ScoreOpt score;
     AlignOpt align;
     MatchOpt match;
+    TrainOpt train;
     std::set<std::string> given;                            // the options that were given, by their long names
     bool has(const char *name) const { return given.count(name) != 0; }
     bool any_of(std::initializer_list<const char *> names) const
@@ -300,6 +321,20 @@ int parse_options(int argc, char **argv, Options &o)
         else if (a == "--match-threshold") { if (!real(value(), o.match.threshold, [](double x) { return !std::isnan(x); })) return fail("--match-threshold takes a number."); }
         else if (a == "--match-separation") { if (!real(value(), o.match.separation, finite_zero_or_more)) return fail("--match-separation takes a number of seconds, 0 or more."); }
         else if (a == "--match-anchor") { if (!integer(value(), 0, SYLDET_MATCH_MAX_TEMPLATE - 1, o.match.anchor)) return fail("--match-anchor takes a frame of the template, 0 or more."); }
+        else if (a == "--train") o.train.labels_path = value();
+        else if (a == "--train-out") o.train.out_path = value();
+        else if (a == "--train-log") o.train.log_path = value();
+        else if (a == "--train-steps") { if (!integer(value(), 0, 1L << 24, o.train.steps)) return fail("--train-steps takes a number of steps, 0 or more."); }
+        else if (a == "--train-rate") { if (!real(value(), o.train.rate, [](double x) { return x > 0.0 && !std::isinf(x); })) return fail("--train-rate takes a positive number."); }
+        else if (a == "--train-width") { if (!real(value(), o.train.width, finite_zero_or_more)) return fail("--train-width takes a number of seconds, 0 or more."); }
+        else if (a == "--train-seed") {
+            long long seed = 0;
+            if (!integer(value(), 0, INT64_MAX, seed)) return fail("--train-seed takes a whole number, 0 or more.");
+            o.train.seed = (unsigned long long)seed;
+            o.train.has_seed = true;
+        }
+        else if (a == "--train-fit-map") o.train.fit_map = true;
+        else if (a == "--train-output") { if (!integer(value(), 0, 65535, o.train.output)) return fail("--train-output takes the number of a network output, 0 or more."); }
         else if (a == "--resample") {
             if (text() != "linear" && v != "sinc") return fail("--resample takes linear or sinc.");
             o.conv.sinc = v == "sinc";
@@ -362,6 +397,14 @@ int check_options(const Options &o)
     if (o.any_of({"--match-out", "--match-threshold", "--match-separation", "--match-anchor"}) && !o.has("--match"))
         return fail("--match-out, --match-threshold, --match-separation and --match-anchor need --match <template.npy>.");
     if (o.has("--match") && (o.match.path.empty() || o.match.out_path.empty())) return fail("--match <template.npy> needs --match-out <matches.tsv>.");
+    if (o.any_of({"--train-out", "--train-steps", "--train-rate", "--train-width", "--train-seed", "--train-fit-map", "--train-output", "--train-log"}) && !o.has("--train"))
+        return fail("--train-out, --train-steps, --train-rate, --train-width, --train-seed, --train-fit-map, --train-output and --train-log need --train <labels.tsv>.");
+    // the trainer's detectors are the recordings of a batch
+    if (o.has("--train") && !o.batch.on) return fail("--train needs --batch.");
+    if (o.has("--train") && (o.train.labels_path.empty() || o.train.out_path.empty())) return fail("--train <labels.tsv> needs --train-out <net.txt>.");
+    if (o.has("--train") && o.net.size() > 1) return fail("--train takes one network (-n).");
+    // (what needs the loaded network -- one the trainer does not take, --train-output beyond its outputs, --train-fit-map without a
+    // mapminmax -- is a usage error of train_begin, cli/train.hpp, reported behind these and before the GPU is opened)
     std::string twice;
     // every audio file's windows go under its own name, beside the three stack files
     if (o.has("--align-dir") && !(twice = name_given_twice(o.audio, {"count", "sum", "sumsq"})).empty())

@@ -189,6 +189,13 @@ class SyllableDetectorConfig:
                     "layer%d.transferFunction = %s" % (i, L.transferFunction)]
         return "\n".join(out) + "\n"
 
+    def saveText(self, path) -> None:
+        """syldet_config_save_text: writes toText()'s bytes to `path` through the library (arrays as float32, as the bank takes
+        them)."""
+        c, keep = self.to_abi()
+        check(_abi.lib.syldet_config_save_text(C.byref(c), str(path).encode()))
+        del keep
+
     # ---- C struct -----------------------------------------------------------------
     def to_abi(self):
         """Returns (Config, keepalive): the struct points into `keepalive`'s arrays."""

@@ -584,6 +584,18 @@ int train_groups(const TrainDesc &d, int rows, int64_t n_evals);   // workgroups
 hipError_t launch_train_gradient(const TrainDesc &d, const float *columns, int64_t row_stride, int rows, const float *params, const float *targets,
                                  const float *weights, int64_t n_evals, double *part, hipStream_t stream);
 hipError_t launch_train_combine(const TrainDesc &d, int groups, const double *part, double *loss, float *gradient, hipStream_t stream);
+// the input range in front of input function `at` (train_first_map: the first mapminmax, -1 without one): part as above <- the
+// groups' least and greatest [2][I] floats and their int64 counts (train_range_kernel); then range [2][I], count [1]
+// (train_range_combine_kernel; groups 0: {+inf, -inf} and 0)
+int train_first_map(const TrainDesc &d);
+hipError_t launch_train_range(const TrainDesc &d, int at, const float *columns, int64_t row_stride, int rows, const float *weights, int64_t n_evals,
+                              double *part, hipStream_t stream);
+hipError_t launch_train_range_combine(const TrainDesc &d, int groups, const double *part, float *range, int64_t *count, hipStream_t stream);
+// one Adam step on params [P] in place (train_adam.hpp; kernels_train_adam.hip): loss {L, Wsum} and gradient as the combine kernel
+// left them, read on the device; mean_loss (may be NULL) <- L / Wsum
+struct TrainAdamStep;
+hipError_t launch_train_adam(const TrainAdamStep &k, int P, const double *loss, const float *gradient, float *m, float *v, float *params, double *mean_loss,
+                             hipStream_t stream);
 
 // ---- template matching (kernels_match.hip; syldet_match_scores_device and syldet_match_peaks_device of include/syldet.h) ----
 // A detector of a packed plan: its frame 0 is frame `first` of row `row`, and it has `units` frames.

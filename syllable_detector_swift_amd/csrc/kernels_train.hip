@@ -18,6 +18,11 @@
 //                  Each tile's sums go into the workgroup's fp64 partial in global memory, every entry by the one thread that owns
 //                  it: no atomics, and the order is a function of the shapes alone.
 //   train_combine_kernel   A thread a parameter: the G partials added in group order in fp64, rounded once to fp32.
+//   train_range_kernel     The same tiles, staged the same way: a thread an evaluation makes the statistics of the input functions in
+//                  front of the first mapminmax and decides whether all I values there are finite; then a thread an input position
+//                  takes the least and the greatest over the tile's contributing evaluations into the workgroup's partial.  The
+//                  staging, the statistics and the values are the gradient kernel's own text (the SD_TRAIN_ macros).
+//   train_range_combine_kernel   A thread an input position: least and greatest over the G partials; the counts added.
 //
 // gfx950 only: wave = 64 lanes.  Plain HIP C++, vector loads and stores, no float atomics.
 
@@ -87,6 +92,115 @@ __device__ __forceinline__ float apply_fn(int kind, float v, float a, float b, f
     return kind == 0 || kind == 2 ? (v - a) / b : (v - a) * b + c;
 }
 
+// The input chain of one evaluation, ONE TEXT for train_gradient_kernel and train_range_kernel, as macros that are expanded inside the
+// kernels and not as functions: written as __forceinline__ functions (with the statistics in a struct, or in three arrays passed
+// by reference) the same statements gave the same bits but compiled to another instruction stream for the gradient kernel -- 15 %
+// more instructions in its inner loops, 31.3 -> 34.8 ms a gradient on the archive of MEASUREMENTS "Training" -- whereas expanded in
+// place the gradient kernel's code is instruction for instruction what it was before the range kernel shared it.  They use the
+// kernels' own names: d, cols, row, row_stride, e0, n, tid, NT, F, FP, T, I, stage; mine_rows, sa, sb, sc; stats, KS, xo, gn.
+//   SD_TRAIN_STAGE_TILE    the tile's n + T - 1 frames into LDS, scaled (linear / log / dB)
+//   SD_TRAIN_CHAIN_VALUE   defines value(t, f, upto): element (t, f) behind the input functions in front of `upto`
+//   SD_TRAIN_CHAIN_STATS   the statistics sa, sb, sc of the input functions in front of UPTO, in file order (l2normalize: frame sums,
+//                          then their sum; normalize: a range of 0 fills -1; normalizestd: the population sigma; a map: its y)
+//   SD_TRAIN_CHAIN_AT      V, the staged element of evaluation E at the thread's input position, through the functions in front of UPTO
+#define SD_TRAIN_STAGE_TILE()                                                  \
+    {                                                                          \
+        const float *src = cols + (int64_t)row * row_stride + e0 * F;          \
+        const unsigned total = (unsigned)(n + T - 1) * (unsigned)F;            \
+        for (unsigned idx = (unsigned)tid; idx < total; idx += (unsigned)NT) { \
+            const unsigned fr = idx / (unsigned)F, f = idx - fr * (unsigned)F; \
+            float v = src[idx];                                                \
+            if (d.scaling == 1) v = logf(v);                                   \
+            else if (d.scaling == 2) v = 20.0f * log10f(v);                    \
+            stage[fr * FP + f] = v;                                            \
+        }                                                                      \
+    }
+
+#define SD_TRAIN_CHAIN_VALUE()                                 \
+    auto value = [&](int t, int f, int upto) {                 \
+        float v = mine_rows[t * FP + f];                       \
+    _Pragma("unroll")                                          \
+        for (int kk = 0; kk < kMaxFns; kk++) {                 \
+            if (kk < upto) {                                   \
+                const int kind = d.in_fns[kk].kind;            \
+                float a = sa[kk], b = sb[kk];                  \
+                if (kind >= 3) {                               \
+                    a = d.maps[d.in_fns[kk].xoff + t * F + f]; \
+                    b = d.maps[d.in_fns[kk].gain + t * F + f]; \
+                }                                              \
+                v = apply_fn(kind, v, a, b, sc[kk]);           \
+            }                                                  \
+        }                                                      \
+        return v;                                              \
+    };
+
+#define SD_TRAIN_CHAIN_STATS(UPTO)                                    \
+    _Pragma("unroll")                                                 \
+    for (int k = 0; k < kMaxFns; k++) {                               \
+        if (k < (UPTO)) {                                             \
+            const int kind = d.in_fns[k].kind;                        \
+            if (kind == 0) {                                          \
+                float s = 0.0f;                                       \
+                for (int t = 0; t < T; t++) {                         \
+                    float fs = 0.0f;                                  \
+                    for (int f = 0; f < F; f++) {                     \
+                        const float v = value(t, f, k);               \
+                        fs = fmaf(v, v, fs);                          \
+                    }                                                 \
+                    s += fs;                                          \
+                }                                                     \
+                sb[k] = sqrtf(s);                                     \
+            } else if (kind == 1) {                                   \
+                float mn = INFINITY, mx = -INFINITY;                  \
+                for (int t = 0; t < T; t++)                           \
+                    for (int f = 0; f < F; f++) {                     \
+                        const float v = value(t, f, k);               \
+                        mn = fminf(mn, v);                            \
+                        mx = fmaxf(mx, v);                            \
+                    }                                                 \
+                const float range = mx - mn;                          \
+                if (range == 0.0f) {                                  \
+                    sb[k] = 0.0f;                                     \
+                    sc[k] = -1.0f;                                    \
+                } else {                                              \
+                    sb[k] = 2.0f / range;                             \
+                    sc[k] = (0.0f - mn - mx) / range;                 \
+                }                                                     \
+            } else if (kind == 2) {                                   \
+                float s = 0.0f;                                       \
+                for (int t = 0; t < T; t++) {                         \
+                    float fs = 0.0f;                                  \
+                    for (int f = 0; f < F; f++) fs += value(t, f, k); \
+                    s += fs;                                          \
+                }                                                     \
+                const float mean = s / (float)I;                      \
+                float q = 0.0f;                                       \
+                for (int t = 0; t < T; t++) {                         \
+                    float fq = 0.0f;                                  \
+                    for (int f = 0; f < F; f++) {                     \
+                        const float dl = value(t, f, k) - mean;       \
+                        fq = fmaf(dl, dl, fq);                        \
+                    }                                                 \
+                    q += fq;                                          \
+                }                                                     \
+                sa[k] = mean;                                         \
+                sb[k] = sqrtf(q / (float)I);                          \
+            } else {                                                  \
+                sc[k] = d.in_fns[k].y;                                \
+            }                                                         \
+        }                                                             \
+    }
+
+#define SD_TRAIN_CHAIN_AT(V, UPTO, E)                                                        \
+    _Pragma("unroll")                                                                        \
+    for (int k = 0; k < kMaxFns; k++) {                                                      \
+        if (k < (UPTO)) {                                                                    \
+            const int kind = d.in_fns[k].kind;                                               \
+            const float4 st = stats[(E) * KS + k];                                           \
+            V = apply_fn(kind, V, kind >= 3 ? xo[k] : st.x, kind >= 3 ? gn[k] : st.y, st.z); \
+        }                                                                                    \
+    }
+
 template <int HP>
 __global__ void __launch_bounds__(512)
 train_gradient_kernel(TrainDesc d, const float *__restrict__ cols, int64_t row_stride, const float *__restrict__ theta,
@@ -126,17 +240,7 @@ train_gradient_kernel(TrainDesc d, const float *__restrict__ cols, int64_t row_s
         const bool active = wgt > 0.0f;                        // (a NaN weight is not selected)
         if (!__syncthreads_or(active ? 1 : 0)) continue;
         if (tid < d.tile) sel[tid] = active ? 1 : 0;
-        {
-            const float *src = cols + (int64_t)row * row_stride + e0 * F;
-            const unsigned total = (unsigned)(n + T - 1) * (unsigned)F;
-            for (unsigned idx = (unsigned)tid; idx < total; idx += (unsigned)NT) {
-                const unsigned fr = idx / (unsigned)F, f = idx - fr * (unsigned)F;
-                float v = src[idx];
-                if (d.scaling == 1) v = logf(v);
-                else if (d.scaling == 2) v = 20.0f * log10f(v);
-                stage[fr * FP + f] = v;
-            }
-        }
+        SD_TRAIN_STAGE_TILE()
         __syncthreads();
 
         // ---- forward and the deltas: a thread an evaluation ----
@@ -155,78 +259,8 @@ train_gradient_kernel(TrainDesc d, const float *__restrict__ cols, int64_t row_s
         double loss = 0.0;
         if (active) {
             const float *mine_rows = stage + tid * FP;
-            // element (t, f) behind the input functions in front of `upto`
-            auto value = [&](int t, int f, int upto) {
-                float v = mine_rows[t * FP + f];
-#pragma unroll
-                for (int kk = 0; kk < kMaxFns; kk++) {
-                    if (kk < upto) {
-                        const int kind = d.in_fns[kk].kind;
-                        float a = sa[kk], b = sb[kk];
-                        if (kind >= 3) {
-                            a = d.maps[d.in_fns[kk].xoff + t * F + f];
-                            b = d.maps[d.in_fns[kk].gain + t * F + f];
-                        }
-                        v = apply_fn(kind, v, a, b, sc[kk]);
-                    }
-                }
-                return v;
-            };
-#pragma unroll
-            for (int k = 0; k < kMaxFns; k++) {
-                if (k < K) {
-                    const int kind = d.in_fns[k].kind;
-                    if (kind == 0) {                           // l2normalize: frame sums, then their sum
-                        float s = 0.0f;
-                        for (int t = 0; t < T; t++) {
-                            float fs = 0.0f;
-                            for (int f = 0; f < F; f++) {
-                                const float v = value(t, f, k);
-                                fs = fmaf(v, v, fs);
-                            }
-                            s += fs;
-                        }
-                        sb[k] = sqrtf(s);
-                    } else if (kind == 1) {                    // normalize
-                        float mn = INFINITY, mx = -INFINITY;
-                        for (int t = 0; t < T; t++)
-                            for (int f = 0; f < F; f++) {
-                                const float v = value(t, f, k);
-                                mn = fminf(mn, v);
-                                mx = fmaxf(mx, v);
-                            }
-                        const float range = mx - mn;
-                        if (range == 0.0f) {
-                            sb[k] = 0.0f;
-                            sc[k] = -1.0f;
-                        } else {
-                            sb[k] = 2.0f / range;
-                            sc[k] = (0.0f - mn - mx) / range;
-                        }
-                    } else if (kind == 2) {                    // normalizestd (population sigma)
-                        float s = 0.0f;
-                        for (int t = 0; t < T; t++) {
-                            float fs = 0.0f;
-                            for (int f = 0; f < F; f++) fs += value(t, f, k);
-                            s += fs;
-                        }
-                        const float mean = s / (float)I;
-                        float q = 0.0f;
-                        for (int t = 0; t < T; t++) {
-                            float fq = 0.0f;
-                            for (int f = 0; f < F; f++) {
-                                const float dl = value(t, f, k) - mean;
-                                fq = fmaf(dl, dl, fq);
-                            }
-                            q += fq;
-                        }
-                        sa[k] = mean;
-                        sb[k] = sqrtf(q / (float)I);
-                    } else {
-                        sc[k] = d.in_fns[k].y;
-                    }
-                }
-            }
+            SD_TRAIN_CHAIN_VALUE()
+            SD_TRAIN_CHAIN_STATS(K)
             // the first layer: a frame's products summed on their own, then the frames
             float acc[HP];
 #pragma unroll
@@ -357,14 +391,7 @@ train_gradient_kernel(TrainDesc d, const float *__restrict__ cols, int64_t row_s
             for (int e = 0; e < n; e++) {
                 if (!sel[e]) continue;
                 float v = col[e * FP];
-#pragma unroll
-                for (int k = 0; k < kMaxFns; k++) {
-                    if (k < K) {
-                        const int kind = d.in_fns[k].kind;
-                        const float4 st = stats[e * KS + k];
-                        v = apply_fn(kind, v, kind >= 3 ? xo[k] : st.x, kind >= 3 ? gn[k] : st.y, st.z);
-                    }
-                }
+                SD_TRAIN_CHAIN_AT(v, K, e)
                 const float4 *dr = (const float4 *)(d1s + e * HP);
 #pragma unroll
                 for (int q = 0; q < HP / 4; q++) {
@@ -391,6 +418,112 @@ train_combine_kernel(int P, int groups, const double *__restrict__ part, double 
     for (int g = 0; g < groups; g++) s = s + part[(int64_t)g * (P + 2) + p];
     if (p < P) gradient[p] = (float)s;
     else loss[p - P] = s;
+}
+
+// The input range (syldet_train_input_range_device): the gradient kernel's tiling and staging, the statistics and values of the
+// functions in front of input function `at` by the gradient's own text (the SD_TRAIN_ macros above).  A workgroup's partial
+// is float [2][I] (least, greatest) and an int64 count behind it, in the P + 2 doubles the gradient keeps a workgroup.
+__global__ void __launch_bounds__(512)
+train_range_kernel(TrainDesc d, int at, const float *__restrict__ cols, int64_t row_stride, const float *__restrict__ weights, int64_t n_evals,
+                   int tiles_per_row, int n_tiles, double *part)
+{
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    const int tid = (int)threadIdx.x, NT = (int)blockDim.x;
+    const int F = d.F, T = d.T, I = d.I, FP = d.FP, K = d.n_in_fns, KS = K > 0 ? K : 1;
+    const int P = d.H * I + d.H + d.O * d.H + d.O;
+    float *stage = (float *)(smem + d.lds_stage);              // [tile + T - 1][FP]
+    float4 *stats = (float4 *)(smem + d.lds_stats);            // [tile][KS]
+    int *sel = (int *)(smem + d.lds_sel);                      // [tile]
+    float *mine = (float *)(part + (int64_t)blockIdx.x * (P + 2));
+    for (int i = tid; i < I; i += NT) {
+        mine[i] = INFINITY;
+        mine[I + i] = -INFINITY;
+    }
+    int64_t count = 0;
+    for (int tl = (int)blockIdx.x; tl < n_tiles; tl += (int)gridDim.x) {
+        const int row = tl / tiles_per_row;
+        const int64_t e0 = (int64_t)(tl - row * tiles_per_row) * d.tile;
+        const int n = (int)(n_evals - e0 < d.tile ? n_evals - e0 : d.tile);
+        __syncthreads();                                       // the last tile's LDS is read to the end
+        float wgt = 0.0f;
+        if (tid < n) wgt = weights[(int64_t)row * n_evals + e0 + tid];
+        const bool active = wgt > 0.0f;                        // (a NaN weight is not selected)
+        if (!__syncthreads_or(active ? 1 : 0)) continue;
+        SD_TRAIN_STAGE_TILE()
+        __syncthreads();
+
+        // ---- a thread an evaluation: the statistics in front of the map, and whether all I values there are finite ----
+        float sa[kMaxFns], sb[kMaxFns], sc[kMaxFns];
+#pragma unroll
+        for (int k = 0; k < kMaxFns; k++) {
+            sa[k] = 0.0f;
+            sb[k] = 1.0f;
+            sc[k] = 0.0f;
+        }
+        bool whole = false;
+        if (active) {
+            const float *mine_rows = stage + tid * FP;
+            SD_TRAIN_CHAIN_VALUE()
+            SD_TRAIN_CHAIN_STATS(at)
+            whole = true;
+            for (int t = 0; t < T; t++)
+                for (int f = 0; f < F; f++) whole = whole && isfinite(value(t, f, at));
+        }
+        if (tid < d.tile) {
+            sel[tid] = whole ? 1 : 0;
+#pragma unroll
+            for (int k = 0; k < kMaxFns; k++)
+                if (k < KS) stats[tid * KS + k] = make_float4(sa[k], sb[k], sc[k], 0.0f);
+        }
+        const int contributing = __syncthreads_count(whole ? 1 : 0);
+        count += contributing;
+        if (!contributing) continue;
+
+        // ---- a thread an input position: the tile's contributing evaluations ----
+        for (int i = tid; i < I; i += NT) {
+            const int t = i / F, f = i - t * F;
+            float xo[kMaxFns], gn[kMaxFns];
+#pragma unroll
+            for (int k = 0; k < kMaxFns; k++) {
+                xo[k] = gn[k] = 0.0f;
+                if (k < at && d.in_fns[k].kind >= 3) {
+                    xo[k] = d.maps[d.in_fns[k].xoff + i];
+                    gn[k] = d.maps[d.in_fns[k].gain + i];
+                }
+            }
+            float mn = INFINITY, mx = -INFINITY;
+            const float *col = stage + t * FP + f;
+            for (int e = 0; e < n; e++) {
+                if (!sel[e]) continue;
+                float v = col[e * FP];
+                SD_TRAIN_CHAIN_AT(v, at, e)
+                mn = fminf(mn, v);
+                mx = fmaxf(mx, v);
+            }
+            mine[i] = fminf(mine[i], mn);
+            mine[I + i] = fmaxf(mine[I + i], mx);
+        }
+    }
+    if (tid == 0) *(int64_t *)(mine + 2 * I) = count;
+}
+
+// A thread an input position: the least and the greatest over the G partials (a zero as +0.0); thread 0 adds the counts.
+__global__ void __launch_bounds__(256)
+train_range_combine_kernel(int I, int P, int groups, const double *__restrict__ part, float *__restrict__ range, int64_t *__restrict__ count)
+{
+    const int i = (int)blockIdx.x * 256 + (int)threadIdx.x;
+    if (i >= I) return;
+    float mn = INFINITY, mx = -INFINITY;
+    int64_t c = 0;
+    for (int g = 0; g < groups; g++) {
+        const float *one = (const float *)(part + (int64_t)g * (P + 2));
+        mn = fminf(mn, one[i]);
+        mx = fmaxf(mx, one[I + i]);
+        if (i == 0) c += *(const int64_t *)(one + 2 * I);
+    }
+    range[i] = mn == 0.0f ? 0.0f : mn;
+    range[I + i] = mx == 0.0f ? 0.0f : mx;
+    if (i == 0) *count = c;
 }
 
 int up16(int n) { return (n + 15) / 16 * 16; }
@@ -454,7 +587,8 @@ hipError_t train_prepare(const TrainDesc &d)
 {
     if (d.lds_total <= 64 * 1024) return hipSuccess;
     const void *kern = d.HP == 4 ? (const void *)train_gradient_kernel<4> : d.HP == 8 ? (const void *)train_gradient_kernel<8> : (const void *)train_gradient_kernel<16>;
-    return hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, d.lds_total);
+    const hipError_t e = hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, d.lds_total);
+    return e != hipSuccess ? e : hipFuncSetAttribute((const void *)train_range_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, d.lds_total);
 }
 
 int train_groups(const TrainDesc &d, int rows, int64_t n_evals)
@@ -486,6 +620,31 @@ hipError_t launch_train_combine(const TrainDesc &d, int groups, const double *pa
 {
     const int P = train_param_count(d.I, d.H, d.O);
     hipLaunchKernelGGL(train_combine_kernel, dim3((unsigned)((P + 2 + 255) / 256)), dim3(256), 0, stream, P, groups, part, loss, gradient);
+    return hipGetLastError();
+}
+
+int train_first_map(const TrainDesc &d)
+{
+    for (int k = 0; k < d.n_in_fns; k++)
+        if (d.in_fns[k].kind == 3) return k;
+    return -1;
+}
+
+hipError_t launch_train_range(const TrainDesc &d, int at, const float *columns, int64_t row_stride, int rows, const float *weights, int64_t n_evals,
+                              double *part, hipStream_t stream)
+{
+    const int groups = train_groups(d, rows, n_evals);
+    if (groups <= 0) return hipSuccess;
+    const int tiles_per_row = (int)((n_evals + d.tile - 1) / d.tile), n_tiles = rows * tiles_per_row;
+    hipLaunchKernelGGL(train_range_kernel, dim3((unsigned)groups), dim3((unsigned)d.threads), (size_t)d.lds_total, stream, d, at, columns, row_stride, weights, n_evals,
+                       tiles_per_row, n_tiles, part);
+    return hipGetLastError();
+}
+
+hipError_t launch_train_range_combine(const TrainDesc &d, int groups, const double *part, float *range, int64_t *count, hipStream_t stream)
+{
+    hipLaunchKernelGGL(train_range_combine_kernel, dim3((unsigned)((d.I + 255) / 256)), dim3(256), 0, stream, d.I, train_param_count(d.I, d.H, d.O), groups, part, range,
+                       count);
     return hipGetLastError();
 }
 

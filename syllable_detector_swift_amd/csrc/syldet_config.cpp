@@ -530,6 +530,16 @@ const char *syldet_strerror(int status)
     }
 }
 
+// A configuration the library owns, as syldet_config_load_text hands one out.
+static int hand_out(std::unique_ptr<OwnedConfig> oc, syldet_config_t **out)
+{
+    Loaded *l = new Loaded();
+    l->owned = oc.release();
+    l->view = l->owned->view;
+    *out = &l->view;
+    return SYLDET_OK;
+}
+
 int syldet_config_load_text(const char *path, syldet_config_t **out)
 {
     if (!path || !out) return fail(SYLDET_ERR_INVALID_ARGUMENT, "NULL argument");
@@ -542,11 +552,7 @@ int syldet_config_load_text(const char *path, syldet_config_t **out)
     } catch (const std::bad_alloc &) {
         return fail(SYLDET_ERR_OUT_OF_MEMORY, "out of memory");
     }
-    Loaded *l = new Loaded();
-    l->owned = oc.release();
-    l->view = l->owned->view;
-    *out = &l->view;
-    return SYLDET_OK;
+    return hand_out(std::move(oc), out);
 }
 
 void syldet_config_free(syldet_config_t *cfg)
@@ -555,6 +561,126 @@ void syldet_config_free(syldet_config_t *cfg)
     Loaded *l = reinterpret_cast<Loaded *>(cfg);
     delete l->owned;
     delete l;
+}
+
+int syldet_train_config_with(const syldet_config_t *cfg, const float *params, int64_t n_params, const float *x_offsets, const float *gains, float y,
+                             syldet_config_t **out)
+{
+    if (!out) return fail(SYLDET_ERR_INVALID_ARGUMENT, "NULL argument");
+    *out = nullptr;
+    if (!cfg || !params) return fail(SYLDET_ERR_INVALID_ARGUMENT, "NULL argument");
+    if (x_offsets && !gains) return fail(SYLDET_ERR_INVALID_ARGUMENT, "x_offsets without gains");
+    try {
+        std::unique_ptr<OwnedConfig> oc(new OwnedConfig());
+        if (int st = oc->assign(*cfg)) return st;
+        if (oc->layers.size() != 2) return fail(SYLDET_ERR_UNSUPPORTED, "the trainer takes networks of exactly two layers");
+        if (oc->layers[1].inputs != oc->layers[0].outputs) return fail(SYLDET_ERR_LAYER_SHAPE, "the two layers do not fit each other");
+        int64_t P = 0;
+        for (int l = 0; l < 2; l++) P += (int64_t)oc->weights[l].size() + (int64_t)oc->biases[l].size();
+        if (n_params != P) return fail(SYLDET_ERR_INVALID_ARGUMENT, "n_params is " + std::to_string(n_params) + ", the two layers hold " + std::to_string(P));
+        const float *at = params;
+        for (int l = 0; l < 2; l++) {
+            std::copy(at, at + oc->weights[l].size(), oc->weights[l].begin());
+            at += oc->weights[l].size();
+            std::copy(at, at + oc->biases[l].size(), oc->biases[l].begin());
+            at += oc->biases[l].size();
+        }
+        if (x_offsets) {
+            size_t k = 0;
+            while (k < oc->input_fns.size() && oc->input_fns[k].kind != SYLDET_FN_MAPMINMAX) k++;
+            if (k == oc->input_fns.size()) return fail(SYLDET_ERR_UNSUPPORTED, "the configuration has no mapminmax input function");
+            std::copy(x_offsets, x_offsets + oc->fn_xoff_in[k].size(), oc->fn_xoff_in[k].begin());
+            std::copy(gains, gains + oc->fn_gain_in[k].size(), oc->fn_gain_in[k].begin());
+            oc->input_fns[k].y = y;
+        }
+        oc->relink();
+        return hand_out(std::move(oc), out);
+    } catch (const std::bad_alloc &) {
+        return fail(SYLDET_ERR_OUT_OF_MEMORY, "out of memory");
+    }
+}
+
+int syldet_config_save_text(const syldet_config_t *cfg, const char *path)
+{
+    if (!cfg || !path) return fail(SYLDET_ERR_INVALID_ARGUMENT, "NULL argument");
+    if (cfg->n_input_fns < 0 || cfg->n_output_fns < 0 || cfg->n_layers < 0 || cfg->n_thresholds < 0 || (cfg->n_layers > 0 && !cfg->layers) ||
+        (cfg->n_input_fns > 0 && !cfg->input_fns) || (cfg->n_output_fns > 0 && !cfg->output_fns) || (cfg->n_thresholds > 0 && !cfg->thresholds))
+        return fail(SYLDET_ERR_INVALID_ARGUMENT, "NULL array or negative count in configuration");
+    if (cfg->scaling < SYLDET_SCALING_LINEAR || cfg->scaling > SYLDET_SCALING_DB) return fail(SYLDET_ERR_INVALID_ARGUMENT, "bad enum value in configuration");
+    static const char *const fn_names[] = {"l2normalize", "normalize", "normalizestd", "mapminmax", "mapstd"};
+    static const char *const tf_names[] = {"TanSig", "LogSig", "PureLin", "SatLin"};
+    static const char *const scalings[] = {"linear", "log", "db"};
+    std::string text;
+    char buf[64];
+    try {
+        const auto num = [&](double v) {                   // %.15g, convert_to_text.m's
+            std::snprintf(buf, sizeof buf, "%.15g", v);
+            text += buf;
+        };
+        const auto integer = [&](const std::string &key, long long v) { text += key + " = " + std::to_string(v) + "\n"; };
+        const auto floats = [&](const std::string &key, const float *a, size_t n) {
+            text += key + " = ";
+            for (size_t i = 0; i < n; i++) {
+                if (i) text += ", ";
+                num((double)a[i]);
+            }
+            text += "\n";
+        };
+        text += "# AUTOMATICALLY GENERATED SYLLABLE DETECTOR CONFIGURATION\n";
+        std::snprintf(buf, sizeof buf, "samplingRate = %.1f\n", cfg->sampling_rate);
+        text += buf;
+        integer("fourierLength", cfg->fourier_length);
+        integer("windowLength", cfg->window_length);
+        integer("windowOverlap", cfg->window_overlap);
+        std::snprintf(buf, sizeof buf, "freqRange = %.1f, %.1f\n", cfg->freq_lo, cfg->freq_hi);
+        text += buf;
+        integer("timeRange", cfg->time_range);
+        text += "thresholds = ";
+        for (int i = 0; i < cfg->n_thresholds; i++) {
+            if (i) text += ", ";
+            num(cfg->thresholds[i]);
+        }
+        text += std::string("\nscaling = ") + scalings[cfg->scaling] + "\n";
+        for (int side = 0; side < 2; side++) {
+            const std::string nm = side ? "processOutputs" : "processInputs";
+            const int n = side ? cfg->n_output_fns : cfg->n_input_fns;
+            const syldet_fn_t *fns = side ? cfg->output_fns : cfg->input_fns;
+            integer(nm + "Count", n);
+            for (int k = 0; k < n; k++) {
+                const syldet_fn_t &f = fns[k];
+                const std::string key = nm + std::to_string(k);
+                if (f.kind < SYLDET_FN_L2NORMALIZE || f.kind > SYLDET_FN_MAPSTD) return fail(SYLDET_ERR_INVALID_ARGUMENT, "unknown processing function kind");
+                text += key + ".function = " + fn_names[f.kind] + "\n";
+                if (f.kind >= SYLDET_FN_MAPMINMAX) {
+                    if (f.count < 0 || (f.count > 0 && (!f.x_offsets || !f.gains))) return fail(SYLDET_ERR_INVALID_ARGUMENT, "mapminmax/mapstd need x_offsets and gains");
+                    floats(key + ".xOffsets", f.x_offsets, (size_t)f.count);
+                    floats(key + ".gains", f.gains, (size_t)f.count);
+                    text += key + (f.kind == SYLDET_FN_MAPMINMAX ? ".yMin = " : ".yMean = ");
+                    num((double)f.y);
+                    text += "\n";
+                }
+            }
+        }
+        integer("layers", cfg->n_layers);
+        for (int l = 0; l < cfg->n_layers; l++) {
+            const syldet_layer_t &L = cfg->layers[l];
+            const std::string key = "layer" + std::to_string(l);
+            if (L.inputs < 0 || L.outputs < 0 || !L.weights || !L.biases) return fail(SYLDET_ERR_INVALID_ARGUMENT, "NULL layer weights/biases");
+            if (L.transfer < SYLDET_TF_TANSIG || L.transfer > SYLDET_TF_SATLIN) return fail(SYLDET_ERR_INVALID_ARGUMENT, "unknown transfer function");
+            integer(key + ".inputs", L.inputs);
+            integer(key + ".outputs", L.outputs);
+            floats(key + ".weights", L.weights, (size_t)L.inputs * (size_t)L.outputs);
+            floats(key + ".biases", L.biases, (size_t)L.outputs);
+            text += key + ".transferFunction = " + tf_names[L.transfer] + "\n";
+        }
+    } catch (const std::bad_alloc &) {
+        return fail(SYLDET_ERR_OUT_OF_MEMORY, "out of memory");
+    }
+    FILE *f = std::fopen(path, "wb");
+    bool ok = f != nullptr && std::fwrite(text.data(), 1, text.size(), f) == text.size();
+    if (f && std::fclose(f) != 0) ok = false;
+    if (!ok) return fail(SYLDET_ERR_PARSE_OPEN, std::string("unableToOpenPath(\"") + path + "\")");
+    return SYLDET_OK;
 }
 
 int syldet_config_geometry(const syldet_config_t *cfg, syldet_geometry_t *out)

@@ -1,8 +1,11 @@
 // syldet_train.cpp -- training (include/syldet.h, "training"; kernels_train.hip): the trainer that keeps a packed plan's detectors,
 // the caller's labels, the network's fixed part and the partial sums on the device, so that syldet_train_targets_device with the
 // same labels and every syldet_train_gradient_device are launches only; and the targets on the host (train_targets.hpp, one detector).
+// Training from the tool (include/syldet.h): the input range of the chain in front of the first mapminmax and the trainer's own
+// copy of that map, the Adam step on the moments the trainer keeps, and the fit that enqueues gradient, combine and step.
 
 #include "syldet_handle.hpp"
+#include "train_adam.hpp"
 #include "train_targets.hpp"
 
 static_assert(SYLDET_TRAIN_MAX_HIDDEN == sd::kTrainMaxHidden && SYLDET_TRAIN_MAX_OUTPUTS == sd::kTrainMaxOut, "the header's limits are the kernel's");
@@ -16,6 +19,9 @@ struct syldet_trainer {
     sd::TrainDesc desc{};
     sd::DeviceBuffer d_fixed;                // maps | (packed) TrainDetDev [D] | row_begin [rows + 1]
     sd::DeviceBuffer d_part;                 // [max_groups][P + 2] fp64
+    sd::DeviceBuffer d_opt;                  // the optimiser's: loss [2] fp64 | gradient [P] | m [P] | v [P] fp32
+    int map_at = -1;                         // the first mapminmax input function (-1: none) and the host's copy of its parameters
+    std::vector<float> map;                  // x_offsets [I] | gains [I]
     const sd::TrainDetDev *d_dets = nullptr;
     const int32_t *d_row_begin = nullptr;
     hipStream_t last = nullptr;              // the stream of the last call that may still read the labels or write the partials
@@ -62,6 +68,36 @@ int outputs_arg(const int32_t *label_output, int64_t n, int O)
 }
 
 size_t up16(size_t n) { return (n + 15) / 16 * 16; }
+
+// what the gradient, the range and the fit check of their columns; row_stride 0 becomes a row's elements
+int columns_args(const syldet_trainer *t, int64_t n_evals, int64_t n_frames, int64_t *row_stride)
+{
+    if (n_evals < 0 || n_frames < 0) return fail(SYLDET_ERR_INVALID_ARGUMENT, "n_evals or n_frames is negative");
+    const sd::TrainDesc &d = t->desc;
+    if (t->packed && (n_evals != t->row_evals || n_frames != t->row_frames))
+        return fail(SYLDET_ERR_INVALID_ARGUMENT, "n_evals and n_frames must be the packed rows' " + std::to_string(t->row_evals) + " evaluations and " +
+                                                     std::to_string(t->row_frames) + " frames");
+    if (n_evals > 0 && n_frames < n_evals + d.T - 1)
+        return fail(SYLDET_ERR_INVALID_ARGUMENT, std::to_string(n_evals) + " evaluations read " + std::to_string(n_evals + d.T - 1) + " frames, " +
+                                                     std::to_string(n_frames) + " given");
+    if (n_frames > ((int64_t)1 << 40) / d.F) return fail(SYLDET_ERR_INVALID_ARGUMENT, "n_frames x bins is above 2^40");
+    if (*row_stride == 0) *row_stride = n_frames * d.F;
+    if (*row_stride < n_frames * d.F)
+        return fail(SYLDET_ERR_INVALID_ARGUMENT, "row_stride " + std::to_string(*row_stride) + " is below the " + std::to_string(n_frames * d.F) + " elements of a row");
+    return SYLDET_OK;
+}
+
+int tiles_arg(const syldet_trainer *t, int64_t n_evals)
+{
+    if ((int64_t)t->bank.channels * ((n_evals + t->desc.tile - 1) / t->desc.tile) > 0x7fffffff) return fail(SYLDET_ERR_UNSUPPORTED, "more than 2^31 - 1 tiles");
+    return SYLDET_OK;
+}
+
+int adam_args(int64_t step, double lr, double beta1, double beta2, double eps)
+{
+    const char *why = sd::train_adam_refusal(step, lr, beta1, beta2, eps);
+    return why ? fail(SYLDET_ERR_INVALID_ARGUMENT, why) : SYLDET_OK;
+}
 
 }  // namespace
 
@@ -176,6 +212,7 @@ int syldet_trainer_create(const syldet_t *h, const syldet_recordings_t *r, sylde
     SYLDET_HIP(sd::train_prepare(d));
     if (int st = t->d_fixed.reserve(n_maps + n_dets + n_rows + 16)) return st;
     if (int st = t->d_part.reserve((size_t)d.max_groups * ((size_t)t->P + 2) * sizeof(double))) return st;
+    if (int st = t->d_opt.reserve(16 + 3 * (size_t)t->P * sizeof(float))) return st;
     char *base = (char *)t->d_fixed.ptr;
     if (!maps.empty()) SYLDET_HIP(hipMemcpy(base, maps.data(), maps.size() * sizeof(float), hipMemcpyHostToDevice));
     if (!dets.empty()) SYLDET_HIP(hipMemcpy(base + n_maps, dets.data(), dets.size() * sizeof(sd::TrainDetDev), hipMemcpyHostToDevice));
@@ -184,6 +221,15 @@ int syldet_trainer_create(const syldet_t *h, const syldet_recordings_t *r, sylde
     t->d_dets = r ? (const sd::TrainDetDev *)(base + n_maps) : nullptr;
     t->d_row_begin = r ? (const int32_t *)(base + n_maps + n_dets) : nullptr;
     t->desc = d;
+    t->map_at = sd::train_first_map(d);
+    if (t->map_at >= 0) {
+        try {
+            t->map.assign(maps.begin() + d.in_fns[t->map_at].xoff, maps.begin() + d.in_fns[t->map_at].xoff + I);
+            t->map.insert(t->map.end(), maps.begin() + d.in_fns[t->map_at].gain, maps.begin() + d.in_fns[t->map_at].gain + I);
+        } catch (const std::bad_alloc &) {
+            return fail(SYLDET_ERR_OUT_OF_MEMORY, "out of memory");
+        }
+    }
     *out = t.release();
     return SYLDET_OK;
 }
@@ -191,9 +237,10 @@ int syldet_trainer_create(const syldet_t *h, const syldet_recordings_t *r, sylde
 int syldet_trainer_destroy(syldet_trainer_t *t)
 {
     if (!t) return SYLDET_OK;
-    if (t->d_fixed.ptr || t->d_part.ptr || t->d_labels.ptr) (void)hipSetDevice(t->bank.device);
+    if (t->d_fixed.ptr || t->d_part.ptr || t->d_labels.ptr || t->d_opt.ptr) (void)hipSetDevice(t->bank.device);
     t->d_fixed.release();
     t->d_part.release();
+    t->d_opt.release();
     t->d_labels.release();
     delete t;
     return SYLDET_OK;
@@ -306,21 +353,11 @@ int syldet_train_gradient_device(syldet_trainer_t *t, const float *d_columns, in
 {
     if (!t) return fail(SYLDET_ERR_INVALID_ARGUMENT, "NULL handle");
     if (!d_params || !d_loss || !d_gradient) return fail(SYLDET_ERR_INVALID_ARGUMENT, "NULL argument");
-    if (n_evals < 0 || n_frames < 0) return fail(SYLDET_ERR_INVALID_ARGUMENT, "n_evals or n_frames is negative");
     const sd::TrainDesc &d = t->desc;
-    if (t->packed && (n_evals != t->row_evals || n_frames != t->row_frames))
-        return fail(SYLDET_ERR_INVALID_ARGUMENT, "n_evals and n_frames must be the packed rows' " + std::to_string(t->row_evals) + " evaluations and " +
-                                                     std::to_string(t->row_frames) + " frames");
-    if (n_evals > 0 && n_frames < n_evals + d.T - 1)
-        return fail(SYLDET_ERR_INVALID_ARGUMENT, std::to_string(n_evals) + " evaluations read " + std::to_string(n_evals + d.T - 1) + " frames, " +
-                                                     std::to_string(n_frames) + " given");
-    if (n_frames > ((int64_t)1 << 40) / d.F) return fail(SYLDET_ERR_INVALID_ARGUMENT, "n_frames x bins is above 2^40");
-    if (row_stride == 0) row_stride = n_frames * d.F;
-    if (row_stride < n_frames * d.F)
-        return fail(SYLDET_ERR_INVALID_ARGUMENT, "row_stride " + std::to_string(row_stride) + " is below the " + std::to_string(n_frames * d.F) + " elements of a row");
+    if (int st = columns_args(t, n_evals, n_frames, &row_stride)) return st;
     const int rows = t->bank.channels;
     if (n_evals > 0 && rows > 0 && (!d_columns || !d_targets || !d_weights)) return fail(SYLDET_ERR_INVALID_ARGUMENT, "NULL argument");
-    if ((int64_t)rows * ((n_evals + d.tile - 1) / d.tile) > 0x7fffffff) return fail(SYLDET_ERR_UNSUPPORTED, "more than 2^31 - 1 tiles");
+    if (int st = tiles_arg(t, n_evals)) return st;
     hipStream_t stream = (hipStream_t)hip_stream;
     SYLDET_HIP(hipSetDevice(t->bank.device));
     t->last = stream;
@@ -332,6 +369,113 @@ int syldet_train_gradient_device(syldet_trainer_t *t, const float *d_columns, in
     }
     KernelTimer timer(t->h, stream, "train_combine_kernel");
     SYLDET_HIP(sd::launch_train_combine(d, groups, (const double *)t->d_part.ptr, d_loss, d_gradient, stream));
+    return SYLDET_OK;
+}
+
+int syldet_train_input_range_device(syldet_trainer_t *t, const float *d_columns, int64_t n_frames, int64_t row_stride, const float *d_weights,
+                                    int64_t n_evals, float *d_range, int64_t *d_count, void *hip_stream)
+{
+    if (!t) return fail(SYLDET_ERR_INVALID_ARGUMENT, "NULL handle");
+    if (!d_range || !d_count) return fail(SYLDET_ERR_INVALID_ARGUMENT, "NULL argument");
+    if (int st = columns_args(t, n_evals, n_frames, &row_stride)) return st;
+    const sd::TrainDesc &d = t->desc;
+    const int rows = t->bank.channels;
+    if (n_evals > 0 && rows > 0 && (!d_columns || !d_weights)) return fail(SYLDET_ERR_INVALID_ARGUMENT, "NULL argument");
+    if (int st = tiles_arg(t, n_evals)) return st;
+    if (t->map_at < 0) return fail(SYLDET_ERR_UNSUPPORTED, "the configuration has no mapminmax input function");
+    hipStream_t stream = (hipStream_t)hip_stream;
+    SYLDET_HIP(hipSetDevice(t->bank.device));
+    t->last = stream;
+    const int groups = sd::train_groups(d, rows, n_evals);
+    t->h->prof_begin();
+    {
+        KernelTimer timer(t->h, stream, "train_range_kernel");
+        SYLDET_HIP(sd::launch_train_range(d, t->map_at, d_columns, row_stride, rows, d_weights, n_evals, (double *)t->d_part.ptr, stream));
+    }
+    KernelTimer timer(t->h, stream, "train_range_combine_kernel");
+    SYLDET_HIP(sd::launch_train_range_combine(d, groups, (const double *)t->d_part.ptr, d_range, d_count, stream));
+    return SYLDET_OK;
+}
+
+int syldet_trainer_set_input_map(syldet_trainer_t *t, const float *x_offsets, const float *gains, float y)
+{
+    if (!t) return fail(SYLDET_ERR_INVALID_ARGUMENT, "NULL handle");
+    if (!x_offsets || !gains) return fail(SYLDET_ERR_INVALID_ARGUMENT, "NULL argument");
+    if (t->map_at < 0) return fail(SYLDET_ERR_UNSUPPORTED, "the configuration has no mapminmax input function");
+    if (std::isnan(y)) return fail(SYLDET_ERR_INVALID_ARGUMENT, "y is NaN");
+    const int I = t->desc.I;
+    const sd::DevFn &fn = t->desc.in_fns[t->map_at];
+    // behind the last call, which may still read the old map: one blocking copy (x_offsets and gains lie side by side)
+    SYLDET_HIP(hipSetDevice(t->bank.device));
+    SYLDET_HIP(hipStreamSynchronize(t->last));
+    std::copy(x_offsets, x_offsets + I, t->map.begin());
+    std::copy(gains, gains + I, t->map.begin() + I);
+    SYLDET_HIP(hipMemcpy((char *)t->d_fixed.ptr + (size_t)fn.xoff * sizeof(float), t->map.data(), 2 * (size_t)I * sizeof(float), hipMemcpyHostToDevice));
+    t->desc.in_fns[t->map_at].y = y;
+    return SYLDET_OK;
+}
+
+int syldet_trainer_input_map(const syldet_trainer_t *t, int32_t *index, float *x_offsets, float *gains, float *y)
+{
+    if (!t) return fail(SYLDET_ERR_INVALID_ARGUMENT, "NULL handle");
+    if (t->map_at < 0) return fail(SYLDET_ERR_UNSUPPORTED, "the configuration has no mapminmax input function");
+    const int I = t->desc.I;
+    if (index) *index = t->map_at;
+    if (x_offsets) std::copy(t->map.begin(), t->map.begin() + I, x_offsets);
+    if (gains) std::copy(t->map.begin() + I, t->map.end(), gains);
+    if (y) *y = t->desc.in_fns[t->map_at].y;
+    return SYLDET_OK;
+}
+
+int syldet_train_adam_device(syldet_trainer_t *t, float *d_params, const double *d_loss, const float *d_gradient, int64_t step, double lr, double beta1,
+                             double beta2, double eps, double *d_mean_loss, void *hip_stream)
+{
+    if (!t) return fail(SYLDET_ERR_INVALID_ARGUMENT, "NULL handle");
+    if (!d_params || !d_loss || !d_gradient) return fail(SYLDET_ERR_INVALID_ARGUMENT, "NULL argument");
+    if (int st = adam_args(step, lr, beta1, beta2, eps)) return st;
+    hipStream_t stream = (hipStream_t)hip_stream;
+    SYLDET_HIP(hipSetDevice(t->bank.device));
+    t->last = stream;
+    float *m = (float *)((char *)t->d_opt.ptr + 16) + t->P, *v = m + t->P;
+    t->h->prof_begin();
+    KernelTimer timer(t->h, stream, "train_adam_kernel");
+    SYLDET_HIP(sd::launch_train_adam(sd::train_adam_consts(step, lr, beta1, beta2, eps), t->P, d_loss, d_gradient, m, v, d_params, d_mean_loss, stream));
+    return SYLDET_OK;
+}
+
+int syldet_train_fit_device(syldet_trainer_t *t, const float *d_columns, int64_t n_frames, int64_t row_stride, const float *d_targets, const float *d_weights,
+                            int64_t n_evals, float *d_params, int64_t steps, double lr, double beta1, double beta2, double eps, double *d_history,
+                            void *hip_stream)
+{
+    if (!t) return fail(SYLDET_ERR_INVALID_ARGUMENT, "NULL handle");
+    if (!d_params) return fail(SYLDET_ERR_INVALID_ARGUMENT, "NULL argument");
+    if (steps < 0 || steps > ((int64_t)1 << 31)) return fail(SYLDET_ERR_INVALID_ARGUMENT, "steps must be in [0, 2^31]");
+    if (steps > 0 && !d_history) return fail(SYLDET_ERR_INVALID_ARGUMENT, "NULL d_history");
+    if (int st = adam_args(1, lr, beta1, beta2, eps)) return st;
+    if (int st = columns_args(t, n_evals, n_frames, &row_stride)) return st;
+    const sd::TrainDesc &d = t->desc;
+    const int rows = t->bank.channels;
+    if (n_evals > 0 && rows > 0 && (!d_columns || !d_targets || !d_weights)) return fail(SYLDET_ERR_INVALID_ARGUMENT, "NULL argument");
+    if (int st = tiles_arg(t, n_evals)) return st;
+    hipStream_t stream = (hipStream_t)hip_stream;
+    SYLDET_HIP(hipSetDevice(t->bank.device));
+    t->last = stream;
+    const int groups = sd::train_groups(d, rows, n_evals);
+    double *loss = (double *)t->d_opt.ptr;
+    float *grad = (float *)((char *)t->d_opt.ptr + 16), *m = grad + t->P, *v = m + t->P;
+    for (int64_t k = 1; k <= steps; k++) {
+        t->h->prof_begin();                                // (a step is a call of the profile: three kernels)
+        {
+            KernelTimer timer(t->h, stream, "train_gradient_kernel");
+            SYLDET_HIP(sd::launch_train_gradient(d, d_columns, row_stride, rows, d_params, d_targets, d_weights, n_evals, (double *)t->d_part.ptr, stream));
+        }
+        {
+            KernelTimer timer(t->h, stream, "train_combine_kernel");
+            SYLDET_HIP(sd::launch_train_combine(d, groups, (const double *)t->d_part.ptr, loss, grad, stream));
+        }
+        KernelTimer timer(t->h, stream, "train_adam_kernel");
+        SYLDET_HIP(sd::launch_train_adam(sd::train_adam_consts(k, lr, beta1, beta2, eps), t->P, loss, grad, m, v, d_params, d_history + (k - 1), stream));
+    }
     return SYLDET_OK;
 }
 

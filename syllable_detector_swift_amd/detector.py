@@ -2093,6 +2093,69 @@ class Trainer:
         history = torch.stack(history).cpu().tolist() if history else []
         return p.detach(), history
 
+    # ---- training from the tool: the input map, the optimiser, the fit (include/syldet.h "training from the tool") ----
+    def inputRange(self, cols, weights, stream=None):
+        """syldet_train_input_range_device: per input position the least and the greatest value behind the input functions in front
+        of the first mapminmax, over the evaluations with weight > 0 whose values there are all finite -> (range [2, I] float32,
+        count: a 0-dim int64 tensor), on the device.  Two launches."""
+        torch = _torch()
+        det = self.detector
+        I = det.geometry.inputs
+        ok = lambda x, dims: x.is_cuda and x.dtype == torch.float32 and x.dim() == dims and x.is_contiguous() and x.device.index == det.device
+        if not (ok(cols, 3) and cols.shape[0] == det.channels and cols.shape[2] == det.geometry.bins):
+            raise ValueError("cols must be a contiguous float32 CUDA tensor [channels, n_frames, %d] on the detector's device" % det.geometry.bins)
+        if not (ok(weights, 2) and weights.shape[0] == det.channels):
+            raise ValueError("weights must be a contiguous float32 CUDA tensor [channels, n_evals]")
+        rng = torch.empty((2, I), dtype=torch.float32, device=cols.device)
+        count = torch.empty(1, dtype=torch.int64, device=cols.device)
+        check(_abi.lib.syldet_train_input_range_device(self._h, cols.data_ptr(), int(cols.shape[1]), 0, weights.data_ptr(), int(weights.shape[1]),
+                                                       rng.data_ptr(), count.data_ptr(), det._stream_ptr(stream)))
+        return rng, count[0]
+
+    def setInputMap(self, xOffsets, gains, y: float = -1.0) -> None:
+        """syldet_trainer_set_input_map: replaces the first mapminmax's parameters in the trainer's own tables (host arrays [I]);
+        later gradient, range and fit calls use them.  Waits for the trainer's last call."""
+        I = self.detector.geometry.inputs
+        xo = np.ascontiguousarray(xOffsets, dtype=np.float32).reshape(-1)
+        g = np.ascontiguousarray(gains, dtype=np.float32).reshape(-1)
+        if xo.size != I or g.size != I:
+            raise ValueError("xOffsets and gains must hold %d values each" % I)
+        check(_abi.lib.syldet_trainer_set_input_map(self._h, xo.ctypes.data_as(_abi.c_float_p), g.ctypes.data_as(_abi.c_float_p), float(y)))
+
+    def inputMap(self):
+        """syldet_trainer_input_map -> (xOffsets [I], gains [I], y, the function's index in the input chain)"""
+        I = self.detector.geometry.inputs
+        xo, g = np.zeros(I, np.float32), np.zeros(I, np.float32)
+        y, at = C.c_float(), C.c_int32()
+        check(_abi.lib.syldet_trainer_input_map(self._h, C.byref(at), xo.ctypes.data_as(_abi.c_float_p), g.ctypes.data_as(_abi.c_float_p), C.byref(y)))
+        return xo, g, float(y.value), int(at.value)
+
+    def adamStep(self, params, loss, grad, step: int, lr: float = 0.01, beta1: float = 0.9, beta2: float = 0.999, eps: float = 1e-8, stream=None):
+        """syldet_train_adam_device: step number `step` (from 1) of Adam on params [P] IN PLACE, on the moments the trainer keeps,
+        from loss (float64 [2]: L, Wsum) and grad [P] as gradient(out=...) left them -> the mean loss L / Wsum, a 0-dim float64
+        tensor.  One launch."""
+        torch = _torch()
+        ok = lambda x, dt, n: x.is_cuda and x.dtype == dt and x.numel() == n and x.is_contiguous() and x.device.index == self.detector.device
+        if not (ok(params, torch.float32, self.paramCount) and ok(grad, torch.float32, self.paramCount) and ok(loss, torch.float64, 2)):
+            raise ValueError("params and grad must be contiguous float32 CUDA tensors of %d values, loss float64 [2]" % self.paramCount)
+        mean = torch.empty(1, dtype=torch.float64, device=params.device)
+        check(_abi.lib.syldet_train_adam_device(self._h, params.data_ptr(), loss.data_ptr(), grad.data_ptr(), int(step), float(lr), float(beta1), float(beta2),
+                                                float(eps), mean.data_ptr(), self.detector._stream_ptr(stream)))
+        return mean[0]
+
+    def fitDevice(self, cols, targets, weights, params, steps: int, lr: float = 0.01, beta1: float = 0.9, beta2: float = 0.999, eps: float = 1e-8,
+                  stream=None):
+        """syldet_train_fit_device: `steps` full-batch Adam steps on the mean loss, enqueued as 3 x steps launches -> (params [P]: a
+        copy of `params` after the steps, history: float64 [steps] on the device, the mean loss in front of every step)."""
+        torch = _torch()
+        self._check(cols, params, targets, weights)
+        p = params.detach().clone()
+        history = torch.empty(max(int(steps), 0), dtype=torch.float64, device=cols.device)
+        check(_abi.lib.syldet_train_fit_device(self._h, cols.data_ptr(), int(cols.shape[1]), 0, targets.data_ptr(), weights.data_ptr(), int(weights.shape[1]),
+                                               p.data_ptr(), int(steps), float(lr), float(beta1), float(beta2), float(eps), history.data_ptr(),
+                                               self.detector._stream_ptr(stream)))
+        return p, history
+
     def fitInputMap(self, cols, events, chunk: int = 1 << 16) -> SyllableDetectorConfig:
         """Refits the configuration's first mapminmax input function to data, as the MATLAB side does before it trains: the
         network inputs at `events` (a list of arrays of sample numbers, one per detector; an event's input is the evaluation it
@@ -2148,6 +2211,40 @@ class Trainer:
         fns[at].gains = np.where(rng > 0, np.float32(2.0) / np.where(rng > 0, rng, 1), np.float32(1.0)).astype(np.float32)
         fns[at].y = -1.0
         return cfg
+
+
+def trainInputMapHost(rng):
+    """syldet_train_input_map_host: range [2, I] -> (xOffsets [I], gains [I]) float32: xOffsets = least, gains = 2 / (greatest - least)
+    in float32, 1 where they are equal; yMin is -1."""
+    r = np.ascontiguousarray(rng, dtype=np.float32)
+    if r.ndim != 2 or r.shape[0] != 2:
+        raise ValueError("range must be [2, I]")
+    I = r.shape[1]
+    xo, g = np.zeros(I, np.float32), np.zeros(I, np.float32)
+    check(_abi.lib.syldet_train_input_map_host(r.ctypes.data_as(_abi.c_float_p), I, xo.ctypes.data_as(_abi.c_float_p), g.ctypes.data_as(_abi.c_float_p)))
+    return xo, g
+
+
+def trainAdamHost(params, m, v, grad, loss, step: int, lr: float = 0.01, beta1: float = 0.9, beta2: float = 0.999, eps: float = 1e-8):
+    """syldet_train_adam_host: one Adam step in the kernel's own text on float32 host arrays -> (params, m, v, mean loss); the
+    arguments are not changed."""
+    p, m, v = (np.array(a, dtype=np.float32).reshape(-1) for a in (params, m, v))
+    g = np.ascontiguousarray(grad, dtype=np.float32).reshape(-1)
+    l = np.ascontiguousarray(loss, dtype=np.float64).reshape(-1)
+    if not (p.size == m.size == v.size == g.size) or l.size != 2:
+        raise ValueError("params, m, v and grad must have one size, loss two values")
+    mean = C.c_double()
+    fp = lambda a: a.ctypes.data_as(_abi.c_float_p)
+    check(_abi.lib.syldet_train_adam_host(fp(p), fp(m), fp(v), fp(g), p.size, l.ctypes.data_as(_abi.c_double_p), int(step), float(lr), float(beta1), float(beta2),
+                                          float(eps), C.byref(mean)))
+    return p, m, v, float(mean.value)
+
+
+def trainInitHost(seed: int, inputs: int, hidden: int, outputs: int) -> np.ndarray:
+    """syldet_train_init_host: the seeded starting parameters [H I + H + O H + O] float32 of an (I, H, O) network."""
+    theta = np.zeros(max(int(hidden) * int(inputs) + int(hidden) + int(outputs) * int(hidden) + int(outputs), 1), np.float32)
+    check(_abi.lib.syldet_train_init_host(int(seed) & 0xFFFFFFFFFFFFFFFF, int(inputs), int(hidden), int(outputs), theta.ctypes.data_as(_abi.c_float_p)))
+    return theta
 
 
 def trainParamCount(config: SyllableDetectorConfig) -> int:
