@@ -1277,7 +1277,7 @@ int syldet_align_stats_host(const float *windows, const int64_t *present, int64_
  *   `tile` evaluations (syldet_trainer_shape); workgroup g of G = min(tiles, a bound from P) takes the tiles g, g + G, .. in order,
  *   adds each tile's fp32 sums into its fp64 partial, and a second kernel adds the G partials in order and rounds once to fp32.
  * LIMITS of this version, anything else SYLDET_ERR_UNSUPPORTED at creation: a plain bank (one network: not multi-network, mixed or
- *   sharded), exactly two layers, H <= SYLDET_TRAIN_MAX_HIDDEN, O <= SYLDET_TRAIN_MAX_OUTPUTS, and an input that fits the
+ *   sharded; a multi-network bank has syldet_trainer_create_multi below), exactly two layers, H <= SYLDET_TRAIN_MAX_HIDDEN, O <= SYLDET_TRAIN_MAX_OUTPUTS, and an input that fits the
  *   kernel's local memory (290 and 1160 inputs do); any scaling, any input chain, any output chain.
  *   syldet_trainer_create    h: the bank; r: NULL (D = its channels) or a packed-recordings handle of h (D = its recordings).  The
  *       network's fixed part, for recordings the slots, and the partial sums' scratch are put on the device once.  h, and r if
@@ -1394,6 +1394,45 @@ int syldet_train_init_host(uint64_t seed, int32_t n_inputs, int32_t n_hidden, in
 int syldet_train_config_with(const syldet_config_t *cfg, const float *params, int64_t n_params, const float *x_offsets,
                              const float *gains, float y, syldet_config_t **out);
 int syldet_config_save_text(const syldet_config_t *cfg, const char *path);
+
+/* ---- training a network per channel: the trainer of a multi-network bank ----
+ * A rig with N birds needs N networks, each trained on its own bird's rows.  syldet_trainer_create_multi makes ONE trainer for the N
+ * networks of a syldet_create_multi bank: every call below is then one launch (or two, or 3 x steps) for all of them, and network
+ * n's results are BIT FOR BIT what a plain trainer (syldet_trainer_create) on a plain bank of network n gives on that network's rows
+ * alone.  syldet_trainer_create itself is unchanged: it still refuses multi-network banks.
+ * THE CONVENTION:
+ *   - Network n's rows are the bank's rows whose channel_net is n, in ascending order.  With r a recording trains the network of
+ *     the row it was planned onto.
+ *   - Its tiles are those rows' tiles, numbered row-major; its workgroups are G_n = min(tiles_n, the plain trainer's bound for P)
+ *     (syldet_trainer_groups).  Workgroup g of network n takes the tiles g, g + G_n, .. in order; its fp64 partial and the combine
+ *     in group order are the plain kernel's, from the same text.
+ *   - Hence network n's {L, Wsum}, gradient, range, count, Adam step and fit history have THE BITS a plain trainer on a plain bank
+ *     of that network gives on those rows alone: the same columns, targets and weights gathered contiguously, with r = NULL.
+ *   - A trainer made by syldet_trainer_create_multi always runs the multi form, also at N = 1 (a plain bank).
+ *   - A network without a selected evaluation (or without a row) gives L = 0, Wsum = 0 and g = 0 exactly; Adam leaves its
+ *     parameters' bits.  Adam's 1 / Wsum is per network; c1 and c2 are shared.
+ * Each network's fixed part -- the input functions' x_offsets, gains and y, the output maps -- is read from ITS OWN configuration;
+ * compatibility (syldet_config_compatible) guarantees that the shapes, kinds, scaling and transfers are shared.
+ * THE ARRAYS of the calls above on such a trainer take a leading network dimension: d_params [N][P], d_loss [N][2], d_gradient
+ * [N][P], d_range [N][2][I], d_count [N], d_mean_loss [N], d_history [steps][N]; the moments are [N] x 2 P inside the trainer.
+ * Targets, weights and columns stay [rows][n_evals].. and syldet_train_targets_device is unchanged.  Statuses, the launch rule
+ * (gradient, range, Adam and fit are launches only: no allocation, no synchronisation, no copy; the group tables go to the device
+ * at creation) and the profile's names are the plain trainer's.
+ * LIMITS of this version: a plain bank (N = 1) or a syldet_create_multi bank; mixed and sharded banks stay SYLDET_ERR_UNSUPPORTED,
+ *   and every limit of the plain trainer holds for each network (two layers, H <= 16, O <= 4, the local memory, <= 8 functions,
+ *   N x P <= 2^31 - 1, N <= 65535).  The scratch is N x the plain trainer's, reserved at creation: SYLDET_ERR_OUT_OF_MEMORY where it does
+ *   not fit.  Out of scope: the command-line tool (--train keeps taking one network), mixed and sharded banks, a matrix-
+ *   instruction form of the first layer's gradient, deeper networks.
+ *   syldet_trainer_create_multi   h: a plain bank or a syldet_create_multi bank; r: NULL or a packed-recordings handle of h.
+ *   syldet_trainer_networks       N and (may be NULL) row_network [rows]: each bank row's network.  Any trainer (plain: 1, zeros).
+ *   syldet_trainer_groups         host only: groups [N] <- G_n for n_evals evaluations a row.  Any trainer.
+ *   syldet_trainer_set_input_map_of, syldet_trainer_input_map_of   syldet_trainer_set_input_map and syldet_trainer_input_map (which
+ *       address network 0) for network `net`; a net outside [0, N) is SYLDET_ERR_INVALID_ARGUMENT.                              */
+int syldet_trainer_create_multi(const syldet_t *h, const syldet_recordings_t *r, syldet_trainer_t **out);
+int syldet_trainer_networks(const syldet_trainer_t *t, int32_t *n_networks, int32_t *row_network);
+int syldet_trainer_groups(const syldet_trainer_t *t, int64_t n_evals, int32_t *groups);
+int syldet_trainer_set_input_map_of(syldet_trainer_t *t, int32_t net, const float *x_offsets, const float *gains, float y);
+int syldet_trainer_input_map_of(const syldet_trainer_t *t, int32_t net, int32_t *index, float *x_offsets, float *gains, float *y);
 
 /* ---- template matching: find a syllable's occurrences in the columns ----
  * The scorer, the aligner and the trainer all start from labels; in the workflow the reference belongs to, labels come from matching

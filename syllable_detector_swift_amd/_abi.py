@@ -321,6 +321,11 @@ SIGNATURES = {
     "syldet_train_init_host": (C.c_int, [C.c_uint64, C.c_int32, C.c_int32, C.c_int32, c_float_p]),
     "syldet_train_config_with": (C.c_int, [Config_p, c_float_p, C.c_int64, c_float_p, c_float_p, C.c_float, C.POINTER(Config_p)]),
     "syldet_config_save_text": (C.c_int, [Config_p, C.c_char_p]),
+    "syldet_trainer_create_multi": (C.c_int, [Handle, Handle, C.POINTER(Handle)]),
+    "syldet_trainer_networks": (C.c_int, [Handle, c_int32_p, c_int32_p]),
+    "syldet_trainer_groups": (C.c_int, [Handle, C.c_int64, c_int32_p]),
+    "syldet_trainer_set_input_map_of": (C.c_int, [Handle, C.c_int32, c_float_p, c_float_p, C.c_float]),
+    "syldet_trainer_input_map_of": (C.c_int, [Handle, C.c_int32, c_int32_p, c_float_p, c_float_p, c_float_p]),
     "syldet_matcher_create": (C.c_int, [Handle, Handle, c_float_p, C.c_int32, C.c_int32, C.c_int32, C.POINTER(Handle)]),
     "syldet_matcher_destroy": (C.c_int, [Handle]),
     "syldet_matcher_shape": (C.c_int, [Handle, c_int32_p, c_int32_p, c_int32_p, c_int32_p, c_int32_p]),

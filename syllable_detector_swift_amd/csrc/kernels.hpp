@@ -596,6 +596,29 @@ hipError_t launch_train_range_combine(const TrainDesc &d, int groups, const doub
 struct TrainAdamStep;
 hipError_t launch_train_adam(const TrainAdamStep &k, int P, const double *loss, const float *gradient, float *m, float *v, float *params, double *mean_loss,
                              hipStream_t stream);
+// The multi form (syldet_trainer_create_multi): a network per row.  The tables lie on the device from creation: every network's
+// own TrainDesc (its maps and its functions' y; the shape and the launch shape are shared), the bank's rows sorted by network
+// (ascending within one) and where each network's rows begin.  The grid is (min(max_rows x tiles a row, max_groups), N):
+// workgroup g of network n leaves at once unless g < G_n = min(network n's tiles, max_groups), and else is workgroup g of G_n of a
+// plain launch over that network's rows alone -- the same tiles in the same order, partial n max_groups + g.  params [N][P];
+// loss [N][2], gradient [N][P]; range [N][2][I], count [N]; the Adam step's moments and mean_loss [N].
+struct TrainMulti {
+    const TrainDesc *descs;                  // [N]
+    const int32_t *rows;                     // [rows] sorted by network
+    const int32_t *net_row_begin;            // [N + 1]
+    int n_nets, max_rows;                    // max_rows: the most rows one network has
+};
+hipError_t train_prepare_multi(const TrainDesc &d);
+hipError_t launch_train_gradient_multi(const TrainDesc &d, const TrainMulti &mu, const float *columns, int64_t row_stride, const float *params,
+                                       const float *targets, const float *weights, int64_t n_evals, double *part, hipStream_t stream);
+hipError_t launch_train_combine_multi(const TrainDesc &d, const TrainMulti &mu, int64_t n_evals, const double *part, double *loss, float *gradient,
+                                      hipStream_t stream);
+hipError_t launch_train_range_multi(const TrainDesc &d, const TrainMulti &mu, int at, const float *columns, int64_t row_stride, const float *weights,
+                                    int64_t n_evals, double *part, hipStream_t stream);
+hipError_t launch_train_range_combine_multi(const TrainDesc &d, const TrainMulti &mu, int64_t n_evals, const double *part, float *range, int64_t *count,
+                                            hipStream_t stream);
+hipError_t launch_train_adam_multi(const TrainAdamStep &k, int P, int n_nets, const double *loss, const float *gradient, float *m, float *v, float *params,
+                                   double *mean_loss, hipStream_t stream);
 
 // ---- template matching (kernels_match.hip; syldet_match_scores_device and syldet_match_peaks_device of include/syldet.h) ----
 // A detector of a packed plan: its frame 0 is frame `first` of row `row`, and it has `units` frames.

@@ -755,6 +755,7 @@ static int create_multi_impl(const syldet_config_t *const *cfgs, int32_t n_nets,
         h->fused.desc.thresholds = h->net.thresholds;            // (network 0's, first in the table that replaced its own)
         if (on_fold)
             if (int st = upload_fold_nets(h.get(), own)) return st;
+        h->net_cfgs = std::move(own);
     } catch (const std::bad_alloc &) {
         return fail(SYLDET_ERR_OUT_OF_MEMORY, "out of memory");
     }

@@ -184,6 +184,7 @@ struct syldet {
     // and thresholds (net.params_stride / thr_stride), and the fold kernel's FusedNet tables (d_fnets, fnets).
     int n_nets = 1;
     std::vector<int> net_of;          // [C] (empty for one network)
+    std::vector<std::unique_ptr<OwnedConfig>> net_cfgs;   // [n_nets] every network's configuration (what syldet_trainer_create_multi reads)
     std::vector<double> chan_thr0;    // [C] the first threshold of each channel's network (syldet_last_detected)
     DeviceBuffer d_net_of;            // [C] int
     // the Simulator's trace (syldet_trace*): channel c divides by Float(thresholds[k]) of its own network

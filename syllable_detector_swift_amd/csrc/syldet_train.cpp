@@ -3,6 +3,8 @@
 // same labels and every syldet_train_gradient_device are launches only; and the targets on the host (train_targets.hpp, one detector).
 // Training from the tool (include/syldet.h): the input range of the chain in front of the first mapminmax and the trainer's own
 // copy of that map, the Adam step on the moments the trainer keeps, and the fit that enqueues gradient, combine and step.
+// Training a network per channel (syldet_trainer_create_multi): the same trainer with N networks' fixed parts and the group tables
+// (kernels.hpp, TrainMulti) on the device; its calls launch the multi form of the kernels (kernels_train_multi.hip).
 
 #include "syldet_handle.hpp"
 #include "train_adam.hpp"
@@ -17,11 +19,19 @@ struct syldet_trainer {
     int D = 0, P = 0;
     int64_t row_evals = 0, row_frames = 0;   // (packed) what n_evals and n_frames must be
     sd::TrainDesc desc{};
-    sd::DeviceBuffer d_fixed;                // maps | (packed) TrainDetDev [D] | row_begin [rows + 1]
-    sd::DeviceBuffer d_part;                 // [max_groups][P + 2] fp64
-    sd::DeviceBuffer d_opt;                  // the optimiser's: loss [2] fp64 | gradient [P] | m [P] | v [P] fp32
+    sd::DeviceBuffer d_fixed;                // maps [N] | (packed) TrainDetDev [D] | row_begin [rows + 1] | (multi) TrainDesc [N] | rows by network | net_row_begin [N + 1]
+    sd::DeviceBuffer d_part;                 // [N][max_groups][P + 2] fp64
+    sd::DeviceBuffer d_opt;                  // the optimiser's: loss [N][2] fp64 | gradient [N][P] | m [N][P] | v [N][P] fp32
     int map_at = -1;                         // the first mapminmax input function (-1: none) and the host's copy of its parameters
-    std::vector<float> map;                  // x_offsets [I] | gains [I]
+    std::vector<float> map;                  // [N] x_offsets [I] | gains [I]
+    // the multi form (syldet_trainer_create_multi; N = 1 and multi = false: the plain trainer, whose launches read desc alone)
+    bool multi = false;
+    int N = 1;
+    int maps_per = 0;                        // floats a network has in maps
+    std::vector<int32_t> row_net, net_rows;  // [rows] a row's network; [N] the rows a network has
+    std::vector<sd::TrainDesc> descs;        // [N] every network's own (desc is network 0's); on the device at descs_at of d_fixed
+    size_t descs_at = 0;
+    sd::TrainMulti mu{};
     const sd::TrainDetDev *d_dets = nullptr;
     const int32_t *d_row_begin = nullptr;
     hipStream_t last = nullptr;              // the stream of the last call that may still read the labels or write the partials
@@ -112,20 +122,33 @@ int syldet_train_param_count(const syldet_config_t *cfg, int64_t *n_params)
     return SYLDET_OK;
 }
 
-int syldet_trainer_create(const syldet_t *h, const syldet_recordings_t *r, syldet_trainer_t **out)
+// Both creations.  cfgs: the N networks' configurations, cfgs[0] the bank's own; multi: the trainer runs the multi form (also at N = 1).
+static int trainer_create(const syldet_t *h, const syldet_recordings_t *r, const std::vector<const syldet_config_t *> &cfgs, bool multi, syldet_trainer_t **out)
 {
-    if (!out) return fail(SYLDET_ERR_INVALID_ARGUMENT, "NULL argument");
-    *out = nullptr;
-    if (!h) return fail(SYLDET_ERR_INVALID_ARGUMENT, "NULL handle");
-    if (h->n_nets != 1 || !h->classes.empty() || h->root)
-        return fail(SYLDET_ERR_UNSUPPORTED, "the trainer takes a plain bank: one network, not a multi-network or mixed one");
-    const syldet_config_t &c = h->cfg.view;
+    const syldet_config_t &c = *cfgs[0];
+    const int N = (int)cfgs.size();
     int I = 0, H = 0, O = 0;
-    if (int st = two_layers(c, &I, &H, &O)) return st;
-    if (H > SYLDET_TRAIN_MAX_HIDDEN || O > SYLDET_TRAIN_MAX_OUTPUTS)
-        return fail(SYLDET_ERR_UNSUPPORTED, "the trainer takes up to " + std::to_string(SYLDET_TRAIN_MAX_HIDDEN) + " hidden units and " +
-                                                std::to_string(SYLDET_TRAIN_MAX_OUTPUTS) + " outputs (" + std::to_string(H) + " and " + std::to_string(O) + " given)");
-    if (c.n_input_fns > sd::kMaxFns || c.n_output_fns > sd::kMaxFns) return fail(SYLDET_ERR_UNSUPPORTED, "more than 8 processing functions");
+    for (int n = 0; n < N; n++) {
+        const syldet_config_t &cn = *cfgs[(size_t)n];
+        int In = 0, Hn = 0, On = 0;
+        if (int st = two_layers(cn, &In, &Hn, &On)) return st;
+        if (Hn > SYLDET_TRAIN_MAX_HIDDEN || On > SYLDET_TRAIN_MAX_OUTPUTS)
+            return fail(SYLDET_ERR_UNSUPPORTED, "the trainer takes up to " + std::to_string(SYLDET_TRAIN_MAX_HIDDEN) + " hidden units and " +
+                                                    std::to_string(SYLDET_TRAIN_MAX_OUTPUTS) + " outputs (" + std::to_string(Hn) + " and " + std::to_string(On) + " given)");
+        if (cn.n_input_fns > sd::kMaxFns || cn.n_output_fns > sd::kMaxFns) return fail(SYLDET_ERR_UNSUPPORTED, "more than 8 processing functions");
+        if (n == 0) {
+            I = In;
+            H = Hn;
+            O = On;
+            continue;
+        }
+        // (what syldet_config_compatible guarantees of a multi-network bank, checked where the kernel relies on it)
+        bool same = In == I && Hn == H && On == O && cn.scaling == c.scaling && cn.n_input_fns == c.n_input_fns && cn.n_output_fns == c.n_output_fns &&
+                    cn.layers[0].transfer == c.layers[0].transfer && cn.layers[1].transfer == c.layers[1].transfer;
+        for (int k = 0; same && k < c.n_input_fns; k++) same = cn.input_fns[k].kind == c.input_fns[k].kind;
+        for (int k = 0; same && k < c.n_output_fns; k++) same = cn.output_fns[k].kind == c.output_fns[k].kind;
+        if (!same) return fail(SYLDET_ERR_UNSUPPORTED, "network " + std::to_string(n) + " differs from network 0 in shape, scaling, transfer or chain");
+    }
     sd::BankInfo b{};
     sd::bank_info(h, &b);
     sd::TrainDesc d{};
@@ -142,6 +165,9 @@ int syldet_trainer_create(const syldet_t *h, const syldet_recordings_t *r, sylde
     if (I != b.geom.inputs || O != b.geom.outputs || !sd::train_plan(d))
         return fail(SYLDET_ERR_UNSUPPORTED, "a network of " + std::to_string(I) + " inputs (" + std::to_string(d.F) + " bins x " + std::to_string(d.T) +
                                                 " columns) does not fit the gradient kernel's local memory");
+    const int P = sd::train_param_count(I, H, O);
+    if ((int64_t)N * P > 0x7fffffff) return fail(SYLDET_ERR_UNSUPPORTED, "more than 2^31 - 1 parameters in all");
+    if (N > 65535) return fail(SYLDET_ERR_UNSUPPORTED, "more than 65535 networks (the network is a launch's grid.y)");
     int32_t D = b.channels;
     int64_t row_samples = 0, row_evals = 0;
     if (r)
@@ -150,7 +176,7 @@ int syldet_trainer_create(const syldet_t *h, const syldet_recordings_t *r, sylde
     std::unique_ptr<syldet_trainer, int (*)(syldet_trainer_t *)> t(nullptr, syldet_trainer_destroy);
     std::vector<float> maps;
     std::vector<sd::TrainDetDev> dets;
-    std::vector<int32_t> row_begin;
+    std::vector<int32_t> row_begin, sorted_rows, net_row_begin;
     try {
         t.reset(new syldet_trainer());
         t->bank = b;
@@ -159,21 +185,40 @@ int syldet_trainer_create(const syldet_t *h, const syldet_recordings_t *r, sylde
             maps.insert(maps.end(), p, p + n);
             return at;
         };
-        for (int k = 0; k < c.n_input_fns; k++) {
-            const syldet_fn_t &f = c.input_fns[k];
-            d.in_fns[k].kind = f.kind;
-            d.in_fns[k].y = f.y;
-            if (f.kind >= SYLDET_FN_MAPMINMAX) {
-                d.in_fns[k].xoff = push(f.x_offsets, I);
-                d.in_fns[k].gain = push(f.gains, I);
+        // every network's maps in a block of its own, laid out alike: the offsets below are into the network's block
+        for (int n = 0; n < N; n++) {
+            const syldet_config_t &cn = *cfgs[(size_t)n];
+            sd::TrainDesc dn = d;
+            const int base = (int)maps.size();
+            for (int k = 0; k < cn.n_input_fns; k++) {
+                const syldet_fn_t &f = cn.input_fns[k];
+                dn.in_fns[k].kind = f.kind;
+                dn.in_fns[k].y = f.y;
+                if (f.kind >= SYLDET_FN_MAPMINMAX) {
+                    dn.in_fns[k].xoff = push(f.x_offsets, I) - base;
+                    dn.in_fns[k].gain = push(f.gains, I) - base;
+                }
             }
+            for (int k = 0; k < cn.n_output_fns; k++) {
+                const syldet_fn_t &f = cn.output_fns[k];
+                dn.out_fns[k].kind = f.kind;
+                dn.out_fns[k].y = f.y;
+                dn.out_fns[k].xoff = push(f.x_offsets, O) - base;
+                dn.out_fns[k].gain = push(f.gains, O) - base;
+            }
+            t->maps_per = (int)maps.size() - base;
+            t->descs.push_back(dn);
         }
-        for (int k = 0; k < c.n_output_fns; k++) {
-            const syldet_fn_t &f = c.output_fns[k];
-            d.out_fns[k].kind = f.kind;
-            d.out_fns[k].y = f.y;
-            d.out_fns[k].xoff = push(f.x_offsets, O);
-            d.out_fns[k].gain = push(f.gains, O);
+        t->row_net.assign((size_t)b.channels, 0);
+        if (N > 1 && b.channel_net) t->row_net.assign(b.channel_net, b.channel_net + b.channels);
+        t->net_rows.assign((size_t)N, 0);
+        for (int32_t n : t->row_net) t->net_rows[(size_t)n]++;
+        net_row_begin.assign((size_t)N + 1, 0);
+        for (int n = 0; n < N; n++) net_row_begin[(size_t)n + 1] = net_row_begin[(size_t)n] + t->net_rows[(size_t)n];
+        sorted_rows.assign((size_t)b.channels, 0);
+        {
+            std::vector<int32_t> at(net_row_begin.begin(), net_row_begin.end() - 1);
+            for (int32_t row = 0; row < b.channels; row++) sorted_rows[(size_t)at[(size_t)t->row_net[(size_t)row]]++] = row;
         }
         t->begin.assign((size_t)D + 1, 0);
         if (r) {
@@ -200,38 +245,90 @@ int syldet_trainer_create(const syldet_t *h, const syldet_recordings_t *r, sylde
     }
     t->h = const_cast<syldet_t *>(h);
     t->packed = r != nullptr;
+    t->multi = multi;
+    t->N = N;
     t->D = D;
-    t->P = sd::train_param_count(I, H, O);
+    t->P = P;
     t->row_evals = row_evals;
     t->row_frames = r ? std::max<int64_t>(0, sd::count_frames(b.geom, b.window_length, row_samples)) : 0;
     if (r && row_evals > 0 && t->row_frames < row_evals + d.T - 1) return fail(SYLDET_ERR_INVALID_ARGUMENT, "the packed rows hold fewer frames than their evaluations read");
 
     const size_t n_maps = up16(maps.size() * sizeof(float)), n_dets = up16(dets.size() * sizeof(sd::TrainDetDev)),
-                 n_rows = up16(row_begin.size() * sizeof(int32_t));
+                 n_rows = up16(row_begin.size() * sizeof(int32_t)), n_descs = multi ? up16((size_t)N * sizeof(sd::TrainDesc)) : 0,
+                 n_sorted = multi ? up16(sorted_rows.size() * sizeof(int32_t)) : 0, n_begin = multi ? up16(net_row_begin.size() * sizeof(int32_t)) : 0;
     SYLDET_HIP(hipSetDevice(b.device));
     SYLDET_HIP(sd::train_prepare(d));
-    if (int st = t->d_fixed.reserve(n_maps + n_dets + n_rows + 16)) return st;
-    if (int st = t->d_part.reserve((size_t)d.max_groups * ((size_t)t->P + 2) * sizeof(double))) return st;
-    if (int st = t->d_opt.reserve(16 + 3 * (size_t)t->P * sizeof(float))) return st;
+    if (multi) SYLDET_HIP(sd::train_prepare_multi(d));
+    if (int st = t->d_fixed.reserve(n_maps + n_dets + n_rows + n_descs + n_sorted + n_begin + 16)) return st;
+    if (int st = t->d_part.reserve((size_t)N * (size_t)d.max_groups * ((size_t)P + 2) * sizeof(double))) return st;
+    if (int st = t->d_opt.reserve(16 * (size_t)N + 3 * (size_t)N * (size_t)P * sizeof(float))) return st;
     char *base = (char *)t->d_fixed.ptr;
     if (!maps.empty()) SYLDET_HIP(hipMemcpy(base, maps.data(), maps.size() * sizeof(float), hipMemcpyHostToDevice));
     if (!dets.empty()) SYLDET_HIP(hipMemcpy(base + n_maps, dets.data(), dets.size() * sizeof(sd::TrainDetDev), hipMemcpyHostToDevice));
     if (!row_begin.empty()) SYLDET_HIP(hipMemcpy(base + n_maps + n_dets, row_begin.data(), row_begin.size() * sizeof(int32_t), hipMemcpyHostToDevice));
-    d.maps = (const float *)base;
+    for (int n = 0; n < N; n++) t->descs[(size_t)n].maps = (const float *)base + (size_t)n * (size_t)t->maps_per;
+    d = t->descs[0];
     t->d_dets = r ? (const sd::TrainDetDev *)(base + n_maps) : nullptr;
     t->d_row_begin = r ? (const int32_t *)(base + n_maps + n_dets) : nullptr;
+    if (multi) {
+        t->descs_at = n_maps + n_dets + n_rows;
+        char *tables = base + t->descs_at;
+        SYLDET_HIP(hipMemcpy(tables, t->descs.data(), (size_t)N * sizeof(sd::TrainDesc), hipMemcpyHostToDevice));
+        if (!sorted_rows.empty()) SYLDET_HIP(hipMemcpy(tables + n_descs, sorted_rows.data(), sorted_rows.size() * sizeof(int32_t), hipMemcpyHostToDevice));
+        SYLDET_HIP(hipMemcpy(tables + n_descs + n_sorted, net_row_begin.data(), net_row_begin.size() * sizeof(int32_t), hipMemcpyHostToDevice));
+        t->mu.descs = (const sd::TrainDesc *)tables;
+        t->mu.rows = (const int32_t *)(tables + n_descs);
+        t->mu.net_row_begin = (const int32_t *)(tables + n_descs + n_sorted);
+        t->mu.n_nets = N;
+        t->mu.max_rows = *std::max_element(t->net_rows.begin(), t->net_rows.end());
+    }
     t->desc = d;
     t->map_at = sd::train_first_map(d);
     if (t->map_at >= 0) {
         try {
-            t->map.assign(maps.begin() + d.in_fns[t->map_at].xoff, maps.begin() + d.in_fns[t->map_at].xoff + I);
-            t->map.insert(t->map.end(), maps.begin() + d.in_fns[t->map_at].gain, maps.begin() + d.in_fns[t->map_at].gain + I);
+            for (int n = 0; n < N; n++) {
+                const float *own = maps.data() + (size_t)n * (size_t)t->maps_per;
+                t->map.insert(t->map.end(), own + d.in_fns[t->map_at].xoff, own + d.in_fns[t->map_at].xoff + I);
+                t->map.insert(t->map.end(), own + d.in_fns[t->map_at].gain, own + d.in_fns[t->map_at].gain + I);
+            }
         } catch (const std::bad_alloc &) {
             return fail(SYLDET_ERR_OUT_OF_MEMORY, "out of memory");
         }
     }
     *out = t.release();
     return SYLDET_OK;
+}
+
+int syldet_trainer_create(const syldet_t *h, const syldet_recordings_t *r, syldet_trainer_t **out)
+{
+    if (!out) return fail(SYLDET_ERR_INVALID_ARGUMENT, "NULL argument");
+    *out = nullptr;
+    if (!h) return fail(SYLDET_ERR_INVALID_ARGUMENT, "NULL handle");
+    if (h->n_nets != 1 || !h->classes.empty() || h->root)
+        return fail(SYLDET_ERR_UNSUPPORTED, "the trainer takes a plain bank: one network, not a multi-network or mixed one");
+    try {
+        return trainer_create(h, r, std::vector<const syldet_config_t *>{&h->cfg.view}, false, out);
+    } catch (const std::bad_alloc &) {
+        return fail(SYLDET_ERR_OUT_OF_MEMORY, "out of memory");
+    }
+}
+
+int syldet_trainer_create_multi(const syldet_t *h, const syldet_recordings_t *r, syldet_trainer_t **out)
+{
+    if (!out) return fail(SYLDET_ERR_INVALID_ARGUMENT, "NULL argument");
+    *out = nullptr;
+    if (!h) return fail(SYLDET_ERR_INVALID_ARGUMENT, "NULL handle");
+    if (!h->classes.empty() || h->root) return fail(SYLDET_ERR_UNSUPPORTED, "the multi trainer takes a plain or a multi-network bank, not a mixed one");
+    try {
+        std::vector<const syldet_config_t *> cfgs;
+        if (h->n_nets == 1) cfgs.push_back(&h->cfg.view);
+        else if ((int)h->net_cfgs.size() == h->n_nets)
+            for (const auto &own : h->net_cfgs) cfgs.push_back(&own->view);
+        else return fail(SYLDET_ERR_UNSUPPORTED, "the bank does not keep its networks' configurations");
+        return trainer_create(h, r, cfgs, true, out);
+    } catch (const std::bad_alloc &) {
+        return fail(SYLDET_ERR_OUT_OF_MEMORY, "out of memory");
+    }
 }
 
 int syldet_trainer_destroy(syldet_trainer_t *t)
@@ -253,6 +350,23 @@ int syldet_trainer_shape(const syldet_trainer_t *t, int32_t *n_detectors, int64_
     if (n_params) *n_params = t->P;
     if (n_out) *n_out = t->desc.O;
     if (tile) *tile = t->desc.tile;
+    return SYLDET_OK;
+}
+
+int syldet_trainer_networks(const syldet_trainer_t *t, int32_t *n_networks, int32_t *row_network)
+{
+    if (!t) return fail(SYLDET_ERR_INVALID_ARGUMENT, "NULL argument");
+    if (n_networks) *n_networks = t->N;
+    if (row_network) std::copy(t->row_net.begin(), t->row_net.end(), row_network);
+    return SYLDET_OK;
+}
+
+int syldet_trainer_groups(const syldet_trainer_t *t, int64_t n_evals, int32_t *groups)
+{
+    if (!t || !groups) return fail(SYLDET_ERR_INVALID_ARGUMENT, "NULL argument");
+    if (n_evals < 0) return fail(SYLDET_ERR_INVALID_ARGUMENT, "n_evals is negative");
+    if (int st = tiles_arg(t, n_evals)) return st;
+    for (int n = 0; n < t->N; n++) groups[n] = sd::train_groups(t->desc, t->net_rows[(size_t)n], n_evals);
     return SYLDET_OK;
 }
 
@@ -365,10 +479,14 @@ int syldet_train_gradient_device(syldet_trainer_t *t, const float *d_columns, in
     t->h->prof_begin();
     {
         KernelTimer timer(t->h, stream, "train_gradient_kernel");
-        SYLDET_HIP(sd::launch_train_gradient(d, d_columns, row_stride, rows, d_params, d_targets, d_weights, n_evals, (double *)t->d_part.ptr, stream));
+        if (t->multi)
+            SYLDET_HIP(sd::launch_train_gradient_multi(d, t->mu, d_columns, row_stride, d_params, d_targets, d_weights, n_evals, (double *)t->d_part.ptr, stream));
+        else
+            SYLDET_HIP(sd::launch_train_gradient(d, d_columns, row_stride, rows, d_params, d_targets, d_weights, n_evals, (double *)t->d_part.ptr, stream));
     }
     KernelTimer timer(t->h, stream, "train_combine_kernel");
-    SYLDET_HIP(sd::launch_train_combine(d, groups, (const double *)t->d_part.ptr, d_loss, d_gradient, stream));
+    if (t->multi) SYLDET_HIP(sd::launch_train_combine_multi(d, t->mu, n_evals, (const double *)t->d_part.ptr, d_loss, d_gradient, stream));
+    else SYLDET_HIP(sd::launch_train_combine(d, groups, (const double *)t->d_part.ptr, d_loss, d_gradient, stream));
     return SYLDET_OK;
 }
 
@@ -390,41 +508,64 @@ int syldet_train_input_range_device(syldet_trainer_t *t, const float *d_columns,
     t->h->prof_begin();
     {
         KernelTimer timer(t->h, stream, "train_range_kernel");
-        SYLDET_HIP(sd::launch_train_range(d, t->map_at, d_columns, row_stride, rows, d_weights, n_evals, (double *)t->d_part.ptr, stream));
+        if (t->multi) SYLDET_HIP(sd::launch_train_range_multi(d, t->mu, t->map_at, d_columns, row_stride, d_weights, n_evals, (double *)t->d_part.ptr, stream));
+        else SYLDET_HIP(sd::launch_train_range(d, t->map_at, d_columns, row_stride, rows, d_weights, n_evals, (double *)t->d_part.ptr, stream));
     }
     KernelTimer timer(t->h, stream, "train_range_combine_kernel");
-    SYLDET_HIP(sd::launch_train_range_combine(d, groups, (const double *)t->d_part.ptr, d_range, d_count, stream));
+    if (t->multi) SYLDET_HIP(sd::launch_train_range_combine_multi(d, t->mu, n_evals, (const double *)t->d_part.ptr, d_range, d_count, stream));
+    else SYLDET_HIP(sd::launch_train_range_combine(d, groups, (const double *)t->d_part.ptr, d_range, d_count, stream));
     return SYLDET_OK;
 }
 
-int syldet_trainer_set_input_map(syldet_trainer_t *t, const float *x_offsets, const float *gains, float y)
+int syldet_trainer_set_input_map_of(syldet_trainer_t *t, int32_t net, const float *x_offsets, const float *gains, float y)
 {
     if (!t) return fail(SYLDET_ERR_INVALID_ARGUMENT, "NULL handle");
+    if (net < 0 || net >= t->N) return fail(SYLDET_ERR_INVALID_ARGUMENT, "net " + std::to_string(net) + " is outside [0, " + std::to_string(t->N) + ")");
     if (!x_offsets || !gains) return fail(SYLDET_ERR_INVALID_ARGUMENT, "NULL argument");
     if (t->map_at < 0) return fail(SYLDET_ERR_UNSUPPORTED, "the configuration has no mapminmax input function");
     if (std::isnan(y)) return fail(SYLDET_ERR_INVALID_ARGUMENT, "y is NaN");
     const int I = t->desc.I;
     const sd::DevFn &fn = t->desc.in_fns[t->map_at];
-    // behind the last call, which may still read the old map: one blocking copy (x_offsets and gains lie side by side)
+    float *own = t->map.data() + 2 * (size_t)I * (size_t)net;
+    // behind the last call, which may still read the old map: one blocking copy (x_offsets and gains lie side by side), and in the
+    // multi form one more of the network's y in its TrainDesc
     SYLDET_HIP(hipSetDevice(t->bank.device));
     SYLDET_HIP(hipStreamSynchronize(t->last));
-    std::copy(x_offsets, x_offsets + I, t->map.begin());
-    std::copy(gains, gains + I, t->map.begin() + I);
-    SYLDET_HIP(hipMemcpy((char *)t->d_fixed.ptr + (size_t)fn.xoff * sizeof(float), t->map.data(), 2 * (size_t)I * sizeof(float), hipMemcpyHostToDevice));
-    t->desc.in_fns[t->map_at].y = y;
+    std::copy(x_offsets, x_offsets + I, own);
+    std::copy(gains, gains + I, own + I);
+    SYLDET_HIP(hipMemcpy((char *)t->d_fixed.ptr + ((size_t)net * (size_t)t->maps_per + (size_t)fn.xoff) * sizeof(float), own, 2 * (size_t)I * sizeof(float),
+                         hipMemcpyHostToDevice));
+    t->descs[(size_t)net].in_fns[t->map_at].y = y;
+    if (net == 0) t->desc.in_fns[t->map_at].y = y;
+    if (t->multi) {
+        const size_t at = t->descs_at + (size_t)net * sizeof(sd::TrainDesc) + offsetof(sd::TrainDesc, in_fns) + (size_t)t->map_at * sizeof(sd::DevFn) + offsetof(sd::DevFn, y);
+        SYLDET_HIP(hipMemcpy((char *)t->d_fixed.ptr + at, &y, sizeof(float), hipMemcpyHostToDevice));
+    }
     return SYLDET_OK;
+}
+
+int syldet_trainer_input_map_of(const syldet_trainer_t *t, int32_t net, int32_t *index, float *x_offsets, float *gains, float *y)
+{
+    if (!t) return fail(SYLDET_ERR_INVALID_ARGUMENT, "NULL handle");
+    if (net < 0 || net >= t->N) return fail(SYLDET_ERR_INVALID_ARGUMENT, "net " + std::to_string(net) + " is outside [0, " + std::to_string(t->N) + ")");
+    if (t->map_at < 0) return fail(SYLDET_ERR_UNSUPPORTED, "the configuration has no mapminmax input function");
+    const int I = t->desc.I;
+    const float *own = t->map.data() + 2 * (size_t)I * (size_t)net;
+    if (index) *index = t->map_at;
+    if (x_offsets) std::copy(own, own + I, x_offsets);
+    if (gains) std::copy(own + I, own + 2 * I, gains);
+    if (y) *y = t->descs[(size_t)net].in_fns[t->map_at].y;
+    return SYLDET_OK;
+}
+
+int syldet_trainer_set_input_map(syldet_trainer_t *t, const float *x_offsets, const float *gains, float y)
+{
+    return syldet_trainer_set_input_map_of(t, 0, x_offsets, gains, y);
 }
 
 int syldet_trainer_input_map(const syldet_trainer_t *t, int32_t *index, float *x_offsets, float *gains, float *y)
 {
-    if (!t) return fail(SYLDET_ERR_INVALID_ARGUMENT, "NULL handle");
-    if (t->map_at < 0) return fail(SYLDET_ERR_UNSUPPORTED, "the configuration has no mapminmax input function");
-    const int I = t->desc.I;
-    if (index) *index = t->map_at;
-    if (x_offsets) std::copy(t->map.begin(), t->map.begin() + I, x_offsets);
-    if (gains) std::copy(t->map.begin() + I, t->map.end(), gains);
-    if (y) *y = t->desc.in_fns[t->map_at].y;
-    return SYLDET_OK;
+    return syldet_trainer_input_map_of(t, 0, index, x_offsets, gains, y);
 }
 
 int syldet_train_adam_device(syldet_trainer_t *t, float *d_params, const double *d_loss, const float *d_gradient, int64_t step, double lr, double beta1,
@@ -436,10 +577,13 @@ int syldet_train_adam_device(syldet_trainer_t *t, float *d_params, const double 
     hipStream_t stream = (hipStream_t)hip_stream;
     SYLDET_HIP(hipSetDevice(t->bank.device));
     t->last = stream;
-    float *m = (float *)((char *)t->d_opt.ptr + 16) + t->P, *v = m + t->P;
+    const size_t NP = (size_t)t->N * (size_t)t->P;
+    float *m = (float *)((char *)t->d_opt.ptr + 16 * (size_t)t->N) + NP, *v = m + NP;
     t->h->prof_begin();
     KernelTimer timer(t->h, stream, "train_adam_kernel");
-    SYLDET_HIP(sd::launch_train_adam(sd::train_adam_consts(step, lr, beta1, beta2, eps), t->P, d_loss, d_gradient, m, v, d_params, d_mean_loss, stream));
+    if (t->multi)
+        SYLDET_HIP(sd::launch_train_adam_multi(sd::train_adam_consts(step, lr, beta1, beta2, eps), t->P, t->N, d_loss, d_gradient, m, v, d_params, d_mean_loss, stream));
+    else SYLDET_HIP(sd::launch_train_adam(sd::train_adam_consts(step, lr, beta1, beta2, eps), t->P, d_loss, d_gradient, m, v, d_params, d_mean_loss, stream));
     return SYLDET_OK;
 }
 
@@ -462,19 +606,27 @@ int syldet_train_fit_device(syldet_trainer_t *t, const float *d_columns, int64_t
     t->last = stream;
     const int groups = sd::train_groups(d, rows, n_evals);
     double *loss = (double *)t->d_opt.ptr;
-    float *grad = (float *)((char *)t->d_opt.ptr + 16), *m = grad + t->P, *v = m + t->P;
+    const size_t NP = (size_t)t->N * (size_t)t->P;
+    float *grad = (float *)((char *)t->d_opt.ptr + 16 * (size_t)t->N), *m = grad + NP, *v = m + NP;
     for (int64_t k = 1; k <= steps; k++) {
         t->h->prof_begin();                                // (a step is a call of the profile: three kernels)
         {
             KernelTimer timer(t->h, stream, "train_gradient_kernel");
-            SYLDET_HIP(sd::launch_train_gradient(d, d_columns, row_stride, rows, d_params, d_targets, d_weights, n_evals, (double *)t->d_part.ptr, stream));
+            if (t->multi)
+                SYLDET_HIP(sd::launch_train_gradient_multi(d, t->mu, d_columns, row_stride, d_params, d_targets, d_weights, n_evals, (double *)t->d_part.ptr, stream));
+            else
+                SYLDET_HIP(sd::launch_train_gradient(d, d_columns, row_stride, rows, d_params, d_targets, d_weights, n_evals, (double *)t->d_part.ptr, stream));
         }
         {
             KernelTimer timer(t->h, stream, "train_combine_kernel");
-            SYLDET_HIP(sd::launch_train_combine(d, groups, (const double *)t->d_part.ptr, loss, grad, stream));
+            if (t->multi) SYLDET_HIP(sd::launch_train_combine_multi(d, t->mu, n_evals, (const double *)t->d_part.ptr, loss, grad, stream));
+            else SYLDET_HIP(sd::launch_train_combine(d, groups, (const double *)t->d_part.ptr, loss, grad, stream));
         }
         KernelTimer timer(t->h, stream, "train_adam_kernel");
-        SYLDET_HIP(sd::launch_train_adam(sd::train_adam_consts(k, lr, beta1, beta2, eps), t->P, loss, grad, m, v, d_params, d_history + (k - 1), stream));
+        if (t->multi)
+            SYLDET_HIP(sd::launch_train_adam_multi(sd::train_adam_consts(k, lr, beta1, beta2, eps), t->P, t->N, loss, grad, m, v, d_params, d_history + (k - 1) * t->N,
+                                                   stream));
+        else SYLDET_HIP(sd::launch_train_adam(sd::train_adam_consts(k, lr, beta1, beta2, eps), t->P, loss, grad, m, v, d_params, d_history + (k - 1), stream));
     }
     return SYLDET_OK;
 }

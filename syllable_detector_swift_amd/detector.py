@@ -951,6 +951,11 @@ class SyllableDetector:
         network, up to 16 hidden units and 4 outputs."""
         return Trainer(self)
 
+    def multiTrainer(self) -> "MultiTrainer":
+        """A MultiTrainer over this bank's channels (syldet_trainer_create_multi): one trainer for the N networks of a multi bank
+        (or of a plain bank, N = 1), each trained on its own rows with the bits a plain Trainer would give."""
+        return MultiTrainer(self)
+
     # ---- template matching: a syllable's occurrences in the columns ------------------------
     def matcher(self, template, anchor: Optional[int] = None) -> "Matcher":
         """A Matcher over this bank's channels (syldet_matcher_create): scores(cols) is the cosine between `template`
@@ -1488,6 +1493,11 @@ class Recordings:
         are spectrogram(rows)."""
         return Trainer(self.detector, recordings=self)
 
+    def multiTrainer(self) -> "MultiTrainer":
+        """A MultiTrainer whose detectors are these recordings: a recording trains the network of the row it was planned onto
+        (SyllableDetector.multiTrainer, trainer)."""
+        return MultiTrainer(self.detector, recordings=self)
+
     def matcher(self, template, anchor: Optional[int] = None) -> "Matcher":
         """A Matcher whose detectors are these recordings: a window never reaches beyond its recording, matches are never
         suppressed across two recordings of a row, and events count from each recording's own start (SyllableDetector.matcher).
@@ -1952,22 +1962,9 @@ def _train_label_args(labels, labelOutputs):
     return flat, begin, np.ascontiguousarray(np.concatenate(outs) if outs else np.zeros(0, np.int32), dtype=np.int32)
 
 
-class Trainer:
-    """Training (syldet_trainer_*, include/syldet.h "training"): loss and gradient of a two-layer network's parameters over
-    weighted, labelled evaluations, straight from the columns.  A detector is a channel of the bank, or (made by
-    Recordings.trainer) a recording.  shape = (detectors, parameters, outputs); the parameters are one flat float32 vector,
-    layer0.weights [H][I], layer0.biases [H], layer1.weights [O][H], layer1.biases [O]; everything else of the network is the
-    bank's configuration's.  The optimiser is torch's.  The detector (and the Recordings) must outlive it."""
-
-    def __init__(self, detector: SyllableDetector, recordings: Optional[Recordings] = None):
-        self.detector = detector
-        self.recordings = recordings
-        self._h = _abi.Handle()
-        check(_abi.lib.syldet_trainer_create(detector._h, None if recordings is None else recordings._h, C.byref(self._h)))
-        d, p, o, tile = C.c_int32(), C.c_int64(), C.c_int32(), C.c_int32()
-        check(_abi.lib.syldet_trainer_shape(self._h, C.byref(d), C.byref(p), C.byref(o), C.byref(tile)))
-        self.shape = (d.value, p.value, o.value)
-        self.count, self.paramCount, self.outputs, self.tile = d.value, p.value, o.value, tile.value
+class _TrainerHandle:
+    """What Trainer and MultiTrainer share: the handle's life, the targets and the checks of the device arrays.  A subclass sets
+    detector, recordings, _h, count, paramCount, outputs and _paramsShape."""
 
     def close(self):
         if getattr(self, "_h", None):
@@ -1986,30 +1983,10 @@ class Trainer:
     def __exit__(self, *exc):
         self.close()
 
-    # ---- parameters <-> configuration ----
-    def params(self, config: Optional[SyllableDetectorConfig] = None):
-        """The flat float32 parameter vector of a configuration's two layers (default: the bank's), on the detector's device."""
-        torch = _torch()
-        layers = (config or self.detector.config).net.layers
-        flat = np.concatenate([np.asarray(a, np.float32).reshape(-1) for L in layers for a in (L.weights, L.biases)])
-        if len(layers) != 2 or flat.size != self.paramCount:
-            raise ValueError("the configuration's layers do not have the trainer's %d parameters" % self.paramCount)
-        return torch.from_numpy(flat).to("cuda:%d" % self.detector.device)
-
-    def configWith(self, params) -> SyllableDetectorConfig:
-        """A deep copy of the bank's configuration with the two layers' weights and biases replaced by `params`."""
-        import copy
-        p = (params.detach().cpu().numpy() if hasattr(params, "detach") else np.asarray(params)).astype(np.float32).reshape(-1)
-        if p.size != self.paramCount:
-            raise ValueError("params must hold %d values" % self.paramCount)
-        cfg = copy.deepcopy(self.detector.config)
-        at = 0
-        for L in cfg.net.layers:
-            L.weights = p[at:at + L.outputs * L.inputs].reshape(L.outputs, L.inputs).copy()
-            at += L.outputs * L.inputs
-            L.biases = p[at:at + L.outputs].copy()
-            at += L.outputs
-        return cfg
+    def _shape(self):
+        d, p, o, tile = C.c_int32(), C.c_int64(), C.c_int32(), C.c_int32()
+        check(_abi.lib.syldet_trainer_shape(self._h, C.byref(d), C.byref(p), C.byref(o), C.byref(tile)))
+        self.count, self.paramCount, self.outputs, self.tile = d.value, p.value, o.value, tile.value
 
     # ---- targets ----
     def _n_evals(self, n_evals):
@@ -2040,7 +2017,7 @@ class Trainer:
                                                    float(weightNegative), E, t.data_ptr(), w.data_ptr(), det._stream_ptr(stream)))
         return t, w
 
-    # ---- loss and gradient ----
+    # ---- the device arrays of a gradient or a fit ----
     def _check(self, cols, params, targets, weights):
         torch = _torch()
         det = self.detector
@@ -2051,13 +2028,56 @@ class Trainer:
 
         if not (ok(cols, 3) and cols.shape[0] == det.channels and cols.shape[2] == bins):
             raise ValueError("cols must be a contiguous float32 CUDA tensor [channels, n_frames, %d] on the detector's device" % bins)
-        if not (ok(params, 1) and params.numel() == self.paramCount):
-            raise ValueError("params must be a contiguous float32 CUDA tensor of %d values" % self.paramCount)
+        if not (ok(params, len(self._paramsShape)) and tuple(params.shape) == self._paramsShape):
+            raise ValueError("params must be a contiguous float32 CUDA tensor %s" % (list(self._paramsShape),))
         if not (ok(weights, 2) and weights.shape[0] == det.channels):
             raise ValueError("weights must be a contiguous float32 CUDA tensor [channels, n_evals]")
         if not (ok(targets, 3) and tuple(targets.shape) == (det.channels, weights.shape[1], self.outputs)):
             raise ValueError("targets must be a contiguous float32 CUDA tensor [channels, n_evals, %d]" % self.outputs)
 
+
+class Trainer(_TrainerHandle):
+    """Training (syldet_trainer_*, include/syldet.h "training"): loss and gradient of a two-layer network's parameters over
+    weighted, labelled evaluations, straight from the columns.  A detector is a channel of the bank, or (made by
+    Recordings.trainer) a recording.  shape = (detectors, parameters, outputs); the parameters are one flat float32 vector,
+    layer0.weights [H][I], layer0.biases [H], layer1.weights [O][H], layer1.biases [O]; everything else of the network is the
+    bank's configuration's.  The optimiser is torch's.  The detector (and the Recordings) must outlive it."""
+
+    def __init__(self, detector: SyllableDetector, recordings: Optional[Recordings] = None):
+        self.detector = detector
+        self.recordings = recordings
+        self._h = _abi.Handle()
+        check(_abi.lib.syldet_trainer_create(detector._h, None if recordings is None else recordings._h, C.byref(self._h)))
+        self._shape()
+        self.shape = (self.count, self.paramCount, self.outputs)
+        self._paramsShape = (self.paramCount,)
+
+    # ---- parameters <-> configuration ----
+    def params(self, config: Optional[SyllableDetectorConfig] = None):
+        """The flat float32 parameter vector of a configuration's two layers (default: the bank's), on the detector's device."""
+        torch = _torch()
+        layers = (config or self.detector.config).net.layers
+        flat = np.concatenate([np.asarray(a, np.float32).reshape(-1) for L in layers for a in (L.weights, L.biases)])
+        if len(layers) != 2 or flat.size != self.paramCount:
+            raise ValueError("the configuration's layers do not have the trainer's %d parameters" % self.paramCount)
+        return torch.from_numpy(flat).to("cuda:%d" % self.detector.device)
+
+    def configWith(self, params) -> SyllableDetectorConfig:
+        """A deep copy of the bank's configuration with the two layers' weights and biases replaced by `params`."""
+        import copy
+        p = (params.detach().cpu().numpy() if hasattr(params, "detach") else np.asarray(params)).astype(np.float32).reshape(-1)
+        if p.size != self.paramCount:
+            raise ValueError("params must hold %d values" % self.paramCount)
+        cfg = copy.deepcopy(self.detector.config)
+        at = 0
+        for L in cfg.net.layers:
+            L.weights = p[at:at + L.outputs * L.inputs].reshape(L.outputs, L.inputs).copy()
+            at += L.outputs * L.inputs
+            L.biases = p[at:at + L.outputs].copy()
+            at += L.outputs
+        return cfg
+
+    # ---- loss and gradient ----
     def gradient(self, cols, params, targets, weights, out=None, stream=None):
         """cols [C, n_frames, bins] as spectrogram() wrote them, params [P], targets and weights as targets() made them (or any
         others of those shapes) -> (loss, weightSum, grad): two 0-dim float64 tensors -- the sum over the selected evaluations
@@ -2211,6 +2231,152 @@ class Trainer:
         fns[at].gains = np.where(rng > 0, np.float32(2.0) / np.where(rng > 0, rng, 1), np.float32(1.0)).astype(np.float32)
         fns[at].y = -1.0
         return cfg
+
+
+class MultiTrainer(_TrainerHandle):
+    """A network per channel (syldet_trainer_create_multi, include/syldet.h "training a network per channel"): ONE trainer for the
+    N networks of a SyllableDetector.multi bank (or of a plain bank, N = 1).  Row r trains network rowNetwork[r] -- with
+    Recordings, a recording the network of the row it was planned onto -- and network n's loss, gradient, range, Adam step and
+    fit are bit for bit a plain Trainer's on a plain bank of that network over those rows alone.  shape = (detectors, networks,
+    parameters, outputs); params, gradients and moments are [N, P].  The detector (and the Recordings) must outlive it."""
+
+    def __init__(self, detector: SyllableDetector, recordings: Optional[Recordings] = None):
+        self.detector = detector
+        self.recordings = recordings
+        self._h = _abi.Handle()
+        check(_abi.lib.syldet_trainer_create_multi(detector._h, None if recordings is None else recordings._h, C.byref(self._h)))
+        self._shape()
+        n = C.c_int32()
+        rows = np.zeros(detector.channels, np.int32)
+        check(_abi.lib.syldet_trainer_networks(self._h, C.byref(n), rows.ctypes.data_as(_abi.c_int32_p)))
+        self.networks, self.rowNetwork = int(n.value), rows
+        self.shape = (self.count, self.networks, self.paramCount, self.outputs)
+        self._paramsShape = (self.networks, self.paramCount)
+        self.configs = list(getattr(detector, "configs", None) or [detector.config])
+        if len(self.configs) != self.networks:
+            raise ValueError("the detector holds %d configurations for %d networks" % (len(self.configs), self.networks))
+
+    def groups(self, n_evals: int) -> np.ndarray:
+        """syldet_trainer_groups: the workgroups G_n each network gets for n_evals evaluations a row, int32 [N] (host only)."""
+        g = np.zeros(self.networks, np.int32)
+        check(_abi.lib.syldet_trainer_groups(self._h, int(n_evals), g.ctypes.data_as(_abi.c_int32_p)))
+        return g
+
+    # ---- parameters <-> configurations ----
+    def params(self, configs=None):
+        """The networks' flat float32 parameter vectors [N, P] (default: the bank's own configurations), on the detector's device."""
+        torch = _torch()
+        configs = list(configs) if configs is not None else self.configs
+        if len(configs) != self.networks:
+            raise ValueError("one configuration per network (%d given, %d networks)" % (len(configs), self.networks))
+        flat = []
+        for cfg in configs:
+            flat.append(np.concatenate([np.asarray(a, np.float32).reshape(-1) for L in cfg.net.layers for a in (L.weights, L.biases)]))
+            if len(cfg.net.layers) != 2 or flat[-1].size != self.paramCount:
+                raise ValueError("a configuration's layers do not have the trainer's %d parameters" % self.paramCount)
+        return torch.from_numpy(np.stack(flat)).to("cuda:%d" % self.detector.device)
+
+    def configsWith(self, params) -> List[SyllableDetectorConfig]:
+        """One syldet_train_config_with per network: network n's configuration with its two layers replaced by params[n] and,
+        where it has a mapminmax input function, that function's parameters by the trainer's own (inputMap(n))."""
+        p = np.ascontiguousarray((params.detach().cpu().numpy() if hasattr(params, "detach") else np.asarray(params)), dtype=np.float32)
+        if p.shape != (self.networks, self.paramCount):
+            raise ValueError("params must be [%d, %d]" % (self.networks, self.paramCount))
+        has_map = any(f.function == "mapminmax" for f in self.configs[0].net.inputProcessing)
+        out = []
+        fp = lambda a: a.ctypes.data_as(_abi.c_float_p)
+        for n, cfg in enumerate(self.configs):
+            c, keep = cfg.to_abi()
+            made = _abi.Config_p()
+            if has_map:
+                xo, g, y, _ = self.inputMap(n)
+                check(_abi.lib.syldet_train_config_with(C.byref(c), fp(p[n]), self.paramCount, fp(xo), fp(g), float(y), C.byref(made)))
+            else:
+                check(_abi.lib.syldet_train_config_with(C.byref(c), fp(p[n]), self.paramCount, None, None, 0.0, C.byref(made)))
+            del keep
+            try:
+                out.append(SyllableDetectorConfig._from_abi(made.contents))
+            finally:
+                _abi.lib.syldet_config_free(made)
+        return out
+
+    # ---- loss and gradient ----
+    def gradient(self, cols, params, targets, weights, out=None, stream=None):
+        """Trainer.gradient for every network at once: params [N, P] -> (loss [N], weightSum [N]) float64 and grad [N, P] float32 on
+        the device, network n's over its own rows alone.  out: a (float64 [N, 2], float32 [N, P]) pair.  Two launches."""
+        torch = _torch()
+        self._check(cols, params, targets, weights)
+        N, P = self.networks, self.paramCount
+        if out is None:
+            out = (torch.empty((N, 2), dtype=torch.float64, device=cols.device), torch.empty((N, P), dtype=torch.float32, device=cols.device))
+        loss, grad = out
+        if not (loss.is_cuda and loss.dtype == torch.float64 and tuple(loss.shape) == (N, 2) and loss.is_contiguous() and grad.is_cuda
+                and grad.dtype == torch.float32 and tuple(grad.shape) == (N, P) and grad.is_contiguous()):
+            raise ValueError("out must be a (float64 [%d, 2], float32 [%d, %d]) pair of contiguous CUDA tensors" % (N, N, P))
+        check(_abi.lib.syldet_train_gradient_device(self._h, cols.data_ptr(), int(cols.shape[1]), 0, params.data_ptr(), targets.data_ptr(),
+                                                    weights.data_ptr(), int(weights.shape[1]), loss.data_ptr(), grad.data_ptr(),
+                                                    self.detector._stream_ptr(stream)))
+        return loss[:, 0], loss[:, 1], grad
+
+    def inputRange(self, cols, weights, stream=None):
+        """Trainer.inputRange per network -> (range [N, 2, I] float32, count [N] int64), on the device.  Two launches."""
+        torch = _torch()
+        det = self.detector
+        I = det.geometry.inputs
+        ok = lambda x, dims: x.is_cuda and x.dtype == torch.float32 and x.dim() == dims and x.is_contiguous() and x.device.index == det.device
+        if not (ok(cols, 3) and cols.shape[0] == det.channels and cols.shape[2] == det.geometry.bins):
+            raise ValueError("cols must be a contiguous float32 CUDA tensor [channels, n_frames, %d] on the detector's device" % det.geometry.bins)
+        if not (ok(weights, 2) and weights.shape[0] == det.channels):
+            raise ValueError("weights must be a contiguous float32 CUDA tensor [channels, n_evals]")
+        rng = torch.empty((self.networks, 2, I), dtype=torch.float32, device=cols.device)
+        count = torch.empty(self.networks, dtype=torch.int64, device=cols.device)
+        check(_abi.lib.syldet_train_input_range_device(self._h, cols.data_ptr(), int(cols.shape[1]), 0, weights.data_ptr(), int(weights.shape[1]),
+                                                       rng.data_ptr(), count.data_ptr(), det._stream_ptr(stream)))
+        return rng, count
+
+    def setInputMap(self, net: int, xOffsets, gains, y: float = -1.0) -> None:
+        """syldet_trainer_set_input_map_of: Trainer.setInputMap for network `net`."""
+        I = self.detector.geometry.inputs
+        xo = np.ascontiguousarray(xOffsets, dtype=np.float32).reshape(-1)
+        g = np.ascontiguousarray(gains, dtype=np.float32).reshape(-1)
+        if xo.size != I or g.size != I:
+            raise ValueError("xOffsets and gains must hold %d values each" % I)
+        check(_abi.lib.syldet_trainer_set_input_map_of(self._h, int(net), xo.ctypes.data_as(_abi.c_float_p), g.ctypes.data_as(_abi.c_float_p), float(y)))
+
+    def inputMap(self, net: int = 0):
+        """syldet_trainer_input_map_of -> (xOffsets [I], gains [I], y, the function's index in the input chain) of network `net`"""
+        I = self.detector.geometry.inputs
+        xo, g = np.zeros(I, np.float32), np.zeros(I, np.float32)
+        y, at = C.c_float(), C.c_int32()
+        check(_abi.lib.syldet_trainer_input_map_of(self._h, int(net), C.byref(at), xo.ctypes.data_as(_abi.c_float_p), g.ctypes.data_as(_abi.c_float_p),
+                                                   C.byref(y)))
+        return xo, g, float(y.value), int(at.value)
+
+    def adamStep(self, params, loss, grad, step: int, lr: float = 0.01, beta1: float = 0.9, beta2: float = 0.999, eps: float = 1e-8, stream=None):
+        """syldet_train_adam_device on params [N, P] IN PLACE from loss (float64 [N, 2]) and grad [N, P] as gradient(out=...) left
+        them; 1 / Wsum is each network's own -> the mean losses, float64 [N].  One launch."""
+        torch = _torch()
+        N, P = self.networks, self.paramCount
+        ok = lambda x, dt, n: x.is_cuda and x.dtype == dt and x.numel() == n and x.is_contiguous() and x.device.index == self.detector.device
+        if not (ok(params, torch.float32, N * P) and ok(grad, torch.float32, N * P) and ok(loss, torch.float64, 2 * N)):
+            raise ValueError("params and grad must be contiguous float32 CUDA tensors [%d, %d], loss float64 [%d, 2]" % (N, P, N))
+        mean = torch.empty(N, dtype=torch.float64, device=params.device)
+        check(_abi.lib.syldet_train_adam_device(self._h, params.data_ptr(), loss.data_ptr(), grad.data_ptr(), int(step), float(lr), float(beta1), float(beta2),
+                                                float(eps), mean.data_ptr(), self.detector._stream_ptr(stream)))
+        return mean
+
+    def fitDevice(self, cols, targets, weights, params, steps: int, lr: float = 0.01, beta1: float = 0.9, beta2: float = 0.999, eps: float = 1e-8,
+                  stream=None):
+        """syldet_train_fit_device for every network at once: 3 x steps launches -> (params [N, P]: a copy of `params` after the
+        steps, history: float64 [steps, N] on the device, each network's mean loss in front of every step)."""
+        torch = _torch()
+        self._check(cols, params, targets, weights)
+        p = params.detach().clone()
+        history = torch.empty((max(int(steps), 0), self.networks), dtype=torch.float64, device=cols.device)
+        check(_abi.lib.syldet_train_fit_device(self._h, cols.data_ptr(), int(cols.shape[1]), 0, targets.data_ptr(), weights.data_ptr(), int(weights.shape[1]),
+                                               p.data_ptr(), int(steps), float(lr), float(beta1), float(beta2), float(eps), history.data_ptr(),
+                                               self.detector._stream_ptr(stream)))
+        return p, history
 
 
 def trainInputMapHost(rng):
