@@ -1507,6 +1507,69 @@ int syldet_match_scores_host(const float *t_hat, int32_t n, int32_t bins, const 
 int syldet_match_peaks_host(const float *scores, int64_t n_positions, float threshold, int32_t separation, int64_t origin, int64_t hop,
                             int32_t anchor, int64_t *events, int64_t capacity, int64_t *count, float *event_scores);
 
+/* ---- template matching: a bank of templates ----
+ * A real song has several syllable types, and one exemplar of a syllable is a poor detector of it: a lab keeps a handful of
+ * exemplars a syllable and takes the best of them.  A bank does that in one pass over the columns: the frames of a tile are staged
+ * and their energies taken once for all templates, where K matchers pay both K times.  Everything the section above defines -- the
+ * detector, the template's rules and t^, the score, the result's NaN, the peaks rule, the events -- holds here for every template.
+ * A BANK is K templates, 1 <= K <= SYLDET_MATCH_MAX_TEMPLATES, each [n][bins]; all share one n, one bins and one anchor; each obeys
+ *   the single template's rules (finite, not all zero, n bins <= SYLDET_MATCH_MAX_TEMPLATE) and is normalised on its own as
+ *   syldet_match_normalize_host does it.
+ * CLASSES.  template_class[k] lies in [0, C), 1 <= C <= SYLDET_MATCH_MAX_CLASSES; every class has at least one template.  A class
+ *   is a syllable, its templates that syllable's exemplars.  A NULL template_class means class k = k and C = K (n_classes K or 0),
+ *   which is refused when K > SYLDET_MATCH_MAX_CLASSES.
+ * THE TEMPLATE SCORE s_k(p) is the single matcher's score of template k at position p WITH THE SAME BITS: the same chains in the
+ *   same order in the same form.  The form (matrix or plain) is the single matcher's function of (n, bins); K does not enter it.
+ * THE CLASS SCORE S_c(p) is the greatest s_k(p) over the templates of class c.  All templates share n, so they share windows: a
+ *   position is NaN for every template or for none, and its NaN-ness, its E and its +0.0 on silence are the single matcher's.  The
+ *   templates are taken in ascending k and the running value is replaced only where s_k > running, so which_c(p) is the LOWEST k
+ *   of the class that attains the maximum; it is -1 where the score is NaN.  Comparisons only: S_c(p) has the bits of
+ *   s_{which_c(p)}(p).  (csrc/match_classes.hpp: one text for the kernels, the host and a stand-alone test.)
+ * THE RESULT is d_scores [C][rows][n_frames] fp32, every element written exactly once, NaN wherever the single matcher writes NaN;
+ *   d_which [C][rows][n_frames] int32 or NULL, every element written exactly once when given.
+ * PEAKS.  Each class is matched on its own plane by the rule above (csrc/match_peaks.hpp, unchanged) with its own thresholds[c]
+ *   -- a HOST array of C floats, none NaN, passed to the kernel by value: nothing is uploaded -- and the shared separation.
+ *   d_events [C][D][capacity], d_counts [C][D], d_event_scores [C][D][capacity] or NULL; d_event_template [C][D][capacity] int32 or
+ *   NULL is which at each matched position and needs d_which (SYLDET_ERR_INVALID_ARGUMENT without it).  Class c's tables are byte
+ *   for byte what syldet_match_peaks_device writes from plane c with thresholds[c].  CLASSES DO NOT SUPPRESS EACH OTHER: two
+ *   classes may match at the same position, and a caller who wants one label a position decides between them.
+ *   syldet_matcher_bank_create     h, r, the anchor as syldet_matcher_create; templates [K][n][bins].  The normalised templates,
+ *       the class table and, for recordings, the slots go to the device once.
+ *   syldet_matcher_bank_shape      D, K, C, n, bins, the anchor, the form (each may be NULL)
+ *   syldet_matcher_bank_templates  t^ [K][n][bins] and the class of each template (either may be NULL)
+ *   syldet_match_bank_scores_device   ONE launch for any K and C.  "match_bank_scores_mfma_kernel" keeps the tile, the grid and the
+ *       LDS layout of "match_scores_mfma_kernel": the frames of 256 positions are staged once, their energies taken and the
+ *       non-finite values zeroed once, E of a position summed once; every template then makes one pass of the same
+ *       v_mfma_f32_16x16x4_f32 chain over the staged frames through the one template region of the tile, the next template staged
+ *       behind the barrier that ends a pass.  "match_bank_scores_plain_kernel" where the single matcher takes the plain form.
+ *   syldet_match_bank_peaks_device    ONE launch for any C and D ("match_bank_peaks_kernel", grid (D, C): the body of
+ *       "match_peaks_kernel" a class).
+ *   syldet_match_classes_host      host only: template scores [K][n_positions] -> class_scores [C][n_positions] and which (may be
+ *       NULL) by the rule above; of the values given, a NaN is never taken, so a position is NaN, -1 iff all its class's are NaN.
+ * Statuses as above, decided before any device is touched; besides: K or C outside their ranges, a class outside [0, C), a class
+ * without a template, NULL thresholds or a NaN among them, d_event_template without d_which are SYLDET_ERR_INVALID_ARGUMENT.  Mixed
+ * and sharded banks get the answers the single matcher gives them.
+ * THE LAUNCH RULE is the matcher's: both device calls are launches only -- no allocation, no synchronisation, no copy -- and each
+ * records into the profile of h under its kernel's name.
+ * NOT HERE: templates of different lengths in one bank; suppression across classes; a class column in label files; training more
+ * than output 0 from the command-line tool; sharded banks.                                                                        */
+#define SYLDET_MATCH_MAX_TEMPLATES 64
+#define SYLDET_MATCH_MAX_CLASSES   16
+typedef struct syldet_matcher_bank syldet_matcher_bank_t;
+int syldet_matcher_bank_create(const syldet_t *h, const syldet_recordings_t *r, const float *templates, int32_t n_templates, int32_t n,
+                               int32_t bins, int32_t anchor, const int32_t *template_class, int32_t n_classes, syldet_matcher_bank_t **out);
+int syldet_matcher_bank_destroy(syldet_matcher_bank_t *m);
+int syldet_matcher_bank_shape(const syldet_matcher_bank_t *m, int32_t *n_detectors, int32_t *n_templates, int32_t *n_classes, int32_t *n,
+                              int32_t *bins, int32_t *anchor, int32_t *matrix_form);
+int syldet_matcher_bank_templates(const syldet_matcher_bank_t *m, float *t_hat, int32_t *template_class);
+int syldet_match_bank_scores_device(syldet_matcher_bank_t *m, const float *d_columns, int64_t n_frames, int64_t row_stride, float *d_scores,
+                                    int32_t *d_which, void *hip_stream);
+int syldet_match_bank_peaks_device(syldet_matcher_bank_t *m, const float *d_scores, const int32_t *d_which, int64_t n_frames,
+                                   const float *thresholds, int32_t separation, int64_t *d_events, int64_t capacity, int64_t *d_counts,
+                                   float *d_event_scores, int32_t *d_event_template, void *hip_stream);
+int syldet_match_classes_host(const float *template_scores, int64_t n_positions, int32_t n_templates, const int32_t *template_class,
+                              int32_t n_classes, float *class_scores, int32_t *which);
+
 #ifdef __cplusplus
 }
 #endif

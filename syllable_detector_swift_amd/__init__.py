@@ -11,7 +11,7 @@ from .config import (InvalidValue, MismatchedLength, MissingValue, NeuralNet, Ne
                      createWindow, frequencyIndexRange)
 from .bank import PinnedArray, ShardedSyllableDetectorBank, shard_table
 from ._abi import ALIGN_COLUMNS, ALIGN_OUTPUTS, ALIGN_SAMPLES, PCM_F32, PCM_F64, PCM_S16, PCM_S24, PCM_S32, PCM_U8
-from .detector import (PCM24, Aligner, Matcher, matchNormalizeHost, matchPeaksHost, matchScoresHost, Recordings, Scorer, SyllableDetector, Trainer, MultiTrainer, trainParamCount, trainTargetsHost, trainAdamHost, trainInitHost, trainInputMapHost, alignHost, alignStatsHost, chooseThreshold, configsCompatible, configsShareClock, fusedFormOfConfig,
+from .detector import (PCM24, Aligner, Matcher, MatcherBank, matchClassesHost, matchNormalizeHost, matchPeaksHost, matchScoresHost, Recordings, Scorer, SyllableDetector, Trainer, MultiTrainer, trainParamCount, trainTargetsHost, trainAdamHost, trainInitHost, trainInputMapHost, alignHost, alignStatsHost, chooseThreshold, configsCompatible, configsShareClock, fusedFormOfConfig,
                        pcmDecode, pcmSampleBytes, planRecordings, recordingLengths, scoreHost)
 from .resampler import ResamplerLinear, ResamplerSinc, sincReady, convertRate, deinterleave, sincCoefficient, sincDefaults, sincTaps
 
@@ -24,4 +24,5 @@ __all__ = ["SyllableDetector", "SyllableDetectorConfig", "NeuralNet", "NeuralNet
            "PCM_U8", "PCM_S16", "PCM_S24", "PCM_S32", "PCM_F32", "PCM_F64", "PCM24", "pcmDecode", "pcmSampleBytes",
            "Aligner", "alignHost", "alignStatsHost", "ALIGN_COLUMNS", "ALIGN_OUTPUTS", "ALIGN_SAMPLES",
            "Trainer", "MultiTrainer", "trainParamCount", "trainTargetsHost", "trainAdamHost", "trainInitHost", "trainInputMapHost",
-           "Matcher", "matchNormalizeHost", "matchScoresHost", "matchPeaksHost"]
+           "Matcher", "matchNormalizeHost", "matchScoresHost", "matchPeaksHost",
+           "MatcherBank", "matchClassesHost"]

@@ -108,6 +108,7 @@ TRAIN_MAX_HIDDEN, TRAIN_MAX_OUTPUTS = 16, 4
 
 # the matcher's limits (SYLDET_MATCH_*)
 MATCH_MAX_TEMPLATE, MATCH_MAX_SEPARATION = 32768, 4096
+MATCH_MAX_TEMPLATES, MATCH_MAX_CLASSES = 64, 16
 
 Handle = C.c_void_p
 Config_p = C.POINTER(Config)
@@ -337,6 +338,15 @@ SIGNATURES = {
     "syldet_match_scores_host": (C.c_int, [c_float_p, C.c_int32, C.c_int32, c_float_p, C.c_int64, c_float_p]),
     "syldet_match_peaks_host": (C.c_int, [c_float_p, C.c_int64, C.c_float, C.c_int32, C.c_int64, C.c_int64, C.c_int32, c_int64_p, C.c_int64,
                                           c_int64_p, c_float_p]),
+    "syldet_matcher_bank_create": (C.c_int, [Handle, Handle, c_float_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, c_int32_p, C.c_int32,
+                                             C.POINTER(Handle)]),
+    "syldet_matcher_bank_destroy": (C.c_int, [Handle]),
+    "syldet_matcher_bank_shape": (C.c_int, [Handle, c_int32_p, c_int32_p, c_int32_p, c_int32_p, c_int32_p, c_int32_p, c_int32_p]),
+    "syldet_matcher_bank_templates": (C.c_int, [Handle, c_float_p, c_int32_p]),
+    "syldet_match_bank_scores_device": (C.c_int, [Handle, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "syldet_match_bank_peaks_device": (C.c_int, [Handle, C.c_void_p, C.c_void_p, C.c_int64, c_float_p, C.c_int32, C.c_void_p, C.c_int64,
+                                                 C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "syldet_match_classes_host": (C.c_int, [c_float_p, C.c_int64, C.c_int32, c_int32_p, C.c_int32, c_float_p, c_int32_p]),
 }
 
 

@@ -413,7 +413,7 @@ bool batch_write(const Batch &b, int rc)
         if (!write_track(TrackDirs::in(o.dirs.ttl, f.path), rate, tracks, n, b.ttl_frames.data() + p.frames_at[i])) written = false;
         if (!ons.empty() && !write_onsets(ons, tracks, b.on_idx.empty() ? nullptr : b.on_idx.data() + k0 * (size_t)b.on_cap, b.on_cnt.data() + k0, b.on_cap, rate)) written = false;
         if (b.run.align && align_write_file(*b.run.align, f.path, b.al, k0, tracks, rate)) written = false;
-        if (b.run.match) match_add_file(*b.run.match, f.path, b.matched, k0, tracks);
+        if (b.run.match) match_add_file(*b.run.match, f.path, b.matched, k0, tracks, (size_t)b.plan.K);
         if (!o.dirs.levels.empty()) {
             const LevelTable table{tracks, o.levels.buffer, b.lv_P, b.lv_first[k0 + 1] - b.lv_first[k0], n, b.lv_first.data() + k0, b.lv_in.data(), b.lv_out.data(), b.lv_empty.data()};
             if (!write_levels(TrackDirs::in(o.dirs.levels, f.path, ".tsv"), table, rate)) written = false;

@@ -9,7 +9,8 @@
 // the fp32 path's bits on x / 32768, which is what the decoder would have produced).
 // --simulate-dir / --ttl-dir / --ttl-onsets-dir write the same files for any number of audio files; under --batch a batch's tracks are
 // made by syldet_recordings_trace_device_s16 / syldet_recordings_trigger*_device_s16 straight into every file's frames.
-// --match writes the occurrences of an exemplar in every track's columns as the labels --score reads (syldet_matcher_*).
+// --match writes the occurrences of an exemplar in every track's columns as the labels --score reads; given several times, each is a
+// syllable class of one or more exemplars with a file of its own, all matched in one pass (syldet_matcher_bank_*).
 // --train trains the network on the one batch's recordings against such labels and writes it in the text format (syldet_trainer_*,
 // syldet_train_fit_device, syldet_config_save_text).
 // --levels-dir writes every file's --levels table likewise; under --batch by syldet_recordings_levels_device* /

@@ -1,4 +1,6 @@
-// --match: the template and what a run gathers (see MatchOpt), the matches of one bank's detectors, and the file written at the end.
+// --match: the templates and what a run gathers (see MatchOpt), the matches of one bank's detectors, and the files written at the end.
+// The i-th --match is class i of one bank of templates (syldet_matcher_bank_*): one scores call and one peaks call a bank of
+// detectors, whatever the number of classes and exemplars.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -11,15 +13,17 @@ namespace {
 
 struct MatchRun {
     MatchOpt opt;
-    std::vector<float> templ;                              // [n][bins]
-    int n = 0, bins = 0, anchor = -1, separation = 0;      // the separation in frames
-    float threshold = 0.0f;
-    std::string lines;                                      // file<TAB>track<TAB>sample, in command-line order, then track, then sample
+    std::vector<float> templ;                              // [K][n][bins], class by class
+    std::vector<int32_t> tclass;                           // [K]
+    std::vector<float> thresholds;                         // [C]
+    int K = 0, C = 0, n = 0, bins = 0, anchor = -1, separation = 0;      // the separation in frames
+    std::vector<std::string> lines;                        // [C] file<TAB>track<TAB>sample, in command-line order, then track, then sample
     bool failed = false;
 };
 
-// A NumPy file (format 1.0 or 2.0) of a little-endian float32 or float64 C-order array of two dimensions -> float32 values.
-bool read_npy(const std::string &path, std::vector<float> &values, int64_t shape[2], std::string &err)
+// A NumPy file (format 1.0 or 2.0) of a little-endian float32 or float64 C-order array [frames][bins] or [exemplars][frames][bins] ->
+// float32 values and shape = {exemplars (1 for two dimensions), frames, bins}.
+bool read_npy(const std::string &path, std::vector<float> &values, int64_t shape[3], std::string &err)
 {
     FILE *f = std::fopen(path.c_str(), "rb");
     if (!f) { err = "unable to open " + path; return false; }
@@ -46,15 +50,21 @@ bool read_npy(const std::string &path, std::vector<float> &values, int64_t shape
     int dims = 0;
     while (*p && *p != ')') {
         const long long v = std::strtoll(p, &end, 10);
-        if (end == p || v < 0 || dims == 2) return bad("not an array [frames][bins]");
+        if (end == p || v < 0 || dims == 3) return bad("not an array [frames][bins]");
         shape[dims++] = v;
         p = end;
         while (*p == ',' || *p == ' ') p++;
     }
-    if (dims != 2 || shape[0] < 1 || shape[1] < 1 || shape[0] > SYLDET_MATCH_MAX_TEMPLATE || shape[1] > SYLDET_MATCH_MAX_TEMPLATE ||
-        shape[0] * shape[1] > SYLDET_MATCH_MAX_TEMPLATE)
+    if (dims == 2) {
+        shape[2] = shape[1];
+        shape[1] = shape[0];
+        shape[0] = 1;
+    }
+    if (dims < 2 || shape[1] < 1 || shape[2] < 1 || shape[1] > SYLDET_MATCH_MAX_TEMPLATE || shape[2] > SYLDET_MATCH_MAX_TEMPLATE ||
+        shape[1] * shape[2] > SYLDET_MATCH_MAX_TEMPLATE)
         return bad("not an array [frames][bins] of 1 to 32768 values");
-    const size_t count = (size_t)(shape[0] * shape[1]), el = f4 ? 4 : 8;
+    if (shape[0] < 1 || shape[0] > SYLDET_MATCH_MAX_TEMPLATES) return bad("not 1 to 64 exemplars [exemplars][frames][bins]");
+    const size_t count = (size_t)(shape[0] * shape[1] * shape[2]), el = f4 ? 4 : 8;
     if (bytes.size() - at - hlen < count * el) return bad("fewer values than the shape says");
     values.resize(count);
     const char *data = bytes.data() + at + hlen;
@@ -65,24 +75,41 @@ bool read_npy(const std::string &path, std::vector<float> &values, int64_t shape
     return true;
 }
 
-// The template, and the options in the network's units.  0, or the usage error.
+// The templates, and the options in the network's units.  0, or the usage error.
 int match_begin(MatchRun &run, const MatchOpt &opt, const std::vector<syldet_config_t *> &cfgs)
 {
     run.opt = opt;
     if (cfgs.size() > 1) return fail("--match takes one network (-n): the columns of several are ragged.");
     syldet_geometry_t g;
     if (const int st = syldet_config_geometry(cfgs[0], &g)) return fail(std::string("Unable to use the network configuration: ") + syldet_strerror(st) + ": " + syldet_last_error());
-    std::string err;
-    int64_t shape[2] = {0, 0};
-    if (!read_npy(opt.path, run.templ, shape, err)) return fail("--match: " + err + ".");
-    run.n = (int)shape[0];
-    run.bins = (int)shape[1];
-    if (run.bins != g.bins) return fail("--match: the template has " + std::to_string(run.bins) + " bins, the network's columns " + std::to_string(g.bins) + ".");
-    std::vector<float> t_hat(run.templ.size());
-    if (syldet_match_normalize_host(run.templ.data(), run.n, run.bins, t_hat.data())) return fail(std::string("--match: ") + syldet_last_error() + ".");
+    run.C = (int)opt.paths.size();
+    run.lines.assign((size_t)run.C, std::string());
+    for (int c = 0; c < run.C; c++) {
+        std::string err;
+        std::vector<float> values;
+        int64_t shape[3] = {0, 0, 0};
+        if (!read_npy(opt.paths[(size_t)c], values, shape, err)) return fail("--match: " + err + ".");
+        if (c == 0) {
+            run.n = (int)shape[1];
+            run.bins = (int)shape[2];
+            if (run.bins != g.bins) return fail("--match: the template has " + std::to_string(run.bins) + " bins, the network's columns " + std::to_string(g.bins) + ".");
+        } else if (shape[1] != run.n || shape[2] != run.bins) {
+            return fail("--match: " + opt.paths[0] + " is [" + std::to_string(run.n) + "][" + std::to_string(run.bins) + "] and " + opt.paths[(size_t)c] + " [" +
+                        std::to_string(shape[1]) + "][" + std::to_string(shape[2]) + "]: the templates of one run share their frames and bins.");
+        }
+        run.K += (int)shape[0];
+        if (run.K > SYLDET_MATCH_MAX_TEMPLATES) return fail("--match takes " + std::to_string(SYLDET_MATCH_MAX_TEMPLATES) + " exemplars at most, all files together.");
+        const size_t one = (size_t)run.n * (size_t)run.bins;
+        std::vector<float> t_hat(one);
+        for (int64_t k = 0; k < shape[0]; k++)
+            if (syldet_match_normalize_host(values.data() + (size_t)k * one, run.n, run.bins, t_hat.data())) return fail(std::string("--match: ") + syldet_last_error() + ".");
+        run.templ.insert(run.templ.end(), values.begin(), values.end());
+        run.tclass.insert(run.tclass.end(), (size_t)shape[0], c);
+    }
     if (opt.anchor >= run.n) return fail("--match-anchor takes a frame of the template, 0 to " + std::to_string(run.n - 1) + ".");
     run.anchor = opt.anchor < 0 ? run.n - 1 : (int)opt.anchor;
-    run.threshold = (float)opt.threshold;
+    for (int c = 0; c < run.C; c++)
+        run.thresholds.push_back((float)(opt.thresholds.empty() ? 0.77 : opt.thresholds[opt.thresholds.size() == 1 ? 0 : (size_t)c]));
     // the separation in frames: the template's own length unless given
     const double frames = opt.separation < 0.0 ? (double)run.n : opt.separation * cfgs[0]->sampling_rate / (double)g.hop;
     if (!(frames <= (double)SYLDET_MATCH_MAX_SEPARATION)) return fail("--match-separation may be " + std::to_string(SYLDET_MATCH_MAX_SEPARATION) + " frames at most.");
@@ -91,29 +118,33 @@ int match_begin(MatchRun &run, const MatchOpt &opt, const std::vector<syldet_con
 }
 
 // The matches of one bank's detectors -- a batch's recordings (r), or a file's tracks (r NULL) -- from the fp32 rows the bank was fed:
-// the rows' columns, the scores, the peaks (twice where the first table is too small), and back.  false: the device's or the library's refusal.
+// the rows' columns, every class's scores in one call, every class's peaks in one call (twice where the first table is too small),
+// and back: events [class * D + detector].  false: the device's or the library's refusal.
 bool match_bank(MatchRun &run, syldet_t *h, syldet_recordings_t *r, const float *rows, int64_t row_samples, int64_t stride, int C, int D, hipStream_t stream,
                 std::vector<std::vector<int64_t>> &events)
 {
-    events.assign((size_t)D, {});
+    const size_t N = (size_t)run.C * (size_t)D;             // tables: a class's detectors one after another
+    events.assign(N, {});
     const int64_t J = std::max<int64_t>(0, syldet_count_frames(h, row_samples));
     if (J <= 0 || D <= 0) return true;
-    syldet_matcher_t *m = nullptr;
-    int st = syldet_matcher_create(h, r, run.templ.data(), run.n, run.bins, run.anchor, &m);
+    syldet_matcher_bank_t *m = nullptr;
+    int st = syldet_matcher_bank_create(h, r, run.templ.data(), run.K, run.n, run.bins, run.anchor, run.tclass.data(), run.C, &m);
     DevBuf d_cols, d_scores, d_events, d_counts;
     bool ok = true;
-    std::vector<int64_t> counts((size_t)D, 0), table;
+    std::vector<int64_t> counts(N, 0), table;
     int64_t cap = 1024;
     if (!st) {
-        ok = d_cols.alloc((size_t)C * (size_t)J * (size_t)run.bins * sizeof(float)) && d_scores.alloc((size_t)C * (size_t)J * sizeof(float)) &&
-             d_counts.alloc((size_t)D * sizeof(int64_t));
+        ok = d_cols.alloc((size_t)C * (size_t)J * (size_t)run.bins * sizeof(float)) && d_scores.alloc((size_t)run.C * (size_t)C * (size_t)J * sizeof(float)) &&
+             d_counts.alloc(N * sizeof(int64_t));
         if (ok) st = syldet_spectrogram_device(h, rows, row_samples, stride, (float *)d_cols.p, stream);
-        if (ok && !st) st = syldet_match_scores_device(m, (const float *)d_cols.p, J, 0, (float *)d_scores.p, stream);
+        if (ok && !st) st = syldet_match_bank_scores_device(m, (const float *)d_cols.p, J, 0, (float *)d_scores.p, nullptr, stream);
         for (int pass = 0; ok && !st && pass < 2; pass++) {
             DevBuf d_table;
-            ok = d_table.alloc((size_t)D * (size_t)cap * sizeof(int64_t));
-            if (ok) st = syldet_match_peaks_device(m, (const float *)d_scores.p, J, run.threshold, run.separation, (int64_t *)d_table.p, cap, (int64_t *)d_counts.p, nullptr, stream);
-            table.assign((size_t)D * (size_t)cap, 0);
+            ok = d_table.alloc(N * (size_t)cap * sizeof(int64_t));
+            if (ok)
+                st = syldet_match_bank_peaks_device(m, (const float *)d_scores.p, nullptr, J, run.thresholds.data(), run.separation, (int64_t *)d_table.p, cap,
+                                                    (int64_t *)d_counts.p, nullptr, nullptr, stream);
+            table.assign(N * (size_t)cap, 0);
             if (ok && !st)
                 ok = hipMemcpyAsync(counts.data(), d_counts.p, counts.size() * sizeof(int64_t), hipMemcpyDeviceToHost, stream) == hipSuccess &&
                      hipMemcpyAsync(table.data(), d_table.p, table.size() * sizeof(int64_t), hipMemcpyDeviceToHost, stream) == hipSuccess &&
@@ -123,28 +154,36 @@ bool match_bank(MatchRun &run, syldet_t *h, syldet_recordings_t *r, const float 
             cap = most;                                     // a table too small: once more with the largest count
         }
     }
-    syldet_matcher_destroy(m);
+    syldet_matcher_bank_destroy(m);
     if (st) std::fprintf(stderr, "Unable to match the template: %s: %s\n", syldet_strerror(st), syldet_last_error());
     if (!ok || st) return false;
-    for (int d = 0; d < D; d++) events[(size_t)d].assign(table.begin() + (size_t)d * (size_t)cap, table.begin() + (size_t)d * (size_t)cap + (size_t)std::min(counts[(size_t)d], cap));
+    for (size_t d = 0; d < N; d++) events[d].assign(table.begin() + d * (size_t)cap, table.begin() + d * (size_t)cap + (size_t)std::min(counts[d], cap));
     return true;
 }
 
-// one file's lines: its tracks are the bank's detectors k0 .. k0 + tracks - 1
-void match_add_file(MatchRun &run, const std::string &path, const std::vector<std::vector<int64_t>> &events, size_t k0, int tracks)
+// one file's lines, class by class: its tracks are the bank's detectors k0 .. k0 + tracks - 1 of D (events: match_bank's; a bank that
+// failed has none)
+void match_add_file(MatchRun &run, const std::string &path, const std::vector<std::vector<int64_t>> &events, size_t k0, int tracks, size_t D)
 {
-    for (size_t t = 0; t < (size_t)tracks && k0 + t < events.size(); t++)
-        for (const int64_t s : events[k0 + t]) run.lines += path + "\t" + std::to_string(t) + "\t" + std::to_string(s) + "\n";
+    if (events.size() != (size_t)run.C * D) return;
+    for (size_t c = 0; c < (size_t)run.C; c++)
+        for (size_t t = 0; t < (size_t)tracks && k0 + t < D; t++)
+            for (const int64_t s : events[c * D + k0 + t]) run.lines[c] += path + "\t" + std::to_string(t) + "\t" + std::to_string(s) + "\n";
 }
 
-// the file, behind the last audio file
+// the files, behind the last audio file: class i's matches in the i-th --match-out
 bool match_finish(const MatchRun &run)
 {
-    FILE *f = std::fopen(run.opt.out_path.c_str(), "wb");
-    bool ok = f != nullptr && std::fwrite(run.lines.data(), 1, run.lines.size(), f) == run.lines.size();
-    if (f && std::fclose(f) != 0) ok = false;
-    if (!ok) std::fprintf(stderr, "Unable to write %s.\n", run.opt.out_path.c_str());
-    return ok && !run.failed;
+    bool all = true;
+    for (size_t c = 0; c < (size_t)run.C; c++) {
+        const std::string &out = run.opt.out_paths[c];
+        FILE *f = std::fopen(out.c_str(), "wb");
+        bool ok = f != nullptr && std::fwrite(run.lines[c].data(), 1, run.lines[c].size(), f) == run.lines[c].size();
+        if (f && std::fclose(f) != 0) ok = false;
+        if (!ok) std::fprintf(stderr, "Unable to write %s.\n", out.c_str());
+        all = all && ok;
+    }
+    return all && !run.failed;
 }
 
 }  // namespace

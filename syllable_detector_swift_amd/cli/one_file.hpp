@@ -380,7 +380,7 @@ int write_files(OneFile &f)
     if (!f.mux_refused && !write_track(ttl.path, rate, ttl.mux ? 2 * f.C : f.C, f.fed, f.ttl_track.data())) c = 3;
     if (!ttl.onsets.empty() && !write_onsets(ttl.onsets, f.ttl_cnt.empty() ? 0 : f.C, f.ttl_idx.data(), f.ttl_cnt.data(), f.ttl_cap, rate)) c = 3;
     const int w = f.run.align ? align_write_file(*f.run.align, f.path, f.al, 0, f.C, rate) : 0;
-    if (f.run.match) match_add_file(*f.run.match, f.path, f.matched, 0, f.C);
+    if (f.run.match) match_add_file(*f.run.match, f.path, f.matched, 0, f.C, (size_t)f.C);
     return a ? a : (b ? b : (c ? c : w));
 }
 

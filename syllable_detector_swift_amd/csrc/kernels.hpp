@@ -648,6 +648,27 @@ hipError_t launch_match_scores(const MatchDesc &d, const float *columns, int64_t
 // events [D][capacity], counts [D], event_scores [D][capacity] or nullptr <- scores [rows][n_frames]; one launch (match_peaks_kernel)
 hipError_t launch_match_peaks(const MatchDesc &d, const float *scores, int64_t n_frames, float threshold, int separation, int64_t *events,
                               int64_t capacity, int64_t *counts, float *event_scores, hipStream_t stream);
+// A bank of K templates in C classes ("template matching: a bank of templates" of include/syldet.h): d.templ is [K][n][bins], the
+// form and the LDS of a tile are match_plan's, which K does not enter.
+struct MatchBankDesc {
+    MatchDesc d;
+    const int32_t *order;                    // [K] the templates class by class, ascending k within a class (on the device)
+    const int32_t *order_class;              // [K] the class of order[i]
+    int K, C;
+};
+struct MatchBankKeys {
+    uint32_t key[16];                        // match_key of every class's threshold
+};
+hipError_t match_bank_prepare();             // as match_prepare, for the bank's peaks kernel
+// scores [C][rows][n_frames], which [C][rows][n_frames] or nullptr <- columns; every element written once; one launch
+// (match_bank_scores_mfma_kernel or match_bank_scores_plain_kernel)
+hipError_t launch_match_bank_scores(const MatchBankDesc &b, const float *columns, int64_t n_frames, int64_t row_stride, float *scores, int32_t *which,
+                                    hipStream_t stream);
+// events [C][D][capacity], counts [C][D], event_scores and event_template [C][D][capacity] or nullptr <- scores and which
+// [C][rows][n_frames]; one launch (match_bank_peaks_kernel), grid (D, C)
+hipError_t launch_match_bank_peaks(const MatchBankDesc &b, const float *scores, const int32_t *which, int64_t n_frames, const float *thresholds,
+                                   int separation, int64_t *events, int64_t capacity, int64_t *counts, float *event_scores, int32_t *event_template,
+                                   hipStream_t stream);
 
 // detection flags <-> bits (bit b of byte t of a row = flag 8 t + b), rows padded to whole bytes
 hipError_t launch_pack_flags(const uint8_t *flags, int64_t rows, int64_t row_len, uint8_t *bits, hipStream_t stream);

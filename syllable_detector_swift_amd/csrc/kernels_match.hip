@@ -22,10 +22,16 @@
 //                  step and of S positions on either side go to LDS, log2 S passes of m[i] = max(m[i], m[i + 2^l]) make the maxima of
 //                  all windows of 2^k positions, two of which cover any window of S; a thread marks its 8 consecutive positions by
 //                  the rule, and a scan over the workgroup's counts places the events in order.
+//   match_bank_scores_mfma_kernel, match_bank_scores_plain_kernel, match_bank_peaks_kernel   K templates in C classes in one launch
+//                  ("template matching: a bank of templates"): the frames are staged and their energies taken once, every template
+//                  then runs the single kernel's products through the same device functions, so template k's score has the single
+//                  matcher's bits, and a class's score is the greatest of its templates' (match_classes.hpp); the peaks kernel is
+//                  match_peaks_kernel's body a class, grid (D, C).
 //
 // gfx950 only: wave = 64 lanes.
 
 #include "kernels.hpp"
+#include "match_classes.hpp"
 #include "match_peaks.hpp"
 
 namespace sd {
@@ -63,23 +69,36 @@ __device__ __forceinline__ float match_score(float dot, float E)
     return (dot + 0.0f) / sqrtf(E);                          // (-0.0 -> +0.0: zeros added behind a window may have done so already)
 }
 
-__global__ void __launch_bounds__(kThreads)
-match_scores_mfma_kernel(MatchDesc d, const float *__restrict__ columns, int64_t n_frames, int64_t row_stride, float *__restrict__ scores)
-{
-    extern __shared__ float match_lds[];
-    const int tid = (int)threadIdx.x, row = (int)blockIdx.y;
-    const int64_t p0 = (int64_t)blockIdx.x * kMatchTile;
-    const int n = d.n, bins = d.bins, Fp = d.Fp, FT = d.FT;
-    const int G = kMatchTile - 1 + n;                        // staged frames
-    float *X = match_lds;                                    // frame g, bin b at g Fp + 4 (g >> 4) + b
-    float *T = X + G * Fp + 4 * ((G + 15) >> 4);             // t^ frame j, bin b at j FT + b
-    float *Efr = T + n * FT;                                 // [G] the frames' energies
-    float *red = Efr + G;                                    // [4][256] the waves' sums
-    const float *__restrict__ src = columns + (int64_t)row * row_stride;
+// ---- the matrix form's phases: one text for match_scores_mfma_kernel and match_bank_scores_mfma_kernel ----
+// A tile's LDS: the staged frames, one template, the frames' energies, the waves' sums (match_plan counts the same floats).
+struct MatchTile {
+    float *X;                                                // frame g, bin b at g Fp + 4 (g >> 4) + b
+    float *T;                                                // t^ frame j, bin b at j FT + b
+    float *Efr;                                              // [G] the frames' energies
+    float *red;                                              // [4][256] the waves' sums
+    int G;                                                   // staged frames
+};
 
-    // (eight loads a thread in flight: one at a time, the tile's staging waits out a memory latency an element and takes longer
-    // than its matrix instructions)
-    constexpr int kStage = 8;
+__device__ __forceinline__ MatchTile match_tile(float *lds, const MatchDesc &d)
+{
+    MatchTile t;
+    t.G = kMatchTile - 1 + d.n;
+    t.X = lds;
+    t.T = t.X + t.G * d.Fp + 4 * ((t.G + 15) >> 4);
+    t.Efr = t.T + d.n * d.FT;
+    t.red = t.Efr + t.G;
+    return t;
+}
+
+// (eight loads a thread in flight: one at a time, the tile's staging waits out a memory latency an element and takes longer
+// than its matrix instructions)
+constexpr int kStage = 8;
+
+// the frames from p0 on of one row -> X, bins padded to Fp and frames behind the row's end zero by selection
+__device__ __forceinline__ void match_stage_frames(const MatchDesc &d, const MatchTile &t, const float *__restrict__ src, int64_t p0, int64_t n_frames,
+                                                   int tid)
+{
+    const int bins = d.bins, Fp = d.Fp, G = t.G;
     for (int base = tid; base < G * Fp; base += kThreads * kStage) {
         float v[kStage];
         int at[kStage];
@@ -94,8 +113,14 @@ match_scores_mfma_kernel(MatchDesc d, const float *__restrict__ columns, int64_t
         }
 #pragma unroll
         for (int u = 0; u < kStage; u++)
-            if (at[u] >= 0) X[at[u]] = v[u];
+            if (at[u] >= 0) t.X[at[u]] = v[u];
     }
+}
+
+// one template t^ [n][bins] -> T
+__device__ __forceinline__ void match_stage_template(const MatchDesc &d, float *T, const float *__restrict__ templ, int tid)
+{
+    const int n = d.n, bins = d.bins, FT = d.FT;
     for (int base = tid; base < n * FT; base += kThreads * kStage) {
         float v[kStage];
 #pragma unroll
@@ -103,25 +128,34 @@ match_scores_mfma_kernel(MatchDesc d, const float *__restrict__ columns, int64_t
             const int idx = base + u * kThreads;
             const int j = idx / FT, b = idx - j * FT;
             v[u] = 0.0f;
-            if (idx < n * FT && b < bins) v[u] = d.templ[j * bins + b];
+            if (idx < n * FT && b < bins) v[u] = templ[j * bins + b];
         }
 #pragma unroll
         for (int u = 0; u < kStage; u++)
             if (base + u * kThreads < n * FT) T[base + u * kThreads] = v[u];
     }
-    __syncthreads();
-    for (int g = tid; g < G; g += kThreads) {
-        float *x = X + g * Fp + 4 * (g >> 4);
+}
+
+// a thread a frame: its energy from the staged values, and a NaN or an Inf replaced by zero
+__device__ __forceinline__ void match_energies(const MatchDesc &d, const MatchTile &t, int tid)
+{
+    for (int g = tid; g < t.G; g += kThreads) {
+        float *x = t.X + g * d.Fp + 4 * (g >> 4);
         float e = 0.0f;
-        for (int b = 0; b < bins; b++) {
+        for (int b = 0; b < d.bins; b++) {
             const float v = x[b];
             e = fmaf(v, v, e);
             if (!finite_bits(v)) x[b] = 0.0f;
         }
-        Efr[g] = e;
+        t.Efr[g] = e;
     }
-    __syncthreads();
+}
 
+// the products of the staged frames with the staged template: wave w's chains over the bin groups w, w + 4, .. -> red[w]
+__device__ __forceinline__ void match_products(const MatchDesc &d, const MatchTile &t, int tid)
+{
+    const int n = d.n, Fp = d.Fp, FT = d.FT;
+    const float *X = t.X, *T = t.T;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63;
     const int groups = Fp >> 2;
     if (wave < groups) {
@@ -157,22 +191,108 @@ match_scores_mfma_kernel(MatchDesc d, const float *__restrict__ columns, int64_t
             b = b1;
             in = in1;
         }
-        for (int r = 0; r < 4; r++) red[wave * kMatchTile + 16 * (4 * (lane >> 4) + r) + (lane & 15)] = acc[r];
+        for (int r = 0; r < 4; r++) t.red[wave * kMatchTile + 16 * (4 * (lane >> 4) + r) + (lane & 15)] = acc[r];
     }
+}
+
+// a thread a position: the waves' sums added in wave order; the window's energy from its first frame on
+__device__ __forceinline__ float match_dot(const MatchDesc &d, const MatchTile &t, int tid)
+{
+    const int groups = d.Fp >> 2, nw = groups < 4 ? groups : 4;
+    float dot = t.red[tid];
+    for (int w = 1; w < nw; w++) dot = dot + t.red[w * kMatchTile + tid];
+    return dot;
+}
+
+__device__ __forceinline__ float match_energy(const MatchDesc &d, const MatchTile &t, int tid)
+{
+    float E = 0.0f;
+    for (int j = 0; j < d.n; j++) E = E + t.Efr[tid + j];
+    return E;
+}
+
+__global__ void __launch_bounds__(kThreads)
+match_scores_mfma_kernel(MatchDesc d, const float *__restrict__ columns, int64_t n_frames, int64_t row_stride, float *__restrict__ scores)
+{
+    extern __shared__ float match_lds[];
+    const int tid = (int)threadIdx.x, row = (int)blockIdx.y;
+    const int64_t p0 = (int64_t)blockIdx.x * kMatchTile;
+    const MatchTile t = match_tile(match_lds, d);
+    match_stage_frames(d, t, columns + (int64_t)row * row_stride, p0, n_frames, tid);
+    match_stage_template(d, t.T, d.templ, tid);
+    __syncthreads();
+    match_energies(d, t, tid);
+    __syncthreads();
+    match_products(d, t, tid);
     __syncthreads();
 
     const int64_t q = p0 + tid;
     if (q >= n_frames) return;
     float s = __uint_as_float(0x7fc00000u);
-    if (match_position(d, row, q, n_frames)) {
-        const int nw = groups < 4 ? groups : 4;
-        float dot = red[tid];
-        for (int w = 1; w < nw; w++) dot = dot + red[w * kMatchTile + tid];
-        float E = 0.0f;
-        for (int j = 0; j < n; j++) E = E + Efr[tid + j];
-        s = match_score(dot, E);
-    }
+    if (match_position(d, row, q, n_frames)) s = match_score(match_dot(d, t, tid), match_energy(d, t, tid));
     scores[(int64_t)row * n_frames + q] = s;
+}
+
+// The bank: the frames staged and their energies taken once, then a pass of the same products a template, the templates class by
+// class (b.order: ascending k within a class, so a thread holds one running maximum and writes it behind its class's last
+// template).  One template region: template i + 1 is staged behind the barrier that ends template i's products, beside the
+// thread-a-position step, so K does not enter the tile's LDS.
+__global__ void __launch_bounds__(kThreads)
+match_bank_scores_mfma_kernel(MatchBankDesc b, const float *__restrict__ columns, int64_t n_frames, int64_t row_stride, float *__restrict__ scores,
+                              int32_t *__restrict__ which)
+{
+    extern __shared__ float match_lds[];
+    const MatchDesc &d = b.d;
+    const int tid = (int)threadIdx.x, row = (int)blockIdx.y;
+    const int64_t p0 = (int64_t)blockIdx.x * kMatchTile;
+    const int64_t one = (int64_t)d.n * d.bins;
+    const MatchTile t = match_tile(match_lds, d);
+    match_stage_frames(d, t, columns + (int64_t)row * row_stride, p0, n_frames, tid);
+    match_stage_template(d, t.T, d.templ + b.order[0] * one, tid);
+    __syncthreads();
+    match_energies(d, t, tid);
+    __syncthreads();
+
+    const int64_t q = p0 + tid;
+    const bool live = q < n_frames, pos = live && match_position(d, row, q, n_frames);
+    const float E = pos ? match_energy(d, t, tid) : 0.0f;    // one sum for the K scores
+    const int64_t plane = (int64_t)d.rows * n_frames, at = (int64_t)row * n_frames + q;
+    float running;
+    int32_t w;
+    match_class_begin(running, w);
+    for (int i = 0; i < b.K; i++) {
+        const int k = b.order[i], c = b.order_class[i];
+        const bool more = i + 1 < b.K;
+        match_products(d, t, tid);
+        __syncthreads();
+        if (more) match_stage_template(d, t.T, d.templ + b.order[i + 1] * one, tid);
+        if (pos) match_class_take(match_score(match_dot(d, t, tid), E), k, running, w);
+        if (!more || b.order_class[i + 1] != c) {            // the class's last template
+            if (live) {
+                scores[c * plane + at] = running;
+                if (which) which[c * plane + at] = w;
+            }
+            match_class_begin(running, w);
+        }
+        if (more) __syncthreads();                           // (the template and the waves' sums are the next pass's)
+    }
+}
+
+// one thread a position: the window's chains from global memory
+template <bool kEnergy>
+__device__ __forceinline__ void match_plain_chains(const float *__restrict__ x, const float *__restrict__ t, int n, int bins, float &dot, float &E)
+{
+    dot = 0.0f;
+    if (kEnergy) E = 0.0f;
+    for (int j = 0; j < n; j++) {
+        float e = 0.0f;
+        for (int b = 0; b < bins; b++) {
+            const float v = x[j * bins + b];
+            if (kEnergy) e = fmaf(v, v, e);
+            dot = fmaf(finite_bits(v) ? v : 0.0f, t[j * bins + b], dot);
+        }
+        if (kEnergy) E = E + e;
+    }
 }
 
 __global__ void __launch_bounds__(kThreads)
@@ -183,29 +303,51 @@ match_scores_plain_kernel(MatchDesc d, const float *__restrict__ columns, int64_
     if (q >= n_frames) return;
     float s = __uint_as_float(0x7fc00000u);
     if (match_position(d, row, q, n_frames)) {
-        const float *__restrict__ x = columns + (int64_t)row * row_stride + q * d.bins;
-        const float *__restrict__ t = d.templ;
-        float dot = 0.0f, E = 0.0f;
-        for (int j = 0; j < d.n; j++) {
-            float e = 0.0f;
-            for (int b = 0; b < d.bins; b++) {
-                const float v = x[j * d.bins + b];
-                e = fmaf(v, v, e);
-                dot = fmaf(finite_bits(v) ? v : 0.0f, t[j * d.bins + b], dot);
-            }
-            E = E + e;
-        }
+        float dot, E;
+        match_plain_chains<true>(columns + (int64_t)row * row_stride + q * d.bins, d.templ, d.n, d.bins, dot, E);
         s = match_score(dot, E);
     }
     scores[(int64_t)row * n_frames + q] = s;
 }
 
+// the bank: the same chains a template, E with the first
 __global__ void __launch_bounds__(kThreads)
-match_peaks_kernel(MatchDesc d, const float *__restrict__ scores, int64_t n_frames, uint32_t threshold_key, int S, int64_t *__restrict__ events,
-                   int64_t capacity, int64_t *__restrict__ counts, float *__restrict__ event_scores)
+match_bank_scores_plain_kernel(MatchBankDesc b, const float *__restrict__ columns, int64_t n_frames, int64_t row_stride, float *__restrict__ scores,
+                               int32_t *__restrict__ which)
 {
-    extern __shared__ uint32_t match_keys[];
-    __shared__ int wave_sum[kThreads / 64];
+    const MatchDesc &d = b.d;
+    const int row = (int)blockIdx.y;
+    const int64_t q = (int64_t)blockIdx.x * kMatchTile + (int)threadIdx.x;
+    if (q >= n_frames) return;
+    const bool pos = match_position(d, row, q, n_frames);
+    const float *__restrict__ x = columns + (int64_t)row * row_stride + q * d.bins;
+    const int64_t one = (int64_t)d.n * d.bins, plane = (int64_t)d.rows * n_frames, at = (int64_t)row * n_frames + q;
+    float running, E = 0.0f;
+    int32_t w;
+    match_class_begin(running, w);
+    for (int i = 0; i < b.K; i++) {
+        const int k = b.order[i], c = b.order_class[i];
+        if (pos) {
+            float dot;
+            if (i == 0) match_plain_chains<true>(x, d.templ + k * one, d.n, d.bins, dot, E);
+            else match_plain_chains<false>(x, d.templ + k * one, d.n, d.bins, dot, E);
+            match_class_take(match_score(dot, E), k, running, w);
+        }
+        if (i + 1 == b.K || b.order_class[i + 1] != c) {
+            scores[c * plane + at] = running;
+            if (which) which[c * plane + at] = w;
+            match_class_begin(running, w);
+        }
+    }
+}
+
+// One detector's matches among the scores of its plane: the body of match_peaks_kernel and, a class a block row, of
+// match_bank_peaks_kernel (which, event_template: the bank's, nullptr otherwise).
+__device__ __forceinline__ void match_peaks_body(const MatchDesc &d, const float *__restrict__ scores, const int32_t *__restrict__ which, int64_t n_frames,
+                                                 uint32_t threshold_key, int S, int64_t *__restrict__ events, int64_t capacity,
+                                                 int64_t *__restrict__ counts, float *__restrict__ event_scores, int32_t *__restrict__ event_template,
+                                                 uint32_t *match_keys, int *wave_sum)
+{
     const int tid = (int)threadIdx.x, det = (int)blockIdx.x;
     int64_t row = det, first = 0, U = n_frames;
     if (d.by_det) {
@@ -264,6 +406,7 @@ match_peaks_kernel(MatchDesc d, const float *__restrict__ scores, int64_t n_fram
             if (at < capacity) {
                 events[(int64_t)det * capacity + at] = match_event(d.origin, d.hop, p, d.anchor);
                 if (event_scores) event_scores[(int64_t)det * capacity + at] = s[p];
+                if (event_template) event_template[(int64_t)det * capacity + at] = which[row * n_frames + first + p];
             }
             at++;
         }
@@ -271,6 +414,34 @@ match_peaks_kernel(MatchDesc d, const float *__restrict__ scores, int64_t n_fram
         __syncthreads();                                     // (the keys and wave_sum are the next step's)
     }
     if (tid == 0) counts[det] = total;
+}
+
+__global__ void __launch_bounds__(kThreads)
+match_peaks_kernel(MatchDesc d, const float *__restrict__ scores, int64_t n_frames, uint32_t threshold_key, int S, int64_t *__restrict__ events,
+                   int64_t capacity, int64_t *__restrict__ counts, float *__restrict__ event_scores)
+{
+    extern __shared__ uint32_t match_keys[];
+    __shared__ int wave_sum[kThreads / 64];
+    match_peaks_body(d, scores, nullptr, n_frames, threshold_key, S, events, capacity, counts, event_scores, nullptr, match_keys, wave_sum);
+}
+
+// grid (D, C): class c's plane with class c's threshold into class c's tables; classes do not meet
+__global__ void __launch_bounds__(kThreads)
+match_bank_peaks_kernel(MatchBankDesc b, MatchBankKeys keys, const float *__restrict__ scores, const int32_t *__restrict__ which, int64_t n_frames, int S,
+                        int64_t *__restrict__ events, int64_t capacity, int64_t *__restrict__ counts, float *__restrict__ event_scores,
+                        int32_t *__restrict__ event_template)
+{
+    extern __shared__ uint32_t match_keys[];
+    __shared__ int wave_sum[kThreads / 64];
+    const int c = (int)blockIdx.y;
+    uint32_t key = 0u;
+#pragma unroll
+    for (int e = 0; e < kMatchMaxClasses; e++)
+        if (e == c) key = keys.key[e];
+    const int64_t plane = (int64_t)b.d.rows * n_frames, table = (int64_t)b.d.D * capacity;
+    match_peaks_body(b.d, scores + c * plane, which ? which + c * plane : nullptr, n_frames, key, S, events + c * table, capacity,
+                     counts + (int64_t)c * b.d.D, event_scores ? event_scores + c * table : nullptr,
+                     event_template ? event_template + c * table : nullptr, match_keys, wave_sum);
 }
 
 }  // namespace
@@ -309,6 +480,38 @@ hipError_t launch_match_peaks(const MatchDesc &d, const float *scores, int64_t n
     const size_t lds = 2 * (size_t)(kMatchChunk + 2 * separation) * sizeof(uint32_t);
     hipLaunchKernelGGL(match_peaks_kernel, dim3((unsigned)d.D), dim3(kThreads), lds, stream, d, scores, n_frames, match_key(threshold), separation,
                        events, capacity, counts, event_scores);
+    return hipGetLastError();
+}
+
+hipError_t match_bank_prepare()
+{
+    return hipFuncSetAttribute((const void *)match_bank_peaks_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
+                               2 * (kMatchChunk + 2 * kMatchMaxSeparation) * (int)sizeof(uint32_t));
+}
+
+hipError_t launch_match_bank_scores(const MatchBankDesc &b, const float *columns, int64_t n_frames, int64_t row_stride, float *scores, int32_t *which,
+                                    hipStream_t stream)
+{
+    if (n_frames <= 0 || b.d.rows <= 0) return hipSuccess;
+    const dim3 grid((unsigned)((n_frames + kMatchTile - 1) / kMatchTile), (unsigned)b.d.rows);
+    if (b.d.matrix)
+        hipLaunchKernelGGL(match_bank_scores_mfma_kernel, grid, dim3(kThreads), (size_t)b.d.lds_bytes, stream, b, columns, n_frames, row_stride, scores,
+                           which);
+    else
+        hipLaunchKernelGGL(match_bank_scores_plain_kernel, grid, dim3(kThreads), 0, stream, b, columns, n_frames, row_stride, scores, which);
+    return hipGetLastError();
+}
+
+hipError_t launch_match_bank_peaks(const MatchBankDesc &b, const float *scores, const int32_t *which, int64_t n_frames, const float *thresholds,
+                                   int separation, int64_t *events, int64_t capacity, int64_t *counts, float *event_scores, int32_t *event_template,
+                                   hipStream_t stream)
+{
+    if (b.d.D <= 0) return hipSuccess;
+    MatchBankKeys keys{};
+    for (int c = 0; c < b.C; c++) keys.key[c] = match_key(thresholds[c]);
+    const size_t lds = 2 * (size_t)(kMatchChunk + 2 * separation) * sizeof(uint32_t);
+    hipLaunchKernelGGL(match_bank_peaks_kernel, dim3((unsigned)b.d.D, (unsigned)b.C), dim3(kThreads), lds, stream, b, keys, scores, which, n_frames,
+                       separation, events, capacity, counts, event_scores, event_template);
     return hipGetLastError();
 }
 

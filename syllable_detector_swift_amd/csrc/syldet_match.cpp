@@ -1,24 +1,41 @@
 // syldet_match.cpp -- template matching (include/syldet.h, "template matching"; kernels_match.hip): the matcher that keeps the
 // normalised template and a packed plan's detectors on the device, so that syldet_match_scores_device and
 // syldet_match_peaks_device are launches only; and the host functions (match_peaks.hpp: the rule the kernel runs).
+// A bank of templates (syldet_matcher_bank_*, "template matching: a bank of templates") is the same matcher with K templates and a
+// class table on the device; match_classes.hpp holds the rule of a class's score.
 
 #include <limits>
 
+#include "match_classes.hpp"
 #include "match_peaks.hpp"
 #include "syldet_handle.hpp"
 
-static_assert(SYLDET_MATCH_MAX_TEMPLATE == sd::kMatchMaxTemplate && SYLDET_MATCH_MAX_SEPARATION == sd::kMatchMaxSeparation,
+static_assert(SYLDET_MATCH_MAX_TEMPLATE == sd::kMatchMaxTemplate && SYLDET_MATCH_MAX_SEPARATION == sd::kMatchMaxSeparation &&
+                  SYLDET_MATCH_MAX_TEMPLATES == sd::kMatchMaxTemplates && SYLDET_MATCH_MAX_CLASSES == sd::kMatchMaxClasses,
               "the header's limits are the kernels'");
 
-struct syldet_matcher {
+// what a matcher and a bank of templates share: the bank, the packed plan and the kernels' plan
+struct MatcherCore {
     syldet_t *h = nullptr;                   // the bank (it outlives the matcher): its profile
     sd::BankInfo bank{};
     bool packed = false;
     int D = 0;
     int64_t row_frames = 0;                  // (packed) what n_frames must be
-    std::vector<float> templ;                // t^ [n][bins]
-    sd::DeviceBuffer d_fixed;                // t^ | by_det [D] | by_row [D] | row_begin [rows + 1]
+    std::vector<float> templ;                // t^ [n][bins]; a bank of templates: [K][n][bins]
+    sd::DeviceBuffer d_fixed;                // t^ | (a bank's tables) | by_det [D] | by_row [D] | row_begin [rows + 1]
     sd::MatchDesc desc{};
+    ~MatcherCore()
+    {
+        if (d_fixed.ptr) (void)hipSetDevice(bank.device);
+        d_fixed.release();
+    }
+};
+
+struct syldet_matcher : MatcherCore {};
+
+struct syldet_matcher_bank : MatcherCore {
+    std::vector<int32_t> tclass;             // [K]
+    sd::MatchBankDesc b{};
 };
 
 namespace {
@@ -57,17 +74,11 @@ int peaks_args(float threshold, int32_t separation, int64_t capacity)
 
 size_t up16(size_t n) { return (n + 15) / 16 * 16; }
 
-}  // namespace
-
-extern "C" {
-
-int syldet_matcher_create(const syldet_t *h, const syldet_recordings_t *r, const float *templ, int32_t n, int32_t bins, int32_t anchor,
-                          syldet_matcher_t **out)
+// Everything of a matcher behind its arguments' own rules: the bank's checks, t^ of each of the K templates, the packed plan, the
+// kernels' plan, and t^ | tables | by_det | by_row | row_begin on the device (*d_tables: where `tables` lies there).
+int core_create(MatcherCore *m, const syldet_t *h, const syldet_recordings_t *r, const float *templates, int K, int32_t n, int32_t bins, int32_t anchor,
+                const std::vector<int32_t> &tables, const int32_t **d_tables)
 {
-    if (!out) return fail(SYLDET_ERR_INVALID_ARGUMENT, "NULL argument");
-    *out = nullptr;
-    if (!h) return fail(SYLDET_ERR_INVALID_ARGUMENT, "NULL handle");
-    if (int st = template_args(templ, n, bins)) return st;
     if (h->classes.size() > 1) return fail(SYLDET_ERR_UNSUPPORTED, "columns of a mixed bank: its classes' columns are ragged");
     sd::BankInfo b{};
     sd::bank_info(h, &b);
@@ -80,14 +91,14 @@ int syldet_matcher_create(const syldet_t *h, const syldet_recordings_t *r, const
     if (r)
         if (int st = syldet_recordings_shape(r, &D, &row_samples, nullptr, nullptr)) return st;
 
-    std::unique_ptr<syldet_matcher, int (*)(syldet_matcher_t *)> m(nullptr, syldet_matcher_destroy);
     std::vector<sd::MatchDetDev> by_det, by_row;
     std::vector<int32_t> row_begin;
+    const size_t one = (size_t)n * bins;
     try {
-        m.reset(new syldet_matcher());
         m->bank = b;
-        m->templ.assign((size_t)n * bins, 0.0f);
-        if (int st = normalise(templ, n, bins, m->templ.data())) return st;
+        m->templ.assign((size_t)K * one, 0.0f);
+        for (int k = 0; k < K; k++)
+            if (int st = normalise(templates + (size_t)k * one, n, bins, m->templ.data() + (size_t)k * one)) return st;
         if (r) {
             m->row_frames = std::max<int64_t>(0, sd::count_frames(b.geom, b.window_length, row_samples));
             std::vector<syldet_slot_t> plan((size_t)D);
@@ -130,31 +141,67 @@ int syldet_matcher_create(const syldet_t *h, const syldet_recordings_t *r, const
     if (const char *e = std::getenv("SYLDET_MATCH_PLAIN"))
         if (e[0] == '1') d.matrix = 0;
 
-    const size_t n_t = up16(m->templ.size() * sizeof(float)), n_d = up16(by_det.size() * sizeof(sd::MatchDetDev)),
-                 n_r = up16(row_begin.size() * sizeof(int32_t));
+    const size_t n_t = up16(m->templ.size() * sizeof(float)), n_x = up16(tables.size() * sizeof(int32_t)),
+                 n_d = up16(by_det.size() * sizeof(sd::MatchDetDev)), n_r = up16(row_begin.size() * sizeof(int32_t));
     SYLDET_HIP(hipSetDevice(b.device));
     SYLDET_HIP(sd::match_prepare());
-    if (int st = m->d_fixed.reserve(n_t + 2 * n_d + n_r + 16)) return st;
+    if (d_tables) SYLDET_HIP(sd::match_bank_prepare());
+    if (int st = m->d_fixed.reserve(n_t + n_x + 2 * n_d + n_r + 16)) return st;
     char *base = (char *)m->d_fixed.ptr;
     SYLDET_HIP(hipMemcpy(base, m->templ.data(), m->templ.size() * sizeof(float), hipMemcpyHostToDevice));
+    if (!tables.empty()) SYLDET_HIP(hipMemcpy(base + n_t, tables.data(), tables.size() * sizeof(int32_t), hipMemcpyHostToDevice));
+    char *plan = base + n_t + n_x;
     if (!by_det.empty()) {
-        SYLDET_HIP(hipMemcpy(base + n_t, by_det.data(), by_det.size() * sizeof(sd::MatchDetDev), hipMemcpyHostToDevice));
-        SYLDET_HIP(hipMemcpy(base + n_t + n_d, by_row.data(), by_row.size() * sizeof(sd::MatchDetDev), hipMemcpyHostToDevice));
+        SYLDET_HIP(hipMemcpy(plan, by_det.data(), by_det.size() * sizeof(sd::MatchDetDev), hipMemcpyHostToDevice));
+        SYLDET_HIP(hipMemcpy(plan + n_d, by_row.data(), by_row.size() * sizeof(sd::MatchDetDev), hipMemcpyHostToDevice));
     }
-    if (!row_begin.empty()) SYLDET_HIP(hipMemcpy(base + n_t + 2 * n_d, row_begin.data(), row_begin.size() * sizeof(int32_t), hipMemcpyHostToDevice));
+    if (!row_begin.empty()) SYLDET_HIP(hipMemcpy(plan + 2 * n_d, row_begin.data(), row_begin.size() * sizeof(int32_t), hipMemcpyHostToDevice));
     d.templ = (const float *)base;
-    d.by_det = r ? (const sd::MatchDetDev *)(base + n_t) : nullptr;
-    d.by_row = r ? (const sd::MatchDetDev *)(base + n_t + n_d) : nullptr;
-    d.row_begin = r ? (const int32_t *)(base + n_t + 2 * n_d) : nullptr;
+    if (d_tables) *d_tables = (const int32_t *)(base + n_t);
+    d.by_det = r ? (const sd::MatchDetDev *)plan : nullptr;
+    d.by_row = r ? (const sd::MatchDetDev *)(plan + n_d) : nullptr;
+    d.row_begin = r ? (const int32_t *)(plan + 2 * n_d) : nullptr;
+    return SYLDET_OK;
+}
+
+// what the two scores calls ask of n_frames and row_stride (0: the rows lie end to end)
+int scores_args(const MatcherCore *m, int64_t n_frames, int64_t &row_stride)
+{
+    if (n_frames < 0) return fail(SYLDET_ERR_INVALID_ARGUMENT, "n_frames is negative");
+    if (m->packed && n_frames != m->row_frames)
+        return fail(SYLDET_ERR_INVALID_ARGUMENT, "n_frames must be the packed rows' " + std::to_string(m->row_frames) + " frames");
+    if (n_frames > ((int64_t)1 << 40) / m->desc.bins) return fail(SYLDET_ERR_INVALID_ARGUMENT, "n_frames x bins is above 2^40");
+    if (row_stride == 0) row_stride = n_frames * m->desc.bins;
+    if (row_stride < n_frames * m->desc.bins)
+        return fail(SYLDET_ERR_INVALID_ARGUMENT, "row_stride " + std::to_string(row_stride) + " is below the " + std::to_string(n_frames * m->desc.bins) +
+                                                     " elements of a row");
+    return SYLDET_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int syldet_matcher_create(const syldet_t *h, const syldet_recordings_t *r, const float *templ, int32_t n, int32_t bins, int32_t anchor,
+                          syldet_matcher_t **out)
+{
+    if (!out) return fail(SYLDET_ERR_INVALID_ARGUMENT, "NULL argument");
+    *out = nullptr;
+    if (!h) return fail(SYLDET_ERR_INVALID_ARGUMENT, "NULL handle");
+    if (int st = template_args(templ, n, bins)) return st;
+    std::unique_ptr<syldet_matcher> m;
+    try {
+        m.reset(new syldet_matcher());
+    } catch (const std::bad_alloc &) {
+        return fail(SYLDET_ERR_OUT_OF_MEMORY, "out of memory");
+    }
+    if (int st = core_create(m.get(), h, r, templ, 1, n, bins, anchor, {}, nullptr)) return st;
     *out = m.release();
     return SYLDET_OK;
 }
 
 int syldet_matcher_destroy(syldet_matcher_t *m)
 {
-    if (!m) return SYLDET_OK;
-    if (m->d_fixed.ptr) (void)hipSetDevice(m->bank.device);
-    m->d_fixed.release();
     delete m;
     return SYLDET_OK;
 }
@@ -180,14 +227,7 @@ int syldet_matcher_template(const syldet_matcher_t *m, float *t_hat)
 int syldet_match_scores_device(syldet_matcher_t *m, const float *d_columns, int64_t n_frames, int64_t row_stride, float *d_scores, void *hip_stream)
 {
     if (!m) return fail(SYLDET_ERR_INVALID_ARGUMENT, "NULL handle");
-    if (n_frames < 0) return fail(SYLDET_ERR_INVALID_ARGUMENT, "n_frames is negative");
-    if (m->packed && n_frames != m->row_frames)
-        return fail(SYLDET_ERR_INVALID_ARGUMENT, "n_frames must be the packed rows' " + std::to_string(m->row_frames) + " frames");
-    if (n_frames > ((int64_t)1 << 40) / m->desc.bins) return fail(SYLDET_ERR_INVALID_ARGUMENT, "n_frames x bins is above 2^40");
-    if (row_stride == 0) row_stride = n_frames * m->desc.bins;
-    if (row_stride < n_frames * m->desc.bins)
-        return fail(SYLDET_ERR_INVALID_ARGUMENT, "row_stride " + std::to_string(row_stride) + " is below the " + std::to_string(n_frames * m->desc.bins) +
-                                                     " elements of a row");
+    if (int st = scores_args(m, n_frames, row_stride)) return st;
     if (n_frames > 0 && (!d_columns || !d_scores)) return fail(SYLDET_ERR_INVALID_ARGUMENT, "NULL argument");
     if (n_frames == 0) return SYLDET_OK;
     hipStream_t stream = (hipStream_t)hip_stream;
@@ -213,6 +253,149 @@ int syldet_match_peaks_device(syldet_matcher_t *m, const float *d_scores, int64_
     m->h->prof_begin();
     KernelTimer t(m->h, stream, "match_peaks_kernel");
     SYLDET_HIP(sd::launch_match_peaks(m->desc, d_scores, n_frames, threshold, separation, d_events, capacity, d_counts, d_event_scores, stream));
+    return SYLDET_OK;
+}
+
+// ---- a bank of templates ----
+int syldet_matcher_bank_create(const syldet_t *h, const syldet_recordings_t *r, const float *templates, int32_t n_templates, int32_t n, int32_t bins,
+                               int32_t anchor, const int32_t *template_class, int32_t n_classes, syldet_matcher_bank_t **out)
+{
+    if (!out) return fail(SYLDET_ERR_INVALID_ARGUMENT, "NULL argument");
+    *out = nullptr;
+    if (!h) return fail(SYLDET_ERR_INVALID_ARGUMENT, "NULL handle");
+    if (n_templates < 1 || n_templates > SYLDET_MATCH_MAX_TEMPLATES)
+        return fail(SYLDET_ERR_INVALID_ARGUMENT, std::to_string(n_templates) + " templates are outside [1, " + std::to_string(SYLDET_MATCH_MAX_TEMPLATES) + "]");
+    if (int st = template_args(templates, n, bins)) return st;
+    const int K = n_templates;
+    if (!template_class) {
+        if (n_classes != 0 && n_classes != K)
+            return fail(SYLDET_ERR_INVALID_ARGUMENT, "without a class table there are as many classes as templates (or 0 for that number)");
+        n_classes = K;
+    }
+    if (n_classes < 1 || n_classes > SYLDET_MATCH_MAX_CLASSES)
+        return fail(SYLDET_ERR_INVALID_ARGUMENT, std::to_string(n_classes) + " classes are outside [1, " + std::to_string(SYLDET_MATCH_MAX_CLASSES) + "]");
+    std::unique_ptr<syldet_matcher_bank> m;
+    std::vector<int32_t> tables;
+    try {
+        m.reset(new syldet_matcher_bank());
+        m->tclass.resize((size_t)K);
+        std::vector<int> members((size_t)n_classes, 0);
+        for (int k = 0; k < K; k++) {
+            const int32_t c = template_class ? template_class[k] : k;
+            if (c < 0 || c >= n_classes)
+                return fail(SYLDET_ERR_INVALID_ARGUMENT, "template " + std::to_string(k) + "'s class " + std::to_string(c) + " is outside [0, " +
+                                                             std::to_string(n_classes) + ")");
+            m->tclass[(size_t)k] = c;
+            members[(size_t)c]++;
+        }
+        for (int c = 0; c < n_classes; c++)
+            if (!members[(size_t)c]) return fail(SYLDET_ERR_INVALID_ARGUMENT, "class " + std::to_string(c) + " has no template");
+        // order [K]: the templates class by class, ascending k within a class; then the class of each
+        for (int c = 0; c < n_classes; c++)
+            for (int k = 0; k < K; k++)
+                if (m->tclass[(size_t)k] == c) tables.push_back(k);
+        for (int i = 0; i < K; i++) tables.push_back(m->tclass[(size_t)tables[(size_t)i]]);
+    } catch (const std::bad_alloc &) {
+        return fail(SYLDET_ERR_OUT_OF_MEMORY, "out of memory");
+    }
+    const int32_t *d_tables = nullptr;
+    if (int st = core_create(m.get(), h, r, templates, K, n, bins, anchor, tables, &d_tables)) return st;
+    m->b.d = m->desc;
+    m->b.order = d_tables;
+    m->b.order_class = d_tables + K;
+    m->b.K = K;
+    m->b.C = n_classes;
+    *out = m.release();
+    return SYLDET_OK;
+}
+
+int syldet_matcher_bank_destroy(syldet_matcher_bank_t *m)
+{
+    delete m;
+    return SYLDET_OK;
+}
+
+int syldet_matcher_bank_shape(const syldet_matcher_bank_t *m, int32_t *n_detectors, int32_t *n_templates, int32_t *n_classes, int32_t *n, int32_t *bins,
+                              int32_t *anchor, int32_t *matrix_form)
+{
+    if (!m) return fail(SYLDET_ERR_INVALID_ARGUMENT, "NULL argument");
+    if (n_detectors) *n_detectors = m->D;
+    if (n_templates) *n_templates = m->b.K;
+    if (n_classes) *n_classes = m->b.C;
+    if (n) *n = m->desc.n;
+    if (bins) *bins = m->desc.bins;
+    if (anchor) *anchor = m->desc.anchor;
+    if (matrix_form) *matrix_form = m->desc.matrix;
+    return SYLDET_OK;
+}
+
+int syldet_matcher_bank_templates(const syldet_matcher_bank_t *m, float *t_hat, int32_t *template_class)
+{
+    if (!m) return fail(SYLDET_ERR_INVALID_ARGUMENT, "NULL argument");
+    if (t_hat) std::memcpy(t_hat, m->templ.data(), m->templ.size() * sizeof(float));
+    if (template_class) std::memcpy(template_class, m->tclass.data(), m->tclass.size() * sizeof(int32_t));
+    return SYLDET_OK;
+}
+
+int syldet_match_bank_scores_device(syldet_matcher_bank_t *m, const float *d_columns, int64_t n_frames, int64_t row_stride, float *d_scores,
+                                    int32_t *d_which, void *hip_stream)
+{
+    if (!m) return fail(SYLDET_ERR_INVALID_ARGUMENT, "NULL handle");
+    if (int st = scores_args(m, n_frames, row_stride)) return st;
+    if (n_frames > 0 && (!d_columns || !d_scores)) return fail(SYLDET_ERR_INVALID_ARGUMENT, "NULL argument");
+    if (n_frames == 0) return SYLDET_OK;
+    hipStream_t stream = (hipStream_t)hip_stream;
+    SYLDET_HIP(hipSetDevice(m->bank.device));
+    m->h->prof_begin();
+    KernelTimer t(m->h, stream, m->desc.matrix ? "match_bank_scores_mfma_kernel" : "match_bank_scores_plain_kernel");
+    SYLDET_HIP(sd::launch_match_bank_scores(m->b, d_columns, n_frames, row_stride, d_scores, d_which, stream));
+    return SYLDET_OK;
+}
+
+int syldet_match_bank_peaks_device(syldet_matcher_bank_t *m, const float *d_scores, const int32_t *d_which, int64_t n_frames, const float *thresholds,
+                                   int32_t separation, int64_t *d_events, int64_t capacity, int64_t *d_counts, float *d_event_scores,
+                                   int32_t *d_event_template, void *hip_stream)
+{
+    if (!m) return fail(SYLDET_ERR_INVALID_ARGUMENT, "NULL handle");
+    if (!thresholds) return fail(SYLDET_ERR_INVALID_ARGUMENT, "NULL thresholds");
+    for (int c = 0; c < m->b.C; c++)
+        if (int st = peaks_args(thresholds[c], separation, capacity)) return st;
+    if (d_event_template && !d_which) return fail(SYLDET_ERR_INVALID_ARGUMENT, "d_event_template needs d_which");
+    if (n_frames < 0) return fail(SYLDET_ERR_INVALID_ARGUMENT, "n_frames is negative");
+    if (m->packed && n_frames != m->row_frames)
+        return fail(SYLDET_ERR_INVALID_ARGUMENT, "n_frames must be the packed rows' " + std::to_string(m->row_frames) + " frames");
+    if (m->D > 0 && (!d_counts || (n_frames > 0 && !d_scores) || (capacity > 0 && !d_events))) return fail(SYLDET_ERR_INVALID_ARGUMENT, "NULL argument");
+    if (m->D == 0) return SYLDET_OK;
+    hipStream_t stream = (hipStream_t)hip_stream;
+    SYLDET_HIP(hipSetDevice(m->bank.device));
+    m->h->prof_begin();
+    KernelTimer t(m->h, stream, "match_bank_peaks_kernel");
+    SYLDET_HIP(sd::launch_match_bank_peaks(m->b, d_scores, d_which, n_frames, thresholds, separation, d_events, capacity, d_counts, d_event_scores,
+                                           capacity > 0 ? d_event_template : nullptr, stream));
+    return SYLDET_OK;
+}
+
+int syldet_match_classes_host(const float *template_scores, int64_t n_positions, int32_t n_templates, const int32_t *template_class, int32_t n_classes,
+                              float *class_scores, int32_t *which)
+{
+    if (n_templates < 1 || n_templates > SYLDET_MATCH_MAX_TEMPLATES)
+        return fail(SYLDET_ERR_INVALID_ARGUMENT, std::to_string(n_templates) + " templates are outside [1, " + std::to_string(SYLDET_MATCH_MAX_TEMPLATES) + "]");
+    if (!template_class) {
+        if (n_classes != 0 && n_classes != n_templates)
+            return fail(SYLDET_ERR_INVALID_ARGUMENT, "without a class table there are as many classes as templates (or 0 for that number)");
+        n_classes = n_templates;
+    }
+    if (n_classes < 1 || n_classes > SYLDET_MATCH_MAX_CLASSES)
+        return fail(SYLDET_ERR_INVALID_ARGUMENT, std::to_string(n_classes) + " classes are outside [1, " + std::to_string(SYLDET_MATCH_MAX_CLASSES) + "]");
+    if (n_positions < 0 || (n_positions > 0 && (!template_scores || !class_scores))) return fail(SYLDET_ERR_INVALID_ARGUMENT, "a NULL array or a negative count");
+    uint32_t members = 0;
+    for (int k = 0; k < n_templates; k++) {
+        const int32_t c = template_class ? template_class[k] : k;
+        if (c < 0 || c >= n_classes) return fail(SYLDET_ERR_INVALID_ARGUMENT, "template " + std::to_string(k) + "'s class is outside [0, " + std::to_string(n_classes) + ")");
+        members |= 1u << c;
+    }
+    if (members != (1u << n_classes) - 1u) return fail(SYLDET_ERR_INVALID_ARGUMENT, "a class has no template");
+    sd::match_classes(template_scores, n_positions, n_templates, template_class, n_classes, class_scores, which);
     return SYLDET_OK;
 }
 

@@ -964,6 +964,11 @@ class SyllableDetector:
         (default: its last, n - 1)."""
         return Matcher(self, template, anchor)
 
+    def matcherBank(self, templates, classes=None, anchor: Optional[int] = None) -> "MatcherBank":
+        """A MatcherBank over this bank's channels (syldet_matcher_bank_create): `templates` [K, n, bins] in classes (`classes`
+        [K], None: template k is class k) matched in one pass; a class's score is the greatest of its templates' scores."""
+        return MatcherBank(self, templates, classes, anchor)
+
     # ---- batch, host arrays -------------------------------------------------------
     def runHost(self, samples: np.ndarray, outputs: Optional[np.ndarray] = None, flags: Optional[np.ndarray] = None) -> Tuple[np.ndarray, np.ndarray]:
         """syldet_run: the batch call on host arrays, pipelined along time inside the library.  `outputs` / `flags`: arrays to
@@ -1504,6 +1509,10 @@ class Recordings:
         The columns are spectrogram(rows)."""
         return Matcher(self.detector, template, anchor, recordings=self)
 
+    def matcherBank(self, templates, classes=None, anchor: Optional[int] = None) -> "MatcherBank":
+        """A MatcherBank whose detectors are these recordings (SyllableDetector.matcherBank, Recordings.matcher)."""
+        return MatcherBank(self.detector, templates, classes, anchor, recordings=self)
+
 
 def _score_args(thresholds, labels):
     thr = np.ascontiguousarray(thresholds, dtype=np.float64).reshape(-1)
@@ -1912,6 +1921,159 @@ class Matcher:
             c = cnt.cpu().numpy()
         ev, es = ev.cpu().numpy(), es.cpu().numpy()
         return [ev[d, :c[d]].copy() for d in range(self.count)], [es[d, :c[d]].copy() for d in range(self.count)]
+
+
+class MatcherBank:
+    """A bank of templates (syldet_matcher_bank_*, include/syldet.h "template matching: a bank of templates"): K templates [K, n,
+    bins] in C classes matched in one pass.  Template k's score has the bits of Matcher(template k)'s; a class's score is the
+    greatest of its templates', `which` the lowest template that attains it (-1 where the score is NaN).  classes: the class of
+    each template (None: template k is class k).  shape = (detectors, templates, classes, frames, bins, anchor); templates: the
+    normalised templates; classes: the class table; form: "matrix" or "plain".  The detector (and the Recordings) must outlive
+    it."""
+
+    def __init__(self, detector: SyllableDetector, templates, classes=None, anchor: Optional[int] = None, recordings: Optional[Recordings] = None):
+        self.detector = detector
+        self.recordings = recordings
+        t = np.asarray(templates)
+        if t.ndim != 3 or t.dtype.kind != "f":
+            raise ValueError("the templates must be a float array [templates, frames, bins]")
+        t = np.ascontiguousarray(t, dtype=np.float32)
+        cls, n_classes = None, 0
+        if classes is not None:
+            cls = np.ascontiguousarray(classes, dtype=np.int32).reshape(-1)
+            if cls.size != t.shape[0]:
+                raise ValueError("one class per template")
+            n_classes = int(cls.max()) + 1 if cls.size else 0
+        self._h = _abi.Handle()
+        check(_abi.lib.syldet_matcher_bank_create(detector._h, None if recordings is None else recordings._h, t.ctypes.data_as(_abi.c_float_p),
+                                                  t.shape[0], t.shape[1], t.shape[2], -1 if anchor is None else int(anchor),
+                                                  None if cls is None else cls.ctypes.data_as(_abi.c_int32_p), n_classes, C.byref(self._h)))
+        d, k, c, n, b, a, mf = (C.c_int32() for _ in range(7))
+        check(_abi.lib.syldet_matcher_bank_shape(self._h, C.byref(d), C.byref(k), C.byref(c), C.byref(n), C.byref(b), C.byref(a), C.byref(mf)))
+        self.shape = (d.value, k.value, c.value, n.value, b.value, a.value)
+        self.count, self.nTemplates, self.nClasses, self.frames, self.bins, self.anchor = self.shape
+        self.form = "matrix" if mf.value else "plain"
+        self.templates = np.empty((k.value, n.value, b.value), np.float32)
+        self.classes = np.empty(k.value, np.int32)
+        check(_abi.lib.syldet_matcher_bank_templates(self._h, self.templates.ctypes.data_as(_abi.c_float_p), self.classes.ctypes.data_as(_abi.c_int32_p)))
+
+    def close(self):
+        if getattr(self, "_h", None):
+            _abi.lib.syldet_matcher_bank_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def _thresholds(self, thresholds):
+        t = np.ascontiguousarray(thresholds, dtype=np.float32).reshape(-1)
+        if t.size == 1:
+            t = np.full(self.nClasses, t[0], np.float32)             # a scalar: the same value for every class
+        if t.size != self.nClasses:
+            raise ValueError("one threshold, or one per class")
+        return t
+
+    def scores(self, cols, which: bool = False, out=None, stream=None):
+        """cols [channels, n_frames, bins] as Matcher.scores takes them -> the class scores [C, channels, n_frames] float32, or with
+        which=True (scores, which [C, channels, n_frames] int32).  out: a tensor for the scores, or with which=True a pair.  One
+        launch for any K and C.  Asynchronous on `stream`."""
+        torch = _torch()
+        det = self.detector
+        if not (cols.is_cuda and cols.dtype == torch.float32 and cols.device.index == det.device and cols.dim() == 3
+                and cols.shape[0] == det.channels and cols.shape[2] == self.bins):
+            raise ValueError("cols must be a float32 CUDA tensor [channels, n_frames, %d] on the detector's device" % self.bins)
+        J = int(cols.shape[1])
+        if J > 0 and not (cols.stride(2) == 1 and cols.stride(1) == self.bins):
+            raise ValueError("the frames of a row of cols must be contiguous")
+        row_stride = int(cols.stride(0)) if (det.channels > 1 and J > 0) else 0
+        want = (self.nClasses, det.channels, J)
+        out_s, out_w = (out if which else (out, None)) if out is not None else (None, None)
+        if out_s is None:
+            out_s = torch.empty(want, dtype=torch.float32, device=cols.device)
+        elif not (out_s.is_cuda and out_s.dtype == torch.float32 and tuple(out_s.shape) == want and out_s.is_contiguous() and out_s.device == cols.device):
+            raise ValueError("out must be a contiguous float32 CUDA tensor of shape %s on the columns' device" % (want,))
+        if which:
+            if out_w is None:
+                out_w = torch.empty(want, dtype=torch.int32, device=cols.device)
+            elif not (out_w.is_cuda and out_w.dtype == torch.int32 and tuple(out_w.shape) == want and out_w.is_contiguous() and out_w.device == cols.device):
+                raise ValueError("which must be a contiguous int32 CUDA tensor of shape %s on the columns' device" % (want,))
+        check(_abi.lib.syldet_match_bank_scores_device(self._h, cols.data_ptr() if J else None, J, row_stride, out_s.data_ptr() if J else None,
+                                                       out_w.data_ptr() if (which and J) else None, det._stream_ptr(stream)))
+        return (out_s, out_w) if which else out_s
+
+    def peaks(self, scores, thresholds, separation: int, capacity: Optional[int] = None, which=None, withScores: bool = True, stream=None):
+        """scores [C, channels, n_frames] as scores() made them -> (events [C, D, capacity] int64, counts [C, D] int64, eventScores
+        [C, D, capacity] float32 or None, eventTemplates [C, D, capacity] int32 or None): every class's tables as Matcher.peaks makes
+        them from that class's plane with that class's threshold (a scalar: the same for all); classes do not suppress each other.
+        which: scores()'s second tensor, for eventTemplates.  One launch."""
+        torch = _torch()
+        det = self.detector
+        Cn = self.nClasses
+        if not (scores.is_cuda and scores.dtype == torch.float32 and scores.dim() == 3 and scores.shape[0] == Cn and scores.shape[1] == det.channels
+                and scores.is_contiguous() and scores.device.index == det.device):
+            raise ValueError("scores must be a contiguous float32 CUDA tensor [classes, channels, n_frames] on the detector's device")
+        if which is not None and not (which.is_cuda and which.dtype == torch.int32 and tuple(which.shape) == tuple(scores.shape) and which.is_contiguous()
+                                      and which.device == scores.device):
+            raise ValueError("which must be a contiguous int32 CUDA tensor of the scores' shape on their device")
+        thr = self._thresholds(thresholds)
+        cap = 1024 if capacity is None else int(capacity)
+        D = self.count
+        events = torch.empty((Cn, D, max(cap, 0)), dtype=torch.int64, device=scores.device)
+        counts = torch.empty((Cn, D), dtype=torch.int64, device=scores.device)
+        ev_scores = torch.empty((Cn, D, max(cap, 0)), dtype=torch.float32, device=scores.device) if withScores else None
+        ev_templ = torch.empty((Cn, D, max(cap, 0)), dtype=torch.int32, device=scores.device) if which is not None else None
+        J = int(scores.shape[2])
+        check(_abi.lib.syldet_match_bank_peaks_device(self._h, scores.data_ptr() if J else None, which.data_ptr() if (which is not None and J) else None,
+                                                      J, thr.ctypes.data_as(_abi.c_float_p), int(separation),
+                                                      events.data_ptr() if events.numel() else None, cap, counts.data_ptr() if D else None,
+                                                      ev_scores.data_ptr() if (withScores and ev_scores.numel()) else None,
+                                                      ev_templ.data_ptr() if (ev_templ is not None and ev_templ.numel() and J) else None,
+                                                      det._stream_ptr(stream)))
+        return events, counts, ev_scores, ev_templ
+
+    def find(self, cols, thresholds, separation: int, stream=None):
+        """scores() and peaks() -> (events, eventScores, eventTemplates): three lists with, a class, a list with one array a
+        detector (int64, float32, int32), every match of it (the tables are made again with the largest count as capacity where the
+        first capacity was too small)."""
+        s, w = self.scores(cols, which=True, stream=stream)
+        ev, cnt, es, et = self.peaks(s, thresholds, separation, which=w, stream=stream)
+        c = cnt.cpu().numpy()
+        if c.size and int(c.max()) > ev.shape[2]:
+            ev, cnt, es, et = self.peaks(s, thresholds, separation, capacity=int(c.max()), which=w, stream=stream)
+            c = cnt.cpu().numpy()
+        ev, es, et = ev.cpu().numpy(), es.cpu().numpy(), et.cpu().numpy()
+        per = lambda a: [[a[k, d, :c[k, d]].copy() for d in range(self.count)] for k in range(self.nClasses)]
+        return per(ev), per(es), per(et)
+
+
+def matchClassesHost(templateScores, classes=None):
+    """syldet_match_classes_host: template scores [K, positions] float32 -> (class scores [C, positions] float32, which [C,
+    positions] int32): a class's score is the greatest of its templates', taken in ascending k and replaced only where greater, so
+    which is the lowest template that attains it, -1 where every one is NaN.  classes None: template k is class k."""
+    s = np.ascontiguousarray(templateScores, dtype=np.float32)
+    if s.ndim != 2:
+        raise ValueError("templateScores must be [templates, positions]")
+    cls, Cn = None, s.shape[0]
+    if classes is not None:
+        cls = np.ascontiguousarray(classes, dtype=np.int32).reshape(-1)
+        if cls.size != s.shape[0]:
+            raise ValueError("one class per template")
+        Cn = int(cls.max()) + 1 if cls.size else 0
+    out = np.empty((max(Cn, 0), s.shape[1]), np.float32)
+    which = np.empty((max(Cn, 0), s.shape[1]), np.int32)
+    check(_abi.lib.syldet_match_classes_host(s.ctypes.data_as(_abi.c_float_p), s.shape[1], s.shape[0],
+                                             None if cls is None else cls.ctypes.data_as(_abi.c_int32_p), Cn if cls is not None else 0,
+                                             out.ctypes.data_as(_abi.c_float_p), which.ctypes.data_as(_abi.c_int32_p)))
+    return out, which
 
 
 def matchNormalizeHost(template):
