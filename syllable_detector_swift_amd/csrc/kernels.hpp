@@ -6,6 +6,8 @@
 
 #include <cstdint>
 
+#include "detector_spans.hpp"
+
 namespace sd {
 
 constexpr int kMaxFns = 8;
@@ -495,13 +497,13 @@ hipError_t launch_recordings_levels_out(const RecLevelsDesc &d, int C, const flo
 
 // ---- threshold calibration (kernels_score.hip; syldet_score_device of include/syldet.h) ----
 // What a scorer keeps on the device.  A detector is a channel (slots == nullptr: its evaluations are row `det`) or a recording
-// (slots [D]: its own part of its row).
+// (slots [D], detector_spans.hpp in evaluations: its own part of its row).
 struct ScoreDesc {
     const float *thresholds;                 // [K] the smallest float >= each threshold (score_scan.hpp)
     const float *group_least;                // [ceil(K / 64)] the least of each group of 64
     const int64_t *labels;                   // every detector's sorted labels, end to end
     const int64_t *label_begin;              // [D + 1] detector d's labels are [label_begin[d], label_begin[d + 1])
-    const RecEventDev *slots;
+    const DetSpan *slots;
     int K;
     int64_t tolerance, debounce_frames;
 };
@@ -510,14 +512,9 @@ hipError_t launch_score(const ScoreDesc &d, int D, const float *outputs, int64_t
                         int64_t hop, int64_t *table, hipStream_t stream);
 
 // ---- event-aligned windows (kernels_align.hip; syldet_align_device and syldet_align_stats_device of include/syldet.h) ----
-// A detector of a packed plan: its unit 0 is unit `base` of row `row`, and it has `units` units.
-struct AlignDetDev {
-    int64_t base, units;
-    int32_t row, pad;
-};
 // What an aligner keeps on the device for the windows.  dets == nullptr: detector d is row d, from unit 0, with the call's n_units.
 struct AlignDesc {
-    const AlignDetDev *dets;                 // [D]
+    const DetSpan *dets;                     // [D] a packed plan's detectors in the source's unit (detector_spans.hpp)
     const int64_t *event_begin;              // [D + 1] the kept prefix
     int2 *spans;                             // [N] each window's present elements (first, count): what the statistics count by
     int D, width;
@@ -544,14 +541,8 @@ hipError_t launch_align_stats(const AlignStatsDesc &d, const float *windows, int
 hipError_t launch_align_combine(const AlignStatsDesc &d, int L, int64_t *count, double *sum, double *sumsq, hipStream_t stream);
 
 // ---- training (kernels_train.hip; syldet_train_targets_device and syldet_train_gradient_device of include/syldet.h) ----
-// A detector of a packed plan as the targets kernel finds it: the table is sorted by (row, first_eval), row c's detectors are
-// [row_begin[c], row_begin[c + 1]).
-struct TrainDetDev {
-    int64_t first_eval, n_evals;
-    int32_t det, row;                        // the recording (the caller's order) and its bank row
-};
 struct TrainTargetsDesc {
-    const TrainDetDev *dets;                 // packed plans; nullptr: detector c is row c, all of it
+    const DetSpan *dets;                     // packed plans: the by_row table in evaluations (detector_spans.hpp); nullptr: detector c is row c, all of it
     const int32_t *row_begin;                // [rows + 1]
     const int64_t *labels;                   // every detector's sorted labels, end to end
     const int64_t *label_begin;              // [D + 1]
@@ -621,17 +612,12 @@ hipError_t launch_train_adam_multi(const TrainAdamStep &k, int P, int n_nets, co
                                    double *mean_loss, hipStream_t stream);
 
 // ---- template matching (kernels_match.hip; syldet_match_scores_device and syldet_match_peaks_device of include/syldet.h) ----
-// A detector of a packed plan: its frame 0 is frame `first` of row `row`, and it has `units` frames.
-struct MatchDetDev {
-    int64_t first, units;
-    int32_t det, row;
-};
 constexpr int kMatchTile = 256;              // positions a workgroup of the score kernels takes
 constexpr int kMatchChunk = 2048;            // positions a step of the peaks kernel takes
 struct MatchDesc {
-    const MatchDetDev *by_row;               // packed plans: sorted by (row, first), row c's detectors are [row_begin[c], row_begin[c + 1]);
+    const DetSpan *by_row;                   // packed plans: the by_row table in frames (detector_spans.hpp), row c's detectors are [row_begin[c], row_begin[c + 1]);
     const int32_t *row_begin;                //   nullptr: detector c is row c, all of it
-    const MatchDetDev *by_det;               // packed plans: [D] in the caller's order
+    const DetSpan *by_det;                   // packed plans: [D] in the caller's order
     const float *templ;                      // t^ [n][bins]
     int rows, D, n, bins, anchor;
     int64_t origin, hop;

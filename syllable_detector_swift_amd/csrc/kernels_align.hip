@@ -69,9 +69,9 @@ align_windows_kernel(AlignDesc d, const float *__restrict__ src, int64_t n_units
         }
         int64_t row = det, base = 0, U = n_units;
         if (d.dets) {
-            const AlignDetDev e = d.dets[det];
+            const DetSpan e = d.dets[det];
             row = e.row;
-            base = e.base;
+            base = e.first;
             U = e.units;
         }
         const int64_t s = events[event_stride ? (int64_t)det * event_stride + (w - begin) : w];

@@ -49,15 +49,9 @@ __device__ __forceinline__ bool finite_bits(float v) { return (__float_as_uint(v
 __device__ __forceinline__ bool match_position(const MatchDesc &d, int row, int64_t q, int64_t n_frames)
 {
     if (!d.by_row) return q + d.n <= n_frames;
-    int lo = d.row_begin[row], hi = d.row_begin[row + 1];
-    const int begin = lo;
-    while (lo < hi) {                                        // the first detector that starts behind q
-        const int mid = (lo + hi) >> 1;
-        if (d.by_row[mid].first <= q) lo = mid + 1;
-        else hi = mid;
-    }
-    if (lo == begin) return false;
-    const MatchDetDev e = d.by_row[lo - 1];
+    const int at = span_at_or_before(d.by_row, d.row_begin, row, q);
+    if (at < 0) return false;
+    const DetSpan e = d.by_row[at];
     return q + d.n <= e.first + e.units;
 }
 
@@ -351,7 +345,7 @@ __device__ __forceinline__ void match_peaks_body(const MatchDesc &d, const float
     const int tid = (int)threadIdx.x, det = (int)blockIdx.x;
     int64_t row = det, first = 0, U = n_frames;
     if (d.by_det) {
-        const MatchDetDev e = d.by_det[det];
+        const DetSpan e = d.by_det[det];
         row = e.row;
         first = e.first;
         U = e.units;

@@ -32,9 +32,9 @@ score_kernel(ScoreDesc d, const float *__restrict__ outputs, int64_t n_evals, in
     // the detector's evaluations: a channel's row, or a recording's own part of its row
     int64_t base = (int64_t)det * n_evals, E = n_evals;
     if (d.slots) {
-        const RecEventDev s = d.slots[det];
-        base = (int64_t)s.row * n_evals + s.first_eval;
-        E = s.n_evals;
+        const DetSpan s = d.slots[det];
+        base = (int64_t)s.row * n_evals + s.first;
+        E = s.units;
     }
     const int k = g * kWave + lane;
     const float thr = k < d.K ? d.thresholds[k] : __builtin_inff();       // (a lane without a threshold: its row is never written)

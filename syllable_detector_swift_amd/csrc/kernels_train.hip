@@ -28,6 +28,7 @@
 //
 // gfx950 only: wave = 64 lanes.  Plain HIP C++, vector loads and stores, no float atomics.
 
+#include "carve.hpp"
 #include "generic_eval.hpp"
 #include "train_kernels.hpp"
 #include "train_targets.hpp"
@@ -50,18 +51,11 @@ train_targets_kernel(TrainTargetsDesc d, int64_t n_evals, float *__restrict__ ta
     int64_t own = e;
     bool has = true;
     if (d.dets) {
-        // the last detector of the row that starts at or before e
-        int lo = d.row_begin[row], hi = d.row_begin[row + 1];
-        const int first = lo;
-        while (lo < hi) {
-            const int mid = (lo + hi) >> 1;
-            if (d.dets[mid].first_eval <= e) lo = mid + 1;
-            else hi = mid;
-        }
-        has = lo > first && e - d.dets[lo - 1].first_eval < d.dets[lo - 1].n_evals;
+        const int at = span_at_or_before(d.dets, d.row_begin, row, e);
+        has = at >= 0 && e - d.dets[at].first < d.dets[at].units;
         if (has) {
-            det = d.dets[lo - 1].det;
-            own = e - d.dets[lo - 1].first_eval;
+            det = d.dets[at].det;
+            own = e - d.dets[at].first;
         }
     }
     uint32_t mask = 0;

@@ -4,20 +4,9 @@
 
 #include <cstddef>
 
+#include "carve.hpp"
+
 namespace sd {
-
-inline size_t up16(size_t n) { return (n + 15) / 16 * 16; }
-
-// Sections taken one behind the other from one block, each from a multiple of 16 bytes; a section of no bytes takes nothing.
-struct Carver {
-    size_t total = 0;
-    size_t take(size_t bytes)
-    {
-        const size_t at = total;
-        total += up16(bytes);
-        return at;
-    }
-};
 
 // Where every table of a handle of K recordings on C rows of `tiles` tiles begins in the block: every device pointer and every
 // descriptor of the handle is the block's base plus one of these, and a new table is one more take().

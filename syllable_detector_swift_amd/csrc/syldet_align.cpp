@@ -9,14 +9,10 @@ static_assert(SYLDET_ALIGN_COLUMNS == sd::kAlignColumns && SYLDET_ALIGN_OUTPUTS 
               "the header's sources are the span's");
 static_assert(SYLDET_ALIGN_MAX_WINDOW == sd::kAlignMaxWindow && SYLDET_ALIGN_BLOCK == sd::kAlignBlock, "the header's limits are the kernels'");
 
-struct syldet_aligner {
-    syldet_t *h = nullptr;                   // the bank (it outlives the aligner): its profile
-    sd::BankInfo bank{};
-    bool packed = false;
-    int source = 0, D = 0, width = 0;
+struct syldet_aligner : sd::DetectorTable {  // (the spans: units of the source)
+    int source = 0, width = 0;
     int64_t before = 0, after = 0, origin = 0, step = 1;
-    int64_t row_units = 0;                   // (packed) what n_units must be
-    sd::DeviceBuffer d_dets;                 // (packed) AlignDetDev [D]
+    sd::DeviceBuffer d_dets;                 // (packed) the spans
     hipStream_t last = nullptr;              // the stream of the last call that may still read or write the tables below
 
     // the kept event prefix, and what is sized by it
@@ -129,62 +125,27 @@ int syldet_aligner_create(const syldet_t *h, const syldet_recordings_t *r, int32
     int width = 1;
     anchor_of(b, source, &origin, &step, &width);
     if (int st = window_args(source, before, after, width)) return st;
-    int32_t D = b.channels;
-    int64_t row_samples = 0, row_evals = 0;
-    if (r)
-        if (int st = syldet_recordings_shape(r, &D, &row_samples, &row_evals, nullptr)) return st;
+    const sd::SpanUnit unit = source == SYLDET_ALIGN_COLUMNS ? sd::kSpanFrames : source == SYLDET_ALIGN_OUTPUTS ? sd::kSpanEvals : sd::kSpanSamples;
 
     std::unique_ptr<syldet_aligner, int (*)(syldet_aligner_t *)> a(nullptr, syldet_aligner_destroy);
-    std::vector<sd::AlignDetDev> dets;
     try {
         a.reset(new syldet_aligner());
-        a->bank = b;                         // (the deleter sets this device; no call of it is made while nothing is on one)
-        a->begin.assign((size_t)D + 1, 0);
-        a->group.assign((size_t)D, 0);
-        if (r && D > 0) {
-            std::vector<syldet_slot_t> plan((size_t)D);
-            if (int st = syldet_recordings_slots(r, plan.data())) return st;
-            for (const syldet_slot_t &p : plan) {
-                sd::AlignDetDev e{};
-                e.row = p.row;
-                if (source == SYLDET_ALIGN_COLUMNS) {
-                    e.base = p.first_eval;
-                    e.units = std::max<int64_t>(0, sd::count_frames(b.geom, b.window_length, p.n_samples));
-                } else if (source == SYLDET_ALIGN_OUTPUTS) {
-                    e.base = p.first_eval;
-                    e.units = p.n_evals;
-                } else {
-                    e.base = p.offset;
-                    e.units = p.n_samples;
-                }
-                dets.push_back(e);
-            }
-        }
+        if (int st = a->read(h, r, unit)) return st;
+        a->begin.assign((size_t)a->D + 1, 0);
+        a->group.assign((size_t)a->D, 0);
     } catch (const std::bad_alloc &) {
         return fail(SYLDET_ERR_OUT_OF_MEMORY, "out of memory");
     }
-    a->h = const_cast<syldet_t *>(h);
-    a->bank = b;
-    a->packed = r != nullptr;
     a->source = source;
-    a->D = D;
     a->width = width;
     a->before = before;
     a->after = after;
     a->origin = origin;
     a->step = step;
-    if (r) {
-        a->row_units = source == SYLDET_ALIGN_COLUMNS ? std::max<int64_t>(0, sd::count_frames(b.geom, b.window_length, row_samples))
-                       : source == SYLDET_ALIGN_OUTPUTS ? row_evals : row_samples;
-        // (the plan's guarantee, held here once more: no detector reaches beyond its row)
-        for (size_t k = 0; k < dets.size(); k++)
-            if (dets[k].units > 0 && (dets[k].base < 0 || dets[k].base + dets[k].units > a->row_units || dets[k].row < 0 || dets[k].row >= b.channels))
-                return fail(SYLDET_ERR_INVALID_ARGUMENT, "recording " + std::to_string(k) + " reaches beyond its row");
-    }
-    if (!dets.empty()) {
+    if (!a->spans.empty()) {
         SYLDET_HIP(hipSetDevice(b.device));
-        if (int st = a->d_dets.reserve(dets.size() * sizeof(sd::AlignDetDev))) return st;
-        SYLDET_HIP(hipMemcpy(a->d_dets.ptr, dets.data(), dets.size() * sizeof(sd::AlignDetDev), hipMemcpyHostToDevice));
+        if (int st = a->d_dets.reserve(bytes_of(a->spans))) return st;
+        SYLDET_HIP(upload(a->d_dets.ptr, 0, a->spans));
     }
     *out = a.release();
     return SYLDET_OK;
@@ -220,8 +181,7 @@ int syldet_align_device(syldet_aligner_t *a, const float *d_src, int64_t n_units
     const int64_t N = event_begin[a->D], L = a->L();
     if (n_units < 0) return fail(SYLDET_ERR_INVALID_ARGUMENT, "n_units is negative");
     if (N > 0 && ((n_units > 0 && !d_src) || !d_events || !d_windows)) return fail(SYLDET_ERR_INVALID_ARGUMENT, "NULL argument");
-    if (a->packed && n_units != a->row_units)
-        return fail(SYLDET_ERR_INVALID_ARGUMENT, "n_units must be the packed rows' " + std::to_string(a->row_units) + " units of this source");
+    if (int st = a->row_units_arg(n_units, "n_units", "units of this source")) return st;
     if (n_units > ((int64_t)1 << 40) / a->width) return fail(SYLDET_ERR_INVALID_ARGUMENT, "n_units x width is above 2^40");
     if (row_stride == 0) row_stride = n_units * a->width;
     if (row_stride < n_units * a->width)
@@ -250,7 +210,7 @@ int syldet_align_device(syldet_aligner_t *a, const float *d_src, int64_t n_units
     a->last = stream;
     if (N == 0) return SYLDET_OK;
     sd::AlignDesc desc{};
-    desc.dets = a->packed ? (const sd::AlignDetDev *)a->d_dets.ptr : nullptr;
+    desc.dets = a->packed ? (const sd::DetSpan *)a->d_dets.ptr : nullptr;
     desc.event_begin = (const int64_t *)a->d_begin.ptr;
     desc.spans = (int2 *)a->d_spans.ptr;
     desc.D = a->D;

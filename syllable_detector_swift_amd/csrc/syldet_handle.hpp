@@ -18,6 +18,7 @@
 #include <string>
 #include <vector>
 
+#include "carve.hpp"
 #include "fused_plan.hpp"
 #include "kernels.hpp"
 #include "sample_ring.hpp"
@@ -303,6 +304,66 @@ struct Samples {
     Samples(const float *f) : p(f) {}
     Samples(const void *q, bool pcm16) : p(q), s16(pcm16) {}
 };
+
+// What the handles that sit on a bank and, optionally, on a packed-recordings plan share (the scorer, the aligner, the trainer,
+// the matchers): the bank, and the plan's detectors as spans of the handle's unit (detector_spans.hpp).
+struct DetectorTable {
+    syldet *h = nullptr;                     // the bank (it outlives the handle): its profile
+    BankInfo bank{};
+    bool packed = false;
+    int D = 0;                               // detectors: the bank's channels, or (packed) the plan's recordings
+    int64_t row_samples = 0, row_evals = 0;  // (packed) syldet_recordings_shape's
+    int64_t row_units = 0;                   // (packed) a row's length in the spans' unit: what a call's row length must be
+    std::vector<DetSpan> spans;              // (packed) [D] in the caller's order
+
+    // the bank's clock and, of a plan (r may be NULL), its slots in `unit`, held once more to the plan's guarantee that no
+    // recording reaches beyond its row
+    int read(const syldet_t *bank_handle, const syldet_recordings_t *r, SpanUnit unit)
+    {
+        h = const_cast<syldet *>(bank_handle);
+        bank_info(bank_handle, &bank);
+        packed = r != nullptr;
+        D = bank.channels;
+        if (!r) return SYLDET_OK;
+        int32_t K = 0;
+        if (int st = syldet_recordings_shape(r, &K, &row_samples, &row_evals, nullptr)) return st;
+        D = K;
+        row_units = span_row_units(bank, unit, row_samples, row_evals);
+        std::vector<syldet_slot_t> plan((size_t)D);
+        if (D > 0)
+            if (int st = syldet_recordings_slots(r, plan.data())) return st;
+        spans.reserve((size_t)D);
+        for (int k = 0; k < D; k++) spans.push_back(span_of(plan[(size_t)k], k, bank, unit));
+        const int64_t bad = spans_first_beyond(spans.data(), D, bank.channels, row_units);
+        return bad < 0 ? SYLDET_OK : fail(SYLDET_ERR_INVALID_ARGUMENT, "recording " + std::to_string(bad) + " reaches beyond its row");
+    }
+    // a call's row length on a packed plan is the rows': `name` "n_evals", `of` "evaluations"
+    int row_units_arg(int64_t n, const char *name, const char *of) const
+    {
+        return packed && n != row_units ? packed_rows_refusal(name, std::to_string(row_units) + " " + of) : SYLDET_OK;
+    }
+    static int packed_rows_refusal(const char *names, const std::string &lengths)
+    {
+        return fail(SYLDET_ERR_INVALID_ARGUMENT, std::string(names) + " must be the packed rows' " + lengths);
+    }
+};
+
+// One section of a handle's device block (laid out with carve.hpp's Carver): `bytes` from the host to `at` of the block; a section
+// of no bytes copies nothing.
+inline hipError_t upload(void *block, size_t at, const void *from, size_t bytes)
+{
+    return bytes ? hipMemcpy((char *)block + at, from, bytes, hipMemcpyHostToDevice) : hipSuccess;
+}
+template <class T>
+hipError_t upload(void *block, size_t at, const std::vector<T> &from)
+{
+    return upload(block, at, from.data(), from.size() * sizeof(T));
+}
+template <class T>
+size_t bytes_of(const std::vector<T> &v)
+{
+    return v.size() * sizeof(T);
+}
 
 inline bool engine_known(int32_t e) { return e == SYLDET_ENGINE_AUTO || e == SYLDET_ENGINE_GENERIC || e == SYLDET_ENGINE_FUSED || e == SYLDET_ENGINE_WIDE_BF16; }
 // syldet_api.cpp

@@ -15,12 +15,7 @@ static_assert(SYLDET_MATCH_MAX_TEMPLATE == sd::kMatchMaxTemplate && SYLDET_MATCH
               "the header's limits are the kernels'");
 
 // what a matcher and a bank of templates share: the bank, the packed plan and the kernels' plan
-struct MatcherCore {
-    syldet_t *h = nullptr;                   // the bank (it outlives the matcher): its profile
-    sd::BankInfo bank{};
-    bool packed = false;
-    int D = 0;
-    int64_t row_frames = 0;                  // (packed) what n_frames must be
+struct MatcherCore : sd::DetectorTable {     // (the spans: frames)
     std::vector<float> templ;                // t^ [n][bins]; a bank of templates: [K][n][bins]
     sd::DeviceBuffer d_fixed;                // t^ | (a bank's tables) | by_det [D] | by_row [D] | row_begin [rows + 1]
     sd::MatchDesc desc{};
@@ -72,8 +67,6 @@ int peaks_args(float threshold, int32_t separation, int64_t capacity)
     return SYLDET_OK;
 }
 
-size_t up16(size_t n) { return (n + 15) / 16 * 16; }
-
 // Everything of a matcher behind its arguments' own rules: the bank's checks, t^ of each of the K templates, the packed plan, the
 // kernels' plan, and t^ | tables | by_det | by_row | row_begin on the device (*d_tables: where `tables` lies there).
 int core_create(MatcherCore *m, const syldet_t *h, const syldet_recordings_t *r, const float *templates, int K, int32_t n, int32_t bins, int32_t anchor,
@@ -86,48 +79,20 @@ int core_create(MatcherCore *m, const syldet_t *h, const syldet_recordings_t *r,
         return fail(SYLDET_ERR_INVALID_ARGUMENT, "the template has " + std::to_string(bins) + " bins, the bank's columns " + std::to_string(b.geom.bins));
     if (anchor < 0) anchor = n - 1;
     if (anchor >= n) return fail(SYLDET_ERR_INVALID_ARGUMENT, "anchor " + std::to_string(anchor) + " is outside [0, " + std::to_string(n) + ")");
-    int32_t D = b.channels;
-    int64_t row_samples = 0;
-    if (r)
-        if (int st = syldet_recordings_shape(r, &D, &row_samples, nullptr, nullptr)) return st;
 
-    std::vector<sd::MatchDetDev> by_det, by_row;
+    std::vector<sd::DetSpan> by_row;
     std::vector<int32_t> row_begin;
     const size_t one = (size_t)n * bins;
     try {
-        m->bank = b;
         m->templ.assign((size_t)K * one, 0.0f);
         for (int k = 0; k < K; k++)
             if (int st = normalise(templates + (size_t)k * one, n, bins, m->templ.data() + (size_t)k * one)) return st;
-        if (r) {
-            m->row_frames = std::max<int64_t>(0, sd::count_frames(b.geom, b.window_length, row_samples));
-            std::vector<syldet_slot_t> plan((size_t)D);
-            if (D > 0)
-                if (int st = syldet_recordings_slots(r, plan.data())) return st;
-            for (int k = 0; k < D; k++) {
-                const syldet_slot_t &p = plan[(size_t)k];
-                const sd::MatchDetDev e{p.first_eval, std::max<int64_t>(0, sd::count_frames(b.geom, b.window_length, p.n_samples)), k, p.row};
-                if (e.row < 0 || e.row >= b.channels || (e.units > 0 && (e.first < 0 || e.first + e.units > m->row_frames)))
-                    return fail(SYLDET_ERR_INVALID_ARGUMENT, "recording " + std::to_string(k) + " reaches beyond its row");
-                by_det.push_back(e);
-            }
-            // by (row, first): what the score kernels search (a recording without frames in front of one that starts at the same
-            // frame, so that the last detector at or before a frame is the one that holds it)
-            by_row = by_det;
-            std::stable_sort(by_row.begin(), by_row.end(), [](const sd::MatchDetDev &x, const sd::MatchDetDev &y) {
-                if (x.row != y.row) return x.row < y.row;
-                return x.first != y.first ? x.first < y.first : x.units < y.units;
-            });
-            row_begin.assign((size_t)b.channels + 1, 0);
-            for (const sd::MatchDetDev &e : by_row) row_begin[(size_t)e.row + 1]++;
-            for (int c = 0; c < b.channels; c++) row_begin[(size_t)c + 1] += row_begin[(size_t)c];
-        }
+        if (int st = m->read(h, r, sd::kSpanFrames)) return st;
+        if (r) sd::spans_by_row(m->spans, b.channels, &by_row, &row_begin);
     } catch (const std::bad_alloc &) {
         return fail(SYLDET_ERR_OUT_OF_MEMORY, "out of memory");
     }
-    m->h = const_cast<syldet_t *>(h);
-    m->packed = r != nullptr;
-    m->D = D;
+    const int D = m->D;
     sd::MatchDesc &d = m->desc;
     d.rows = b.channels;
     d.D = D;
@@ -141,26 +106,24 @@ int core_create(MatcherCore *m, const syldet_t *h, const syldet_recordings_t *r,
     if (const char *e = std::getenv("SYLDET_MATCH_PLAIN"))
         if (e[0] == '1') d.matrix = 0;
 
-    const size_t n_t = up16(m->templ.size() * sizeof(float)), n_x = up16(tables.size() * sizeof(int32_t)),
-                 n_d = up16(by_det.size() * sizeof(sd::MatchDetDev)), n_r = up16(row_begin.size() * sizeof(int32_t));
+    sd::Carver blob;
+    const size_t at_t = blob.take(bytes_of(m->templ)), at_x = blob.take(bytes_of(tables)), at_det = blob.take(bytes_of(m->spans)),
+                 at_row = blob.take(bytes_of(by_row)), at_begin = blob.take(bytes_of(row_begin));
     SYLDET_HIP(hipSetDevice(b.device));
     SYLDET_HIP(sd::match_prepare());
     if (d_tables) SYLDET_HIP(sd::match_bank_prepare());
-    if (int st = m->d_fixed.reserve(n_t + n_x + 2 * n_d + n_r + 16)) return st;
+    if (int st = m->d_fixed.reserve(blob.total + 16)) return st;
     char *base = (char *)m->d_fixed.ptr;
-    SYLDET_HIP(hipMemcpy(base, m->templ.data(), m->templ.size() * sizeof(float), hipMemcpyHostToDevice));
-    if (!tables.empty()) SYLDET_HIP(hipMemcpy(base + n_t, tables.data(), tables.size() * sizeof(int32_t), hipMemcpyHostToDevice));
-    char *plan = base + n_t + n_x;
-    if (!by_det.empty()) {
-        SYLDET_HIP(hipMemcpy(plan, by_det.data(), by_det.size() * sizeof(sd::MatchDetDev), hipMemcpyHostToDevice));
-        SYLDET_HIP(hipMemcpy(plan + n_d, by_row.data(), by_row.size() * sizeof(sd::MatchDetDev), hipMemcpyHostToDevice));
-    }
-    if (!row_begin.empty()) SYLDET_HIP(hipMemcpy(plan + 2 * n_d, row_begin.data(), row_begin.size() * sizeof(int32_t), hipMemcpyHostToDevice));
-    d.templ = (const float *)base;
-    if (d_tables) *d_tables = (const int32_t *)(base + n_t);
-    d.by_det = r ? (const sd::MatchDetDev *)plan : nullptr;
-    d.by_row = r ? (const sd::MatchDetDev *)(plan + n_d) : nullptr;
-    d.row_begin = r ? (const int32_t *)(plan + 2 * n_d) : nullptr;
+    SYLDET_HIP(upload(base, at_t, m->templ));
+    SYLDET_HIP(upload(base, at_x, tables));
+    SYLDET_HIP(upload(base, at_det, m->spans));
+    SYLDET_HIP(upload(base, at_row, by_row));
+    SYLDET_HIP(upload(base, at_begin, row_begin));
+    d.templ = (const float *)(base + at_t);
+    if (d_tables) *d_tables = (const int32_t *)(base + at_x);
+    d.by_det = r ? (const sd::DetSpan *)(base + at_det) : nullptr;
+    d.by_row = r ? (const sd::DetSpan *)(base + at_row) : nullptr;
+    d.row_begin = r ? (const int32_t *)(base + at_begin) : nullptr;
     return SYLDET_OK;
 }
 
@@ -168,8 +131,7 @@ int core_create(MatcherCore *m, const syldet_t *h, const syldet_recordings_t *r,
 int scores_args(const MatcherCore *m, int64_t n_frames, int64_t &row_stride)
 {
     if (n_frames < 0) return fail(SYLDET_ERR_INVALID_ARGUMENT, "n_frames is negative");
-    if (m->packed && n_frames != m->row_frames)
-        return fail(SYLDET_ERR_INVALID_ARGUMENT, "n_frames must be the packed rows' " + std::to_string(m->row_frames) + " frames");
+    if (int st = m->row_units_arg(n_frames, "n_frames", "frames")) return st;
     if (n_frames > ((int64_t)1 << 40) / m->desc.bins) return fail(SYLDET_ERR_INVALID_ARGUMENT, "n_frames x bins is above 2^40");
     if (row_stride == 0) row_stride = n_frames * m->desc.bins;
     if (row_stride < n_frames * m->desc.bins)
@@ -244,8 +206,7 @@ int syldet_match_peaks_device(syldet_matcher_t *m, const float *d_scores, int64_
     if (!m) return fail(SYLDET_ERR_INVALID_ARGUMENT, "NULL handle");
     if (int st = peaks_args(threshold, separation, capacity)) return st;
     if (n_frames < 0) return fail(SYLDET_ERR_INVALID_ARGUMENT, "n_frames is negative");
-    if (m->packed && n_frames != m->row_frames)
-        return fail(SYLDET_ERR_INVALID_ARGUMENT, "n_frames must be the packed rows' " + std::to_string(m->row_frames) + " frames");
+    if (int st = m->row_units_arg(n_frames, "n_frames", "frames")) return st;
     if (m->D > 0 && (!d_counts || (n_frames > 0 && !d_scores) || (capacity > 0 && !d_events))) return fail(SYLDET_ERR_INVALID_ARGUMENT, "NULL argument");
     if (m->D == 0) return SYLDET_OK;
     hipStream_t stream = (hipStream_t)hip_stream;
@@ -362,8 +323,7 @@ int syldet_match_bank_peaks_device(syldet_matcher_bank_t *m, const float *d_scor
         if (int st = peaks_args(thresholds[c], separation, capacity)) return st;
     if (d_event_template && !d_which) return fail(SYLDET_ERR_INVALID_ARGUMENT, "d_event_template needs d_which");
     if (n_frames < 0) return fail(SYLDET_ERR_INVALID_ARGUMENT, "n_frames is negative");
-    if (m->packed && n_frames != m->row_frames)
-        return fail(SYLDET_ERR_INVALID_ARGUMENT, "n_frames must be the packed rows' " + std::to_string(m->row_frames) + " frames");
+    if (int st = m->row_units_arg(n_frames, "n_frames", "frames")) return st;
     if (m->D > 0 && (!d_counts || (n_frames > 0 && !d_scores) || (capacity > 0 && !d_events))) return fail(SYLDET_ERR_INVALID_ARGUMENT, "NULL argument");
     if (m->D == 0) return SYLDET_OK;
     hipStream_t stream = (hipStream_t)hip_stream;

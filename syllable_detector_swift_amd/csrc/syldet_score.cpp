@@ -1,33 +1,19 @@
 // syldet_score.cpp -- threshold calibration (include/syldet.h, "threshold calibration"): the scorer that keeps thresholds, labels
 // and a packed plan's slots on the device so that syldet_score_device is one launch (kernels_score.hip), the same scan on the
 // host (score_scan.hpp, one threshold after another), and the choice of a threshold from the tables.
-#include <hip/hip_runtime.h>
+#include <limits>
 
-#include <cmath>
-#include <cstring>
-#include <memory>
-#include <new>
-#include <string>
-#include <vector>
-
-#include "kernels.hpp"
 #include "score_scan.hpp"
-#include "syldet_internal.hpp"
-
-using sd::fail;
+#include "syldet_handle.hpp"
 
 static_assert(SYLDET_SCORE_COLUMNS == sd::kScoreColumns && SYLDET_SCORE_DETECTIONS == sd::kScoreDetections && SYLDET_SCORE_HITS == sd::kScoreHits &&
               SYLDET_SCORE_FALSE_POSITIVES == sd::kScoreFalsePositives && SYLDET_SCORE_REPEATS == sd::kScoreRepeats &&
               SYLDET_SCORE_SUM_OFFSET == sd::kScoreSumOffset && SYLDET_SCORE_SUM_OFFSET_SQUARED == sd::kScoreSumOffsetSquared,
               "the header's columns are the scan's");
 
-struct syldet_scorer {
-    sd::BankInfo bank{};
-    bool packed = false;
-    int64_t row_evals = 0;                   // (packed) what n_evals must be
-    int D = 0;
+struct syldet_scorer : sd::DetectorTable {  // (the spans: evaluations)
     int64_t n_labels = 0;
-    void *d_blob = nullptr;                  // thresholds | group_least | label_begin | labels | slots
+    sd::DeviceBuffer d_blob;                 // thresholds | group_least | label_begin | labels | spans
     sd::ScoreDesc desc{};
 };
 
@@ -63,8 +49,6 @@ int check_labels(const int64_t *t, int64_t n, int64_t m, int64_t detector)
     return SYLDET_OK;
 }
 
-size_t up16(size_t n) { return (n + 15) / 16 * 16; }
-
 }  // namespace
 
 extern "C" {
@@ -79,14 +63,17 @@ int syldet_scorer_create(const syldet_t *h, const syldet_recordings_t *r, const 
     if (int st = check_thresholds(thresholds, n_thresholds)) return st;
     if (int st = check_tolerance(tolerance_samples)) return st;
     if (!label_begin) return fail(SYLDET_ERR_INVALID_ARGUMENT, "NULL label_begin");
-    sd::BankInfo b{};
-    sd::bank_info(h, &b);
+    std::unique_ptr<syldet_scorer, int (*)(syldet_scorer_t *)> s(nullptr, syldet_scorer_destroy);
+    try {
+        s.reset(new syldet_scorer());
+        if (int st = s->read(h, r, sd::kSpanEvals)) return st;
+    } catch (const std::bad_alloc &) {
+        return fail(SYLDET_ERR_OUT_OF_MEMORY, "out of memory");
+    }
+    const sd::BankInfo &b = s->bank;
+    const int32_t D = s->D;
     const double frames = debounce_seconds * b.sampling_rate;            // TrackDetector.swift:19-26
     if (!(std::fabs(frames) < (double)kFrameLimit)) return fail(SYLDET_ERR_INVALID_ARGUMENT, "debounce_seconds x samplingRate is not a number below 2^62");
-    int32_t D = b.channels;
-    int64_t row_evals = 0;
-    if (r)
-        if (int st = syldet_recordings_shape(r, &D, nullptr, &row_evals, nullptr)) return st;
     if (label_begin[0] != 0) return fail(SYLDET_ERR_INVALID_ARGUMENT, "label_begin[0] must be 0");
     for (int32_t d = 0; d < D; d++)
         if (label_begin[d + 1] < label_begin[d]) return fail(SYLDET_ERR_INVALID_ARGUMENT, "label_begin[" + std::to_string(d + 1) + "] decreases");
@@ -97,50 +84,34 @@ int syldet_scorer_create(const syldet_t *h, const syldet_recordings_t *r, const 
     const int K = n_thresholds, groups = (K + 63) / 64;
     if ((int64_t)D * groups > 0x7fffffff) return fail(SYLDET_ERR_UNSUPPORTED, "more than 2^31 - 1 (detector, group of 64 thresholds) pairs");
 
-    std::unique_ptr<syldet_scorer, int (*)(syldet_scorer_t *)> s(nullptr, syldet_scorer_destroy);
     std::vector<float> thr, least;
-    std::vector<sd::RecEventDev> slots;
     try {
-        s.reset(new syldet_scorer());
         thr.resize((size_t)K);
         least.assign((size_t)groups, std::numeric_limits<float>::infinity());
         for (int k = 0; k < K; k++) {
             thr[(size_t)k] = sd::score_threshold_f32(thresholds[k]);
             least[(size_t)(k / 64)] = std::fmin(least[(size_t)(k / 64)], thr[(size_t)k]);
         }
-        if (r && D > 0) {
-            std::vector<syldet_slot_t> plan((size_t)D);
-            if (int st = syldet_recordings_slots(r, plan.data())) return st;
-            for (const syldet_slot_t &p : plan) slots.push_back(sd::RecEventDev{p.first_eval, p.n_evals, p.row, 0});
-        }
     } catch (const std::bad_alloc &) {
         return fail(SYLDET_ERR_OUT_OF_MEMORY, "out of memory");
     }
-    s->bank = b;
-    s->packed = r != nullptr;
-    s->row_evals = row_evals;
-    s->D = D;
     s->n_labels = n_labels;
-    const size_t n_thr = up16((size_t)K * sizeof(float)), n_least = up16((size_t)groups * sizeof(float)),
-                 n_begin = up16(((size_t)D + 1) * sizeof(int64_t)), n_lab = up16((size_t)n_labels * sizeof(int64_t)),
-                 n_slots = up16(slots.size() * sizeof(sd::RecEventDev));
+    sd::Carver blob;
+    const size_t at_thr = blob.take(bytes_of(thr)), at_least = blob.take(bytes_of(least)), at_begin = blob.take(((size_t)D + 1) * sizeof(int64_t)),
+                 at_labels = blob.take((size_t)n_labels * sizeof(int64_t)), at_spans = blob.take(bytes_of(s->spans));
     SYLDET_HIP(hipSetDevice(b.device));
-    hipError_t e = hipMalloc(&s->d_blob, n_thr + n_least + n_begin + n_lab + n_slots + 16);
-    if (e != hipSuccess) {
-        s->d_blob = nullptr;
-        return fail(e == hipErrorOutOfMemory ? SYLDET_ERR_OUT_OF_MEMORY : SYLDET_ERR_DEVICE, std::string("hipMalloc: ") + hipGetErrorString(e));
-    }
-    char *base = (char *)s->d_blob;
-    SYLDET_HIP(hipMemcpy(base, thr.data(), (size_t)K * sizeof(float), hipMemcpyHostToDevice));
-    SYLDET_HIP(hipMemcpy(base + n_thr, least.data(), (size_t)groups * sizeof(float), hipMemcpyHostToDevice));
-    SYLDET_HIP(hipMemcpy(base + n_thr + n_least, label_begin, ((size_t)D + 1) * sizeof(int64_t), hipMemcpyHostToDevice));
-    if (n_labels > 0) SYLDET_HIP(hipMemcpy(base + n_thr + n_least + n_begin, labels, (size_t)n_labels * sizeof(int64_t), hipMemcpyHostToDevice));
-    if (!slots.empty()) SYLDET_HIP(hipMemcpy(base + n_thr + n_least + n_begin + n_lab, slots.data(), slots.size() * sizeof(sd::RecEventDev), hipMemcpyHostToDevice));
-    s->desc = sd::ScoreDesc{(const float *)base,
-                            (const float *)(base + n_thr),
-                            (const int64_t *)(base + n_thr + n_least + n_begin),
-                            (const int64_t *)(base + n_thr + n_least),
-                            r ? (const sd::RecEventDev *)(base + n_thr + n_least + n_begin + n_lab) : nullptr,
+    if (int st = s->d_blob.reserve(blob.total + 16)) return st;
+    char *base = (char *)s->d_blob.ptr;
+    SYLDET_HIP(upload(base, at_thr, thr));
+    SYLDET_HIP(upload(base, at_least, least));
+    SYLDET_HIP(upload(base, at_begin, label_begin, ((size_t)D + 1) * sizeof(int64_t)));
+    SYLDET_HIP(upload(base, at_labels, labels, (size_t)n_labels * sizeof(int64_t)));
+    SYLDET_HIP(upload(base, at_spans, s->spans));
+    s->desc = sd::ScoreDesc{(const float *)(base + at_thr),
+                            (const float *)(base + at_least),
+                            (const int64_t *)(base + at_labels),
+                            (const int64_t *)(base + at_begin),
+                            r ? (const sd::DetSpan *)(base + at_spans) : nullptr,
                             K,
                             tolerance_samples,
                             (int64_t)frames};
@@ -151,10 +122,8 @@ int syldet_scorer_create(const syldet_t *h, const syldet_recordings_t *r, const 
 int syldet_scorer_destroy(syldet_scorer_t *s)
 {
     if (!s) return SYLDET_OK;
-    if (s->d_blob) {
-        (void)hipSetDevice(s->bank.device);
-        (void)hipFree(s->d_blob);
-    }
+    if (s->d_blob.ptr) (void)hipSetDevice(s->bank.device);
+    s->d_blob.release();
     delete s;
     return SYLDET_OK;
 }
@@ -174,8 +143,7 @@ int syldet_score_device(syldet_scorer_t *s, const float *d_outputs, int64_t n_ev
     if (n_evals < 0) return fail(SYLDET_ERR_INVALID_ARGUMENT, "n_evals is negative");
     if (output < 0 || output >= s->bank.geom.outputs)
         return fail(SYLDET_ERR_INVALID_ARGUMENT, "output " + std::to_string(output) + " outside [0, " + std::to_string(s->bank.geom.outputs) + ")");
-    if (s->packed && n_evals != s->row_evals)
-        return fail(SYLDET_ERR_INVALID_ARGUMENT, "n_evals must be the packed rows' " + std::to_string(s->row_evals) + " evaluations");
+    if (int st = s->row_units_arg(n_evals, "n_evals", "evaluations")) return st;
     if (s->D == 0) return SYLDET_OK;
     SYLDET_HIP(hipSetDevice(s->bank.device));
     SYLDET_HIP(sd::launch_score(s->desc, s->D, d_outputs, n_evals, s->bank.geom.outputs, output, s->bank.geom.first_index, s->bank.geom.hop, d_table,

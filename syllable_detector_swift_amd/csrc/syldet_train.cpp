@@ -12,14 +12,11 @@
 
 static_assert(SYLDET_TRAIN_MAX_HIDDEN == sd::kTrainMaxHidden && SYLDET_TRAIN_MAX_OUTPUTS == sd::kTrainMaxOut, "the header's limits are the kernel's");
 
-struct syldet_trainer {
-    syldet_t *h = nullptr;                   // the bank (it outlives the trainer): its profile
-    sd::BankInfo bank{};
-    bool packed = false;
-    int D = 0, P = 0;
-    int64_t row_evals = 0, row_frames = 0;   // (packed) what n_evals and n_frames must be
+struct syldet_trainer : sd::DetectorTable {  // (the spans: evaluations)
+    int P = 0;
+    int64_t row_frames = 0;                  // (packed) what n_frames must be
     sd::TrainDesc desc{};
-    sd::DeviceBuffer d_fixed;                // maps [N] | (packed) TrainDetDev [D] | row_begin [rows + 1] | (multi) TrainDesc [N] | rows by network | net_row_begin [N + 1]
+    sd::DeviceBuffer d_fixed;                // maps [N] | (packed) by_row [D] | row_begin [rows + 1] | (multi) TrainDesc [N] | rows by network | net_row_begin [N + 1]
     sd::DeviceBuffer d_part;                 // [N][max_groups][P + 2] fp64
     sd::DeviceBuffer d_opt;                  // the optimiser's: loss [N][2] fp64 | gradient [N][P] | m [N][P] | v [N][P] fp32
     int map_at = -1;                         // the first mapminmax input function (-1: none) and the host's copy of its parameters
@@ -32,7 +29,7 @@ struct syldet_trainer {
     std::vector<sd::TrainDesc> descs;        // [N] every network's own (desc is network 0's); on the device at descs_at of d_fixed
     size_t descs_at = 0;
     sd::TrainMulti mu{};
-    const sd::TrainDetDev *d_dets = nullptr;
+    const sd::DetSpan *d_dets = nullptr;
     const int32_t *d_row_begin = nullptr;
     hipStream_t last = nullptr;              // the stream of the last call that may still read the labels or write the partials
     // the kept labels
@@ -77,16 +74,13 @@ int outputs_arg(const int32_t *label_output, int64_t n, int O)
     return SYLDET_OK;
 }
 
-size_t up16(size_t n) { return (n + 15) / 16 * 16; }
-
 // what the gradient, the range and the fit check of their columns; row_stride 0 becomes a row's elements
 int columns_args(const syldet_trainer *t, int64_t n_evals, int64_t n_frames, int64_t *row_stride)
 {
     if (n_evals < 0 || n_frames < 0) return fail(SYLDET_ERR_INVALID_ARGUMENT, "n_evals or n_frames is negative");
     const sd::TrainDesc &d = t->desc;
-    if (t->packed && (n_evals != t->row_evals || n_frames != t->row_frames))
-        return fail(SYLDET_ERR_INVALID_ARGUMENT, "n_evals and n_frames must be the packed rows' " + std::to_string(t->row_evals) + " evaluations and " +
-                                                     std::to_string(t->row_frames) + " frames");
+    if (t->packed && (n_evals != t->row_units || n_frames != t->row_frames))
+        return t->packed_rows_refusal("n_evals and n_frames", std::to_string(t->row_units) + " evaluations and " + std::to_string(t->row_frames) + " frames");
     if (n_evals > 0 && n_frames < n_evals + d.T - 1)
         return fail(SYLDET_ERR_INVALID_ARGUMENT, std::to_string(n_evals) + " evaluations read " + std::to_string(n_evals + d.T - 1) + " frames, " +
                                                      std::to_string(n_frames) + " given");
@@ -168,18 +162,14 @@ static int trainer_create(const syldet_t *h, const syldet_recordings_t *r, const
     const int P = sd::train_param_count(I, H, O);
     if ((int64_t)N * P > 0x7fffffff) return fail(SYLDET_ERR_UNSUPPORTED, "more than 2^31 - 1 parameters in all");
     if (N > 65535) return fail(SYLDET_ERR_UNSUPPORTED, "more than 65535 networks (the network is a launch's grid.y)");
-    int32_t D = b.channels;
-    int64_t row_samples = 0, row_evals = 0;
-    if (r)
-        if (int st = syldet_recordings_shape(r, &D, &row_samples, &row_evals, nullptr)) return st;
 
     std::unique_ptr<syldet_trainer, int (*)(syldet_trainer_t *)> t(nullptr, syldet_trainer_destroy);
     std::vector<float> maps;
-    std::vector<sd::TrainDetDev> dets;
+    std::vector<sd::DetSpan> by_row;
     std::vector<int32_t> row_begin, sorted_rows, net_row_begin;
     try {
         t.reset(new syldet_trainer());
-        t->bank = b;
+        if (int st = t->read(h, r, sd::kSpanEvals)) return st;
         auto push = [&maps](const float *p, int n) {
             const int at = (int)maps.size();
             maps.insert(maps.end(), p, p + n);
@@ -220,65 +210,43 @@ static int trainer_create(const syldet_t *h, const syldet_recordings_t *r, const
             std::vector<int32_t> at(net_row_begin.begin(), net_row_begin.end() - 1);
             for (int32_t row = 0; row < b.channels; row++) sorted_rows[(size_t)at[(size_t)t->row_net[(size_t)row]]++] = row;
         }
-        t->begin.assign((size_t)D + 1, 0);
-        if (r) {
-            std::vector<syldet_slot_t> plan((size_t)D);
-            if (D > 0)
-                if (int st = syldet_recordings_slots(r, plan.data())) return st;
-            // the detectors by (row, first_eval): what the targets kernel searches (an empty recording in front of one that starts
-            // at the same evaluation, so that the last detector at or before an evaluation is the one that holds it)
-            for (int k = 0; k < D; k++) dets.push_back(sd::TrainDetDev{plan[(size_t)k].first_eval, plan[(size_t)k].n_evals, k, plan[(size_t)k].row});
-            std::stable_sort(dets.begin(), dets.end(), [](const sd::TrainDetDev &x, const sd::TrainDetDev &y) {
-                if (x.row != y.row) return x.row < y.row;
-                return x.first_eval != y.first_eval ? x.first_eval < y.first_eval : x.n_evals < y.n_evals;
-            });
-            row_begin.assign((size_t)b.channels + 1, 0);
-            for (const sd::TrainDetDev &e : dets) {
-                if (e.row < 0 || e.row >= b.channels || (e.n_evals > 0 && (e.first_eval < 0 || e.first_eval + e.n_evals > row_evals)))
-                    return fail(SYLDET_ERR_INVALID_ARGUMENT, "recording " + std::to_string(e.det) + " reaches beyond its row");
-                row_begin[(size_t)e.row + 1]++;
-            }
-            for (int c2 = 0; c2 < b.channels; c2++) row_begin[(size_t)c2 + 1] += row_begin[(size_t)c2];
-        }
+        t->begin.assign((size_t)t->D + 1, 0);
+        if (r) sd::spans_by_row(t->spans, b.channels, &by_row, &row_begin);     // what the targets kernel searches
     } catch (const std::bad_alloc &) {
         return fail(SYLDET_ERR_OUT_OF_MEMORY, "out of memory");
     }
-    t->h = const_cast<syldet_t *>(h);
-    t->packed = r != nullptr;
     t->multi = multi;
     t->N = N;
-    t->D = D;
     t->P = P;
-    t->row_evals = row_evals;
-    t->row_frames = r ? std::max<int64_t>(0, sd::count_frames(b.geom, b.window_length, row_samples)) : 0;
-    if (r && row_evals > 0 && t->row_frames < row_evals + d.T - 1) return fail(SYLDET_ERR_INVALID_ARGUMENT, "the packed rows hold fewer frames than their evaluations read");
+    t->row_frames = r ? sd::span_row_units(b, sd::kSpanFrames, t->row_samples, t->row_evals) : 0;
+    if (r && t->row_evals > 0 && t->row_frames < t->row_evals + d.T - 1) return fail(SYLDET_ERR_INVALID_ARGUMENT, "the packed rows hold fewer frames than their evaluations read");
 
-    const size_t n_maps = up16(maps.size() * sizeof(float)), n_dets = up16(dets.size() * sizeof(sd::TrainDetDev)),
-                 n_rows = up16(row_begin.size() * sizeof(int32_t)), n_descs = multi ? up16((size_t)N * sizeof(sd::TrainDesc)) : 0,
-                 n_sorted = multi ? up16(sorted_rows.size() * sizeof(int32_t)) : 0, n_begin = multi ? up16(net_row_begin.size() * sizeof(int32_t)) : 0;
+    sd::Carver blob;
+    const size_t at_maps = blob.take(bytes_of(maps)), at_dets = blob.take(bytes_of(by_row)), at_rows = blob.take(bytes_of(row_begin)),
+                 at_descs = blob.take(multi ? bytes_of(t->descs) : 0), at_sorted = blob.take(multi ? bytes_of(sorted_rows) : 0),
+                 at_begin = blob.take(multi ? bytes_of(net_row_begin) : 0);
     SYLDET_HIP(hipSetDevice(b.device));
     SYLDET_HIP(sd::train_prepare(d));
     if (multi) SYLDET_HIP(sd::train_prepare_multi(d));
-    if (int st = t->d_fixed.reserve(n_maps + n_dets + n_rows + n_descs + n_sorted + n_begin + 16)) return st;
+    if (int st = t->d_fixed.reserve(blob.total + 16)) return st;
     if (int st = t->d_part.reserve((size_t)N * (size_t)d.max_groups * ((size_t)P + 2) * sizeof(double))) return st;
     if (int st = t->d_opt.reserve(16 * (size_t)N + 3 * (size_t)N * (size_t)P * sizeof(float))) return st;
     char *base = (char *)t->d_fixed.ptr;
-    if (!maps.empty()) SYLDET_HIP(hipMemcpy(base, maps.data(), maps.size() * sizeof(float), hipMemcpyHostToDevice));
-    if (!dets.empty()) SYLDET_HIP(hipMemcpy(base + n_maps, dets.data(), dets.size() * sizeof(sd::TrainDetDev), hipMemcpyHostToDevice));
-    if (!row_begin.empty()) SYLDET_HIP(hipMemcpy(base + n_maps + n_dets, row_begin.data(), row_begin.size() * sizeof(int32_t), hipMemcpyHostToDevice));
-    for (int n = 0; n < N; n++) t->descs[(size_t)n].maps = (const float *)base + (size_t)n * (size_t)t->maps_per;
+    SYLDET_HIP(upload(base, at_maps, maps));
+    SYLDET_HIP(upload(base, at_dets, by_row));
+    SYLDET_HIP(upload(base, at_rows, row_begin));
+    for (int n = 0; n < N; n++) t->descs[(size_t)n].maps = (const float *)(base + at_maps) + (size_t)n * (size_t)t->maps_per;
     d = t->descs[0];
-    t->d_dets = r ? (const sd::TrainDetDev *)(base + n_maps) : nullptr;
-    t->d_row_begin = r ? (const int32_t *)(base + n_maps + n_dets) : nullptr;
+    t->d_dets = r ? (const sd::DetSpan *)(base + at_dets) : nullptr;
+    t->d_row_begin = r ? (const int32_t *)(base + at_rows) : nullptr;
     if (multi) {
-        t->descs_at = n_maps + n_dets + n_rows;
-        char *tables = base + t->descs_at;
-        SYLDET_HIP(hipMemcpy(tables, t->descs.data(), (size_t)N * sizeof(sd::TrainDesc), hipMemcpyHostToDevice));
-        if (!sorted_rows.empty()) SYLDET_HIP(hipMemcpy(tables + n_descs, sorted_rows.data(), sorted_rows.size() * sizeof(int32_t), hipMemcpyHostToDevice));
-        SYLDET_HIP(hipMemcpy(tables + n_descs + n_sorted, net_row_begin.data(), net_row_begin.size() * sizeof(int32_t), hipMemcpyHostToDevice));
-        t->mu.descs = (const sd::TrainDesc *)tables;
-        t->mu.rows = (const int32_t *)(tables + n_descs);
-        t->mu.net_row_begin = (const int32_t *)(tables + n_descs + n_sorted);
+        t->descs_at = at_descs;
+        SYLDET_HIP(upload(base, at_descs, t->descs));
+        SYLDET_HIP(upload(base, at_sorted, sorted_rows));
+        SYLDET_HIP(upload(base, at_begin, net_row_begin));
+        t->mu.descs = (const sd::TrainDesc *)(base + at_descs);
+        t->mu.rows = (const int32_t *)(base + at_sorted);
+        t->mu.net_row_begin = (const int32_t *)(base + at_begin);
         t->mu.n_nets = N;
         t->mu.max_rows = *std::max_element(t->net_rows.begin(), t->net_rows.end());
     }
@@ -389,14 +357,15 @@ int syldet_train_targets_device(syldet_trainer_t *t, const int64_t *labels, cons
     if (int st = half_width_arg(half_width_samples)) return st;
     if (int st = class_weights(weight_positive, weight_negative)) return st;
     if (n_evals < 0) return fail(SYLDET_ERR_INVALID_ARGUMENT, "n_evals is negative");
-    if (t->packed && n_evals != t->row_evals)
-        return fail(SYLDET_ERR_INVALID_ARGUMENT, "n_evals must be the packed rows' " + std::to_string(t->row_evals) + " evaluations");
+    if (int st = t->row_units_arg(n_evals, "n_evals", "evaluations")) return st;
     if (n_evals > ((int64_t)1 << 31)) return fail(SYLDET_ERR_UNSUPPORTED, "more than 2^31 evaluations a row");
     const int rows = t->bank.channels;
     if (n_evals > 0 && rows > 0 && (!d_targets || !d_weights)) return fail(SYLDET_ERR_INVALID_ARGUMENT, "NULL argument");
     hipStream_t stream = (hipStream_t)hip_stream;
     SYLDET_HIP(hipSetDevice(t->bank.device));
     const size_t nb = ((size_t)t->D + 1) * sizeof(int64_t), nl = (size_t)n_labels * sizeof(int64_t), no = (size_t)n_labels * sizeof(int32_t);
+    sd::Carver blob;
+    const size_t at_begin = blob.take(nb), at_labels = blob.take(nl), at_output = blob.take(no);
     const bool same = t->has_labels && std::memcmp(t->begin.data(), label_begin, nb) == 0 &&
                       (n_labels == 0 || std::memcmp(t->labels.data(), labels, nl) == 0) && t->has_output == (label_output != nullptr) &&
                       (!label_output || n_labels == 0 || std::memcmp(t->output.data(), label_output, no) == 0);
@@ -412,11 +381,10 @@ int syldet_train_targets_device(syldet_trainer_t *t, const int64_t *labels, cons
         } catch (const std::bad_alloc &) {
             return fail(SYLDET_ERR_OUT_OF_MEMORY, "out of memory");
         }
-        if (int st = t->d_labels.reserve(up16(nb) + up16(nl) + up16(no) + 16)) return st;
-        char *base = (char *)t->d_labels.ptr;
-        SYLDET_HIP(hipMemcpy(base, label_begin, nb, hipMemcpyHostToDevice));
-        if (n_labels > 0) SYLDET_HIP(hipMemcpy(base + up16(nb), labels, nl, hipMemcpyHostToDevice));
-        if (n_labels > 0 && label_output) SYLDET_HIP(hipMemcpy(base + up16(nb) + up16(nl), label_output, no, hipMemcpyHostToDevice));
+        if (int st = t->d_labels.reserve(blob.total + 16)) return st;
+        SYLDET_HIP(upload(t->d_labels.ptr, at_begin, label_begin, nb));
+        SYLDET_HIP(upload(t->d_labels.ptr, at_labels, labels, nl));
+        if (label_output) SYLDET_HIP(upload(t->d_labels.ptr, at_output, label_output, no));
         t->has_output = label_output != nullptr;
         t->has_labels = true;
     }
@@ -426,9 +394,9 @@ int syldet_train_targets_device(syldet_trainer_t *t, const int64_t *labels, cons
     sd::TrainTargetsDesc d{};
     d.dets = t->d_dets;
     d.row_begin = t->d_row_begin;
-    d.label_begin = (const int64_t *)base;
-    d.labels = (const int64_t *)(base + up16(nb));
-    d.label_output = label_output ? (const int32_t *)(base + up16(nb) + up16(nl)) : nullptr;
+    d.label_begin = (const int64_t *)(base + at_begin);
+    d.labels = (const int64_t *)(base + at_labels);
+    d.label_output = label_output ? (const int32_t *)(base + at_output) : nullptr;
     d.rows = rows;
     d.n_out = t->desc.O;
     d.first_index = t->bank.geom.first_index;

@@ -529,9 +529,6 @@ train_range_combine_kernel(int I, int P, int groups, const double *__restrict__ 
     if (i == 0) *count = c;
 }
 
-// the LDS layout's rounding (train_plan) and the launchers' own
-inline int up16(int n) { return (n + 15) / 16 * 16; }
-
 }  // namespace
 
 }  // namespace sd
