@@ -1551,8 +1551,8 @@ int syldet_match_peaks_host(const float *scores, int64_t n_positions, float thre
  * and sharded banks get the answers the single matcher gives them.
  * THE LAUNCH RULE is the matcher's: both device calls are launches only -- no allocation, no synchronisation, no copy -- and each
  * records into the profile of h under its kernel's name.
- * NOT HERE: templates of different lengths in one bank; suppression across classes; a class column in label files; training more
- * than output 0 from the command-line tool; sharded banks.                                                                        */
+ * NOT HERE: suppression across classes; a class column in label files; training more than output 0 from the command-line tool;
+ * sharded banks.  (Templates of their own lengths: the next section.)                                                            */
 #define SYLDET_MATCH_MAX_TEMPLATES 64
 #define SYLDET_MATCH_MAX_CLASSES   16
 typedef struct syldet_matcher_bank syldet_matcher_bank_t;
@@ -1569,6 +1569,74 @@ int syldet_match_bank_peaks_device(syldet_matcher_bank_t *m, const float *d_scor
                                    float *d_event_scores, int32_t *d_event_template, void *hip_stream);
 int syldet_match_classes_host(const float *template_scores, int64_t n_positions, int32_t n_templates, const int32_t *template_class,
                               int32_t n_classes, float *class_scores, int32_t *which);
+
+/* ---- template matching: a ragged bank ----
+ * The syllables of one song do not share a duration, and exemplars of one syllable cut from different renditions differ by a frame
+ * or two.  A ragged bank holds templates of different lengths in one bank, so the frames are staged and their energies taken once
+ * for all of them; with different lengths "position = first frame of the window" no longer lines the templates of a class up, so
+ * THE TEMPLATES ARE LINED UP AT THEIR ANCHORS.  The handle is the bank's (syldet_matcher_bank_t); everything the two sections above
+ * define holds for every template.  A bank made by syldet_matcher_bank_create is untouched: its kernels, its planes (indexed by the
+ * window's first frame) and its bytes stay as they are.
+ * A RAGGED BANK is K templates, 1 <= K <= SYLDET_MATCH_MAX_TEMPLATES; template k is [n_k][bins], n_k >= 1, n_k bins <=
+ *   SYLDET_MATCH_MAX_TEMPLATE; `templates` is their concatenation in k order; each obeys the single template's rules and is
+ *   normalised on its own as syldet_match_normalize_host does it.  template_n[k] = n_k.  template_anchor[k] = a_k lies in [0, n_k); a
+ *   NULL table means n_k - 1 for every k.  Classes are the bank's: the same table rules, NULL = identity, C <=
+ *   SYLDET_MATCH_MAX_CLASSES.
+ * THE PLANES ARE INDEXED BY THE ANCHOR FRAME.  Element first + u of a detector's row in plane c belongs to frame u of the detector,
+ *   0 <= u < U_d.  Template k's window for u is the frames [u - a_k, u - a_k + n_k); it exists iff 0 <= u - a_k and
+ *   u - a_k + n_k <= U_d: it lies inside the detector's own frames ON BOTH SIDES.  The front side is new: a packed recording's window
+ *   never reads the previous recording of its row or the gap before it.  Where the window exists, s_k(u) is the single matcher's
+ *   score of template k on that window.
+ * THE CLASS SCORE S_c(u) is the greatest s_k(u) over the templates of class c whose window exists at u and whose score is not NaN,
+ *   taken in ascending k and replaced only where greater (csrc/match_classes.hpp: a NaN is never taken); which is the LOWEST k that
+ *   attains it; the result is NaN, -1 iff no template of the class has a non-NaN score there.  Unlike the uniform bank a position can
+ *   be NaN for one template and not for another: near a detector's ends the shorter window fits where the longer does not, and the
+ *   shorter window can miss a NaN or an Inf that the longer one holds.
+ * BITS.  The bank's form is matrix iff its tile (below) fits the single matcher's 64 KB; otherwise every template takes the plain
+ *   form.  In a matrix-form bank every template's single matcher is matrix-form too (its tile is no larger), so s_k(u) has the bytes
+ *   of syldet_matcher_create(template k)'s score at position u - a_k: the chains, their order, the zeros by selection, E as the chain
+ *   of frame energies from the window's first frame on and the division are the same device functions.  In a plain-form bank s_k
+ *   has the plain form's bytes, which are the single matcher's wherever the single matcher of (n_k, bins) is plain as well; where it
+ *   is not -- a 12-frame template beside a 100-frame one at 29 bins -- the score is the plain form's of the same sums, within the
+ *   single matcher's distance of the fp64 value.
+ * EVENTS.  A match at u is the sample origin + u hop: the plane's index is the anchor, so the plane's own anchor is 0.  The peaks
+ *   rule is csrc/match_peaks.hpp, unchanged, over all U_d elements of the detector; NaN neither matches nor suppresses.  The tables
+ *   go as they are into the aligner, the scorer and syldet_train_targets_device.
+ * A SEPARATION A CLASS.  A short syllable repeats faster than a long one: syldet_match_bank_peaks_each_device takes `separations`, a
+ *   HOST array of C values in [0, SYLDET_MATCH_MAX_SEPARATION] passed by value like the thresholds.  Class c's tables are byte for
+ *   byte what syldet_match_peaks_host writes from that detector's stretch of plane c with thresholds[c], separations[c] and (on a
+ *   ragged bank) anchor 0.
+ *   syldet_matcher_bank_create_ragged   the lengths, anchors, offsets, the class order and, for recordings, the slots go to the device
+ *       once.  On its handle syldet_matcher_bank_shape reports the greatest n_k as n and 0 as the anchor, and
+ *       syldet_matcher_bank_templates writes the concatenated t^.
+ *   syldet_matcher_bank_lengths         n_k and a_k of every template and whether the bank is ragged (each may be NULL); a uniform
+ *       bank: K times (n, anchor), 0.
+ *   syldet_match_bank_scores_device     on a ragged handle ONE launch for any K, C and lengths.  "match_ragged_scores_mfma_kernel"
+ *       keeps the bank kernel's workgroup and its tile of 256 plane elements p0 .. p0 + 255.  With the lead a_max = max a_k and the
+ *       tail r_max = max (n_k - a_k) it stages the G = 255 + a_max + r_max frames p0 - a_max .. p0 + 255 + r_max - 1 once (frames
+ *       before the row's start and behind its end zero by selection), takes their energies and zeroes the non-finite values once,
+ *       and makes one pass a template in the class order through the one template region of n_max frames; template k's pass runs the
+ *       bank's products with n_k as loop and selection bound from s_k = a_max - a_k frames into the staged block, and its E from the
+ *       same frame.  The tile's floats are counted as the single matcher's with this G and this region (csrc/match_ragged.hpp: one
+ *       text for the kernels, the host and a stand-alone test).  "match_ragged_scores_plain_kernel", a thread a plane element, where
+ *       that tile does not fit.
+ *   syldet_match_bank_peaks_device      works on a ragged handle too (the shared separation).
+ *   syldet_match_bank_peaks_each_device ONE launch ("match_bank_peaks_each_kernel": the body of "match_peaks_kernel" a class with the
+ *       class's own separation; LDS by the greatest).  On a uniform handle with equal separations it writes the bytes of
+ *       syldet_match_bank_peaks_device.
+ * Statuses as above, decided before any device is touched; a refused call leaves its outputs as they were.  Besides the bank's:
+ * NULL template_n, an n_k < 1 or n_k bins over the limit, an anchor outside [0, n_k), NULL separations or one outside its range are
+ * SYLDET_ERR_INVALID_ARGUMENT.  Mixed and sharded banks get the answers the bank gives them.
+ * THE LAUNCH RULE is the bank's: no call allocates, synchronises or copies.
+ * NOT HERE: exemplars of different lengths within one .npy file of the command-line tool (a file is [k][n][bins]: give one file a
+ * length, or use the library); suppression across classes; a class column in label files; sharded banks.                          */
+int syldet_matcher_bank_create_ragged(const syldet_t *h, const syldet_recordings_t *r, const float *templates, int32_t n_templates,
+                                      const int32_t *template_n, int32_t bins, const int32_t *template_anchor,
+                                      const int32_t *template_class, int32_t n_classes, syldet_matcher_bank_t **out);
+int syldet_matcher_bank_lengths(const syldet_matcher_bank_t *m, int32_t *template_n, int32_t *template_anchor, int32_t *ragged);
+int syldet_match_bank_peaks_each_device(syldet_matcher_bank_t *m, const float *d_scores, const int32_t *d_which, int64_t n_frames,
+                                        const float *thresholds, const int32_t *separations, int64_t *d_events, int64_t capacity,
+                                        int64_t *d_counts, float *d_event_scores, int32_t *d_event_template, void *hip_stream);
 
 #ifdef __cplusplus
 }

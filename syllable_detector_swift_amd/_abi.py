@@ -347,6 +347,11 @@ SIGNATURES = {
     "syldet_match_bank_peaks_device": (C.c_int, [Handle, C.c_void_p, C.c_void_p, C.c_int64, c_float_p, C.c_int32, C.c_void_p, C.c_int64,
                                                  C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "syldet_match_classes_host": (C.c_int, [c_float_p, C.c_int64, C.c_int32, c_int32_p, C.c_int32, c_float_p, c_int32_p]),
+    "syldet_matcher_bank_create_ragged": (C.c_int, [Handle, Handle, c_float_p, C.c_int32, c_int32_p, C.c_int32, c_int32_p, c_int32_p, C.c_int32,
+                                                    C.POINTER(Handle)]),
+    "syldet_matcher_bank_lengths": (C.c_int, [Handle, c_int32_p, c_int32_p, c_int32_p]),
+    "syldet_match_bank_peaks_each_device": (C.c_int, [Handle, C.c_void_p, C.c_void_p, C.c_int64, c_float_p, c_int32_p, C.c_void_p, C.c_int64,
+                                                      C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
 }
 
 

@@ -71,8 +71,8 @@ class ShardedSyllableDetectorBank:
         from .config import SyllableDetectorError
         raise SyllableDetectorError(_abi.ERR_UNSUPPORTED, "template matching on a sharded bank: use a SyllableDetector per device")
 
-    def matcherBank(self, templates, classes=None, anchor=None):
-        """A bank of templates (SyllableDetector.matcherBank) has no sharded form either."""
+    def matcherBank(self, templates, classes=None, anchor=None, ragged=None):
+        """A bank of templates (SyllableDetector.matcherBank), ragged or not, has no sharded form either."""
         from .config import SyllableDetectorError
         raise SyllableDetectorError(_abi.ERR_UNSUPPORTED, "template matching on a sharded bank: use a SyllableDetector per device")
 

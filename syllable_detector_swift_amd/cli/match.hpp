@@ -1,11 +1,15 @@
 // --match: the templates and what a run gathers (see MatchOpt), the matches of one bank's detectors, and the files written at the end.
 // The i-th --match is class i of one bank of templates (syldet_matcher_bank_*): one scores call and one peaks call a bank of
-// detectors, whatever the number of classes and exemplars.
+// detectors, whatever the number of classes and exemplars.  Files that all share their frame count make the uniform bank; with
+// --match-ragged files of different frame counts make a ragged one (syldet_matcher_bank_create_ragged), whose planes are indexed by
+// the anchor frame.
 #pragma once
 
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <cstring>
+#include <functional>
 
 #include "align.hpp"
 
@@ -13,10 +17,14 @@ namespace {
 
 struct MatchRun {
     MatchOpt opt;
-    std::vector<float> templ;                              // [K][n][bins], class by class
+    std::vector<float> templ;                              // [K][n][bins], class by class (ragged: each [n_k][bins], one after another)
     std::vector<int32_t> tclass;                           // [K]
+    std::vector<int32_t> tn, ta;                           // [K] every template's frames and anchor frame
+    std::vector<int32_t> class_n;                          // [C] the frames of a class's file
     std::vector<float> thresholds;                         // [C]
-    int K = 0, C = 0, n = 0, bins = 0, anchor = -1, separation = 0;      // the separation in frames
+    std::vector<int32_t> separations;                      // [C] in frames
+    bool ragged = false;                                   // the files differ in their frame counts
+    int K = 0, C = 0, n = 0, bins = 0, anchor = -1;        // n, anchor: the uniform bank's
     std::vector<std::string> lines;                        // [C] file<TAB>track<TAB>sample, in command-line order, then track, then sample
     bool failed = false;
 };
@@ -93,27 +101,47 @@ int match_begin(MatchRun &run, const MatchOpt &opt, const std::vector<syldet_con
             run.n = (int)shape[1];
             run.bins = (int)shape[2];
             if (run.bins != g.bins) return fail("--match: the template has " + std::to_string(run.bins) + " bins, the network's columns " + std::to_string(g.bins) + ".");
-        } else if (shape[1] != run.n || shape[2] != run.bins) {
+        } else if (shape[2] != run.bins || (shape[1] != run.n && !opt.ragged)) {
             return fail("--match: " + opt.paths[0] + " is [" + std::to_string(run.n) + "][" + std::to_string(run.bins) + "] and " + opt.paths[(size_t)c] + " [" +
-                        std::to_string(shape[1]) + "][" + std::to_string(shape[2]) + "]: the templates of one run share their frames and bins.");
+                        std::to_string(shape[1]) + "][" + std::to_string(shape[2]) + "]: the templates of one run share their frames and bins (--match-ragged: their bins).");
         }
+        const int n = (int)shape[1];
+        run.ragged = run.ragged || n != run.n;
+        run.class_n.push_back(n);
         run.K += (int)shape[0];
         if (run.K > SYLDET_MATCH_MAX_TEMPLATES) return fail("--match takes " + std::to_string(SYLDET_MATCH_MAX_TEMPLATES) + " exemplars at most, all files together.");
-        const size_t one = (size_t)run.n * (size_t)run.bins;
+        const size_t one = (size_t)n * (size_t)run.bins;
         std::vector<float> t_hat(one);
         for (int64_t k = 0; k < shape[0]; k++)
-            if (syldet_match_normalize_host(values.data() + (size_t)k * one, run.n, run.bins, t_hat.data())) return fail(std::string("--match: ") + syldet_last_error() + ".");
+            if (syldet_match_normalize_host(values.data() + (size_t)k * one, n, run.bins, t_hat.data())) return fail(std::string("--match: ") + syldet_last_error() + ".");
         run.templ.insert(run.templ.end(), values.begin(), values.end());
         run.tclass.insert(run.tclass.end(), (size_t)shape[0], c);
+        run.tn.insert(run.tn.end(), (size_t)shape[0], n);
     }
-    if (opt.anchor >= run.n) return fail("--match-anchor takes a frame of the template, 0 to " + std::to_string(run.n - 1) + ".");
-    run.anchor = opt.anchor < 0 ? run.n - 1 : (int)opt.anchor;
+    // the anchors: each class's last frame unless given; one for all is a frame of the shortest template
+    const int shortest = *std::min_element(run.class_n.begin(), run.class_n.end());
+    if (opt.anchors.size() == 1 && opt.anchors[0] >= shortest)
+        return fail("--match-anchor takes a frame of the template, 0 to " + std::to_string(shortest - 1) + ".");
+    std::vector<int32_t> class_anchor;
+    for (int c = 0; c < run.C; c++) {
+        const int n = run.class_n[(size_t)c];
+        const long a = opt.anchors.empty() ? n - 1 : opt.anchors[opt.anchors.size() == 1 ? 0 : (size_t)c];
+        if (a >= n) return fail("--match-anchor takes a frame of the template: " + opt.paths[(size_t)c] + " has the frames 0 to " + std::to_string(n - 1) + ".");
+        class_anchor.push_back((int32_t)a);
+    }
+    for (int k = 0; k < run.K; k++) run.ta.push_back(class_anchor[(size_t)run.tclass[(size_t)k]]);
+    // (files of one length with an anchor a class are lined up at their anchors too: the ragged bank)
+    run.ragged = run.ragged || std::adjacent_find(class_anchor.begin(), class_anchor.end(), std::not_equal_to<int32_t>()) != class_anchor.end();
+    run.anchor = class_anchor[0];
     for (int c = 0; c < run.C; c++)
         run.thresholds.push_back((float)(opt.thresholds.empty() ? 0.77 : opt.thresholds[opt.thresholds.size() == 1 ? 0 : (size_t)c]));
-    // the separation in frames: the template's own length unless given
-    const double frames = opt.separation < 0.0 ? (double)run.n : opt.separation * cfgs[0]->sampling_rate / (double)g.hop;
-    if (!(frames <= (double)SYLDET_MATCH_MAX_SEPARATION)) return fail("--match-separation may be " + std::to_string(SYLDET_MATCH_MAX_SEPARATION) + " frames at most.");
-    run.separation = (int)frames;
+    // the separations in frames: each class's own length unless given
+    for (int c = 0; c < run.C; c++) {
+        const double frames = opt.separations.empty() ? (double)run.class_n[(size_t)c]
+                                                      : opt.separations[opt.separations.size() == 1 ? 0 : (size_t)c] * cfgs[0]->sampling_rate / (double)g.hop;
+        if (!(frames <= (double)SYLDET_MATCH_MAX_SEPARATION)) return fail("--match-separation may be " + std::to_string(SYLDET_MATCH_MAX_SEPARATION) + " frames at most.");
+        run.separations.push_back((int32_t)frames);
+    }
     return 0;
 }
 
@@ -128,7 +156,10 @@ bool match_bank(MatchRun &run, syldet_t *h, syldet_recordings_t *r, const float 
     const int64_t J = std::max<int64_t>(0, syldet_count_frames(h, row_samples));
     if (J <= 0 || D <= 0) return true;
     syldet_matcher_bank_t *m = nullptr;
-    int st = syldet_matcher_bank_create(h, r, run.templ.data(), run.K, run.n, run.bins, run.anchor, run.tclass.data(), run.C, &m);
+    // (files of one length: the uniform bank, whose matches and bytes are what they were)
+    int st = run.ragged ? syldet_matcher_bank_create_ragged(h, r, run.templ.data(), run.K, run.tn.data(), run.bins, run.ta.data(), run.tclass.data(), run.C, &m)
+                        : syldet_matcher_bank_create(h, r, run.templ.data(), run.K, run.n, run.bins, run.anchor, run.tclass.data(), run.C, &m);
+    const bool each = std::adjacent_find(run.separations.begin(), run.separations.end(), std::not_equal_to<int32_t>()) != run.separations.end();
     DevBuf d_cols, d_scores, d_events, d_counts;
     bool ok = true;
     std::vector<int64_t> counts(N, 0), table;
@@ -141,8 +172,11 @@ bool match_bank(MatchRun &run, syldet_t *h, syldet_recordings_t *r, const float 
         for (int pass = 0; ok && !st && pass < 2; pass++) {
             DevBuf d_table;
             ok = d_table.alloc(N * (size_t)cap * sizeof(int64_t));
-            if (ok)
-                st = syldet_match_bank_peaks_device(m, (const float *)d_scores.p, nullptr, J, run.thresholds.data(), run.separation, (int64_t *)d_table.p, cap,
+            if (ok && each)
+                st = syldet_match_bank_peaks_each_device(m, (const float *)d_scores.p, nullptr, J, run.thresholds.data(), run.separations.data(),
+                                                         (int64_t *)d_table.p, cap, (int64_t *)d_counts.p, nullptr, nullptr, stream);
+            else if (ok)
+                st = syldet_match_bank_peaks_device(m, (const float *)d_scores.p, nullptr, J, run.thresholds.data(), run.separations[0], (int64_t *)d_table.p, cap,
                                                     (int64_t *)d_counts.p, nullptr, nullptr, stream);
             table.assign(N * (size_t)cap, 0);
             if (ok && !st)

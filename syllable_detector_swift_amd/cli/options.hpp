@@ -21,7 +21,7 @@ constexpr int kExUsage = 64;   // EX_USAGE, main.swift:40
 void usage(FILE *to)
 {
     std::fprintf(to,
-                 "Usage: syllable-detector-cli -n <net> [-a <audio>]... [-d <seconds>] [--device <k>] [--chunk <frames>] [--format <shortest|swift4>] [--resample <linear|sinc>] [--resample-quality <Z,beta,rolloff>] [--simulate <out.wav>] [--simulate-output <k>] [--levels <out.tsv>] [--levels-buffer <L>] [--levels-period <seconds>] [--ttl <out.wav>] [--ttl-mux] [--ttl-width <seconds>] [--ttl-steps <n>] [--ttl-buffer <L>] [--ttl-latency <seconds>] [--ttl-onsets <out.tsv>] [--simulate-dir <dir>] [--ttl-dir <dir>] [--ttl-onsets-dir <dir>] [--batch] [--batch-rows <N>] [--batch-bytes <B>] [--score <labels.tsv> --score-out <table.tsv>] [--score-thresholds <lo:hi:n>] [--score-tolerance <seconds>] [--score-cost <c>] [--score-output <k>] [--align-dir <dir>] [--align <columns|outputs|samples>] [--align-at <detections|labels>] [--align-before <units>] [--align-after <units>] [--match <template.npy> --match-out <matches.tsv>]... [--match-threshold <v>]... [--match-separation <seconds>] [--match-anchor <frame>] [--train <labels.tsv> --train-out <net.txt>] [--train-steps <n>] [--train-rate <lr>] [--train-width <seconds>] [--train-seed <s>] [--train-fit-map] [--train-output <k>] [--train-log <log.tsv>] [--probe]\n"
+                 "Usage: syllable-detector-cli -n <net> [-a <audio>]... [-d <seconds>] [--device <k>] [--chunk <frames>] [--format <shortest|swift4>] [--resample <linear|sinc>] [--resample-quality <Z,beta,rolloff>] [--simulate <out.wav>] [--simulate-output <k>] [--levels <out.tsv>] [--levels-buffer <L>] [--levels-period <seconds>] [--ttl <out.wav>] [--ttl-mux] [--ttl-width <seconds>] [--ttl-steps <n>] [--ttl-buffer <L>] [--ttl-latency <seconds>] [--ttl-onsets <out.tsv>] [--simulate-dir <dir>] [--ttl-dir <dir>] [--ttl-onsets-dir <dir>] [--batch] [--batch-rows <N>] [--batch-bytes <B>] [--score <labels.tsv> --score-out <table.tsv>] [--score-thresholds <lo:hi:n>] [--score-tolerance <seconds>] [--score-cost <c>] [--score-output <k>] [--align-dir <dir>] [--align <columns|outputs|samples>] [--align-at <detections|labels>] [--align-before <units>] [--align-after <units>] [--match <template.npy> --match-out <matches.tsv>]... [--match-threshold <v>]... [--match-separation <seconds>] [--match-anchor <frame>] [--match-ragged] [--train <labels.tsv> --train-out <net.txt>] [--train-steps <n>] [--train-rate <lr>] [--train-width <seconds>] [--train-seed <s>] [--train-fit-map] [--train-output <k>] [--train-log <log.tsv>] [--probe]\n"
                  "  -n, --net <net>:\n      Path to trained network file.  Given k > 1 times: each file must have exactly k tracks, and track t runs network t (one mixed bank; the networks must share the sampling rate, window length, window overlap, time range and number of outputs).\n"
                  "  -a, --audio <audio>:\n      Path to the audio file to process.\n"
                  "  -d, --debounce <seconds>:\n      Number of seconds to debounce triggers.\n"
@@ -60,8 +60,9 @@ void usage(FILE *to)
                  "      --match <template.npy>:\n      Also find the occurrences of one exemplar in every track's spectrogram columns: a NumPy file of a little-endian float32 or float64 array [frames][bins] in C order, the bins those of the network's band (a window --align-dir writes, or sum.npy / count.npy). A position's score is the cosine between the template and the columns from there on; a match is a score at or above the threshold that nothing within the separation exceeds (the earlier of two equal ones). One network only. Needs --match-out. A file [exemplars][frames][bins] holds several exemplars of one syllable: a position's score is the greatest of theirs. Given several times (16 at most, 64 exemplars in all, every file the same frames and bins), the i-th --match is syllable class i and writes to the i-th --match-out, all classes in one pass; classes do not suppress each other. (A repeated --match used to replace the one before it.)\n"
                  "      --match-out <matches.tsv>:\n      Where --match writes its matches (given as many times as --match, in its order): lines of file, track and sample, tab separated, as --score reads them (the file as -a names it, the sample of the template's anchor frame at the network's rate), in command-line order, then track, then sample. With or without --batch, the same bytes.\n"
                  "      --match-threshold <v>:\n      The least score of a match (default 0.77): once for all classes, or as many times as --match, in its order.\n"
-                 "      --match-separation <seconds>:\n      No two matches of a track are closer than this (default: the template's length; at most 4096 frames).\n"
-                 "      --match-anchor <frame>:\n      The template's frame whose sample a match names (default: its last).\n"
+                 "      --match-separation <seconds>:\n      No two matches of a track are closer than this (default: the template's length; at most 4096 frames): once for all classes, or as many times as --match, in its order.\n"
+                 "      --match-anchor <frame>:\n      The template's frame whose sample a match names (default: its last): once for all classes (a frame of the shortest template), or as many times as --match, in its order.\n"
+                 "      --match-ragged:\n      The --match files may differ in their frame counts (without it that is an error): the classes are matched in one pass all the same, lined up at their --match-anchor frames. Files that all share their frame count write what they write without it.\n"
                  "      --train <labels.tsv>:\n      Under --batch, also train the (one) network on the batch's recordings: lines of file, track and sample as --score reads and --match-out writes them, the labelled samples of one output. An evaluation within --train-width of a label is a positive, every other a negative; the two classes weigh a half each. Adam on the mean squared error, full batch, on the GPU. The detections printed are those of the network as given. All audio files must go through one batch: otherwise nothing is trained or written. Where the network cannot be written the exit status is 1 at least. Needs --train-out.\n"
                  "      --train-out <net.txt>:\n      Where --train writes the trained network, in the text format -n reads.\n"
                  "      --train-steps <n>:\n      Steps of the optimiser (default 200).\n"
@@ -161,12 +162,14 @@ struct AlignOpt {
 // --match: template matching (syldet_matcher_bank_*): the occurrences of exemplars [frames][bins] in the columns of every track of every
 // file, written as the labels --score reads; the i-th --match (a file [exemplars][frames][bins]: several exemplars) is class i and
 // writes the i-th --match-out.  The scores do not depend on where a track lies in a bank, so the file is the same
-// bytes with and without --batch.
+// bytes with and without --batch.  With --match-ragged, files of different frame counts make a ragged bank (syldet_matcher_bank_create_ragged): a class's
+// templates share the file's length, the classes are lined up at their anchors.
 struct MatchOpt {
     std::vector<std::string> paths, out_paths;             // a class each, in command-line order
     std::vector<double> thresholds;                        // none: 0.77; one: every class's; else a class each
-    double separation = -1.0;                              // in seconds; < 0: the template's length
-    long anchor = -1;                                       // < 0: the template's last frame
+    std::vector<double> separations;                       // in seconds; none: each class's own length; one: every class's; else a class each
+    std::vector<long> anchors;                             // none: each class's last frame; one: every class's; else a class each
+    bool ragged = false;                                   // --match-ragged: the files may differ in their frame counts
 };
 
 // --train: training (syldet_trainer_*, syldet_train_fit_device): the network of -n trained on the recordings of the one batch against
@@ -320,9 +323,10 @@ int parse_options(int argc, char **argv, Options &o)
         else if (a == "--align-after") { if (!integer(value(), 0, SYLDET_ALIGN_MAX_WINDOW, o.align.after)) return fail("--align-before and --align-after take a number of units, 0 or more."); }
         else if (a == "--match") o.match.paths.push_back(value());
         else if (a == "--match-out") o.match.out_paths.push_back(value());
+        else if (a == "--match-ragged") o.match.ragged = true;
         else if (a == "--match-threshold") { double v = 0.0; if (!real(value(), v, [](double x) { return !std::isnan(x); })) return fail("--match-threshold takes a number."); o.match.thresholds.push_back(v); }
-        else if (a == "--match-separation") { if (!real(value(), o.match.separation, finite_zero_or_more)) return fail("--match-separation takes a number of seconds, 0 or more."); }
-        else if (a == "--match-anchor") { if (!integer(value(), 0, SYLDET_MATCH_MAX_TEMPLATE - 1, o.match.anchor)) return fail("--match-anchor takes a frame of the template, 0 or more."); }
+        else if (a == "--match-separation") { double v = 0.0; if (!real(value(), v, finite_zero_or_more)) return fail("--match-separation takes a number of seconds, 0 or more."); o.match.separations.push_back(v); }
+        else if (a == "--match-anchor") { long v = 0; if (!integer(value(), 0, SYLDET_MATCH_MAX_TEMPLATE - 1, v)) return fail("--match-anchor takes a frame of the template, 0 or more."); o.match.anchors.push_back(v); }
         else if (a == "--train") o.train.labels_path = value();
         else if (a == "--train-out") o.train.out_path = value();
         else if (a == "--train-log") o.train.log_path = value();
@@ -396,6 +400,7 @@ int check_options(const Options &o)
     if (o.any_of({"--align", "--align-at", "--align-before", "--align-after"}) && !o.has("--align-dir"))
         return fail("--align, --align-at, --align-before and --align-after need --align-dir <dir>.");
     if (o.align.at_labels && !o.has("--score")) return fail("--align-at labels needs --score <labels.tsv>.");
+    if (o.has("--match-ragged") && !o.has("--match")) return fail("--match-ragged needs --match <template.npy>.");
     if (o.any_of({"--match-out", "--match-threshold", "--match-separation", "--match-anchor"}) && !o.has("--match"))
         return fail("--match-out, --match-threshold, --match-separation and --match-anchor need --match <template.npy>.");
     if (o.has("--match") && o.match.out_paths.empty()) return fail("--match <template.npy> needs --match-out <matches.tsv>.");
@@ -404,6 +409,10 @@ int check_options(const Options &o)
     if (o.match.paths.size() > SYLDET_MATCH_MAX_CLASSES) return fail("--match may be given " + std::to_string(SYLDET_MATCH_MAX_CLASSES) + " times at most.");
     if (o.match.thresholds.size() > 1 && o.match.thresholds.size() != o.match.paths.size())
         return fail("--match-threshold is given once for all classes, or as many times as --match.");
+    if (o.match.separations.size() > 1 && o.match.separations.size() != o.match.paths.size())
+        return fail("--match-separation is given once for all classes, or as many times as --match.");
+    if (o.match.anchors.size() > 1 && o.match.anchors.size() != o.match.paths.size())
+        return fail("--match-anchor is given once for all classes, or as many times as --match.");
     if (o.any_of({"--train-out", "--train-steps", "--train-rate", "--train-width", "--train-seed", "--train-fit-map", "--train-output", "--train-log"}) && !o.has("--train"))
         return fail("--train-out, --train-steps, --train-rate, --train-width, --train-seed, --train-fit-map, --train-output and --train-log need --train <labels.tsv>.");
     // the trainer's detectors are the recordings of a batch

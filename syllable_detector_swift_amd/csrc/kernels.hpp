@@ -655,6 +655,27 @@ hipError_t launch_match_bank_scores(const MatchBankDesc &b, const float *columns
 hipError_t launch_match_bank_peaks(const MatchBankDesc &b, const float *scores, const int32_t *which, int64_t n_frames, const float *thresholds,
                                    int separation, int64_t *events, int64_t capacity, int64_t *counts, float *event_scores, int32_t *event_template,
                                    hipStream_t stream);
+// ... with a separation a class, passed by value beside the keys (match_bank_peaks_each_kernel); LDS by the greatest of them
+struct MatchBankSeps {
+    int32_t S[16];
+};
+hipError_t launch_match_bank_peaks_each(const MatchBankDesc &b, const float *scores, const int32_t *which, int64_t n_frames, const float *thresholds,
+                                        const int32_t *separations, int64_t *events, int64_t capacity, int64_t *counts, float *event_scores,
+                                        int32_t *event_template, hipStream_t stream);
+// A ragged bank ("template matching: a ragged bank" of include/syldet.h; match_ragged.hpp): template k is [len[k]][bins] at
+// d.templ + offset[k], its window at plane element u the frames [u - anchor[k], u - anchor[k] + len[k]).  d.n: the greatest
+// length; d.Fp, d.FT, d.matrix, d.lds_bytes: match_ragged_plan's.  The planes are indexed by the anchor frame.
+struct MatchRaggedDesc {
+    MatchDesc d;
+    const int32_t *order, *order_class;      // [K] as MatchBankDesc's
+    const int32_t *len, *anchor, *offset;    // [K] by template (on the device)
+    int K, C;
+    int a_max, G;                            // the staged frames of a tile begin a_max in front of its first element; their number
+};
+// scores and which [C][rows][n_frames] <- columns; every element written once; one launch (match_ragged_scores_mfma_kernel or
+// match_ragged_scores_plain_kernel)
+hipError_t launch_match_ragged_scores(const MatchRaggedDesc &b, const float *columns, int64_t n_frames, int64_t row_stride, float *scores,
+                                      int32_t *which, hipStream_t stream);
 
 // detection flags <-> bits (bit b of byte t of a row = flag 8 t + b), rows padded to whole bytes
 hipError_t launch_pack_flags(const uint8_t *flags, int64_t rows, int64_t row_len, uint8_t *bits, hipStream_t stream);

@@ -27,12 +27,18 @@
 //                  then runs the single kernel's products through the same device functions, so template k's score has the single
 //                  matcher's bits, and a class's score is the greatest of its templates' (match_classes.hpp); the peaks kernel is
 //                  match_peaks_kernel's body a class, grid (D, C).
+//   match_ragged_scores_mfma_kernel, match_ragged_scores_plain_kernel, match_bank_peaks_each_kernel   templates of their own lengths
+//                  n_k lined up at their anchors a_k ("template matching: a ragged bank"; match_ragged.hpp): a plane is indexed by
+//                  the anchor frame, a tile stages max a_k frames in front of its 256 elements and max (n_k - a_k) behind them, and
+//                  template k's pass is the bank's with n_k and its first frame a_max - a_k as arguments; a window exists where it
+//                  lies inside the detector on both sides.  The third is the bank's peaks kernel with a separation a class.
 //
 // gfx950 only: wave = 64 lanes.
 
 #include "kernels.hpp"
 #include "match_classes.hpp"
 #include "match_peaks.hpp"
+#include "match_ragged.hpp"
 
 namespace sd {
 
@@ -41,18 +47,40 @@ namespace {
 constexpr int kThreads = 256;
 constexpr int kOwn = kMatchChunk / kThreads;                 // positions a thread of the peaks kernel marks
 
+static_assert(kMatchTile == kMatchTileElements, "match_ragged.hpp plans the score kernels' tile");
+
 typedef float f4 __attribute__((ext_vector_type(4)));
 
 __device__ __forceinline__ bool finite_bits(float v) { return (__float_as_uint(v) & 0x7f800000u) != 0x7f800000u; }
+
+// A packed plan: the frames [first, end) of the detector of row `row` that starts last at or before frame q; false where the row
+// has none.  Whether it still holds q, or a window from q on, is the caller's to ask of `end`.
+__device__ __forceinline__ bool match_span(const MatchDesc &d, int row, int64_t q, int64_t &first, int64_t &end)
+{
+    const int at = span_at_or_before(d.by_row, d.row_begin, row, q);
+    if (at < 0) return false;
+    const DetSpan e = d.by_row[at];
+    first = e.first;
+    end = e.first + e.units;
+    return true;
+}
 
 // Does position q of row `row` hold a score: does a detector's window of n frames begin there?
 __device__ __forceinline__ bool match_position(const MatchDesc &d, int row, int64_t q, int64_t n_frames)
 {
     if (!d.by_row) return q + d.n <= n_frames;
-    const int at = span_at_or_before(d.by_row, d.row_begin, row, q);
-    if (at < 0) return false;
-    const DetSpan e = d.by_row[at];
-    return q + d.n <= e.first + e.units;
+    int64_t first, end;
+    if (!match_span(d, row, q, first, end)) return false;
+    return q + d.n <= end;
+}
+
+// The frames [first, end) of the detector that holds frame q (a channel: the row); false where none does
+__device__ __forceinline__ bool match_holder(const MatchDesc &d, int row, int64_t q, int64_t n_frames, int64_t &first, int64_t &end)
+{
+    first = 0;
+    end = n_frames;
+    if (!d.by_row) return true;
+    return match_span(d, row, q, first, end) && q < end;
 }
 
 // dot: the window's products with t^ (NaN and Inf taken as zero); E: its energy (which keeps them)
@@ -73,22 +101,27 @@ struct MatchTile {
     int G;                                                   // staged frames
 };
 
-__device__ __forceinline__ MatchTile match_tile(float *lds, const MatchDesc &d)
+// G staged frames and a template region of n frames (a ragged bank's: its greatest)
+__device__ __forceinline__ MatchTile match_tile_of(float *lds, const MatchDesc &d, int G, int n)
 {
     MatchTile t;
-    t.G = kMatchTile - 1 + d.n;
+    t.G = G;
     t.X = lds;
     t.T = t.X + t.G * d.Fp + 4 * ((t.G + 15) >> 4);
-    t.Efr = t.T + d.n * d.FT;
+    t.Efr = t.T + n * d.FT;
     t.red = t.Efr + t.G;
     return t;
 }
+
+__device__ __forceinline__ MatchTile match_tile(float *lds, const MatchDesc &d) { return match_tile_of(lds, d, kMatchTile - 1 + d.n, d.n); }
 
 // (eight loads a thread in flight: one at a time, the tile's staging waits out a memory latency an element and takes longer
 // than its matrix instructions)
 constexpr int kStage = 8;
 
-// the frames from p0 on of one row -> X, bins padded to Fp and frames behind the row's end zero by selection
+// the frames from p0 on of one row -> X, bins padded to Fp and frames behind the row's end zero by selection (kFront: p0 may lie
+// in front of the row's start, and those frames are zero likewise)
+template <bool kFront>
 __device__ __forceinline__ void match_stage_frames(const MatchDesc &d, const MatchTile &t, const float *__restrict__ src, int64_t p0, int64_t n_frames,
                                                    int tid)
 {
@@ -103,7 +136,7 @@ __device__ __forceinline__ void match_stage_frames(const MatchDesc &d, const Mat
             const int64_t gf = p0 + g;
             at[u] = idx < G * Fp ? idx + 4 * (g >> 4) : -1;
             v[u] = 0.0f;
-            if (idx < G * Fp && b < bins && gf < n_frames) v[u] = src[gf * bins + b];
+            if (idx < G * Fp && b < bins && gf < n_frames && (!kFront || gf >= 0)) v[u] = src[gf * bins + b];
         }
 #pragma unroll
         for (int u = 0; u < kStage; u++)
@@ -112,9 +145,9 @@ __device__ __forceinline__ void match_stage_frames(const MatchDesc &d, const Mat
 }
 
 // one template t^ [n][bins] -> T
-__device__ __forceinline__ void match_stage_template(const MatchDesc &d, float *T, const float *__restrict__ templ, int tid)
+__device__ __forceinline__ void match_stage_template(const MatchDesc &d, float *T, const float *__restrict__ templ, int n, int tid)
 {
-    const int n = d.n, bins = d.bins, FT = d.FT;
+    const int bins = d.bins, FT = d.FT;
     for (int base = tid; base < n * FT; base += kThreads * kStage) {
         float v[kStage];
 #pragma unroll
@@ -145,10 +178,13 @@ __device__ __forceinline__ void match_energies(const MatchDesc &d, const MatchTi
     }
 }
 
-// the products of the staged frames with the staged template: wave w's chains over the bin groups w, w + 4, .. -> red[w]
-__device__ __forceinline__ void match_products(const MatchDesc &d, const MatchTile &t, int tid)
+// the products of the staged frames with the staged template of n frames: wave w's chains over the bin groups w, w + 4, .. ->
+// red[w].  s: the staged frame at which the tile's first window begins (0; a ragged bank: match_ragged_first), so row m of the A
+// operand is the frames from 16 m + s on.  The skew 4 (g >> 4) follows the frame g = 16 m + s + f, and (g >> 4) = m + ((s + f) >> 4):
+// the lanes of an A read (m, k) are 16 Fp m + 4 m + k floats apart -- 64 banks, Fp being a multiple of 4 -- for any s.
+__device__ __forceinline__ void match_products(const MatchDesc &d, const MatchTile &t, int n, int s, int tid)
 {
-    const int n = d.n, Fp = d.Fp, FT = d.FT;
+    const int Fp = d.Fp, FT = d.FT;
     const float *X = t.X, *T = t.T;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63;
     const int groups = Fp >> 2;
@@ -156,12 +192,12 @@ __device__ __forceinline__ void match_products(const MatchDesc &d, const MatchTi
         const int m = lane & 15, k = lane >> 4;              // A: row m, k; B: k, column m
         const float *xa = X + (16 * m) * Fp + 4 * m + k;
         f4 acc = {0.0f, 0.0f, 0.0f, 0.0f};
-        // the operands of step (f, bg): frame 16 m + f of the tile, and the template's frame f - m that column m meets there
+        // the operands of step (f, bg): frame 16 m + s + f of the tile, and the template's frame f - m that column m meets there
         // (in: column m's window holds frame f; the zero above and below the template is selected where the operand is used)
         auto operands = [&](int f, int bg, float &a, float &b, bool &in) {
             const int j = f - m;
             in = (unsigned)j < (unsigned)n;
-            a = xa[f * Fp + 4 * (f >> 4) + 4 * bg];
+            a = xa[(f + s) * Fp + 4 * ((f + s) >> 4) + 4 * bg];
             b = T[(in ? j : 0) * FT + k + 4 * bg];
         };
         // every step's operands are read one step ahead of its matrix instruction
@@ -198,10 +234,11 @@ __device__ __forceinline__ float match_dot(const MatchDesc &d, const MatchTile &
     return dot;
 }
 
-__device__ __forceinline__ float match_energy(const MatchDesc &d, const MatchTile &t, int tid)
+// (n frames from the staged frame s + tid on)
+__device__ __forceinline__ float match_energy(const MatchTile &t, int n, int s, int tid)
 {
     float E = 0.0f;
-    for (int j = 0; j < d.n; j++) E = E + t.Efr[tid + j];
+    for (int j = 0; j < n; j++) E = E + t.Efr[tid + s + j];
     return E;
 }
 
@@ -212,18 +249,18 @@ match_scores_mfma_kernel(MatchDesc d, const float *__restrict__ columns, int64_t
     const int tid = (int)threadIdx.x, row = (int)blockIdx.y;
     const int64_t p0 = (int64_t)blockIdx.x * kMatchTile;
     const MatchTile t = match_tile(match_lds, d);
-    match_stage_frames(d, t, columns + (int64_t)row * row_stride, p0, n_frames, tid);
-    match_stage_template(d, t.T, d.templ, tid);
+    match_stage_frames<false>(d, t, columns + (int64_t)row * row_stride, p0, n_frames, tid);
+    match_stage_template(d, t.T, d.templ, d.n, tid);
     __syncthreads();
     match_energies(d, t, tid);
     __syncthreads();
-    match_products(d, t, tid);
+    match_products(d, t, d.n, 0, tid);
     __syncthreads();
 
     const int64_t q = p0 + tid;
     if (q >= n_frames) return;
     float s = __uint_as_float(0x7fc00000u);
-    if (match_position(d, row, q, n_frames)) s = match_score(match_dot(d, t, tid), match_energy(d, t, tid));
+    if (match_position(d, row, q, n_frames)) s = match_score(match_dot(d, t, tid), match_energy(t, d.n, 0, tid));
     scores[(int64_t)row * n_frames + q] = s;
 }
 
@@ -241,15 +278,15 @@ match_bank_scores_mfma_kernel(MatchBankDesc b, const float *__restrict__ columns
     const int64_t p0 = (int64_t)blockIdx.x * kMatchTile;
     const int64_t one = (int64_t)d.n * d.bins;
     const MatchTile t = match_tile(match_lds, d);
-    match_stage_frames(d, t, columns + (int64_t)row * row_stride, p0, n_frames, tid);
-    match_stage_template(d, t.T, d.templ + b.order[0] * one, tid);
+    match_stage_frames<false>(d, t, columns + (int64_t)row * row_stride, p0, n_frames, tid);
+    match_stage_template(d, t.T, d.templ + b.order[0] * one, d.n, tid);
     __syncthreads();
     match_energies(d, t, tid);
     __syncthreads();
 
     const int64_t q = p0 + tid;
     const bool live = q < n_frames, pos = live && match_position(d, row, q, n_frames);
-    const float E = pos ? match_energy(d, t, tid) : 0.0f;    // one sum for the K scores
+    const float E = pos ? match_energy(t, d.n, 0, tid) : 0.0f;    // one sum for the K scores
     const int64_t plane = (int64_t)d.rows * n_frames, at = (int64_t)row * n_frames + q;
     float running;
     int32_t w;
@@ -257,10 +294,57 @@ match_bank_scores_mfma_kernel(MatchBankDesc b, const float *__restrict__ columns
     for (int i = 0; i < b.K; i++) {
         const int k = b.order[i], c = b.order_class[i];
         const bool more = i + 1 < b.K;
-        match_products(d, t, tid);
+        match_products(d, t, d.n, 0, tid);
         __syncthreads();
-        if (more) match_stage_template(d, t.T, d.templ + b.order[i + 1] * one, tid);
+        if (more) match_stage_template(d, t.T, d.templ + b.order[i + 1] * one, d.n, tid);
         if (pos) match_class_take(match_score(match_dot(d, t, tid), E), k, running, w);
+        if (!more || b.order_class[i + 1] != c) {            // the class's last template
+            if (live) {
+                scores[c * plane + at] = running;
+                if (which) which[c * plane + at] = w;
+            }
+            match_class_begin(running, w);
+        }
+        if (more) __syncthreads();                           // (the template and the waves' sums are the next pass's)
+    }
+}
+
+// The ragged bank: the bank's kernel with a length n_k and an anchor a_k a template (match_ragged.hpp).  Thread tid holds plane
+// element u = p0 + tid, the ANCHOR frame; the staged frames begin a_max in front of p0, so template k's window at u, the frames
+// [u - a_k, ..), begins at the staged frame tid + s_k, s_k = a_max - a_k.  A pass is the bank's pass with (n_k, s_k); a window's
+// energy is summed a template, from the window's first frame on, since the windows differ.  A window exists where it lies inside
+// the detector that holds u on both sides: frames in front of the detector only ever meet zeros of the Toeplitz operand.
+__global__ void __launch_bounds__(kThreads)
+match_ragged_scores_mfma_kernel(MatchRaggedDesc b, const float *__restrict__ columns, int64_t n_frames, int64_t row_stride, float *__restrict__ scores,
+                                int32_t *__restrict__ which)
+{
+    extern __shared__ float match_lds[];
+    const MatchDesc &d = b.d;
+    const int tid = (int)threadIdx.x, row = (int)blockIdx.y;
+    const int64_t p0 = (int64_t)blockIdx.x * kMatchTile;
+    const MatchTile t = match_tile_of(match_lds, d, b.G, d.n);
+    match_stage_frames<true>(d, t, columns + (int64_t)row * row_stride, p0 - b.a_max, n_frames, tid);
+    match_stage_template(d, t.T, d.templ + b.offset[b.order[0]], b.len[b.order[0]], tid);
+    __syncthreads();
+    match_energies(d, t, tid);
+    __syncthreads();
+
+    const int64_t q = p0 + tid;
+    const bool live = q < n_frames;
+    int64_t first = 0, end = 0;
+    const bool held = live && match_holder(d, row, q, n_frames, first, end);
+    const int64_t plane = (int64_t)d.rows * n_frames, at = (int64_t)row * n_frames + q;
+    float running;
+    int32_t w;
+    match_class_begin(running, w);
+    for (int i = 0; i < b.K; i++) {
+        const int k = b.order[i], c = b.order_class[i];
+        const int n = b.len[k], a = b.anchor[k], s = b.a_max - a;
+        const bool more = i + 1 < b.K;
+        match_products(d, t, n, s, tid);
+        __syncthreads();
+        if (more) match_stage_template(d, t.T, d.templ + b.offset[b.order[i + 1]], b.len[b.order[i + 1]], tid);
+        if (held && match_ragged_window(first, end, q, a, n)) match_class_take(match_score(match_dot(d, t, tid), match_energy(t, n, s, tid)), k, running, w);
         if (!more || b.order_class[i + 1] != c) {            // the class's last template
             if (live) {
                 scores[c * plane + at] = running;
@@ -325,6 +409,38 @@ match_bank_scores_plain_kernel(MatchBankDesc b, const float *__restrict__ column
             float dot;
             if (i == 0) match_plain_chains<true>(x, d.templ + k * one, d.n, d.bins, dot, E);
             else match_plain_chains<false>(x, d.templ + k * one, d.n, d.bins, dot, E);
+            match_class_take(match_score(dot, E), k, running, w);
+        }
+        if (i + 1 == b.K || b.order_class[i + 1] != c) {
+            scores[c * plane + at] = running;
+            if (which) which[c * plane + at] = w;
+            match_class_begin(running, w);
+        }
+    }
+}
+
+// the ragged bank: a thread a plane element, the chains of template k's window from its first frame u - a_k on, E a template
+__global__ void __launch_bounds__(kThreads)
+match_ragged_scores_plain_kernel(MatchRaggedDesc b, const float *__restrict__ columns, int64_t n_frames, int64_t row_stride, float *__restrict__ scores,
+                                 int32_t *__restrict__ which)
+{
+    const MatchDesc &d = b.d;
+    const int row = (int)blockIdx.y;
+    const int64_t q = (int64_t)blockIdx.x * kMatchTile + (int)threadIdx.x;
+    if (q >= n_frames) return;
+    int64_t first = 0, end = 0;
+    const bool held = match_holder(d, row, q, n_frames, first, end);
+    const float *__restrict__ x = columns + (int64_t)row * row_stride;
+    const int64_t plane = (int64_t)d.rows * n_frames, at = (int64_t)row * n_frames + q;
+    float running;
+    int32_t w;
+    match_class_begin(running, w);
+    for (int i = 0; i < b.K; i++) {
+        const int k = b.order[i], c = b.order_class[i];
+        const int n = b.len[k], a = b.anchor[k];
+        if (held && match_ragged_window(first, end, q, a, n)) {
+            float dot, E;
+            match_plain_chains<true>(x + (q - a) * d.bins, d.templ + b.offset[k], n, d.bins, dot, E);
             match_class_take(match_score(dot, E), k, running, w);
         }
         if (i + 1 == b.K || b.order_class[i + 1] != c) {
@@ -438,15 +554,36 @@ match_bank_peaks_kernel(MatchBankDesc b, MatchBankKeys keys, const float *__rest
                      event_template ? event_template + c * table : nullptr, match_keys, wave_sum);
 }
 
+// ... with class c's own separation beside its key (a short syllable repeats faster than a long one)
+__global__ void __launch_bounds__(kThreads)
+match_bank_peaks_each_kernel(MatchBankDesc b, MatchBankKeys keys, MatchBankSeps seps, const float *__restrict__ scores, const int32_t *__restrict__ which,
+                             int64_t n_frames, int64_t *__restrict__ events, int64_t capacity, int64_t *__restrict__ counts,
+                             float *__restrict__ event_scores, int32_t *__restrict__ event_template)
+{
+    extern __shared__ uint32_t match_keys[];
+    __shared__ int wave_sum[kThreads / 64];
+    const int c = (int)blockIdx.y;
+    uint32_t key = 0u;
+    int S = 0;
+#pragma unroll
+    for (int e = 0; e < kMatchMaxClasses; e++)
+        if (e == c) {
+            key = keys.key[e];
+            S = seps.S[e];
+        }
+    const int64_t plane = (int64_t)b.d.rows * n_frames, table = (int64_t)b.d.D * capacity;
+    match_peaks_body(b.d, scores + c * plane, which ? which + c * plane : nullptr, n_frames, key, S, events + c * table, capacity,
+                     counts + (int64_t)c * b.d.D, event_scores ? event_scores + c * table : nullptr,
+                     event_template ? event_template + c * table : nullptr, match_keys, wave_sum);
+}
+
 }  // namespace
 
 void match_plan(MatchDesc &d)
 {
-    d.Fp = (d.bins + 3) / 4 * 4;
-    d.FT = ((d.Fp / 4) & 1) ? d.Fp : d.Fp + 4;
     const int64_t G = kMatchTile - 1 + d.n;
-    const int64_t floats = G * d.Fp + 4 * ((G + 15) / 16) + (int64_t)d.n * d.FT + G + 4 * kMatchTile;
-    d.matrix = floats * 4 <= 64 * 1024;
+    const int64_t floats = match_tile_floats(G, d.n, d.bins, &d.Fp, &d.FT);
+    d.matrix = floats * 4 <= kMatchLdsBytes;
     d.lds_bytes = d.matrix ? (int)(floats * 4) : 0;
 }
 
@@ -479,8 +616,9 @@ hipError_t launch_match_peaks(const MatchDesc &d, const float *scores, int64_t n
 
 hipError_t match_bank_prepare()
 {
-    return hipFuncSetAttribute((const void *)match_bank_peaks_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                               2 * (kMatchChunk + 2 * kMatchMaxSeparation) * (int)sizeof(uint32_t));
+    const int lds = 2 * (kMatchChunk + 2 * kMatchMaxSeparation) * (int)sizeof(uint32_t);
+    if (hipError_t e = hipFuncSetAttribute((const void *)match_bank_peaks_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, lds)) return e;
+    return hipFuncSetAttribute((const void *)match_bank_peaks_each_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
 }
 
 hipError_t launch_match_bank_scores(const MatchBankDesc &b, const float *columns, int64_t n_frames, int64_t row_stride, float *scores, int32_t *which,
@@ -506,6 +644,38 @@ hipError_t launch_match_bank_peaks(const MatchBankDesc &b, const float *scores, 
     const size_t lds = 2 * (size_t)(kMatchChunk + 2 * separation) * sizeof(uint32_t);
     hipLaunchKernelGGL(match_bank_peaks_kernel, dim3((unsigned)b.d.D, (unsigned)b.C), dim3(kThreads), lds, stream, b, keys, scores, which, n_frames,
                        separation, events, capacity, counts, event_scores, event_template);
+    return hipGetLastError();
+}
+
+hipError_t launch_match_bank_peaks_each(const MatchBankDesc &b, const float *scores, const int32_t *which, int64_t n_frames, const float *thresholds,
+                                        const int32_t *separations, int64_t *events, int64_t capacity, int64_t *counts, float *event_scores,
+                                        int32_t *event_template, hipStream_t stream)
+{
+    if (b.d.D <= 0) return hipSuccess;
+    MatchBankKeys keys{};
+    MatchBankSeps seps{};
+    int most = 0;
+    for (int c = 0; c < b.C; c++) {
+        keys.key[c] = match_key(thresholds[c]);
+        seps.S[c] = separations[c];
+        most = separations[c] > most ? separations[c] : most;
+    }
+    const size_t lds = 2 * (size_t)(kMatchChunk + 2 * most) * sizeof(uint32_t);
+    hipLaunchKernelGGL(match_bank_peaks_each_kernel, dim3((unsigned)b.d.D, (unsigned)b.C), dim3(kThreads), lds, stream, b, keys, seps, scores, which,
+                       n_frames, events, capacity, counts, event_scores, event_template);
+    return hipGetLastError();
+}
+
+hipError_t launch_match_ragged_scores(const MatchRaggedDesc &b, const float *columns, int64_t n_frames, int64_t row_stride, float *scores,
+                                      int32_t *which, hipStream_t stream)
+{
+    if (n_frames <= 0 || b.d.rows <= 0) return hipSuccess;
+    const dim3 grid((unsigned)((n_frames + kMatchTile - 1) / kMatchTile), (unsigned)b.d.rows);
+    if (b.d.matrix)
+        hipLaunchKernelGGL(match_ragged_scores_mfma_kernel, grid, dim3(kThreads), (size_t)b.d.lds_bytes, stream, b, columns, n_frames, row_stride, scores,
+                           which);
+    else
+        hipLaunchKernelGGL(match_ragged_scores_plain_kernel, grid, dim3(kThreads), 0, stream, b, columns, n_frames, row_stride, scores, which);
     return hipGetLastError();
 }
 

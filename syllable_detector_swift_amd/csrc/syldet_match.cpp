@@ -2,12 +2,14 @@
 // normalised template and a packed plan's detectors on the device, so that syldet_match_scores_device and
 // syldet_match_peaks_device are launches only; and the host functions (match_peaks.hpp: the rule the kernel runs).
 // A bank of templates (syldet_matcher_bank_*, "template matching: a bank of templates") is the same matcher with K templates and a
-// class table on the device; match_classes.hpp holds the rule of a class's score.
+// class table on the device; match_classes.hpp holds the rule of a class's score.  A ragged bank ("template matching: a ragged
+// bank") is a bank whose templates have their own lengths and anchors: the same handle type, match_ragged.hpp its plan.
 
 #include <limits>
 
 #include "match_classes.hpp"
 #include "match_peaks.hpp"
+#include "match_ragged.hpp"
 #include "syldet_handle.hpp"
 
 static_assert(SYLDET_MATCH_MAX_TEMPLATE == sd::kMatchMaxTemplate && SYLDET_MATCH_MAX_SEPARATION == sd::kMatchMaxSeparation &&
@@ -30,7 +32,10 @@ struct syldet_matcher : MatcherCore {};
 
 struct syldet_matcher_bank : MatcherCore {
     std::vector<int32_t> tclass;             // [K]
-    sd::MatchBankDesc b{};
+    std::vector<int32_t> tn, ta;             // [K] every template's frames and anchor (a uniform bank: K times the same)
+    sd::MatchBankDesc b{};                   // a ragged bank: the peaks kernels' (planes indexed by the anchor: n 1, anchor 0)
+    bool ragged = false;
+    sd::MatchRaggedDesc rg{};
 };
 
 namespace {
@@ -69,8 +74,9 @@ int peaks_args(float threshold, int32_t separation, int64_t capacity)
 
 // Everything of a matcher behind its arguments' own rules: the bank's checks, t^ of each of the K templates, the packed plan, the
 // kernels' plan, and t^ | tables | by_det | by_row | row_begin on the device (*d_tables: where `tables` lies there).
+// lens: NULL (K templates of n frames), or a ragged bank's lengths, n the greatest and *plan its tile.
 int core_create(MatcherCore *m, const syldet_t *h, const syldet_recordings_t *r, const float *templates, int K, int32_t n, int32_t bins, int32_t anchor,
-                const std::vector<int32_t> &tables, const int32_t **d_tables)
+                const std::vector<int32_t> &tables, const int32_t **d_tables, const int32_t *lens = nullptr, const sd::MatchRaggedPlan *plan = nullptr)
 {
     if (h->classes.size() > 1) return fail(SYLDET_ERR_UNSUPPORTED, "columns of a mixed bank: its classes' columns are ragged");
     sd::BankInfo b{};
@@ -82,11 +88,15 @@ int core_create(MatcherCore *m, const syldet_t *h, const syldet_recordings_t *r,
 
     std::vector<sd::DetSpan> by_row;
     std::vector<int32_t> row_begin;
-    const size_t one = (size_t)n * bins;
     try {
-        m->templ.assign((size_t)K * one, 0.0f);
-        for (int k = 0; k < K; k++)
-            if (int st = normalise(templates + (size_t)k * one, n, bins, m->templ.data() + (size_t)k * one)) return st;
+        size_t all = 0;
+        for (int k = 0; k < K; k++) all += (size_t)(lens ? lens[k] : n) * bins;
+        m->templ.assign(all, 0.0f);
+        for (size_t k = 0, at = 0; k < (size_t)K; k++) {
+            const int nk = lens ? lens[k] : n;
+            if (int st = normalise(templates + at, nk, bins, m->templ.data() + at)) return st;
+            at += (size_t)nk * bins;
+        }
         if (int st = m->read(h, r, sd::kSpanFrames)) return st;
         if (r) sd::spans_by_row(m->spans, b.channels, &by_row, &row_begin);
     } catch (const std::bad_alloc &) {
@@ -102,6 +112,10 @@ int core_create(MatcherCore *m, const syldet_t *h, const syldet_recordings_t *r,
     d.origin = (int64_t)b.geom.gap + b.window_length;       // syldet_align_anchor(COLUMNS)
     d.hop = b.geom.hop;
     sd::match_plan(d);
+    if (plan) {
+        d.matrix = plan->matrix;
+        d.lds_bytes = plan->lds_bytes;
+    }
     // (measurement only, tools/match_timing.py: the plain form on a shape the matrix form takes)
     if (const char *e = std::getenv("SYLDET_MATCH_PLAIN"))
         if (e[0] == '1') d.matrix = 0;
@@ -137,6 +151,60 @@ int scores_args(const MatcherCore *m, int64_t n_frames, int64_t &row_stride)
     if (row_stride < n_frames * m->desc.bins)
         return fail(SYLDET_ERR_INVALID_ARGUMENT, "row_stride " + std::to_string(row_stride) + " is below the " + std::to_string(n_frames * m->desc.bins) +
                                                      " elements of a row");
+    return SYLDET_OK;
+}
+
+// K and C of a bank (n_classes: K where there is no table)
+int bank_count_args(int32_t n_templates, const int32_t *template_class, int32_t &n_classes)
+{
+    if (n_templates < 1 || n_templates > SYLDET_MATCH_MAX_TEMPLATES)
+        return fail(SYLDET_ERR_INVALID_ARGUMENT, std::to_string(n_templates) + " templates are outside [1, " + std::to_string(SYLDET_MATCH_MAX_TEMPLATES) + "]");
+    if (!template_class) {
+        if (n_classes != 0 && n_classes != n_templates)
+            return fail(SYLDET_ERR_INVALID_ARGUMENT, "without a class table there are as many classes as templates (or 0 for that number)");
+        n_classes = n_templates;
+    }
+    if (n_classes < 1 || n_classes > SYLDET_MATCH_MAX_CLASSES)
+        return fail(SYLDET_ERR_INVALID_ARGUMENT, std::to_string(n_classes) + " classes are outside [1, " + std::to_string(SYLDET_MATCH_MAX_CLASSES) + "]");
+    return SYLDET_OK;
+}
+
+// the handle with its class table, and the tables that go to the device: order [K], the templates class by class, ascending k within
+// a class; then the class of each
+int bank_begin(std::unique_ptr<syldet_matcher_bank> &m, int K, const int32_t *template_class, int32_t n_classes, std::vector<int32_t> &tables)
+{
+    try {
+        m.reset(new syldet_matcher_bank());
+        m->tclass.resize((size_t)K);
+        std::vector<int> members((size_t)n_classes, 0);
+        for (int k = 0; k < K; k++) {
+            const int32_t c = template_class ? template_class[k] : k;
+            if (c < 0 || c >= n_classes)
+                return fail(SYLDET_ERR_INVALID_ARGUMENT, "template " + std::to_string(k) + "'s class " + std::to_string(c) + " is outside [0, " +
+                                                             std::to_string(n_classes) + ")");
+            m->tclass[(size_t)k] = c;
+            members[(size_t)c]++;
+        }
+        for (int c = 0; c < n_classes; c++)
+            if (!members[(size_t)c]) return fail(SYLDET_ERR_INVALID_ARGUMENT, "class " + std::to_string(c) + " has no template");
+        for (int c = 0; c < n_classes; c++)
+            for (int k = 0; k < K; k++)
+                if (m->tclass[(size_t)k] == c) tables.push_back(k);
+        for (int i = 0; i < K; i++) tables.push_back(m->tclass[(size_t)tables[(size_t)i]]);
+    } catch (const std::bad_alloc &) {
+        return fail(SYLDET_ERR_OUT_OF_MEMORY, "out of memory");
+    }
+    return SYLDET_OK;
+}
+
+// what the bank's two peaks calls ask behind their thresholds and separations
+int bank_peaks_args(const syldet_matcher_bank *m, const float *d_scores, const int32_t *d_which, int64_t n_frames, const int64_t *d_events, int64_t capacity,
+                    const int64_t *d_counts, const int32_t *d_event_template)
+{
+    if (d_event_template && !d_which) return fail(SYLDET_ERR_INVALID_ARGUMENT, "d_event_template needs d_which");
+    if (n_frames < 0) return fail(SYLDET_ERR_INVALID_ARGUMENT, "n_frames is negative");
+    if (int st = m->row_units_arg(n_frames, "n_frames", "frames")) return st;
+    if (m->D > 0 && (!d_counts || (n_frames > 0 && !d_scores) || (capacity > 0 && !d_events))) return fail(SYLDET_ERR_INVALID_ARGUMENT, "NULL argument");
     return SYLDET_OK;
 }
 
@@ -224,38 +292,15 @@ int syldet_matcher_bank_create(const syldet_t *h, const syldet_recordings_t *r, 
     if (!out) return fail(SYLDET_ERR_INVALID_ARGUMENT, "NULL argument");
     *out = nullptr;
     if (!h) return fail(SYLDET_ERR_INVALID_ARGUMENT, "NULL handle");
-    if (n_templates < 1 || n_templates > SYLDET_MATCH_MAX_TEMPLATES)
-        return fail(SYLDET_ERR_INVALID_ARGUMENT, std::to_string(n_templates) + " templates are outside [1, " + std::to_string(SYLDET_MATCH_MAX_TEMPLATES) + "]");
+    if (int st = bank_count_args(n_templates, template_class, n_classes)) return st;
     if (int st = template_args(templates, n, bins)) return st;
     const int K = n_templates;
-    if (!template_class) {
-        if (n_classes != 0 && n_classes != K)
-            return fail(SYLDET_ERR_INVALID_ARGUMENT, "without a class table there are as many classes as templates (or 0 for that number)");
-        n_classes = K;
-    }
-    if (n_classes < 1 || n_classes > SYLDET_MATCH_MAX_CLASSES)
-        return fail(SYLDET_ERR_INVALID_ARGUMENT, std::to_string(n_classes) + " classes are outside [1, " + std::to_string(SYLDET_MATCH_MAX_CLASSES) + "]");
     std::unique_ptr<syldet_matcher_bank> m;
     std::vector<int32_t> tables;
+    if (int st = bank_begin(m, K, template_class, n_classes, tables)) return st;
     try {
-        m.reset(new syldet_matcher_bank());
-        m->tclass.resize((size_t)K);
-        std::vector<int> members((size_t)n_classes, 0);
-        for (int k = 0; k < K; k++) {
-            const int32_t c = template_class ? template_class[k] : k;
-            if (c < 0 || c >= n_classes)
-                return fail(SYLDET_ERR_INVALID_ARGUMENT, "template " + std::to_string(k) + "'s class " + std::to_string(c) + " is outside [0, " +
-                                                             std::to_string(n_classes) + ")");
-            m->tclass[(size_t)k] = c;
-            members[(size_t)c]++;
-        }
-        for (int c = 0; c < n_classes; c++)
-            if (!members[(size_t)c]) return fail(SYLDET_ERR_INVALID_ARGUMENT, "class " + std::to_string(c) + " has no template");
-        // order [K]: the templates class by class, ascending k within a class; then the class of each
-        for (int c = 0; c < n_classes; c++)
-            for (int k = 0; k < K; k++)
-                if (m->tclass[(size_t)k] == c) tables.push_back(k);
-        for (int i = 0; i < K; i++) tables.push_back(m->tclass[(size_t)tables[(size_t)i]]);
+        m->tn.assign((size_t)K, n);
+        m->ta.assign((size_t)K, anchor < 0 ? n - 1 : anchor);
     } catch (const std::bad_alloc &) {
         return fail(SYLDET_ERR_OUT_OF_MEMORY, "out of memory");
     }
@@ -308,6 +353,11 @@ int syldet_match_bank_scores_device(syldet_matcher_bank_t *m, const float *d_col
     hipStream_t stream = (hipStream_t)hip_stream;
     SYLDET_HIP(hipSetDevice(m->bank.device));
     m->h->prof_begin();
+    if (m->ragged) {
+        KernelTimer t(m->h, stream, m->desc.matrix ? "match_ragged_scores_mfma_kernel" : "match_ragged_scores_plain_kernel");
+        SYLDET_HIP(sd::launch_match_ragged_scores(m->rg, d_columns, n_frames, row_stride, d_scores, d_which, stream));
+        return SYLDET_OK;
+    }
     KernelTimer t(m->h, stream, m->desc.matrix ? "match_bank_scores_mfma_kernel" : "match_bank_scores_plain_kernel");
     SYLDET_HIP(sd::launch_match_bank_scores(m->b, d_columns, n_frames, row_stride, d_scores, d_which, stream));
     return SYLDET_OK;
@@ -321,10 +371,7 @@ int syldet_match_bank_peaks_device(syldet_matcher_bank_t *m, const float *d_scor
     if (!thresholds) return fail(SYLDET_ERR_INVALID_ARGUMENT, "NULL thresholds");
     for (int c = 0; c < m->b.C; c++)
         if (int st = peaks_args(thresholds[c], separation, capacity)) return st;
-    if (d_event_template && !d_which) return fail(SYLDET_ERR_INVALID_ARGUMENT, "d_event_template needs d_which");
-    if (n_frames < 0) return fail(SYLDET_ERR_INVALID_ARGUMENT, "n_frames is negative");
-    if (int st = m->row_units_arg(n_frames, "n_frames", "frames")) return st;
-    if (m->D > 0 && (!d_counts || (n_frames > 0 && !d_scores) || (capacity > 0 && !d_events))) return fail(SYLDET_ERR_INVALID_ARGUMENT, "NULL argument");
+    if (int st = bank_peaks_args(m, d_scores, d_which, n_frames, d_events, capacity, d_counts, d_event_template)) return st;
     if (m->D == 0) return SYLDET_OK;
     hipStream_t stream = (hipStream_t)hip_stream;
     SYLDET_HIP(hipSetDevice(m->bank.device));
@@ -335,18 +382,109 @@ int syldet_match_bank_peaks_device(syldet_matcher_bank_t *m, const float *d_scor
     return SYLDET_OK;
 }
 
+// ---- a ragged bank ----
+int syldet_matcher_bank_create_ragged(const syldet_t *h, const syldet_recordings_t *r, const float *templates, int32_t n_templates,
+                                      const int32_t *template_n, int32_t bins, const int32_t *template_anchor, const int32_t *template_class,
+                                      int32_t n_classes, syldet_matcher_bank_t **out)
+{
+    if (!out) return fail(SYLDET_ERR_INVALID_ARGUMENT, "NULL argument");
+    *out = nullptr;
+    if (!h) return fail(SYLDET_ERR_INVALID_ARGUMENT, "NULL handle");
+    if (int st = bank_count_args(n_templates, template_class, n_classes)) return st;
+    if (!template_n) return fail(SYLDET_ERR_INVALID_ARGUMENT, "NULL template_n");
+    const int K = n_templates;
+    int32_t n_max = 0;
+    for (int k = 0; k < K; k++) {
+        if (int st = template_args(templates, template_n[k], bins)) return st;
+        const int32_t a = template_anchor ? template_anchor[k] : template_n[k] - 1;
+        if (a < 0 || a >= template_n[k])
+            return fail(SYLDET_ERR_INVALID_ARGUMENT, "template " + std::to_string(k) + "'s anchor " + std::to_string(a) + " is outside [0, " +
+                                                         std::to_string(template_n[k]) + ")");
+        n_max = std::max(n_max, template_n[k]);
+    }
+    std::unique_ptr<syldet_matcher_bank> m;
+    std::vector<int32_t> tables;
+    if (int st = bank_begin(m, K, template_class, n_classes, tables)) return st;
+    sd::MatchRaggedPlan plan{};
+    try {
+        m->tn.assign(template_n, template_n + K);
+        m->ta.resize((size_t)K);
+        for (int k = 0; k < K; k++) m->ta[(size_t)k] = template_anchor ? template_anchor[k] : template_n[k] - 1;
+        plan = sd::match_ragged_plan(m->tn.data(), m->ta.data(), K, bins);
+        // the reads of a pass and of an energy sum lie in the staged frames [0, G)
+        for (int k = 0; k < K; k++)
+            if (sd::match_ragged_first(plan, m->ta[(size_t)k]) < 0 || sd::match_ragged_last(plan, m->tn[(size_t)k], m->ta[(size_t)k]) > plan.G - 1)
+                return fail(SYLDET_ERR_INVALID_ARGUMENT, "a ragged bank's tile does not hold template " + std::to_string(k) + "'s windows");
+        // ... behind order and order_class: every template's frames, anchor and first element in the concatenated t^
+        tables.insert(tables.end(), m->tn.begin(), m->tn.end());
+        tables.insert(tables.end(), m->ta.begin(), m->ta.end());
+        int32_t at = 0;
+        for (int k = 0; k < K; k++) {
+            tables.push_back(at);
+            at += m->tn[(size_t)k] * bins;
+        }
+    } catch (const std::bad_alloc &) {
+        return fail(SYLDET_ERR_OUT_OF_MEMORY, "out of memory");
+    }
+    const int32_t *d_tables = nullptr;
+    if (int st = core_create(m.get(), h, r, templates, K, n_max, bins, 0, tables, &d_tables, m->tn.data(), &plan)) return st;
+    m->ragged = true;
+    sd::MatchRaggedDesc &g = m->rg;
+    g.d = m->desc;
+    g.order = d_tables;
+    g.order_class = d_tables + K;
+    g.len = d_tables + 2 * K;
+    g.anchor = d_tables + 3 * K;
+    g.offset = d_tables + 4 * K;
+    g.K = K;
+    g.C = n_classes;
+    g.a_max = plan.a_max;
+    g.G = plan.G;
+    // the peaks kernels' view: every element of a detector is a position of its own, and the plane's index is the anchor frame
+    m->b.d = m->desc;
+    m->b.d.n = 1;
+    m->b.d.anchor = 0;
+    m->b.order = g.order;
+    m->b.order_class = g.order_class;
+    m->b.K = K;
+    m->b.C = n_classes;
+    *out = m.release();
+    return SYLDET_OK;
+}
+
+int syldet_matcher_bank_lengths(const syldet_matcher_bank_t *m, int32_t *template_n, int32_t *template_anchor, int32_t *ragged)
+{
+    if (!m) return fail(SYLDET_ERR_INVALID_ARGUMENT, "NULL argument");
+    if (template_n) std::memcpy(template_n, m->tn.data(), m->tn.size() * sizeof(int32_t));
+    if (template_anchor) std::memcpy(template_anchor, m->ta.data(), m->ta.size() * sizeof(int32_t));
+    if (ragged) *ragged = m->ragged ? 1 : 0;
+    return SYLDET_OK;
+}
+
+int syldet_match_bank_peaks_each_device(syldet_matcher_bank_t *m, const float *d_scores, const int32_t *d_which, int64_t n_frames, const float *thresholds,
+                                        const int32_t *separations, int64_t *d_events, int64_t capacity, int64_t *d_counts, float *d_event_scores,
+                                        int32_t *d_event_template, void *hip_stream)
+{
+    if (!m) return fail(SYLDET_ERR_INVALID_ARGUMENT, "NULL handle");
+    if (!thresholds) return fail(SYLDET_ERR_INVALID_ARGUMENT, "NULL thresholds");
+    if (!separations) return fail(SYLDET_ERR_INVALID_ARGUMENT, "NULL separations");
+    for (int c = 0; c < m->b.C; c++)
+        if (int st = peaks_args(thresholds[c], separations[c], capacity)) return st;
+    if (int st = bank_peaks_args(m, d_scores, d_which, n_frames, d_events, capacity, d_counts, d_event_template)) return st;
+    if (m->D == 0) return SYLDET_OK;
+    hipStream_t stream = (hipStream_t)hip_stream;
+    SYLDET_HIP(hipSetDevice(m->bank.device));
+    m->h->prof_begin();
+    KernelTimer t(m->h, stream, "match_bank_peaks_each_kernel");
+    SYLDET_HIP(sd::launch_match_bank_peaks_each(m->b, d_scores, d_which, n_frames, thresholds, separations, d_events, capacity, d_counts, d_event_scores,
+                                                capacity > 0 ? d_event_template : nullptr, stream));
+    return SYLDET_OK;
+}
+
 int syldet_match_classes_host(const float *template_scores, int64_t n_positions, int32_t n_templates, const int32_t *template_class, int32_t n_classes,
                               float *class_scores, int32_t *which)
 {
-    if (n_templates < 1 || n_templates > SYLDET_MATCH_MAX_TEMPLATES)
-        return fail(SYLDET_ERR_INVALID_ARGUMENT, std::to_string(n_templates) + " templates are outside [1, " + std::to_string(SYLDET_MATCH_MAX_TEMPLATES) + "]");
-    if (!template_class) {
-        if (n_classes != 0 && n_classes != n_templates)
-            return fail(SYLDET_ERR_INVALID_ARGUMENT, "without a class table there are as many classes as templates (or 0 for that number)");
-        n_classes = n_templates;
-    }
-    if (n_classes < 1 || n_classes > SYLDET_MATCH_MAX_CLASSES)
-        return fail(SYLDET_ERR_INVALID_ARGUMENT, std::to_string(n_classes) + " classes are outside [1, " + std::to_string(SYLDET_MATCH_MAX_CLASSES) + "]");
+    if (int st = bank_count_args(n_templates, template_class, n_classes)) return st;
     if (n_positions < 0 || (n_positions > 0 && (!template_scores || !class_scores))) return fail(SYLDET_ERR_INVALID_ARGUMENT, "a NULL array or a negative count");
     uint32_t members = 0;
     for (int k = 0; k < n_templates; k++) {

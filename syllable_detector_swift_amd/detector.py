@@ -964,10 +964,12 @@ class SyllableDetector:
         (default: its last, n - 1)."""
         return Matcher(self, template, anchor)
 
-    def matcherBank(self, templates, classes=None, anchor: Optional[int] = None) -> "MatcherBank":
+    def matcherBank(self, templates, classes=None, anchor=None, ragged: Optional[bool] = None) -> "MatcherBank":
         """A MatcherBank over this bank's channels (syldet_matcher_bank_create): `templates` [K, n, bins] in classes (`classes`
-        [K], None: template k is class k) matched in one pass; a class's score is the greatest of its templates' scores."""
-        return MatcherBank(self, templates, classes, anchor)
+        [K], None: template k is class k) matched in one pass; a class's score is the greatest of its templates' scores.  A list
+        of arrays [n_k, bins] of differing lengths makes a ragged bank (syldet_matcher_bank_create_ragged), whose planes are indexed
+        by the anchor frame; anchor: None (each template's last frame), one frame for all, or one per template."""
+        return MatcherBank(self, templates, classes, anchor, ragged=ragged)
 
     # ---- batch, host arrays -------------------------------------------------------
     def runHost(self, samples: np.ndarray, outputs: Optional[np.ndarray] = None, flags: Optional[np.ndarray] = None) -> Tuple[np.ndarray, np.ndarray]:
@@ -1509,9 +1511,9 @@ class Recordings:
         The columns are spectrogram(rows)."""
         return Matcher(self.detector, template, anchor, recordings=self)
 
-    def matcherBank(self, templates, classes=None, anchor: Optional[int] = None) -> "MatcherBank":
-        """A MatcherBank whose detectors are these recordings (SyllableDetector.matcherBank, Recordings.matcher)."""
-        return MatcherBank(self.detector, templates, classes, anchor, recordings=self)
+    def matcherBank(self, templates, classes=None, anchor=None, ragged: Optional[bool] = None) -> "MatcherBank":
+        """A MatcherBank whose detectors are these recordings (SyllableDetector.matcherBank, Recordings.matcher); ragged as there."""
+        return MatcherBank(self.detector, templates, classes, anchor, recordings=self, ragged=ragged)
 
 
 def _score_args(thresholds, labels):
@@ -1929,33 +1931,79 @@ class MatcherBank:
     greatest of its templates', `which` the lowest template that attains it (-1 where the score is NaN).  classes: the class of
     each template (None: template k is class k).  shape = (detectors, templates, classes, frames, bins, anchor); templates: the
     normalised templates; classes: the class table; form: "matrix" or "plain".  The detector (and the Recordings) must outlive
-    it."""
+    it.
+    A RAGGED bank ("template matching: a ragged bank"): `templates` a list of arrays [n_k, bins] of differing lengths (or any list
+    of 2-D arrays with ragged=True), lined up at their anchors -- None: each template's last frame; one int for all; or one per
+    template.  Its planes are indexed by the ANCHOR frame: element u holds the scores of the windows whose anchor is frame u, and an
+    event is the sample of frame u.  ragged: is it one; lengths, anchors: every template's frames and anchor frame (a uniform
+    bank: K times the same); templates is then a list, frames the greatest length and anchor 0."""
 
-    def __init__(self, detector: SyllableDetector, templates, classes=None, anchor: Optional[int] = None, recordings: Optional[Recordings] = None):
+    def __init__(self, detector: SyllableDetector, templates, classes=None, anchor=None, recordings: Optional[Recordings] = None,
+                 ragged: Optional[bool] = None):
         self.detector = detector
         self.recordings = recordings
-        t = np.asarray(templates)
-        if t.ndim != 3 or t.dtype.kind != "f":
-            raise ValueError("the templates must be a float array [templates, frames, bins]")
-        t = np.ascontiguousarray(t, dtype=np.float32)
+        rec = None if recordings is None else recordings._h
+        parts = None
+        if isinstance(templates, (list, tuple)) and len(templates) and all(np.ndim(t) == 2 for t in templates):
+            parts = [np.asarray(t) for t in templates]
+            per_template = anchor is not None and np.ndim(anchor) > 0
+            if ragged is None:
+                ragged = len({p.shape[0] for p in parts}) > 1 or per_template
+        if ragged and parts is None:
+            raise ValueError("a ragged bank takes a list of arrays [frames, bins]")
+        K = len(parts) if ragged else None
+        if ragged:
+            if any(p.dtype.kind != "f" for p in parts) or len({p.shape[1] for p in parts}) != 1:
+                raise ValueError("the templates must be float arrays [frames, bins] of the same bins")
+            t = np.ascontiguousarray(np.concatenate([np.ascontiguousarray(p, dtype=np.float32).reshape(-1) for p in parts]))
+            lens = np.array([p.shape[0] for p in parts], np.int32)
+            anc = None
+            if anchor is not None:
+                anc = np.ascontiguousarray(anchor, dtype=np.int32).reshape(-1)
+                if anc.size == 1:
+                    anc = np.full(K, anc[0], np.int32)                    # one frame: every template's
+                if anc.size != K:
+                    raise ValueError("one anchor, or one per template")
+        else:
+            t = np.asarray(templates)
+            if t.ndim != 3 or t.dtype.kind != "f":
+                raise ValueError("the templates must be a float array [templates, frames, bins]")
+            t = np.ascontiguousarray(t, dtype=np.float32)
+            K = t.shape[0]
+            if anchor is not None and np.ndim(anchor) > 0:
+                raise ValueError("a bank of one length has one anchor")
         cls, n_classes = None, 0
         if classes is not None:
             cls = np.ascontiguousarray(classes, dtype=np.int32).reshape(-1)
-            if cls.size != t.shape[0]:
+            if cls.size != K:
                 raise ValueError("one class per template")
             n_classes = int(cls.max()) + 1 if cls.size else 0
         self._h = _abi.Handle()
-        check(_abi.lib.syldet_matcher_bank_create(detector._h, None if recordings is None else recordings._h, t.ctypes.data_as(_abi.c_float_p),
-                                                  t.shape[0], t.shape[1], t.shape[2], -1 if anchor is None else int(anchor),
-                                                  None if cls is None else cls.ctypes.data_as(_abi.c_int32_p), n_classes, C.byref(self._h)))
+        if ragged:
+            check(_abi.lib.syldet_matcher_bank_create_ragged(detector._h, rec, t.ctypes.data_as(_abi.c_float_p), K, lens.ctypes.data_as(_abi.c_int32_p),
+                                                             parts[0].shape[1], None if anc is None else anc.ctypes.data_as(_abi.c_int32_p),
+                                                             None if cls is None else cls.ctypes.data_as(_abi.c_int32_p), n_classes, C.byref(self._h)))
+        else:
+            check(_abi.lib.syldet_matcher_bank_create(detector._h, rec, t.ctypes.data_as(_abi.c_float_p),
+                                                      t.shape[0], t.shape[1], t.shape[2], -1 if anchor is None else int(anchor),
+                                                      None if cls is None else cls.ctypes.data_as(_abi.c_int32_p), n_classes, C.byref(self._h)))
         d, k, c, n, b, a, mf = (C.c_int32() for _ in range(7))
         check(_abi.lib.syldet_matcher_bank_shape(self._h, C.byref(d), C.byref(k), C.byref(c), C.byref(n), C.byref(b), C.byref(a), C.byref(mf)))
         self.shape = (d.value, k.value, c.value, n.value, b.value, a.value)
         self.count, self.nTemplates, self.nClasses, self.frames, self.bins, self.anchor = self.shape
         self.form = "matrix" if mf.value else "plain"
-        self.templates = np.empty((k.value, n.value, b.value), np.float32)
+        self.lengths, self.anchors, rg = np.empty(k.value, np.int32), np.empty(k.value, np.int32), C.c_int32()
+        check(_abi.lib.syldet_matcher_bank_lengths(self._h, self.lengths.ctypes.data_as(_abi.c_int32_p), self.anchors.ctypes.data_as(_abi.c_int32_p),
+                                                   C.byref(rg)))
+        self.ragged = bool(rg.value)
+        flat = np.empty(int(self.lengths.sum()) * b.value, np.float32)
         self.classes = np.empty(k.value, np.int32)
-        check(_abi.lib.syldet_matcher_bank_templates(self._h, self.templates.ctypes.data_as(_abi.c_float_p), self.classes.ctypes.data_as(_abi.c_int32_p)))
+        check(_abi.lib.syldet_matcher_bank_templates(self._h, flat.ctypes.data_as(_abi.c_float_p), self.classes.ctypes.data_as(_abi.c_int32_p)))
+        if self.ragged:
+            ends = np.cumsum(self.lengths.astype(np.int64)) * b.value
+            self.templates = [flat[e - nk * b.value:e].reshape(nk, b.value) for e, nk in zip(ends, self.lengths)]
+        else:
+            self.templates = flat.reshape(k.value, n.value, b.value)
 
     def close(self):
         if getattr(self, "_h", None):
@@ -1981,6 +2029,15 @@ class MatcherBank:
         if t.size != self.nClasses:
             raise ValueError("one threshold, or one per class")
         return t
+
+    def _separations(self, separation):
+        """None where one separation serves every class (the shared call), else one int32 per class"""
+        if np.ndim(separation) == 0:
+            return None
+        s = np.ascontiguousarray(separation, dtype=np.int32).reshape(-1)
+        if s.size != self.nClasses:
+            raise ValueError("one separation, or one per class")
+        return s
 
     def scores(self, cols, which: bool = False, out=None, stream=None):
         """cols [channels, n_frames, bins] as Matcher.scores takes them -> the class scores [C, channels, n_frames] float32, or with
@@ -2010,11 +2067,12 @@ class MatcherBank:
                                                        out_w.data_ptr() if (which and J) else None, det._stream_ptr(stream)))
         return (out_s, out_w) if which else out_s
 
-    def peaks(self, scores, thresholds, separation: int, capacity: Optional[int] = None, which=None, withScores: bool = True, stream=None):
+    def peaks(self, scores, thresholds, separation, capacity: Optional[int] = None, which=None, withScores: bool = True, stream=None):
         """scores [C, channels, n_frames] as scores() made them -> (events [C, D, capacity] int64, counts [C, D] int64, eventScores
         [C, D, capacity] float32 or None, eventTemplates [C, D, capacity] int32 or None): every class's tables as Matcher.peaks makes
         them from that class's plane with that class's threshold (a scalar: the same for all); classes do not suppress each other.
-        which: scores()'s second tensor, for eventTemplates.  One launch."""
+        which: scores()'s second tensor, for eventTemplates.  separation: one int, or one per class
+        (syldet_match_bank_peaks_each_device).  One launch."""
         torch = _torch()
         det = self.detector
         Cn = self.nClasses
@@ -2025,6 +2083,7 @@ class MatcherBank:
                                       and which.device == scores.device):
             raise ValueError("which must be a contiguous int32 CUDA tensor of the scores' shape on their device")
         thr = self._thresholds(thresholds)
+        seps = self._separations(separation)
         cap = 1024 if capacity is None else int(capacity)
         D = self.count
         events = torch.empty((Cn, D, max(cap, 0)), dtype=torch.int64, device=scores.device)
@@ -2032,15 +2091,17 @@ class MatcherBank:
         ev_scores = torch.empty((Cn, D, max(cap, 0)), dtype=torch.float32, device=scores.device) if withScores else None
         ev_templ = torch.empty((Cn, D, max(cap, 0)), dtype=torch.int32, device=scores.device) if which is not None else None
         J = int(scores.shape[2])
-        check(_abi.lib.syldet_match_bank_peaks_device(self._h, scores.data_ptr() if J else None, which.data_ptr() if (which is not None and J) else None,
-                                                      J, thr.ctypes.data_as(_abi.c_float_p), int(separation),
-                                                      events.data_ptr() if events.numel() else None, cap, counts.data_ptr() if D else None,
-                                                      ev_scores.data_ptr() if (withScores and ev_scores.numel()) else None,
-                                                      ev_templ.data_ptr() if (ev_templ is not None and ev_templ.numel() and J) else None,
-                                                      det._stream_ptr(stream)))
+        call, sep = ((_abi.lib.syldet_match_bank_peaks_device, int(separation)) if seps is None
+                     else (_abi.lib.syldet_match_bank_peaks_each_device, seps.ctypes.data_as(_abi.c_int32_p)))
+        check(call(self._h, scores.data_ptr() if J else None, which.data_ptr() if (which is not None and J) else None,
+                   J, thr.ctypes.data_as(_abi.c_float_p), sep,
+                   events.data_ptr() if events.numel() else None, cap, counts.data_ptr() if D else None,
+                   ev_scores.data_ptr() if (withScores and ev_scores.numel()) else None,
+                   ev_templ.data_ptr() if (ev_templ is not None and ev_templ.numel() and J) else None,
+                   det._stream_ptr(stream)))
         return events, counts, ev_scores, ev_templ
 
-    def find(self, cols, thresholds, separation: int, stream=None):
+    def find(self, cols, thresholds, separation, stream=None):
         """scores() and peaks() -> (events, eventScores, eventTemplates): three lists with, a class, a list with one array a
         detector (int64, float32, int32), every match of it (the tables are made again with the largest count as capacity where the
         first capacity was too small)."""

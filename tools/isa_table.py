@@ -29,7 +29,10 @@ def main():
     print("# kernel: vgpr sgpr lds scratch insts, parent -> this (a compile result of hipcc --offload-arch=gfx950, not a timing)")
     for f in files:
         tables = [kernels(os.path.join(lib, "obj", "isa", f + "-hip-amdgcn-amd-amdhsa-gfx950.s")) for lib in (parent, this)]
-        assert sorted(tables[0]) == sorted(tables[1]), (f, sorted(set(tables[0]) ^ set(tables[1])))
+        assert not set(tables[0]) - set(tables[1]), (f, sorted(set(tables[0]) - set(tables[1])))
+        for name in tables[1]:
+            if name not in tables[0]:                                     # a kernel this build adds
+                print("%s %s: %s   <- new" % (f, name, " ".join("%s %d" % (k, tables[1][name][k]) for k in ("vgpr", "sgpr", "lds", "scratch", "insts"))))
         for name in tables[0]:
             a, b = tables[0][name], tables[1][name]
             cols = " ".join("%s %d -> %d" % (k, a[k], b[k]) for k in ("vgpr", "sgpr", "lds", "scratch", "insts"))
